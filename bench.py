@@ -14,7 +14,12 @@ before it touches the GPU, runs `python -m torch.distributed.run --nnodes=1 --np
 as a child process, relays rank 0's JSON line and exits with the child's code.  Under torch.distributed.run (RANK set)
 it is one rank.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times exactly K steps and prints the result line (metric, value, unit, higher_is_better,
+dtype, ms_per_step = milliseconds per timed step, ...); nothing else runs on the GPU.  `--dump-outputs DIR` also writes what the
+last timed step returned -- the packed detections [clips x ranks, top_k, 40] (stmask_amd.dist layout) -- as DIR/detections.npy
+(float32); the inputs are seeded, so two builds given the same flags can be compared output for output.
+
+`--full` adds everything else the benchmark measures or checks, as extra objects on the same line:
   roofline        dominant kernel (conv_planar_kernel), timed live with HIP events on its launch stream inside the timed region
   roofline_im2col deformable sampler (the kernel north_star names), same method, HBM bound
   cpu_baseline    the CPU oracle path ("port": torch-CPU trunk + oracle C kernels) on this box's host cores, rank 0, N=1,
@@ -63,11 +68,17 @@ def parse_args(argv=None):
     ap.add_argument("--config", default="STMask_plus_resnet50_config")
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the side measurements and checks: the instrumented roofline passes, extras, the CPU "
+                         "baseline and its parity block, and (N > 1) the pass without the all-gather.  Off: a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the packed detections of every clip) as DIR/detections.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle leg (and the parity block that needs it)")
     ap.add_argument("--no-extras", action="store_true", help="skip the 8-clip / 1-clip / bf16x3 side measurements")
     ap.add_argument("--events-in-timed-region", action="store_true",
                     help="record the per-launch HIP events of the roofline objects INSIDE the timed region (rounds 1-4 did; two event records around each of "
-                         "~190 launches cost ~1.1 ms per step at 32 clips, so by default they are taken in an eager pass of the same K steps right after it)")
+                         "~190 launches cost ~1.1 ms per step at 32 clips, so by default they are taken in an eager pass of the same K steps right after it; "
+                         "with --full)")
     ap.add_argument("--no-sampler-pass", action="store_true",
                     help="skip the short eager pass with the fused deformable convolution switched off that only serves roofline_im2col (kernel traces: one kind of step)")
     ap.add_argument("--extras", default=DEFAULT_EXTRAS, help="which side measurements to run (comma-separated)")
@@ -82,7 +93,7 @@ def parse_args(argv=None):
                     help="operand format of the planar MFMA convolutions: two fp16 planes / 3 products (default, fp32-equivalent), "
                          "three bf16 planes / 6 products (fp32-equivalent, no fp16 range limit), or fp16x1 = ONE fp16 plane / one "
                          "product (BASELINE config 5: genuine fp16 convolutions with fp32 accumulation, ~1e-3 relative)")
-    ap.add_argument("--layer-table", action="store_true", help="per-layer-shape timing table of the planar convolution on stderr")
+    ap.add_argument("--layer-table", action="store_true", help="per-layer-shape timing table of the planar convolution on stderr (with --full)")
     ap.add_argument("--no-planar", dest="planar", action="store_false",
                     help="dense convolutions through MIOpen instead of the planar matrix-core kernel")
     ap.add_argument("--graph", choices=("auto", "on", "off"), default="auto",
@@ -107,7 +118,19 @@ def parse_args(argv=None):
     ap.add_argument("--launch-check", action="store_true",
                     help="host-only check of the multi-rank plumbing (self-launch, rendezvous, clip sharding, all-gather, max-over-"
                          "ranks timing, JSON relay) with synthetic detection rows instead of the model; needs no GPU")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    for flag, on in (("--layer-table", args.layer_table), ("--events-in-timed-region", args.events_in_timed_region)):
+        if on and not args.full:
+            ap.error(f"{flag} serves the roofline objects of --full: give --full as well")
+    return args
+
+
+def dump_outputs(out_dir, out):
+    """What the timed path's caller receives from its last step: the packed detections [clips x ranks, top_k, 40], float32
+    (stmask_amd.dist layout: box, score, class, object id, valid flag, mask coefficients)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "detections.npy"), out.detach().to("cpu", torch.float32).numpy())
 
 
 def main():
@@ -166,25 +189,29 @@ def main():
     if args.world2_one_gpu:
         run.keep = []
     # The timed region carries no instrumentation: the per-launch HIP events the roofline objects are built from are recorded in a second pass of the same
-    # K steps right after it (eager; under a trunk graph that was always so).  --events-in-timed-region puts them back inside.
-    events_inside = args.events_in_timed_region and not graphed and not args.world2_one_gpu
+    # K steps right after it (eager; under a trunk graph that was always so).  --events-in-timed-region puts them back inside.  A plain run (no --full)
+    # has neither: it times the K steps and nothing else.
+    events_inside = args.full and args.events_in_timed_region and not graphed and not args.world2_one_gpu
     elapsed, out, timing, conv_t = run.timed(args.warmup, args.steps, use_dist, collect=events_inside)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     tracked_mean = round(run.tracked_sum / max(run.tracked_steps, 1), 1)      # of the timed region (the later passes reset the counters)
     if args.world2_one_gpu:
         sys.exit(checks.world2_report(args, run, dev, rank, world, elapsed, use_dist))
     coll_local = coll_delta = None
     if use_dist and run.batched:
         # the collective's report, taken HERE: the block this rank packed in the last timed step (before any further pass advances the pipeline), and
-        # the same K steps once more with the exchange switched off (the process group stays): what the all-gather costs a step
+        # (--full) the same K steps once more with the exchange switched off (the process group stays): what the all-gather costs a step
         run.gatherer.wait()
         coll_local = run.pipe._pack_outputs(dev).clone()
+    if args.full and use_dist and run.batched:
         saved_mode = run.gatherer.mode
         run.gatherer.mode = 2
         el_nog, _, _, _ = run.timed(args.warmup, args.steps, use_dist)         # the same step indices as the timed region: same frames, same tracker phase
         run.gatherer.mode = saved_mode
         coll_delta = (elapsed - el_nog) / args.steps * 1e3
     instrumented_s = None
-    if not events_inside:
+    if args.full and not events_inside:
         # the per-kernel HIP-event timing of the roofline objects: a second, eager pass of the same K steps right after the timed region (same kernels,
         # same shapes, same process; a graph replay cannot be bracketed kernel by kernel at all)
         if graphed:
@@ -205,7 +232,7 @@ def main():
     # EVERY rank runs the passes below: they contain barriers and the per-step all-gather (a pass on rank 0 alone would wait for ranks that have left)
     fused_t = getattr(run, "fused_t", None) or []
     im2col_in = None
-    if fused_t and not timing and not args.no_sampler_pass:
+    if args.full and fused_t and not timing and not args.no_sampler_pass:
         # the sampler the north star names did not run in that pass (every DCN layer took the fused kernel): its own figure from a short eager
         # pass of the same pipeline with fusion switched off (same process, right after; nothing of it enters the headline)
         from stmask_amd import planar as _plf
@@ -286,34 +313,35 @@ def main():
                                                                     if coll_local is not None else None)}
         default_wl = args.clips == DEFAULT_CLIPS and args.config == "STMask_plus_resnet50_config" and args.planes == "fp16x2"
         f_ms = f_fl = 0.0
-        if fused_t:
-            tr_f, src_f, why_f = rf.pmc_traffic("dcn_fused", len(fused_t) / args.steps) if default_wl else (None, None, "not the profiled workload")
-            res["roofline_dcn_fused"], f_ms, f_fl = rf.dcn_fused_roofline(fused_t, args.steps, tr_f, src_f, why_f)
-        n_samp_steps = min(args.steps, 8) if im2col_in else args.steps
-        tr_s, src_s, why_s = (rf.pmc_traffic("dcn_sample_planar", len(timing) / n_samp_steps) if (default_wl and planar_graph and timing)
-                              else (None, None, "not the profiled workload"))
-        im2col_roof = rf.im2col_roofline(timing, planar_graph, n_samp_steps, tr_s, src_s, why_s, im2col_in)
-        if conv_t:
-            tr_c, src_c, why_c = rf.pmc_traffic("conv_planar", len(conv_t) / args.steps) if default_wl else (None, None, "not the profiled workload")
-            res["roofline"] = rf.conv_roofline(conv_t, args.steps, args.planes, tr_c, src_c,
-                                               "the timed region" if events_inside else "an eager pass of the same K steps right after the timed region (which "
-                                               + ("replays HIP graphs" if graphed else "carries no per-launch events: they cost ~0.8 ms per step") + "), next-trunk overlap 'late' so that "
-                                               "no two convolution launches share the GPU", traffic_refused=why_c)
-            res["frac_trunk_only"] = res["roofline"]["frac_trunk_only"]
+        if args.full:
             if fused_t:
-                # `roofline` keeps its definition of the earlier rounds -- the plane-split dense-convolution kernels -- so the deformable layers' products,
-                # which those kernels ran until round 4 (0.25 TFLOP per step), left it together with their time; the same figure WITH the fused kernel's
-                # launches (whose time also holds the sampling the old sampler kernel did outside any roofline object):
-                ro = res["roofline"]
-                c_ms, c_fl = ro["ms_per_step"] * args.steps + f_ms, ro["tflop_per_step"] * args.steps * 1e12 + f_fl
-                ro["with_dcn_fused"] = {"achieved": round(c_fl / (c_ms * 1e-3) / 1e12, 1), "frac": round(c_fl / (c_ms * 1e-3) / 1e12 / ro["peak"], 4),
-                                        "ms_per_step": round(c_ms / args.steps, 3), "tflop_per_step": round(c_fl / args.steps / 1e12, 3)}
-            res["roofline_im2col"] = im2col_roof
-            if args.layer_table:
-                rf.print_layer_table(conv_t, args.steps)
-        else:
-            res["roofline"] = im2col_roof
-        if world == 1 and not args.no_extras and run.batched:
+                tr_f, src_f, why_f = rf.pmc_traffic("dcn_fused", len(fused_t) / args.steps) if default_wl else (None, None, "not the profiled workload")
+                res["roofline_dcn_fused"], f_ms, f_fl = rf.dcn_fused_roofline(fused_t, args.steps, tr_f, src_f, why_f)
+            n_samp_steps = min(args.steps, 8) if im2col_in else args.steps
+            tr_s, src_s, why_s = (rf.pmc_traffic("dcn_sample_planar", len(timing) / n_samp_steps) if (default_wl and planar_graph and timing)
+                                  else (None, None, "not the profiled workload"))
+            im2col_roof = rf.im2col_roofline(timing, planar_graph, n_samp_steps, tr_s, src_s, why_s, im2col_in)
+            if conv_t:
+                tr_c, src_c, why_c = rf.pmc_traffic("conv_planar", len(conv_t) / args.steps) if default_wl else (None, None, "not the profiled workload")
+                res["roofline"] = rf.conv_roofline(conv_t, args.steps, args.planes, tr_c, src_c,
+                                                   "the timed region" if events_inside else "an eager pass of the same K steps right after the timed region (which "
+                                                   + ("replays HIP graphs" if graphed else "carries no per-launch events: they cost ~0.8 ms per step") + "), next-trunk overlap 'late' so that "
+                                                   "no two convolution launches share the GPU", traffic_refused=why_c)
+                res["frac_trunk_only"] = res["roofline"]["frac_trunk_only"]
+                if fused_t:
+                    # `roofline` keeps its definition of the earlier rounds -- the plane-split dense-convolution kernels -- so the deformable layers' products,
+                    # which those kernels ran until round 4 (0.25 TFLOP per step), left it together with their time; the same figure WITH the fused kernel's
+                    # launches (whose time also holds the sampling the old sampler kernel did outside any roofline object):
+                    ro = res["roofline"]
+                    c_ms, c_fl = ro["ms_per_step"] * args.steps + f_ms, ro["tflop_per_step"] * args.steps * 1e12 + f_fl
+                    ro["with_dcn_fused"] = {"achieved": round(c_fl / (c_ms * 1e-3) / 1e12, 1), "frac": round(c_fl / (c_ms * 1e-3) / 1e12 / ro["peak"], 4),
+                                            "ms_per_step": round(c_ms / args.steps, 3), "tflop_per_step": round(c_fl / args.steps / 1e12, 3)}
+                res["roofline_im2col"] = im2col_roof
+                if args.layer_table:
+                    rf.print_layer_table(conv_t, args.steps)
+            else:
+                res["roofline"] = im2col_roof
+        if args.full and world == 1 and not args.no_extras and run.batched:
             # side measurements on the same process and box (short; the headline above is untouched by them)
             from stmask_amd import planar as _pl
             saved_fmt = (_pl.FMT, _pl.BACKBONE_FMT)
@@ -335,7 +363,7 @@ def main():
                 extras.update(bx.config_lines(args, dev, rank, world, [n for n in names if n.startswith("config")]))
                 _pl.set_format(*saved_fmt)
             res["extras"] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             base, ref_dets = checks.cpu_baseline(args)
             res["cpu_baseline"] = base
             try:

@@ -6,7 +6,7 @@ C=${1:-32}; R=${2:-3}; MT=${3:-200}
 for r in $(seq $R); do
   for f in 0 $MT; do
     if [ $f = 0 ]; then export STM_DCN_FUSED=0; else export STM_DCN_FUSED=1 STM_DCN_FUSED_MIN_TILES=$f; fi
-    python bench.py --clips $C --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+    python bench.py --full --clips $C --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

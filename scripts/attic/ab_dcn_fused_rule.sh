@@ -7,7 +7,7 @@ for cfg in STMask_plus_resnet50_config STMask_plus_base_ali_config; do
 for r in $(seq $R); do
   for f in off 0 1; do
     if [ $f = off ]; then export STM_DCN_FUSED=0; else export STM_DCN_FUSED=1 STM_DCN_FUSED_RULE=$f; fi
-    python bench.py --config $cfg --clips $C --steps 16 --warmup 4 --no-cpu-baseline --no-extras --no-sampler-pass 2>/dev/null | python -c "
+    python bench.py --full --config $cfg --clips $C --steps 16 --warmup 4 --no-cpu-baseline --no-extras --no-sampler-pass 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

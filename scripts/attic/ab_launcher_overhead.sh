@@ -19,9 +19,9 @@ for l in sys.stdin:
               ('all-gathers %s on comm stream %s, equal %s' % (c.get('all_gathers_on_comm_stream'), c.get('comm_stream'), c.get('last_gather_equals_local_block'))) if c else ''))"; }
 P=29530
 for r in $(seq $R); do
-  python bench.py $ARGS 2>/dev/null | show plain
-  OMP_NUM_THREADS=1 python bench.py $ARGS 2>/dev/null | show plain-omp1
-  P=$((P+1)); python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $P bench.py --gpus 1 $ARGS 2>/dev/null | show nccl
-  P=$((P+1)); OMP_NUM_THREADS=32 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $P bench.py --gpus 1 $ARGS 2>/dev/null | show nccl-omp32
-  P=$((P+1)); python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $P bench.py --gpus 1 --backend gloo $ARGS 2>/dev/null | show gloo
+  python bench.py --full $ARGS 2>/dev/null | show plain
+  OMP_NUM_THREADS=1 python bench.py --full $ARGS 2>/dev/null | show plain-omp1
+  P=$((P+1)); python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $P bench.py --full --gpus 1 $ARGS 2>/dev/null | show nccl
+  P=$((P+1)); OMP_NUM_THREADS=32 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $P bench.py --full --gpus 1 $ARGS 2>/dev/null | show nccl-omp32
+  P=$((P+1)); python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $P bench.py --full --gpus 1 --backend gloo $ARGS 2>/dev/null | show gloo
 done

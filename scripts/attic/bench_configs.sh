@@ -4,11 +4,11 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; TAG=${1:-r04}; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT; cd $R
 : > $OUT/bench_configs.jsonl
 for cfg in STMask_plus_resnet50_ada_config STMask_plus_base_ali_config; do for clips in 8 32; do
-  timeout 600 python bench.py --config $cfg --clips $clips --steps 16 --warmup 4 --no-cpu-baseline --no-extras >> $OUT/bench_configs.jsonl 2>> $OUT/bench_configs.err; echo "$cfg $clips exit $?"
+  timeout 600 python bench.py --full --config $cfg --clips $clips --steps 16 --warmup 4 --no-cpu-baseline --no-extras >> $OUT/bench_configs.jsonl 2>> $OUT/bench_configs.err; echo "$cfg $clips exit $?"
 done; done
-timeout 600 python bench.py --config STMask_plus_base_ali_config --height 736 --width 1280 --planes fp16x1 --clips 4 --steps 16 --warmup 4 --no-cpu-baseline --no-extras >> $OUT/bench_configs.jsonl 2>> $OUT/bench_configs.err; echo "config5 fp16x1 exit $?"
-timeout 600 python bench.py --config STMask_plus_base_ali_config --height 736 --width 1280 --clips 4 --steps 16 --warmup 4 --no-cpu-baseline --no-extras >> $OUT/bench_configs.jsonl 2>> $OUT/bench_configs.err; echo "config5 fp16x2 exit $?"
-timeout 600 python bench.py --max-instances 8 --clips 8 --steps 16 --warmup 4 --no-cpu-baseline --no-extras >> $OUT/bench_configs.jsonl 2>> $OUT/bench_configs.err; echo "realistic 8 clips exit $?"
+timeout 600 python bench.py --full --config STMask_plus_base_ali_config --height 736 --width 1280 --planes fp16x1 --clips 4 --steps 16 --warmup 4 --no-cpu-baseline --no-extras >> $OUT/bench_configs.jsonl 2>> $OUT/bench_configs.err; echo "config5 fp16x1 exit $?"
+timeout 600 python bench.py --full --config STMask_plus_base_ali_config --height 736 --width 1280 --clips 4 --steps 16 --warmup 4 --no-cpu-baseline --no-extras >> $OUT/bench_configs.jsonl 2>> $OUT/bench_configs.err; echo "config5 fp16x2 exit $?"
+timeout 600 python bench.py --full --max-instances 8 --clips 8 --steps 16 --warmup 4 --no-cpu-baseline --no-extras >> $OUT/bench_configs.jsonl 2>> $OUT/bench_configs.err; echo "realistic 8 clips exit $?"
 python - "$OUT/bench_configs.jsonl" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

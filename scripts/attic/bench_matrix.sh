@@ -1,7 +1,7 @@
 #!/bin/bash
 # The bench variants quoted in DESIGN.md section 6, one JSON line each (no CPU baseline).  Output: gpurun_out/bench_matrix.txt
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; OUT=$R/gpurun_out/bench_matrix.txt; : > $OUT
-run() { echo "== $*" >> $OUT; timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | cut -c1-2400 >> $OUT; }
+run() { echo "== $*" >> $OUT; timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | cut -c1-2400 >> $OUT; }
 run
 run --overlap early
 run --overlap off

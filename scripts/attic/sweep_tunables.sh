@@ -3,7 +3,7 @@
 # usage: CLIPS=8 scripts/sweep_tunables.sh
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 CLIPS=${CLIPS:-32}
-run() { echo "== $*"; env "$@" python bench.py --clips $CLIPS --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['ms_per_step'])"; }
+run() { echo "== $*"; env "$@" python bench.py --full --clips $CLIPS --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['ms_per_step'])"; }
 run A=0
 run STM_TILE64_MAX_SLABS=4
 run STM_TILE64_MAX_SLABS=16

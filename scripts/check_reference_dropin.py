@@ -10,8 +10,13 @@ stmask_amd/shims first on sys.path and verify that
   * the reference's call sites bind against the shim signatures: backbone.py:21-22 (DCN), Featurealign.py:27-31,72
     (DeformConv2d), track_to_segment_head.py:53-59 (spatial_correlation_sample), :86 (roi_align).
 
-Reads /root/reference: never shipped to or run on the GPU box.  No GPU needed (nothing is executed on tensors).
+Reads the reference checkout (STMASK_REFERENCE): never shipped to or run on the GPU box.  No GPU needed (nothing is executed on tensors).
+
+    --write-golden PATH   also store the reference nets' state-dict keys / shapes and DCN / DeformConv2d counts as JSON
+    --golden PATH         without the reference: the same mmcv and call-site checks, and stmask_amd.model.STMask's state
+                          dicts against that stored record (tests/golden/reference_state_dicts.json; tests/test_reference_dropin.py)
 """
+import argparse
 import collections
 import collections.abc
 import inspect
@@ -81,16 +86,46 @@ def stub_absent_third_party():
     torch.cuda.current_device = lambda: "cpu"       # STMask.py:15 calls it at import
 
 
-def main():
-    if not os.path.isdir(REF):
+def state_dict_record(net, n_dcn, n_fcb):
+    return {"keys": [[k, list(v.shape)] for k, v in net.state_dict().items()], "n_dcn": n_dcn, "n_fcb": n_fcb}
+
+
+def check_against_golden(path):
+    """The state dicts of stmask_amd.model.STMask for the four configs against the stored record of the reference's own STMask()."""
+    import json
+    from stmask_amd import dcn_v2 as amd_dcn, mmcv_ops as amd_mmcv
+    from stmask_amd.config import get_cfg
+    from stmask_amd.model import STMask as AmdSTMask
+    with open(path) as fh:
+        golden = json.load(fh)
+    assert sorted(golden) == sorted(CONFIGS), sorted(golden)
+    for name in CONFIGS:
+        ours = AmdSTMask(get_cfg(name))
+        n_dcn = sum(isinstance(m, amd_dcn.DCN) for m in ours.modules())
+        n_fcb = sum(isinstance(m, amd_mmcv.DeformConv2d) for m in ours.modules())
+        rec, g = state_dict_record(ours, n_dcn, n_fcb), golden[name]
+        assert [k for k, _ in rec["keys"]] == [k for k, _ in g["keys"]], (name, {k for k, _ in rec["keys"]} ^ {k for k, _ in g["keys"]})
+        assert rec["keys"] == g["keys"], name
+        assert (n_dcn, n_fcb) == (g["n_dcn"], g["n_fcb"]) and n_dcn in (7, 11), (name, n_dcn, n_fcb, g["n_dcn"], g["n_fcb"])
+        print(f"{name}: stored reference STMask() record, {len(rec['keys'])} state-dict entries identical, {n_dcn} DCN, {n_fcb} DeformConv2d")
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--write-golden", metavar="PATH")
+    ap.add_argument("--golden", metavar="PATH")
+    args = ap.parse_args(argv)
+    use_ref = args.golden is None
+    if use_ref and not os.path.isdir(REF):
         print("reference not present: nothing to check")
         return 0
     tmp = tempfile.mkdtemp(prefix="installed_mmcv_")
     make_installed_mmcv(tmp)
     for m in [k for k in sys.modules if k == "mmcv" or k.startswith("mmcv.") or k in ("dcn_v2", "spatial_correlation_sampler")]:
         del sys.modules[m]
-    sys.path[:0] = [os.path.join(ROOT, "stmask_amd", "shims"), ROOT, REF, tmp]   # shims first; tmp = "site-packages"
-    stub_absent_third_party()
+    sys.path[:0] = [os.path.join(ROOT, "stmask_amd", "shims"), ROOT] + ([REF] if use_ref else []) + [tmp]   # INTEGRATION.md: shims first; tmp = "site-packages"
+    if use_ref:
+        stub_absent_third_party()
 
     import mmcv
     import mmcv.ops
@@ -101,12 +136,16 @@ def main():
     assert DataContainer(1).data == 1 and mmcv.STMASK_AMD_OPS
     assert mmcv.ops.DeformConv2d is amd_mmcv.DeformConv2d and mmcv.ops.roi_align is amd_mmcv.roi_align
     print("mmcv: installed package intact, mmcv.ops served by stmask_amd")
+    import dcn_v2
+    import spatial_correlation_sampler
+    assert dcn_v2.DCN is amd_dcn.DCN and spatial_correlation_sampler.spatial_correlation_sample is amd_corr.spatial_correlation_sample
 
-    from datasets.config import cfg, set_cfg
-    import backbone as ref_backbone
-    from layers.modules import Featurealign as ref_fa, track_to_segment_head as ref_t2s
-    assert ref_backbone.DCN is amd_dcn.DCN and ref_fa.DeformConv2d is amd_mmcv.DeformConv2d
-    assert ref_t2s.roi_align is amd_mmcv.roi_align and ref_t2s.spatial_correlation_sample is amd_corr.spatial_correlation_sample
+    if use_ref:
+        from datasets.config import cfg, set_cfg
+        import backbone as ref_backbone
+        from layers.modules import Featurealign as ref_fa, track_to_segment_head as ref_t2s
+        assert ref_backbone.DCN is amd_dcn.DCN and ref_fa.DeformConv2d is amd_mmcv.DeformConv2d
+        assert ref_t2s.roi_align is amd_mmcv.roi_align and ref_t2s.spatial_correlation_sample is amd_corr.spatial_correlation_sample
 
     # call-site signatures (bind only: no tensors are touched)
     inspect.signature(amd_dcn.DCN.__init__).bind(None, 128, 128, kernel_size=3, stride=2, padding=1, dilation=1, deformable_groups=1)   # backbone.py:21-22
@@ -118,9 +157,13 @@ def main():
                                                                 dilation_patch=1)                                                   # :53-59
     print("call sites bind against the shim signatures")
 
+    if not use_ref:
+        check_against_golden(args.golden)
+        return 0
     import STMask as ref_stmask
     from stmask_amd.config import get_cfg
     from stmask_amd.model import STMask as AmdSTMask
+    record = {}
     for name in CONFIGS:
         set_cfg(name)
         ref_net = ref_stmask.STMask()
@@ -133,6 +176,12 @@ def main():
         assert n_dcn == sum(isinstance(m, amd_dcn.DCN) for m in ours.modules()) and n_dcn in (7, 11), (name, n_dcn)
         assert n_fcb == (3 if cfg.use_dcn_class else 0), (name, n_fcb)
         print(f"{name}: reference STMask() built on the shims, {len(rs)} state-dict entries identical, {n_dcn} DCN, {n_fcb} DeformConv2d")
+        record[name] = state_dict_record(ref_net, n_dcn, n_fcb)
+    if args.write_golden:
+        import json
+        with open(args.write_golden, "w") as fh:
+            json.dump(record, fh, separators=(",", ":"))
+            fh.write("\n")
     return 0
 
 

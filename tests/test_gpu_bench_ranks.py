@@ -1,5 +1,5 @@
 """The N-rank flow of bench.py END TO END on the GPU box: two ranks under torch.distributed.run, both on device 0 (--share-gpu, gloo exchange -- RCCL refuses two
-ranks on one device), through every pass of main(): timed region, no-gather pass, instrumented pass, the sampler pass, max-over-ranks timing, rank 0's result line,
+ranks on one device), through every pass of main() (--full): timed region, no-gather pass, instrumented pass, the sampler pass, max-over-ranks timing, rank 0's result line,
 the final barrier.  No 8-GPU node is available to the builder; this is what executes the rank-symmetric structure of the file for real (round 6 found a pass that
 only rank 0 ran, with barriers and all-gathers inside: it would have hung every N > 1 run on hardware)."""
 import json
@@ -20,7 +20,7 @@ def test_two_ranks_run_the_whole_bench_flow_and_print_one_line():
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--clips", "2", "--steps", "4", "--warmup", "2"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--clips", "2", "--steps", "4", "--warmup", "2", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

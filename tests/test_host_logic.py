@@ -88,17 +88,23 @@ def test_fused_deform_conv_grid_helper_follows_the_tile_shapes(monkeypatch):
 
 
 def test_bench_defaults_of_round_5():
-    """The driver runs `python bench.py` bare: the next trunk starts early, the timed region carries no per-launch events, the roofline passes exist."""
+    """The driver runs `python bench.py` bare: the next trunk starts early, the timed region carries no per-launch events; with --full the roofline
+    passes exist."""
     import bench
     a = bench.parse_args([])
     assert a.overlap == "early" and not a.events_in_timed_region and not a.no_sampler_pass and a.gpus == 1
-    assert bench.parse_args(["--events-in-timed-region", "--overlap", "late"]).events_in_timed_region
+    assert not a.full and a.dump_outputs is None
+    assert bench.parse_args(["--full"]).full
+    assert bench.parse_args(["--full", "--events-in-timed-region", "--overlap", "late"]).events_in_timed_region
+    for extra in (["--events-in-timed-region"], ["--layer-table"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(extra)                                             # they serve --full's roofline objects only
 
 
 def test_bench_defaults_of_round_6():
-    """The bare `python bench.py` also runs the sustained line and one short line per remaining BASELINE configuration."""
+    """`python bench.py --full` also runs the sustained line and one short line per remaining BASELINE configuration."""
     import bench
-    names = bench.parse_args([]).extras.split(",")
+    names = bench.parse_args(["--full"]).extras.split(",")
     assert {"sustained", "config3", "config4", "config5", "clips1", "clips8", "realistic"} <= set(names)
     from benchlib.extras import CONFIG_LINES
     assert [c[0] for c in CONFIG_LINES] == ["config3", "config4", "config5"]

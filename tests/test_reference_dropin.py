@@ -1,13 +1,12 @@
-"""The drop-in boundary: the import shims must not shadow an installed mmcv, and -- in the build
-container, where /root/reference exists -- the reference's own STMask.py must import and build on them with identical
-state-dict keys (scripts/check_reference_dropin.py).  CPU only; the GPU box has no reference and skips the second test."""
+"""The drop-in boundary: the import shims must not shadow an installed mmcv, the reference's call
+sites bind against them, and stmask_amd.model.STMask has the reference STMask()'s state-dict keys and shapes for the four
+benchmark configs -- checked against tests/golden/reference_state_dicts.json, the record scripts/check_reference_dropin.py
+--write-golden took of the reference's own nets built on the shims.  CPU only."""
 import os
 import subprocess
 import sys
 
-import pytest
-
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
 SHIMS = os.path.join(ROOT, "stmask_amd", "shims")
 
@@ -37,9 +36,8 @@ def test_shim_without_installed_mmcv_pretends_nothing():
     assert p.returncode == 0 and "ok True" in p.stdout, p.stderr[-1500:]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="build container only: needs the reference checkout")
-def test_reference_stmask_imports_and_builds_on_the_shims():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_reference_dropin.py")], capture_output=True, text=True,
-                       timeout=900)
+def test_shims_and_state_dicts_match_the_stored_reference_record():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "check_reference_dropin.py"),
+                        "--golden", os.path.join(GOLDEN, "reference_state_dicts.json")], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     assert p.stdout.count("state-dict entries identical") == 4 and "installed package intact" in p.stdout
