@@ -36,7 +36,9 @@
  *     stm_debug_launch_count;
  *      4: those three entry points are part of the version now (a library that lacks them must not pass for this ABI), plus the fused
  *     deformable convolution stm_deform_conv_fused_planar_f32 / stm_deform_conv_fused_planar_supported; stm_debug_launch_count(1); the batched per-class Fast NMS
- *     stm_fast_nms_batched_f32 / stm_fast_nms_batched_workspace_bytes; the host-side stm_rle_strings_host).
+ *     stm_fast_nms_batched_f32 / stm_fast_nms_batched_workspace_bytes; the host-side stm_rle_strings_host);
+ *      5: struct stm_frame_desc (stm_struct_bytes(4)) and stm_preprocess_u8_multi_f32, the pre-processing of a batch whose frames come from
+ *     different tensors of different source sizes).
  */
 #ifndef STMASK_HIP_H_
 #define STMASK_HIP_H_
@@ -48,7 +50,7 @@
 extern "C" {
 #endif
 
-#define STM_ABI_VERSION 4
+#define STM_ABI_VERSION 5
 
 enum stm_status {
     STM_OK = 0,
@@ -541,6 +543,18 @@ int stm_dcn_sample_planar_f16(const float* x, const float* offset_mask, int om_l
  * (cfg.backbone.transform.{normalize, subtract_means, to_float}).  Bit-exact against oracle orc_preprocess_u8. */
 int stm_preprocess_u8_f32(const uint8_t* img, float* out, int n, int H0, int W0, int h, int w, int Hp, int Wp,
                           const double* mean, const double* stdv, int mode, stm_stream_t stream);
+
+/* The same pre-processing for n frames that need not share a tensor or a source size (a serving batch whose slots hold frames of different
+ * videos): frames[i] describes image i -- uint8 HWC rows of W0 * 3 contiguous bytes, row_stride_bytes apart (>= 3 * W0: a crop view is fine).
+ * out [n, 3, Hp, Wp] as above.  The descriptors are read on the host and travel in the kernel arguments, 64 frames per launch (no host -> device
+ * copy; a launch can be captured in a graph).  Image i is bit-identical to stm_preprocess_u8_f32 of the same image.  ABI 5. */
+typedef struct stm_frame_desc {
+    const uint8_t* ptr;
+    int H0, W0;
+    int64_t row_stride_bytes;
+} stm_frame_desc;
+int stm_preprocess_u8_multi_f32(const stm_frame_desc* frames, int n, float* out, int h, int w, int Hp, int Wp, const double* mean,
+                                const double* stdv, int mode, stm_stream_t stream);
 
 /* ---- head output assembly (row a5 / f4) -----------------------------------------------------------------------------
  * Replaces the cat / view / tanh / F.normalize tail of PredictionModule_FC.forward (prediction_head_FC.py:168-195) for the

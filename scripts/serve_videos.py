@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""Continuous batching of a video queue (stmask_amd.serve.VideoBatcher) on the GPU: seeded synthetic uint8 videos of seeded lengths in two source
+sizes, served at each --slots count with graph-replayed trunks.  A measuring tool, not a test.
+
+Prints one JSON line: per slot count the frames/s (device-synchronised wall clock around the whole queue, after one warm-up queue), the slot
+occupancy (active slot-steps / all slot-steps) and the number of videos and frames.
+
+usage: python scripts/serve_videos.py [--videos 64] [--min-frames 8] [--max-frames 36] [--slots 8 32]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from stmask_amd import synthetic  # noqa: E402
+from stmask_amd.config import get_cfg  # noqa: E402
+from stmask_amd.fuse import optimize_for_inference  # noqa: E402
+from stmask_amd.model import STMask  # noqa: E402
+from stmask_amd.serve import VideoBatcher  # noqa: E402
+
+SIZES = [(720, 1280), (480, 854)]
+
+
+def make_queue(n, lo, hi, seed, dev):
+    """n videos: lengths uniform in [lo, hi], sizes alternating; every video a seeded noise base image translated per frame (on the device)."""
+    g = torch.Generator().manual_seed(seed)
+    lengths = torch.randint(lo, hi + 1, (n,), generator=g).tolist()
+    vids = []
+    for i, T in enumerate(lengths):
+        h, w = SIZES[i % 2]
+        base = torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).to(dev)
+        vids.append((i, torch.stack([torch.roll(base, shifts=(4 * t, 6 * t), dims=(0, 1)) for t in range(T)])))
+    return vids
+
+
+def build_net(config, dev):
+    net = STMask(get_cfg(config))
+    net.eval()
+    synthetic.fill_state_dict(net, seed=0, bg_bias=4.7)
+    net = net.to(dev)
+    optimize_for_inference(net, planar=True)
+    net = net.to(memory_format=torch.channels_last)
+    net.TemporalNet = net.TemporalNet.to(memory_format=torch.contiguous_format)
+    return net
+
+
+def measure(net, slots, queue, warm):
+    vb = VideoBatcher(net, slots, use_graph=True)
+    vb.run(warm)                                      # warm-up queue: graph capture, workspaces, prior cache
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    vb.run(queue)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    frames = sum(int(v.shape[0]) for _, v in queue)
+    return {"slots": slots, "frames_per_s": round(frames / dt, 1), "occupancy": round(vb.occupancy(), 4), "videos": len(queue),
+            "frames": frames, "steps": vb.steps, "graph": vb.pipe.graph_active, "seconds": round(dt, 3)}
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--videos", type=int, default=64)
+    ap.add_argument("--min-frames", type=int, default=8)
+    ap.add_argument("--max-frames", type=int, default=36)
+    ap.add_argument("--slots", type=int, nargs="+", default=[8, 32])
+    ap.add_argument("--config", default="STMask_plus_resnet50_config")
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    dev = "cuda"
+    net = build_net(a.config, dev)
+    queue = make_queue(a.videos, a.min_frames, a.max_frames, a.seed, dev)
+    rows = []
+    for s in a.slots:
+        warm = make_queue(max(s, 4), a.min_frames, a.min_frames + 4, a.seed + 1, dev)
+        rows.append(measure(net, s, queue, warm))
+    print(json.dumps({"tool": "serve_videos", "config": a.config, "runs": rows}))

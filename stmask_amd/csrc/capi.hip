@@ -25,6 +25,7 @@ extern "C" size_t stm_struct_bytes(int which)
         case 1: return sizeof(stm_conv_geom);
         case 2: return sizeof(stm_conv_window);
         case 3: return sizeof(stm_head_layout);
+        case 4: return sizeof(stm_frame_desc);
         default: return 0;
     }
 }

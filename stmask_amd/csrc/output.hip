@@ -169,6 +169,32 @@ __device__ __forceinline__ void resize_coeffs(int src, int dst, int d, bool clam
     c1 = min(max(a1, -32768), 32767);
 }
 
+// One output pixel (x, y) < (w, h) of an image whose source rows start at `img` with `row_stride` bytes between rows (3 bytes per pixel):
+// the fixed-point bilinear taps, then the mode's normalisation in double.  Both pre-processing kernels run exactly this sequence.
+__device__ __forceinline__ void preprocess_pixel(const uint8_t* __restrict__ img, int64_t row_stride, int H0, int W0, int h, int w, int x, int y,
+                                                 const double (&mean)[3], const double (&stdv)[3], int mode, float (&o)[3])
+{
+    int sx, sy, a0, a1, b0, b1;
+    resize_coeffs(W0, w, x, true, sx, a0, a1);
+    resize_coeffs(H0, h, y, false, sy, b0, b1);
+    const int sx1 = min(sx + 1, W0 - 1);
+    const int y0 = min(max(sy, 0), H0 - 1), y1 = min(max(sy + 1, 0), H0 - 1);
+    const uint8_t* r0 = img + (int64_t)y0 * row_stride;
+    const uint8_t* r1 = img + (int64_t)y1 * row_stride;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int D0 = r0[sx * 3 + c] * a0 + r0[sx1 * 3 + c] * a1;
+        const int D1 = r1[sx * 3 + c] * a0 + r1[sx1 * 3 + c] * a1;
+        int v = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2;
+        v = min(max(v, 0), 255);
+        double d = (double)v;
+        if (mode == 1) d = (d - mean[c]) / stdv[c];
+        else if (mode == 2) d = d - mean[c];
+        else if (mode == 3) d = d / 255.0;
+        o[c] = (float)d;
+    }
+}
+
 __global__ __launch_bounds__(256) void preprocess_u8_kernel(const uint8_t* __restrict__ img, float* __restrict__ out, int H0, int W0,
                                                             int h, int w, int Hp, int Wp, double m0, double m1, double m2, double s0,
                                                             double s1, double s2, int mode)
@@ -179,26 +205,32 @@ __global__ __launch_bounds__(256) void preprocess_u8_kernel(const uint8_t* __res
     if (x >= Wp || y >= Hp) return;
     float o[3] = {0.0f, 0.0f, 0.0f};
     if (y < h && x < w) {
-        int sx, sy, a0, a1, b0, b1;
-        resize_coeffs(W0, w, x, true, sx, a0, a1);
-        resize_coeffs(H0, h, y, false, sy, b0, b1);
-        const int sx1 = min(sx + 1, W0 - 1);
-        const int y0 = min(max(sy, 0), H0 - 1), y1 = min(max(sy + 1, 0), H0 - 1);
-        const uint8_t* r0 = img + ((size_t)i * H0 + y0) * W0 * 3;
-        const uint8_t* r1 = img + ((size_t)i * H0 + y1) * W0 * 3;
         const double mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
+        preprocess_pixel(img + (size_t)i * H0 * W0 * 3, (int64_t)W0 * 3, H0, W0, h, w, x, y, mean, stdv, mode, o);
+    }
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int D0 = r0[sx * 3 + c] * a0 + r0[sx1 * 3 + c] * a1;
-            const int D1 = r1[sx * 3 + c] * a0 + r1[sx1 * 3 + c] * a1;
-            int v = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2;
-            v = min(max(v, 0), 255);
-            double d = (double)v;
-            if (mode == 1) d = (d - mean[c]) / stdv[c];
-            else if (mode == 2) d = d - mean[c];
-            else if (mode == 3) d = d / 255.0;
-            o[c] = (float)d;
-        }
+    for (int c = 0; c < 3; ++c) out[(((size_t)i * 3 + c) * Hp + y) * Wp + x] = o[c];
+}
+
+// Up to 64 frames of different source sizes (and tensors) per launch: the descriptors travel in the kernel argument, so a launch needs no
+// host -> device copy and can be captured in a graph.  blockIdx.z = frame within the chunk.
+constexpr int kMultiFrames = 64;
+struct PreprocessMultiArgs {
+    stm_frame_desc f[kMultiFrames];
+};
+
+__global__ __launch_bounds__(256) void preprocess_u8_multi_kernel(const PreprocessMultiArgs a, float* __restrict__ out, int h, int w, int Hp, int Wp,
+                                                                  double m0, double m1, double m2, double s0, double s1, double s2, int mode)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int i = blockIdx.z;
+    if (x >= Wp || y >= Hp) return;
+    float o[3] = {0.0f, 0.0f, 0.0f};
+    if (y < h && x < w) {
+        const stm_frame_desc d = a.f[i];
+        const double mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
+        preprocess_pixel(d.ptr, d.row_stride_bytes, d.H0, d.W0, h, w, x, y, mean, stdv, mode, o);
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[(((size_t)i * 3 + c) * Hp + y) * Wp + x] = o[c];
@@ -220,5 +252,34 @@ extern "C" int stm_preprocess_u8_f32(const uint8_t* img, float* out, int n, int 
     hipLaunchKernelGGL(preprocess_u8_kernel, grid, dim3(256), 0, stm_hs(stream), img, out, H0, W0, h, w, Hp, Wp, m[0], m[1], m[2],
                        s[0], s[1], s[2], mode);
     STM_CHECK_LAUNCH("preprocess_u8_kernel");
+    return STM_OK;
+}
+
+extern "C" int stm_preprocess_u8_multi_f32(const stm_frame_desc* frames, int n, float* out, int h, int w, int Hp, int Wp, const double* mean,
+                                           const double* stdv, int mode, stm_stream_t stream)
+{
+    STM_REQUIRE(frames && out, STM_ENULL, "stm_preprocess_u8_multi_f32: frames/out must be non-NULL");
+    STM_REQUIRE(n > 0 && h > 0 && w > 0 && Hp >= h && Wp >= w, STM_EINVAL, "stm_preprocess_u8_multi_f32: bad sizes n=%d dst=%dx%d padded=%dx%d",
+                n, h, w, Hp, Wp);
+    STM_REQUIRE(mode >= 0 && mode <= 3, STM_EINVAL, "stm_preprocess_u8_multi_f32: mode %d not in 0..3", mode);
+    STM_REQUIRE(mode == 0 || mode == 3 || (mean && (mode == 2 || stdv)), STM_ENULL, "stm_preprocess_u8_multi_f32: mean/std needed for mode %d", mode);
+    for (int i = 0; i < n; ++i) {
+        const stm_frame_desc& d = frames[i];
+        STM_REQUIRE(d.ptr, STM_ENULL, "stm_preprocess_u8_multi_f32: frame %d has a NULL pointer", i);
+        STM_REQUIRE(d.H0 > 0 && d.W0 > 0 && d.row_stride_bytes >= 3 * (int64_t)d.W0, STM_EINVAL,
+                    "stm_preprocess_u8_multi_f32: frame %d: bad source size %dx%d (row stride %lld bytes)", i, d.H0, d.W0,
+                    (long long)d.row_stride_bytes);
+    }
+    const double m[3] = {mean ? mean[0] : 0.0, mean ? mean[1] : 0.0, mean ? mean[2] : 0.0};
+    const double s[3] = {stdv ? stdv[0] : 1.0, stdv ? stdv[1] : 1.0, stdv ? stdv[2] : 1.0};
+    for (int i0 = 0; i0 < n; i0 += kMultiFrames) {
+        const int k = min(kMultiFrames, n - i0);
+        PreprocessMultiArgs a = {};
+        for (int i = 0; i < k; ++i) a.f[i] = frames[i0 + i];
+        const dim3 grid(stm_cdiv(Wp, 64), stm_cdiv(Hp, 4), k);
+        hipLaunchKernelGGL(preprocess_u8_multi_kernel, grid, dim3(256), 0, stm_hs(stream), a, out + (size_t)i0 * 3 * Hp * Wp, h, w, Hp, Wp,
+                           m[0], m[1], m[2], s[0], s[1], s[2], mode);
+        STM_CHECK_LAUNCH("preprocess_u8_multi_kernel");
+    }
     return STM_OK;
 }

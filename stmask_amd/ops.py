@@ -1147,6 +1147,37 @@ def preprocess_frames(img_u8, size=(640, 360), divisor=32, mean=(123.675, 116.28
     return out
 
 
+def preprocess_frames_multi(frames, out=None, size=(640, 360), divisor=32, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375),
+                            mode=1):
+    """preprocess_frames for n frames that need not share a tensor or a source size: frames = sequence of uint8 [H_i, W_i, 3] device tensors
+    (rows may be strided, e.g. a crop view; pixels and channels contiguous).  One launch per 64 frames writes image i into out[i]
+    ([n, 3, Hp, Wp] fp32 contiguous, allocated when None), bit-identical to preprocess_frames of that image alone."""
+    frames = list(frames)
+    if not frames:
+        raise StmError("preprocess_frames_multi: no frames")
+    _dev(*frames)
+    w, h = size
+    Hp, Wp = -(-h // divisor) * divisor, -(-w // divisor) * divisor
+    n, dev = len(frames), frames[0].device
+    desc = (_lib.FrameDesc * n)()
+    keep = []                                       # contiguous copies made here live until the launch is enqueued (same stream)
+    for i, f in enumerate(frames):
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3 or f.device != dev:
+            raise StmError(f"preprocess_frames_multi: frame {i}: expected uint8 [H,W,3] on {dev}, got {f.dtype} {tuple(f.shape)} on {f.device}")
+        if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.shape[1]:
+            f = f.contiguous()
+            keep.append(f)
+        desc[i].ptr, desc[i].H0, desc[i].W0, desc[i].row_stride_bytes = f.data_ptr(), f.shape[0], f.shape[1], f.stride(0)
+    if out is None:
+        out = torch.empty(n, 3, Hp, Wp, device=dev, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, 3, Hp, Wp) or not out.is_contiguous() or out.device != dev:
+        raise StmError(f"preprocess_frames_multi: out must be contiguous fp32 {(n, 3, Hp, Wp)} on {dev}, got {out.dtype} {tuple(out.shape)}")
+    m3, s3 = (ctypes.c_double * 3)(*mean), (ctypes.c_double * 3)(*std)
+    check(_lib.lib().stm_preprocess_u8_multi_f32(desc, c_i(n), _p(out), c_i(h), c_i(w), c_i(Hp), c_i(Wp), m3, s3, c_i(mode), _stream()),
+          "stm_preprocess_u8_multi_f32")
+    return out
+
+
 def head_assemble(small, trk, B, sizes, n_cls, mask_dim, embed_dim, group_pad):
     """prediction_head_FC.py:168-195 for the planar head: small / trk = per-kernel-shape lists of [pixels, 3*group_pad] /
     [pixels, embed] fp32 matrices over the concatenated levels `sizes` = [(H, W), ...] with B images each.

@@ -84,13 +84,17 @@ class _TrackedRows(dict):
     rewritten from the prototypes at the next step anyway; the keep rule reads their bit words): `rows["mask"]` gathers them on
     first use from the two sources and the gather plan of that update."""
 
-    def defer_mask(self, prev_mask, det_mask, plan, n_prev):
-        self._deferred = (prev_mask, det_mask, plan, n_prev)
+    def defer_mask(self, prev_mask, det_mask, plan, n_prev, plan_host=None):
+        self._deferred = (prev_mask, det_mask, plan, n_prev, plan_host)
         dict.pop(self, "mask", None)
+
+    def deferred_mask(self):
+        """(prev_mask, det_mask, plan, n_prev, host plan) of a mask not gathered yet, else None."""
+        return None if dict.__contains__(self, "mask") else getattr(self, "_deferred", None)
 
     def _materialize(self):
         if not dict.__contains__(self, "mask") and getattr(self, "_deferred", None) is not None:
-            a, b, plan, n_prev = self._deferred
+            a, b, plan, n_prev, _ = self._deferred
             dict.__setitem__(self, "mask", ops.gather_rows2([a], [b], plan, n_prev)[0])
             self._deferred = None
 
@@ -211,6 +215,8 @@ class BatchedClipPipeline:
         self._graph_warm = 0
         self._graph_ws = []          # per slot: the workspaces its captured graph writes into (kept alive here)
         self._graph_planes = None    # plane format of the net's inference graph when the slots were captured (a net may serve several pipelines: _trunk)
+        self._idle_masks = {}        # inactive-slot pattern -> device bool [B] (see step's `active`)
+        self._idle_dev = None
         # Workload knob of the benchmark ("a max_instances cap to study n ~ 5-10, the realistic regime"), NOT
         # a reference semantic: the reference's tracker never prunes (track_TF.py:132-165).  n > 0: at most n detections per frame
         # (the best-scoring ones: Fast NMS returns them sorted) and at most n tracked instances per clip (an unmatched detection
@@ -403,7 +409,7 @@ class BatchedClipPipeline:
                 for t_ in list(pred.values()) + list(fpn_outs):  # allocated on the side stream, consumed on this one
                     if torch.is_tensor(t_):
                         t_.record_stream(torch.cuda.current_stream())
-                t2s_ = pred["T2S_feat"][net.correlation_selected_layer] if isinstance(pred.get("T2S_feat"), (list, tuple)) else None
+                t2s_ = pred["T2S_feat"][net.correlation_selected_layer] if isinstance(pred.get("T2S_feat"), (list, tuple)) and self.tf else None
                 if torch.is_tensor(t2s_):
                     t2s_.record_stream(torch.cuda.current_stream())
         else:
@@ -426,28 +432,122 @@ class BatchedClipPipeline:
                              cfg.nms_top_k, cfg.max_num_detections)
 
     @torch.no_grad()
-    def step(self, frames, is_first=None, next_frames=None):
+    def step(self, frames, is_first=None, next_frames=None, active=None):
         """frames [B,3,H,W] -> packed detections [B, top_k, 40] (stmask_amd.dist layout) without a final sync, plus the
         per-clip tracked-instance counts (host ints).  next_frames (optional): the frames the NEXT call will be given -- or a list: those of the
         next call, of the one after it, ... (the same tensor OBJECTS the later calls pass as `frames`); their trunks are started on side streams
         while this step's tracker logic runs (_prefetch_trunk).
 
+        is_first: None (True on the first step), a bool for every clip, or B bools (a list / tuple / CPU bool tensor [B]): clip b starts a new
+        video on this frame -- its tracked rows are dropped before anything reads them and the reference's first-frame rule applies to it alone
+        (track_TF.py:86-93, track.py:92-97), while the other clips keep their state.  active: None (all) or B bools; an inactive slot reports
+        nothing (its detection count is 0 on the device, its tracked rows are dropped, its packed rows are zero) -- a serving loop with fewer
+        videos than slots (stmask_amd.serve) gives it a frame of zeros.
+
         fp16 plane graphs carry |activation| <= 65504 only; their producers raise a sticky device flag beyond that, which arrives with the step's
         first host read (ops.RangeError).  The step is then NOT lost: the tracker state it had touched is put back, the inference graph is rebuilt
         with bf16x3 planes (fp32's range; weights repacked from the same modules, in-process), the step is repeated on it and the pipeline stays
         there (`fell_back`; logged once on stderr).  range_fallback = False restores the raise."""
-        first = (self.t == 0) if is_first is None else is_first
+        first, resets = self._first_flags(is_first)
+        idle = self._idle_flags(active, frames.device)
         if first:
             self.prev, self.prev_n, self.prev_feat = None, [0] * self.B, None
             self.tracked = [[] for _ in range(self.B)]
+        drop = sorted(set(resets) | set(idle))
         snap = self._snapshot() if (self.range_fallback and self._range_guarded()) else None
+        self._drop_clips(drop, frames.device)
         try:
             return self._step(frames, first, next_frames)
         except ops.RangeError:
             if snap is None:
                 raise
             self._fall_back(snap)
+            self._drop_clips(drop, frames.device)
             return self._step(frames, first, next_frames)
+
+    def _clip_flags(self, v, what):
+        if torch.is_tensor(v):
+            if v.device.type != "cpu" or v.dtype != torch.bool or tuple(v.shape) != (self.B,):
+                raise ValueError(f"BatchedClipPipeline.step: {what} must be a CPU bool tensor of shape [{self.B}], got {v.dtype} {tuple(v.shape)} on {v.device}")
+            v = v.tolist()
+        v = [bool(x) for x in v]
+        if len(v) != self.B:
+            raise ValueError(f"BatchedClipPipeline.step: {what} has {len(v)} entries for {self.B} clips")
+        return v
+
+    def _first_flags(self, is_first):
+        """-> (reset every clip, [clips that reset alone]).  An all-True / all-False sequence is the scalar form."""
+        if is_first is None:
+            return self.t == 0, []
+        if (torch.is_tensor(is_first) and is_first.dim() == 0) or not hasattr(is_first, "__len__"):
+            return bool(is_first), []
+        f = self._clip_flags(is_first, "is_first")
+        if all(f) or not any(f):
+            return f[0], []
+        return False, [b for b in range(self.B) if f[b]]
+
+    def _idle_flags(self, active, dev):
+        """-> [inactive clips]; sets self._idle_dev (device bool [B], or None when every clip is active) for the detection-count mask."""
+        self._idle_dev = None
+        if active is None:
+            return []
+        a = self._clip_flags(active, "active")
+        if all(a):
+            return []
+        key = (dev, tuple(a))
+        if key not in self._idle_masks:
+            self._idle_masks[key] = torch.tensor([not x for x in a], dtype=torch.bool).to(dev)
+        self._idle_dev = self._idle_masks[key]
+        return [b for b in range(self.B) if not a[b]]
+
+    def _drop_clips(self, clips, dev):
+        """Per-clip reset: the tracked rows of `clips` leave the concatenated set before CandidateShift reads it -- every row tensor and the
+        masks' bit words in ONE gather_rows2 launch (<= 8 tensors), a deferred soft-mask gather (_TrackedRows) stays deferred with its plan
+        composed on the host; the clip row offsets and the plan(s) go to the device in one copy.  New tensors: the set before the drop stays
+        intact for _fall_back.  The clips then hold nothing, and the pn == 0 branches of the tracker apply the first-frame rule to them."""
+        if not clips:
+            return
+        prev_n = list(self.prev_n)
+        for b in clips:
+            self.tracked[b] = []
+            self.prev_n[b] = 0
+        if self.prev is None or not any(prev_n[b] for b in clips):
+            return
+        gone = set(clips)
+        keep, p0 = [], 0
+        for b, n in enumerate(prev_n):
+            if b not in gone:
+                keep.extend(range(p0, p0 + n))
+            p0 += n
+        if not keep:
+            self.prev, self._bits, self._prev_bits = None, None, None
+            return
+        prev = self.prev
+        deferred = prev.deferred_mask() if isinstance(prev, _TrackedRows) else None
+        mask_plan = [deferred[4][r] for r in keep] if deferred is not None and deferred[4] is not None else None
+        if deferred is not None and mask_plan is None:
+            prev["mask"]                                  # (a deferral without a host plan: gather it now)
+            deferred = None
+        off = [0]
+        for n in self.prev_n:
+            off.append(off[-1] + n)
+        meta = torch.tensor(off + keep + (mask_plan or []), dtype=torch.int32).to(dev, non_blocking=True)
+        nb, nk = len(off), len(keep)
+        self._off_dev, keep_dev = meta[:nb], meta[nb:nb + nk]
+        keys = [k for k in dict.keys(prev) if k != "mask"]
+        srcs = [dict.__getitem__(prev, k) for k in keys] + [self._bits]
+        rows = ops.gather_rows2(srcs, [t[:0] for t in srcs], keep_dev, p0)
+        kept = _TrackedRows() if self.tf else {}
+        for k, t in zip(keys, rows[:-1]):
+            kept[k] = t
+        if self.tf:
+            if deferred is not None:
+                a, b_, _, n_prev, _ = deferred
+                kept.defer_mask(a, b_, meta[nb + nk:], n_prev, mask_plan)
+            elif dict.__contains__(prev, "mask"):
+                m = dict.__getitem__(prev, "mask")
+                kept.defer_mask(m, m[:0], keep_dev, p0, keep)
+        self.prev, self._bits, self._prev_bits = kept, rows[-1], None
 
     def _range_guarded(self):
         g = getattr(self.net, "_planar", None)
@@ -460,7 +560,9 @@ class BatchedClipPipeline:
         rows = None
         if self.tf and prev is not None and sum(self.prev_n):
             rows = tuple(prev[k].clone() for k in ("box", "mask_coeff", "score"))
-        return rows, [list(t) for t in self.tracked], self.t
+        # (a per-clip reset replaces the tracked set by new tensors before the step: the set, its counts, bit words and offsets are kept as they were)
+        state = (prev, list(self.prev_n), getattr(self, "_bits", None), getattr(self, "_prev_bits", None), getattr(self, "_off_dev", None))
+        return rows, [list(t) for t in self.tracked], self.t, state
 
     def _fall_back(self, snap):
         import sys
@@ -477,7 +579,8 @@ class BatchedClipPipeline:
             net._planar_bf16x3 = fuse.build_planar(net, "bf16x3")
         fuse.attach_planar(net, net._planar_bf16x3)
         self._graphs, self._graph_next, self.graph_active, self._graph_warm, self._graph_ws = [], 0, False, 0, []
-        rows, tracked, t = snap
+        rows, tracked, t, state = snap
+        self.prev, self.prev_n, self._bits, self._prev_bits, self._off_dev = state[0], list(state[1]), state[2], state[3], state[4]
         if rows is not None:
             for k, v in zip(("box", "mask_coeff", "score"), rows):
                 self.prev[k].copy_(v)
@@ -517,6 +620,8 @@ class BatchedClipPipeline:
         idx, cls, score, box, cnt = self._detect(pred)
         if self.max_instances > 0:
             cnt = torch.clamp(cnt, max=self.max_instances)
+        if self._idle_dev is not None:
+            cnt = cnt.masked_fill(self._idle_dev, 0)                   # inactive slots detect nothing
         counts, host_scores = ops.counts_to_host(cnt, extra=score)  # host read 1: B counts + the fp16 range flag + the NMS scores
         tmr.toc("detect")
         D = sum(counts)
@@ -588,7 +693,7 @@ class BatchedClipPipeline:
                 merged = _TrackedRows()
                 for k, t in zip(keys, rows[:-1]):
                     merged[k] = t
-                merged.defer_mask(prev["mask"], det["mask"], plan_dev, Pn)
+                merged.defer_mask(prev["mask"], det["mask"], plan_dev, Pn, plan)
                 self.prev, self._bits = merged, rows[-1]
             else:
                 self._bits = self._prev_bits if Pn else None
@@ -613,6 +718,8 @@ class BatchedClipPipeline:
         proto = pred["proto"]
         mc = torch.tanh(pred["mask_coeff"])                               # STMask.py:324 (generate_mask applies tanh AGAIN on this path: reproduced)
         idx, cls, score, box, cnt = self._detect(pred)
+        if self._idle_dev is not None:
+            cnt = cnt.masked_fill(self._idle_dev, 0)                   # inactive slots detect nothing
         counts, host_scores = ops.counts_to_host(cnt, extra=score)       # host read 1
         D, cap = sum(counts), idx.shape[1]
         det = ops.gather_detections(idx, cls, score, box, cnt, mc, pred["track"], pred["centerness"], D)

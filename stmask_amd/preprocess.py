@@ -21,3 +21,21 @@ def preprocess_eval_frames(frames_u8, idx=None, size=(640, 360), transform="norm
         meta["frame_id"] = idx
     meta["is_first"] = idx is None or idx == 0
     return out, meta
+
+
+def preprocess_eval_frames_multi(frames_u8, frame_ids=None, out=None, size=(640, 360), transform="normalize"):
+    """preprocess_eval_frames for a batch whose frames come from different videos: frames_u8 = sequence of uint8 [H_i, W_i, 3] device tensors
+    (sizes may differ), frame_ids = their frame indices within their videos (or None).  One kernel launch per 64 frames writes them into `out`
+    (fp32 [n, 3, 384, 640], allocated when None).  -> (batch, [img_meta of frame i]) with each frame's own ori_shape."""
+    frames_u8 = list(frames_u8)
+    out = ops.preprocess_frames_multi(frames_u8, out=out, size=size, divisor=32, mean=MEANS, std=STD, mode=_MODES[transform])
+    w, h = size
+    metas = []
+    for i, f in enumerate(frames_u8):
+        meta = {"ori_shape": (int(f.shape[0]), int(f.shape[1]), 3), "img_shape": (h, w, 3), "pad_shape": (out.shape[2], out.shape[3], 3)}
+        idx = None if frame_ids is None else frame_ids[i]
+        if idx is not None:
+            meta["frame_id"] = idx
+        meta["is_first"] = idx is None or idx == 0
+        metas.append(meta)
+    return out, metas
