@@ -2,6 +2,7 @@
 """Generate golden vectors by importing the REFERENCE's own Python (build container only).
 
     python tests/golden/gen_golden.py            # writes tests/golden/*.npz
+    python tests/golden/gen_golden.py model_full_tf model_full_tf16 model_full_tf_gaps model_full_tf_r101   # the full-size TF clips (CPU, ~2 min)
 
 The reference (/root/reference) never travels to the GPU box; only the small .npz files
 written here do.  They hold inputs + the outputs of the reference's torch code for the
@@ -23,6 +24,7 @@ below fakes the CUDA-only bits; nothing of the reference is c
 import collections
 import collections.abc
 import os
+import re
 import sys
 import types
 
@@ -322,14 +324,31 @@ def gen_model_full(cfg_name, tag, hw=(384, 640), row_step=16):
 
 
 FRAGILE_EPS = 1e-4
+SCORE_EPS = 1e-5
 
 
-def gen_model_full_tf(cfg_name, tag, hw=(384, 640), n_frames=3, n_masks=32):
-    """frames 0..2 of a FULL-SIZE clip through the reference's eval forward (STMask.py:310-329) with the benchmark's weights:
-    frame 0 detects, frames 1-2 run CandidateShift (TF_utils.py:12-51: correlation, RoIAlign, TemporalNet, decode, lincomb on the current
-    prototypes) and Track_TF.track (track_TF.py:50-181: comp scores, greedy resolution, ids, keep rule) on ~100 tracked instances.  Stored per
-    frame: every tracked instance's box / score / class / id / coefficients / centerness, float64 checksums (sum, sum of squares, count of pixels
-    > 0.5) of EVERY soft mask, the first n_masks soft masks whole, and checksums of the frame's head outputs."""
+def _row_mask_stats(m):
+    """float64 (sum, sum of squares, count > 0.5) of every soft mask [n, h, w]."""
+    m = m.double()
+    return torch.stack([m.sum(dim=(1, 2)), m.pow(2).sum(dim=(1, 2)), (m > 0.5).double().sum(dim=(1, 2))], 1)
+
+
+def gen_model_full_tf(cfg_name, name, hw=(384, 640), frame_src=3, clip_seed=0, n_masks=32, mask_frames=None, expect=None, coeff_sums=False):
+    """a FULL-SIZE clip through the reference's eval forward (STMask.py:310-329) with the benchmark's weights: the first frame
+    detects, the later ones run CandidateShift (TF_utils.py:12-51: correlation, RoIAlign, TemporalNet, decode, lincomb on the current prototypes)
+    and Track_TF.track (track_TF.py:50-181: comp scores, greedy resolution, ids, keep rule) on the whole tracked set.
+
+    frame_src: the frames fed, as indices into synthetic_clip(max + 1, *hw, seed=clip_seed) with -1 for an all-zero frame (no detections with these
+    weights), or an int T for frames 0..T-1.  Stored per frame: every tracked instance's box / score / class / id / coefficients / centerness, float64
+    checksums (sum, sum of squares, count of pixels > 0.5) of EVERY soft mask, the first n_masks reported soft masks whole on mask_frames (default:
+    every frame), checksums of the frame's head outputs, the tracker's whole state after the frame, which rows the keep rule (track_TF.py:160-164)
+    dropped for one condition alone (only_cond1 / 2 / 3), the rows excused from exact comparison (see below) and which branch of Track_TF.track ran
+    (spied: CandidateShift calls, prev_candidate before / after).  expect: {frame: branch} the generator asserts.  coeff_sums (the long clips, to keep
+    the files small): every row's 32 mask coefficients are stored as their float64 (sum, sum |.|) -- *_mask_coeff_sums -- and the reported rows'
+    centerness is left out.
+
+    The default clip seed 0 gives no count-fragile frame for the shipped fixtures; if a change of weights makes one appear, the generator stops:
+    pick another clip seed here rather than loosening the test."""
     from datasets.config import cfg, set_cfg
     set_cfg(cfg_name)
     cfg.temporal_fusion_module = True
@@ -337,41 +356,101 @@ def gen_model_full_tf(cfg_name, tag, hw=(384, 640), n_frames=3, n_masks=32):
     net = stmask_mod.STMask()
     net.eval()
     synthetic.fill_state_dict(net, seed=0, bg_bias=synthetic.BENCH_BG_BIAS)
-    frames = synthetic.synthetic_clip(n_frames, hw[0], hw[1], seed=0)
+    src = list(range(frame_src)) if isinstance(frame_src, int) else list(frame_src)
+    clip = synthetic.synthetic_clip(max(src) + 1, hw[0], hw[1], seed=clip_seed)
+    frames = torch.stack([clip[s] if s >= 0 else torch.zeros_like(clip[0]) for s in src])
+    n_frames = len(src)
+    mask_frames = list(range(n_frames)) if mask_frames is None else list(mask_frames)
     out = {"frames_hw": np.array(hw), "n_frames": np.array(n_frames), "n_masks": np.array(n_masks), "fragile_eps": np.array(FRAGILE_EPS)}
+    extra = {"frame_src": np.array(src, dtype=np.int64), "clip_seed": np.array(clip_seed), "mask_frames": np.array(mask_frames, dtype=np.int64),
+             "score_eps": np.array(SCORE_EPS)}
     # Which rows of the tracker state hang on a near-tie.  Track_TF.track decides by argmax over comp scores (track_TF.py:125) and, among detections that
     # pick the same object, by det_score > best (track_TF.py:141); with 120-200 overlapping instances some of those comparisons are closer than the
     # ~1e-6 by which two correct fp32 implementations of the trunk differ.  Recorded from the reference's OWN values, per frame: the rows whose outcome
     # a perturbation below FRAGILE_EPS could change (the test compares all other rows exactly) and whether the row COUNT could change.
+    # (fragile_rows: the matching decisions of that frame alone; excused_rows: every kind -- matching, the score threshold of cond3 within SCORE_EPS,
+    # a > 0.5 pixel count of cond2 that a pixel within FRAGILE_EPS of 0.5 could move across 1 -- and sticky: a row once fragile stays excused.)
     import layers.functions.track_TF as ttf
     seen = {}
-    real_ccs = ttf.compute_comp_scores
+    real_ccs, real_shift = ttf.compute_comp_scores, ttf.CandidateShift
 
     def spy(match_ll, bbox_scores, *a, **k):
         comp = real_ccs(match_ll, bbox_scores, *a, **k)
         seen["comp"], seen["score"] = comp.clone(), bbox_scores.view(-1).clone()
         return comp
-    ttf.compute_comp_scores = spy
+
+    def spy_shift(*a, **k):
+        seen["shift"] = seen.get("shift", 0) + 1
+        return real_shift(*a, **k)
+
+    tracker = net.Track_TF
+    real_track = tracker.track
+
+    def spy_track(net_, candidate, img_meta, img=None):
+        seen["n_cand"] = candidate["box"].nelement() // 4 if candidate["box"].dim() else 0
+        seen["prev_before"] = tracker.prev_candidate is not None and not img_meta["is_first"]
+        r = real_track(net_, candidate, img_meta, img=img)
+        seen["prev_after"] = tracker.prev_candidate is not None
+        return r
+
+    real_fs = net.forward_single
+
+    def spy_fs(x):
+        fpn_outs, po = real_fs(x)
+        seen["sums"] = {k: po[k][0].double() for k in ("loc", "conf", "mask_coeff", "centerness", "proto")}
+        seen["sums"] = {k: np.array([v.sum().item(), v.abs().sum().item()]) for k, v in seen["sums"].items()}
+        return fpn_outs, po
+
+    ttf.compute_comp_scores, ttf.CandidateShift = spy, spy_shift
+    tracker.track = spy_track
+    net.forward_single = spy_fs
+    excused, branches, any_count_fragile, prev_tm = set(), [], False, []
     with torch.no_grad():
         for t in range(n_frames):
             seen.clear()
-            _, po = net.forward_single(frames[t:t + 1])
-            for k in ("loc", "conf", "mask_coeff", "centerness", "proto"):
-                v = po[k][0].double()
-                out[f"t{t}_sum_{k}"] = np.array([v.sum().item(), v.abs().sum().item()])
             res = net(frames[t:t + 1], img_meta=[{"is_first": t == 0, "video_id": 0, "frame_id": t}])[0]["detection"]
+            for k in ("loc", "conf", "mask_coeff", "centerness", "proto"):
+                out[f"t{t}_sum_{k}"] = seen["sums"][k]
+            # which branch of Track_TF.track ran (track_TF.py:56-66 / 88-93 / 96-156), from the spies, not inferred from the outputs
+            shifted, matched = seen.get("shift", 0), "comp" in seen
+            if seen["n_cand"] == 0 and not seen["prev_before"]:
+                br = "empty_first"                  # :56-58, nothing tracked and nothing detected
+                assert shifted == 0 and not matched and not seen["prev_after"]
+            elif seen["n_cand"] == 0:
+                br = "empty_shift"                  # :61-66, CandidateShift and no matching
+                assert shifted == 1 and not matched and seen["prev_after"]
+            elif not seen["prev_before"]:
+                br = "first" if t == 0 else "first_late"   # :88-93 (first_late: is_first False, prev_candidate None)
+                assert shifted == 0 and not matched and seen["prev_after"]
+            else:
+                br = "match"
+                assert shifted == 1 and matched
+            branches.append(br)
+            if expect is not None and t in expect:
+                assert br == expect[t], (name, t, br, expect[t])
+            n_rep = len(res["box"]) if res["box"].nelement() else 0
             for k in ("box", "score", "class", "box_ids", "mask_coeff", "centerness"):
-                out[f"t{t}_{k}"] = res[k]
-            m = res["mask"].double()
-            out[f"t{t}_mask_sums"] = torch.stack([m.sum(dim=(1, 2)), m.pow(2).sum(dim=(1, 2)), (m > 0.5).double().sum(dim=(1, 2))], 1)
-            out[f"t{t}_mask"] = res["mask"][:n_masks]
+                v = res.get(k, torch.zeros(0))
+                out[f"t{t}_{k}"] = v if n_rep else v.new_zeros((0,) + ((4,) if k == "box" else (32,) if k == "mask_coeff" else ()))
+            if n_rep:
+                out[f"t{t}_mask_sums"] = _row_mask_stats(res["mask"])
+            else:
+                out[f"t{t}_mask_sums"] = torch.zeros(0, 3, dtype=torch.float64)
+            if t in mask_frames:
+                out[f"t{t}_mask"] = res["mask"][:n_masks] if n_rep else torch.zeros(0, hw[0] // 4, hw[1] // 4)
             # the tracker's whole state after the frame (row = instance id): what CandidateShift moved and Track_TF.track matched / appended,
             # including the instances the keep rule (track_TF.py:168-178) holds back from the output
-            st = net.Track_TF.prev_candidate
-            for k in ("box", "score", "class", "mask_coeff", "tracked_mask"):
-                out[f"t{t}_state_{k}"] = st[k].clone()          # (the next frame updates matched rows IN PLACE: track_TF.py:150)
-            ms = st["mask"].double()
-            out[f"t{t}_state_mask_sums"] = torch.stack([ms.sum(dim=(1, 2)), ms.pow(2).sum(dim=(1, 2)), (ms > 0.5).double().sum(dim=(1, 2))], 1)
+            st = tracker.prev_candidate
+            if st is None:
+                n_st = 0
+                for k, shp in (("box", (0, 4)), ("score", (0,)), ("class", (0,)), ("mask_coeff", (0, 32)), ("tracked_mask", (0,))):
+                    out[f"t{t}_state_{k}"] = torch.zeros(shp, dtype=torch.int64 if k == "class" else torch.float32)
+                out[f"t{t}_state_mask_sums"] = torch.zeros(0, 3, dtype=torch.float64)
+            else:
+                n_st = len(st["box"])
+                for k in ("box", "score", "class", "mask_coeff", "tracked_mask"):
+                    out[f"t{t}_state_{k}"] = st[k].clone()          # (the next frame updates matched rows IN PLACE: track_TF.py:150)
+                out[f"t{t}_state_mask_sums"] = _row_mask_stats(st["mask"])
             fragile, count_fragile, min_margin = set(), False, float("inf")
             if "comp" in seen:
                 comp, dsc = seen["comp"], seen["score"]
@@ -400,10 +479,58 @@ def gen_model_full_tf(cfg_name, tag, hw=(384, 640), n_frames=3, n_masks=32):
             out[f"t{t}_fragile_rows"] = np.array(sorted(fragile), dtype=np.int64)
             out[f"t{t}_count_fragile"] = np.array(count_fragile)
             out[f"t{t}_min_margin"] = np.array(min_margin)
-            print(tag, "state rows", len(st["box"]), "fragile rows", sorted(fragile), "count fragile", count_fragile, "min margin %.2e" % min_margin)
-            print(tag, "full-size TF frame", t, "tracked", len(res["box"]), "ids", int(res["box_ids"].max()) + 1 if len(res["box"]) else 0)
-    ttf.compute_comp_scores = real_ccs
-    save(f"model_full_tf_{tag}.npz", **out)
+            any_count_fragile |= count_fragile
+            # the keep rule's three conditions on the state (track_TF.py:160-164), and which rows fail exactly one of them
+            only = {1: [], 2: [], 3: []}
+            score_margin = float("inf")
+            if n_st:
+                tm = st["tracked_mask"]
+                c1 = tm <= 10
+                cnt = (st["mask"] > 0.5).sum([1, 2])
+                c2 = cnt > 1
+                c3 = st["score"] > cfg.eval_conf_thresh
+                for i, (a, b, c) in enumerate(zip(c1.tolist(), c2.tolist(), c3.tolist())):
+                    if [a, b, c].count(False) == 1:
+                        only[[a, b, c].index(False) + 1].append(i)
+                d3 = (st["score"] - cfg.eval_conf_thresh).abs()
+                score_margin = float(d3.min())
+                fragile |= set(torch.nonzero(d3 < SCORE_EPS).view(-1).tolist())
+                lo = (st["mask"] > 0.5 + FRAGILE_EPS).sum([1, 2])
+                hi = (st["mask"] > 0.5 - FRAGILE_EPS).sum([1, 2])
+                fragile |= set(torch.nonzero((lo > 1) != (hi > 1)).view(-1).tolist())
+                rem = [int(v) for v in torch.nonzero((tm == 0) & (torch.tensor(prev_tm + [0] * (n_st - len(prev_tm))) >= 5)).view(-1)] if t else []
+            else:
+                rem = []
+            excused |= fragile
+            for c in (1, 2, 3):
+                extra[f"t{t}_only_cond{c}"] = np.array(only[c], dtype=np.int64)
+            extra[f"t{t}_excused_rows"] = np.array(sorted(excused), dtype=np.int64)
+            extra[f"t{t}_rematched"] = np.array(rem, dtype=np.int64)
+            extra[f"t{t}_score_margin"] = np.array(score_margin)
+            prev_tm = [int(v) for v in st["tracked_mask"].tolist()] if n_st else []
+            print(f"{name} frame {t:2d} {br:11s} cand {seen['n_cand']:3d} state {n_st:3d} reported {n_rep:3d} age>10 {int((~c1).sum()) if n_st else 0:3d} "
+                  f"rematched(>=5) {len(rem):2d} score<=thr {int((~c3).sum()) if n_st else 0:3d} pix<=1 {int((~c2).sum()) if n_st else 0:3d} "
+                  f"only c1/c2/c3 {len(only[1])}/{len(only[2])}/{len(only[3])} excused {len(excused)} margins match {min_margin:.1e} score {score_margin:.1e}")
+    ttf.compute_comp_scores, ttf.CandidateShift = real_ccs, real_shift
+    tracker.track, net.forward_single = real_track, real_fs
+    if any_count_fragile:
+        raise SystemExit(f"{name}: a frame's row COUNT hangs on a comparison closer than {FRAGILE_EPS}: pick another clip seed for this fixture")
+    extra["branches"] = np.array(branches)
+    out.update(extra)
+    if coeff_sums:
+        for k in [k for k in out if re.fullmatch(r"t\d+_(state_)?mask_coeff", k)]:
+            v = torch.as_tensor(out.pop(k)).double()
+            out[k + "_sums"] = torch.stack([v.sum(1), v.abs().sum(1)], 1)
+        for k in [k for k in out if re.fullmatch(r"t\d+_centerness", k)]:
+            del out[k]
+    save(name, **out)
+    return branches
+
+
+# Frames of the gaps fixture (-1: all zeros, no detections): nothing detected on the first frame (track_TF.py:56-58), the first detections on a
+# non-first frame (:88-93 with prev_candidate None), two frames without detections (:61-66, CandidateShift alone), then re-matching after the gap.
+GAPS_FRAMES = (-1, 1, 2, 3, 4, 5, -1, -1, 8, 9, 10, 11)
+GAPS_BRANCHES = {0: "empty_first", 1: "first_late", 2: "match", 6: "empty_shift", 7: "empty_shift", 8: "match", 11: "match"}
 
 
 from synth_results import synth_video_results  # noqa: E402  (tests/golden/synth_results.py, shared with the test)
@@ -457,8 +584,18 @@ def main():
         gen_model_full("STMask_plus_resnet50_ada_config", "r50_ada")
         gen_model_full("STMask_plus_base_ali_config", "r101_ali")
     if "model_full_tf" in which:
-        gen_model_full_tf("STMask_plus_resnet50_config", "r50_fca")
-        gen_model_full_tf("STMask_plus_resnet50_ada_config", "r50_ada")
+        gen_model_full_tf("STMask_plus_resnet50_config", "model_full_tf_r50_fca.npz")
+        gen_model_full_tf("STMask_plus_resnet50_ada_config", "model_full_tf_r50_ada.npz")
+    if "model_full_tf_r101" in which:
+        gen_model_full_tf("STMask_plus_base_ali_config", "model_full_tf_r101_ali.npz")
+    if "model_full_tf16" in which:
+        # the benchmark's clip length (bench.py --frames 16)
+        for cfg_name, tag in (("STMask_plus_resnet50_config", "r50_fca"), ("STMask_plus_resnet50_ada_config", "r50_ada")):
+            gen_model_full_tf(cfg_name, f"model_full_tf16_{tag}.npz", frame_src=16, n_masks=16, mask_frames=(0, 11, 15),
+                              coeff_sums=True)
+    if "model_full_tf_gaps" in which:
+        gen_model_full_tf("STMask_plus_resnet50_config", "model_full_tf_gaps_r50_fca.npz", frame_src=GAPS_FRAMES, n_masks=16, mask_frames=(1, 7, 11),
+                          expect=GAPS_BRANCHES, coeff_sums=True)
     if "model_full_720p" in which:
         gen_model_full("STMask_plus_base_ali_config", "r101_ali_736x1280", hw=(736, 1280), row_step=64)
     if "model_extra" in which:

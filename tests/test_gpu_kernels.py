@@ -415,6 +415,85 @@ def test_fused_detect_more_candidates_than_the_lds_sort_holds(quantum):
     assert torch.equal(again[0], idx) and torch.equal(again[2], sc)
 
 
+def _detect_case(N, counts, quantum, logits, seed):
+    """B = len(counts) frames over N priors with EXACTLY counts[b] candidates each (max foreground probability > 0.05): the other rows get a
+    background logit 40 above the rest, the candidates a class logit 3 above their row's maximum.  quantum > 0: few distinct scores, so that the 200th
+    best key is shared by many rows -- probabilities floored to the quantum (logits=False), or candidate rows drawn from a pool of 40 logit rows
+    (logits=True: the kernel's softmax of equal rows is equal).  logits=True, quantum 0: the candidates' scores (probability x centerness) are set
+    to distinct values 2e-5 or more apart, so that no rank hangs on the last bits of a softmax."""
+    g = torch.Generator().manual_seed(seed)
+    B = len(counts)
+    lg = torch.randn(B, N, 41, generator=g) * 2.0
+    cen = torch.ones(B, N) if quantum else torch.tanh(torch.randn(B, N, generator=g) + 1.5)
+    for b, k in enumerate(counts):
+        perm = torch.randperm(N, generator=g)
+        cand, rest = perm[:k], perm[k:]
+        cls = torch.randint(1, 41, (k,), generator=g)
+        if logits and not quantum:
+            target = 0.1 + 0.35 * (torch.randperm(k, generator=g).double() + 0.5) / k          # score = probability x centerness
+            cen[b, cand] = 0.5 + 0.5 * torch.rand(k, generator=g)
+            prob = target / cen[b, cand].double()
+            row = torch.randn(k, 41, generator=g).double() * 0.5
+            row[torch.arange(k), cls] = -float("inf")
+            row[torch.arange(k), cls] = torch.logsumexp(row, 1) + torch.log(prob / (1 - prob))
+            lg[b, cand] = row.float()
+        else:
+            lg[b, cand, cls] = lg[b, cand].max(1).values + 3.0
+        if quantum and logits:
+            pool = lg[b, cand[:40]].clone()
+            lg[b, cand] = pool[torch.randint(0, 40, (k,), generator=g)]
+        lg[b, rest, 0] = lg[b, rest].max(1).values + 40.0
+    conf = torch.softmax(lg, -1)
+    if quantum and not logits:
+        conf = (conf / quantum).floor() * quantum + 0.001
+    pri = torch.cat([torch.rand(N, 2, generator=g), torch.rand(N, 2, generator=g) * 0.2 + 0.02], 1)
+    loc = torch.randn(B, N, 4, generator=g) * 0.5
+    n_cand = [(conf[b, :, 1:].max(1).values > 0.05).sum().item() for b in range(B)]
+    assert n_cand == list(counts), (n_cand, counts)
+    return loc, pri, lg if logits else conf, cen
+
+
+def _well_separated(logits, cen, top_k=200):
+    """No two of the top_k + 1 best scores are closer than 2e-6 unless equal: ranks that the kernel's softmax (scores within 16 ulp of torch's, <= 1e-6
+    below 1) cannot swap."""
+    p = torch.softmax(logits, -1)[:, 1:].max(1).values * cen
+    top = p.sort(descending=True).values[:top_k + 1]
+    gaps = top[:-1] - top[1:]
+    return bool(((gaps == 0) | (gaps > 2e-6)).all())
+
+
+@pytest.mark.parametrize("logits", [False, True], ids=["probs", "logits"])
+@pytest.mark.parametrize("quantum", [0.0, 0.02])
+@pytest.mark.parametrize("N,counts", [(15345, (4096, 4097, 6000, 12000, 15345)), (5000, (4096, 4097, 5000))])
+def test_fused_detect_select_path_matches_oracle(N, counts, quantum, logits):
+    """cc_nms_kernel's exact top-k selection (postproc.hip: radix select of the 200th best key, then ties by lower row) runs for every frame with more
+    than NMS_SELECT_FROM = 4 096 candidates, also when they all fit the LDS sort (N <= 16 384 priors: Kp = 16 384 or 8 192).  Candidate counts on
+    both sides of that switch (4 096 sorts, 4 097 selects), up to all N; one frame per launch, then three frames in one launch (4 096, 4 097, all N).
+    Against oracle.cpu_path._detect_cc (every candidate sorted, stable): prior indices, classes and boxes bit for bit; scores bit for bit on
+    probabilities, within 16 ulp on logits (the kernel's per-row softmax takes another exp and summation order than torch's: 9 ulp measured at
+    scores near 0.95; the inputs are built so that no two ranked scores that differ are within twice that, and the test checks it).  Each launch twice: equal outputs (the candidates are inserted by atomics)."""
+    from oracle.cpu_path import _detect_cc
+    cases = [(k,) for k in counts] + [(4096, 4097, N)]
+    for i, cnts in enumerate(cases):
+        loc, pri, conf, cen = _detect_case(N, cnts, quantum, logits, seed=100 + 10 * i)
+        assert not logits or all(_well_separated(conf[b], cen[b]) for b in range(len(cnts)))
+        out = ops.detect_cc(loc.to(DEV), pri.to(DEV), conf.to(DEV), cen.to(DEV), 0.05, 0.5, 200, logits=logits)
+        again = ops.detect_cc(loc.to(DEV), pri.to(DEV), conf.to(DEV), cen.to(DEV), 0.05, 0.5, 200, logits=logits)
+        for a, b in zip(out, again):
+            assert torch.equal(a, b), (N, cnts)
+        idx, cls, sc, bx, cnt = (t.cpu() for t in out)
+        o_idx, o_cls, o_sc, o_bx, o_cnt = _detect_cc(loc, pri, conf, cen, 0.05, 0.5, 200, logits=logits)
+        for b in range(len(cnts)):
+            n = int(cnt[b])
+            assert n == int(o_cnt[b]) and n > 0, (N, cnts, b, n, int(o_cnt[b]))
+            assert torch.equal(idx[b, :n], o_idx[b, :n]) and torch.equal(cls[b, :n], o_cls[b, :n]), (N, cnts, b)
+            assert torch.equal(bx[b, :n], o_bx[b, :n]), (N, cnts, b)
+            if logits:
+                assert ulp_diff(sc[b, :n], o_sc[b, :n]).max().item() <= 16, (N, cnts, b)
+            else:
+                assert torch.equal(sc[b, :n], o_sc[b, :n]), (N, cnts, b)
+
+
 def test_cc_fast_nms_more_rows_than_the_lds_sort_holds():
     """The reference-shaped call (candidate rows in, Detect_TF.cc_fast_nms) with K = 57 000 rows -- what a 736x1280 frame of the
     FCB(ali) config produces with synthetic weights -- goes through stm_cc_fast_nms_ws_f32 and equals the oracle."""

@@ -436,14 +436,14 @@ def test_trunk_branches_in_the_graph_are_bit_equal_to_the_plain_order(monkeypatc
 
 
 # ------------------------------------------------------------------------------------------------- full-size temporal fusion
-FULL_TF = [("STMask_plus_resnet50_config", "r50_fca"), ("STMask_plus_resnet50_ada_config", "r50_ada")]
+FULL_TF = [("STMask_plus_resnet50_config", "r50_fca"), ("STMask_plus_resnet50_ada_config", "r50_ada"), ("STMask_plus_base_ali_config", "r101_ali")]
 
 
 @pytest.mark.parametrize("name,tag", FULL_TF)
 def test_full_size_temporal_fusion_clip_matches_reference(name, tag):
     """Frames 0..2 of a FULL-SIZE 384x640 clip (the benchmark's weights) through the pipeline bench.py times, against the reference's own eval forward
     (gen_golden.py model_full_tf): frame 0 detects, frames 1-2 run CandidateShift (TF_utils.py:12-51) and Track_TF.track (track_TF.py:50-181) on the
-    whole tracked set (~40 instances on R50-FCA, 120-200 on FCB-ada).  Checked per frame: the tracker's WHOLE state row by row (row = instance id:
+    whole tracked set (~40 instances on R50-FCA, 120-200 on FCB-ada, ~100 on R101-FCB(ali)).  Checked per frame: the tracker's WHOLE state row by row (row = instance id:
     classes and frames-since-match counters equal, boxes / scores 5e-6, every soft mask's float64 sum and > 0.5 pixel count), then the reported
     instances (ids equal, boxes 5e-6, the stored soft masks 1e-4 RMS).  Two clips per step: batching must not couple them."""
     from stmask_amd.pipeline import BatchedClipPipeline

@@ -200,3 +200,25 @@ def test_non_tf_detect_track_path_is_self_consistent():
     assert n > 5 and torch.equal(d0["box_ids"], torch.arange(n))
     assert d1["box"].shape[0] == n and torch.equal(d1["box_ids"], d0["box_ids"])   # identical frame -> same ids
     assert torch.equal(d1["box"], d0["box"]) and d0["mask"].shape == (n, 32, 48)
+
+
+@pytest.mark.parametrize("fixture,zero_companion", [("model_full_tf16_r50_fca.npz", ()), ("model_full_tf_gaps_r50_fca.npz", (6,))])
+def test_batched_pipeline_long_clip_matches_reference_on_cpu(fixture, zero_companion):
+    """The benchmark's 16-frame full-size clip, and a clip with gaps (no detections on the first frame, first detections on a non-first frame, two
+    frames without detections, re-matching after them), through BatchedClipPipeline beside a second clip, against the reference's own eval forward
+    (gen_golden.py gen_model_full_tf): the host-side greedy matching, the frames-since-match counters, the keep rule and the packed output over the
+    frames where the age-out, the score decay and the pixel rule first decide.  In the gaps clip, frame 6 has no detection in EITHER clip
+    (the step keeps the shifted masks' bit words), frame 7 none in clip 0 alone."""
+    from long_clip_check import golden_clips, rules_decided, run_long_clip
+    from stmask_amd.pipeline import BatchedClipPipeline
+    g = load_golden(fixture)
+    net = STMask(get_cfg("STMask_plus_resnet50_config"))
+    net.eval()
+    synthetic.fill_state_dict(net, seed=0, bg_bias=synthetic.BENCH_BG_BIAS)
+    decided, rematched = rules_decided(g)
+    assert decided >= {2, 3} and rematched > 0, (decided, rematched)
+    clips = golden_clips(g, zero_companion)
+    with oracle_ops(), torch.no_grad():
+        rep = run_long_clip(fixture, BatchedClipPipeline(net, 2), g, clips, tol=1e-5, mask_rms=1e-5, mask_abs=1e-5,
+                            zero_companion=zero_companion)
+    assert rep[f"t{int(g['n_frames']) - 1}"]["state_rows"] > 100
