@@ -163,6 +163,7 @@ def attach_planar(net, built):
     from . import planar as _planar
     graph, bb, tn, planes = built
     _planar.set_format(0 if planes == "bf16x3" else 1, backbone_fmt=2 if planes == "fp16x1" else None)
+    ops.set_range_format(planes)
     net._planar, net._planar_backbone = graph, bb
     if tn is not None:
         net._planar_temporal = tn

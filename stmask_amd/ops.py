@@ -832,8 +832,20 @@ class RangeError(StmError):
     pipeline catches it, rebuilds the inference graph with bf16x3 planes (any fp32 range) and repeats the step."""
 
 
-RANGE_MESSAGE = ("an activation left the range of the fp16x2 planar format (|x| > 65504, inf or nan): results of this step are "
+RANGE_MESSAGE = ("an activation left the range of the {} planar format (|x| > 65504, inf or nan): results of this step are "
                  "invalid; build the graph with optimize_for_inference(net, planar=True, planes='bf16x3')")
+# the plane format of the graph attached last (fuse.attach_planar), named in the message.  Process-global like planar.set_format:
+# with nets of different formats in one process the message names the last one attached, not necessarily the one that raised
+_range_format = "fp16x2"
+
+
+def set_range_format(planes):
+    global _range_format
+    _range_format = planes
+
+
+def range_message():
+    return RANGE_MESSAGE.format(_range_format)
 
 
 def check_planar_range():
@@ -841,7 +853,7 @@ def check_planar_range():
     flag = _range_flags.get(torch.cuda.current_device())
     if flag is not None and int(flag.item()):
         flag.zero_()
-        raise RangeError(RANGE_MESSAGE)
+        raise RangeError(range_message())
 
 
 def counts_to_host(cnt, extra=None):
@@ -861,7 +873,7 @@ def counts_to_host(cnt, extra=None):
     n = cnt.numel()
     if flag is not None and int(host[n]):
         flag.zero_()
-        raise RangeError(RANGE_MESSAGE)
+        raise RangeError(range_message())
     counts = host[:n].tolist()
     if extra is None:
         return counts
