@@ -38,7 +38,9 @@
  *     deformable convolution stm_deform_conv_fused_planar_f32 / stm_deform_conv_fused_planar_supported; stm_debug_launch_count(1); the batched per-class Fast NMS
  *     stm_fast_nms_batched_f32 / stm_fast_nms_batched_workspace_bytes; the host-side stm_rle_strings_host);
  *      5: struct stm_frame_desc (stm_struct_bytes(4)) and stm_preprocess_u8_multi_f32, the pre-processing of a batch whose frames come from
- *     different tensors of different source sizes).
+ *     different tensors of different source sizes;
+ *      6: struct stm_render_frame (stm_struct_bytes(5)), stm_render_workspace_bytes and stm_render_overlay_u8, display mode: tracked
+ *     instances drawn onto their frames).
  */
 #ifndef STMASK_HIP_H_
 #define STMASK_HIP_H_
@@ -50,7 +52,7 @@
 extern "C" {
 #endif
 
-#define STM_ABI_VERSION 5
+#define STM_ABI_VERSION 6
 
 enum stm_status {
     STM_OK = 0,
@@ -663,6 +665,36 @@ int stm_deform_conv_fused_planar_f32(const float* x, int x_ld, const float* offs
                                      const float* bias, void* out_planes, int out_np, int out_pixel_offset, long long out_plane_stride,
                                      int Cout, int relu, float out_scale, const stm_deform_geom* g, int fmt, int out_fmt,
                                      stm_stream_t stream);
+
+/* ---- display mode (reference eval.py prep_display): tracked instances drawn onto uint8 frames --------------------------------
+ * One frame per descriptor, up to 64 per launch (the descriptors travel in the kernel argument, as stm_preprocess_u8_multi_f32's).
+ * masks fp32 [n_masks][mh][mw]: the soft masks of every frame concatenated; frame f owns rows [inst_begin, inst_begin + n_inst) of
+ * masks, of colors fp32 [n_masks][3] (palette colour / 255 in the OUTPUT's channel order) and of boxes int32 [n_masks][4]
+ * (x1, y1, x2, y2 in output pixels, clamped by the caller; NULL = no outlines).  Row 0 of a frame is drawn on top.
+ *   - coverage: the mask rows [0, crop_h) x [0, crop_w) resized bilinearly (align_corners=False) to out_h x out_w, then > 0.5: exactly the
+ *     pixels stm_mask_resize_rle_f32 encodes for the same rows;
+ *   - the base image, fp32 in [0, 1] per output pixel and channel: base_fmt 0 = uint8 HWC (3 bytes per pixel, base_row_stride bytes per row,
+ *     base_h x base_w == out_h x out_w) / 255; base_fmt 1 = fp32 planar [3][base_h][base_w] (a network input), its [0, base_crop_h) x
+ *     [0, base_crop_w) region resized bilinearly to out_h x out_w, then (v * stdv[c] + mean[c]) / 255 in double, clipped to [0, 1];
+ *   - composite in fp32 in the reference's operation order, out = (uint8)(value * 255) truncated;
+ *   - outlines: the 3-pixel band centred on each edge of the box, opaque, in the row's colour, drawn after the masks with row 0 on top.
+ * out: uint8 HWC, out_row_stride bytes per row (>= 3 * out_w).  Sizes <= 32767, strides < 2^31.  Workspace:
+ * stm_render_workspace_bytes(n_masks).  Every descriptor is checked before anything is launched.  ABI 6. */
+typedef struct stm_render_frame {
+    const void* base;
+    uint8_t* out;
+    int64_t base_row_stride;      /* base_fmt 0: bytes between rows */
+    int64_t out_row_stride;       /* bytes between output rows */
+    double mean[3], stdv[3];      /* base_fmt 1: de-normalisation per output channel */
+    int base_fmt, base_h, base_w, base_crop_h, base_crop_w;
+    int out_h, out_w;
+    int inst_begin, n_inst, crop_h, crop_w;
+    int reserved;
+} stm_render_frame;
+size_t stm_render_workspace_bytes(int n_masks);
+int stm_render_overlay_u8(const stm_render_frame* frames, int n_frames, const float* masks, int n_masks, int mh, int mw,
+                          const float* colors, const int* boxes, float alpha, void* workspace, size_t workspace_bytes,
+                          stm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -3,9 +3,10 @@
 sizes, served at each --slots count with graph-replayed trunks.  A measuring tool, not a test.
 
 Prints one JSON line: per slot count the frames/s (device-synchronised wall clock around the whole queue, after one warm-up queue), the slot
-occupancy (active slot-steps / all slot-steps) and the number of videos and frames.
+occupancy (active slot-steps / all slot-steps) and the number of videos and frames.  --render: every busy slot's frame is also drawn on the
+device each step (VideoBatcher.run(on_frame=...), stmask_amd.display source mode); the annotated frames are dropped.
 
-usage: python scripts/serve_videos.py [--videos 64] [--min-frames 8] [--max-frames 36] [--slots 8 32]"""
+usage: python scripts/serve_videos.py [--videos 64] [--min-frames 8] [--max-frames 36] [--slots 8 32] [--render]"""
 import argparse
 import json
 import os
@@ -47,17 +48,18 @@ def build_net(config, dev):
     return net
 
 
-def measure(net, slots, queue, warm):
+def measure(net, slots, queue, warm, render=False):
     vb = VideoBatcher(net, slots, use_graph=True)
-    vb.run(warm)                                      # warm-up queue: graph capture, workspaces, prior cache
+    on_frame = (lambda vid, fid, img: None) if render else None
+    vb.run(warm, on_frame=on_frame)                   # warm-up queue: graph capture, workspaces, prior cache
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    vb.run(queue)
+    vb.run(queue, on_frame=on_frame)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     frames = sum(int(v.shape[0]) for _, v in queue)
     return {"slots": slots, "frames_per_s": round(frames / dt, 1), "occupancy": round(vb.occupancy(), 4), "videos": len(queue),
-            "frames": frames, "steps": vb.steps, "graph": vb.pipe.graph_active, "seconds": round(dt, 3)}
+            "frames": frames, "steps": vb.steps, "graph": vb.pipe.graph_active, "seconds": round(dt, 3), "render": render}
 
 
 if __name__ == "__main__":
@@ -68,6 +70,7 @@ if __name__ == "__main__":
     ap.add_argument("--slots", type=int, nargs="+", default=[8, 32])
     ap.add_argument("--config", default="STMask_plus_resnet50_config")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--render", action="store_true", help="draw every served frame on the device (display source mode)")
     a = ap.parse_args()
     dev = "cuda"
     net = build_net(a.config, dev)
@@ -75,5 +78,5 @@ if __name__ == "__main__":
     rows = []
     for s in a.slots:
         warm = make_queue(max(s, 4), a.min_frames, a.min_frames + 4, a.seed + 1, dev)
-        rows.append(measure(net, s, queue, warm))
+        rows.append(measure(net, s, queue, warm, a.render))
     print(json.dumps({"tool": "serve_videos", "config": a.config, "runs": rows}))

@@ -13,7 +13,7 @@ _lib = None
 c_i, c_l, c_f, c_p, c_sz = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
 # every symbol include/stmask_hip.h declares (tests/test_abi.py checks the library exports all of them)
-ABI_VERSION = 5   # include/stmask_hip.h STM_ABI_VERSION
+ABI_VERSION = 6   # include/stmask_hip.h STM_ABI_VERSION
 ABI_SYMBOLS = [
     "stm_version", "stm_last_error_string", "stm_struct_bytes", "stm_debug_reload_tunables", "stm_debug_launch_count", "stm_conv_kxr_packed_bytes", "stm_conv_pack_weights_kxr_f32", "stm_conv2d_planar_kxr_f32", "stm_conv2d_planar_dual_f32", "stm_conv2d_planar_windows_f32", "stm_conv2d_planar_windows_pool_f32", "stm_temporal_pool_fc_f32", "stm_stem_packed_weight_bytes", "stm_stem_pack_weights_f32", "stm_stem_fused_f32", "stm_chain_tail_weight_bytes", "stm_chain_tail_weight_bytes_proj", "stm_chain_pack_tail_f32", "stm_chain_pack_tail_proj_f32", "stm_bottleneck_chain_f32", "stm_bottleneck_chain_proj_f32", "stm_deform_im2col_f32", "stm_deform_conv_workspace_bytes",
     "stm_deform_conv_fwd_f32", "stm_gemm_bias_f32", "stm_gemm_workspace_bytes", "stm_gemm_bias_ws_f32", "stm_fcb_ali_offsets_f32", "stm_corr_patch_f32", "stm_corr_patch_nhwc_f32",
@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "stm_gather_detections_f32", "stm_shift_rois_f32", "stm_shift_apply_f32", "stm_match_scores_f32", "stm_match_scores_embed_f32", "stm_gather_rows2", "stm_pack_tracked_f32", "stm_pack_tracked_bits_f32",
     "stm_lincomb_sigmoid_crop_bits_f32", "stm_mask_iou_bits_f32", "stm_split_planes_f16", "stm_conv_pack_weights_f16", "stm_conv2d_planar_f16", "stm_dcn_sample_planar_f16",
     "stm_deform_conv_fused_planar_supported", "stm_deform_conv_fused_planar_f32", "stm_fast_nms_batched_workspace_bytes", "stm_fast_nms_batched_f32", "stm_rle_strings_host",
-    "stm_preprocess_u8_multi_f32",
+    "stm_preprocess_u8_multi_f32", "stm_render_workspace_bytes", "stm_render_overlay_u8",
 ]
 
 
@@ -55,6 +55,13 @@ class FrameDesc(ctypes.Structure):
     _fields_ = [("ptr", c_p), ("H0", c_i), ("W0", c_i), ("row_stride_bytes", c_l)]
 
 
+class RenderFrame(ctypes.Structure):
+    _fields_ = ([("base", c_p), ("out", c_p), ("base_row_stride", c_l), ("out_row_stride", c_l), ("mean", ctypes.c_double * 3),
+                 ("stdv", ctypes.c_double * 3)] +
+                [(n, c_i) for n in ("base_fmt", "base_h", "base_w", "base_crop_h", "base_crop_w", "out_h", "out_w", "inst_begin", "n_inst",
+                                    "crop_h", "crop_w", "reserved")])
+
+
 class HeadLayout(ctypes.Structure):
     _fields_ = ([(n, c_i) for n in ("B", "K", "n_levels", "n_cls", "mask_dim", "embed_dim", "group_pad", "small_ld", "trk_ld")] +
                 [("lvl_start", c_i * 8), ("lvl_hw", c_i * 8)])
@@ -80,7 +87,7 @@ def lib():
         _lib.stm_last_error_string.restype = ctypes.c_char_p
         _lib.stm_version.restype = c_i
         for name in ("stm_deform_conv_workspace_bytes", "stm_gemm_workspace_bytes", "stm_mask_rle_workspace_bytes", "stm_detect_cc_workspace_bytes", "stm_fast_nms_workspace_bytes",
-                     "stm_mask_iou_workspace_bytes", "stm_conv_packed_weight_bytes", "stm_conv_packed_weight_bytes_tiled", "stm_cc_fast_nms_workspace_bytes", "stm_conv_kxr_packed_bytes", "stm_stem_packed_weight_bytes", "stm_chain_tail_weight_bytes", "stm_chain_tail_weight_bytes_proj", "stm_fast_nms_batched_workspace_bytes"):
+                     "stm_mask_iou_workspace_bytes", "stm_conv_packed_weight_bytes", "stm_conv_packed_weight_bytes_tiled", "stm_cc_fast_nms_workspace_bytes", "stm_conv_kxr_packed_bytes", "stm_stem_packed_weight_bytes", "stm_chain_tail_weight_bytes", "stm_chain_tail_weight_bytes_proj", "stm_fast_nms_batched_workspace_bytes", "stm_render_workspace_bytes"):
             getattr(_lib, name).restype = c_sz
         _lib.stm_struct_bytes.restype = c_sz
         _lib.stm_debug_reload_tunables.restype = None
@@ -88,7 +95,8 @@ def lib():
         # this binding and the library must describe the same structs (a stale .so would read garbage past a shorter struct)
         if _lib.stm_version() != ABI_VERSION or _lib.stm_struct_bytes(0) != ctypes.sizeof(DeformGeom) or \
                 _lib.stm_struct_bytes(1) != ctypes.sizeof(ConvGeom) or _lib.stm_struct_bytes(2) != ctypes.sizeof(ConvWindow) or \
-                _lib.stm_struct_bytes(3) != ctypes.sizeof(HeadLayout) or _lib.stm_struct_bytes(4) != ctypes.sizeof(FrameDesc):
+                _lib.stm_struct_bytes(3) != ctypes.sizeof(HeadLayout) or _lib.stm_struct_bytes(4) != ctypes.sizeof(FrameDesc) or \
+                _lib.stm_struct_bytes(5) != ctypes.sizeof(RenderFrame):
             v = _lib.stm_version()
             _lib = None
             raise StmError(f"{LIB_PATH} has ABI version {v}, this binding was written for {ABI_VERSION} (or a struct size "

@@ -26,6 +26,7 @@ extern "C" size_t stm_struct_bytes(int which)
         case 2: return sizeof(stm_conv_window);
         case 3: return sizeof(stm_head_layout);
         case 4: return sizeof(stm_frame_desc);
+        case 5: return sizeof(stm_render_frame);
         default: return 0;
     }
 }

@@ -29,15 +29,11 @@ __global__ __launch_bounds__(256) void resize_threshold_pack_kernel(const float*
     if (p < (int64_t)out_h * out_w) {
         const int x = (int)(p / out_h), y = (int)(p - (int64_t)x * out_h);
         const float* m = masks + (int64_t)i * mh * mw;
-        const float sh = (float)crop_h / (float)out_h, sw = (float)crop_w / (float)out_w;
-        float fy = sh * ((float)y + 0.5f) - 0.5f, fx = sw * ((float)x + 0.5f) - 0.5f;
-        if (fy < 0.0f) fy = 0.0f;
-        if (fx < 0.0f) fx = 0.0f;
-        const int y0 = (int)fy, x0 = (int)fx;
-        const int y1 = y0 + (y0 < crop_h - 1 ? 1 : 0), x1 = x0 + (x0 < crop_w - 1 ? 1 : 0);
-        const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.0f - ly, hx = 1.0f - lx;
-        const float v = hy * (hx * m[y0 * mw + x0] + lx * m[y0 * mw + x1]) + ly * (hx * m[y1 * mw + x0] + lx * m[y1 * mw + x1]);
-        b = v > thr;
+        int y0, y1, x0, x1;
+        float ly, hy, lx, hx;
+        stm_bilinear_tap(y, (float)crop_h / (float)out_h, crop_h, y0, y1, ly, hy);
+        stm_bilinear_tap(x, (float)crop_w / (float)out_w, crop_w, x0, x1, lx, hx);
+        b = stm_bilinear_blend(m, mw, y0, y1, x0, x1, ly, hy, lx, hx) > thr;
     }
     const unsigned long long bal = __ballot(b);
     if (lane == 0) bits[(int64_t)i * words + word] = bal;

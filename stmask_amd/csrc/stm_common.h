@@ -62,6 +62,24 @@ __device__ __forceinline__ int64_t stm_xcd_block(int64_t nblocks)
 __device__ __forceinline__ int64_t stm_xcd_block_or_plain(int xcd, int64_t nblocks) { return xcd ? stm_xcd_block(nblocks) : (int64_t)blockIdx.x; }
 static inline unsigned stm_xcd_grid(int64_t nblocks) { return (unsigned)(8 * ((nblocks + 7) / 8)); }
 
+// Bilinear sampling as ATen's upsample_bilinear2d (align_corners=False) in fp32, operand order as in oracle/stm_oracle.c.  Shared by the
+// mask encoder (output.hip) and the display renderer (display.hip): the masks drawn are the masks written to the json, bit for bit.
+// stm_bilinear_tap: output index o of a length-`in` axis resized with `scale` = (float)in / (float)out -> taps i0, i1 and weights h, l.
+__device__ __forceinline__ void stm_bilinear_tap(int o, float scale, int in, int& i0, int& i1, float& l, float& h)
+{
+    float f = scale * ((float)o + 0.5f) - 0.5f;
+    if (f < 0.0f) f = 0.0f;
+    i0 = (int)f;
+    i1 = i0 + (i0 < in - 1 ? 1 : 0);
+    l = f - (float)i0;
+    h = 1.0f - l;
+}
+__device__ __forceinline__ float stm_bilinear_blend(const float* __restrict__ m, int64_t ld, int y0, int y1, int x0, int x1, float ly, float hy,
+                                                    float lx, float hx)
+{
+    return hy * (hx * m[y0 * ld + x0] + lx * m[y0 * ld + x1]) + ly * (hx * m[y1 * ld + x0] + lx * m[y1 * ld + x1]);
+}
+
 // Canonical exp (oracle/stm_oracle.c: stm_exp_f64): identical IEEE operation sequence in double, rounded
 // once to fp32.  Compiled with -ffp-contract=off; every fused step is an explicit fma().
 __device__ __forceinline__ double stm_exp_f64(double x)

@@ -71,21 +71,20 @@ def rle_strings(counts_host, n_runs_host):
     return [out[i, :lens[i]].tobytes() for i in range(n)]
 
 
-def postprocess_ytbvis(det_output, img_meta, interpolation_mode="bilinear", display_mask=False, score_threshold=0,
-                       preserve_aspect_ratio=True):
-    """Same contract as the reference: returns the detection dict with 'segm' (list of COCO RLE dicts, or the binary
-    masks on the device when display_mask) and integer pixel 'box'.  `preserve_aspect_ratio` is what eval.py sets on the
-    global cfg before calling (eval.py:639)."""
-    if interpolation_mode != "bilinear":
-        raise NotImplementedError("the reference only ever calls this with bilinear interpolation")
-    dets = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in det_output["detection"].items()}
+def select_rows(det, img_meta, score_threshold=0, preserve_aspect_ratio=True):
+    """Row selection of postprocess_ytbvis (reference output_utils.py:45-69): the rows with score > score_threshold (when > 0) and, with
+    preserve_aspect_ratio, whose box centre lies inside the image.  det: the detection dict (not modified; unselected keys are shared).
+    -> (dict of the kept rows, crop_h, crop_w, out_h, out_w): the un-padded mask size and the size the masks are resized to."""
+    dets = dict(det)
     ori_h, ori_w = img_meta["ori_shape"][:2]
     img_h, img_w = img_meta["img_shape"][:2]
     pad_h, pad_w = img_meta["pad_shape"][:2]
     s_w, s_h = img_w / pad_w, img_h / pad_h
+    out_h, out_w = (ori_h, ori_w) if preserve_aspect_ratio else (img_h, img_w)
+    masks = dets.get("mask")
+    crop_h, crop_w = (int(s_h * masks.size(1)), int(s_w * masks.size(2))) if masks is not None and masks.dim() == 3 else (0, 0)
     if dets["box"].nelement() == 0:
-        dets["segm"] = []
-        return dets
+        return dets, crop_h, crop_w, out_h, out_w
 
     def keep_rows(keep):
         idx = torch.nonzero(keep).view(-1)
@@ -98,23 +97,45 @@ def postprocess_ytbvis(det_output, img_meta, interpolation_mode="bilinear", disp
     if preserve_aspect_ratio and dets["score"].nelement() != 0:
         c = center_size(dets["box"])
         keep_rows(((c[:, 0] > s_w).int() + (c[:, 1] > s_h).int()) < 1)
+    return dets, crop_h, crop_w, out_h, out_w
+
+
+def pixel_boxes(boxes, img_meta, preserve_aspect_ratio=True):
+    """Normalised boxes [n, 4] (relative to the padded input) -> integer pixel boxes of the output frame (reference output_utils.py:112-129)."""
+    img_h, img_w = img_meta["img_shape"][:2]
+    pad_h, pad_w = img_meta["pad_shape"][:2]
+    s_w, s_h = img_w / pad_w, img_h / pad_h
+    out_h, out_w = img_meta["ori_shape"][:2] if preserve_aspect_ratio else (img_h, img_w)
+    boxes = boxes.clone()
+    boxes[:, 0::2] = boxes[:, 0::2] / s_w
+    boxes[:, 1::2] = boxes[:, 1::2] / s_h
+    boxes[:, 0], boxes[:, 2] = sanitize_coordinates(boxes[:, 0], boxes[:, 2], out_w, cast=False)
+    boxes[:, 1], boxes[:, 3] = sanitize_coordinates(boxes[:, 1], boxes[:, 3], out_h, cast=False)
+    return boxes.long()
+
+
+def postprocess_ytbvis(det_output, img_meta, interpolation_mode="bilinear", display_mask=False, score_threshold=0,
+                       preserve_aspect_ratio=True):
+    """Same contract as the reference: returns the detection dict with 'segm' (list of COCO RLE dicts, or the binary
+    masks on the device when display_mask) and integer pixel 'box'.  `preserve_aspect_ratio` is what eval.py sets on the
+    global cfg before calling (eval.py:639)."""
+    if interpolation_mode != "bilinear":
+        raise NotImplementedError("the reference only ever calls this with bilinear interpolation")
+    dets = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in det_output["detection"].items()}
+    if dets["box"].nelement() == 0:
+        dets["segm"] = []
+        return dets
+    dets, crop_h, crop_w, out_h, out_w = select_rows(dets, img_meta, score_threshold, preserve_aspect_ratio)
     if dets["score"].size(0) == 0:
         dets["segm"] = []
         return dets
 
-    masks, boxes = dets["mask"], dets["box"]
-    crop_h, crop_w = int(s_h * masks.size(1)), int(s_w * masks.size(2))
-    out_h, out_w = (ori_h, ori_w) if preserve_aspect_ratio else (img_h, img_w)
+    masks = dets["mask"]
     if display_mask:
         up = torch.nn.functional.interpolate(masks[None, :, :crop_h, :crop_w], (out_h, out_w), mode="bilinear",
                                              align_corners=False)[0]
         dets["segm"] = up.gt_(0.5)
     else:
         dets["segm"] = encode_masks(masks, crop_h, crop_w, out_h, out_w)
-    boxes = boxes.clone()
-    boxes[:, 0::2] = boxes[:, 0::2] / s_w
-    boxes[:, 1::2] = boxes[:, 1::2] / s_h
-    boxes[:, 0], boxes[:, 2] = sanitize_coordinates(boxes[:, 0], boxes[:, 2], out_w, cast=False)
-    boxes[:, 1], boxes[:, 3] = sanitize_coordinates(boxes[:, 1], boxes[:, 3], out_h, cast=False)
-    dets["box"] = boxes.long()
+    dets["box"] = pixel_boxes(dets["box"], img_meta, preserve_aspect_ratio)
     return dets

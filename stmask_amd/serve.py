@@ -9,12 +9,15 @@ same slot on the next step (``is_first[b] = True``; the other slots keep their t
 
 The whole schedule is known before the first step, so the batches of the next ``pipe.prefetch_depth`` steps are pre-processed ahead and handed
 to the pipeline as ``next_frames`` (the same tensor objects the later steps pass as ``frames``): their trunks run beside the current step.
+
+``run(..., on_frame=f)`` also draws every busy slot's tracked instances onto that slot's own source frame on the device (display.render_batch,
+source mode: one launch per step) and calls f(video_id, frame_id, frame_u8) per slot; without it nothing is drawn.
 """
 from collections import deque
 
 import torch
 
-from . import eval_utils, output_utils, preprocess
+from . import display, eval_utils, output_utils, preprocess
 
 
 def schedule(lengths, n_slots):
@@ -86,7 +89,9 @@ class VideoBatcher:
         return self.busy_slot_steps / max(1, self.steps * self.B)
 
     @torch.no_grad()
-    def run(self, videos, out_file=None):
+    def run(self, videos, out_file=None, on_frame=None):
+        """-> the YouTube-VIS records (or results2json_videoseg's output when out_file is given).  on_frame(video_id, frame_id, frame_u8):
+        called per busy slot and step with its frame annotated on the device (uint8 [H, W, 3] in the frame's own channel order)."""
         videos = list(videos)
         plan = schedule([int(v[1].shape[0]) for v in videos], self.B)
         depth = self.pipe.prefetch_depth if self.lookahead is None else int(self.lookahead)
@@ -109,6 +114,14 @@ class VideoBatcher:
             nxt = [r[0] for r in list(ready)[:depth]] if depth > 0 else None
             self.pipe.step(batch, is_first=is_first, next_frames=nxt or None, active=active)
             dets = self.pipe.detections()
+            if on_frame is not None:
+                busy = [b for b, c in enumerate(row) if c is not None]
+                dev = batch.device
+                srcs = [videos[row[b][0]][1][row[b][1]] for b in busy]
+                srcs = [f if f.device == dev else f.to(dev, non_blocking=True) for f in srcs]
+                drawn = display.render_batch([dets[b] for b in busy], srcs, [metas[b] for b in busy], mode="source")
+                for b, img in zip(busy, drawn):
+                    on_frame(videos[row[b][0]][0], row[b][1], img)
             for b, c in enumerate(row):
                 if c is None:
                     continue
