@@ -41,6 +41,8 @@
  *     different tensors of different source sizes;
  *      6: struct stm_render_frame (stm_struct_bytes(5)), stm_render_workspace_bytes and stm_render_overlay_u8, display mode: tracked
  *     instances drawn onto their frames).
+ *     Added since without a version change (new entry points only; the binding refuses a library that lacks one): the backward kernels of
+ *     the training path stm_deform_col2im_f32, stm_deform_col2im_coord_f32, stm_roi_align_backward_f32, stm_corr_backward_f32.
  */
 #ifndef STMASK_HIP_H_
 #define STMASK_HIP_H_
@@ -695,6 +697,36 @@ size_t stm_render_workspace_bytes(int n_masks);
 int stm_render_overlay_u8(const stm_render_frame* frames, int n_frames, const float* masks, int n_masks, int mh, int mw,
                           const float* colors, const int* boxes, float alpha, void* workspace, size_t workspace_bytes,
                           stm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Backward of the drop-ins (the training path: stmask_amd/autograd.py).  fp32; the bilinear conventions are the forwards' own.
+ * Replaces: dcn_v2 _backend.dcn_v2_backward, mmcv ext_module.deform_conv_backward_input / roi_align_backward,
+ *           spatial_correlation_sampler's backward.
+ *
+ * stm_deform_col2im_f32: grad_x[B,C,H,W] += the column gradient grad_cols[B][C*K][Ho*Wo] (layout of stm_deform_im2col_f32's cols) scattered
+ *   to the 4 bilinear corners of every tap, times the mask (mask NULL: v1; mask_is_logit: sigmoid applied as the forward does).  Corners
+ *   outside the image are dropped.  fp32 atomic adds: the caller zeroes grad_x; the sum order varies run to run in the last bits.
+ * stm_deform_col2im_coord_f32: grad_offset (channel g*2K + 2k = d/d dy, + 1 = d/d dx, the forward's layout; batch stride goff_bstride) and
+ *   grad_mask (channel g*K + k; batch stride gmask_bstride), each the sum over the C/dg channels of its group in channel order (no atomics,
+ *   run-to-run identical).  With mask_is_logit grad_mask is the gradient w.r.t. the logit: d/dm * s * (1 - s), evaluated as e / (1 + e)^2
+ *   with e = exp(-logit) (no cancellation for s near 1).  The coordinate derivative
+ *   takes h_low = floor(h), also at integer h, and is 0 outside (-1, H) x (-1, W).  Either output may be NULL; grad_mask needs a mask.
+ * ------------------------------------------------------------------------------------------------- */
+int stm_deform_col2im_f32(const float* grad_cols, const float* offset, int64_t off_bstride, const float* mask, int64_t mask_bstride,
+                          int mask_is_logit, float* grad_x, const stm_deform_geom* g, stm_stream_t stream);
+int stm_deform_col2im_coord_f32(const float* grad_cols, const float* x, const float* offset, int64_t off_bstride, const float* mask,
+                                int64_t mask_bstride, int mask_is_logit, float* grad_offset, int64_t goff_bstride, float* grad_mask,
+                                int64_t gmask_bstride, const stm_deform_geom* g, stm_stream_t stream);
+/* grad_feat[B,C,H,W] += the gradient of stm_roi_align_avg_f32 (same arguments; grad_out [n,C,PH,PW]): every sample scatters
+ * grad / count times its 4 bilinear weights on the clamped coordinate; samples outside [-1, H] x [-1, W] and RoIs whose batch index is
+ * outside [0, B) contribute nothing.  fp32 atomic adds (the caller zeroes grad_feat).  No gradient w.r.t. rois. */
+int stm_roi_align_backward_f32(const float* grad_out, const float* rois, float* grad_feat, int B, int C, int H, int W, int n, int PH,
+                               int PW, float spatial_scale, int sampling_ratio, int aligned, stm_stream_t stream);
+/* Gradients of stm_corr_patch_f32 with scale = 1, leaky_slope = 1 (grad_out [B,P,P,H,W]):
+ *   grad_in1[b,c,y,x] = sum_{i,j} g[b,i,j,y,x] * in2[b,c,y+dy,x+dx],  grad_in2[b,c,y,x] = sum_{i,j} g[b,i,j,y-dy,x-dx] * in1[b,c,y-dy,x-dx]
+ * (terms outside the map are 0).  Written, not accumulated; either output may be NULL.  One fixed-order sum per output. */
+int stm_corr_backward_f32(const float* grad_out, const float* in1, const float* in2, float* grad_in1, float* grad_in2, int B, int C, int H,
+                          int W, int P, int dil, stm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,126 @@
+"""Autograd for the drop-in deformable convolution, RoIAlign and correlation (the training path of dcn_v2 / mmcv.ops /
+spatial_correlation_sampler).
+
+Each Function's forward is the launch the shim makes without autograd (ops.deform_conv / roi_align / corr_patch), so values under
+autograd are bit-identical to the no-grad call.  Only inputs are saved: the deformable columns are recomputed in backward with the
+forward's own im2col.  Backward runs the gfx950 kernels of csrc/deform_backward.hip and csrc/temporal_backward.hip on the current
+stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.
+"""
+import torch
+
+from . import ops
+
+
+def wants_grad(*tensors):
+    """The shims take the autograd path only when grad mode is on and some tensor input or parameter requires grad."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+class ModulatedDeformConvFunction(torch.autograd.Function):
+    """dcn_v2 DCNv2: y = deform_conv(x, offset, mask, weight, bias).  With fused=True `offset` is DCN's raw conv_offset_mask output
+    (offsets, then mask logits; the sigmoid is applied in-kernel) and `mask` is None: the gradient returned for it is the gradient
+    w.r.t. those raw channels."""
+
+    @staticmethod
+    def forward(ctx, x, offset, mask, weight, bias, stride, padding, dilation, deform_groups, fused):
+        ctx.conv = (stride, padding, dilation, deform_groups, fused)
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x, offset, mask, weight)
+        if fused:
+            return ops.deform_conv(x, None, None, weight, bias, stride, padding, dilation, deform_groups, fused_om=offset)
+        return ops.deform_conv(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, offset, mask, weight = ctx.saved_tensors
+        stride, padding, dilation, dg, fused = ctx.conv
+        nx, noff, nmask, nw, nb = ctx.needs_input_grad[:5]
+        need = (nx, noff, nmask and mask is not None, nw, nb and ctx.has_bias)
+        if not any(need):
+            return (None,) * 10
+        if fused:
+            gx, goff, _, gw, gb = ops.deform_conv_backward(grad_out.contiguous(), x, None, None, weight, stride, padding, dilation, dg,
+                                                           fused_om=offset, need=(nx, noff, noff, nw, need[4]))
+            return gx, goff, None, gw, gb, None, None, None, None, None
+        gx, goff, gmask, gw, gb = ops.deform_conv_backward(grad_out.contiguous(), x, offset, mask, weight, stride, padding, dilation, dg,
+                                                           need=need)
+        return gx, goff, gmask, gw, gb, None, None, None, None, None
+
+
+class DeformConvFunction(torch.autograd.Function):
+    """mmcv DeformConv2d (v1: no mask, no bias): y = deform_conv(x, offset, None, weight)."""
+
+    @staticmethod
+    def forward(ctx, x, offset, weight, stride, padding, dilation, deform_groups):
+        ctx.conv = (stride, padding, dilation, deform_groups)
+        ctx.save_for_backward(x, offset, weight)
+        return ops.deform_conv(x, offset, None, weight, None, stride, padding, dilation, deform_groups)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, offset, weight = ctx.saved_tensors
+        stride, padding, dilation, dg = ctx.conv
+        nx, noff, nw = ctx.needs_input_grad[:3]
+        if not (nx or noff or nw):
+            return (None,) * 7
+        gx, goff, _, gw, _ = ops.deform_conv_backward(grad_out.contiguous(), x, offset, None, weight, stride, padding, dilation, dg,
+                                                      need=(nx, noff, False, nw, False))
+        return gx, goff, gw, None, None, None, None
+
+
+class RoIAlignFunction(torch.autograd.Function):
+    """mmcv roi_align (avg): gradient w.r.t. the feature map only (mmcv returns none for the RoIs)."""
+
+    @staticmethod
+    def forward(ctx, feat, rois, output_size, spatial_scale, sampling_ratio, aligned):
+        ctx.args = (tuple(feat.shape), output_size, spatial_scale, sampling_ratio, aligned)
+        ctx.save_for_backward(rois)
+        return ops.roi_align(feat, rois, output_size, spatial_scale, sampling_ratio, aligned)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        (rois,) = ctx.saved_tensors
+        shape, output_size, spatial_scale, sampling_ratio, aligned = ctx.args
+        gfeat = ops.roi_align_backward(grad_out.contiguous(), rois, shape, output_size, spatial_scale, sampling_ratio, aligned)
+        return gfeat, None, None, None, None, None
+
+
+class CorrelationFunction(torch.autograd.Function):
+    """spatial_correlation_sample(kernel_size=1, patch_size=P, dilation_patch=d): [B,C,H,W] x 2 -> [B,P,P,H,W]."""
+
+    @staticmethod
+    def forward(ctx, in1, in2, patch_size, dilation_patch):
+        ctx.dil = dilation_patch
+        ctx.save_for_backward(in1, in2)
+        return ops.corr_patch(in1, in2, patch_size, dilation_patch)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        n1, n2 = ctx.needs_input_grad[:2]
+        if not (n1 or n2):
+            return None, None, None, None
+        in1, in2 = ctx.saved_tensors
+        g1, g2 = ops.corr_patch_backward(grad_out.contiguous(), in1, in2, ctx.dil, need1=n1, need2=n2)
+        return g1, g2, None, None
+
+
+def modulated_deform_conv(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups):
+    return ModulatedDeformConvFunction.apply(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups, False)
+
+
+def modulated_deform_conv_fused(x, om, weight, bias, stride, padding, dilation, deform_groups):
+    return ModulatedDeformConvFunction.apply(x, om, None, weight, bias, stride, padding, dilation, deform_groups, True)
+
+
+def deform_conv(x, offset, weight, stride, padding, dilation, deform_groups):
+    return DeformConvFunction.apply(x, offset, weight, stride, padding, dilation, deform_groups)
+
+
+def roi_align(feat, rois, output_size, spatial_scale, sampling_ratio, aligned):
+    return RoIAlignFunction.apply(feat, rois, output_size, spatial_scale, sampling_ratio, aligned)
+
+
+def correlation(in1, in2, patch_size, dilation_patch):
+    return CorrelationFunction.apply(in1, in2, patch_size, dilation_patch)

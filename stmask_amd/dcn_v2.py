@@ -7,14 +7,15 @@ names, shapes and state-dict keys are therefore part of the contract (SURVEY.md 
 
 Forward = one hand-written gfx950 launch pair (deformable im2col + fp32 MFMA GEMM with fused bias); the chunk / cat /
 sigmoid that dcn_v2 does in torch is folded into the im2col kernel (it reads the raw ``conv_offset_mask`` output).
-Inference only: no backward kernels (training is outside the hot path).
+When grad mode is on and an input or parameter requires grad, the same launch runs inside a torch.autograd.Function whose backward
+is hand-written gfx950 kernels too (stmask_amd/autograd.py); otherwise no autograd node is made.
 """
 import math
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import autograd, ops
 
 
 def _pair(v):
@@ -43,6 +44,9 @@ class DCNv2(nn.Module):
         K = self.kernel_size[0] * self.kernel_size[1]
         if offset.shape[1] != 2 * self.deformable_groups * K or mask.shape[1] != self.deformable_groups * K:
             raise ValueError("DCNv2: offset / mask channel count does not match kernel size and deformable_groups")
+        if autograd.wants_grad(input, offset, mask, self.weight, self.bias):
+            return autograd.modulated_deform_conv(input, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation,
+                                                  self.deformable_groups)
         return ops.deform_conv(input, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation,
                                self.deformable_groups)
 
@@ -64,5 +68,11 @@ class DCN(DCNv2):
     def forward(self, input):
         om = self.conv_offset_mask(input)
         # offsets = om[:, :2*dg*K], mask = sigmoid(om[:, 2*dg*K:]) -- read in place by the kernel
+        if autograd.wants_grad(input, om, self.weight, self.bias):
+            if self.fuse_relu:
+                raise RuntimeError("DCN with fuse_relu (fuse.optimize_for_inference) is inference-only: run it under torch.no_grad() "
+                                   "or build the module without fusing")
+            return autograd.modulated_deform_conv_fused(input, om, self.weight, self.bias, self.stride, self.padding, self.dilation,
+                                                        self.deformable_groups)
         return ops.deform_conv(input, None, None, self.weight, self.bias, self.stride, self.padding, self.dilation,
                                self.deformable_groups, relu=self.fuse_relu, fused_om=om)

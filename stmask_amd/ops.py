@@ -337,6 +337,112 @@ def roi_align(feat, rois, output_size, spatial_scale=1.0, sampling_ratio=0, alig
     return out
 
 
+def deform_col2im(grad_cols, offset, mask, g, fused_om=None):
+    """grad_x [B,C,H,W] of deform_im2col from the column gradient grad_cols [B, C*kh*kw, Ho*Wo] (fp32 atomic scatter)."""
+    _dev(grad_cols, offset, mask, fused_om)
+    grad_cols = _f32c(grad_cols)
+    off, obs, _, mk_ptr, mbs = _offset_mask_views(offset, mask, g, fused_om)
+    gx = torch.zeros(g.B, g.C, g.H, g.W, device=grad_cols.device, dtype=torch.float32)
+    check(_lib.lib().stm_deform_col2im_f32(_p(grad_cols), _p(off), c_l(obs), c_p(mk_ptr), c_l(mbs), c_i(1 if fused_om is not None else 0),
+                                           _p(gx), ctypes.byref(g), _stream()), "stm_deform_col2im_f32")
+    return gx
+
+
+def deform_col2im_coord(grad_cols, x, offset, mask, g, fused_om=None, want_offset=True, want_mask=True):
+    """(grad_offset, grad_mask) of deform_im2col (deterministic).  With fused_om: one tensor shaped like it, the offset channels followed
+    by the gradient w.r.t. the mask LOGITS (channels a part that was not asked for stay 0)."""
+    _dev(grad_cols, x, offset, mask, fused_om)
+    grad_cols, x = _f32c(grad_cols), _f32c(x)
+    off, obs, _, mk_ptr, mbs = _offset_mask_views(offset, mask, g, fused_om)
+    K, HWo = g.kh * g.kw, g.Ho * g.Wo
+    L = _lib.lib()
+    if fused_om is not None:
+        gom = torch.zeros_like(off) if not (want_offset and want_mask) else torch.empty_like(off)
+        bs = g.dg * 3 * K * HWo
+        check(L.stm_deform_col2im_coord_f32(_p(grad_cols), _p(x), _p(off), c_l(obs), c_p(mk_ptr), c_l(mbs), c_i(1),
+                                            _p(gom) if want_offset else c_p(0), c_l(bs),
+                                            c_p(gom.data_ptr() + 4 * g.dg * 2 * K * HWo) if want_mask else c_p(0), c_l(bs),
+                                            ctypes.byref(g), _stream()), "stm_deform_col2im_coord_f32")
+        return gom
+    goff = torch.empty(g.B, g.dg * 2 * K, g.Ho, g.Wo, device=x.device, dtype=torch.float32) if want_offset else None
+    gmask = torch.empty(g.B, g.dg * K, g.Ho, g.Wo, device=x.device, dtype=torch.float32) if (want_mask and mk_ptr) else None
+    if goff is None and gmask is None:
+        return None, None
+    check(L.stm_deform_col2im_coord_f32(_p(grad_cols), _p(x), _p(off), c_l(obs), c_p(mk_ptr), c_l(mbs), c_i(0), _p(goff), c_l(g.dg * 2 * K * HWo),
+                                        _p(gmask), c_l(g.dg * K * HWo), ctypes.byref(g), _stream()), "stm_deform_col2im_coord_f32")
+    return goff, gmask
+
+
+def deform_conv_backward(grad_out, x, offset, mask, weight, stride=1, padding=0, dilation=1, deform_groups=1, fused_om=None,
+                         need=(True, True, True, True, True)):
+    """Gradients of deform_conv (relu=False) -> (grad_x, grad_offset, grad_mask, grad_weight, grad_bias); need[i] False -> None, nothing
+    launched for it.  With fused_om, grad_offset is the gradient w.r.t. the whole raw conv_offset_mask output and grad_mask is None.
+    The columns are recomputed with the forward's im2col; the two dense products run on the library's fp32 GEMM (fixed order):
+    grad_cols = W^T grad_out, grad_weight = sum_b grad_out_b cols_b^T; grad_bias is torch's sum of grad_out."""
+    need_x, need_off, need_mask, need_w, need_b = need
+    _dev(grad_out, x, offset, mask, weight, fused_om)
+    x, weight = _f32c(x), _f32c(weight)
+    go = _f32c(grad_out)
+    O, C, kh, kw = weight.shape
+    g = _geom(x, (kh, kw), stride, padding, dilation, deform_groups)
+    CK, HWo = C * kh * kw, g.Ho * g.Wo
+    if tuple(go.shape) != (g.B, O, g.Ho, g.Wo):
+        raise StmError(f"deform_conv_backward: grad_out {tuple(go.shape)} != {(g.B, O, g.Ho, g.Wo)}")
+    gx = goff = gmask = gw = gb = None
+    if need_b:
+        gb = go.sum((0, 2, 3))
+    if need_w:
+        cols = deform_im2col(x, offset, mask, (kh, kw), stride, padding, dilation, deform_groups, fused_om=fused_om)
+        # grad_weight^T [CK, O] = cols [CK, B*HWo] . grad_out^T [B*HWo, O]
+        a = cols[0] if g.B == 1 else cols.permute(1, 0, 2).reshape(CK, g.B * HWo)
+        bm = go.view(g.B, O, HWo).permute(0, 2, 1).reshape(g.B * HWo, O)
+        gw = gemm_bias(a.contiguous(), bm.contiguous()).t().reshape(O, C, kh, kw).contiguous()
+        del cols, a
+    if need_x or need_off or need_mask:
+        gcols = gemm_bias(weight.view(O, CK).t().contiguous(), go.view(g.B, O, HWo))        # [B, CK, HWo]
+        if need_x:
+            gx = deform_col2im(gcols, offset, mask, g, fused_om)
+        if need_off or (need_mask and (mask is not None or fused_om is not None)):
+            if fused_om is not None:
+                goff = deform_col2im_coord(gcols, x, None, None, g, fused_om, want_offset=need_off, want_mask=need_mask)
+            else:
+                goff, gmask = deform_col2im_coord(gcols, x, offset, mask, g, None, want_offset=need_off, want_mask=need_mask)
+    return gx, goff, gmask, gw, gb
+
+
+def roi_align_backward(grad_out, rois, feat_shape, output_size, spatial_scale=1.0, sampling_ratio=0, aligned=True):
+    """grad_feat of roi_align (fp32 atomic scatter); no gradient w.r.t. rois."""
+    _dev(grad_out, rois)
+    go, rois = _f32c(grad_out), _f32c(rois)
+    ph, pw = _pair(output_size)
+    B, C, H, W = feat_shape
+    n = rois.shape[0]
+    if tuple(go.shape) != (n, C, ph, pw):
+        raise StmError(f"roi_align_backward: grad_out {tuple(go.shape)} != {(n, C, ph, pw)}")
+    gfeat = torch.zeros(B, C, H, W, device=go.device, dtype=torch.float32)
+    check(_lib.lib().stm_roi_align_backward_f32(_p(go), _p(rois), _p(gfeat), c_i(B), c_i(C), c_i(H), c_i(W), c_i(n), c_i(ph), c_i(pw),
+                                                c_f(spatial_scale), c_i(sampling_ratio), c_i(1 if aligned else 0), _stream()),
+          "stm_roi_align_backward_f32")
+    return gfeat
+
+
+def corr_patch_backward(grad_out, f1, f2, dilation_patch=1, need1=True, need2=True):
+    """(grad_f1, grad_f2) of corr_patch(scale=1, leaky_slope=1); a gradient not needed is None and not computed."""
+    _dev(grad_out, f1, f2)
+    go, f1, f2 = _f32c(grad_out), _f32c(f1), _f32c(f2)
+    B, C, H, W = f1.shape
+    P = go.shape[1]
+    if tuple(go.shape) != (B, P, P, H, W) or f2.shape != f1.shape:
+        raise StmError(f"corr_patch_backward: grad_out {tuple(go.shape)} does not match inputs {tuple(f1.shape)}")
+    g1 = torch.empty_like(f1) if need1 else None
+    g2 = torch.empty_like(f2) if need2 else None
+    if g1 is None and g2 is None:
+        return None, None
+    check(_lib.lib().stm_corr_backward_f32(_p(go), _p(f1), _p(f2), _p(g1), _p(g2), c_i(B), c_i(C), c_i(H), c_i(W), c_i(P),
+                                           c_i(dilation_patch), _stream()), "stm_corr_backward_f32")
+    return g1, g2
+
+
 def decode(loc, priors):
     """box_utils.py:238-283, bit-exact vs the oracle."""
     _dev(loc, priors)
