@@ -4,8 +4,12 @@ spatial_correlation_sampler).
 Each Function's forward is the launch the shim makes without autograd (ops.deform_conv / roi_align / corr_patch), so values under
 autograd are bit-identical to the no-grad call.  Only inputs are saved: the deformable columns are recomputed in backward with the
 forward's own im2col.  Backward runs the gfx950 kernels of csrc/deform_backward.hip and csrc/temporal_backward.hip on the current
-stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.
+stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
+every backward is @first_order_only: a double backward (create_graph=True, then differentiating the result) raises instead of
+silently dropping the second-order term.
 """
+import functools
+
 import torch
 
 from . import ops
@@ -14,6 +18,36 @@ from . import ops
 def wants_grad(*tensors):
     """The shims take the autograd path only when grad mode is on and some tensor input or parameter requires grad."""
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+class _NotTwiceDifferentiable(torch.autograd.Function):
+    """Identity on `grad`; the other arguments are what `grad` was computed from.  Differentiating through it raises."""
+
+    @staticmethod
+    def forward(ctx, grad, *made_from):
+        return grad.view_as(grad)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise RuntimeError("stmask_amd: the drop-ins' backward kernels are not differentiable (no double backward): a gradient made with "
+                           "create_graph=True cannot be differentiated again")
+
+
+def first_order_only(backward):
+    """For a Function.backward made of kernel launches.  torch's once_differentiable raises only when the incoming grad_out requires grad; under
+    create_graph=True the gradients also depend on the saved inputs (grad_x on the weight and the offsets, ...), and a later backward through
+    them would silently miss that term.  Here every returned gradient is tied to grad_out AND the saved tensors by a node that raises."""
+    @functools.wraps(backward)
+    def wrapper(ctx, *grad_outs):
+        if not torch.is_grad_enabled():             # the usual backward pass
+            return backward(ctx, *grad_outs)
+        with torch.no_grad():
+            outs = backward(ctx, *grad_outs)
+        made_from = [t for t in (*grad_outs, *ctx.saved_tensors) if t is not None and t.requires_grad]
+        if not made_from:
+            return outs
+        return tuple(o if o is None else _NotTwiceDifferentiable.apply(o, *made_from) for o in outs)
+    return wrapper
 
 
 class ModulatedDeformConvFunction(torch.autograd.Function):
@@ -31,6 +65,7 @@ class ModulatedDeformConvFunction(torch.autograd.Function):
         return ops.deform_conv(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups)
 
     @staticmethod
+    @first_order_only
     def backward(ctx, grad_out):
         x, offset, mask, weight = ctx.saved_tensors
         stride, padding, dilation, dg, fused = ctx.conv
@@ -57,6 +92,7 @@ class DeformConvFunction(torch.autograd.Function):
         return ops.deform_conv(x, offset, None, weight, None, stride, padding, dilation, deform_groups)
 
     @staticmethod
+    @first_order_only
     def backward(ctx, grad_out):
         x, offset, weight = ctx.saved_tensors
         stride, padding, dilation, dg = ctx.conv
@@ -78,6 +114,7 @@ class RoIAlignFunction(torch.autograd.Function):
         return ops.roi_align(feat, rois, output_size, spatial_scale, sampling_ratio, aligned)
 
     @staticmethod
+    @first_order_only
     def backward(ctx, grad_out):
         if not ctx.needs_input_grad[0]:
             return (None,) * 6
@@ -97,6 +134,7 @@ class CorrelationFunction(torch.autograd.Function):
         return ops.corr_patch(in1, in2, patch_size, dilation_patch)
 
     @staticmethod
+    @first_order_only
     def backward(ctx, grad_out):
         n1, n2 = ctx.needs_input_grad[:2]
         if not (n1 or n2):

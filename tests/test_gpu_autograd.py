@@ -6,6 +6,11 @@ values (for the offsets, where the bilinear derivative is a difference, autograd
 Where a sample position comes out of a GPU layer (DCN's conv_offset_mask, an offset convolution), the fp64 side takes that layer's fp32
 VALUE and its own fp64 graph, so both sides sample at the same point (a floor() on either side of an integer would be a different gradient).
 The tests call only the shims and the restatements: on a tree without backward kernels they fail on the missing gradients.
+
+What this file deliberately avoids: sample positions ON integers and ON -1 / H / W (_offsets moves every integer offset by 0.125), because
+grid_sample, the yardstick here, is not right there.  test_gpu_autograd_edges.py covers exactly those positions (a freshly constructed DCN, a
+lattice of border / integer / half-integer positions) with the four-corner restatement, and with them correlation maps of several tiles and the
+global-memory form, RoIAlign with aligned=False, and the ways autograd calls the Functions.
 """
 import copy
 
