@@ -54,37 +54,44 @@ def _corner_grads(x, off, mask, w, b, go, st, pad, dl, dg):
 
 
 # ---- 1. a freshly constructed DCN ----------------------------------------------------------------------------------------------------------
-def _dcn_step_compare(tag, mg, x, go, stride):
+def _dcn_step_compare(tag, mg, x, go, stride, padding=1, dilation=1, check_forward=False):
     """One forward / backward of the GPU module mg against the fp64 four-corner restatement of dcn_v2.DCN.forward with mg's parameters; the fp64
-    conv_offset_mask output takes the GPU's fp32 value (captured), its graph stays fp64.  Returns the fp64 om value."""
+    conv_offset_mask output takes the GPU's fp32 value (captured), its graph stays fp64.  stride / padding / dilation: a number or a pair
+    (conv_offset_mask is built without the dilation, as in dcn_v2).  check_forward: also hold y to the oracle (_check_forward).  Returns
+    (grad_x, grad_weight, grad_bias, the fp64 om value)."""
+    pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)
+    st, pad, dl = pair(stride), pair(padding), pair(dilation)
+    dg, n_off = mg.deformable_groups, 2 * mg.deformable_groups * mg.kernel_size[0] * mg.kernel_size[1]
     cap = _Capture(mg.conv_offset_mask)
     mg.zero_grad()
     xg = x.to(DEV).requires_grad_()
-    mg(xg).backward(go.to(DEV))
+    y = mg(xg)
+    y.backward(go.to(DEV))
     cw64, cb64, w64, b64 = (p.detach().cpu().double().requires_grad_() for p in (mg.conv_offset_mask.weight, mg.conv_offset_mask.bias, mg.weight,
                                                                                  mg.bias))
     x64 = x.double().requires_grad_()
-    om = F.conv2d(x64, cw64, cb64, stride, 1)
+    om = F.conv2d(x64, cw64, cb64, st, pad)
     om = om + (cap.out.detach().cpu().double() - om).detach()
     om.retain_grad()
     o1, o2, mk = torch.chunk(om, 3, dim=1)
-    st, one = (stride, stride), (1, 1)
-    R.deform_conv_corners(x64, torch.cat((o1, o2), 1), torch.sigmoid(mk), w64, b64, st, one, one, 1).backward(go.double())
+    R.deform_conv_corners(x64, torch.cat((o1, o2), 1), torch.sigmoid(mk), w64, b64, st, pad, dl, dg).backward(go.double())
     omd = om.detach()
-    s = torch.sigmoid(omd[:, 18:])
+    s = torch.sigmoid(omd[:, n_off:])
     w, b = mg.weight.detach().cpu(), mg.bias.detach().cpu()
-    _, mag = _corner_grads(x, omd[:, :18].float(), s.float(), w, b, go, st, one, one, 1)
+    if check_forward:
+        _check_forward(tag, y, x, omd[:, :n_off].float(), s.float(), w, b, st, pad, dl, dg)
+    _, mag = _corner_grads(x, omd[:, :n_off].float(), s.float(), w, b, go, st, pad, dl, dg)
     mag_om = torch.cat([mag["offset"], mag["mask"] * s * (1 - s)], 1)
     cw = cw64.detach()
     _check(f"{tag} om", cap.out.grad, om.grad, mag_om)
     # through torch's convolution backward applied to the om gradient: the bound carries |input| * bound(om), at 2e-5 as in test_gpu_autograd.py
-    mag_cw = torch.nn.grad.conv2d_weight(x.double().abs(), cw.shape, mag_om, stride, 1)
+    mag_cw = torch.nn.grad.conv2d_weight(x.double().abs(), cw.shape, mag_om, st, pad)
     _check(f"{tag} conv_offset_mask.weight", mg.conv_offset_mask.weight.grad, cw64.grad, mag_cw, rel=2e-5)
     _check(f"{tag} conv_offset_mask.bias", mg.conv_offset_mask.bias.grad, cb64.grad, mag_om.sum((0, 2, 3)), rel=2e-5)
     _check(f"{tag} weight", mg.weight.grad, w64.grad, mag["weight"])
     _check(f"{tag} bias", mg.bias.grad, b64.grad, mag["bias"])
     # x: the sampler's scatter (1e-5) plus the om gradient sent back through conv_offset_mask by torch (2e-5 of |cw|^T bound(om))
-    mag_x = mag["x"] + 2.0 * torch.nn.grad.conv2d_input(x.shape, cw.abs(), mag_om, stride, 1)
+    mag_x = mag["x"] + 2.0 * torch.nn.grad.conv2d_input(x.shape, cw.abs(), mag_om, st, pad)
     _check(f"{tag} x", xg.grad, x64.grad, mag_x)
     return xg.grad, mg.weight.grad, mg.bias.grad, omd
 

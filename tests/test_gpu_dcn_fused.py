@@ -25,14 +25,15 @@ def rnd(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=g) * scale
 
 
-def fused(x_nchw, om_nchw, w, bias, stride, pad, has_mask, relu, fmt=1, out_fmt=None):
-    """x [B, C, H, W], om [B, 2K (+K), Ho, Wo] (raw offsets, then mask LOGITS) -> fp32 [B*Ho*Wo, O] through the fused kernel."""
+def fused(x_nchw, om_nchw, w, bias, stride, pad, has_mask, relu, fmt=1, out_fmt=None, dil=1):
+    """x [B, C, H, W], om [B, 2K (+K), Ho, Wo] (raw offsets, then mask LOGITS) -> fp32 [B*Ho*Wo, O] through the fused kernel.  stride / pad / dil:
+    a number or a (height, width) pair."""
     B, C, H, W = x_nchw.shape
     O, _, kh, kw = w.shape
     x_pix = x_nchw.permute(0, 2, 3, 1).reshape(B * H * W, C).contiguous().to(DEV)
     om = om_nchw.permute(0, 2, 3, 1).reshape(-1, om_nchw.shape[1]).contiguous().to(DEV)
     packed, out_scale = ops.conv_pack_weights(w.to(DEV), tile_n=128, fmt=fmt)
-    pl = ops.deform_conv_fused_planar(x_pix, B, H, W, C, om, packed, out_scale, None if bias is None else bias.to(DEV), O, (kh, kw), stride, pad, 1,
+    pl = ops.deform_conv_fused_planar(x_pix, B, H, W, C, om, packed, out_scale, None if bias is None else bias.to(DEV), O, (kh, kw), stride, pad, dil,
                                       has_mask=has_mask, relu=relu, fmt=fmt, out_fmt=out_fmt)
     return ops.planes_to_f32(pl).cpu()
 
