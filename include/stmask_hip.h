@@ -575,6 +575,43 @@ typedef struct stm_head_layout {
 int stm_head_assemble_f32(const float* const* small, const float* const* trk, const stm_head_layout* layout, float* conf,
                           float* loc, float* mask, float* track, float* centerness, stm_stream_t stream);
 
+/* ---- the same head at the positions that pass the class threshold only (csrc/head_sparse.hip; stmask_amd/planar.py, sparse head) ----
+ * generate_candidate (TF_utils.py:54-82) keeps a prior only where max(softmax(conf)[1:]) > eval_conf_thresh, and loc / centerness /
+ * mask_coeff / track are read at kept priors only: the class branch runs densely, the other branches on the 9 x 9 neighbourhoods of the
+ * kept positions.  All launches are sized by a capacity and steered by a control block of 8 ints on the device, so that they can live in
+ * a captured graph: ctl[0] positions found, [1] positions listed (0 after an overflow), [2] patches covered (listed, rounded up to 256,
+ * at most the capacity; the extra ones are zeros), [3] / [4] pixel gates of the patch launches (= [2] * patch_pixels_a / _b), [5] pixel
+ * gate of the dense launches of the other branches (n_pixels after an overflow, else 0), [6] overflow flag.
+ *
+ * stm_conv_set_pixel_gate: the calling thread's NEXT stm_conv2d_planar_* / stm_conv2d_planar_kxr_f32 launch reads *valid_pixels on the
+ * device, and its pixel tiles that start at or past that pixel leave at once (no split-K then).  One-shot: the launch call clears it.
+ * The kxr kernel takes any gate on single-level launches; on multi-level ones 0 and >= all pixels are exact.
+ *
+ * stm_head_candidates_f32: cls_logits[k] [pixels][ld] = class logits of kernel shape k over the concatenated levels (level l: B images of
+ * lvl_h[l] x lvl_w[l] from pixel lvl_start[l]; host arrays).  A pixel is listed when one of its K priors passes the candidate pass's own
+ * test (stm_detect_cc_logits_f32, same arithmetic) -- and so is, for a kept prior with row r = pixel * K + k of its level, the pixel
+ * r % (h w): centerness [B,N,1] is in (level, k, pixel) order, so the centerness row r that the detection stage reads with the prior is
+ * that pixel's.  Each pixel once; flags [pixels] ints of scratch; list [capacity] in order of arrival, ctl as above.
+ * stm_head_patch_gather: side x side neighbourhoods of the listed pixels into dst_planes [n_planes][slabs][capacity * side^2][32]
+ * (2-byte elements) from the level maps src_planes [n_planes][slabs][src_np][32], zeros outside a map.  Patches [ctl[1], ctl[2]) are written as zeros.
+ * stm_head_patch_mask: zeroes, in place, the pixels of the listed patches that lie outside their level's map.
+ * stm_head_assemble_sparse_f32: stm_head_assemble_f32's outputs -- conf for every prior from cls_logits; loc / mask / track / centerness
+ * at the K rows of each listed pixel from small[k] [.][small_ld] (centerness + bbox at column 0, mask at column group_pad) and trk[k], row
+ * i * row_mul + row_add for list entry i; after an overflow at every row from small_dense[k] / trk_dense[k] (one row per pixel). */
+void stm_conv_set_pixel_gate(const int* valid_pixels);
+int stm_head_candidates_f32(const float* const* cls_logits, int K, int ld, int n_cls, float conf_thresh, int capacity,
+                            int patch_pixels_a, int patch_pixels_b, int n_levels, int B, const int* lvl_start, const int* lvl_h,
+                            const int* lvl_w, int* flags, int* list, int* ctl, stm_stream_t stream);
+int stm_head_patch_gather(const void* src_planes, long long src_np, void* dst_planes, int side, int n_planes, int slabs,
+                          int capacity, int n_levels, int B, const int* lvl_start, const int* lvl_h, const int* lvl_w, const int* list,
+                          const int* ctl, stm_stream_t stream);
+int stm_head_patch_mask(void* planes, int side, int n_planes, int slabs, int capacity, int n_levels, int B, const int* lvl_start,
+                        const int* lvl_h, const int* lvl_w, const int* list, const int* ctl, stm_stream_t stream);
+int stm_head_assemble_sparse_f32(const float* const* cls_logits, int cls_ld, const float* const* small, const float* const* trk,
+                                 const float* const* small_dense, const float* const* trk_dense, const stm_head_layout* layout,
+                                 int row_mul, int row_add, const int* list, const int* ctl, int capacity, float* conf, float* loc,
+                                 float* mask, float* track, float* centerness, stm_stream_t stream);
+
 /* ---- deformable sampling into the planar format (row a1, inference graph) ------------------------------------------
  * The im2col half of dcn_v2.DCN (backbone.py:20-26,45) for activations that already live in the planar graph: x is fp32
  * NHWC [B,H,W,C] (C = 128 / 256 / 512), offset_mask the raw conv_offset_mask output pixel-major [B*Ho*Wo, om_ld] (18

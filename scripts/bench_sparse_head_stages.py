@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""The shared head's stages timed alone on the benchmark's tensors (32 clips, eager, HIP events, nothing beside them): the eager trunk with
+the dense and the sparse head, then each launch group of PlanarGraph._sparse_head and of the dense head (best of four passes).
+Wrote profiles/sparse_head_stages.txt.   usage: bench_sparse_head_stages.py > profiles/sparse_head_stages.txt"""
+import os, sys
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+import torch
+import bench
+from benchlib.runner import build_net, Runner
+from stmask_amd import ops, planar
+from stmask_amd.planar import _planes_dtype
+
+args = bench.parse_args([])
+B = 32
+dev = torch.device("cuda:0")
+net = build_net(args, dev)
+r = Runner(args, dev, 0, 1, B, net=net)
+x = r.frames_t[1]
+pg = net._planar
+sizes = [(48, 80), (24, 40), (12, 20), (6, 10), (3, 5)]
+ntot = sum(B * h * w for h, w in sizes)
+
+# whole trunk, eager, dense vs sparse
+def trunk(sparse, n=8):
+    pg.sparse = sparse
+    with torch.no_grad():
+        for _ in range(3):
+            net.forward_single(x)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            net.forward_single(x)
+        e1.record()
+    torch.cuda.synchronize()
+    pg.sparse = None
+    return e0.elapsed_time(e1) / n
+thr = net.cfg.eval_conf_thresh
+print("trunk eager ms: dense", trunk(None), "sparse", trunk((thr, None)), "dense", trunk(None), "sparse", trunk((thr, None)), flush=True)
+
+# stages of the sparse head on the `up` planes of this frame
+cap = {}
+orig_up = pg.up.__call__
+ups = []
+class Grab:
+    pass
+orig = planar.PlanarConv.__call__
+def grab(self, *a, **kw):
+    y = orig(self, *a, **kw)
+    if self is pg.up:
+        ups.append(y)
+    return y
+planar.PlanarConv.__call__ = grab
+with torch.no_grad():
+    net.forward_single(x)
+planar.PlanarConv.__call__ = orig
+up = ups[0][1] if isinstance(ups[0], tuple) else ups[0]
+lv = ("levels", B, sizes)
+t1c, t1r, t2c, t2r, cls_l, small_l = pg._build_sparse()
+trk_l = [t for _, t in pg.finals]
+cw, P = 256, 64
+NP, pdt = _planes_dtype(pg.fmt)
+capn = pg.sparse_capacity(B, sizes)
+head = pg.head
+stages = []
+def ev():
+    e = torch.cuda.Event(enable_timing=True); e.record(); return e
+def run_once(record):
+    marks = [("start", ev())]
+    def m(name):
+        marks.append((name, ev()))
+    xx = t1c(up, lv, out="planes", splitk=False); m("t1 class")
+    xx = t2c(xx, lv, out="planes", splitk=False); m("t2 class")
+    cls = [c(xx, lv, out="f32", splitk=False, kxr=True) for c in cls_l]; m("class output layers x3")
+    lst, ctl = ops.head_candidates(cls, head.num_classes, thr, capn, 49, 25, B, sizes); m("candidates")
+    patch = ops.head_patch_gather(up, torch.empty(NP, cw // 32, capn * 81, 32, device=dev, dtype=pdt), 9, capn, B, sizes, lst, ctl); m("gather 9x9")
+    x1 = torch.empty(NP, 3 * cw // 32, capn * 49, 32, device=dev, dtype=pdt)
+    t1r(patch, ("img", capn, 9, 9), out="planes", out_planes=x1, window=(0, 0, 7, 7, 0, 0, 7, 7), gate=(ctl, 3)); m("t1 patches")
+    ops.head_patch_mask(x1, 7, capn, B, sizes, lst, ctl); m("mask 7")
+    xq = torch.empty(NP, 3 * cw // 32, capn * 25, 32, device=dev, dtype=pdt)
+    t2r(x1, ("img", capn, 7, 7), out="planes", out_planes=xq, window=(0, 0, 5, 5, 0, 0, 5, 5), gate=(ctl, 4)); m("t2 patches")
+    ops.head_patch_mask(xq, 5, capn, B, sizes, lst, ctl); m("mask 5")
+    ql = ("levels", capn, [(5, 5)])
+    small = [c(xq, ql, out="f32", gate=(ctl, 4), kxr=True) for c in small_l]; m("small patches x3")
+    trk = [c(xq, ql, out="f32", x_ch_off=2 * cw, gate=(ctl, 4)) for c in trk_l]; m("trk patches x3")
+    gd = (ctl, 5)
+    xx = t1r(up, lv, out="planes", gate=gd); xx = t2r(xx, lv, out="planes", gate=gd); m("dense towers (empty)")
+    small_d = [c(xx, lv, out="f32", gate=gd, kxr=True) for c in small_l]
+    trk_d = [c(xx, lv, out="f32", x_ch_off=2 * cw, gate=gd) for c in trk_l]; m("dense outputs (empty)")
+    out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P, 25, 12, lst, ctl, capn); m("assemble")
+    torch.cuda.synchronize()
+    if record:
+        stages.append([(marks[i][0], marks[i - 1][1].elapsed_time(marks[i][1])) for i in range(1, len(marks))])
+        return ctl.tolist()
+with torch.no_grad():
+    for i in range(6):
+        c = run_once(i >= 2)
+print("ctl", c)
+for j, (name, _) in enumerate(stages[0]):
+    print("%-28s %8.3f ms" % (name, min(s[j][1] for s in stages)))
+print("sum", sum(min(s[j][1] for s in stages) for j in range(len(stages[0]))))
+# dense head stages
+dstages = []
+def dense_once(record):
+    marks = [("start", ev())]
+    def m(name):
+        marks.append((name, ev()))
+    t1 = pg.tower1(up, lv, out="planes"); m("tower1")
+    t2 = pg.tower2(t1, lv, out="planes"); m("tower2")
+    outs = [(s(t2, lv, out="f32"), t(t2, lv, out="f32", x_ch_off=3 * cw)) for s, t in pg.finals]; m("outputs")
+    ops.head_assemble([o[0] for o in outs], [o[1] for o in outs], B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P); m("assemble")
+    torch.cuda.synchronize()
+    if record:
+        dstages.append([(marks[i][0], marks[i - 1][1].elapsed_time(marks[i][1])) for i in range(1, len(marks))])
+with torch.no_grad():
+    for i in range(6):
+        dense_once(i >= 2)
+for j, (name, _) in enumerate(dstages[0]):
+    print("dense %-22s %8.3f ms" % (name, min(s[j][1] for s in dstages)))
+print("dense sum", sum(min(s[j][1] for s in dstages) for j in range(len(dstages[0]))))

@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "stm_deform_conv_fused_planar_supported", "stm_deform_conv_fused_planar_f32", "stm_fast_nms_batched_workspace_bytes", "stm_fast_nms_batched_f32", "stm_rle_strings_host",
     "stm_preprocess_u8_multi_f32", "stm_render_workspace_bytes", "stm_render_overlay_u8",
     "stm_deform_col2im_f32", "stm_deform_col2im_coord_f32", "stm_roi_align_backward_f32", "stm_corr_backward_f32",
+    "stm_conv_set_pixel_gate", "stm_head_candidates_f32", "stm_head_patch_gather", "stm_head_patch_mask", "stm_head_assemble_sparse_f32",
 ]
 
 

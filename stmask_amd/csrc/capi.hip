@@ -31,6 +31,17 @@ extern "C" size_t stm_struct_bytes(int which)
     }
 }
 
+// One-shot pixel gate of the calling thread's next planar convolution launch (stm_conv_set_pixel_gate): set by the caller, taken -- read and
+// cleared -- by the launch function at its entry.
+static thread_local const int* g_pixel_gate = nullptr;
+extern "C" void stm_conv_set_pixel_gate(const int* valid_pixels) { g_pixel_gate = valid_pixels; }
+const int* stm_internal_take_pixel_gate()
+{
+    const int* g = g_pixel_gate;
+    g_pixel_gate = nullptr;
+    return g;
+}
+
 static std::atomic<int> g_env_gen{0};
 int stm_env_generation() { return g_env_gen.load(std::memory_order_relaxed); }
 int stm_env_int_uncached(const char* name, int dflt)

@@ -111,6 +111,9 @@ struct PlanarArgs {
     // window launches (stm_conv_geom.win_w > 0): the launch computes a Ho x Wo window of every output image; output pixel (b, oy, ox) is row
     // b * win_hw + oy * win_w + ox + win_off of the output tensors
     int win_w, win_hw, win_off;
+    // gated launches (stm_conv_set_pixel_gate): a device int read by every workgroup -- pixel tiles that start at or past it leave before
+    // they stage anything, so a launch sized for a capacity costs what its valid pixels cost.  null = every tile runs
+    const int* m_gate;
 };
 // several window launches in ONE grid (CLS instantiation; stm_conv2d_planar_windows_f32): class c = tiles [tile0, next tile0) with its own
 // weights, sub-kernel, window and pixel count -- they replace wp / kh / kw / ph / pw / Ho / Wo / M / slabs / win_off per tile.  (A type of
@@ -404,8 +407,12 @@ __global__ __launch_bounds__(512, 1) void conv_planar_kernel(const typename std:
 
     int tiles_ = a_in.m_tiles * a_in.n_tiles * a_in.splitk;
     if constexpr (CLS) tiles_ = a_in.cls_tiles;
+    // gated launch (never split-K, never regrouped): the tile map below is built over the VALID pixel tiles, so that every XCD gets its share of
+    // them -- over the launch's own tile count the XCDs whose runs lie past the gate would stand idle
+    else if (a_in.m_gate) tiles_ = min(a_in.m_tiles, (*a_in.m_gate + BM - 1) / BM) * a_in.n_tiles;
     const int tiles = tiles_;
     const int per_xcd = (tiles + 7) >> 3;
+    if (!CLS && a_in.m_gate && (int)(blockIdx.x >> 3) >= per_xcd) return;      // (gated: the grid is larger than the map; ids past an XCD's run are not its neighbour's tiles)
     int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     // Which tiles share an XCD at one time decides what its 4-MB L2 must fetch: the 32 workgroups an XCD runs together are 32 / n_tiles pixel
     // tiles x all n_tiles channel tiles in the plain order, i.e. every K-slab of EVERY channel tile's weights for only 4 pixel tiles at
@@ -458,6 +465,7 @@ __global__ __launch_bounds__(512, 1) void conv_planar_kernel(const typename std:
     const int nt = tile - mt * a.n_tiles;
     const int m0 = mt * BM;
     if (m0 >= a.M) return;                           // (pixel tiles the regrouped tile map pads the grid with)
+    if (a.m_gate && m0 >= *a.m_gate) return;         // (gated launch: the tile lies past the valid pixels)
     const int s_begin = ksp * a.kslabs, s_end = min(a.slabs, s_begin + a.kslabs);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -950,8 +958,10 @@ __global__ __launch_bounds__(512, 1) void conv_planar_kx3_kernel(const typename 
             if (i < a_in.n_cls && logical >= a_in.cls[i].tile0) cls_c = i;
         logical -= a_in.cls[cls_c].tile0;
     } else {
-        const int tiles = a_in.m_tiles * n_tiles_;
+        // (gated launch: the tile map over the valid pixel tiles, as in conv_planar_kernel)
+        const int tiles = (a_in.m_gate ? min(a_in.m_tiles, (*a_in.m_gate + BM - 1) / BM) : a_in.m_tiles) * n_tiles_;
         const int per_xcd = (tiles + 7) >> 3;
+        if (a_in.m_gate && (int)(blockIdx.x >> 3) >= per_xcd) return;            // (gated: ids past an XCD's run are not its neighbour's tiles)
         logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
         if (logical >= tiles) return;
     }
@@ -967,6 +977,7 @@ __global__ __launch_bounds__(512, 1) void conv_planar_kx3_kernel(const typename 
     const int mt = n_tiles_ == 1 ? logical : (n_tiles_ == 2 ? logical >> 1 : (n_tiles_ == 4 ? logical >> 2 : logical / n_tiles_));
     const int nt = logical - mt * n_tiles_;
     const int m0 = mt * BM;
+    if (a.m_gate && m0 >= *a.m_gate) return;         // (gated launch: the tile lies past the valid pixels)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 3, wn = wave >> 2;
@@ -2098,6 +2109,7 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
                        int relu, void* workspace, size_t workspace_bytes, stm_stream_t stream, const DualSrc* dual, const WinSet* wset)
 {
     const char* who = dual ? "stm_conv2d_planar_dual_f32" : "stm_conv2d_planar_f32";
+    const int* const gate = stm_internal_take_pixel_gate();      // (one-shot: consumed by this call whatever it returns)
     STM_REQUIRE(x_planes && packed_weight && (out_f32 || out_planes || (wset && wset->pool)), STM_ENULL,
                 "%s: x_planes/packed_weight and at least one output must be non-NULL", who);
     STM_REQUIRE(g, STM_ENULL, "%s: geometry is NULL", who);
@@ -2191,6 +2203,8 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
     STM_REQUIRE(g->planes == want_planes || (a.fmt == 0 && g->planes == 2), STM_EINVAL, "%s: format %d has %d planes (planes = %d)", who, a.fmt,
                 want_planes, g->planes);
     a.splitk = 1; a.kslabs = a.slabs; a.partial = nullptr; a.ldp = a.n_tiles * bn;
+    a.m_gate = gate;
+    STM_REQUIRE(!gate || !wset, STM_EUNSUPPORTED, "%s: window sets take no pixel gate", who);
     a.xp2 = nullptr; a.x2_pstride = 0; a.plane2_bytes = 0; a.c1_slabs = a.slabs; a.x2_np = 0; a.H2 = a.W2 = 0; a.s2 = 1;
     if (dual) {
         const int64_t in2 = (int64_t)g->B * dual->H2 * dual->W2;
@@ -2215,6 +2229,7 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
     bool full = cout_g % 64 == 0;
     for (int gi = 0; gi < groups && gi < 8; ++gi) full = full && a.group_real[gi] == cout_g;
     auto plan_splitk = [&](int tiles) {
+        if (a.m_gate) return;         // (the finishing kernel knows no gate, and a gated launch is sized for a capacity, not for its work)
         int sk = tn.splitk;
         if (sk <= 0) {
             sk = 1;
@@ -2352,7 +2367,7 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
     a.m_tiles = stm_cdiv(M, CV_BM * mg);
     plan_splitk(a.m_tiles * a.n_tiles);
     // regrouped tile map (nsub > 0): whole groups of 32 / nsub pixel tiles -- the padding tiles leave at once
-    a.nsub = ((tn.nsub == 2 || tn.nsub == 4) && a.splitk == 1 && a.n_tiles > tn.nsub && a.n_tiles % tn.nsub == 0 && g->groups == 1 &&
+    a.nsub = ((tn.nsub == 2 || tn.nsub == 4) && a.splitk == 1 && !a.m_gate && a.n_tiles > tn.nsub && a.n_tiles % tn.nsub == 0 && g->groups == 1 &&
               a.m_tiles >= 4 * (32 / tn.nsub)) ? tn.nsub : 0;
     if (a.nsub) a.m_tiles = stm_cdiv(a.m_tiles, 32 / a.nsub) * (32 / a.nsub);
     const int tiles = a.m_tiles * a.n_tiles * a.splitk;

@@ -80,6 +80,8 @@ struct KxrArgs {
     int* range_flag;
     int n_lvl;
     int lvl_start[9], lvl_h[8], lvl_w[8];
+    const int* m_gate;     // gated launch (stm_conv_set_pixel_gate): tiles that start at or past *m_gate pixels are not run; null = all
+    int M;                 // pixels of the launch
 };
 
 typedef __attribute__((address_space(3))) void* lds_ptr;
@@ -117,6 +119,31 @@ __device__ __forceinline__ void kxr_body(const KxrArgs& a, const KxrJob& jb, int
     static_assert(BM + HALO <= XROWS - 1, "the always-zero row must exist");
     static_assert(D >= 2 && D * BUF <= KX_LDS_MAX && (D - 2) * NPD <= 63, "ring does not fit");
 
+    // gated launch: the tile map (id -> tile (id & 7) * per_xcd + (id >> 3), one contiguous run of tiles per XCD) is built over the tiles below the
+    // gate, so that every XCD gets its share of them; a workgroup's ids are a multiple of 8 apart, so its tiles ascend and the gate cuts its
+    // sequence short.  A gate of M or more runs everything (the tiles of a multi-level launch are counted per level, so only "nothing" and
+    // "everything" are exact there: single-level launches take any gate)
+    // (the gated map's per_xcd is recomputed where a tile is decoded, once per tile: kept live through the ring it cost scalar registers the loop
+    // does not have)
+    auto gated_per_xcd = [&]() {
+        int per = jb.per_xcd;
+        if (a.m_gate) {
+            const int gate = *a.m_gate;
+            if (gate < a.M) per = ((gate + BM - 1) / BM + 7) >> 3;
+        }
+        return per;
+    };
+    if (a.m_gate) {
+        const int gate = *a.m_gate;
+        if (gate < a.M) {
+            const int gt = (gate + BM - 1) / BM;                 // tiles below the gate
+            const int per = (gt + 7) >> 3;
+            const int j0 = tile_first >> 3, st = tile_step >> 3;
+            const int jend = min(per, gt - (tile_first & 7) * per);     // this XCD's run: tiles [x per, x per + jend)
+            n_seq = j0 >= jend ? 0 : min(n_seq, (jend - j0 + st - 1) / st);
+        }
+        if (n_seq <= 0) return;
+    }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int S = a.cslabs * a.kh;
@@ -128,7 +155,7 @@ __device__ __forceinline__ void kxr_body(const KxrArgs& a, const KxrJob& jb, int
     // map gives each XCD -- each L2 -- a contiguous run of the job's tiles, so the rows a tile's ky stages share with its neighbours are
     // filled into one L2 once.  Ids of the padding map to tiles behind the last level: every access of such a tile is out of range.
     auto tile_geo = [&](int id) {
-        const int tile = (id & 7) * jb.per_xcd + (id >> 3);
+        const int tile = (id & 7) * gated_per_xcd() + (id >> 3);
         int lvl = 0;
 #pragma unroll
         for (int l = 1; l < 8; ++l)
@@ -548,6 +575,7 @@ extern "C" int stm_conv2d_planar_kxr_f32(const void* x_planes, const void* packe
                                          const stm_conv_geom* g, int relu, stm_stream_t stream)
 {
     const char* who = "stm_conv2d_planar_kxr_f32";
+    const int* const gate = stm_internal_take_pixel_gate();      // (one-shot: consumed by this call whatever it returns)
     STM_REQUIRE(x_planes && packed_weight && (out_f32 || out_planes), STM_ENULL, "%s: x_planes/packed_weight and at least one output must be non-NULL", who);
     KxrPlan pl;
     if (!kxr_plan(g, &pl, who)) return STM_EINVAL;
@@ -614,6 +642,7 @@ extern "C" int stm_conv2d_planar_kxr_f32(const void* x_planes, const void* packe
                 a.out_fmt, g->fmt);
     a.out_scale = g->out_scale > 0.0f ? g->out_scale : 1.0f;
     a.range_flag = stm_internal_range_flag();
+    a.m_gate = gate; a.M = (int)M;
     (void)nc_max;
     if (g->fmt == 1) return g->kw == 3 ? kxr_launch<3, 2>(a, stream) : kxr_launch<5, 2>(a, stream);
     return g->kw == 3 ? kxr_launch<3, 1>(a, stream) : kxr_launch<5, 1>(a, stream);

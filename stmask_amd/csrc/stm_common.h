@@ -43,6 +43,8 @@ int stm_env_int_uncached(const char* name, int dflt);
 int* stm_internal_range_flag();
 long long stm_internal_fused_dcn_launches();   // dcn_fused.hip: launches of dcn_fused_kernel (stm_debug_launch_count(1))   // conv_bf16x.hip: the device flag registered with stm_planar_set_range_flag (or null)
 
+const int* stm_internal_take_pixel_gate();      // capi.hip: the gate set by stm_conv_set_pixel_gate for this thread's next convolution launch (cleared)
+
 static inline hipStream_t stm_hs(stm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 static inline int stm_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

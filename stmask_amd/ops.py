@@ -816,7 +816,7 @@ def conv_kxr_supported(O, C, kh, kw, stride, padding, groups, group_cout, fmt, m
     return True
 
 
-def conv_pack_weights_kxr(weight, geom):
+def conv_pack_weights_kxr(weight, geom, wscale=None):
     """OIHW fp32 weights (grouped layers: group g = rows [g * O / groups, ...)) -> the image stm_conv2d_planar_kxr_f32 streams;
     geom: a ConvGeom with C (per group), Cout, kh, kw, groups, group_cout, fmt set.  Returns (packed, 1 / wscale)."""
     _dev(weight)
@@ -825,9 +825,8 @@ def conv_pack_weights_kxr(weight, geom):
     if nbytes == 0:
         raise StmError("conv_pack_weights_kxr: " + _lib.lib().stm_last_error_string().decode(errors="replace"))
     packed = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
-    import math
-    wmax = float(weight.abs().max())
-    wscale = 2.0 ** (10 - math.floor(math.log2(wmax))) if wmax > 0 else 1.0
+    if wscale is None:          # (given: a layer that holds some of the groups of another one and must round its weights as that one does)
+        wscale = _pow2_wscale(weight)
     check(_lib.lib().stm_conv_pack_weights_kxr_f32(_p(weight), _p(packed), ctypes.byref(geom), c_f(wscale), _stream()),
           "stm_conv_pack_weights_kxr_f32")
     return packed, 1.0 / wscale
@@ -1323,6 +1322,105 @@ def head_assemble(small, trk, B, sizes, n_cls, mask_dim, embed_dim, group_pad):
     tp = (ctypes.c_void_p * 4)(*([t.data_ptr() for t in trk] + [0] * (4 - K)))
     check(_lib.lib().stm_head_assemble_f32(sp, tp, ctypes.byref(L), _p(conf), _p(loc), _p(mask), _p(track), _p(cen), _stream()),
           "stm_head_assemble_f32")
+    return conf, loc, mask, track, cen
+
+
+# ---- sparse head (csrc/head_sparse.hip): control block indices as the header lists them
+HEAD_CTL_RAW, HEAD_CTL_N, HEAD_CTL_FILL, HEAD_CTL_GATE_A, HEAD_CTL_GATE_B, HEAD_CTL_DENSE, HEAD_CTL_OVERFLOW, HEAD_CTL_INTS = 0, 1, 2, 3, 4, 5, 6, 8
+
+
+def conv_set_pixel_gate(ctl, index):
+    """The next planar convolution launch of this thread runs only the pixel tiles below the device int ctl[index] (stm_conv_set_pixel_gate)."""
+    _lib.lib().stm_conv_set_pixel_gate(ctypes.c_void_p(ctl.data_ptr() + 4 * index))
+
+
+def _level_arrays(B, sizes):
+    n = len(sizes)
+    st, hh, ww = (ctypes.c_int * 9)(), (ctypes.c_int * 8)(), (ctypes.c_int * 8)()
+    start = 0
+    for l, (h, w) in enumerate(sizes):
+        st[l], hh[l], ww[l] = start, h, w
+        start += B * h * w
+    st[n] = start
+    return n, st, hh, ww, start
+
+
+def _ptr4(ts):
+    return (ctypes.c_void_p * 4)(*([t.data_ptr() for t in ts] + [0] * (4 - len(ts))))
+
+
+def head_candidates(cls_logits, n_cls, conf_thresh, capacity, patch_pixels_a, patch_pixels_b, B, sizes):
+    """stm_head_candidates_f32: cls_logits = per-kernel-shape [pixels, ld] fp32 class logits over the concatenated levels -> (list int32 [capacity] of
+    the pixels whose rows the detection stage reads for the priors that pass generate_candidate's test, control block int32 [8]: see
+    include/stmask_hip.h)."""
+    _dev(*cls_logits)
+    n_px, ld = cls_logits[0].shape
+    n, st, hh, ww, total = _level_arrays(B, sizes)
+    for t in cls_logits:
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (n_px, ld) or n_px != total:
+            raise StmError("head_candidates: inputs must be contiguous fp32 matrices over all level pixels")
+    dev = cls_logits[0].device
+    lst = torch.empty(capacity, dtype=torch.int32, device=dev)
+    ctl = torch.empty(HEAD_CTL_INTS, dtype=torch.int32, device=dev)
+    flags = torch.empty(n_px, dtype=torch.int32, device=dev)
+    check(_lib.lib().stm_head_candidates_f32(_ptr4(cls_logits), c_i(len(cls_logits)), c_i(ld), c_i(n_cls), c_f(conf_thresh), c_i(capacity),
+                                             c_i(patch_pixels_a), c_i(patch_pixels_b), c_i(n), c_i(B), st, hh, ww, _p(flags), _p(lst), _p(ctl), _stream()),
+          "stm_head_candidates_f32")
+    return lst, ctl
+
+
+def head_patch_gather(src, dst, side, capacity, B, sizes, lst, ctl):
+    """stm_head_patch_gather: side x side neighbourhoods of the listed pixels from the level maps (zeros outside a map), planes [P, S, pixels, 32] in and [P, S, capacity * side^2, 32] out."""
+    _dev(src, dst)
+    if (src.dim() != 4 or dst.dim() != 4 or src.shape[3] != 32 or src.element_size() != 2 or dst.dtype != src.dtype or not src.is_contiguous()
+            or not dst.is_contiguous() or tuple(dst.shape) != (src.shape[0], src.shape[1], capacity * side * side, 32)):
+        raise StmError(f"head_patch_gather: planes {tuple(src.shape)} -> {tuple(dst.shape)} do not fit capacity {capacity}, side {side}")
+    n, st, hh, ww, _ = _level_arrays(B, sizes)
+    check(_lib.lib().stm_head_patch_gather(_p(src), ctypes.c_longlong(src.shape[2]), _p(dst), c_i(side), c_i(src.shape[0]), c_i(src.shape[1]),
+                                           c_i(capacity), c_i(n), c_i(B), st, hh, ww, _p(lst), _p(ctl), _stream()), "stm_head_patch_gather")
+    return dst
+
+
+def head_patch_mask(planes, side, capacity, B, sizes, lst, ctl):
+    """stm_head_patch_mask: zero, in place, the pixels of the listed patches that lie outside their level's map."""
+    _dev(planes)
+    if planes.dim() != 4 or planes.shape[3] != 32 or planes.element_size() != 2 or not planes.is_contiguous() or planes.shape[2] != capacity * side * side:
+        raise StmError(f"head_patch_mask: planes {tuple(planes.shape)} do not fit capacity {capacity}, side {side}")
+    n, st, hh, ww, _ = _level_arrays(B, sizes)
+    check(_lib.lib().stm_head_patch_mask(_p(planes), c_i(side), c_i(planes.shape[0]), c_i(planes.shape[1]), c_i(capacity), c_i(n), c_i(B), st, hh, ww,
+                                         _p(lst), _p(ctl), _stream()), "stm_head_patch_mask")
+    return planes
+
+
+def head_assemble_sparse(cls_logits, small, trk, small_dense, trk_dense, B, sizes, n_cls, mask_dim, embed_dim, group_pad, row_mul, row_add, lst, ctl,
+                         capacity):
+    """stm_head_assemble_sparse_f32 -> (conf, loc, mask, track, centerness) as head_assemble; loc / mask / track / centerness hold values at the
+    rows of the listed pixels only (every row after an overflow), the other rows are NOT written."""
+    _dev(*cls_logits, *small, *trk, *small_dense, *trk_dense)
+    K = len(cls_logits)
+    L = _lib.HeadLayout()
+    L.B, L.K, L.n_levels, L.n_cls, L.mask_dim, L.embed_dim, L.group_pad = B, K, len(sizes), n_cls, mask_dim, embed_dim, group_pad
+    L.small_ld, L.trk_ld = small[0].shape[-1], trk[0].shape[-1]
+    start = 0
+    for l, (h, w) in enumerate(sizes):
+        L.lvl_start[l], L.lvl_hw[l] = start, h * w
+        start += B * h * w
+    N = K * sum(h * w for h, w in sizes)
+    for t in list(cls_logits) + list(small_dense) + list(trk_dense):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[0] != start:
+            raise StmError("head_assemble_sparse: dense inputs must be contiguous fp32 matrices over all level pixels")
+    for t, d in zip(list(small) + list(trk), list(small_dense) + list(trk_dense)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[0] < capacity * row_mul or t.shape[-1] != d.shape[-1]:
+            raise StmError("head_assemble_sparse: patch inputs must be contiguous fp32 matrices of capacity * row_mul rows, as wide as the dense ones")
+    dev = cls_logits[0].device
+    conf = torch.empty(B, N, n_cls, device=dev)
+    loc = torch.empty(B, N, 4, device=dev)
+    mask = torch.empty(B, N, mask_dim, device=dev)
+    track = torch.empty(B, N, embed_dim, device=dev)
+    cen = torch.empty(B, N, 1, device=dev)
+    check(_lib.lib().stm_head_assemble_sparse_f32(_ptr4(cls_logits), c_i(cls_logits[0].shape[-1]), _ptr4(small), _ptr4(trk), _ptr4(small_dense), _ptr4(trk_dense),
+                                                  ctypes.byref(L), c_i(row_mul), c_i(row_add), _p(lst), _p(ctl), c_i(capacity), _p(conf), _p(loc), _p(mask),
+                                                  _p(track), _p(cen), _stream()), "stm_head_assemble_sparse_f32")
     return conf, loc, mask, track, cen
 
 

@@ -214,6 +214,8 @@ class BatchedClipPipeline:
         self._graph_next = 0
         self._graph_warm = 0
         self._graph_ws = []          # per slot: the workspaces its captured graph writes into (kept alive here)
+        self._graph_sparse = None    # sparse-head setting (threshold, capacity) the slots were captured with: baked into the graphs
+        self._sparse_now = None
         self._graph_planes = None    # plane format of the net's inference graph when the slots were captured (a net may serve several pipelines: _trunk)
         self._idle_masks = {}        # inactive-slot pattern -> device bool [B] (see step's `active`)
         self._idle_dev = None
@@ -222,6 +224,25 @@ class BatchedClipPipeline:
         # (the best-scoring ones: Fast NMS returns them sorted) and at most n tracked instances per clip (an unmatched detection
         # opens a new track only while the clip holds fewer).  0 = the reference's behaviour.
         self.max_instances = 0
+        # Sparse head (planar.PlanarGraph._sparse_head, csrc/head_sparse.hip): the bbox / mask / track branches of the shared head run only at
+        # the positions with a prior that passes eval_conf_thresh -- the rows the detection stage reads (generate_candidate, TF_utils.py:54-82).
+        # Results are the dense head's, bit for bit, at every row that is read.  STM_SPARSE_HEAD=0 keeps the dense head (A/B runs).  The
+        # setting (head form, eval_conf_thresh, capacity) is baked into a captured trunk graph: when it changes, the graphs are captured again.
+        self.sparse_head = os.environ.get("STM_SPARSE_HEAD", "1") != "0"
+        # batches from which it is on: a single-stream step is a chain of launches bound by their latency, and the sparse head has 22 more of them
+        # (frames/s dense / sparse at 1 clip 812-817 / 713-733, 2 clips 1 073-1 075 / 1 058-1 064, 4 clips 1 301-1 305 / 1 321-1 324, 8 clips
+        # 1 435 / 1 543: DESIGN.md section 6).  STM_SPARSE_MIN_CLIPS for A/B runs
+        self.sparse_min_clips = int(os.environ.get("STM_SPARSE_MIN_CLIPS", "4"))
+        self.sparse_capacity = None  # positions per step the patch launches are sized for (None: PlanarGraph.sparse_capacity; tests set a small one)
+
+    def _sparse_setting(self, pg):
+        """What PlanarGraph.run gets as `sparse` for this pipeline's trunks: Detect_TF with cross-class Fast NMS is the consumer whose reads are known
+        to be the kept rows only (ops.detect_cc + ops.gather_detections); every other path keeps the dense head."""
+        if not (self.sparse_head and self.B >= self.sparse_min_clips and self.tf and pg is not None and pg.sparse_supported()):
+            return None
+        if not getattr(self.net.Detect_TF, "use_cross_class_nms", True):
+            return None
+        return (float(self.cfg.eval_conf_thresh), self.sparse_capacity)
 
     # -- stage helpers ------------------------------------------------------------------------------------------------
     def _shift_prev(self, P4, T2S, proto, dev):
@@ -302,6 +323,17 @@ class BatchedClipPipeline:
         return 2 * self.prefetch_depth + 2
 
     def _trunk(self, frames):
+        pg = getattr(self.net, "_planar", None)
+        if pg is None or not hasattr(pg, "sparse"):
+            return self._trunk_run(frames)
+        self._sparse_now = self._sparse_setting(pg)
+        before, pg.sparse = pg.sparse, self._sparse_now
+        try:
+            return self._trunk_run(frames)
+        finally:
+            pg.sparse = before
+
+    def _trunk_run(self, frames):
         """forward_single(frames).  With use_graph the ~110 launches of the trunk (every one a Python -> ctypes call: ~25 us of
         host time each, i.e. more than the GPU needs for them at 1-8 clips) are captured once per slot into a HIP graph and
         replayed: one copy of the frames into the slot's static input + one graph launch per step.  Slots in round-robin,
@@ -315,7 +347,7 @@ class BatchedClipPipeline:
                 and ops._im2col_timing is None):
             return net.forward_single(frames)
         planes = getattr(net, "_planar_planes", None)
-        if self._graphs and self._graph_planes != planes:
+        if self._graphs and (self._graph_planes != planes or self._graph_sparse != self._sparse_now):
             # another pipeline on the same net fell back to bf16x3 planes (_fall_back swaps the net's inference graph): this pipeline's captured trunks
             # still replay the fp16 graph they were captured from -- drop them (with their private pools) and capture again on the net's current graph
             self._pending = []
@@ -359,6 +391,7 @@ class BatchedClipPipeline:
                     return net.forward_single(frames)
             self._graphs.append((static_in, graph, out))
             self._graph_planes = planes
+            self._graph_sparse = self._sparse_now
             self.graph_active = True
         static_in, graph, out = self._graphs[self._graph_next]
         self._graph_next = (self._graph_next + 1) % self.n_graph_slots

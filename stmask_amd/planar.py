@@ -108,6 +108,8 @@ class PlanarConv:
         self.relu, self.groups, self.planes, self.tile_n = relu, groups, (planes if self.fmt == 0 else ops.plane_layout(self.fmt)[0]), tile_n
         self._packed = {}
         self.out_scale = 1.0
+        self.wscale = None           # fp16 formats: pack under this power-of-two weight scale instead of the layer's own (a layer that holds some of
+                                     # the output channels of another one rounds its weights exactly as that one does)
         self.role = "trunk"          # "temporal" for TemporalNet's layers: bench.py reports the trunk-only roofline beside the overall one
         # few output channels per group, stride 1, kw >= 3: the kx-reuse kernel (stm_conv2d_planar_kxr_f32) -- these layers run at the
         # L2 -> LDS staging rate on the 128 x 64 tiles (head output layers, DCN offset convolutions, layer1's 3x3)
@@ -120,10 +122,14 @@ class PlanarConv:
         if tile_n not in self._packed:
             if self.fmt >= 1:
                 ops.planar_range_flag()     # the producers of fp16 planes report |x| > 65504 through it
-                self._packed[tile_n], self.out_scale = ops.conv_pack_weights(self.weight, tile_n=tile_n, fmt=self.fmt)
+                self._packed[tile_n], self.out_scale = ops.conv_pack_weights(self.weight, tile_n=tile_n, fmt=self.fmt, wscale=self.wscale)
             else:
                 self._packed[tile_n] = ops.conv_pack_weights(self.weight, self.planes, tile_n)
         return self._packed[tile_n]
+
+    def kxr_rule_pixels(self):
+        """Pixels from which the kx-reuse kernel takes a layer it supports (measured: see __call__)."""
+        return 20000 if self.groups > 1 else 30000
 
     def pick_tile(self, M):
         """Measured on the R50 layer shapes at batch 8 (scripts/bench_conv.py): 128-channel tiles (256 or 128 pixels, one
@@ -152,11 +158,13 @@ class PlanarConv:
         return 128
 
     def __call__(self, xp, shape, out="planes", x_off=0, out_planes=None, out_f32=None, out_off=0, residual=None, x_ch_off=0,
-                 out_ch_off=0, x2=None, window=None):
+                 out_ch_off=0, x2=None, window=None, gate=None, kxr=None, splitk=True):
         """xp: [P, S, N, 32] planes in this layer's format (channel-slab major; 2 x fp16 or 3 x bf16).  shape: ("img", B, H, W) -> pixels [x_off, x_off + B*H*W)
         of xp are one image batch; ("levels", B, [(H, W), ...]) -> all of xp, concatenated levels.  The layer reads
         groups*C channels starting at channel x_ch_off.  out: "planes" | "f32" | "both" allocates dense outputs
-        ([3, O/32, M, 32] / [M, O]) unless out_planes / out_f32 are given, then pixels [out_off, ...) are written."""
+        ([3, O/32, M, 32] / [M, O]) unless out_planes / out_f32 are given, then pixels [out_off, ...) are written.
+        gate = (int32 device tensor, index): only the pixel tiles below that device value run (ops.conv_set_pixel_gate; never split-K).
+        kxr: True / False decides the kx-reuse kernel for a layer it supports (None: by the pixel count); splitk = False: never split K."""
         NP, dt = _planes_dtype(self.fmt)
         if xp.dtype != dt or xp.dim() != 4 or xp.shape[0] < NP or xp.shape[3] != 32 or not xp.is_contiguous():
             raise StmError(f"PlanarConv: expected contiguous {dt} planes [{NP}, S, N, 32], got {xp.dtype} {tuple(xp.shape)}")
@@ -205,7 +213,7 @@ class PlanarConv:
         # ~20 000 pixels (x1.3-1.8), single-group layers of up to 48 channels from ~30 000 (x1.1-1.4); below that its 256-pixel tiles
         # leave CUs idle, and four channel tiles (layer1's 64 -> 64) stay on the general kernel (x0.65)
         use_kxr = (self.kxr and residual is None and window is None and (shape[0] == "levels" or (Ho, Wo) == (H, W))
-                   and M >= (self.kxr_min_pixels if self.kxr_min_pixels is not None else (20000 if self.groups > 1 else 30000)))
+                   and (kxr if kxr is not None else M >= (self.kxr_min_pixels if self.kxr_min_pixels is not None else self.kxr_rule_pixels())))
         g.tile_n = 0 if use_kxr else self.pick_tile(M)
         dev = xp.device
         NPo, dto = _planes_dtype(self.out_fmt)
@@ -249,8 +257,10 @@ class PlanarConv:
             g.fmt = self.fmt
             if "kxr" not in self._packed:
                 ops.planar_range_flag()
-                self._packed["kxr"] = ops.conv_pack_weights_kxr(self.weight, g)
+                self._packed["kxr"] = ops.conv_pack_weights_kxr(self.weight, g, wscale=self.wscale)
             packed, g.out_scale = self._packed["kxr"]
+            if gate is not None:
+                ops.conv_set_pixel_gate(*gate)
             rc = _lib.lib().stm_conv2d_planar_kxr_f32(ctypes.c_void_p(x_ptr), ops._p(packed), ops._p(self.bias), ctypes.c_void_p(p_f32),
                                                       ctypes.c_void_p(p_pl), ctypes.byref(g), c_i(1 if self.relu else 0), ops._stream())
             check(rc, "stm_conv2d_planar_kxr_f32")
@@ -258,7 +268,11 @@ class PlanarConv:
         packed = self.packed(g.tile_n)                     # (sets self.out_scale for the fp16 format)
         g.fmt, g.out_scale = self.fmt, self.out_scale
         g.out_fmt_plus1 = 0 if self.out_fmt == self.fmt else self.out_fmt + 1
-        ws = ops._workspace(self.SPLITK_WS_BYTES, dev, "conv_splitk")     # grow-only, shared: split-K partial sums
+        ws = ops._workspace(self.SPLITK_WS_BYTES, dev, "conv_splitk") if splitk and gate is None else None     # grow-only, shared: split-K partial sums
+        if gate is not None:
+            if x2 is not None:
+                raise StmError("PlanarConv: gated launches take no second source")
+            ops.conv_set_pixel_gate(*gate)
         if x2 is not None:
             p2, H2, W2, s2 = x2
             if p2.dtype != dt or p2.dim() != 4 or p2.shape[0] < NP or p2.shape[3] != 32 or not p2.is_contiguous() or shape[0] != "img":
@@ -273,7 +287,7 @@ class PlanarConv:
         rc = _lib.lib().stm_conv2d_planar_ws_f32(ctypes.c_void_p(x_ptr), ops._p(packed),
                                                  ops._p(self.bias), ctypes.c_void_p(r32), ctypes.c_void_p(rpl),
                                                  ctypes.c_void_p(p_f32), ctypes.c_void_p(p_pl), ctypes.byref(g),
-                                                 c_i(1 if self.relu else 0), ops._p(ws), ctypes.c_size_t(ws.numel()),
+                                                 c_i(1 if self.relu else 0), ops._p(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0),
                                                  ops._stream())
         check(rc, "stm_conv2d_planar_f32")
         return self._finish(timing, e0 if timing is not None else None, M, shape, g, NP, NPo, dt, out, out_f32, out_planes, residual)
@@ -416,6 +430,98 @@ class PlanarGraph:
                     entry.append(None)
             self.finals.append(tuple(entry))
         self.head = head
+        # Sparse head (csrc/head_sparse.hip): set by the caller for the calls it wants it on -- BatchedClipPipeline, whose detection stage reads loc /
+        # centerness / mask_coeff / track at the priors that pass generate_candidate's class threshold only -- as (eval_conf_thresh, capacity in
+        # positions or None).  None: every branch densely (forward_single, the layer API, the per-clip pipeline).  FCA heads with one prior per
+        # kernel shape only: under FCB the class branch reads the dense box regression.
+        self.sparse = None
+        self._sparse_layers = None
+
+    # a kept position costs a 9 x 9 patch: 7 x 7 output pixels of the first tower layer (valid convolution), 5 x 5 of the second -- against
+    # 2 sum(h w) pixel-layers per frame of the dense launches: the paper break-even is 2 sum(h w) / 74 positions per frame (138 at 384 x 640);
+    # DESIGN.md section 6 has the measured curve
+    SPARSE_SIDES = (9, 7, 5)
+
+    def sparse_supported(self):
+        return self.head_planar and not self.fcb and self.head.num_priors == 1
+
+    def sparse_capacity(self, B, sizes):
+        """Positions the patch launches are sized for, all frames of the batch pooled; a multiple of 256 (the launches cover whole groups of 256
+        patches).  More positions than this in a step: the dense launches of the three branches run instead."""
+        s0, s1, s2 = self.SPARSE_SIDES
+        per_frame = max(1, 2 * sum(h * w for h, w in sizes) // (s1 * s1 + s2 * s2))
+        return -(-per_frame * B // 256) * 256
+
+    def _build_sparse(self):
+        """The head's layers cut into the class branch and the three other branches.  Same weights, rounded under the scale of the layer they are
+        cut from, same K order: each output value is the sum the uncut layer forms."""
+        if self._sparse_layers is not None:
+            return self._sparse_layers
+        P = self.GROUP_PAD
+        cw = self.tower2.O // 4
+
+        def cut(layer, rows, **kw):
+            c = PlanarConv(layer.weight[rows], layer.bias[rows], 1, (layer.ph, layer.pw), relu=layer.relu, fmt=layer.fmt, **kw)
+            c.wscale = ops._pow2_wscale(layer.weight) if layer.fmt >= 1 else None
+            return c
+
+        t1c, t1r = cut(self.tower1, slice(0, cw)), cut(self.tower1, slice(cw, 4 * cw))
+        t2c, t2r = cut(self.tower2, slice(0, cw)), cut(self.tower2, slice(cw, 4 * cw), groups=3)
+        cls, small = [], []
+        for sm, _ in self.finals:
+            gc = sm.group_cout
+            cls.append(cut(sm, slice(0, P), tile_n=64, group_cout=gc[:1], algo_frac=gc[0] / float(P)))
+            small.append(cut(sm, slice(P, 3 * P), groups=2, tile_n=64, group_cout=gc[1:], algo_frac=sum(gc[1:]) / (2.0 * P)))
+        self._sparse_layers = (t1c, t1r, t2c, t2r, cls, small)
+        return self._sparse_layers
+
+    def _sparse_head(self, up, B, sizes, ntot, dev, toc):
+        """conf for every prior; loc / mask_coeff / track / centerness at the rows of the positions with a prior that passes the class threshold
+        (the other rows are not written).  No host read: launches are sized by the capacity and gated by device counts."""
+        head = self.head
+        thresh, cap = self.sparse
+        if cap is None:
+            cap = self.sparse_capacity(B, sizes)
+        t1c, t1r, t2c, t2r, cls_l, small_l = self._build_sparse()
+        trk_l = [trk for _, trk in self.finals]
+        lv = ("levels", B, sizes)
+        cw, P = self.tower2.O // 4, self.GROUP_PAD
+        S0, S1, S2 = self.SPARSE_SIDES
+        NP, pdt = _planes_dtype(self.fmt)
+        # the output layers run on the kernel the dense head would pick for them (the kx-reuse kernel forms its sums with other operand roles)
+        kx = ntot >= self.finals[0][0].kxr_rule_pixels()
+        # 1. the class branch, dense
+        x = t1c(up, lv, out="planes", splitk=False)
+        x = t2c(x, lv, out="planes", splitk=False)
+        cls = [c(x, lv, out="f32", splitk=False, kxr=kx) for c in cls_l]
+        toc("head_towers")
+        # 2. positions whose rows the detection stage will read
+        lst, ctl = ops.head_candidates(cls, head.num_classes, thresh, cap, S1 * S1, S2 * S2, B, sizes)
+        # 3. their 9 x 9 patches through the two tower layers of the other branches as valid convolutions (window launches with no padding:
+        # 9 x 9 -> 7 x 7 -> 5 x 5); after each layer the pixels outside the level's map become zero -- the padding the dense launch reads there
+        patch = ops.head_patch_gather(up, torch.empty(NP, cw // 32, cap * S0 * S0, 32, device=dev, dtype=pdt), S0, cap, B, sizes, lst, ctl)
+        x1 = torch.empty(NP, 3 * cw // 32, cap * S1 * S1, 32, device=dev, dtype=pdt)
+        t1r(patch, ("img", cap, S0, S0), out="planes", out_planes=x1, window=(0, 0, S1, S1, 0, 0, S1, S1), gate=(ctl, ops.HEAD_CTL_GATE_A))
+        ops.head_patch_mask(x1, S1, cap, B, sizes, lst, ctl)
+        gb = (ctl, ops.HEAD_CTL_GATE_B)
+        xq = torch.empty(NP, 3 * cw // 32, cap * S2 * S2, 32, device=dev, dtype=pdt)
+        t2r(x1, ("img", cap, S1, S1), out="planes", out_planes=xq, window=(0, 0, S2, S2, 0, 0, S2, S2), gate=gb)
+        ops.head_patch_mask(xq, S2, cap, B, sizes, lst, ctl)
+        # ... and the output layers over the 5 x 5 maps (all that their windows at the centre pixel read), "same" padding
+        ql = ("levels", cap, [(S2, S2)])
+        small = [c(xq, ql, out="f32", gate=gb, kxr=kx) for c in small_l]
+        trk = [c(xq, ql, out="f32", x_ch_off=2 * cw, gate=gb) for c in trk_l]
+        # 4. more positions than the capacity: the same layers over every pixel (empty launches otherwise)
+        gd = (ctl, ops.HEAD_CTL_DENSE)
+        x = t1r(up, lv, out="planes", gate=gd)
+        x = t2r(x, lv, out="planes", gate=gd)
+        small_d = [c(x, lv, out="f32", gate=gd, kxr=kx) for c in small_l]
+        trk_d = [c(x, lv, out="f32", x_ch_off=2 * cw, gate=gd) for c in trk_l]
+        toc("head_finals")
+        out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P,
+                                       S2 * S2, (S2 * S2) // 2, lst, ctl, cap)
+        self.sparse_ctl, self.sparse_list = ctl, lst       # (tests, diagnosis: the step's counts and positions)
+        return out
 
     # ------------------------------------------------------------------------------------------------------------
     def run(self, bb_outs, planes=None):
@@ -588,10 +694,15 @@ class PlanarGraph:
             up32, up = self.up(feat, lv, out="both")
         else:
             up32, up = None, self.up(feat, lv, out="planes")
-        t1 = self.tower1(up, lv, out="planes")
+        sparse_out = None
+        if self.sparse is not None and self.sparse_supported():
+            sparse_out = self._sparse_head(up, B, sizes, ntot, dev, toc)
+        t1 = self.tower1(up, lv, out="planes") if sparse_out is None else None
         cw = self.tower2.O // 4                                       # channels per branch in t2 (conf, bbox, mask, track)
         P = self.GROUP_PAD
-        if not self.fcb:
+        if sparse_out is not None:
+            outs = None
+        elif not self.fcb:
             t2 = self.tower2(t1, lv, out="planes")
             toc("head_towers")
             outs = [(small(t2, lv, out="f32"), trk(t2, lv, out="f32", x_ch_off=3 * cw)) for small, trk in self.finals]
@@ -665,7 +776,9 @@ class PlanarGraph:
         for hh, ww in sizes:
             pred["priors"].append(head.make_priors(hh, ww, dev))
         pred["priors"] = torch.cat(pred["priors"], 1)
-        if npri == 1:
+        if sparse_out is not None:
+            pred["conf"], pred["loc"], pred["mask_coeff"], pred["track"], pred["centerness"] = sparse_out
+        elif npri == 1:
             # one kernel for the reference's cat / view / tanh / normalize tail over all levels and kernel shapes
             conf, loc, mask, track, cen = ops.head_assemble([o[0] for o in outs], [o[1] for o in outs], B, sizes,
                                                             head.num_classes, head.mask_dim, head.embed_dim, P)
