@@ -42,7 +42,8 @@
  *      6: struct stm_render_frame (stm_struct_bytes(5)), stm_render_workspace_bytes and stm_render_overlay_u8, display mode: tracked
  *     instances drawn onto their frames).
  *     Added since without a version change (new entry points only; the binding refuses a library that lacks one): the backward kernels of
- *     the training path stm_deform_col2im_f32, stm_deform_col2im_coord_f32, stm_roi_align_backward_f32, stm_corr_backward_f32.
+ *     the training path stm_deform_col2im_f32, stm_deform_col2im_coord_f32, stm_roi_align_backward_f32, stm_corr_backward_f32, and of the layer
+ *     functions stm_lincomb_backward_workspace_bytes, stm_lincomb_backward_f32, stm_decode_boxes_backward_f32, stm_jaccard_backward_f32.
  */
 #ifndef STMASK_HIP_H_
 #define STMASK_HIP_H_
@@ -764,6 +765,33 @@ int stm_roi_align_backward_f32(const float* grad_out, const float* rois, float* 
  * (terms outside the map are 0).  Written, not accumulated; either output may be NULL.  One fixed-order sum per output. */
 int stm_corr_backward_f32(const float* grad_out, const float* in1, const float* in2, float* grad_in1, float* grad_in2, int B, int C, int H,
                           int W, int P, int dil, stm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Backward of the layer functions the reference's loss differentiates through (stmask_amd/autograd.py: generate_mask, decode, jaccard).
+ * fp32, only the forwards' inputs are read, no float atomics: every output is bit-identical from run to run.
+ *
+ * stm_lincomb_backward_f32: backward of stm_lincomb_sigmoid_crop_f32 (one prototype set, no n_dev / row_proto).  grad_out [n,h,w],
+ *   proto [h,w,m], coeff [n,m], boxes [n,4] or NULL, m in {8, 32, 64}.  With t = tanh(coeff) (apply_tanh) or coeff, a = proto . t_d,
+ *   s = sigmoid(a):  z[d,pix] = grad_out[d,pix] * s (1 - s) inside row d's crop rectangle (the forward's, padding 1) and exactly 0 outside,
+ *   where grad_out is not read at all;  grad_proto[pix,k] = sum_d z[d,pix] t[d,k]  (written, not accumulated);
+ *   grad_coeff[d,k] = (sum_pix z[d,pix] proto[pix,k]) * (1 - t^2)  (the last factor with apply_tanh only).  s (1 - s) is evaluated as
+ *   e / (1 + e)^2, e = exp(-|a|), and 1 - t^2 as 4 e / (1 + e)^2, e = exp(-2 |coeff|): neither cancels.  No gradient w.r.t. the boxes (the
+ *   reference's crop has none).  Either gradient may be NULL and is then not computed.  workspace:
+ *   stm_lincomb_backward_workspace_bytes(n, h, w, m) bytes, 16-byte aligned.
+ * stm_decode_boxes_backward_f32: backward of stm_decode_boxes_f32, the derivative of its expression including the in-place point-form step
+ *   (x1 = cx - w / 2, x2 = w + x1).  grad_boxes [n,4] -> grad_loc [n,4] and grad_priors [n,4]; either may be NULL.
+ * stm_jaccard_backward_f32: backward of stm_jaccard_f32.  grad_out [na,nb] -> grad_a [na,4] (sum over b in a fixed order) and grad_b [nb,4]
+ *   (sum over a in row order); either may be NULL.  Ties: where min(a.x2, b.x2) or max(a.x1, b.x1) compares equal the gradient goes to a's
+ *   coordinate; an overlap extent that the clamp at 0 cut, or that is exactly 0, passes no gradient.
+ * ------------------------------------------------------------------------------------------------- */
+size_t stm_lincomb_backward_workspace_bytes(int n, int h, int w, int m);
+int stm_lincomb_backward_f32(const float* grad_out, const float* proto, const float* coeff, const float* boxes, float* grad_proto,
+                             float* grad_coeff, int h, int w, int m, int n, int apply_tanh, void* workspace, size_t workspace_bytes,
+                             stm_stream_t stream);
+int stm_decode_boxes_backward_f32(const float* grad_boxes, const float* loc, const float* priors, float* grad_loc, float* grad_priors,
+                                  int64_t n, stm_stream_t stream);
+int stm_jaccard_backward_f32(const float* grad_out, const float* a, int na, const float* b, int nb, float* grad_a, float* grad_b,
+                             stm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,10 +1,11 @@
 """Autograd for the drop-in deformable convolution, RoIAlign and correlation (the training path of dcn_v2 / mmcv.ops /
-spatial_correlation_sampler).
+spatial_correlation_sampler) and for the layer functions the reference's loss differentiates through -- generate_mask, decode, jaccard
+(INTEGRATION.md section 14).
 
 Each Function's forward is the launch the shim makes without autograd (ops.deform_conv / roi_align / corr_patch), so values under
 autograd are bit-identical to the no-grad call.  Only inputs are saved: the deformable columns are recomputed in backward with the
-forward's own im2col.  Backward runs the gfx950 kernels of csrc/deform_backward.hip and csrc/temporal_backward.hip on the current
-stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
+forward's own im2col, the mask sigmoid from the prototypes and coefficients.  Backward runs the gfx950 kernels of csrc/deform_backward.hip,
+csrc/temporal_backward.hip and csrc/mask_backward.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
 every backward is @first_order_only: a double backward (create_graph=True, then differentiating the result) raises instead of
 silently dropping the second-order term.
 """
@@ -144,6 +145,63 @@ class CorrelationFunction(torch.autograd.Function):
         return g1, g2, None, None
 
 
+class LincombMaskFunction(torch.autograd.Function):
+    """generate_mask: sigmoid(proto @ tanh(coeff)^T) cropped to the boxes, [h,w,M] x [n,M] -> [n,h,w].  No gradient w.r.t. the boxes (the
+    reference's crop has none)."""
+
+    @staticmethod
+    def forward(ctx, proto, coeff, boxes, apply_tanh):
+        ctx.apply_tanh = apply_tanh
+        ctx.save_for_backward(proto, coeff, boxes)
+        return ops.lincomb_sigmoid_crop(proto, coeff, boxes, apply_tanh=apply_tanh)
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_out):
+        np_, nc = ctx.needs_input_grad[:2]
+        if not (np_ or nc):
+            return None, None, None, None
+        proto, coeff, boxes = ctx.saved_tensors
+        gp, gc = ops.lincomb_sigmoid_crop_backward(grad_out.contiguous(), proto, coeff, boxes, ctx.apply_tanh, need_proto=np_, need_coeff=nc)
+        return gp, gc, None, None
+
+
+class DecodeFunction(torch.autograd.Function):
+    """box_utils.decode: loc [n,4], priors [n,4] -> point-form boxes [n,4]."""
+
+    @staticmethod
+    def forward(ctx, loc, priors):
+        ctx.save_for_backward(loc, priors)
+        return ops.decode(loc, priors)
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_boxes):
+        nl, npr = ctx.needs_input_grad[:2]
+        if not (nl or npr):
+            return None, None
+        loc, priors = ctx.saved_tensors
+        return ops.decode_backward(grad_boxes.contiguous(), loc, priors, need_loc=nl, need_priors=npr)
+
+
+class JaccardFunction(torch.autograd.Function):
+    """box_utils.jaccard, 2-D form: [A,4] x [B,4] -> [A,B]."""
+
+    @staticmethod
+    def forward(ctx, box_a, box_b):
+        ctx.save_for_backward(box_a, box_b)
+        return ops.jaccard(box_a, box_b)
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_out):
+        na, nb = ctx.needs_input_grad[:2]
+        if not (na or nb):
+            return None, None
+        a, b = ctx.saved_tensors
+        return ops.jaccard_backward(grad_out.contiguous(), a, b, need_a=na, need_b=nb)
+
+
 def modulated_deform_conv(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups):
     return ModulatedDeformConvFunction.apply(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups, False)
 
@@ -162,3 +220,15 @@ def roi_align(feat, rois, output_size, spatial_scale, sampling_ratio, aligned):
 
 def correlation(in1, in2, patch_size, dilation_patch):
     return CorrelationFunction.apply(in1, in2, patch_size, dilation_patch)
+
+
+def lincomb_mask(proto, coeff, boxes=None, apply_tanh=True):
+    return LincombMaskFunction.apply(proto, coeff, boxes, apply_tanh)
+
+
+def decode(loc, priors):
+    return DecodeFunction.apply(loc, priors)
+
+
+def jaccard(box_a, box_b):
+    return JaccardFunction.apply(box_a, box_b)

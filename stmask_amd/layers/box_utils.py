@@ -4,10 +4,12 @@ sanitize_coordinates(_hw) (:298-337), crop (:341-364), mask_iou (:435-447).
 
 decode / jaccard / mask_iou run as hand-written HIP kernels (bit-exact vs the oracle); the tiny element-wise helpers
 stay as torch ops in the reference's operand order (IEEE add / sub / mul / div are identical on CPU and GPU).
+decode and jaccard take the autograd path (autograd.DecodeFunction / JaccardFunction: the same launch, the backward of
+csrc/mask_backward.hip) when an input requires grad; mask_iou is binarised and has no gradient, as in the reference.
 """
 import torch
 
-from .. import ops
+from .. import autograd, ops
 
 
 def point_form(boxes):
@@ -23,17 +25,20 @@ def decode(loc, priors, use_yolo_regressors=False):
         raise NotImplementedError("use_yolo_regressors is False in every STMask config (config.py)")
     if loc.shape[0] == 0:
         return loc.new_zeros(0, 4)
+    if autograd.wants_grad(loc, priors):
+        return autograd.decode(loc, priors)
     return ops.decode(loc, priors)
 
 
 def jaccard(box_a, box_b, iscrowd=False):
     if iscrowd:
         raise NotImplementedError("iscrowd is a training-only path")
+    pair = autograd.jaccard if autograd.wants_grad(box_a, box_b) else ops.jaccard
     if box_a.dim() == 3:  # batched form used by per-class Fast NMS
-        return torch.stack([ops.jaccard(a, b) for a, b in zip(box_a, box_b)])
+        return torch.stack([pair(a, b) for a, b in zip(box_a, box_b)])
     if box_a.shape[0] == 0 or box_b.shape[0] == 0:
         return box_a.new_zeros(box_a.shape[0], box_b.shape[0])
-    return ops.jaccard(box_a, box_b)
+    return pair(box_a, box_b)
 
 
 def sanitize_coordinates(_x1, _x2, img_size, padding=0, cast=True):

@@ -453,6 +453,21 @@ def decode(loc, priors):
     return boxes
 
 
+def decode_backward(grad_boxes, loc, priors, need_loc=True, need_priors=False):
+    """(grad_loc, grad_priors) of decode; a gradient not needed is None and not computed."""
+    _dev(grad_boxes, loc, priors)
+    gb, loc, priors = _f32c(grad_boxes), _f32c(loc), _f32c(priors)
+    if gb.shape != loc.shape or priors.shape != loc.shape:
+        raise StmError(f"decode_backward: grad_boxes {tuple(gb.shape)}, loc {tuple(loc.shape)} and priors {tuple(priors.shape)} differ")
+    gl = torch.empty_like(loc) if need_loc else None
+    gp = torch.empty_like(priors) if need_priors else None
+    if gl is None and gp is None:
+        return None, None
+    check(_lib.lib().stm_decode_boxes_backward_f32(_p(gb), _p(loc), _p(priors), _p(gl), _p(gp), c_l(loc.shape[0]), _stream()),
+          "stm_decode_boxes_backward_f32")
+    return gl, gp
+
+
 def generate_candidates(loc, priors, conf, thresh=0.05):
     """TF_utils.py:54-82 core.  loc [B,N,4], priors [N,4], conf [B,N,ncls] soft-maxed ->
     keep_idx [B,N] (first count[b] valid, ascending), cand_box [B,N,4], count [B] (device int32)."""
@@ -579,6 +594,21 @@ def jaccard(a, b):
     return out
 
 
+def jaccard_backward(grad_out, a, b, need_a=True, need_b=True):
+    """(grad_a, grad_b) of jaccard (2-D form); fixed-order sums, no atomics.  Ties: INTEGRATION.md section 14."""
+    _dev(grad_out, a, b)
+    go, a, b = _f32c(grad_out), _f32c(a), _f32c(b)
+    if tuple(go.shape) != (a.shape[0], b.shape[0]):
+        raise StmError(f"jaccard_backward: grad_out {tuple(go.shape)} != {(a.shape[0], b.shape[0])}")
+    ga = torch.empty_like(a) if need_a else None
+    gb = torch.empty_like(b) if need_b else None
+    if ga is None and gb is None:
+        return None, None
+    check(_lib.lib().stm_jaccard_backward_f32(_p(go), _p(a), c_i(a.shape[0]), _p(b), c_i(b.shape[0]), _p(ga), _p(gb), _stream()),
+          "stm_jaccard_backward_f32")
+    return ga, gb
+
+
 def lincomb_sigmoid_crop_bits(proto, coeff, boxes, row_proto, thr=0.5, apply_tanh=True):
     """lincomb_sigmoid_crop that also returns the binarised masks (value > thr) bit-packed, [n, ceil(h*w/64)] int64 words -- the
     form mask_iou_bits consumes, produced in the pass that writes the soft masks instead of a second read of them."""
@@ -627,6 +657,27 @@ def lincomb_sigmoid_crop(proto, coeff, boxes=None, apply_tanh=True, n_dev=None, 
                                                   c_i(1 if apply_tanh else 0), _p(n_dev), _p(row_proto), _stream()),
           "stm_lincomb_sigmoid_crop_f32")
     return out
+
+
+def lincomb_sigmoid_crop_backward(grad_out, proto, coeff, boxes=None, apply_tanh=True, need_proto=True, need_coeff=True):
+    """(grad_proto, grad_coeff) of lincomb_sigmoid_crop(proto [h,w,m], coeff [n,m], boxes [n,4] or None); only the inputs are read (the
+    sigmoid is recomputed), both sums run in a fixed order.  A gradient not needed is None and not computed; none w.r.t. the boxes."""
+    _dev(grad_out, proto, coeff, boxes)
+    go, proto, coeff = _f32c(grad_out), _f32c(proto), _f32c(coeff)
+    h, w, m = proto.shape
+    n = coeff.shape[0]
+    if tuple(go.shape) != (n, h, w) or coeff.shape[1] != m or (boxes is not None and tuple(boxes.shape) != (n, 4)):
+        raise StmError(f"lincomb_sigmoid_crop_backward: grad_out {tuple(go.shape)}, proto {tuple(proto.shape)}, coeff {tuple(coeff.shape)} do not match")
+    gp = torch.empty_like(proto) if need_proto else None
+    gc = torch.empty_like(coeff) if need_coeff else None
+    if gp is None and gc is None:
+        return None, None
+    bx = _f32c(boxes) if boxes is not None else None
+    need = _lib.lib().stm_lincomb_backward_workspace_bytes(c_i(n), c_i(h), c_i(w), c_i(m))
+    ws = _workspace(need, proto.device, "lcb")
+    check(_lib.lib().stm_lincomb_backward_f32(_p(go), _p(proto), _p(coeff), _p(bx), _p(gp), _p(gc), c_i(h), c_i(w), c_i(m), c_i(n),
+                                              c_i(1 if apply_tanh else 0), _p(ws), c_sz(ws.numel()), _stream()), "stm_lincomb_backward_f32")
+    return gp, gc
 
 
 def mask_iou(m1, m2, thr=0.5, group1=None, group2=None):
