@@ -43,7 +43,8 @@
  *     instances drawn onto their frames).
  *     Added since without a version change (new entry points only; the binding refuses a library that lacks one): the backward kernels of
  *     the training path stm_deform_col2im_f32, stm_deform_col2im_coord_f32, stm_roi_align_backward_f32, stm_corr_backward_f32, and of the layer
- *     functions stm_lincomb_backward_workspace_bytes, stm_lincomb_backward_f32, stm_decode_boxes_backward_f32, stm_jaccard_backward_f32.
+ *     functions stm_lincomb_backward_workspace_bytes, stm_lincomb_backward_f32, stm_decode_boxes_backward_f32, stm_jaccard_backward_f32;
+ *     the training target assignment stm_match_workspace_bytes, stm_match_priors_f32, stm_encode_boxes_f32.
  */
 #ifndef STMASK_HIP_H_
 #define STMASK_HIP_H_
@@ -792,6 +793,35 @@ int stm_decode_boxes_backward_f32(const float* grad_boxes, const float* loc, con
                                   int64_t n, stm_stream_t stream);
 int stm_jaccard_backward_f32(const float* grad_out, const float* a, int na, const float* b, int nb, float* grad_a, float* grad_b,
                              stm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Training target assignment.  Replaces: layers.box_utils.match (box_utils.py:119-197, with use_prediction_matching,
+ * use_change_matching and use_yolo_regressors False as in every config) followed by the gather of multibox_loss.py:142, and
+ * layers.box_utils.encode (:200-235).  Three launches for the whole batch, whatever the number of boxes; no float atomics, every sum
+ * and arg-max in one order: outputs are bit-identical run to run.
+ *
+ * stm_match_priors_f32: image b owns rows offsets[b] .. offsets[b+1]-1 of boxes [G_total,4] (point form), labels and ids (int64);
+ *   offsets is a DEVICE array of B+1 int32.  G_total and G_max (the largest per-image count) are given by the caller, who knows them
+ *   from its tensor shapes: 1 <= G_max <= 128, G_max <= P, 2 <= C <= 128, P <= 262144 (beyond: STM_EUNSUPPORTED; no box at all, or more
+ *   boxes than priors: STM_EINVAL).  priors [P,4] (priors_batched = 0) or [B,P,4] (1), centre-size form; conf [B,P,C] raw class scores,
+ *   read only at the priors whose best overlap passes pos_thresh.  pos_thresh / neg_thresh are doubles as the reference's Python
+ *   floats: pos, pos - 0.1 and (pos + neg) / 2 are formed in double and rounded to fp32 once.
+ *   Conventions: the first index wins every maximum tie (prior -> box, box -> prior, and the order of the forced matches); overlaps,
+ *   point_form and columns 0-1 of loc_t are IEEE fp32 in the reference's operand order (idx_t is exact, not a tolerance); the cross
+ *   entropy and the log of loc_t's columns 2-3 are evaluated in double and rounded once; mean(cla) is a fixed-order double sum.
+ *   Outputs: loc_t [B,P,4] (encode of the matched box), gt_boxes_t [B,P,4] (the matched box), conf_t [B,P] (label, -1 neutral,
+ *   0 background), idx_t [B,P] (matched box, image-local), ids_t [B,P] (instance id, 0 unless positive), all int64.
+ *   status (optional, DEVICE int32 [B]): 0, or bit 0 = offsets[b..b+1] out of contract (the image's targets are all zero), bit 1 = a
+ *   box with x2 <= x1 or y2 <= y1 (or NaN), bit 2 = no finite overlap left to force.  Such input never faults; its targets are
+ *   unspecified.  workspace: stm_match_workspace_bytes(B, P, G_total, G_max) bytes, 16-byte aligned.
+ * stm_encode_boxes_f32: matched [n,4] (point form), priors [n,4] (centre-size) -> out [n,4], variances 0.1 / 0.2.
+ * ------------------------------------------------------------------------------------------------- */
+size_t stm_match_workspace_bytes(int B, int P, int G_total, int G_max);
+int stm_match_priors_f32(const float* boxes, const int64_t* labels, const int64_t* ids, const int* offsets, int B, int G_total, int G_max,
+                         const float* priors, int priors_batched, int P, const float* conf, int C, double pos_thresh, double neg_thresh,
+                         float* loc_t, float* gt_boxes_t, int64_t* conf_t, int64_t* idx_t, int64_t* ids_t, int* status, void* workspace,
+                         size_t workspace_bytes, stm_stream_t stream);
+int stm_encode_boxes_f32(const float* matched, const float* priors, float* out, int64_t n, stm_stream_t stream);
 
 #ifdef __cplusplus
 }

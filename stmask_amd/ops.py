@@ -585,6 +585,78 @@ def detect_pc(loc, priors, conf, centerness, conf_thresh=0.05, iou_thr=0.5, top_
     return idx, cls, sc, bx, cnt
 
 
+def encode(matched, priors):
+    """box_utils.py:200-235 (use_yolo_regressors=False): matched [n,4] point form, priors [n,4] centre-size -> [n,4].  Columns 0-1 are the
+    reference's fp32 arithmetic bit for bit; the log of columns 2-3 is evaluated in double and rounded once."""
+    _dev(matched, priors)
+    matched, priors = _f32c(matched), _f32c(priors)
+    if matched.dim() != 2 or matched.shape[1] != 4 or priors.shape != matched.shape:
+        raise StmError(f"encode: matched {tuple(matched.shape)} and priors {tuple(priors.shape)} must both be [n, 4]")
+    out = torch.empty_like(matched)
+    check(_lib.lib().stm_encode_boxes_f32(_p(matched), _p(priors), _p(out), c_l(matched.shape[0]), _stream()), "stm_encode_boxes_f32")
+    return out
+
+
+_match_offsets = {}   # (device index, G) -> int32 [0, G] on the device, for the one-image form (G <= 128: bounded)
+
+
+def match_offsets(counts, device):
+    """Per-image box counts (Python ints) -> the int32 [B+1] row offsets on the device, without a host synchronisation: the one-image form is
+    cached, a batch goes through pinned memory and an asynchronous copy."""
+    if len(counts) == 1:
+        key = (device.index, counts[0])
+        t = _match_offsets.get(key)
+        if t is None:
+            t = _match_offsets[key] = torch.tensor([0, counts[0]], dtype=torch.int32, device=device)
+        return t
+    acc = [0]
+    for c in counts:
+        acc.append(acc[-1] + int(c))
+    return torch.tensor(acc, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
+
+
+def match_priors(boxes, labels, ids, counts, priors, conf, pos_thresh, neg_thresh, out=None, offsets=None, want_status=False):
+    """box_utils.py:119-197 for a whole batch in three launches (stm_match_priors_f32; conventions in include/stmask_hip.h and INTEGRATION.md
+    section 14).  boxes [G_total,4] fp32 point form, labels / ids [G_total] int64, counts: the per-image numbers of boxes (Python ints, from the
+    callers' tensor shapes), priors [P,4] or [B,P,4], conf [B,P,C] (read detached).  out: optional (loc_t, gt_boxes_t, conf_t, idx_t, ids_t) to
+    fill -- contiguous fp32 [B,P,4] x 2 and int64 [B,P] x 3.  Returns that tuple, plus the device int32 [B] status word with want_status."""
+    _dev(boxes, labels, ids, priors, conf)
+    counts = [int(c) for c in counts]
+    B, G_total, G_max = len(counts), sum(counts), max(counts) if counts else 0
+    conf = conf.detach()
+    boxes, priors, conf = _f32c(boxes), _f32c(priors), _f32c(conf)
+    if conf.dim() == 2:
+        conf = conf[None]
+    if conf.dim() != 3 or conf.shape[0] != B:
+        raise StmError(f"match_priors: conf {tuple(conf.shape)} for {B} images (expected [B, P, C])")
+    P, C = conf.shape[1], conf.shape[2]
+    if tuple(boxes.shape) != (G_total, 4) or labels.shape[0] != G_total or ids.shape[0] != G_total:
+        raise StmError(f"match_priors: boxes {tuple(boxes.shape)}, labels {tuple(labels.shape)}, ids {tuple(ids.shape)} for {G_total} boxes")
+    if tuple(priors.shape) not in ((P, 4), (B, P, 4)):
+        raise StmError(f"match_priors: priors {tuple(priors.shape)} for P={P}, B={B}")
+    labels, ids = labels.to(torch.int64).contiguous(), ids.to(torch.int64).contiguous()
+    dev = conf.device
+    if offsets is None:
+        offsets = match_offsets(counts, dev)
+    if out is None:
+        out = (torch.empty(B, P, 4, dtype=torch.float32, device=dev), torch.empty(B, P, 4, dtype=torch.float32, device=dev),
+               torch.empty(B, P, dtype=torch.int64, device=dev), torch.empty(B, P, dtype=torch.int64, device=dev),
+               torch.empty(B, P, dtype=torch.int64, device=dev))
+    else:
+        for t, dt, shp in zip(out, (torch.float32,) * 2 + (torch.int64,) * 3, ((B, P, 4),) * 2 + ((B, P),) * 3):
+            if t.dtype != dt or t.numel() != B * P * (4 if len(shp) == 3 else 1) or not t.is_contiguous() or t.device != dev:
+                raise StmError(f"match_priors: output {tuple(t.shape)} {t.dtype} must be contiguous {dt} with the elements of {shp}")
+    status = torch.empty(B, dtype=torch.int32, device=dev) if want_status else None
+    L = _lib.lib()
+    nbytes = L.stm_match_workspace_bytes(c_i(B), c_i(P), c_i(G_total), c_i(G_max))
+    ws = _workspace(nbytes, dev, "match")
+    check(L.stm_match_priors_f32(_p(boxes), _p(labels), _p(ids), _p(offsets), c_i(B), c_i(G_total), c_i(G_max), _p(priors),
+                                 c_i(1 if priors.dim() == 3 else 0), c_i(P), _p(conf), c_i(C), ctypes.c_double(float(pos_thresh)),
+                                 ctypes.c_double(float(neg_thresh)), _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _p(out[4]), _p(status),
+                                 _p(ws), c_sz(nbytes), _stream()), "stm_match_priors_f32")
+    return tuple(out) + ((status,) if want_status else ())
+
+
 def jaccard(a, b):
     """box_utils.py:60-88 (2-D form), bit-exact."""
     _dev(a, b)
