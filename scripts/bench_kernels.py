@@ -70,11 +70,8 @@ def bench_gemm(B):
         bias = torch.randn(M, device=DEV)
         fl = 2.0 * M * N * K * B
         line = f"gemm {name} M={M} N={N} K={K} batch={B}: "
-        for tile in ("64", "128", "256"):
-            os.environ["STM_GEMM_TILE"] = tile
-            ms = timeit(lambda: ops.gemm_bias(A, Bm, bias))
-            line += f"| tile{tile} {ms * 1e3:8.1f} us {fl / ms / 1e9:6.1f} TF "
-        os.environ.pop("STM_GEMM_TILE", None)
+        ms = timeit(lambda: ops.gemm_bias(A, Bm, bias))
+        line += f"| stm {ms * 1e3:8.1f} us {fl / ms / 1e9:6.1f} TF "
         ms = timeit(lambda: torch.matmul(A, Bm))
         line += f"| torch.matmul {ms * 1e3:8.1f} us {fl / ms / 1e9:6.1f} TF"
         print(line, flush=True)

@@ -16,53 +16,24 @@
 // producer's epilogue, and staging a K-slab (one tap, 32 channels) is pure LDS-DMA.  Tiles: 128*MG pixels x 64*NJ channels, 4*MG
 // waves; LDS rows of 64 B with the 16-B chunk index XORed by f((row >> 2) & 3), conflict-free for the 16x16x32 fragment reads;
 // two LDS buffers, or a three-buffer ring with fragment prefetch (fp16 formats); split-K for grids that would idle the chip.
-// DESIGN.md section 4 has the history of this kernel and what bounds it.
+// DESIGN.md section 4 has the history of this kernel and what bounds it.  The producers of the plane layouts that are not
+// convolutions (split, resize, RoI features, stem patches) and the weight packer live in planar_prep.hip.
 #include "planar_common.h"
 #include <algorithm>
 #include <type_traits>
 #include <atomic>
-#include <mutex>
-#include <unordered_map>
 
 namespace {
 
-// Write 8 consecutive channels of one pixel into a planar tensor: dst = address of the 16-byte group in plane 0, plane_b = bytes
-// between planes.  fmt 0: three bf16 planes; 1: two fp16 planes (h, (x - h) * 2048); 2: ONE fp16 plane (h only -- the genuine
-// fp16 activation format of BASELINE config 5; plane 0 of a fmt-1 tensor is a valid fmt-2 tensor).  nt: nontemporal stores.
-__device__ __forceinline__ void store_planes8(uint8_t* dst, size_t plane_b, const float (&v)[8], int fmt, int* range_flag, bool nt)
-{
-    unsigned q0[4], q1[4], q2[4];
-    if (fmt == 0) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) split2(f32x2{v[2 * e], v[2 * e + 1]}, q0[e], q1[e], q2[e]);
-    } else {
-        f16_range_check8(v, range_flag);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) split2_f16(f32x2{v[2 * e], v[2 * e + 1]}, q0[e], q1[e]);
-    }
-    const int np = fmt == 0 ? 3 : (fmt == 1 ? 2 : 1);
-    if (nt) {
-        __builtin_nontemporal_store(u32x4{q0[0], q0[1], q0[2], q0[3]}, reinterpret_cast<u32x4*>(dst));
-        if (np > 1) __builtin_nontemporal_store(u32x4{q1[0], q1[1], q1[2], q1[3]}, reinterpret_cast<u32x4*>(dst + plane_b));
-        if (np > 2) __builtin_nontemporal_store(u32x4{q2[0], q2[1], q2[2], q2[3]}, reinterpret_cast<u32x4*>(dst + 2 * plane_b));
-    } else {
-        *reinterpret_cast<u32x4*>(dst) = u32x4{q0[0], q0[1], q0[2], q0[3]};
-        if (np > 1) *reinterpret_cast<u32x4*>(dst + plane_b) = u32x4{q1[0], q1[1], q1[2], q1[3]};
-        if (np > 2) *reinterpret_cast<u32x4*>(dst + 2 * plane_b) = u32x4{q2[0], q2[1], q2[2], q2[3]};
-    }
-}
-
 // the sticky fp16-range flag, one per device (a process that drives several GPUs registers one flag on each)
-constexpr int STM_MAX_DEVICES = 32;
 static int* g_range_flags[STM_MAX_DEVICES] = {};
 static int* current_range_flag()
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= STM_MAX_DEVICES) return nullptr;
-    return g_range_flags[dev];
+    const int dev = stm_current_device();
+    return dev >= 0 ? g_range_flags[dev] : nullptr;
 }
 
-// ---- planar variant: the activation arrives ALREADY split, as NPL bf16 planes [NPL][B*H*W][x_ld] (the format the
+// ---- planar variant: the activation arrives ALREADY split, as NPL bf16 planes [NPL][C/32][pixels][32] (the format the
 // epilogue below writes), so staging a K-slab is pure data movement: LDS-DMA (buffer_load ... lds, 16 B per lane,
 // out-of-range offsets deliver the zero padding) for the activation rows and global_load_lds for the pre-tiled weights,
 // no registers and no VALU beyond a handful of address operations.  Each element is split once, where it is produced,
@@ -80,11 +51,10 @@ struct PlanarArgs {
     uint8_t* out_pl;        // [3][Cout/32][out_np][32] bf16 or null
     int B, H, W, C, Ho, Wo, Cout;
     int kh, kw, sh, sw, ph, pw;
-    int x_ld, out_ld, res_ld;                        // fp32 tensors only (pixels x ld)
+    int relu;               // (kept here: with it after the np fields the <2, 1, 1, 1, 3, DUAL> instantiation takes 129 registers instead of 128)
+    int out_ld, res_ld;                              // fp32 tensors only (pixels x ld)
     int x_np, out_np, res_np;                        // pixels per channel slab of the planar buffers
-    int relu;
     int M, n_tiles, m_tiles, slabs;
-    int nsub;                // 0, or the channel tiles of one pixel tile that run TOGETHER on an XCD (see the tile map)
     unsigned plane_bytes;   // bytes of one input plane that may be addressed (buffer range)
     long long x_pstride, out_pstride, res_pstride;   // bytes between planes
     int groups, ntpg, cout_g;                        // grouped conv: n-tiles per group, output channels per group
@@ -97,7 +67,6 @@ struct PlanarArgs {
     int out_fmt;              // format of out_pl (normally fmt; a fmt-2 layer may write fmt 1 for a consumer that wants both planes)
     float out_scale;          // 1 / (power-of-two weight scale of the packed image)
     int* range_flag;          // fmt 1: set to 1 when an output has no fp16 representation (see f16_range_check8); may be null
-    int nt_out;               // fmt 1: nontemporal plane stores (outputs far larger than L2)
     int splitk, kslabs, ldp;  // split-K: K-slabs per split, fp32 partial sums [splitk][M][ldp] in `partial`
     float* partial;
     int vec_epilogue;       // Cout, out_ld, res_ld multiples of 8 and 16-byte aligned pointers: vector epilogue
@@ -213,7 +182,7 @@ __device__ __forceinline__ void epilogue_store8(const PlanarArgs& a, int m, int 
         }
         if (a.out_pl) {
             uint8_t* o = a.out_pl + pidx(mo, co, a.out_np) * 2;
-            store_planes8(o, opl * 2, v, ofmt, a.range_flag, a.nt_out != 0);
+            store_planes8(o, opl * 2, v, ofmt, a.range_flag, false);
         }
         return;
     }
@@ -407,36 +376,21 @@ __global__ __launch_bounds__(512, 1) void conv_planar_kernel(const typename std:
 
     int tiles_ = a_in.m_tiles * a_in.n_tiles * a_in.splitk;
     if constexpr (CLS) tiles_ = a_in.cls_tiles;
-    // gated launch (never split-K, never regrouped): the tile map below is built over the VALID pixel tiles, so that every XCD gets its share of
+    // gated launch (never split-K): the tile map below is built over the VALID pixel tiles, so that every XCD gets its share of
     // them -- over the launch's own tile count the XCDs whose runs lie past the gate would stand idle
     else if (a_in.m_gate) tiles_ = min(a_in.m_tiles, (*a_in.m_gate + BM - 1) / BM) * a_in.n_tiles;
     const int tiles = tiles_;
     const int per_xcd = (tiles + 7) >> 3;
     if (!CLS && a_in.m_gate && (int)(blockIdx.x >> 3) >= per_xcd) return;      // (gated: the grid is larger than the map; ids past an XCD's run are not its neighbour's tiles)
     int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    // Which tiles share an XCD at one time decides what its 4-MB L2 must fetch: the 32 workgroups an XCD runs together are 32 / n_tiles pixel
-    // tiles x all n_tiles channel tiles in the plain order, i.e. every K-slab of EVERY channel tile's weights for only 4 pixel tiles at
-    // n_tiles = 8 (rocprofv3: 3.3 GB fetched per TemporalNet launch for 0.45 GB of input -- the 19-MB weight set streams from the Infinity Cache
-    // once per 4 pixel tiles).  With nsub (2 or 4) the order inside a group of (32 / nsub) pixel tiles is: nsub channel tiles of each pixel
-    // tile, then the next nsub, ... -- 32 / nsub pixel tiles x nsub channel tiles together.  Same tiles, same results.
-    auto regroup = [&](int j, int nt_all, int& mt_o, int& nt_o) {
-        const int pg = 32 / a_in.nsub, G = pg * nt_all;
-        const int gq = j / G, r = j - gq * G;
-        const int nh = r >> 5, rr = r & 31;
-        mt_o = gq * pg + rr / a_in.nsub;
-        nt_o = nh * a_in.nsub + rr % a_in.nsub;
-    };
+    // (Tried in round 4, no effect measured, removed in round 7: a regrouped order in which only 2 or 4 of a pixel tile's channel tiles run
+    // together on an XCD, so that its 4-MB L2 holds fewer channel tiles' weights at one time -- DESIGN.md section 9.)
     if constexpr (CLS) {
         // the classes' tiles differ in length (4, 6 or 9 taps): a contiguous run of tile ids per XCD would give one XCD the short classes and
         // another the long one.  Pixel tiles are dealt round-robin to the XCDs instead, each with all its channel tiles (they share its rows).
         const int j = blockIdx.x >> 3;
-        int jm = j / a_in.n_tiles, nt_ = j - jm * a_in.n_tiles;
-        if (a_in.nsub) regroup(j, a_in.n_tiles, jm, nt_);
+        const int jm = j / a_in.n_tiles, nt_ = j - jm * a_in.n_tiles;
         logical = (jm * 8 + (int)(blockIdx.x & 7)) * a_in.n_tiles + nt_;
-    } else if (a_in.nsub) {
-        int mt_, nt_;
-        regroup(logical, a_in.n_tiles, mt_, nt_);
-        logical = mt_ * a_in.n_tiles + nt_;        // (a trailing partial group maps past `tiles` only where the plain order would too: see launch)
     }
     if (logical >= tiles) return;
     // CLS: the grid is the concatenation of several window launches (classes); this tile's class supplies the fields that differ
@@ -464,7 +418,6 @@ __global__ __launch_bounds__(512, 1) void conv_planar_kernel(const typename std:
     const int mt = a.n_tiles == 1 ? tile : (a.n_tiles == 2 ? tile >> 1 : (a.n_tiles == 4 ? tile >> 2 : tile / a.n_tiles));
     const int nt = tile - mt * a.n_tiles;
     const int m0 = mt * BM;
-    if (m0 >= a.M) return;                           // (pixel tiles the regrouped tile map pads the grid with)
     if (a.m_gate && m0 >= *a.m_gate) return;         // (gated launch: the tile lies past the valid pixels)
     const int s_begin = ksp * a.kslabs, s_end = min(a.slabs, s_begin + a.kslabs);
 
@@ -1256,525 +1209,20 @@ __global__ __launch_bounds__(512, 1) void conv_planar_kx3_kernel(const typename 
 #endif
 }
 
-// Streaming kernels below: workgroup ids are dealt round-robin to the 8 XCDs; a launch of 8 * per_xcd workgroups maps id ->
-// (id & 7) * per_xcd + (id >> 3), so each XCD works on a contiguous run of pixels (neighbouring rows share input lines in
-// one L2 instead of eight).  Returns -1 for the padding workgroups.
-__device__ __forceinline__ int64_t xcd_contiguous_block(int64_t nblocks)
-{
-    const int64_t per_xcd = (nblocks + 7) >> 3;
-    const int64_t b = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    return b < nblocks ? b : -1;
-}
-
-// fp32 [n pixels][C] (NHWC) -> three bf16 planes [3][C/32][n][32] (entry into the planar format from a foreign producer);
-// thread = 8 channels of one pixel
-__global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, uint8_t* __restrict__ planes, int64_t n, int C,
-                                                           int fmt, int* range_flag)
-{
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c8n = C >> 3;
-    if (idx >= n * c8n) return;
-    const int64_t pix = idx / c8n;
-    const int c8 = (int)(idx - pix * c8n);
-    const float* src = x + pix * C + c8 * 8;
-    const f32x4 a0 = *reinterpret_cast<const f32x4*>(src), a1 = *reinterpret_cast<const f32x4*>(src + 4);
-    const size_t plane_b = (size_t)n * C * 2;
-    uint8_t* dst = planes + (((size_t)(c8 >> 2) * n + pix) * 32 + (c8 & 3) * 8) * 2;
-    const float v8[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-    store_planes8(dst, plane_b, v8, fmt, range_flag, false);
-}
-
-// Bilinear resize (F.interpolate(mode="bilinear", align_corners=False): make_net.py's InterpolateModule between the proto-net
-// convolutions) of an fp32 NHWC tensor straight into planes: thread = 8 channels of one output pixel; the fp32 upsampled
-// tensor (4x the input for the proto-net's x2) is never written or re-read.  Same expression order as the ATen kernel.
-__global__ __launch_bounds__(256) void resize_bilinear_planes_kernel(const float* __restrict__ x, uint8_t* __restrict__ planes, int B, int H,
-                                                                    int W, int C, int Ho, int Wo, float sy, float sx, int fmt,
-                                                                    int* range_flag)
-{
-    const int c8n = C >> 3;
-    const int64_t n = (int64_t)B * Ho * Wo;
-    const int64_t blk = xcd_contiguous_block((n * c8n + 255) >> 8);
-    if (blk < 0) return;
-    const int64_t idx = blk * 256 + threadIdx.x;
-    if (idx >= n * c8n) return;
-    const int64_t pix = idx / c8n;
-    const int c8 = (int)(idx - pix * c8n);
-    const int b = (int)(pix / ((int64_t)Ho * Wo));
-    const int rem = (int)(pix - (int64_t)b * Ho * Wo);
-    const int oy = rem / Wo, ox = rem - oy * Wo;
-    // area_pixel_compute_source_index(scale, dst, align_corners=false, cubic=false): max(0, scale * (dst + 0.5) - 0.5)
-    const float fy = fmaxf(sy * ((float)oy + 0.5f) - 0.5f, 0.0f), fx = fmaxf(sx * ((float)ox + 0.5f) - 0.5f, 0.0f);
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-    const float ly1 = fy - (float)y0, lx1 = fx - (float)x0, ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
-    const float* base = x + (size_t)b * H * W * C + c8 * 8;
-    float v[8];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(base + ((size_t)y0 * W + x0) * C + 4 * h);
-        const f32x4 bq = *reinterpret_cast<const f32x4*>(base + ((size_t)y0 * W + x1) * C + 4 * h);
-        const f32x4 c = *reinterpret_cast<const f32x4*>(base + ((size_t)y1 * W + x0) * C + 4 * h);
-        const f32x4 d = *reinterpret_cast<const f32x4*>(base + ((size_t)y1 * W + x1) * C + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[4 * h + e] = ly0 * (lx0 * a[e] + lx1 * bq[e]) + ly1 * (lx0 * c[e] + lx1 * d[e]);
-    }
-    const size_t plane_b = (size_t)n * C * 2;
-    uint8_t* dst = planes + (((size_t)(c8 >> 2) * n + pix) * 32 + (c8 & 3) * 8) * 2;
-    store_planes8(dst, plane_b, v, fmt, range_flag, true);
-}
-
-// ResNet stem tail (backbone.py:73: relu(bn1(conv1)) -> MaxPool2d(3, 2, 1)) on the raw fp32 NHWC convolution output, written as
-// planes for layer1: y = relu(max over the 3x3 window (stride 2, pad 1) + folded-BN bias).  The bias add and the ReLU are
-// monotone and the bias is per channel, so they commute with the max exactly.  thread = 8 channels of one output pixel.
-__global__ __launch_bounds__(256) void bias_relu_maxpool_planes_kernel(const float* __restrict__ x, const float* __restrict__ bias,
-                                                                      uint8_t* __restrict__ planes, int B, int H, int W, int C, int Ho, int Wo,
-                                                                      int fmt, int* range_flag)
-{
-    const int c8n = C >> 3;
-    const int64_t n = (int64_t)B * Ho * Wo;
-    const int64_t blk = xcd_contiguous_block((n * c8n + 255) >> 8);
-    if (blk < 0) return;
-    const int64_t idx = blk * 256 + threadIdx.x;
-    if (idx >= n * c8n) return;
-    const int64_t pix = idx / c8n;
-    const int c8 = (int)(idx - pix * c8n);
-    const int b = (int)(pix / ((int64_t)Ho * Wo));
-    const int rem = (int)(pix - (int64_t)b * Ho * Wo);
-    const int oy = rem / Wo, ox = rem - oy * Wo;
-    const float* base = x + (size_t)b * H * W * C + c8 * 8;
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = -__builtin_inff();
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-        const int iy = 2 * oy - 1 + dy;
-        if ((unsigned)iy >= (unsigned)H) continue;
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const int ix = 2 * ox - 1 + dx;
-            if ((unsigned)ix >= (unsigned)W) continue;
-            const f32x4 a = *reinterpret_cast<const f32x4*>(base + ((size_t)iy * W + ix) * C);
-            const f32x4 c = *reinterpret_cast<const f32x4*>(base + ((size_t)iy * W + ix) * C + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { v[e] = fmaxf(v[e], a[e]); v[4 + e] = fmaxf(v[4 + e], c[e]); }
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float t = v[e] + (bias ? bias[c8 * 8 + e] : 0.0f);
-        v[e] = t > 0.0f ? t : 0.0f;
-    }
-    const size_t plane_b = (size_t)n * C * 2;
-    uint8_t* dst = planes + (((size_t)(c8 >> 2) * n + pix) * 32 + (c8 & 3) * 8) * 2;
-    store_planes8(dst, plane_b, v, fmt, range_flag, true);
-}
-
-// CandidateShift's RoI features (TF_utils.py:30-39: relu(cat(corr, T2S_prev, T2S)) -> mmcv roi_align 7x7, aligned, adaptive
-// sampling grid) written straight into the planes TemporalNet's first convolution reads: no concatenated feature map, no
-// fp32 RoI tensor, no pad / permute / split passes.  Channel order of the planes: [T2S_prev (C1) | T2S (C1) | corr (Cc) |
-// zeros] -- the two feature maps are NHWC, so a lane's 8 channels are two 16-byte loads per corner and the lanes of a
-// wave read one contiguous run; the correlation volume is NCHW (strided, 19 % of the channels).  The arithmetic is
-// roi_align_avg_kernel's, operation for operation (temporal.hip), with the ReLU applied to the sampled inputs.
-struct RoiPlanesArgs {
-    const float* t2s_prev;   // [B][H][W][C1]
-    const float* t2s;        // [B][H][W][C1]
-    const float* corr;       // [B][Cc][H][W], or channels-last [B][H][W][corr_ld] when corr_ld > 0
-    int corr_ld;
-    const float* rois;       // [n][5] = (image, x1, y1, x2, y2) in feature-map pixels
-    uint8_t* planes;         // [P][Cpad/32][n*PH*PW][32]
-    int n, H, W, C1, Cc, Cpad, PH, PW, fmt;
-    int* range_flag;
-};
-
-__global__ __launch_bounds__(256) void roi_align_planes_kernel(const RoiPlanesArgs a)
-{
-    const int gpp = a.Cpad >> 3;                                   // 8-channel groups per output pixel
-    const int64_t npix = (int64_t)a.n * a.PH * a.PW;
-    const int64_t blk = xcd_contiguous_block((npix * gpp + 255) >> 8);
-    if (blk < 0) return;
-    const int64_t idx = blk * 256 + threadIdx.x;
-    if (idx >= npix * gpp) return;
-    const int64_t pix = idx / gpp;
-    const int g = (int)(idx - pix * gpp);
-    const int ri = (int)(pix / (a.PH * a.PW));
-    const int pp = (int)(pix - (int64_t)ri * a.PH * a.PW);
-    const int py = pp / a.PW, px = pp - py * a.PW;
-    const float* roi = a.rois + 5 * ri;
-    const int b = (int)roi[0];
-    const float sw_ = roi[1] - 0.5f, sh_ = roi[2] - 0.5f, ew_ = roi[3] - 0.5f, eh_ = roi[4] - 0.5f;   // aligned, scale 1
-    const float rw = ew_ - sw_, rh = eh_ - sh_;
-    const float bh = rh / (float)a.PH, bw = rw / (float)a.PW;
-    const int gh = (int)ceilf(rh / (float)a.PH), gw = (int)ceilf(rw / (float)a.PW);
-    const float count = (float)max(gh * gw, 1);
-    const int c0 = g * 8;
-    // source of this lane's 8 channels
-    const bool from_prev = c0 < a.C1, from_cur = !from_prev && c0 < 2 * a.C1;
-    const float* nhwc = from_prev ? a.t2s_prev + (size_t)b * a.H * a.W * a.C1 + c0
-                                  : a.t2s + (size_t)b * a.H * a.W * a.C1 + (c0 - a.C1);
-    const int cc0 = c0 - 2 * a.C1;                                 // first correlation channel of the lane (NCHW source)
-    const float* nchw = a.corr + ((size_t)b * a.Cc + (cc0 > 0 ? cc0 : 0)) * a.H * a.W;
-    const float* cl = a.corr + (size_t)b * a.H * a.W * a.corr_ld + (cc0 > 0 ? cc0 : 0);        // channels-last source of the lane's 8 channels
-    const int HW = a.H * a.W;
-    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int iy = 0; iy < gh; ++iy) {
-        const float ys = sh_ + (float)py * bh + ((float)iy + 0.5f) * bh / (float)gh;
-        for (int ix = 0; ix < gw; ++ix) {
-            const float xs = sw_ + (float)px * bw + ((float)ix + 0.5f) * bw / (float)gw;
-            float y = ys, x = xs;
-            if (y < -1.0f || y > (float)a.H || x < -1.0f || x > (float)a.W) continue;     // the sample contributes 0
-            if (y <= 0.0f) y = 0.0f;
-            if (x <= 0.0f) x = 0.0f;
-            int y_low = (int)y, x_low = (int)x, y_high, x_high;
-            if (y_low >= a.H - 1) { y_high = y_low = a.H - 1; y = (float)y_low; } else y_high = y_low + 1;
-            if (x_low >= a.W - 1) { x_high = x_low = a.W - 1; x = (float)x_low; } else x_high = x_low + 1;
-            const float ly = y - (float)y_low, lx = x - (float)x_low, hy = 1.0f - ly, hx = 1.0f - lx;
-            const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
-            const int o1 = y_low * a.W + x_low, o2 = y_low * a.W + x_high, o3 = y_high * a.W + x_low, o4 = y_high * a.W + x_high;
-            float v1[8], v2[8], v3[8], v4[8];
-            if (from_prev || from_cur) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const f32x4 q1 = *reinterpret_cast<const f32x4*>(nhwc + (size_t)o1 * a.C1 + 4 * h);
-                    const f32x4 q2 = *reinterpret_cast<const f32x4*>(nhwc + (size_t)o2 * a.C1 + 4 * h);
-                    const f32x4 q3 = *reinterpret_cast<const f32x4*>(nhwc + (size_t)o3 * a.C1 + 4 * h);
-                    const f32x4 q4 = *reinterpret_cast<const f32x4*>(nhwc + (size_t)o4 * a.C1 + 4 * h);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { v1[4 * h + e] = q1[e]; v2[4 * h + e] = q2[e]; v3[4 * h + e] = q3[e]; v4[4 * h + e] = q4[e]; }
-                }
-            } else if (a.corr_ld > 0) {
-                // (channels past Cc of the padded row are whatever the buffer holds: masked, never used)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    // a 4-channel group that lies wholly in the zero padding past Cc is not loaded at all: its address may be
-                    // beyond the padded row (Cpad rounds 2*C1 + Cc up to 32, corr_ld only Cc up to 8) or, on the last pixel, the buffer
-                    const int hofs = cc0 + 4 * h < a.Cc ? 4 * h : -cc0;          // all-padding group: re-read channel 0 (masked below)
-                    const f32x4 q1 = *reinterpret_cast<const f32x4*>(cl + (size_t)o1 * a.corr_ld + hofs);
-                    const f32x4 q2 = *reinterpret_cast<const f32x4*>(cl + (size_t)o2 * a.corr_ld + hofs);
-                    const f32x4 q3 = *reinterpret_cast<const f32x4*>(cl + (size_t)o3 * a.corr_ld + hofs);
-                    const f32x4 q4 = *reinterpret_cast<const f32x4*>(cl + (size_t)o4 * a.corr_ld + hofs);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const bool real = cc0 + 4 * h + e < a.Cc;
-                        v1[4 * h + e] = real ? q1[e] : 0.0f; v2[4 * h + e] = real ? q2[e] : 0.0f;
-                        v3[4 * h + e] = real ? q3[e] : 0.0f; v4[4 * h + e] = real ? q4[e] : 0.0f;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const bool real = cc0 + e < a.Cc;
-                    const float* im = nchw + (size_t)(real ? e : 0) * HW;
-                    v1[e] = real ? im[o1] : 0.0f; v2[e] = real ? im[o2] : 0.0f; v3[e] = real ? im[o3] : 0.0f; v4[e] = real ? im[o4] : 0.0f;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                acc[e] += w1 * fmaxf(v1[e], 0.0f) + w2 * fmaxf(v2[e], 0.0f) + w3 * fmaxf(v3[e], 0.0f) + w4 * fmaxf(v4[e], 0.0f);
-        }
-    }
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = acc[e] / count;
-    const size_t plane_b = (size_t)npix * a.Cpad * 2;
-    uint8_t* dst = a.planes + (((size_t)(g >> 2) * npix + pix) * 32 + (g & 3) * 8) * 2;
-    store_planes8(dst, plane_b, v, a.fmt, a.range_flag, false);
-}
-
-// The same, laid out for the memory system (round 5; channels-last correlation volume only).  The kernel above gives a wave 64 channel groups of ONE
-// pixel: its plane stores are sixteen 64-byte pieces in sixteen channel slabs per instruction, and nothing of what neighbouring bins share (the corners of
-// adjacent bins of a RoI are the same feature pixels) is reused inside a workgroup.  Here a workgroup owns 16 consecutive output pixels (two to three rows
-// of a 7 x 7 RoI grid) and every channel slab: lane = 4 pixel + chunk, wave w takes slabs w, w + 4, ... -- a plane store is 1 KB contiguous (16 pixels x
-// 64 B), a corner read 16 full 128-byte lines, and the five slabs of a lane share its RoI arithmetic.  Same expressions per output value: bit-equal.
-__global__ __launch_bounds__(256) void roi_align_planes_tiled_kernel(const RoiPlanesArgs a)
-{
-    const int64_t npix = (int64_t)a.n * a.PH * a.PW;
-    const int64_t blk = xcd_contiguous_block((npix + 15) >> 4);
-    if (blk < 0) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t pix_ = blk * 16 + (lane >> 2);
-    const bool live = pix_ < npix;
-    const int64_t pix = live ? pix_ : npix - 1;
-    const int ck = lane & 3;
-    const int ri = (int)(pix / (a.PH * a.PW));
-    const int pp = (int)(pix - (int64_t)ri * a.PH * a.PW);
-    const int py = pp / a.PW, px = pp - py * a.PW;
-    const float* roi = a.rois + 5 * ri;
-    const int b = (int)roi[0];
-    const float sw_ = roi[1] - 0.5f, sh_ = roi[2] - 0.5f, ew_ = roi[3] - 0.5f, eh_ = roi[4] - 0.5f;   // aligned, scale 1
-    const float rw = ew_ - sw_, rh = eh_ - sh_;
-    const float bh = rh / (float)a.PH, bw = rw / (float)a.PW;
-    const int gh = (int)ceilf(rh / (float)a.PH), gw = (int)ceilf(rw / (float)a.PW);
-    const float count = (float)max(gh * gw, 1);
-    const size_t plane_b = (size_t)npix * a.Cpad * 2;
-    const int nslabs = a.Cpad >> 5;
-    for (int s = wave; s < nslabs; s += 4) {
-        const int g = s * 4 + ck;
-        const int c0 = g * 8;
-        const bool from_prev = c0 < a.C1, from_cur = !from_prev && c0 < 2 * a.C1;
-        const float* nhwc = from_prev ? a.t2s_prev + (size_t)b * a.H * a.W * a.C1 + c0
-                                      : a.t2s + (size_t)b * a.H * a.W * a.C1 + (c0 - a.C1);
-        const int cc0 = c0 - 2 * a.C1;                             // first correlation channel of the lane
-        const float* cl = a.corr + (size_t)b * a.H * a.W * a.corr_ld + (cc0 > 0 ? cc0 : 0);
-        float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int iy = 0; iy < gh; ++iy) {
-            const float ys = sh_ + (float)py * bh + ((float)iy + 0.5f) * bh / (float)gh;
-            for (int ix = 0; ix < gw; ++ix) {
-                const float xs = sw_ + (float)px * bw + ((float)ix + 0.5f) * bw / (float)gw;
-                float y = ys, x = xs;
-                if (y < -1.0f || y > (float)a.H || x < -1.0f || x > (float)a.W) continue;     // the sample contributes 0
-                if (y <= 0.0f) y = 0.0f;
-                if (x <= 0.0f) x = 0.0f;
-                int y_low = (int)y, x_low = (int)x, y_high, x_high;
-                if (y_low >= a.H - 1) { y_high = y_low = a.H - 1; y = (float)y_low; } else y_high = y_low + 1;
-                if (x_low >= a.W - 1) { x_high = x_low = a.W - 1; x = (float)x_low; } else x_high = x_low + 1;
-                const float ly = y - (float)y_low, lx = x - (float)x_low, hy = 1.0f - ly, hx = 1.0f - lx;
-                const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
-                const int o1 = y_low * a.W + x_low, o2 = y_low * a.W + x_high, o3 = y_high * a.W + x_low, o4 = y_high * a.W + x_high;
-                float v1[8], v2[8], v3[8], v4[8];
-                if (from_prev || from_cur) {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const f32x4 q1 = *reinterpret_cast<const f32x4*>(nhwc + (size_t)o1 * a.C1 + 4 * h);
-                        const f32x4 q2 = *reinterpret_cast<const f32x4*>(nhwc + (size_t)o2 * a.C1 + 4 * h);
-                        const f32x4 q3 = *reinterpret_cast<const f32x4*>(nhwc + (size_t)o3 * a.C1 + 4 * h);
-                        const f32x4 q4 = *reinterpret_cast<const f32x4*>(nhwc + (size_t)o4 * a.C1 + 4 * h);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { v1[4 * h + e] = q1[e]; v2[4 * h + e] = q2[e]; v3[4 * h + e] = q3[e]; v4[4 * h + e] = q4[e]; }
-                    }
-                } else {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const int hofs = cc0 + 4 * h < a.Cc ? 4 * h : -cc0;          // all-padding group: re-read channel 0 (masked below)
-                        const f32x4 q1 = *reinterpret_cast<const f32x4*>(cl + (size_t)o1 * a.corr_ld + hofs);
-                        const f32x4 q2 = *reinterpret_cast<const f32x4*>(cl + (size_t)o2 * a.corr_ld + hofs);
-                        const f32x4 q3 = *reinterpret_cast<const f32x4*>(cl + (size_t)o3 * a.corr_ld + hofs);
-                        const f32x4 q4 = *reinterpret_cast<const f32x4*>(cl + (size_t)o4 * a.corr_ld + hofs);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const bool real = cc0 + 4 * h + e < a.Cc;
-                            v1[4 * h + e] = real ? q1[e] : 0.0f; v2[4 * h + e] = real ? q2[e] : 0.0f;
-                            v3[4 * h + e] = real ? q3[e] : 0.0f; v4[4 * h + e] = real ? q4[e] : 0.0f;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    acc[e] += w1 * fmaxf(v1[e], 0.0f) + w2 * fmaxf(v2[e], 0.0f) + w3 * fmaxf(v3[e], 0.0f) + w4 * fmaxf(v4[e], 0.0f);
-            }
-        }
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = acc[e] / count;
-        if (live) {
-            uint8_t* dst = a.planes + (((size_t)s * npix + pix) * 32 + ck * 8) * 2;
-            store_planes8(dst, plane_b, v, a.fmt, a.range_flag, false);
-        }
-    }
-}
-
-// ... and with the RoI's feature patch in LDS (round 5; STM_ROI_TILED=2: built, bit-equal, NOT faster -- kept as the measured alternative).  The bins of a RoI sample the same few feature pixels over
-// and over (49 bins x gh gw samples x 4 corners over a patch of a few dozen pixels): through L1 that is 7 GB of gathers per step for 82 MB of feature
-// maps.  One workgroup per RoI: per 32-channel slab the patch (rows / columns any sample of the RoI can touch, ReLU applied, channels past Cc zero) is
-// copied into LDS once -- 144-byte rows: consecutive pixels start 4 banks apart -- and the 49 bins x 4 chunks gather from there; the output pixels of a
-// RoI are consecutive, so a slab's 49 x 64 B leave as one 3-KB run.  Same expressions in the same order per output value (relu(v) is taken when the
-// patch is staged instead of at every use: the same value): bit-equal to the kernels above.  RoIs whose patch exceeds RP_MAX pixels (a tenth of the
-// frame or more at 24 x 40) take the tiled kernel's direct loads inside the same launch.
-constexpr int RP_MAX = 288, RP_PITCH = 144;
-__global__ __launch_bounds__(256) void roi_align_planes_lds_kernel(const RoiPlanesArgs a)
-{
-    extern __shared__ __align__(16) uint8_t rp_smem[];
-    const int64_t blk = xcd_contiguous_block(a.n);
-    if (blk < 0) return;
-    const int ri = (int)blk;
-    const int tid = threadIdx.x;
-    const int64_t npix = (int64_t)a.n * a.PH * a.PW;
-    const int nb = a.PH * a.PW;                                       // bins (output pixels) of the RoI
-    const float* roi = a.rois + 5 * ri;
-    const int b = (int)roi[0];
-    const float sw_ = roi[1] - 0.5f, sh_ = roi[2] - 0.5f, ew_ = roi[3] - 0.5f, eh_ = roi[4] - 0.5f;   // aligned, scale 1
-    const float rw = ew_ - sw_, rh = eh_ - sh_;
-    const float bh = rh / (float)a.PH, bw = rw / (float)a.PW;
-    const int gh = (int)ceilf(rh / (float)a.PH), gw = (int)ceilf(rw / (float)a.PW);
-    const float count = (float)max(gh * gw, 1);
-    // feature rows / columns a sample of this RoI can read: samples lie in [sh_, eh_] x [sw_, ew_], are clamped to [0, H - 1] x [0, W - 1]
-    // and read (low, low + 1)
-    const int y0 = min(max((int)floorf(fminf(sh_, eh_)), 0), a.H - 1), y1 = min(max((int)floorf(fmaxf(sh_, eh_)) + 1, y0), a.H - 1);
-    const int x0 = min(max((int)floorf(fminf(sw_, ew_)), 0), a.W - 1), x1 = min(max((int)floorf(fmaxf(sw_, ew_)) + 1, x0), a.W - 1);
-    const int ph = y1 - y0 + 1, pw = x1 - x0 + 1;
-    const bool staged = ph * pw <= RP_MAX;                            // (uniform over the workgroup)
-    const int pp = tid >> 2, ck = tid & 3;                            // bin and 8-channel chunk of the compute phase
-    const int py = pp / a.PW, px = pp - py * a.PW;
-    const size_t plane_b = (size_t)npix * a.Cpad * 2;
-    const int nslabs = a.Cpad >> 5;
-    for (int s = 0; s < nslabs; ++s) {
-        const int c0s = s * 32;                                       // first channel of the slab
-        const bool from_prev = c0s < a.C1, from_cur = !from_prev && c0s < 2 * a.C1;
-        const int cc0s = c0s - 2 * a.C1;                              // first correlation channel of the slab
-        const float* src = from_prev ? a.t2s_prev + (size_t)b * a.H * a.W * a.C1 + c0s
-                         : from_cur ? a.t2s + (size_t)b * a.H * a.W * a.C1 + (c0s - a.C1)
-                                    : a.corr + (size_t)b * a.H * a.W * a.corr_ld + cc0s;
-        const int ld = (from_prev || from_cur) ? a.C1 : a.corr_ld;
-        if (staged) {
-            __syncthreads();                                          // the previous slab's gathers are done
-            for (int i = tid; i < ph * pw * 8; i += 256) {
-                const int q = i >> 3, c4 = i & 7;                     // patch pixel, 4-channel piece
-                const int qy = q / pw, qx = q - qy * pw;
-                f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-                const int ch = c4 * 4;
-                if (from_prev || from_cur || cc0s + ch < a.Cc) {      // (a piece wholly past Cc is not loaded: it may lie beyond the padded row)
-                    v = *reinterpret_cast<const f32x4*>(src + (size_t)((y0 + qy) * a.W + x0 + qx) * ld + ch);
-                    if (!(from_prev || from_cur)) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (cc0s + ch + e >= a.Cc) v[e] = 0.0f;
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
-                *reinterpret_cast<f32x4*>(rp_smem + q * RP_PITCH + c4 * 16) = v;
-            }
-            __syncthreads();
-        }
-        if (pp < nb) {
-            const int c0 = c0s + ck * 8, cc0 = c0 - 2 * a.C1;
-            float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int iy = 0; iy < gh; ++iy) {
-                const float ys = sh_ + (float)py * bh + ((float)iy + 0.5f) * bh / (float)gh;
-                for (int ix = 0; ix < gw; ++ix) {
-                    const float xs = sw_ + (float)px * bw + ((float)ix + 0.5f) * bw / (float)gw;
-                    float y = ys, x = xs;
-                    if (y < -1.0f || y > (float)a.H || x < -1.0f || x > (float)a.W) continue;     // the sample contributes 0
-                    if (y <= 0.0f) y = 0.0f;
-                    if (x <= 0.0f) x = 0.0f;
-                    int y_low = (int)y, x_low = (int)x, y_high, x_high;
-                    if (y_low >= a.H - 1) { y_high = y_low = a.H - 1; y = (float)y_low; } else y_high = y_low + 1;
-                    if (x_low >= a.W - 1) { x_high = x_low = a.W - 1; x = (float)x_low; } else x_high = x_low + 1;
-                    const float ly = y - (float)y_low, lx = x - (float)x_low, hy = 1.0f - ly, hx = 1.0f - lx;
-                    const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
-                    float v1[8], v2[8], v3[8], v4[8];
-                    if (staged) {
-                        const uint8_t* r1 = rp_smem + ((y_low - y0) * pw + x_low - x0) * RP_PITCH + ck * 32;
-                        const uint8_t* r2 = rp_smem + ((y_low - y0) * pw + x_high - x0) * RP_PITCH + ck * 32;
-                        const uint8_t* r3 = rp_smem + ((y_high - y0) * pw + x_low - x0) * RP_PITCH + ck * 32;
-                        const uint8_t* r4 = rp_smem + ((y_high - y0) * pw + x_high - x0) * RP_PITCH + ck * 32;
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            const f32x4 q1 = *reinterpret_cast<const f32x4*>(r1 + 16 * h), q2 = *reinterpret_cast<const f32x4*>(r2 + 16 * h);
-                            const f32x4 q3 = *reinterpret_cast<const f32x4*>(r3 + 16 * h), q4 = *reinterpret_cast<const f32x4*>(r4 + 16 * h);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) { v1[4 * h + e] = q1[e]; v2[4 * h + e] = q2[e]; v3[4 * h + e] = q3[e]; v4[4 * h + e] = q4[e]; }
-                        }
-                    } else {
-                        const int o1 = y_low * a.W + x_low, o2 = y_low * a.W + x_high, o3 = y_high * a.W + x_low, o4 = y_high * a.W + x_high;
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            const int chh = ck * 8 + 4 * h;
-                            const bool skip = !(from_prev || from_cur) && cc0 + 4 * h >= a.Cc;
-                            const int hofs = skip ? 0 : chh;
-                            const f32x4 q1 = *reinterpret_cast<const f32x4*>(src + (size_t)o1 * ld + hofs), q2 = *reinterpret_cast<const f32x4*>(src + (size_t)o2 * ld + hofs);
-                            const f32x4 q3 = *reinterpret_cast<const f32x4*>(src + (size_t)o3 * ld + hofs), q4 = *reinterpret_cast<const f32x4*>(src + (size_t)o4 * ld + hofs);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const bool real = from_prev || from_cur || cc0 + 4 * h + e < a.Cc;
-                                v1[4 * h + e] = real ? fmaxf(q1[e], 0.0f) : 0.0f; v2[4 * h + e] = real ? fmaxf(q2[e], 0.0f) : 0.0f;
-                                v3[4 * h + e] = real ? fmaxf(q3[e], 0.0f) : 0.0f; v4[4 * h + e] = real ? fmaxf(q4[e], 0.0f) : 0.0f;
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc[e] += w1 * v1[e] + w2 * v2[e] + w3 * v3[e] + w4 * v4[e];
-                }
-            }
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = acc[e] / count;
-            const int64_t pix = (int64_t)ri * nb + pp;
-            uint8_t* dst = a.planes + (((size_t)s * npix + pix) * 32 + ck * 8) * 2;
-            store_planes8(dst, plane_b, v, a.fmt, a.range_flag, false);
-        }
-    }
-}
-
-// Stem entry (backbone.py:73, the 7x7 / stride-2 convolution on the 3-channel frame): the kw * Cin = 21 values one kernel row
-// reads for output column ox are contiguous in the NHWC frame, starting at column sw*ox - pw.  This kernel lays them out as
-// the 32-channel slab of a planar tensor R[b][y][ox][32] (channels >= kw*Cin zero, columns outside the frame zero), which
-// turns the stem into a (kh x 1) convolution with stride (sh, 1) over R on the planar kernel: K = kh * 32 = 224 for 147
-// real products, no im2col buffer, no library call.  thread = 8 channels of one R pixel.
-__global__ __launch_bounds__(256) void stem_rows_planes_kernel(const float* __restrict__ x, uint8_t* __restrict__ planes, int B, int H, int W,
-                                                              int Cin, int kw, int sw, int pw, int Wo, int fmt, int* range_flag)
-{
-    const int64_t n = (int64_t)B * H * Wo;
-    const int64_t blk = xcd_contiguous_block((n * 4 + 255) >> 8);
-    if (blk < 0) return;
-    const int64_t idx = blk * 256 + threadIdx.x;
-    if (idx >= n * 4) return;
-    const int64_t pix = idx >> 2;
-    const int g = (int)(idx & 3);
-    const int ox = (int)(pix % Wo);
-    const int64_t row = pix / Wo;                                   // b * H + y
-    const float* src = x + row * (int64_t)W * Cin;
-    const int c0 = (sw * ox - pw) * Cin;                            // first float of the patch within the frame row
-    const int lim = W * Cin, real = kw * Cin;
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int j = g * 8 + e, c = c0 + j;
-        v[e] = (j < real && c >= 0 && c < lim) ? src[c] : 0.0f;
-    }
-    const size_t plane_b = (size_t)n * 32 * 2;
-    uint8_t* dst = planes + ((size_t)pix * 32 + g * 8) * 2;
-    store_planes8(dst, plane_b, v, fmt, range_flag, false);
-}
-
-// Weights [Cout][Cin][kh][kw] fp32 -> packed [n_tile][slab][plane][row 0..127][swizzled 16-B chunk][8 bf16]; rows past
-// Cout are zero.  One thread per (n_tile, slab, row, chunk).
-__global__ __launch_bounds__(256) void conv_pack_weights_kernel(const float* __restrict__ w, uint8_t* __restrict__ wp, int Cout,
-                                                                int C, int kh, int kw, int slabs, int n_tiles, int npl, int bn, int fmt,
-                                                                float wscale)
-{
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int per_tile = bn * 4;                       // (row, chunk) pairs of one slab tile
-    const int64_t total = (int64_t)n_tiles * slabs * per_tile;
-    if (idx >= total) return;
-    const int chunk = (int)(idx & 3), row = (int)((idx >> 2) % bn);
-    const int slab = (int)((idx / per_tile) % slabs), nt = (int)((idx / per_tile) / slabs);
-    const int taps = kh * kw;
-    const int cs = slab / taps, tap = slab - cs * taps, c0 = cs * CV_BK + chunk * 8;   // K order: channel slab outer, tap inner
-    const int co = nt * bn + row;
-    unsigned pl[3][4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        f32x2 v = {0.0f, 0.0f};
-        if (co < Cout) {
-            v.x = w[((size_t)co * C + c0 + 2 * e) * (kh * kw) + tap];
-            v.y = w[((size_t)co * C + c0 + 2 * e + 1) * (kh * kw) + tap];
-        }
-        if (fmt >= 1) { pl[2][e] = 0; split2_f16(v * wscale, pl[0][e], pl[1][e]); }
-        else split2(v, pl[0][e], pl[1][e], pl[2][e]);
-    }
-    const int wpl = bn * 64;
-    uint8_t* dst = wp + ((size_t)nt * slabs + slab) * (npl * wpl) + lds_off(row, chunk);
-    for (int p = 0; p < npl; ++p) {
-        u32x4 o = {pl[p][0], pl[p][1], pl[p][2], pl[p][3]};
-        *reinterpret_cast<u32x4*>(dst + p * wpl) = o;
-    }
-}
-
 // Launch tunables: read from the environment ONCE (first launch), never per launch.  Defaults are the measured best (DESIGN.md
 // section 9); the variables exist for A/B runs.  stm_debug_reload_tunables() (capi.hip) makes the next launch re-read them.
 std::atomic<long long> g_kx3_launches{0};      // stm_debug_launch_count(0)
+// Constants that were switches until round 6 (DESIGN.md section 9 keeps what their alternatives measured):
+constexpr int CV_RING64_SMALL = 512;   // grids up to this many workgroups take the ring on 128 x 64 tiles whatever K (round 2 sweep)
+constexpr int CV_SK_TARGET = 256;      // workgroups the split-K rule of the 64-wide tiles aims at (one per CU)
+// (removed with their code in round 7: round 1's split-K rule for every layer, nontemporal plane stores for large outputs -- no gain
+// measured in rounds 2-4 --, the element-wise epilogue as a cross-check form, the regrouped tile map)
 struct ConvTunables {
     int ring = 3;          // STM_CONV_RING: 2 = two-buffer loop on the 128-wide tiles, 3 = three-buffer ring (fp16 formats)
-    int ring64_small = 512; // grids up to this many workgroups take the ring on 128 x 64 tiles whatever K (round 2 sweep; a switch until round 6)
     int ring64 = 3;        // STM_CONV_RING64: 2 never / 4 always the ring on 128 x 64 tiles, 3 = by K length (rule below)
     int splitk = 0;        // STM_CONV_SPLITK: force this many K parts (0 = rule)
-    int sk_rule = 0;       // 1 = round 1's split-K rule of the 64-wide tiles for every layer (kept for the record; a switch until round 6)
-    int sk_target = 256;   // workgroups the split-K rule of the 64-wide tiles aims at (one per CU; a switch until round 6)
     int mg = 0;            // STM_CONV_MG: force 128 (1) or 256 (2) pixel tiles
-    long long nt_mb = 0;   // nontemporal plane stores for outputs of at least this many MB (0 = off: no gain measured in rounds 2-4)
-    int scalar_epilogue = 0;   // element-wise epilogue stores (a cross-check form)
     int abl = 0;           // STM_CONV_ABL (builds with -DSTM_ABLATE only)
-    int nsub = 0;          // 2 / 4 = channel tiles of a pixel tile that share an XCD's L2 at one time (regrouped tile map: no effect measured in round 4)
     int kx3 = 1;           // STM_CONV_KX3: 0 = stride-1 kw = 3 layers on the 256 x 128 ring tiles stay on conv_planar_kernel (1: conv_planar_kx3_kernel, kx-reuse staging)
 };
 ConvTunables read_tunables()
@@ -1806,16 +1254,8 @@ int launch_planar(const typename std::conditional<CLS, PlanarArgsCls, PlanarArgs
     size_t lds = (size_t)ST * (NPL * CV_BM * MG * 64 + NPL * (64 * NJ) * 64);
     const size_t park = (size_t)4 * MG * 64 * (32 * NJ + 4) * sizeof(float);   // the epilogue parks one 64 x 32NJ tile per wave
     if (lds < park) lds = park;
-    // per instantiation AND per device (the attribute belongs to the device's copy of the function); it is sticky, so it is set once --
-    // setting it at each launch only costs host time.  Relaxed atomics: two host threads racing here both set the same value.
-    static std::atomic<bool> lds_reserved[STM_MAX_DEVICES];
-    int dev = 0;
-    const bool have_dev = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < STM_MAX_DEVICES;
-    if (!have_dev || !lds_reserved[dev].load(std::memory_order_relaxed)) {
-        STM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_planar_kernel<NPL, MG, NJ, DT, ST, ABL, DUAL, CLS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds) == hipSuccess, STM_ELAUNCH, "stm_conv2d_planar_f32: cannot reserve %zu bytes of LDS", lds);
-        if (have_dev) lds_reserved[dev].store(true, std::memory_order_relaxed);
-    }
+    const int rc = stm_reserve_lds<conv_planar_kernel<NPL, MG, NJ, DT, ST, ABL, DUAL, CLS>>(lds, "stm_conv2d_planar_f32");
+    if (rc != STM_OK) return rc;
     hipLaunchKernelGGL((conv_planar_kernel<NPL, MG, NJ, DT, ST, ABL, DUAL, CLS>), dim3(8 * stm_cdiv(tiles, 8)), dim3(256 * MG), lds, stm_hs(stream), a);
     STM_CHECK_LAUNCH("conv_planar_kernel");
     return STM_OK;
@@ -1849,179 +1289,9 @@ bool geom_ok(const stm_conv_geom* g, const char* who)
 int* stm_internal_range_flag() { return current_range_flag(); }
 extern "C" int stm_planar_set_range_flag(int* device_flag)
 {
-    int dev = 0;
-    STM_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < STM_MAX_DEVICES, STM_EINVAL,
-                "stm_planar_set_range_flag: no current device (or more than %d devices)", STM_MAX_DEVICES);
+    const int dev = stm_current_device();
+    STM_REQUIRE(dev >= 0, STM_EINVAL, "stm_planar_set_range_flag: no current device (or more than %d devices)", STM_MAX_DEVICES);
     g_range_flags[dev] = device_flag;       // the flag of the CURRENT device: kernels launched on device d raise flag d
-    return STM_OK;
-}
-
-extern "C" size_t stm_conv_packed_weight_bytes_tiled(int Cout, int Cin, int kh, int kw, int planes, int tile_n)
-{
-    if (Cout <= 0 || Cin <= 0 || Cin % CV_BK || kh <= 0 || kw <= 0 || (planes < 1 || planes > 3) || (tile_n != 64 && tile_n != 128))
-        return 0;
-    return (size_t)stm_cdiv(Cout, tile_n) * (kh * kw * (Cin / CV_BK)) * planes * (tile_n * 64);
-}
-
-extern "C" size_t stm_conv_packed_weight_bytes(int Cout, int Cin, int kh, int kw, int planes)
-{
-    return stm_conv_packed_weight_bytes_tiled(Cout, Cin, kh, kw, planes, CV_BN);
-}
-
-extern "C" int stm_conv_pack_weights_fmt_f32(const float* weight, void* packed, int Cout, int Cin, int kh, int kw, int tile_n, int fmt,
-                                             float wscale, stm_stream_t stream);
-
-extern "C" int stm_conv_pack_weights_tiled_f32(const float* weight, void* packed, int Cout, int Cin, int kh, int kw, int planes,
-                                               int tile_n, stm_stream_t stream)
-{
-    if (planes == 3) return stm_conv_pack_weights_fmt_f32(weight, packed, Cout, Cin, kh, kw, tile_n, 0, 1.0f, stream);
-    STM_REQUIRE(weight && packed, STM_ENULL, "stm_conv_pack_weights_f32: weight/packed must be non-NULL");
-    STM_REQUIRE(stm_conv_packed_weight_bytes_tiled(Cout, Cin, kh, kw, planes, tile_n) > 0, STM_EINVAL,
-                "stm_conv_pack_weights_f32: bad sizes Cout=%d Cin=%d (multiple of 32) k=%dx%d planes=%d tile_n=%d (64 or 128)", Cout,
-                Cin, kh, kw, planes, tile_n);
-    STM_REQUIRE((uintptr_t)packed % 16 == 0, STM_EINVAL, "stm_conv_pack_weights_f32: packed buffer must be 16-byte aligned");
-    const int slabs = kh * kw * (Cin / CV_BK), n_tiles = stm_cdiv(Cout, tile_n);
-    const int64_t total = (int64_t)n_tiles * slabs * tile_n * 4;
-    hipLaunchKernelGGL(conv_pack_weights_kernel, dim3(stm_cdiv(total, 256)), dim3(256), 0, stm_hs(stream), weight,
-                       static_cast<uint8_t*>(packed), Cout, Cin, kh, kw, slabs, n_tiles, planes, tile_n, 0, 1.0f);
-    STM_CHECK_LAUNCH("conv_pack_weights_kernel");
-    return STM_OK;
-}
-
-extern "C" int stm_conv_pack_weights_fmt_f32(const float* weight, void* packed, int Cout, int Cin, int kh, int kw, int tile_n, int fmt,
-                                             float wscale, stm_stream_t stream)
-{
-    STM_REQUIRE(weight && packed, STM_ENULL, "stm_conv_pack_weights_fmt_f32: weight/packed must be non-NULL");
-    STM_REQUIRE(fmt >= 0 && fmt <= 2, STM_EINVAL, "stm_conv_pack_weights_fmt_f32: fmt must be 0 (bf16 x 3), 1 (fp16 x 2) or 2 (fp16 x 1)");
-    const int planes = fmt == 1 ? 2 : (fmt == 2 ? 1 : 3);
-    STM_REQUIRE(stm_conv_packed_weight_bytes_tiled(Cout, Cin, kh, kw, planes, tile_n) > 0, STM_EINVAL,
-                "stm_conv_pack_weights_fmt_f32: bad sizes Cout=%d Cin=%d (multiple of 32) k=%dx%d tile_n=%d (64 or 128)", Cout, Cin, kh, kw,
-                tile_n);
-    STM_REQUIRE((uintptr_t)packed % 16 == 0, STM_EINVAL, "stm_conv_pack_weights_fmt_f32: packed buffer must be 16-byte aligned");
-    STM_REQUIRE(fmt == 0 || (wscale > 0.0f && wscale < 3.0e38f), STM_EINVAL, "stm_conv_pack_weights_fmt_f32: bad weight scale");
-    const int slabs = kh * kw * (Cin / CV_BK), n_tiles = stm_cdiv(Cout, tile_n);
-    const int64_t total = (int64_t)n_tiles * slabs * tile_n * 4;
-    hipLaunchKernelGGL(conv_pack_weights_kernel, dim3(stm_cdiv(total, 256)), dim3(256), 0, stm_hs(stream), weight,
-                       static_cast<uint8_t*>(packed), Cout, Cin, kh, kw, slabs, n_tiles, planes, tile_n, fmt, fmt >= 1 ? wscale : 1.0f);
-    STM_CHECK_LAUNCH("conv_pack_weights_kernel");
-    return STM_OK;
-}
-
-extern "C" int stm_conv_pack_weights_f32(const float* weight, void* packed, int Cout, int Cin, int kh, int kw, int planes,
-                                         stm_stream_t stream)
-{
-    return stm_conv_pack_weights_tiled_f32(weight, packed, Cout, Cin, kh, kw, planes, CV_BN, stream);
-}
-
-extern "C" int stm_split_planes_fmt_f32(const float* x, void* planes, int64_t n_pixels, int C, int fmt, stm_stream_t stream);
-extern "C" int stm_split_bf16_planes_f32(const float* x, void* planes, int64_t n_pixels, int C, stm_stream_t stream)
-{
-    return stm_split_planes_fmt_f32(x, planes, n_pixels, C, 0, stream);
-}
-
-extern "C" int stm_split_planes_fmt_f32(const float* x, void* planes, int64_t n_pixels, int C, int fmt, stm_stream_t stream)
-{
-    STM_REQUIRE(fmt >= 0 && fmt <= 2, STM_EINVAL, "stm_split_planes_fmt_f32: fmt must be 0 (bf16 x 3), 1 (fp16 x 2) or 2 (fp16 x 1)");
-    STM_REQUIRE(x && planes, STM_ENULL, "stm_split_bf16_planes_f32: x/planes must be non-NULL");
-    STM_REQUIRE(n_pixels > 0 && C > 0 && C % 32 == 0, STM_EINVAL, "stm_split_bf16_planes_f32: n_pixels (%lld) > 0 and C (%d) a multiple of 32",
-                (long long)n_pixels, C);
-    STM_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)planes % 16 == 0, STM_EINVAL, "stm_split_bf16_planes_f32: 16-byte alignment required");
-    hipLaunchKernelGGL(split_planes_kernel, dim3(stm_cdiv(n_pixels * (C / 8), 256)), dim3(256), 0, stm_hs(stream), x,
-                       static_cast<uint8_t*>(planes), n_pixels, C, fmt, current_range_flag());
-    STM_CHECK_LAUNCH("split_planes_kernel");
-    return STM_OK;
-}
-
-extern "C" int stm_resize_bilinear_planes_f32(const float* x, void* planes, int B, int H, int W, int C, int Ho, int Wo, int fmt,
-                                              stm_stream_t stream)
-{
-    STM_REQUIRE(fmt >= 0 && fmt <= 2, STM_EINVAL, "stm_resize_bilinear_planes_f32: fmt must be 0, 1 or 2");
-    STM_REQUIRE(x && planes, STM_ENULL, "stm_resize_bilinear_planes_f32: x/planes must be non-NULL");
-    STM_REQUIRE(B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 32 == 0, STM_EINVAL,
-                "stm_resize_bilinear_planes_f32: sizes must be positive and C (%d) a multiple of 32", C);
-    STM_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)planes % 16 == 0, STM_EINVAL, "stm_resize_bilinear_planes_f32: 16-byte alignment required");
-    const int64_t n = (int64_t)B * Ho * Wo;
-    // scale as ATen computes it for align_corners=false without an explicit scale factor: input size / output size
-    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-    hipLaunchKernelGGL(resize_bilinear_planes_kernel, dim3(8 * stm_cdiv(stm_cdiv(n * (C / 8), 256), 8)), dim3(256), 0, stm_hs(stream), x,
-                       static_cast<uint8_t*>(planes), B, H, W, C, Ho, Wo, sy, sx, fmt, current_range_flag());
-    STM_CHECK_LAUNCH("resize_bilinear_planes_kernel");
-    return STM_OK;
-}
-
-extern "C" int stm_bias_relu_maxpool_planes_f32(const float* x, const float* bias, void* planes, int B, int H, int W, int C, int fmt,
-                                                stm_stream_t stream)
-{
-    STM_REQUIRE(fmt >= 0 && fmt <= 2, STM_EINVAL, "stm_bias_relu_maxpool_planes_f32: fmt must be 0, 1 or 2");
-    STM_REQUIRE(x && planes, STM_ENULL, "stm_bias_relu_maxpool_planes_f32: x/planes must be non-NULL");
-    STM_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 32 == 0, STM_EINVAL,
-                "stm_bias_relu_maxpool_planes_f32: sizes must be positive and C (%d) a multiple of 32", C);
-    STM_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)planes % 16 == 0, STM_EINVAL, "stm_bias_relu_maxpool_planes_f32: 16-byte alignment required");
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;     // MaxPool2d(kernel 3, stride 2, padding 1), floor mode
-    const int64_t n = (int64_t)B * Ho * Wo;
-    hipLaunchKernelGGL(bias_relu_maxpool_planes_kernel, dim3(8 * stm_cdiv(stm_cdiv(n * (C / 8), 256), 8)), dim3(256), 0, stm_hs(stream), x, bias,
-                       static_cast<uint8_t*>(planes), B, H, W, C, Ho, Wo, fmt, current_range_flag());
-    STM_CHECK_LAUNCH("bias_relu_maxpool_planes_kernel");
-    return STM_OK;
-}
-
-extern "C" int stm_roi_align_planes_nhwc_f32(const float* t2s_prev, const float* t2s, const float* corr, int corr_ld, const float* rois,
-                                             void* planes, int B, int H, int W, int C1, int Cc, int n, int PH, int PW, int fmt, stm_stream_t stream);
-extern "C" int stm_roi_align_planes_f32(const float* t2s_prev, const float* t2s, const float* corr, const float* rois, void* planes, int B,
-                                        int H, int W, int C1, int Cc, int n, int PH, int PW, int fmt, stm_stream_t stream)
-{
-    return stm_roi_align_planes_nhwc_f32(t2s_prev, t2s, corr, 0, rois, planes, B, H, W, C1, Cc, n, PH, PW, fmt, stream);
-}
-
-extern "C" int stm_roi_align_planes_nhwc_f32(const float* t2s_prev, const float* t2s, const float* corr, int corr_ld, const float* rois,
-                                             void* planes, int B, int H, int W, int C1, int Cc, int n, int PH, int PW, int fmt, stm_stream_t stream)
-{
-    STM_REQUIRE(corr_ld == 0 || (corr_ld >= (Cc + 7) / 8 * 8 && corr_ld % 4 == 0 && (uintptr_t)corr % 16 == 0), STM_EINVAL,
-                "stm_roi_align_planes_nhwc_f32: corr_ld must be 0 (NCHW) or a multiple of 4 >= Cc rounded up to 8, corr 16-byte aligned");
-    STM_REQUIRE(fmt >= 0 && fmt <= 2, STM_EINVAL, "stm_roi_align_planes_f32: fmt must be 0, 1 or 2");
-    STM_REQUIRE(t2s_prev && t2s && corr && rois && planes, STM_ENULL, "stm_roi_align_planes_f32: NULL argument");
-    STM_REQUIRE(B > 0 && H > 0 && W > 0 && C1 > 0 && C1 % 8 == 0 && Cc > 0 && n > 0 && PH > 0 && PW > 0, STM_EINVAL,
-                "stm_roi_align_planes_f32: bad sizes (C1 = %d must be a multiple of 8)", C1);
-    STM_REQUIRE((uintptr_t)t2s_prev % 16 == 0 && (uintptr_t)t2s % 16 == 0 && (uintptr_t)planes % 16 == 0, STM_EINVAL,
-                "stm_roi_align_planes_f32: 16-byte alignment required");
-    RoiPlanesArgs a;
-    a.t2s_prev = t2s_prev; a.t2s = t2s; a.corr = corr; a.corr_ld = corr_ld; a.rois = rois; a.planes = static_cast<uint8_t*>(planes);
-    a.n = n; a.H = H; a.W = W; a.C1 = C1; a.Cc = Cc; a.Cpad = (2 * C1 + Cc + 31) / 32 * 32; a.PH = PH; a.PW = PW; a.fmt = fmt;
-    a.range_flag = current_range_flag();
-    const int64_t threads = (int64_t)n * PH * PW * (a.Cpad / 8);
-    // STM_ROI_TILED: 0 the first kernel (one pixel's channel groups per wave), 1 (default) the tiled kernel, 2 the RoI's patch in LDS -- bit-equal,
-    // and slower: 399 vs 272 us at 32 clips, 149 vs 80 at 8 (twenty slabs of stage / barrier / gather / barrier per workgroup, 196 of 256 lanes at work)
-    const int roi_form = STM_ENV_INT("STM_ROI_TILED", 1);
-    if (corr_ld > 0 && roi_form == 2 && PH * PW * 4 <= 256 && C1 % 32 == 0 && corr_ld % 32 == 0 && a.Cpad == 2 * C1 + corr_ld) {
-        hipLaunchKernelGGL(roi_align_planes_lds_kernel, dim3(8 * stm_cdiv(n, 8)), dim3(256), (size_t)RP_MAX * RP_PITCH, stm_hs(stream), a);
-        STM_CHECK_LAUNCH("roi_align_planes_lds_kernel");
-        return STM_OK;
-    }
-    if (corr_ld > 0 && roi_form) {
-        const int64_t tiles = ((int64_t)n * PH * PW + 15) >> 4;
-        hipLaunchKernelGGL(roi_align_planes_tiled_kernel, dim3(8 * stm_cdiv(tiles, 8)), dim3(256), 0, stm_hs(stream), a);
-        STM_CHECK_LAUNCH("roi_align_planes_tiled_kernel");
-        return STM_OK;
-    }
-    hipLaunchKernelGGL(roi_align_planes_kernel, dim3(8 * stm_cdiv(stm_cdiv(threads, 256), 8)), dim3(256), 0, stm_hs(stream), a);
-    STM_CHECK_LAUNCH("roi_align_planes_kernel");
-    return STM_OK;
-}
-
-extern "C" int stm_stem_rows_planes_f32(const float* x, void* planes, int B, int H, int W, int Cin, int kw, int sw, int pw, int fmt,
-                                        stm_stream_t stream)
-{
-    STM_REQUIRE(fmt >= 0 && fmt <= 2, STM_EINVAL, "stm_stem_rows_planes_f32: fmt must be 0, 1 or 2");
-    STM_REQUIRE(x && planes, STM_ENULL, "stm_stem_rows_planes_f32: x/planes must be non-NULL");
-    STM_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && kw > 0 && sw > 0 && pw >= 0 && kw * Cin <= 32, STM_EINVAL,
-                "stm_stem_rows_planes_f32: sizes must be positive and kw * Cin (%d) at most 32", kw * Cin);
-    STM_REQUIRE((uintptr_t)planes % 16 == 0, STM_EINVAL, "stm_stem_rows_planes_f32: 16-byte alignment required");
-    const int Wo = (W + 2 * pw - kw) / sw + 1;
-    STM_REQUIRE(Wo > 0 && (int64_t)H * W * Cin < ((int64_t)1 << 31), STM_EINVAL, "stm_stem_rows_planes_f32: bad geometry");
-    const int64_t n = (int64_t)B * H * Wo;
-    hipLaunchKernelGGL(stem_rows_planes_kernel, dim3(8 * stm_cdiv(stm_cdiv(n * 4, 256), 8)), dim3(256), 0, stm_hs(stream), x,
-                       static_cast<uint8_t*>(planes), B, H, W, Cin, kw, sw, pw, Wo, fmt, current_range_flag());
-    STM_CHECK_LAUNCH("stem_rows_planes_kernel");
     return STM_OK;
 }
 
@@ -2164,17 +1434,15 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
     const int64_t ops = g->out_plane_stride ? g->out_plane_stride : o_slabs * out_np * 32;
     const int64_t rps = g->res_plane_stride ? g->res_plane_stride : o_slabs * res_np * 32;
     STM_REQUIRE(xps % 8 == 0, STM_EINVAL, "%s: x_plane_stride must be a multiple of 8 elements", who);
-    const int x_ld = 0;
     PlanarArgs a;
     a.xp = static_cast<const uint8_t*>(x_planes); a.wp = static_cast<const uint8_t*>(packed_weight); a.bias = bias;
     a.res_f32 = residual_f32; a.res_pl = static_cast<const uint8_t*>(residual_planes);
     a.out_f32 = out_f32; a.out_pl = static_cast<uint8_t*>(out_planes);
     a.B = g->B; a.H = g->H; a.W = g->W; a.C = g->C; a.Ho = g->Ho; a.Wo = g->Wo; a.Cout = g->Cout;
     a.kh = g->kh; a.kw = g->kw; a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw;
-    a.x_ld = x_ld; a.out_ld = out_ld; a.res_ld = res_ld; a.relu = relu;
+    a.out_ld = out_ld; a.res_ld = res_ld; a.relu = relu;
     a.x_np = (int)x_np; a.out_np = (int)out_np; a.res_np = (int)res_np;
     a.M = (int)M; a.n_tiles = stm_cdiv(g->Cout, bn); a.slabs = g->kh * g->kw * (g->C / CV_BK);
-    a.nsub = 0;
     a.plane_bytes = (unsigned)plane_bytes;
     a.x_pstride = xps * 2; a.out_pstride = ops * 2; a.res_pstride = rps * 2;
     a.groups = groups; a.cout_g = cout_g; a.ntpg = stm_cdiv(cout_g, bn);
@@ -2185,7 +1453,7 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
     const ConvTunables& tn = tunables();
     a.vec_epilogue = (cout_g % 8 == 0) && (!out_f32 || out_ld % 4 == 0) && (!residual_f32 || res_ld % 4 == 0) && ((uintptr_t)out_f32 % 16 == 0) &&
                      ((uintptr_t)out_planes % 16 == 0) && ((uintptr_t)residual_f32 % 16 == 0) && ((uintptr_t)residual_planes % 16 == 0) &&
-                     (ops % 8 == 0) && (rps % 8 == 0) && !tn.scalar_epilogue;
+                     (ops % 8 == 0) && (rps % 8 == 0);
     STM_REQUIRE(g->kh * g->kw <= 32, STM_EUNSUPPORTED, "%s: more than 32 taps", who);
     a.pointwise = (g->n_levels <= 0 && !win && g->kh == 1 && g->kw == 1 && g->sh == 1 && g->sw == 1 && g->ph == 0 && g->pw == 0) ? 1 : 0;
     a.win_w = win ? g->win_w : 0; a.win_hw = win ? g->win_h * g->win_w : 0; a.win_off = win ? g->win_y0 * g->win_w + g->win_x0 : 0;
@@ -2198,7 +1466,6 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
                 "%s: output format %d cannot be produced by a format-%d layer", who, a.out_fmt, a.fmt);
     a.out_scale = (a.fmt >= 1 && g->out_scale > 0.0f) ? g->out_scale : 1.0f;
     a.range_flag = current_range_flag();
-    a.nt_out = tn.nt_mb > 0 && M * (int64_t)g->Cout * 4 >= tn.nt_mb * 1000000;
     const int want_planes = a.fmt == 0 ? 3 : (a.fmt == 1 ? 2 : 1);
     STM_REQUIRE(g->planes == want_planes || (a.fmt == 0 && g->planes == 2), STM_EINVAL, "%s: format %d has %d planes (planes = %d)", who, a.fmt,
                 want_planes, g->planes);
@@ -2241,10 +1508,10 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
                 // split in 3 vs 20.2 unsplit, 240 x 72 slabs 49.5 vs 39.8, 120 tiles x 64 slabs 29.8 (6 parts) vs 24.4 (2),
                 // 64 x 64 19.4 (6) vs 17.3 (4), 240 x 36 (layer2's 3x3 at 4 clips) 34.3 vs 20.0.
                 // The narrow layers (two-buffer loop) keep round 1's rule: 120 tiles x 72 slabs 36.8 us in 6 parts, 55.2 in 2.
-                if (tn.sk_rule == 1 || !full) {
+                if (!full) {
                     if (tiles <= 256 && a.slabs >= 24) sk = (int)std::min<int64_t>(std::min<int64_t>(8, 768 / tiles), a.slabs / 10);
                 } else if (tiles <= 128 && a.slabs >= 24)
-                    sk = (int)std::min<int64_t>(std::min<int64_t>(8, tn.sk_target / tiles), a.slabs / (tiles <= 40 ? 10 : 16));
+                    sk = (int)std::min<int64_t>(std::min<int64_t>(8, CV_SK_TARGET / tiles), a.slabs / (tiles <= 40 ? 10 : 16));
             } else if (tiles < 128 && a.slabs >= 24) sk = (int)std::min<int64_t>(std::min<int64_t>(8, 256 / tiles), a.slabs / 12);
         }
         if (sk < 2) return;
@@ -2296,27 +1563,17 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
             ac[k].n_cls = ncls[k];
             ac[k].cls_tiles = t0[k];
             ac[k].m_tiles = 0;
-            ac[k].nsub = 0;
             if (k == 0) {
-                ac[0].nsub = ((tn.nsub == 2 || tn.nsub == 4) && a.n_tiles > tn.nsub && a.n_tiles % tn.nsub == 0 && g->groups == 1) ? tn.nsub : 0;
-                // (grid: every XCD gets the same number of pixel tiles x all channel tiles -- a multiple of 32 / nsub of them under the regrouped tile
-                // map, so that its groups are whole; ids past the last tile leave at once)
-                const int pg = ac[0].nsub ? 32 / ac[0].nsub : 1;
+                // (grid: every XCD gets the same number of pixel tiles x all channel tiles; ids past the last tile leave at once)
 #ifndef CLS_ABL
 #define CLS_ABL 0     // timing build (RESULTS WRONG): 16 = the window-set kernel issues its activation DMAs on every third K-slab only
 #endif
-                const int rc0 = launch_planar<2, 2, 2, 1, 3, CLS_ABL, false, true>(ac[0], stm_cdiv(stm_cdiv(t0[0] / a.n_tiles, 8), pg) * pg * 8 * a.n_tiles, stream);
+                const int rc0 = launch_planar<2, 2, 2, 1, 3, CLS_ABL, false, true>(ac[0], stm_cdiv(t0[0] / a.n_tiles, 8) * 8 * a.n_tiles, stream);
                 if (rc0 != STM_OK) return rc0;
             } else {
-                static std::atomic<bool> kx3w_reserved[STM_MAX_DEVICES];
                 constexpr size_t lds = 2 * 2 * 384 * 64 + 3 * KX3_WBUF;      // two 48-KB activation buffers + the weight ring (the epilogue's park needs less)
-                int dev = 0;
-                const bool have_dev = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < STM_MAX_DEVICES;
-                if (!have_dev || !kx3w_reserved[dev].load(std::memory_order_relaxed)) {
-                    STM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_planar_kx3_kernel<KX3_ABL, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                    (int)lds) == hipSuccess, STM_ELAUNCH, "%s: cannot reserve %zu bytes of LDS", who, lds);
-                    if (have_dev) kx3w_reserved[dev].store(true, std::memory_order_relaxed);
-                }
+                const int rc1 = stm_reserve_lds<conv_planar_kx3_kernel<KX3_ABL, true>>(lds, who);
+                if (rc1 != STM_OK) return rc1;
                 hipLaunchKernelGGL((conv_planar_kx3_kernel<KX3_ABL, true>), dim3(stm_cdiv(t0[1] / a.n_tiles, 8) * 8 * a.n_tiles), dim3(512), lds, stm_hs(stream), ac[1]);
                 STM_CHECK_LAUNCH("conv_planar_kx3_kernel<WIN>");
                 g_kx3_launches.fetch_add(1, std::memory_order_relaxed);
@@ -2340,7 +1597,7 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
         // resident workgroup to cover a workgroup's staging gaps: the ring whatever K.  Swept 0 / 128 / 256 / 512 / 1024 on one
         // box (scripts/sweep_ring64_small.sh): 1 clip 399 / 421 / 436 / 456 / 452 frames/s, 2 clips 628 .. 662, 4 clips 836 ..
         // 880, 8 clips flat (1053), 32 clips 1219 .. 1226.
-        const bool small_grid = tiles <= tn.ring64_small;
+        const bool small_grid = tiles <= CV_RING64_SMALL;
         const bool ring = full && (tn.ring64 == 3 ? (small_grid || (a.splitk == 1 && a.slabs >= 12 && a.slabs <= 40)) : tn.ring64 == 4);
         if (dual) {
             if (a.fmt == 2) rc = ring ? launch_planar<1, 1, 1, 1, 3, 0, true>(a, tiles, stream) : launch_planar<1, 1, 1, 1, 2, 0, true>(a, tiles, stream);
@@ -2366,10 +1623,6 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
     const int mg = tn.mg ? tn.mg : (t2 >= 192 ? 2 : 1);
     a.m_tiles = stm_cdiv(M, CV_BM * mg);
     plan_splitk(a.m_tiles * a.n_tiles);
-    // regrouped tile map (nsub > 0): whole groups of 32 / nsub pixel tiles -- the padding tiles leave at once
-    a.nsub = ((tn.nsub == 2 || tn.nsub == 4) && a.splitk == 1 && !a.m_gate && a.n_tiles > tn.nsub && a.n_tiles % tn.nsub == 0 && g->groups == 1 &&
-              a.m_tiles >= 4 * (32 / tn.nsub)) ? tn.nsub : 0;
-    if (a.nsub) a.m_tiles = stm_cdiv(a.m_tiles, 32 / a.nsub) * (32 / a.nsub);
     const int tiles = a.m_tiles * a.n_tiles * a.splitk;
     const bool ring = tn.ring == 3;
 #ifdef STM_ABLATE
@@ -2388,15 +1641,9 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
         // ("same" padding in height too: the kernel decodes a pixel index ONCE and uses it for the output and the staged input rows alike, so
         // Ho == H and Wo == W are part of its contract -- a 3x3 layer with padding (0, 1) stays on conv_planar_kernel)
         // kx-reuse staging (conv_planar_kx3_kernel): one staged run of BM + 2 pixels per (channel slab, ky) serves the three taps of a kernel row
-        static std::atomic<bool> kx3_reserved[STM_MAX_DEVICES];
         constexpr size_t lds = 8 * 64 * (64 + 4) * sizeof(float) > (size_t)KX3_LDS_LOOP ? 8 * 64 * (64 + 4) * sizeof(float) : (size_t)KX3_LDS_LOOP;
-        int dev = 0;
-        const bool have_dev = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < STM_MAX_DEVICES;
-        if (!have_dev || !kx3_reserved[dev].load(std::memory_order_relaxed)) {
-            STM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_planar_kx3_kernel<KX3_ABL, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) ==
-                            hipSuccess, STM_ELAUNCH, "%s: cannot reserve %zu bytes of LDS", who, lds);
-            if (have_dev) kx3_reserved[dev].store(true, std::memory_order_relaxed);
-        }
+        rc = stm_reserve_lds<conv_planar_kx3_kernel<KX3_ABL, false>>(lds, who);
+        if (rc != STM_OK) return rc;
         hipLaunchKernelGGL((conv_planar_kx3_kernel<KX3_ABL, false>), dim3(8 * stm_cdiv(tiles, 8)), dim3(512), lds, stm_hs(stream), a);
         STM_CHECK_LAUNCH("conv_planar_kx3_kernel");
         g_kx3_launches.fetch_add(1, std::memory_order_relaxed);
@@ -2433,17 +1680,6 @@ extern "C" int stm_conv2d_planar_f32(const void* x_planes, const void* packed_we
 // ---- `_f16` entry points ("fp16 variants _f16 for config 5") ------------------------------------------
 // The genuine-fp16 convolution path of BASELINE config 5 under its own names: one fp16 plane per tensor (plane format 2), one
 // v_mfma_f32_16x16x32_f16 product, fp32 accumulation / bias / residual / ReLU.  Thin forms of the format-aware entries above.
-extern "C" int stm_split_planes_f16(const float* x, void* planes, int64_t n_pixels, int C, stm_stream_t stream)
-{
-    return stm_split_planes_fmt_f32(x, planes, n_pixels, C, 2, stream);
-}
-
-extern "C" int stm_conv_pack_weights_f16(const float* weight, void* packed, int Cout, int Cin, int kh, int kw, int tile_n, float wscale,
-                                         stm_stream_t stream)
-{
-    return stm_conv_pack_weights_fmt_f32(weight, packed, Cout, Cin, kh, kw, tile_n, 2, wscale, stream);
-}
-
 extern "C" int stm_conv2d_planar_f16(const void* x_planes, const void* packed_weight, const float* bias, const float* residual_f32,
                                      const void* residual_planes, float* out_f32, void* out_planes, const stm_conv_geom* g, int relu,
                                      void* workspace, size_t workspace_bytes, stm_stream_t stream)

@@ -24,7 +24,6 @@
 #include "planar_common.h"
 
 #include <algorithm>
-#include <atomic>
 
 namespace {
 
@@ -46,7 +45,6 @@ constexpr int CH_RSLOTS = 2;              // half-groups of the shortcut tensor 
 constexpr int CH_PARK_OFF = CH_D * CH_BUF, CH_BIAS_OFF = CH_PARK_OFF + 4 * 8192, CH_LDS = CH_BIAS_OFF + (64 + 256 + 64) * 4;
 static_assert(CH_LDS <= 160 * 1024, "LDS");
 constexpr int CH_CONSUMERS = 4, CH_PRODUCERS = 2, CH_THREADS = 64 * (CH_CONSUMERS + CH_PRODUCERS);
-constexpr int CH_MAX_DEVICES = 32;
 
 struct ChainArgs {
     const uint8_t* xin;      // mid1 planes [2][2][np_in][32]
@@ -715,24 +713,10 @@ static int chain_launch(const char* who, bool proj, const void* mid1_planes, con
     a.dbg = nullptr;
 #endif
     const size_t lds = CH_LDS;
-    static std::atomic<bool> reserved[CH_MAX_DEVICES];
-    static std::atomic<int> n_cus[CH_MAX_DEVICES];
-    int dev = 0;
-    const bool have_dev = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < CH_MAX_DEVICES;
-    if (!have_dev || !reserved[dev].load(std::memory_order_relaxed)) {
-        const void* fns[4] = {reinterpret_cast<const void*>(conv_chain_kernel<true, false>), reinterpret_cast<const void*>(conv_chain_kernel<false, false>),
-                              reinterpret_cast<const void*>(conv_chain_kernel<true, true>), reinterpret_cast<const void*>(conv_chain_kernel<false, true>)};
-        for (const void* fn : fns)
-            STM_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess, STM_ELAUNCH,
-                        "%s: cannot reserve %zu bytes of LDS", who, lds);
-        if (have_dev) reserved[dev].store(true, std::memory_order_relaxed);
-    }
-    int cus = have_dev ? n_cus[dev].load(std::memory_order_relaxed) : 0;
-    if (cus <= 0) {
-        hipDeviceProp_t prop;
-        cus = (have_dev && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        if (have_dev) n_cus[dev].store(cus, std::memory_order_relaxed);
-    }
+    for (const int rc : {stm_reserve_lds<conv_chain_kernel<true, false>>(lds, who), stm_reserve_lds<conv_chain_kernel<false, false>>(lds, who),
+                         stm_reserve_lds<conv_chain_kernel<true, true>>(lds, who), stm_reserve_lds<conv_chain_kernel<false, true>>(lds, who)})
+        if (rc != STM_OK) return rc;
+    const int cus = stm_cu_count();
     const int grid = std::min((a.tiles + 7) / 8 * 8, cus / 8 * 8 > 0 ? cus / 8 * 8 : 8);       // a multiple of 8: the id -> tile map needs id & 7 = XCD
     const dim3 g(grid), b(CH_THREADS);
     if (proj) {

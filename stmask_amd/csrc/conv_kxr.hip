@@ -23,13 +23,11 @@
 #include "planar_common.h"
 
 #include <algorithm>
-#include <atomic>
 
 namespace {
 
 constexpr int KX_CONSUMERS = 4, KX_PRODUCERS = 2, KX_THREADS = 64 * (KX_CONSUMERS + KX_PRODUCERS);
 constexpr int KX_MAX_JOBS = 4;
-constexpr int KX_MAX_DEVICES = 32;
 constexpr int KX_LDS_MAX = 160 * 1024;
 
 // Tile shape of a (kw, planes, channel tiles) combination: each of the 4 consumer waves takes PT pixel tiles of 16 (workgroup tile
@@ -525,22 +523,9 @@ int kxr_launch(KxrArgs a, stm_stream_t stream)
         j.per_xcd = (t0 + 7) / 8;
         a.total += 8 * j.per_xcd;
     }
-    static std::atomic<int> reserved[KX_MAX_DEVICES];      // bytes reserved so far, per instantiation and device
-    int dev = 0;
-    const bool have_dev = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < KX_MAX_DEVICES;
-    if (!have_dev || reserved[dev].load(std::memory_order_relaxed) < (int)lds) {
-        STM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_kxr_kernel<KW, NPL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds) == hipSuccess, STM_ELAUNCH, "stm_conv2d_planar_kxr_f32: cannot reserve %zu bytes of LDS", lds);
-        if (have_dev) reserved[dev].store((int)lds, std::memory_order_relaxed);
-    }
-    // one persistent workgroup per CU (the ring takes most of a CU's LDS)
-    static std::atomic<int> n_cus[KX_MAX_DEVICES];
-    int cus = have_dev ? n_cus[dev].load(std::memory_order_relaxed) : 0;
-    if (cus <= 0) {
-        hipDeviceProp_t prop;
-        cus = (have_dev && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        if (have_dev) n_cus[dev].store(cus, std::memory_order_relaxed);
-    }
+    const int rc = stm_reserve_lds<conv_kxr_kernel<KW, NPL>>(lds, "stm_conv2d_planar_kxr_f32");
+    if (rc != STM_OK) return rc;
+    const int cus = stm_cu_count();      // one persistent workgroup per CU (the ring takes most of a CU's LDS)
     hipLaunchKernelGGL((conv_kxr_kernel<KW, NPL>), dim3(std::min(a.total, std::max(cus / 8 * 8, 8))), dim3(KX_THREADS), lds, stm_hs(stream), a);
     STM_CHECK_LAUNCH("conv_kxr_kernel");
     return STM_OK;

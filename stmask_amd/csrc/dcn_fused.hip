@@ -546,14 +546,8 @@ void pick_patch(int Ho, int Wo, int& TH, int& TW, int DF_TP)
 template <int NPL, bool MASK, int WIDE>
 int df_launch(const FusedArgs& a, size_t lds, hipStream_t stream, const char* who)
 {
-    static std::atomic<int> reserved[32];
-    int dev = 0;
-    const bool have_dev = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 32;
-    if (!have_dev || reserved[dev].load(std::memory_order_relaxed) < (int)lds) {
-        STM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(dcn_fused_kernel<NPL, MASK, WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) ==
-                        hipSuccess, STM_ELAUNCH, "%s: cannot reserve %zu bytes of LDS", who, lds);
-        if (have_dev) reserved[dev].store((int)lds, std::memory_order_relaxed);
-    }
+    const int rc = stm_reserve_lds<dcn_fused_kernel<NPL, MASK, WIDE>>(lds, who);
+    if (rc != STM_OK) return rc;
     const dim3 grid(8 * stm_cdiv((int64_t)a.m_tiles * a.n_tiles, 8));
     hipLaunchKernelGGL((dcn_fused_kernel<NPL, MASK, WIDE>), grid, dim3(512), lds, stream, a);
     STM_CHECK_LAUNCH("dcn_fused_kernel");

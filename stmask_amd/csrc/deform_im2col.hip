@@ -17,7 +17,6 @@
 //                 so the result is exact for ANY offset.
 #include "stm_common.h"
 
-#include <atomic>
 
 namespace {
 
@@ -542,6 +541,19 @@ static int validate_geom(const stm_deform_geom* g, const char* who)
     return STM_OK;
 }
 
+// launch of a tiled im2col kernel (256 threads) with its dynamic LDS reserved where it exceeds the 48 KB a kernel may use without asking
+template <auto Kernel>
+static int imcol_launch(const ImcolArgs& a, dim3 grid, size_t lds, stm_stream_t stream, const char* name)
+{
+    if (lds > 48 * 1024) {
+        const int rc = stm_reserve_lds<Kernel>(lds, "stm_deform_im2col_f32");
+        if (rc != STM_OK) return rc;
+    }
+    hipLaunchKernelGGL(Kernel, grid, dim3(256), lds, stm_hs(stream), a);
+    STM_CHECK_LAUNCH(name);
+    return STM_OK;
+}
+
 extern "C" int stm_deform_im2col_f32(const float* x, const float* offset, int64_t off_bstride, const float* mask,
                                      int64_t mask_bstride, int mask_is_logit, float* cols, const stm_deform_geom* g,
                                      int variant, stm_stream_t stream)
@@ -620,19 +632,9 @@ extern "C" int stm_deform_im2col_f32(const float* x, const float* offset, int64_
             a.th = th3; a.cch = cch3; a.R = R3; a.LW = LW; a.halo = halo; a.tiles_y = tiles3;
             dim3 grid3(tiles3 * (g->C / cch3) * g->B);   // 1-D: the kernel maps ids to tiles XCD-aware
             const int it = stm_cdiv(items3, 256);
-            auto launch = [&](auto kern) {
-                if (lds3 > 48 * 1024)
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              (int)lds3);
-                hipLaunchKernelGGL(kern, grid3, dim3(256), lds3, stm_hs(stream), a);
-            };
-            {
-                if (it <= 1) launch(deform_im2col_lds3<1>);
-                else if (it == 2) launch(deform_im2col_lds3<2>);
-                else launch(deform_im2col_lds3<3>);
-                STM_CHECK_LAUNCH("deform_im2col_lds3");
-                return STM_OK;
-            }
+            if (it <= 1) return imcol_launch<deform_im2col_lds3<1>>(a, grid3, lds3, stream, "deform_im2col_lds3");
+            if (it == 2) return imcol_launch<deform_im2col_lds3<2>>(a, grid3, lds3, stream, "deform_im2col_lds3");
+            return imcol_launch<deform_im2col_lds3<3>>(a, grid3, lds3, stream, "deform_im2col_lds3");
         }
     }
     // Tile choice (scripts/bench_kernels.py --env-sweep on MI355X): 8 channels per workgroup and as many output rows
@@ -666,15 +668,8 @@ extern "C" int stm_deform_im2col_f32(const float* x, const float* offset, int64_
     }
     a.th = th; a.cch = cch; a.R = R; a.LW = LW; a.halo = halo; a.tiles_y = stm_cdiv(g->Ho, th);
     dim3 grid(a.tiles_y * (g->C / cch), g->B);
-    auto launch2 = [&](auto kern, int threads) {
-        if (lds > 48 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, grid, dim3(threads), lds, stm_hs(stream), a);
-    };
-    if (vec) launch2(deform_im2col_lds<4, 256>, 256);
-    else launch2(deform_im2col_lds<1, 256>, 256);
-    STM_CHECK_LAUNCH("deform_im2col_lds");
-    return STM_OK;
+    if (vec) return imcol_launch<deform_im2col_lds<4, 256>>(a, grid, lds, stream, "deform_im2col_lds");
+    return imcol_launch<deform_im2col_lds<1, 256>>(a, grid, lds, stream, "deform_im2col_lds");
 }
 
 extern "C" int stm_validate_deform_geom(const stm_deform_geom* g) { return validate_geom(g, "stm_deform_geom"); }
@@ -701,8 +696,7 @@ struct SampleArgs {
     int x_ld, kw, out_pix0;      // pixel stride of x (floats); kernel width (tap k = (k / kw, k % kw)); first output pixel in the planes
     int om_ld, out_np, M, fmt;   // fmt 0: three bf16 planes, 1: two fp16 planes, 2: one fp16 plane
     int* range_flag;             // fmt 1: raised when a sampled value has no fp16 representation (may be null)
-    int xcd, per_xcd, nt;        // XCD-contiguous workgroup order (workgroups per XCD); nontemporal column stores
-    int prefetch;                // streaming touch of the centre pixels ahead of the gathers
+    int per_xcd, nt;             // XCD-contiguous workgroup order: workgroups per XCD; nontemporal column stores
     long long out_pstride;   // bytes
 };
 
@@ -711,7 +705,7 @@ __device__ __forceinline__ void split2_planes_f16(float a, float b, unsigned& p0
 {
     const f32x2v v = {a, b};
     const f16x2v h = __builtin_convertvector(v, f16x2v);
-    const f32x2v r1 = (v - __builtin_convertvector(h, f32x2v)) * 2048.0f;   // STM_F16_LOW_SCALE of conv_bf16x.hip
+    const f32x2v r1 = (v - __builtin_convertvector(h, f32x2v)) * 2048.0f;   // STM_F16_LOW_SCALE of planar_common.h
     const f16x2v l = __builtin_convertvector(r1, f16x2v);
     p0 = __builtin_bit_cast(unsigned, h);
     p1 = __builtin_bit_cast(unsigned, l);
@@ -740,11 +734,8 @@ __global__ __launch_bounds__(256) void dcn_sample_planar_kernel(const SampleArgs
     const int lane = threadIdx.x & 63, sl = lane % LPP;
     // workgroup ids are dealt round-robin to the 8 XCDs: give each XCD a contiguous run of pixels, so that an input row is
     // gathered through one L2 instead of all eight
-    int bid = blockIdx.x;
-    if (a.xcd) {
-        bid = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
-        if ((int)(blockIdx.x >> 3) >= a.per_xcd) return;
-    }
+    const int bid = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
+    if ((int)(blockIdx.x >> 3) >= a.per_xcd) return;
     const int m = (bid * 4 + (threadIdx.x >> 6)) * PPW + lane / LPP;
     if (bid * 4 * PPW >= a.M) return;
     const bool live = m < a.M;
@@ -758,11 +749,8 @@ __global__ __launch_bounds__(256) void dcn_sample_planar_kernel(const SampleArgs
     // into L2 with full memory-level parallelism.  With the input cold in HBM the gathers' own first-touch misses cost as
     // much as the whole rest of the kernel (230 vs 119 us on layer2 at batch 32); the value is only kept alive, never used.
     typedef float f32x4p __attribute__((ext_vector_type(4)));
-    f32x4p pf = {0.f, 0.f, 0.f, 0.f};
-    if (a.prefetch) {
-        const int cy = min(max(ho * a.sh - a.ph + a.dh, 0), a.H - 1), cx = min(max(wo * a.sw - a.pw + a.dw, 0), a.W - 1);
-        pf = *reinterpret_cast<const f32x4p*>(xb + (size_t)(cy * a.W + cx) * a.x_ld);
-    }
+    const int cy = min(max(ho * a.sh - a.ph + a.dh, 0), a.H - 1), cx = min(max(wo * a.sw - a.pw + a.dw, 0), a.W - 1);
+    const f32x4p pf = *reinterpret_cast<const f32x4p*>(xb + (size_t)(cy * a.W + cx) * a.x_ld);
     // sub-lane k (< 9) of each pixel group prepares tap k: corner weights with the mask folded in and clamped corner
     // offsets; the tap loop broadcasts them inside the group, so the per-tap work is 8 vector loads, 32 FMAs, the split and
     // three 16-byte stores per lane -- not LPP copies of the coefficient arithmetic
@@ -853,11 +841,8 @@ __global__ __launch_bounds__(256) void dcn_sample_planar_f16x2_kernel(const Samp
     constexpr int PPW = 64 / LPP;
     static_assert(K <= LPP, "one sub-lane per tap");
     const int lane = threadIdx.x & 63, sl = lane % LPP;
-    int bid = blockIdx.x;
-    if (a.xcd) {
-        bid = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
-        if ((int)(blockIdx.x >> 3) >= a.per_xcd) return;
-    }
+    const int bid = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
+    if ((int)(blockIdx.x >> 3) >= a.per_xcd) return;
     const int m = (bid * 4 + (threadIdx.x >> 6)) * PPW + lane / LPP;
     if (bid * 4 * PPW >= a.M) return;
     const bool live = m < a.M;
@@ -868,11 +853,8 @@ __global__ __launch_bounds__(256) void dcn_sample_planar_f16x2_kernel(const Samp
     const float* xb = a.x + (size_t)b * a.H * a.W * a.x_ld + sl * 8;
     typedef float f32x4v __attribute__((ext_vector_type(4)));
     typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-    f32x4v pf = {0.f, 0.f, 0.f, 0.f};
-    if (a.prefetch) {
-        const int cy = min(max(ho * a.sh - a.ph + a.dh, 0), a.H - 1), cx = min(max(wo * a.sw - a.pw + a.dw, 0), a.W - 1);
-        pf = *reinterpret_cast<const f32x4v*>(xb + (size_t)(cy * a.W + cx) * a.x_ld);
-    }
+    const int cy = min(max(ho * a.sh - a.ph + a.dh, 0), a.H - 1), cx = min(max(wo * a.sw - a.pw + a.dw, 0), a.W - 1);
+    const f32x4v pf = *reinterpret_cast<const f32x4v*>(xb + (size_t)(cy * a.W + cx) * a.x_ld);
     float cw1 = 0.f, cw2 = 0.f, cw3 = 0.f, cw4 = 0.f;
     int ca1 = 0, ca2 = 0, ca3 = 0, ca4 = 0;
     if (sl < K) {
@@ -1010,8 +992,8 @@ __global__ __launch_bounds__(256) void dcn_sample_planar_lds_kernel(const Sample
     SlCoef* coef = reinterpret_cast<SlCoef*>(sl_smem);               // [TP][K]
     float* reg = reinterpret_cast<float*>(sl_smem + (((size_t)TP * K * sizeof(SlCoef) + 15) & ~(size_t)15));   // [rh][rw][CCH]
     const int64_t nblk = (int64_t)a.B * aa.tiles_y * aa.tiles_x;
-    const int64_t blk = a.xcd ? stm_xcd_block(nblk) : (int64_t)blockIdx.x;
-    if (blk < 0 || blk >= nblk) return;
+    const int64_t blk = stm_xcd_block(nblk);
+    if (blk < 0) return;
     const int tx = (int)(blk % aa.tiles_x), ty = (int)((blk / aa.tiles_x) % aa.tiles_y), b = (int)(blk / ((int64_t)aa.tiles_x * aa.tiles_y));
     const int oy0 = ty * TH, ox0 = tx * SL_TW;
     const int in_y0 = oy0 * a.sh - a.ph - SL_HALO, in_x0 = ox0 * a.sw - a.pw - SL_HALO;
@@ -1201,14 +1183,11 @@ extern "C" int stm_deform_sample_planar_f32(const float* x, int x_ld, const floa
     a.out_pstride = (out_plane_stride > 0 ? out_plane_stride : (long long)(K * g->C / 32) * a.out_np * 32) * 2;
     const int ppw = 512 / g->C;                                  // pixels per wave
     const int nblk = stm_cdiv(M, 4 * ppw);
-    // XCD-contiguous block order, nontemporal column stores (-1: by size), centre-pixel touch: A/B switches until round 6, all on since round 2
-    const int env_xcd = 1, env_nt = -1, env_prefetch = 1;
-    a.xcd = env_xcd;
+    // XCD-contiguous block order and the centre-pixel touch were A/B switches until round 6, both on since round 2: the kernels know no other form
     // nontemporal column stores: 248 -> 115 us on layer2 at batch 32 together with the XCD order (5.6 TB/s algorithmic), but
     // 34 -> 45 us with 512 channels (one pixel per wave, 1-KB runs per tap) -- so up to 256 channels only
-    a.nt = env_nt >= 0 ? env_nt : (g->C <= 256 ? 1 : 0);
+    a.nt = g->C <= 256 ? 1 : 0;
     a.per_xcd = stm_cdiv(nblk, 8);
-    a.prefetch = env_prefetch;
     // LDS-staged form (STM_DCN_LDS=1; default off): tiles of 4 x 16 (stride 1) or 2 x 16 (stride 2) output pixels, 32-channel chunks.
     // Measured at batch 32 on cold inputs (scripts/ab_dcn_lds.py, profiles/r03_dcn_sampler_ab.txt): 241 vs 253 us and 183 vs 177 us on
     // the two layer2 shapes, 1.1-2.7x SLOWER on the smaller layers (few tiles, two waves per SIMD).  Its ablations say why the staging
@@ -1229,20 +1208,12 @@ extern "C" int stm_deform_sample_planar_f32(const float* x, int x_ld, const floa
         const size_t lds = coef_b + (size_t)aa.rh * aa.rw * SL_CCH * sizeof(float);
         if (lds <= 80 * 1024 && aa.rh * aa.rw * (SL_CCH / 4) <= 16 * 256) {
             const int64_t nb = (int64_t)g->B * aa.tiles_y * aa.tiles_x;
-            const dim3 grid_l(a.xcd ? stm_xcd_grid(nb) : (unsigned)nb);
-            static std::atomic<int> reserved[4][32];
-            int dev = 0;
-            const bool have_dev = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 32;
-            const int which = (has_mask ? 2 : 0) + (aa.th == 4 ? 1 : 0);   // (tile height 4: stride 1, 2: stride 2)
-            if (!have_dev || reserved[which][dev].load(std::memory_order_relaxed) < (int)lds) {
-                const void* fn = has_mask ? (aa.th == 4 ? reinterpret_cast<const void*>(dcn_sample_planar_lds_kernel<true, 4>)
-                                                        : reinterpret_cast<const void*>(dcn_sample_planar_lds_kernel<true, 2>))
-                                          : (aa.th == 4 ? reinterpret_cast<const void*>(dcn_sample_planar_lds_kernel<false, 4>)
-                                                        : reinterpret_cast<const void*>(dcn_sample_planar_lds_kernel<false, 2>));
-                STM_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess, STM_ELAUNCH,
-                            "%s: cannot reserve %zu bytes of LDS", who, lds);
-                if (have_dev) reserved[which][dev].store((int)lds, std::memory_order_relaxed);
-            }
+            const dim3 grid_l(stm_xcd_grid(nb));
+            const int rc = has_mask ? (aa.th == 4 ? stm_reserve_lds<dcn_sample_planar_lds_kernel<true, 4>>(lds, who)       // (tile height 4: stride 1, 2: stride 2)
+                                                  : stm_reserve_lds<dcn_sample_planar_lds_kernel<true, 2>>(lds, who))
+                                    : (aa.th == 4 ? stm_reserve_lds<dcn_sample_planar_lds_kernel<false, 4>>(lds, who)
+                                                  : stm_reserve_lds<dcn_sample_planar_lds_kernel<false, 2>>(lds, who));
+            if (rc != STM_OK) return rc;
             if (has_mask && aa.th == 4) hipLaunchKernelGGL((dcn_sample_planar_lds_kernel<true, 4>), grid_l, dim3(256), lds, stm_hs(stream), aa);
             else if (has_mask) hipLaunchKernelGGL((dcn_sample_planar_lds_kernel<true, 2>), grid_l, dim3(256), lds, stm_hs(stream), aa);
             else if (aa.th == 4) hipLaunchKernelGGL((dcn_sample_planar_lds_kernel<false, 4>), grid_l, dim3(256), lds, stm_hs(stream), aa);
@@ -1251,13 +1222,12 @@ extern "C" int stm_deform_sample_planar_f32(const float* x, int x_ld, const floa
             return STM_OK;
         }
     }
-    const dim3 grid(a.xcd ? 8 * a.per_xcd : nblk);
+    const dim3 grid(8 * a.per_xcd);
     // Sampler form: 0 = the run-time-format kernel (rounds 1-3: 64 registers, 8 waves per SIMD); the straight-line fp16x2 kernel: 1 = registers as
-    // the compiler likes (116: 4 waves per SIMD, it hoists the next taps' loads by itself), 2 = explicit one-tap look-ahead (143: 3 waves).  Default
-    // (-1): form 2 on the stride-2 layers of 256 / 512 channels, form 0 elsewhere -- profiles/r04_dcn_sampler_forms.txt: 123 vs 127 us and 65 vs 77 us
+    // the compiler likes (116: 4 waves per SIMD, it hoists the next taps' loads by itself), 2 = explicit one-tap look-ahead (143: 3 waves).  The
+    // rule: form 2 on the stride-2 layers of 256 / 512 channels, form 0 elsewhere -- profiles/r04_dcn_sampler_forms.txt: 123 vs 127 us and 65 vs 77 us
     // there, 20-50 % slower on the stride-1 layers; forms capped to 6 / 8 waves per SIMD spilled (148 / 220 B per lane) and ran at half the rate.
-    int variant = -1;        // (-1: the rule below; 0 / 1 / 2 forced one form everywhere -- an environment switch until round 6)
-    if (variant < 0) variant = (g->sh == 2 && g->C >= 256) ? 2 : 0;
+    const int variant = (g->sh == 2 && g->C >= 256) ? 2 : 0;
     if (variant && fmt == 1 && has_mask && K == 9 && (g->C == 128 || g->C == 256 || g->C == 512)) {
 #define STM_DSV(LPP_) \
         if (variant == 2) hipLaunchKernelGGL((dcn_sample_planar_f16x2_kernel<LPP_, 9, true, 1>), grid, dim3(256), 0, stm_hs(stream), a); \

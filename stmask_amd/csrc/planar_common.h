@@ -1,5 +1,5 @@
-// planar_common.h -- device helpers shared by the planar convolution kernels (conv_bf16x.hip, conv_kxr.hip): vector types, the
-// LDS chunk swizzle, the plane splits.  Everything is internal to the library (anonymous namespace per translation unit).
+// planar_common.h -- device helpers shared by the planar convolution kernels and the producers of their layouts (conv_bf16x.hip,
+// conv_kxr.hip, planar_prep.hip, ...): vector types, the LDS chunk swizzle, the plane splits, the 8-channel plane store.  Everything is internal to the library (anonymous namespace per translation unit).
 #pragma once
 #include "stm_common.h"
 
@@ -66,6 +66,32 @@ __device__ __forceinline__ void f16_range_check8(const float (&v)[8], int* flag)
 #pragma unroll
     for (int e = 0; e < 8; ++e) m = max(m, __builtin_bit_cast(unsigned, v[e]) & 0x7fffffffu);
     if (m > 0x477fe000u && flag) *reinterpret_cast<volatile int*>(flag) = 1;
+}
+
+// Write 8 consecutive channels of one pixel into a planar tensor: dst = address of the 16-byte group in plane 0, plane_b = bytes
+// between planes.  fmt 0: three bf16 planes; 1: two fp16 planes (h, (x - h) * 2048); 2: ONE fp16 plane (h only -- the genuine
+// fp16 activation format of BASELINE config 5; plane 0 of a fmt-1 tensor is a valid fmt-2 tensor).  nt: nontemporal stores.
+__device__ __forceinline__ void store_planes8(uint8_t* dst, size_t plane_b, const float (&v)[8], int fmt, int* range_flag, bool nt)
+{
+    unsigned q0[4], q1[4], q2[4];
+    if (fmt == 0) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) split2(f32x2{v[2 * e], v[2 * e + 1]}, q0[e], q1[e], q2[e]);
+    } else {
+        f16_range_check8(v, range_flag);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) split2_f16(f32x2{v[2 * e], v[2 * e + 1]}, q0[e], q1[e]);
+    }
+    const int np = fmt == 0 ? 3 : (fmt == 1 ? 2 : 1);
+    if (nt) {
+        __builtin_nontemporal_store(u32x4{q0[0], q0[1], q0[2], q0[3]}, reinterpret_cast<u32x4*>(dst));
+        if (np > 1) __builtin_nontemporal_store(u32x4{q1[0], q1[1], q1[2], q1[3]}, reinterpret_cast<u32x4*>(dst + plane_b));
+        if (np > 2) __builtin_nontemporal_store(u32x4{q2[0], q2[1], q2[2], q2[3]}, reinterpret_cast<u32x4*>(dst + 2 * plane_b));
+    } else {
+        *reinterpret_cast<u32x4*>(dst) = u32x4{q0[0], q0[1], q0[2], q0[3]};
+        if (np > 1) *reinterpret_cast<u32x4*>(dst + plane_b) = u32x4{q1[0], q1[1], q1[2], q1[3]};
+        if (np > 2) *reinterpret_cast<u32x4*>(dst + 2 * plane_b) = u32x4{q2[0], q2[1], q2[2], q2[3]};
+    }
 }
 
 }  // namespace

@@ -593,11 +593,11 @@ int next_pow2(int v)
 
 size_t nms_lds_bytes(int Kp, int top_k) { return (size_t)Kp * 8 + (size_t)top_k * (16 + 4 + 4) + 4 * (NMS_WAVES + 16); }
 
-template <typename F>
-void allow_big_lds(F kernel, size_t bytes)
+// dynamic LDS beyond the 48 KB every kernel may use without asking (reserved once per kernel, device and size)
+template <auto Kernel>
+int allow_big_lds(size_t bytes, const char* who)
 {
-    if (bytes > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return bytes > 48 * 1024 ? stm_reserve_lds<Kernel>(bytes, who) : STM_OK;
 }
 
 }  // namespace
@@ -639,7 +639,7 @@ extern "C" int stm_generate_candidates_f32(const float* loc, const float* priors
     STM_REQUIRE(((uintptr_t)loc % 16 == 0) && ((uintptr_t)priors % 16 == 0) && ((uintptr_t)cand_box % 16 == 0), STM_EINVAL,
                 "stm_generate_candidates_f32: loc/priors/cand_box must be 16-byte aligned");
     size_t lds = (size_t)256 * ncls * sizeof(float);
-    allow_big_lds(row_stats_kernel<false>, lds);
+    if (const int rc = allow_big_lds<row_stats_kernel<false>>(lds, "stm_generate_candidates_f32")) return rc;
     hipLaunchKernelGGL(row_stats_kernel<false>, dim3(stm_cdiv(N, 256), batch), dim3(256), lds, stm_hs(stream), loc, priors, conf,
                        (const float*)nullptr, N, ncls, thresh, reinterpret_cast<float4*>(cand_box), keep_idx,
                        (float*)nullptr);
@@ -669,7 +669,7 @@ extern "C" int stm_cc_fast_nms_f32(const float* conf, const float* boxes, const 
                 "stm_cc_fast_nms_f32: boxes must be 16-byte aligned");
     const int Kp = next_pow2(K);
     const size_t lds = nms_lds_bytes(Kp, top_k);
-    allow_big_lds(cc_nms_kernel<0>, lds);
+    if (const int rc = allow_big_lds<cc_nms_kernel<0>>(lds, "stm_cc_fast_nms_f32")) return rc;
     hipLaunchKernelGGL(cc_nms_kernel<0>, dim3(batch), dim3(NMS_THREADS), lds, stm_hs(stream), conf, boxes, centerness,
                        (const float*)nullptr, K, ncls, k_dev, iou_thr, top_k, Kp, idx_out, cls_out, score_out, box_out,
                        count_out);
@@ -698,14 +698,14 @@ extern "C" int stm_cc_fast_nms_ws_f32(const float* conf, const float* boxes, con
                 "stm_cc_fast_nms_ws_f32: boxes / workspace / box_out must be 16-byte aligned");
     float* score_all = reinterpret_cast<float*>(workspace);
     const size_t lds1 = (size_t)256 * ncls * sizeof(float);
-    allow_big_lds(row_stats_kernel<false>, lds1);
+    if (const int rc = allow_big_lds<row_stats_kernel<false>>(lds1, "stm_cc_fast_nms_ws_f32")) return rc;
     // every row is a candidate here (the caller filtered already): threshold -inf
     hipLaunchKernelGGL(row_stats_kernel<false>, dim3(stm_cdiv(K, 256), batch), dim3(256), lds1, stm_hs(stream), (const float*)nullptr,
                        (const float*)nullptr, conf, centerness, K, ncls, -INFINITY, (float4*)nullptr, (int64_t*)nullptr, score_all);
     STM_CHECK_LAUNCH("row_stats_kernel");
     const int Kp = next_pow2(min(K, NMS_MAX_KEYS));
     const size_t lds = nms_lds_bytes(Kp, top_k);
-    allow_big_lds(cc_nms_kernel<1>, lds);
+    if (const int rc = allow_big_lds<cc_nms_kernel<1>>(lds, "stm_cc_fast_nms_ws_f32")) return rc;
     hipLaunchKernelGGL(cc_nms_kernel<1>, dim3(batch), dim3(NMS_THREADS), lds, stm_hs(stream), conf, boxes, centerness, score_all, K, ncls,
                        (const int*)nullptr, iou_thr, top_k, Kp, idx_out, cls_out, score_out, box_out, count_out);
     STM_CHECK_LAUNCH("cc_nms_kernel");
@@ -762,18 +762,18 @@ static int detect_cc_impl(const float* loc, const float* priors, const float* co
     float* score_all = reinterpret_cast<float*>(box_all + (size_t)batch * N);
     size_t lds1 = (size_t)256 * ncls * sizeof(float);
     if (logits) {
-        allow_big_lds(row_stats_kernel<true>, lds1);
+        if (const int rc = allow_big_lds<row_stats_kernel<true>>(lds1, "stm_detect_cc_f32")) return rc;
         hipLaunchKernelGGL(row_stats_kernel<true>, dim3(stm_cdiv(N, 256), batch), dim3(256), lds1, stm_hs(stream), loc, priors, conf,
                            centerness, N, ncls, conf_thresh, box_all, (int64_t*)nullptr, score_all);
     } else {
-        allow_big_lds(row_stats_kernel<false>, lds1);
+        if (const int rc = allow_big_lds<row_stats_kernel<false>>(lds1, "stm_detect_cc_f32")) return rc;
         hipLaunchKernelGGL(row_stats_kernel<false>, dim3(stm_cdiv(N, 256), batch), dim3(256), lds1, stm_hs(stream), loc, priors, conf,
                            centerness, N, ncls, conf_thresh, box_all, (int64_t*)nullptr, score_all);
     }
     STM_CHECK_LAUNCH("row_stats_kernel");
     const int Kp = next_pow2(min(N, NMS_MAX_KEYS));
     const size_t lds = nms_lds_bytes(Kp, top_k);
-    allow_big_lds(cc_nms_kernel<1>, lds);
+    if (const int rc = allow_big_lds<cc_nms_kernel<1>>(lds, "stm_detect_cc_f32")) return rc;
     hipLaunchKernelGGL(cc_nms_kernel<1>, dim3(batch), dim3(NMS_THREADS), lds, stm_hs(stream), conf,
                        reinterpret_cast<const float*>(box_all), centerness, score_all, N, ncls, (const int*)nullptr, iou_thr,
                        top_k, Kp, idx_out, cls_out, score_out, box_out, count_out);
@@ -833,13 +833,13 @@ extern "C" int stm_fast_nms_batched_f32(const float* conf, int64_t conf_bstride,
     int* ws_count = ws_row + (size_t)B * ws_bs;
     const int Kp = next_pow2(K);
     size_t lds = nms_lds_bytes(Kp, top_k);
-    allow_big_lds(pc_nms_class_kernel, lds);
+    if (const int rc = allow_big_lds<pc_nms_class_kernel>(lds, "stm_fast_nms_batched_f32")) return rc;
     hipLaunchKernelGGL(pc_nms_class_kernel, dim3(ncls - 1, B), dim3(NMS_THREADS), lds, stm_hs(stream), conf, boxes, centerness,
                        K, ncls, k_dev, iou_thr, top_k, conf_thresh, Kp, ws_score, ws_row, ws_count, row_index, conf_bstride, (int64_t)K * 4, cen_bstride, ws_bs);
     STM_CHECK_LAUNCH("pc_nms_class_kernel");
     const int Kp2 = next_pow2((ncls - 1) * top_k);
     size_t lds2 = (size_t)Kp2 * 8 + (size_t)(ncls + 4) * 4;
-    allow_big_lds(pc_nms_merge_kernel, lds2);
+    if (const int rc = allow_big_lds<pc_nms_merge_kernel>(lds2, "stm_fast_nms_batched_f32")) return rc;
     hipLaunchKernelGGL(pc_nms_merge_kernel, dim3(B), dim3(NMS_THREADS), lds2, stm_hs(stream), boxes, ncls, top_k, max_det,
                        Kp2, ws_score, ws_row, ws_count, idx_out, cls_out, score_out, box_out, count_out, row_index, K, (int64_t)K * 4, ws_bs);
     STM_CHECK_LAUNCH("pc_nms_merge_kernel");

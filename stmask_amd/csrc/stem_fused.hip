@@ -22,7 +22,6 @@
 // 2048, fp32 accumulation, power-of-two weight scale removed after the sum); format 2 keeps one plane / one product.
 #include "planar_common.h"
 
-#include <atomic>
 
 namespace {
 
@@ -34,7 +33,6 @@ constexpr int ST_IR = 2 * ST_CR + 5;                 // input rows of the patch 
 constexpr int ST_IS = 2 * ST_CC + 6;                 // input pixel slots per patch row (102): slot s = input column ix0 + s
 constexpr int ST_ROWB = ST_IS * 8;                   // bytes per patch row and plane
 constexpr int ST_XPL = ST_IR * ST_ROWB;              // bytes per plane of the patch
-constexpr int ST_MAX_DEVICES = 32;
 
 struct StemArgs {
     const float* x;          // [B][H][W][3]
@@ -276,15 +274,8 @@ extern "C" int stm_stem_fused_f32(const float* x, const void* packed_weight, con
     a.range_flag = stm_internal_range_flag();
     const int npl = fmt == 1 ? 2 : 1;
     const size_t lds = (size_t)npl * ST_XPL;
-    static std::atomic<bool> reserved[2][ST_MAX_DEVICES];
-    int dev = 0;
-    const bool have_dev = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < ST_MAX_DEVICES;
-    if (!have_dev || !reserved[npl - 1][dev].load(std::memory_order_relaxed)) {
-        const void* fn = npl == 2 ? reinterpret_cast<const void*>(stem_fused_kernel<2>) : reinterpret_cast<const void*>(stem_fused_kernel<1>);
-        STM_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess, STM_ELAUNCH,
-                    "%s: cannot reserve %zu bytes of LDS", who, lds);
-        if (have_dev) reserved[npl - 1][dev].store(true, std::memory_order_relaxed);
-    }
+    const int rc = npl == 2 ? stm_reserve_lds<stem_fused_kernel<2>>(lds, who) : stm_reserve_lds<stem_fused_kernel<1>>(lds, who);
+    if (rc != STM_OK) return rc;
     const int64_t nblk = (int64_t)B * a.tiles_y * a.tiles_x;
     if (npl == 2) hipLaunchKernelGGL(stem_fused_kernel<2>, dim3(stm_xcd_grid(nblk)), dim3(256), lds, stm_hs(stream), a);
     else hipLaunchKernelGGL(stem_fused_kernel<1>, dim3(stm_xcd_grid(nblk)), dim3(256), lds, stm_hs(stream), a);

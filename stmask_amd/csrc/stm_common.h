@@ -1,6 +1,7 @@
 // stm_common.h -- shared helpers for the gfx950 kernels behind include/stmask_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -40,14 +41,56 @@ int stm_env_int_uncached(const char* name, int dflt);
         return v_;                                                                       \
     }())
 
-int* stm_internal_range_flag();
-long long stm_internal_fused_dcn_launches();   // dcn_fused.hip: launches of dcn_fused_kernel (stm_debug_launch_count(1))   // conv_bf16x.hip: the device flag registered with stm_planar_set_range_flag (or null)
+int* stm_internal_range_flag();                 // conv_bf16x.hip: the device flag registered with stm_planar_set_range_flag for the current device (or null)
+long long stm_internal_fused_dcn_launches();   // dcn_fused.hip: launches of dcn_fused_kernel (stm_debug_launch_count(1))
 
 const int* stm_internal_take_pixel_gate();      // capi.hip: the gate set by stm_conv_set_pixel_gate for this thread's next convolution launch (cleared)
 
 static inline hipStream_t stm_hs(stm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 static inline int stm_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// ---- launch plumbing: what the host keeps per device ---------------------------------------------
+constexpr int STM_MAX_DEVICES = 32;
+
+// index of the current device, or -1 (no device, or one past the per-device tables)
+static inline int stm_current_device()
+{
+    int dev = 0;
+    return (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < STM_MAX_DEVICES) ? dev : -1;
+}
+
+// Dynamic LDS beyond the default limit must be reserved for a kernel before it is launched.  The attribute belongs to the device's
+// copy of the function and is sticky, so the largest size reserved so far is remembered per kernel (one instantiation of this
+// template each) and device, and the attribute is set only when a launch needs more -- setting it at each launch only costs host
+// time.  Relaxed atomics: two host threads racing here both set a size that covers their own launch, and the larger request is
+// simply made again by whoever finds the smaller one recorded.  Without a current device nothing is remembered.
+template <auto Kernel>
+int stm_reserve_lds(size_t bytes, const char* who)
+{
+    static std::atomic<int> reserved[STM_MAX_DEVICES];
+    const int dev = stm_current_device();
+    if (dev < 0 || reserved[dev].load(std::memory_order_relaxed) < (int)bytes) {
+        STM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess,
+                    STM_ELAUNCH, "%s: cannot reserve %zu bytes of LDS", who, bytes);
+        if (dev >= 0) reserved[dev].store((int)bytes, std::memory_order_relaxed);
+    }
+    return STM_OK;
+}
+
+// compute units of the current device, looked up once per device (256 when it cannot be asked)
+static inline int stm_cu_count()
+{
+    static std::atomic<int> n_cus[STM_MAX_DEVICES];
+    const int dev = stm_current_device();
+    int cus = dev >= 0 ? n_cus[dev].load(std::memory_order_relaxed) : 0;
+    if (cus <= 0) {
+        hipDeviceProp_t prop;
+        cus = (dev >= 0 && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+        if (dev >= 0) n_cus[dev].store(cus, std::memory_order_relaxed);
+    }
+    return cus;
+}
 
 // ---- device helpers -----------------------------------------------------------------------------
 

@@ -99,7 +99,7 @@ def test_planar_conv_kernels_do_not_spill():
     seen = 0
     for b in blocks:
         name = b.split()[0]
-        if "conv_planar_kernel" not in name and "conv_planar_kx_kernel" not in name:
+        if "conv_planar_kernel" not in name and "conv_planar_kx3_kernel" not in name:
             continue
         seen += 1
         scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
