@@ -44,7 +44,8 @@
  *     Added since without a version change (new entry points only; the binding refuses a library that lacks one): the backward kernels of
  *     the training path stm_deform_col2im_f32, stm_deform_col2im_coord_f32, stm_roi_align_backward_f32, stm_corr_backward_f32, and of the layer
  *     functions stm_lincomb_backward_workspace_bytes, stm_lincomb_backward_f32, stm_decode_boxes_backward_f32, stm_jaccard_backward_f32;
- *     the training target assignment stm_match_workspace_bytes, stm_match_priors_f32, stm_encode_boxes_f32.
+ *     the training target assignment stm_match_workspace_bytes, stm_match_priors_f32, stm_encode_boxes_f32; the mask loss tail
+ *     stm_mask_bce_workspace_bytes, stm_mask_bce_upsampled_f32, stm_mask_bce_upsampled_backward_f32.
  */
 #ifndef STMASK_HIP_H_
 #define STMASK_HIP_H_
@@ -822,6 +823,36 @@ int stm_match_priors_f32(const float* boxes, const int64_t* labels, const int64_
                          float* loc_t, float* gt_boxes_t, int64_t* conf_t, int64_t* idx_t, int64_t* ids_t, int* status, void* workspace,
                          size_t workspace_bytes, stm_stream_t stream);
 int stm_encode_boxes_f32(const float* matched, const float* priors, float* out, int64_t n, stm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Mask loss tail.  Replaces the end of lincomb_mask_loss (multibox_loss.py:575, :598-603 and the sum of :613; likewise :293, :303-309, :317):
+ * the gather of one target per instance, F.interpolate(bilinear, align_corners=False) of the soft masks to the target size, clamp to [0, 1],
+ * binary_cross_entropy per pixel and the sum per instance -- without any tensor at target resolution.  No float atomics, no host
+ * synchronisation: loss and grad_pred are bit-identical from run to run.
+ *
+ * pred [n,h,w] fp32 (what stm_lincomb_sigmoid_crop_f32 returns: exactly 0 outside each row's crop).  target [G,H,W], uint8 (a bool tensor is
+ *   passed as bytes; a byte b stands for the value (float)b) or fp32 (target_is_f32; any values).  idx [n] (DEVICE int64): the target row of each
+ *   instance, or NULL: row i uses target i and G must equal n.  An idx value outside [0, G) is data, not an error: nothing is read through it and
+ *   that row's loss / gradient row is NaN.
+ * Table, per axis, fp32, every operation rounded on its own:  scale = (float)in / (float)out,  src = max(scale * (dst + 0.5f) - 0.5f, 0),
+ *   i0 = (int)src,  i1 = i0 + (i0 < in - 1),  l1 = src - i0,  l0 = 1 - l1.  Forward and adjoint use the same values.
+ * stm_mask_bce_upsampled_f32:  up = l0y (l0x p00 + l1x p01) + l1y (l0x p10 + l1x p11),  pc = clamp(up, 0, 1),
+ *   term = -(t max(log pc, -100) + (1 - t) max(log(1 - pc), -100)),  loss[d] = sum of term over all H * W pixels (no box normalisation; the
+ *   whole frame is walked).  So pc = 0 against t = 1, or pc = 1 against t = 0, costs exactly 100.  Per workgroup a fixed-order sum of one
+ *   16 x 128 target tile; the [n][tiles] partials in the workspace are added per instance in a fixed order by a second launch.
+ *   workspace: stm_mask_bce_workspace_bytes(n, H, W) bytes, 4-byte aligned.
+ * stm_mask_bce_upsampled_backward_f32:  grad_pred[d,y,x] = grad_loss[d] * sum over the target pixels that sample (y, x) of weight * dterm,
+ *   dterm = (pc - t) / max(pc (1 - pc), 1e-12) where 0 <= up <= 1 and 0 elsewhere (torch's BCE backward and its clamp backward, inclusive at
+ *   both ends).  A gather, written not accumulated; outside a crop it leaves values of order -1e12 where the target is 1, which
+ *   stm_lincomb_backward_f32 does not read.
+ * Shapes: 1 <= h <= H <= 4096, 1 <= w <= W <= 4096, n <= 65535 (anything else, downsampling included: STM_EUNSUPPORTED); n = 0 returns STM_OK
+ *   without a launch.  W need not be a multiple of 4.
+ * ------------------------------------------------------------------------------------------------- */
+size_t stm_mask_bce_workspace_bytes(int n, int H, int W);
+int stm_mask_bce_upsampled_f32(const float* pred, const void* target, int target_is_f32, const int64_t* idx, float* loss, int n, int h, int w,
+                               int G, int H, int W, void* workspace, size_t workspace_bytes, stm_stream_t stream);
+int stm_mask_bce_upsampled_backward_f32(const float* grad_loss, const float* pred, const void* target, int target_is_f32, const int64_t* idx,
+                                        float* grad_pred, int n, int h, int w, int G, int H, int W, stm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,11 +1,11 @@
 """Autograd for the drop-in deformable convolution, RoIAlign and correlation (the training path of dcn_v2 / mmcv.ops /
-spatial_correlation_sampler) and for the layer functions the reference's loss differentiates through -- generate_mask, decode, jaccard
-(INTEGRATION.md section 14).
+spatial_correlation_sampler) and for the layer functions the reference's loss differentiates through -- generate_mask, decode, jaccard and
+the mask loss tail mask_bce_sum.
 
 Each Function's forward is the launch the shim makes without autograd (ops.deform_conv / roi_align / corr_patch), so values under
 autograd are bit-identical to the no-grad call.  Only inputs are saved: the deformable columns are recomputed in backward with the
 forward's own im2col, the mask sigmoid from the prototypes and coefficients.  Backward runs the gfx950 kernels of csrc/deform_backward.hip,
-csrc/temporal_backward.hip and csrc/mask_backward.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
+csrc/temporal_backward.hip, csrc/mask_backward.hip and csrc/mask_loss.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
 every backward is @first_order_only: a double backward (create_graph=True, then differentiating the result) raises instead of
 silently dropping the second-order term.
 """
@@ -202,6 +202,23 @@ class JaccardFunction(torch.autograd.Function):
         return ops.jaccard_backward(grad_out.contiguous(), a, b, need_a=na, need_b=nb)
 
 
+class MaskBceFunction(torch.autograd.Function):
+    """mask_bce_upsampled: pred [n,h,w], target [G,H,W], idx [n] or None -> loss [n].  Gradient w.r.t. pred only (the targets and the index are data)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, idx):
+        ctx.save_for_backward(pred, target, idx)
+        return ops.mask_bce_upsampled(pred, target, idx)
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        pred, target, idx = ctx.saved_tensors
+        return ops.mask_bce_upsampled_backward(grad_loss.contiguous(), pred, target, idx), None, None
+
+
 def modulated_deform_conv(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups):
     return ModulatedDeformConvFunction.apply(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups, False)
 
@@ -232,3 +249,7 @@ def decode(loc, priors):
 
 def jaccard(box_a, box_b):
     return JaccardFunction.apply(box_a, box_b)
+
+
+def mask_bce(pred, target, idx=None):
+    return MaskBceFunction.apply(pred, target, idx)

@@ -4,6 +4,6 @@ from .box_utils import center_size, crop, decode, encode, jaccard, mask_iou, mat
     sanitize_coordinates, sanitize_coordinates_hw  # noqa: F401
 from .functions import CandidateShift, Detect, Detect_TF, Track, Track_TF, compute_comp_scores, generate_candidate, \
     merge_candidates  # noqa: F401
-from .mask_utils import generate_mask  # noqa: F401
+from .mask_utils import generate_mask, lincomb_mask_loss_image, mask_bce_sum  # noqa: F401
 from .modules import FPN, FeatureAlign, InterpolateModule, PredictionModule_FC, TemporalNet, bbox_feat_extractor, \
     correlate, make_net  # noqa: F401

@@ -752,6 +752,62 @@ def lincomb_sigmoid_crop_backward(grad_out, proto, coeff, boxes=None, apply_tanh
     return gp, gc
 
 
+def _mask_bce_args(who, pred, target, idx, grad_loss=None):
+    """Shapes and dtypes of the mask loss tail, checked before anything touches the device: (pred, target as bytes or fp32, idx, is_f32)."""
+    if pred.dtype != torch.float32 or pred.dim() != 3:
+        raise StmError(f"{who}: pred must be float32 [n,h,w], got {pred.dtype} {tuple(pred.shape)}")
+    if target.dtype not in (torch.uint8, torch.bool, torch.float32) or target.dim() != 3:
+        raise StmError(f"{who}: target must be uint8, bool or float32 [G,H,W], got {target.dtype} {tuple(target.shape)}")
+    n, h, w = pred.shape
+    G, H, W = target.shape
+    if h > H or w > W:
+        raise StmError(f"{who}: pred {h}x{w} is larger than the target {H}x{W} (downsampling is not supported)")
+    if idx is None:
+        if G != n:
+            raise StmError(f"{who}: without idx row i uses target i, but pred has {n} rows and target {G}")
+    elif idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() != n:
+        raise StmError(f"{who}: idx must be int64 [{n}], got {idx.dtype} {tuple(idx.shape)}")
+    if grad_loss is not None and (grad_loss.dtype != torch.float32 or tuple(grad_loss.shape) != (n,)):
+        raise StmError(f"{who}: grad_loss must be float32 [{n}], got {grad_loss.dtype} {tuple(grad_loss.shape)}")
+    _dev(pred, target, idx, grad_loss)
+    target = target if target.is_contiguous() else target.contiguous()
+    if target.dtype == torch.bool:
+        target = target.view(torch.uint8)
+    return _f32c(pred), target, (idx if idx is None or idx.is_contiguous() else idx.contiguous()), target.dtype == torch.float32
+
+
+def mask_bce_upsampled(pred, target, idx=None):
+    """The tail of lincomb_mask_loss (multibox_loss.py:575, :598-603, the sum of :613): pred [n,h,w] soft masks, target [G,H,W] uint8 / bool / float32,
+    idx [n] int64 (the target row of each instance; None: row i uses target i) -> loss [n], the per-instance sum over all H * W pixels of the BCE
+    between the target and the bilinearly upsampled (align_corners=False), clamped prediction.  Nothing at target resolution is materialised."""
+    pred, target, idx, is_f32 = _mask_bce_args("mask_bce_upsampled", pred, target, idx)
+    n, h, w = pred.shape
+    G, H, W = target.shape
+    loss = torch.empty(n, dtype=torch.float32, device=pred.device)
+    if n == 0:
+        return loss
+    need = _lib.lib().stm_mask_bce_workspace_bytes(c_i(n), c_i(H), c_i(W))
+    ws = _workspace(need, pred.device, "mbce")
+    check(_lib.lib().stm_mask_bce_upsampled_f32(_p(pred), _p(target), c_i(1 if is_f32 else 0), _p(idx), _p(loss), c_i(n), c_i(h), c_i(w), c_i(G),
+                                                c_i(H), c_i(W), _p(ws), c_sz(ws.numel()), _stream()), "stm_mask_bce_upsampled_f32")
+    return loss
+
+
+def mask_bce_upsampled_backward(grad_loss, pred, target, idx=None):
+    """grad_pred [n,h,w] of mask_bce_upsampled: grad_loss [n] times the gather of weight * (pc - t) / max(pc (1 - pc), 1e-12) over the target pixels
+    that sample each prediction pixel (0 where the upsampled value left [0, 1]); fixed-order sums, no atomics."""
+    pred, target, idx, is_f32 = _mask_bce_args("mask_bce_upsampled_backward", pred, target, idx, grad_loss)
+    n, h, w = pred.shape
+    G, H, W = target.shape
+    grad_pred = torch.empty_like(pred)
+    if n == 0:
+        return grad_pred
+    check(_lib.lib().stm_mask_bce_upsampled_backward_f32(_p(_f32c(grad_loss)), _p(pred), _p(target), c_i(1 if is_f32 else 0), _p(idx), _p(grad_pred),
+                                                         c_i(n), c_i(h), c_i(w), c_i(G), c_i(H), c_i(W), _stream()),
+          "stm_mask_bce_upsampled_backward_f32")
+    return grad_pred
+
+
 def mask_iou(m1, m2, thr=0.5, group1=None, group2=None):
     """box_utils.py:435-447 on (m > thr).  m1 [n1,h,w], m2 [n2,h,w] soft masks -> [n1,n2].  group1 / group2 (int32, any
     order; sorted rows skip whole workgroups): only pairs of the same group are computed, the others stay 0 (stm_mask_iou_grouped_f32)."""
