@@ -45,7 +45,8 @@
  *     the training path stm_deform_col2im_f32, stm_deform_col2im_coord_f32, stm_roi_align_backward_f32, stm_corr_backward_f32, and of the layer
  *     functions stm_lincomb_backward_workspace_bytes, stm_lincomb_backward_f32, stm_decode_boxes_backward_f32, stm_jaccard_backward_f32;
  *     the training target assignment stm_match_workspace_bytes, stm_match_priors_f32, stm_encode_boxes_f32; the mask loss tail
- *     stm_mask_bce_workspace_bytes, stm_mask_bce_upsampled_f32, stm_mask_bce_upsampled_backward_f32.
+ *     stm_mask_bce_workspace_bytes, stm_mask_bce_upsampled_f32, stm_mask_bce_upsampled_backward_f32; the OHEM class-confidence loss
+ *     stm_ohem_conf_workspace_bytes, stm_ohem_select_neg_f32, stm_ohem_conf_loss_f32, stm_ohem_conf_loss_backward_f32.
  */
 #ifndef STMASK_HIP_H_
 #define STMASK_HIP_H_
@@ -853,6 +854,43 @@ int stm_mask_bce_upsampled_f32(const float* pred, const void* target, int target
                                int G, int H, int W, void* workspace, size_t workspace_bytes, stm_stream_t stream);
 int stm_mask_bce_upsampled_backward_f32(const float* grad_loss, const float* pred, const void* target, int target_is_f32, const int64_t* idx,
                                         float* grad_pred, int n, int h, int w, int G, int H, int W, stm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * OHEM class-confidence loss.  Replaces select_neg_bboxes and ohem_conf_loss of the reference's MultiBoxLoss (multibox_loss.py:402-448,
+ * ohem_use_most_confident = False; the centerness term of :450-455 is not part of it): log-sum-exp per prior, the hard negatives WITHOUT a
+ * sort (radix select on the score bits), the weights and the weighted cross entropy, in a fixed number of launches whose grids depend on
+ * (B, P, C) only.  num_pos, k, num_neg and the cut never reach the host.  No float atomics (integer atomics count positives and fill the
+ * histograms): loss and gradient are bit-identical from run to run.
+ *
+ * conf [B,P,C] fp32 (16-byte aligned), conf_t [B,P] (DEVICE int64: > 0 a class, 0 background, < 0 neutral).  N = B * P, x = conf as [N,C].
+ * Score:  lse_i = m_i + log(sum_c exp(x_ic - m_i)) with the ROW's maximum m_i, evaluated in double and rounded once to fp32;
+ *   score_i = fp32(lse_i - x_i0) where t_i == 0 and exactly +0 where t_i != 0.  score_i >= 0, so its bit pattern orders like an unsigned integer.
+ *   (The reference subtracts the maximum of the whole batch: the same number mathematically; rows far below that maximum are where its fp32
+ *   loses digits or underflows to -inf.)
+ * Cut:  num_pos = #(t > 0), k = min(negpos_ratio * num_pos, N - 1).  Row i is a selected negative iff t_i == 0 and it is among the k largest
+ *   of all N scores under the order (score descending, index ascending): of equal scores the lower flattened index wins.  Positives and
+ *   neutrals take part in the ranking with score 0 and are then dropped, so fewer than k rows may be selected.  k = 0 selects nothing.
+ * Weights:  num_neg = the rows actually selected, w_neg = negpos_ratio * B / num_neg (used by no row when num_neg = 0); a positive of image b
+ *   weighs 1 / max(npos_b, 1).  aligned_weights = 0 (the reference's number): the kept rows (positives and selected negatives) in index order
+ *   get cat([the positives' weights in index order, w_neg x num_neg]) BY POSITION -- the reference multiplies that vector onto the loss of
+ *   conf[keep], whose rows are in prior order.  aligned_weights = 1: every positive its own image's weight, every selected negative w_neg.
+ *   All other rows weigh 0.
+ * Loss:  *loss = conf_alpha * sum_i w_i (lse_i - x_{i,t_i}) / (negpos_ratio + 1), before MultiBoxLoss's own division by the batch size; the
+ *   terms are fp32, products and sums run in double in a fixed order.  lse [N] and w [N] (fp32) are written for the backward.
+ * Gradient:  grad_conf[i,c] = *grad_loss * conf_alpha / (negpos_ratio + 1) * w_i * (exp(x_ic - lse_i) - [c == t_i]), written, not accumulated;
+ *   rows with w_i = 0 are written as zeros without reading conf.  The selection is a constant.  grad_loss is a DEVICE scalar.
+ * stm_ohem_select_neg_f32: neg [N] fp32, 1 where the row is a selected negative and 0 elsewhere (select_neg_bboxes' return value).
+ * A label >= C is data: nothing is read through it; that row's term (so the loss) and its gradient row are NaN, no other row changes.
+ * Shapes: B, P, negpos_ratio >= 1 (else STM_EINVAL); 2 <= C <= 128 and B * P <= 2^22 (else STM_EUNSUPPORTED); checked before any launch.
+ * Launches: 8 for the loss, 7 for the selection, 1 for the gradient.  workspace: stm_ohem_conf_workspace_bytes(B, P, C) bytes, 8-byte aligned.
+ * ------------------------------------------------------------------------------------------------- */
+size_t stm_ohem_conf_workspace_bytes(int B, int P, int C);
+int stm_ohem_select_neg_f32(const float* conf, const int64_t* conf_t, float* neg, int B, int P, int C, int negpos_ratio, void* workspace,
+                            size_t workspace_bytes, stm_stream_t stream);
+int stm_ohem_conf_loss_f32(const float* conf, const int64_t* conf_t, float* loss, float* lse, float* w, int B, int P, int C, int negpos_ratio,
+                           double conf_alpha, int aligned_weights, void* workspace, size_t workspace_bytes, stm_stream_t stream);
+int stm_ohem_conf_loss_backward_f32(const float* grad_loss, const float* conf, const int64_t* conf_t, const float* lse, const float* w,
+                                    float* grad_conf, int B, int P, int C, int negpos_ratio, double conf_alpha, stm_stream_t stream);
 
 #ifdef __cplusplus
 }

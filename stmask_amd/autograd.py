@@ -1,11 +1,11 @@
 """Autograd for the drop-in deformable convolution, RoIAlign and correlation (the training path of dcn_v2 / mmcv.ops /
 spatial_correlation_sampler) and for the layer functions the reference's loss differentiates through -- generate_mask, decode, jaccard and
-the mask loss tail mask_bce_sum.
+the mask loss tail mask_bce_sum and the OHEM class-confidence loss ohem_conf_loss.
 
 Each Function's forward is the launch the shim makes without autograd (ops.deform_conv / roi_align / corr_patch), so values under
 autograd are bit-identical to the no-grad call.  Only inputs are saved: the deformable columns are recomputed in backward with the
 forward's own im2col, the mask sigmoid from the prototypes and coefficients.  Backward runs the gfx950 kernels of csrc/deform_backward.hip,
-csrc/temporal_backward.hip, csrc/mask_backward.hip and csrc/mask_loss.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
+csrc/temporal_backward.hip, csrc/mask_backward.hip, csrc/mask_loss.hip and csrc/conf_loss.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
 every backward is @first_order_only: a double backward (create_graph=True, then differentiating the result) raises instead of
 silently dropping the second-order term.
 """
@@ -219,6 +219,26 @@ class MaskBceFunction(torch.autograd.Function):
         return ops.mask_bce_upsampled_backward(grad_loss.contiguous(), pred, target, idx), None, None
 
 
+class OhemConfLossFunction(torch.autograd.Function):
+    """ohem_conf_loss: conf_data [B,P,C], conf_t [B,P] -> losses['C'].  Saved: the inputs and the two [N] fp32 vectors lse and w, nothing of
+    size N * C.  The selection is a constant of the backward; no gradient w.r.t. conf_t."""
+
+    @staticmethod
+    def forward(ctx, conf_data, conf_t, negpos_ratio, conf_alpha, weights):
+        loss, lse, w = ops.ohem_conf_loss(conf_data, conf_t, negpos_ratio, conf_alpha, weights)
+        ctx.args = (negpos_ratio, conf_alpha)
+        ctx.save_for_backward(conf_data, conf_t, lse, w)
+        return loss
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        conf_data, conf_t, lse, w = ctx.saved_tensors
+        return ops.ohem_conf_loss_backward(grad_loss.contiguous(), conf_data, conf_t, lse, w, *ctx.args), None, None, None, None
+
+
 def modulated_deform_conv(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups):
     return ModulatedDeformConvFunction.apply(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups, False)
 
@@ -253,3 +273,7 @@ def jaccard(box_a, box_b):
 
 def mask_bce(pred, target, idx=None):
     return MaskBceFunction.apply(pred, target, idx)
+
+
+def ohem_conf_loss(conf_data, conf_t, negpos_ratio=3, conf_alpha=1.0, weights="reference"):
+    return OhemConfLossFunction.apply(conf_data, conf_t, negpos_ratio, conf_alpha, weights)

@@ -2,6 +2,7 @@
 modules/__init__.py:1-12) for the components on the hot path."""
 from .box_utils import center_size, crop, decode, encode, jaccard, mask_iou, match, match_batch, point_form, \
     sanitize_coordinates, sanitize_coordinates_hw  # noqa: F401
+from .conf_loss import ohem_conf_loss, select_neg_bboxes  # noqa: F401
 from .functions import CandidateShift, Detect, Detect_TF, Track, Track_TF, compute_comp_scores, generate_candidate, \
     merge_candidates  # noqa: F401
 from .mask_utils import generate_mask, lincomb_mask_loss_image, mask_bce_sum  # noqa: F401

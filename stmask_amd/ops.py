@@ -808,6 +808,79 @@ def mask_bce_upsampled_backward(grad_loss, pred, target, idx=None):
     return grad_pred
 
 
+def _ohem_args(who, conf_data, conf_t, negpos_ratio):
+    """Shapes and dtypes of the OHEM confidence loss, checked before anything touches the device: (x [N,C] fp32 contiguous and 16-byte aligned,
+    t [N] int64 contiguous, B, P, C, ratio)."""
+    if conf_data.dim() not in (2, 3):
+        raise StmError(f"{who}: conf_data must be [B,P,C] or [N,C], got {tuple(conf_data.shape)}")
+    C = conf_data.shape[-1]
+    N = conf_data.numel() // C if C else 0
+    if conf_t.dtype != torch.int64 or conf_t.dim() not in (1, 2) or conf_t.numel() != N:
+        raise StmError(f"{who}: conf_t must be int64 with the {N} priors of conf_data {tuple(conf_data.shape)}, got {conf_t.dtype} "
+                       f"{tuple(conf_t.shape)}")
+    B = conf_data.shape[0] if conf_data.dim() == 3 else (conf_t.shape[0] if conf_t.dim() == 2 else 1)
+    if N == 0 or N % B:
+        raise StmError(f"{who}: {N} priors do not split into {B} images")
+    if int(negpos_ratio) != negpos_ratio or negpos_ratio < 1:
+        raise StmError(f"{who}: negpos_ratio must be a positive integer, got {negpos_ratio}")
+    _dev(conf_data, conf_t)
+    x = _f32c(conf_data).view(N, C)
+    if x.data_ptr() % 16:
+        x = x.clone()
+    return x, conf_t.contiguous().view(N), B, N // B, C, int(negpos_ratio)
+
+
+def ohem_select_neg(conf_data, conf_t, negpos_ratio=3):
+    """multibox_loss.py:402-426 without the sort: float32 [B*P], 1 where the prior is a selected hard negative (stm_ohem_select_neg_f32; the
+    conventions are in include/stmask_hip.h and INTEGRATION.md section 14).  7 launches, no host synchronisation."""
+    x, t, B, P, C, ratio = _ohem_args("ohem_select_neg", conf_data.detach(), conf_t, negpos_ratio)
+    neg = torch.empty(B * P, dtype=torch.float32, device=x.device)
+    L = _lib.lib()
+    nbytes = L.stm_ohem_conf_workspace_bytes(c_i(B), c_i(P), c_i(C))
+    ws = _workspace(nbytes, x.device, "ohem")
+    check(L.stm_ohem_select_neg_f32(_p(x), _p(t), _p(neg), c_i(B), c_i(P), c_i(C), c_i(ratio), _p(ws), c_sz(ws.numel()), _stream()),
+          "stm_ohem_select_neg_f32")
+    return neg
+
+
+OHEM_WEIGHTS = {"reference": 0, "aligned": 1}
+
+
+def ohem_conf_loss(conf_data, conf_t, negpos_ratio=3, conf_alpha=1.0, weights="reference"):
+    """losses['C'] of multibox_loss.py:428-448 -> (loss 0-dim fp32, lse [N] fp32, w [N] fp32); lse and w are what the backward needs besides the
+    inputs.  8 launches, no host synchronisation (stm_ohem_conf_loss_f32)."""
+    if weights not in OHEM_WEIGHTS:
+        raise StmError(f"ohem_conf_loss: weights must be 'reference' or 'aligned', got {weights!r}")
+    x, t, B, P, C, ratio = _ohem_args("ohem_conf_loss", conf_data, conf_t, negpos_ratio)
+    dev = x.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    lse = torch.empty(B * P, dtype=torch.float32, device=dev)
+    w = torch.empty(B * P, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    nbytes = L.stm_ohem_conf_workspace_bytes(c_i(B), c_i(P), c_i(C))
+    ws = _workspace(nbytes, dev, "ohem")
+    check(L.stm_ohem_conf_loss_f32(_p(x), _p(t), _p(loss), _p(lse), _p(w), c_i(B), c_i(P), c_i(C), c_i(ratio), ctypes.c_double(float(conf_alpha)),
+                                   c_i(OHEM_WEIGHTS[weights]), _p(ws), c_sz(ws.numel()), _stream()), "stm_ohem_conf_loss_f32")
+    return loss, lse, w
+
+
+def ohem_conf_loss_backward(grad_loss, conf_data, conf_t, lse, w, negpos_ratio=3, conf_alpha=1.0):
+    """grad_conf (conf_data's shape) of ohem_conf_loss: grad_loss (a 0-dim device tensor) * conf_alpha / (negpos_ratio + 1) * w_i *
+    (softmax(x_i) - onehot(t_i)); rows with w_i = 0 are written as zeros.  One launch."""
+    x, t, B, P, C, ratio = _ohem_args("ohem_conf_loss_backward", conf_data, conf_t, negpos_ratio)
+    N = B * P
+    _dev(grad_loss, lse, w)
+    if grad_loss.dtype != torch.float32 or grad_loss.numel() != 1:
+        raise StmError(f"ohem_conf_loss_backward: grad_loss must be one float32, got {grad_loss.dtype} {tuple(grad_loss.shape)}")
+    if lse.dtype != torch.float32 or w.dtype != torch.float32 or lse.numel() != N or w.numel() != N:
+        raise StmError(f"ohem_conf_loss_backward: lse and w must be float32 [{N}]")
+    grad = torch.empty(conf_data.shape, dtype=torch.float32, device=x.device)
+    check(_lib.lib().stm_ohem_conf_loss_backward_f32(_p(grad_loss.contiguous()), _p(x), _p(t), _p(lse.contiguous()), _p(w.contiguous()), _p(grad),
+                                                     c_i(B), c_i(P), c_i(C), c_i(ratio), ctypes.c_double(float(conf_alpha)), _stream()),
+          "stm_ohem_conf_loss_backward_f32")
+    return grad
+
+
 def mask_iou(m1, m2, thr=0.5, group1=None, group2=None):
     """box_utils.py:435-447 on (m > thr).  m1 [n1,h,w], m2 [n2,h,w] soft masks -> [n1,n2].  group1 / group2 (int32, any
     order; sorted rows skip whole workgroups): only pairs of the same group are computed, the others stay 0 (stm_mask_iou_grouped_f32)."""
