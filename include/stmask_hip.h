@@ -46,7 +46,9 @@
  *     functions stm_lincomb_backward_workspace_bytes, stm_lincomb_backward_f32, stm_decode_boxes_backward_f32, stm_jaccard_backward_f32;
  *     the training target assignment stm_match_workspace_bytes, stm_match_priors_f32, stm_encode_boxes_f32; the mask loss tail
  *     stm_mask_bce_workspace_bytes, stm_mask_bce_upsampled_f32, stm_mask_bce_upsampled_backward_f32; the OHEM class-confidence loss
- *     stm_ohem_conf_workspace_bytes, stm_ohem_select_neg_f32, stm_ohem_conf_loss_f32, stm_ohem_conf_loss_backward_f32.
+ *     stm_ohem_conf_workspace_bytes, stm_ohem_select_neg_f32, stm_ohem_conf_loss_f32, stm_ohem_conf_loss_backward_f32; the loss terms on the
+ *     positive priors stm_box_center_workspace_bytes, stm_box_center_loss_f32, stm_box_center_loss_backward_f32,
+ *     stm_track_loss_workspace_bytes, stm_track_loss_f32, stm_track_loss_backward_f32.
  */
 #ifndef STMASK_HIP_H_
 #define STMASK_HIP_H_
@@ -891,6 +893,58 @@ int stm_ohem_conf_loss_f32(const float* conf, const int64_t* conf_t, float* loss
                            double conf_alpha, int aligned_weights, void* workspace, size_t workspace_bytes, stm_stream_t stream);
 int stm_ohem_conf_loss_backward_f32(const float* grad_loss, const float* conf, const int64_t* conf_t, const float* lse, const float* w,
                                     float* grad_conf, int B, int P, int C, int negpos_ratio, double conf_alpha, stm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Loss terms on the positive priors.  Replace losses['BIoU'] (multibox_loss.py:164-172) with losses['center'] (:450-455), and losses['T']
+ * (track_loss, :328-351).  Dense forms: no boolean gather, no compaction, no host synchronisation, no float atomics; the grids depend on the
+ * shapes only; sums run in double in a fixed order (bit-identical from run to run); outputs are written, not accumulated.
+ * Throughout conf_t [B,P] is DEVICE int64, prior i is positive iff conf_t_i > 0, npos_b counts the positives of image b and a positive of
+ * image b weighs w_i = 1 / max(npos_b, 1) (:159-161), formed on the device.  Any value of conf_t or ids_t is data and cannot fault.
+ *
+ * stm_box_center_loss_f32.  loc [B,P,4], gt_boxes [B,P,4] (point form, what match_batch returns), priors [P,4] (priors_per_image = 0) or
+ *   [B,P,4] (1), centerness [B,P] or NULL (then center must be NULL and its work is skipped); all fp32, the boxes 16-byte aligned.
+ *     *biou   = bboxiou_alpha * sum_pos w_i (1 - DIoU_i)
+ *     *center = center_alpha  * sum_pos w_i smooth_l1(c_i, DIoU_i)      (beta = 1)
+ *   both before MultiBoxLoss's own division by the batch size.  npos [B] (DEVICE int32) is written for the backward.
+ *   DIoU_i = get_DIoU(decode(loc_i, prior_i), gt_i) of :227-245 in fp32 in the reference's operation order: decode as stm_decode_boxes_f32;
+ *   IoU as stm_jaccard_f32(gt, pred); c2 = max((xmax - xmin)^2 + (ymax - ymin)^2, 1e-10) over the four x (y) of both boxes; d2 the squared
+ *   distance of the centres x1 / 2 + x2 / 2; DIoU = IoU - d2 / c2.  The terms are fp32; an image's terms are added in double and divided by
+ *   max(npos_b, 1), the images are added in a fixed order.  An image without positives contributes exactly 0.
+ * stm_box_center_loss_backward_f32.  grad_biou / grad_center: DEVICE scalars (NULL: zero).  grad_loc [B,P,4] and grad_centerness [B,P] (NULL:
+ *   not wanted) are written: exact zeros for every prior that is not positive (the boxes are not read), else, with recomputed decode and DIoU,
+ *     d center / d c_i = sl1'(c_i - DIoU_i), and d / d DIoU_i = -grad_biou * bboxiou_alpha * w_i - grad_center * center_alpha * w_i * sl1'
+ *   -- the DIoU inside losses['center'] is NOT detached in the reference, so center also sends gradient to loc through smooth-L1's target.
+ *   Conventions: c2's clamp passes no gradient where it cut (c2 < 1e-10); the intersection follows stm_jaccard_backward_f32 (ties of min / max
+ *   go to the ground truth's coordinate, i.e. not to loc; an extent that is not strictly positive passes none); max / min over
+ *   cat([pred x1, pred x2, gt x1, gt x2]) send their gradient to the FIRST maximal / minimal element in that order (as torch does); decode's
+ *   adjoint as stm_decode_boxes_backward_f32.  No gradient w.r.t. priors, gt_boxes or conf_t.
+ *
+ * stm_track_loss_f32.  track [B,P,D] fp32, used as given (not normalised here), ids_t [B,P] DEVICE int64 compared for equality only.  With the
+ *   n positives of the whole batch in flattened index order and s_ij = (x_i . x_j + 1) / 2 (the dot in fp32 FMAs in column order, the rest in
+ *   double):  L_ij = -log(max(s_ij, 1e-10)) where ids_i == ids_j, else -log(max(1 - s_ij, 1e-10));
+ *     *loss = track_alpha * sum_{i<j} w_i w_j L_ij / W,   W = sum_{i<j} w_i w_j,
+ *   before any division by the batch.  n never reaches the host.  n < 2: *loss is exactly 0 and the gradient all zeros (the reference divides
+ *   0 by 0 and returns NaN).
+ * stm_track_loss_backward_f32.  grad_track [B,P,D] (16-byte aligned) is written: zeros for every prior that is not positive (track is not read
+ *   for them), else grad_i = sum_{j != i} coef_ij x_j with coef_ij = *grad_loss * track_alpha / W * w_i w_j * dL/ds / 2, dL/ds = -1 / s where
+ *   s > 1e-10 on the equal-id branch, +1 / (1 - s) where 1 - s > 1e-10 otherwise, and exactly 0 where the clamp cut.  Every pair contributes
+ *   to both of its rows; no atomics.  Nothing is saved between forward and backward: the list of positives is rebuilt.
+ * Shapes: B, P >= 1 (else STM_EINVAL); B * P <= 2^22 and 1 <= D <= 512 (else STM_EUNSUPPORTED); checked before any launch.
+ * Launches: box / centerness 2 + 1 for the gradient; track loss 5 + 5 for the gradient.  Workspaces: 8-byte aligned.
+ * ------------------------------------------------------------------------------------------------- */
+size_t stm_box_center_workspace_bytes(int B, int P);
+int stm_box_center_loss_f32(const float* loc, const float* priors, int priors_per_image, const float* gt_boxes, const int64_t* conf_t,
+                            const float* centerness, float* biou, float* center, int* npos, int B, int P, double bboxiou_alpha,
+                            double center_alpha, void* workspace, size_t workspace_bytes, stm_stream_t stream);
+int stm_box_center_loss_backward_f32(const float* grad_biou, const float* grad_center, const float* loc, const float* priors,
+                                     int priors_per_image, const float* gt_boxes, const int64_t* conf_t, const float* centerness,
+                                     const int* npos, float* grad_loc, float* grad_centerness, int B, int P, double bboxiou_alpha,
+                                     double center_alpha, stm_stream_t stream);
+size_t stm_track_loss_workspace_bytes(int B, int P, int D);
+int stm_track_loss_f32(const float* track, const int64_t* conf_t, const int64_t* ids_t, float* loss, int B, int P, int D, double track_alpha,
+                       void* workspace, size_t workspace_bytes, stm_stream_t stream);
+int stm_track_loss_backward_f32(const float* grad_loss, const float* track, const int64_t* conf_t, const int64_t* ids_t, float* grad_track,
+                                int B, int P, int D, double track_alpha, void* workspace, size_t workspace_bytes, stm_stream_t stream);
 
 #ifdef __cplusplus
 }

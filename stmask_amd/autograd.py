@@ -1,11 +1,12 @@
 """Autograd for the drop-in deformable convolution, RoIAlign and correlation (the training path of dcn_v2 / mmcv.ops /
 spatial_correlation_sampler) and for the layer functions the reference's loss differentiates through -- generate_mask, decode, jaccard and
-the mask loss tail mask_bce_sum and the OHEM class-confidence loss ohem_conf_loss.
+the mask loss tail mask_bce_sum, the OHEM class-confidence loss ohem_conf_loss and the positive-prior terms box_center_loss and track_loss
+(INTEGRATION.md section 14).
 
 Each Function's forward is the launch the shim makes without autograd (ops.deform_conv / roi_align / corr_patch), so values under
 autograd are bit-identical to the no-grad call.  Only inputs are saved: the deformable columns are recomputed in backward with the
 forward's own im2col, the mask sigmoid from the prototypes and coefficients.  Backward runs the gfx950 kernels of csrc/deform_backward.hip,
-csrc/temporal_backward.hip, csrc/mask_backward.hip, csrc/mask_loss.hip and csrc/conf_loss.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
+csrc/temporal_backward.hip, csrc/mask_backward.hip, csrc/mask_loss.hip, csrc/conf_loss.hip and csrc/pos_loss.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
 every backward is @first_order_only: a double backward (create_graph=True, then differentiating the result) raises instead of
 silently dropping the second-order term.
 """
@@ -239,6 +240,50 @@ class OhemConfLossFunction(torch.autograd.Function):
         return ops.ohem_conf_loss_backward(grad_loss.contiguous(), conf_data, conf_t, lse, w, *ctx.args), None, None, None, None
 
 
+class BoxCenterLossFunction(torch.autograd.Function):
+    """box_center_loss: loc_data [B,P,4], centerness_data [B,P,1] or None -> (losses['BIoU'], losses['center']).  Saved: the inputs and the [B]
+    int32 counts of positives.  Gradients w.r.t. loc_data and centerness_data only; losses['center'] reaches loc_data too (the reference does
+    not detach smooth-L1's target)."""
+
+    @staticmethod
+    def forward(ctx, loc_data, centerness_data, priors, gt_boxes_t, conf_t, bboxiou_alpha, center_alpha):
+        biou, center, npos = ops.box_center_loss(loc_data, priors, gt_boxes_t, conf_t, centerness_data, bboxiou_alpha, center_alpha)
+        ctx.args = (bboxiou_alpha, center_alpha)
+        ctx.save_for_backward(loc_data, centerness_data, priors, gt_boxes_t, conf_t, npos)
+        if center is None:
+            return biou
+        return biou, center
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_biou, grad_center=None):
+        nl, nc = ctx.needs_input_grad[:2]
+        if not (nl or nc):
+            return (None,) * 7
+        loc_data, centerness_data, priors, gt_boxes_t, conf_t, npos = ctx.saved_tensors
+        gl, gc = ops.box_center_loss_backward(grad_biou, grad_center, loc_data, priors, gt_boxes_t, conf_t, centerness_data, npos, *ctx.args,
+                                              need_centerness=nc)
+        return (gl if nl else None), gc, None, None, None, None, None
+
+
+class TrackLossFunction(torch.autograd.Function):
+    """track_loss: track_data [B,P,D], conf_t, ids_t [B,P] -> losses['T'].  Saved: the inputs, nothing of size n x n or n x D."""
+
+    @staticmethod
+    def forward(ctx, track_data, conf_t, ids_t, track_alpha):
+        ctx.alpha = track_alpha
+        ctx.save_for_backward(track_data, conf_t, ids_t)
+        return ops.track_loss(track_data, conf_t, ids_t, track_alpha)
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        track_data, conf_t, ids_t = ctx.saved_tensors
+        return ops.track_loss_backward(grad_loss.contiguous(), track_data, conf_t, ids_t, ctx.alpha), None, None, None
+
+
 def modulated_deform_conv(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups):
     return ModulatedDeformConvFunction.apply(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups, False)
 
@@ -277,3 +322,12 @@ def mask_bce(pred, target, idx=None):
 
 def ohem_conf_loss(conf_data, conf_t, negpos_ratio=3, conf_alpha=1.0, weights="reference"):
     return OhemConfLossFunction.apply(conf_data, conf_t, negpos_ratio, conf_alpha, weights)
+
+
+def box_center_loss(loc_data, priors, gt_boxes_t, conf_t, centerness_data=None, bboxiou_alpha=1.0, center_alpha=1.0):
+    out = BoxCenterLossFunction.apply(loc_data, centerness_data, priors, gt_boxes_t, conf_t, bboxiou_alpha, center_alpha)
+    return (out, None) if centerness_data is None else out
+
+
+def track_loss(track_data, conf_t, ids_t, track_alpha=1.0):
+    return TrackLossFunction.apply(track_data, conf_t, ids_t, track_alpha)

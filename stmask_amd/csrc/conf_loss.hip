@@ -69,35 +69,7 @@ ConfLayout conf_layout(int B, int N)
 
 __device__ __forceinline__ float nan_f32() { return __builtin_bit_cast(float, 0x7FC00000u); }
 
-// exclusive prefix of v over the 256 threads in thread order, and the total; sw: 4 words of LDS.  Has barriers: call it uniformly.
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned* sw, unsigned& total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();                                     // sw may still be read from an earlier call
-    if (lane == 63) sw[wv] = inc;
-    __syncthreads();
-    unsigned base = 0;
-    for (int i = 0; i < wv; ++i) base += sw[i];
-    total = sw[0] + sw[1] + sw[2] + sw[3];
-    return base + inc - v;
-}
-
-// sum of v over the 256 threads in one fixed order (xor butterfly inside a wave, then the waves in order); sd: 4 doubles of LDS
-__device__ __forceinline__ double block_sum_f64(double v, double* sd)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sd[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sd[0] + sd[1]) + sd[2]) + sd[3];
-}
+// (stm_block_excl_scan, stm_block_sum_f64: stm_common.h)
 
 // The bin that holds the k-th largest key, walking the NB bins of hist from the top: `bin`, and krem = k minus the keys in higher bins (>= 1).
 // k == 0 gives the top bin and krem = 0, which selects nothing further down.  Every workgroup that needs the answer computes it.
@@ -113,7 +85,7 @@ __device__ __forceinline__ void radix_pick(const unsigned* __restrict__ hist, un
         s += c[j];
     }
     unsigned total;
-    const unsigned above = block_excl_scan(s, sw, total);
+    const unsigned above = stm_block_excl_scan(s, sw, total);
     if (threadIdx.x == 0) {
         sres[0] = NB - 1;
         sres[1] = 0;
@@ -277,7 +249,7 @@ __global__ __launch_bounds__(256) void ohem_scan_kernel(const unsigned* __restri
     const int lo = min(nT, tid * chunk), hi = min(nT, lo + chunk);
     unsigned s = 0, total;
     for (int i = lo; i < hi; ++i) s += tilecnt[4 * (size_t)i];
-    const unsigned eq0 = block_excl_scan(s, sw, total);
+    const unsigned eq0 = stm_block_excl_scan(s, sw, total);
     if (tid == 0) sres[0] = 0xFFFFFFFFu, sres[1] = 0u;
     __syncthreads();
     unsigned a = eq0;
@@ -295,8 +267,8 @@ __global__ __launch_bounds__(256) void ohem_scan_kernel(const unsigned* __restri
         const bool live = row < N;
         const bool eq = live && bits[row] == T;
         unsigned tot;
-        const unsigned rank = cut_pre + block_excl_scan(eq ? 1u : 0u, sw, tot);
-        (void)block_excl_scan((eq && rank < krem && t[row] == 0) ? 1u : 0u, sw, cut_taken);
+        const unsigned rank = cut_pre + stm_block_excl_scan(eq ? 1u : 0u, sw, tot);
+        (void)stm_block_excl_scan((eq && rank < krem && t[row] == 0) ? 1u : 0u, sw, cut_taken);
     }
     s = 0;
     a = eq0;
@@ -306,7 +278,7 @@ __global__ __launch_bounds__(256) void ohem_scan_kernel(const unsigned* __restri
         a += c[0];
     }
     unsigned kept;
-    unsigned kp = block_excl_scan(s, sw, kept);
+    unsigned kp = stm_block_excl_scan(s, sw, kept);
     a = eq0;
     for (int i = lo; i < hi; ++i) {
         const unsigned* c = tilecnt + 4 * (size_t)i;
@@ -319,7 +291,7 @@ __global__ __launch_bounds__(256) void ohem_scan_kernel(const unsigned* __restri
     const int blo = min(B, tid * chb), bhi = min(B, blo + chb);
     s = 0;
     for (int i = blo; i < bhi; ++i) s += npos[i];
-    unsigned cp = block_excl_scan(s, sw, total);
+    unsigned cp = stm_block_excl_scan(s, sw, total);
     for (int i = blo; i < bhi; ++i) {
         cum[i] = cp;
         cp += npos[i];
@@ -345,11 +317,11 @@ __global__ __launch_bounds__(256) void ohem_weights_kernel(const unsigned* __res
     const int64_t ti = live ? t[row] : -1;
     const bool eq = live && b == T;
     unsigned tot;
-    const unsigned er = eqpre[blockIdx.x] + block_excl_scan(eq ? 1u : 0u, sw, tot);
+    const unsigned er = eqpre[blockIdx.x] + stm_block_excl_scan(eq ? 1u : 0u, sw, tot);
     const bool pos = live && ti > 0;
     const bool neg = live && ti == 0 && (b > T || (eq && er < krem));
     const bool keep = pos || neg;
-    const unsigned kr = keeppre[blockIdx.x] + block_excl_scan(keep ? 1u : 0u, sw, tot);
+    const unsigned kr = keeppre[blockIdx.x] + stm_block_excl_scan(keep ? 1u : 0u, sw, tot);
     float wv = 0.0f;
     if (keep) {
         int img = -1;                                        // the image whose positive weight this row gets; -1: the negatives' weight
@@ -371,7 +343,7 @@ __global__ __launch_bounds__(256) void ohem_weights_kernel(const unsigned* __res
         if (neg_out) neg_out[row] = neg ? 1.0f : 0.0f;
     }
     const double term = keep ? (double)wv * (double)ce[row] : 0.0;
-    const double sum = block_sum_f64(term, sd);
+    const double sum = stm_block_sum_f64(term, sd);
     if (tid == 0) part[blockIdx.x] = sum;
 }
 
@@ -380,7 +352,7 @@ __global__ __launch_bounds__(256) void ohem_reduce_kernel(const double* __restri
     __shared__ double sd[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < nT; i += 256) s += part[i];
-    s = block_sum_f64(s, sd);
+    s = stm_block_sum_f64(s, sd);
     if (threadIdx.x == 0) *loss = (float)(alpha * s / (double)(ratio + 1));
 }
 

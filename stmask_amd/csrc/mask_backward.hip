@@ -229,45 +229,20 @@ void lb_launch(bool want_p, bool want_c, dim3 grid, hipStream_t st, const float*
 }
 
 // ------------------------------------------------------------------------------------------ decode
-// The forward (postproc.hip decode_one):  cx = p.x + (l.x * 0.1) * p.z,  w = p.z * exp(l.z * 0.2),  x1 = cx - w / 2,  x2 = w + x1  (y alike).
-// x2 is formed from the UPDATED x1 (the reference's in-place point-form step), so x2 = cx + w / 2 and
-//     d/dcx = g_x1 + g_x2,   d/dw = (g_x2 - g_x1) / 2     [-1/2 through x1 into both outputs, +1 directly into x2]
-//     grad_loc.x = d/dcx * 0.1 * p.z          grad_loc.z = d/dw * w * 0.2
-//     grad_priors.x = d/dcx                   grad_priors.z = d/dcx * (l.x * 0.1) + d/dw * exp(l.z * 0.2)
+// The forward and its adjoint are stm_decode_one / stm_decode_one_adjoint of stm_common.h (pos_loss.hip uses the same expressions).
 __global__ void decode_backward_kernel(const float4* __restrict__ grad_boxes, const float4* __restrict__ loc, const float4* __restrict__ priors,
                                        float4* __restrict__ grad_loc, float4* __restrict__ grad_priors, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float v0 = 0.1f, v1 = 0.2f;
-    const float4 gb = grad_boxes[i], l = loc[i], p = priors[i];
-    const float gcx = gb.x + gb.z, gcy = gb.y + gb.w;
-    const float gw = (gb.z - gb.x) / 2.0f, gh = (gb.w - gb.y) / 2.0f;
-    const float ew = stm_expf_canon(l.z * v1), eh = stm_expf_canon(l.w * v1);
-    if (grad_loc) grad_loc[i] = make_float4(gcx * v0 * p.z, gcy * v0 * p.w, gw * (p.z * ew) * v1, gh * (p.w * eh) * v1);
-    if (grad_priors) grad_priors[i] = make_float4(gcx, gcy, gcx * (l.x * v0) + gw * ew, gcy * (l.y * v0) + gh * eh);
+    float4 gl, gp;
+    stm_decode_one_adjoint(grad_boxes[i], loc[i], priors[i], gl, gp);
+    if (grad_loc) grad_loc[i] = gl;
+    if (grad_priors) grad_priors[i] = gp;
 }
 
 // ------------------------------------------------------------------------------------------ jaccard
-// iou = I / U,  I = mx * my,  mx = max(0, min(a.z, b.z) - max(a.x, b.x)),  U = area_a + area_b - I:
-//     dI = g (U + I) / U^2,   d area_a = d area_b = -g I / U^2
-// Ties: min(a.z, b.z) and max(a.x, b.x) pass their gradient to a's coordinate when the two are equal; an overlap extent that is not
-// strictly positive (the clamp at 0, including exactly 0) passes none.
-__device__ __forceinline__ void jaccard_pair_grad(const float4 a, const float4 b, float g, float4& da, float4& db)
-{
-    const float rx = fminf(a.z, b.z) - fmaxf(a.x, b.x), ry = fminf(a.w, b.w) - fmaxf(a.y, b.y);
-    const float mx = rx < 0.0f ? 0.0f : rx, my = ry < 0.0f ? 0.0f : ry;
-    const float inter = mx * my;
-    const float wa = a.z - a.x, ha = a.w - a.y, wb = b.z - b.x, hb = b.w - b.y;
-    const float uni = wa * ha + wb * hb - inter;
-    const float gi = g * (uni + inter) / (uni * uni);
-    const float ga = -(g * inter) / (uni * uni);          // d area_a = d area_b
-    const float gmx = rx > 0.0f ? gi * my : 0.0f, gmy = ry > 0.0f ? gi * mx : 0.0f;
-    const bool ax = a.x >= b.x, ay = a.y >= b.y, az = a.z <= b.z, aw = a.w <= b.w;
-    da = make_float4((ax ? -gmx : 0.0f) - ga * ha, (ay ? -gmy : 0.0f) - ga * wa, (az ? gmx : 0.0f) + ga * ha, (aw ? gmy : 0.0f) + ga * wa);
-    db = make_float4((ax ? 0.0f : -gmx) - ga * hb, (ay ? 0.0f : -gmy) - ga * wb, (az ? 0.0f : gmx) + ga * hb, (aw ? 0.0f : gmy) + ga * wb);
-}
-
+// The pair's adjoint with its tie and clamp conventions is stm_iou_adjoint of stm_common.h.
 // grad_a: one wave per row of a; lane l adds columns l, l + 64, ... in that order, then the lanes are added in the fixed order of stm_wave_sum
 __global__ __launch_bounds__(256) void jaccard_backward_a_kernel(const float* __restrict__ grad_out, const float4* __restrict__ a, int na,
                                                                  const float4* __restrict__ b, int nb, float4* __restrict__ grad_a)
@@ -279,7 +254,7 @@ __global__ __launch_bounds__(256) void jaccard_backward_a_kernel(const float* __
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int j = lane; j < nb; j += 64) {
         float4 da, db;
-        jaccard_pair_grad(ai, b[j], grad_out[(int64_t)i * nb + j], da, db);
+        stm_iou_adjoint(ai, b[j], grad_out[(int64_t)i * nb + j], da, db);
         s.x += da.x; s.y += da.y; s.z += da.z; s.w += da.w;
     }
     s.x = stm_wave_sum(s.x); s.y = stm_wave_sum(s.y); s.z = stm_wave_sum(s.z); s.w = stm_wave_sum(s.w);
@@ -296,7 +271,7 @@ __global__ void jaccard_backward_b_kernel(const float* __restrict__ grad_out, co
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i = 0; i < na; ++i) {
         float4 da, db;
-        jaccard_pair_grad(a[i], bj, grad_out[(int64_t)i * nb + j], da, db);
+        stm_iou_adjoint(a[i], bj, grad_out[(int64_t)i * nb + j], da, db);
         s.x += db.x; s.y += db.y; s.z += db.z; s.w += db.w;
     }
     grad_b[j] = s;

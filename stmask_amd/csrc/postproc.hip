@@ -26,24 +26,12 @@ constexpr int NMS_MAX_KEYS = 16384;
 constexpr int NMS_MAX_TOPK = 512;
 
 // ------------------------------------------------------------------------------------------ decode
-__device__ __forceinline__ float4 decode_one(const float4 l, const float4 p)
-{
-    const float v0 = 0.1f, v1 = 0.2f;
-    float t0 = l.x * v0, t1 = l.y * v0;
-    float cx = p.x + t0 * p.z;
-    float cy = p.y + t1 * p.w;
-    float w = p.z * stm_expf_canon(l.z * v1);
-    float h = p.w * stm_expf_canon(l.w * v1);
-    float x1 = cx - w / 2.0f;
-    float y1 = cy - h / 2.0f;
-    return make_float4(x1, y1, w + x1, h + y1);
-}
-
+// (stm_decode_one: stm_common.h)
 __global__ void decode_kernel(const float4* __restrict__ loc, const float4* __restrict__ priors, float4* __restrict__ boxes,
                               int64_t n)
 {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) boxes[i] = decode_one(loc[i], priors[i]);
+    if (i < n) boxes[i] = stm_decode_one(loc[i], priors[i]);
 }
 
 // Featurealign.py:46-69
@@ -115,7 +103,7 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict_
     if (box_out) {
         const float4 l = reinterpret_cast<const float4*>(loc)[gi];
         const float4 p = reinterpret_cast<const float4*>(priors)[r0 + r];
-        box_out[gi] = decode_one(l, p);
+        box_out[gi] = stm_decode_one(l, p);
     }
     const bool keep = m > thresh;
     if (flag_out) flag_out[gi] = keep ? 1 : 0;

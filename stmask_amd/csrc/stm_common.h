@@ -174,6 +174,54 @@ __device__ __forceinline__ float stm_iou(const float4 a, const float4 b)
     return inter / uni;
 }
 
+// box_utils.py decode (use_yolo_regressors = False) in fp32, reference operand order: cx = p.x + (l.x * 0.1) * p.z, w = p.z * exp(l.z * 0.2),
+// x1 = cx - w / 2, x2 = w + x1 (the reference's in-place point-form step: x2 is formed from the UPDATED x1); y alike.
+__device__ __forceinline__ float4 stm_decode_one(const float4 l, const float4 p)
+{
+    const float v0 = 0.1f, v1 = 0.2f;
+    float t0 = l.x * v0, t1 = l.y * v0;
+    float cx = p.x + t0 * p.z;
+    float cy = p.y + t1 * p.w;
+    float w = p.z * stm_expf_canon(l.z * v1);
+    float h = p.w * stm_expf_canon(l.w * v1);
+    float x1 = cx - w / 2.0f;
+    float y1 = cy - h / 2.0f;
+    return make_float4(x1, y1, w + x1, h + y1);
+}
+
+// ... and its adjoint.  x2 = cx + w / 2, so
+//     d/dcx = g_x1 + g_x2,   d/dw = (g_x2 - g_x1) / 2     [-1/2 through x1 into both outputs, +1 directly into x2]
+//     grad_loc.x = d/dcx * 0.1 * p.z          grad_loc.z = d/dw * w * 0.2
+//     grad_priors.x = d/dcx                   grad_priors.z = d/dcx * (l.x * 0.1) + d/dw * exp(l.z * 0.2)
+__device__ __forceinline__ void stm_decode_one_adjoint(const float4 gb, const float4 l, const float4 p, float4& grad_loc, float4& grad_priors)
+{
+    const float v0 = 0.1f, v1 = 0.2f;
+    const float gcx = gb.x + gb.z, gcy = gb.y + gb.w;
+    const float gw = (gb.z - gb.x) / 2.0f, gh = (gb.w - gb.y) / 2.0f;
+    const float ew = stm_expf_canon(l.z * v1), eh = stm_expf_canon(l.w * v1);
+    grad_loc = make_float4(gcx * v0 * p.z, gcy * v0 * p.w, gw * (p.z * ew) * v1, gh * (p.w * eh) * v1);
+    grad_priors = make_float4(gcx, gcy, gcx * (l.x * v0) + gw * ew, gcy * (l.y * v0) + gh * eh);
+}
+
+// Adjoint of stm_iou for one pair.  iou = I / U,  I = mx * my,  mx = max(0, min(a.z, b.z) - max(a.x, b.x)),  U = area_a + area_b - I:
+//     dI = g (U + I) / U^2,   d area_a = d area_b = -g I / U^2
+// Ties: min(a.z, b.z) and max(a.x, b.x) pass their gradient to a's coordinate when the two are equal; an overlap extent that is not
+// strictly positive (the clamp at 0, including exactly 0) passes none.
+__device__ __forceinline__ void stm_iou_adjoint(const float4 a, const float4 b, float g, float4& da, float4& db)
+{
+    const float rx = fminf(a.z, b.z) - fmaxf(a.x, b.x), ry = fminf(a.w, b.w) - fmaxf(a.y, b.y);
+    const float mx = rx < 0.0f ? 0.0f : rx, my = ry < 0.0f ? 0.0f : ry;
+    const float inter = mx * my;
+    const float wa = a.z - a.x, ha = a.w - a.y, wb = b.z - b.x, hb = b.w - b.y;
+    const float uni = wa * ha + wb * hb - inter;
+    const float gi = g * (uni + inter) / (uni * uni);
+    const float ga = -(g * inter) / (uni * uni);          // d area_a = d area_b
+    const float gmx = rx > 0.0f ? gi * my : 0.0f, gmy = ry > 0.0f ? gi * mx : 0.0f;
+    const bool ax = a.x >= b.x, ay = a.y >= b.y, az = a.z <= b.z, aw = a.w <= b.w;
+    da = make_float4((ax ? -gmx : 0.0f) - ga * ha, (ay ? -gmy : 0.0f) - ga * wa, (az ? gmx : 0.0f) + ga * ha, (aw ? gmy : 0.0f) + ga * wa);
+    db = make_float4((ax ? 0.0f : -gmx) - ga * hb, (ay ? 0.0f : -gmy) - ga * wb, (az ? 0.0f : gmx) + ga * hb, (aw ? 0.0f : gmy) + ga * wb);
+}
+
 // box_utils.py:298-316 (cast=False)
 __device__ __forceinline__ void stm_sanitize(float x1, float x2, int size, int padding, float& lo, float& hi)
 {
@@ -228,4 +276,34 @@ __device__ __forceinline__ int stm_wave_sum_rows(unsigned row_sums)
 #else
     return (int)row_sums;
 #endif
+}
+
+// exclusive prefix of v over the 256 threads of a workgroup in thread order, and the total; sw: 4 words of LDS.  Has barriers: call it uniformly.
+__device__ __forceinline__ unsigned stm_block_excl_scan(unsigned v, unsigned* sw, unsigned& total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned o = __shfl_up(inc, d);
+        if (lane >= d) inc += o;
+    }
+    __syncthreads();                                     // sw may still be read from an earlier call
+    if (lane == 63) sw[wv] = inc;
+    __syncthreads();
+    unsigned base = 0;
+    for (int i = 0; i < wv; ++i) base += sw[i];
+    total = sw[0] + sw[1] + sw[2] + sw[3];
+    return base + inc - v;
+}
+
+// sum of v over the 256 threads of a workgroup in one fixed order (xor butterfly inside a wave, then the waves in order); sd: 4 doubles of LDS
+__device__ __forceinline__ double stm_block_sum_f64(double v, double* sd)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sd[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((sd[0] + sd[1]) + sd[2]) + sd[3];
 }

@@ -4,7 +4,7 @@ synchronisation (the reference: a global-maximum log_sum_exp, a full descending 
 and three host round trips).  Conventions: include/stmask_hip.h and INTEGRATION.md section 14.
 
 ohem_use_most_confident=True (config.py: False in every STMask config) has no form here, and neither have focal_conf_loss and
-focal_conf_sigmoid_loss.  The centerness term of ohem_conf_loss (:450-455) acts on the compacted positives through decode and stays where it is."""
+focal_conf_sigmoid_loss.  The centerness term of ohem_conf_loss (:450-455) is layers.box_center_loss (pos_loss.py)."""
 import torch
 
 from .. import autograd, ops

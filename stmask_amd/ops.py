@@ -881,6 +881,106 @@ def ohem_conf_loss_backward(grad_loss, conf_data, conf_t, lse, w, negpos_ratio=3
     return grad
 
 
+def _box_center_args(who, loc_data, priors, gt_boxes_t, conf_t, centerness_data):
+    """Shapes and dtypes of the box / centerness loss, checked before anything touches the device: (loc, priors, per_image, gt, conf_t,
+    centerness [B,P] or None, B, P), the boxes fp32, contiguous and 16-byte aligned."""
+    if loc_data.dim() != 3 or loc_data.shape[-1] != 4:
+        raise StmError(f"{who}: loc_data must be [B,P,4], got {tuple(loc_data.shape)}")
+    B, P = loc_data.shape[:2]
+    if tuple(priors.shape) not in ((P, 4), (B, P, 4)):
+        raise StmError(f"{who}: priors must be [{P},4] or [{B},{P},4], got {tuple(priors.shape)}")
+    if tuple(gt_boxes_t.shape) != (B, P, 4):
+        raise StmError(f"{who}: gt_boxes_t must be [{B},{P},4], got {tuple(gt_boxes_t.shape)}")
+    if conf_t.dtype != torch.int64 or tuple(conf_t.shape) != (B, P):
+        raise StmError(f"{who}: conf_t must be int64 [{B},{P}], got {conf_t.dtype} {tuple(conf_t.shape)}")
+    if centerness_data is not None and tuple(centerness_data.shape) not in ((B, P), (B, P, 1)):
+        raise StmError(f"{who}: centerness_data must be [{B},{P},1] or [{B},{P}], got {tuple(centerness_data.shape)}")
+    if B * P == 0:
+        raise StmError(f"{who}: no priors in loc_data {tuple(loc_data.shape)}")
+    _dev(loc_data, priors, gt_boxes_t, conf_t, centerness_data)
+
+    def box(t):
+        t = _f32c(t)
+        return t.clone() if t.data_ptr() % 16 else t
+    cent = _f32c(centerness_data).view(B, P) if centerness_data is not None else None
+    return box(loc_data), box(priors), 1 if priors.dim() == 3 else 0, box(gt_boxes_t), conf_t.contiguous(), cent, B, P
+
+
+def box_center_loss(loc_data, priors, gt_boxes_t, conf_t, centerness_data=None, bboxiou_alpha=1.0, center_alpha=1.0):
+    """losses['BIoU'] (multibox_loss.py:164-172) and losses['center'] (:450-455) -> (biou, center or None, npos int32 [B]); npos is what the
+    backward needs besides the inputs.  2 launches, no host synchronisation (stm_box_center_loss_f32)."""
+    loc, pri, per_img, gt, t, cent, B, P = _box_center_args("box_center_loss", loc_data, priors, gt_boxes_t, conf_t, centerness_data)
+    dev = loc.device
+    biou = torch.empty((), dtype=torch.float32, device=dev)
+    center = torch.empty((), dtype=torch.float32, device=dev) if cent is not None else None
+    npos = torch.empty(B, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    ws = _workspace(L.stm_box_center_workspace_bytes(c_i(B), c_i(P)), dev, "bcl")
+    check(L.stm_box_center_loss_f32(_p(loc), _p(pri), c_i(per_img), _p(gt), _p(t), _p(cent), _p(biou), _p(center), _p(npos), c_i(B), c_i(P),
+                                    ctypes.c_double(float(bboxiou_alpha)), ctypes.c_double(float(center_alpha)), _p(ws), c_sz(ws.numel()),
+                                    _stream()), "stm_box_center_loss_f32")
+    return biou, center, npos
+
+
+def box_center_loss_backward(grad_biou, grad_center, loc_data, priors, gt_boxes_t, conf_t, centerness_data, npos, bboxiou_alpha=1.0,
+                             center_alpha=1.0, need_centerness=True):
+    """(grad_loc, grad_centerness or None) of box_center_loss from the two incoming gradients (0-dim device tensors; None: zero): exact zeros
+    outside the positives, decode and DIoU recomputed inside.  One launch."""
+    loc, pri, per_img, gt, t, cent, B, P = _box_center_args("box_center_loss_backward", loc_data, priors, gt_boxes_t, conf_t, centerness_data)
+    _dev(grad_biou, grad_center, npos)
+    for name, g in (("grad_biou", grad_biou), ("grad_center", grad_center)):
+        if g is not None and (g.dtype != torch.float32 or g.numel() != 1):
+            raise StmError(f"box_center_loss_backward: {name} must be one float32, got {g.dtype} {tuple(g.shape)}")
+    if npos.dtype != torch.int32 or npos.numel() != B:
+        raise StmError(f"box_center_loss_backward: npos must be int32 [{B}]")
+    grad_loc = torch.empty(B, P, 4, dtype=torch.float32, device=loc.device)
+    grad_cent = torch.empty(centerness_data.shape, dtype=torch.float32, device=loc.device) if cent is not None and need_centerness else None
+    check(_lib.lib().stm_box_center_loss_backward_f32(_p(grad_biou), _p(grad_center), _p(loc), _p(pri), c_i(per_img), _p(gt), _p(t), _p(cent),
+                                                      _p(npos.contiguous()), _p(grad_loc), _p(grad_cent), c_i(B), c_i(P),
+                                                      ctypes.c_double(float(bboxiou_alpha)), ctypes.c_double(float(center_alpha)), _stream()),
+          "stm_box_center_loss_backward_f32")
+    return grad_loc, grad_cent
+
+
+def _track_args(who, track_data, conf_t, ids_t):
+    if track_data.dim() != 3:
+        raise StmError(f"{who}: track_data must be [B,P,D], got {tuple(track_data.shape)}")
+    B, P, D = track_data.shape
+    for name, t in (("conf_t", conf_t), ("ids_t", ids_t)):
+        if t.dtype != torch.int64 or tuple(t.shape) != (B, P):
+            raise StmError(f"{who}: {name} must be int64 [{B},{P}], got {t.dtype} {tuple(t.shape)}")
+    if B * P == 0:
+        raise StmError(f"{who}: no priors in track_data {tuple(track_data.shape)}")
+    _dev(track_data, conf_t, ids_t)
+    return _f32c(track_data), conf_t.contiguous(), ids_t.contiguous(), B, P, D
+
+
+def track_loss(track_data, conf_t, ids_t, track_alpha=1.0):
+    """losses['T'] of multibox_loss.py:328-351 -> 0-dim fp32; nothing else is kept for the backward.  5 launches, no host synchronisation
+    (stm_track_loss_f32)."""
+    x, t, ids, B, P, D = _track_args("track_loss", track_data, conf_t, ids_t)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    L = _lib.lib()
+    ws = _workspace(L.stm_track_loss_workspace_bytes(c_i(B), c_i(P), c_i(D)), x.device, "trl")
+    check(L.stm_track_loss_f32(_p(x), _p(t), _p(ids), _p(loss), c_i(B), c_i(P), c_i(D), ctypes.c_double(float(track_alpha)), _p(ws),
+                               c_sz(ws.numel()), _stream()), "stm_track_loss_f32")
+    return loss
+
+
+def track_loss_backward(grad_loss, track_data, conf_t, ids_t, track_alpha=1.0):
+    """grad_track [B,P,D] of track_loss: the list of positives is rebuilt, the rows that are not positive are zeros.  5 launches."""
+    x, t, ids, B, P, D = _track_args("track_loss_backward", track_data, conf_t, ids_t)
+    _dev(grad_loss)
+    if grad_loss.dtype != torch.float32 or grad_loss.numel() != 1:
+        raise StmError(f"track_loss_backward: grad_loss must be one float32, got {grad_loss.dtype} {tuple(grad_loss.shape)}")
+    grad = torch.empty(B, P, D, dtype=torch.float32, device=x.device)
+    L = _lib.lib()
+    ws = _workspace(L.stm_track_loss_workspace_bytes(c_i(B), c_i(P), c_i(D)), x.device, "trl")
+    check(L.stm_track_loss_backward_f32(_p(grad_loss.contiguous()), _p(x), _p(t), _p(ids), _p(grad), c_i(B), c_i(P), c_i(D),
+                                        ctypes.c_double(float(track_alpha)), _p(ws), c_sz(ws.numel()), _stream()), "stm_track_loss_backward_f32")
+    return grad
+
+
 def mask_iou(m1, m2, thr=0.5, group1=None, group2=None):
     """box_utils.py:435-447 on (m > thr).  m1 [n1,h,w], m2 [n2,h,w] soft masks -> [n1,n2].  group1 / group2 (int32, any
     order; sorted rows skip whole workgroups): only pairs of the same group are computed, the others stay 0 (stm_mask_iou_grouped_f32)."""
