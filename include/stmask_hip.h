@@ -48,7 +48,9 @@
  *     stm_mask_bce_workspace_bytes, stm_mask_bce_upsampled_f32, stm_mask_bce_upsampled_backward_f32; the OHEM class-confidence loss
  *     stm_ohem_conf_workspace_bytes, stm_ohem_select_neg_f32, stm_ohem_conf_loss_f32, stm_ohem_conf_loss_backward_f32; the loss terms on the
  *     positive priors stm_box_center_workspace_bytes, stm_box_center_loss_f32, stm_box_center_loss_backward_f32,
- *     stm_track_loss_workspace_bytes, stm_track_loss_f32, stm_track_loss_backward_f32.
+ *     stm_track_loss_workspace_bytes, stm_track_loss_f32, stm_track_loss_backward_f32; the temporal-fusion loss stm_t2s_workspace_bytes,
+ *     stm_t2s_targets_f32, stm_t2s_gather_f32, stm_t2s_reduce_f32, stm_t2s_reduce_backward_f32, stm_lincomb_rows_backward_workspace_bytes,
+ *     stm_lincomb_rows_backward_f32.
  */
 #ifndef STMASK_HIP_H_
 #define STMASK_HIP_H_
@@ -945,6 +947,61 @@ int stm_track_loss_f32(const float* track, const int64_t* conf_t, const int64_t*
                        void* workspace, size_t workspace_bytes, stm_stream_t stream);
 int stm_track_loss_backward_f32(const float* grad_loss, const float* track, const int64_t* conf_t, const int64_t* ids_t, float* grad_track,
                                 int B, int P, int D, double track_alpha, void* workspace, size_t workspace_bytes, stm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Temporal-fusion loss.  Replaces track_to_segment_loss (multibox_loss.py:247-326): losses['B_shift'] and losses['M_shift'], the configuration
+ * every config uses (maskshift_loss, mask_proto_crop, sigmoid mask activation, use_yolo_regressors = False, bilinear interpolation).  RoIAlign,
+ * TemporalNet, the mask (stm_lincomb_sigmoid_crop_f32 in its row_proto / n_dev form) and its BCE (stm_mask_bce_upsampled_f32) stay what they are.
+ * The ground truth of the two frames of the B clips is concatenated by the caller: boxes_ref [G_ref_total,4] / boxes_next [G_next_total,4] fp32
+ * point form (16-byte aligned), ids_ref / ids_next DEVICE int64, offs_ref / offs_next DEVICE int32 [B+1] row offsets; at most 128 boxes per
+ * frame.  Prior p of clip i is shift-positive iff ids_t[i,p] > 0 and that id occurs in the clip's ids_ref AND ids_next (int64 equality).  Ids
+ * within a frame are expected distinct; a duplicate resolves to the LAST reference index and the FIRST next index; a positive id absent from the
+ * reference frame makes the prior not shift-positive.  Every id, offset and box value is data and cannot fault.
+ *
+ * stm_t2s_targets_f32 (3 launches).  ids_t [B,P] -> pos_t int64 [B,P] (0 / 1), reg_t [B,P,4] = encode(box_next(id), center_size(box_ref(id)))
+ *   as stm_encode_boxes_f32 (exact zeros where not positive), idx_next int64 [B,P] (the GLOBAL row of the id among the next-frame boxes, -1
+ *   where not positive), prefix int32 [B+1] (NULL: not wanted): the exclusive prefix of the per-clip counts n_i, prefix[B] = n.  The workspace
+ *   (stm_t2s_workspace_bytes(B, P), 8-byte aligned) keeps the ordered list of the n shift-positive rows, their weights 1 / n_i, n, and the
+ *   status word n > max_rows (max_rows <= 0: no cap) for stm_t2s_gather_f32.
+ * stm_t2s_gather_f32 (1 launch).  n_rows rows through the list, the live count read on the device: rois [n_rows,5] = (clip,
+ *   sanitize_coordinates_hw(decode(loc_ref, priors), feat_h, feat_w)), bit-identical to stm_shift_rois_f32 of stm_decode_boxes_f32; reg_rows
+ *   [n_rows,4]; coeff_rows [n_rows,M] from coeff_ref [B,P,M]; box_rows [n_rows,4] the next-frame box; idx_rows int64 [n_rows] its global row;
+ *   row_clip int32 [n_rows]; w_rows [n_rows] = 1 / n_i; *n_dev = min(n, n_rows); *status = (n > max_rows).  Rows past n are padding: weight 0,
+ *   RoI (0; 0, 0, 1, 1), box (0, 0, 1, 1), zero coefficients and targets, row 0, clip 0.  loc_ref [B,P,4], priors [P,4].
+ * stm_t2s_reduce_f32 (1 launch).  bbox_reg [n_rows,4], bce [n_rows] (the mask BCE sums), H x W the mask size:
+ *     *b_shift = boxshift_alpha  / B * sum_r w_r sum_c smooth_l1(bbox_reg[r,c] - reg_rows[r,c])        (beta = 1)
+ *     *m_shift = maskshift_alpha / B * sum_r w_r bce_r / ((x2 - x1) W) / ((y2 - y1) H)                 (the box not clamped, :314-317)
+ *   over the live rows; fp32 terms, products and sums in double in a fixed order that does not depend on n_rows.  m_shift NULL: skipped.
+ *   A set status word makes both NaN.
+ * stm_t2s_reduce_backward_f32 (1 launch).  grad_bbox_reg [n_rows,4] = *grad_b * boxshift_alpha / B * w_r * clamp(d, -1, 1) and grad_bce
+ *   [n_rows] = *grad_m * maskshift_alpha / B * w_r / ((x2 - x1) W) / ((y2 - y1) H), written; padding rows are exact zeros; all NaN under a set
+ *   status word.  Either output may be NULL.
+ * stm_lincomb_rows_backward_f32 (2 launches).  grad_coeff [n,M] of stm_lincomb_sigmoid_crop_f32 with row_proto / n_dev: proto [n_proto,h,w,M],
+ *   row r uses set row_proto[r] (NULL: set 0).  Sums over the pixels of the row's crop rectangle only (grad_out is not read outside), the
+ *   e / (1 + e)^2 and 4 e / (1 + e)^2 forms of stm_lincomb_backward_f32, a fixed-order two-stage sum without atomics; with one set the result
+ *   equals stm_lincomb_backward_f32's bit for bit.  Rows past *n_dev are zeros.  No gradient w.r.t. the prototypes.  m in {8, 32, 64}.
+ * Shapes: B, P >= 1 (else STM_EINVAL); B * P <= 2^22, at most 128 boxes per frame, n_rows <= 65535 (else STM_EUNSUPPORTED); checked before any
+ * launch.  No float atomics; every grid depends on the shapes only.
+ * ------------------------------------------------------------------------------------------------- */
+size_t stm_t2s_workspace_bytes(int B, int P);
+int stm_t2s_targets_f32(const int64_t* ids_t, const float* boxes_ref, const int64_t* ids_ref, const int* offs_ref, int G_ref_total, int G_ref_max,
+                        const float* boxes_next, const int64_t* ids_next, const int* offs_next, int G_next_total, int G_next_max, int64_t* pos_t,
+                        float* reg_t, int64_t* idx_next, int* prefix, int B, int P, int max_rows, void* workspace, size_t workspace_bytes,
+                        stm_stream_t stream);
+int stm_t2s_gather_f32(const float* loc_ref, const float* priors, const float* coeff_ref, const float* reg_t, const int64_t* idx_next,
+                       const float* boxes_next, int G_next_total, float* rois, float* reg_rows, float* coeff_rows, float* box_rows,
+                       int64_t* idx_rows, int* row_clip, float* w_rows, int* n_dev, int* status, int n_rows, int B, int P, int M, int feat_h,
+                       int feat_w, const void* workspace, size_t workspace_bytes, stm_stream_t stream);
+int stm_t2s_reduce_f32(const float* bbox_reg, const float* reg_rows, const float* bce, const float* box_rows, const float* w_rows,
+                       const int* n_dev, const int* status, float* b_shift, float* m_shift, int n_rows, int B, int H, int W,
+                       double boxshift_alpha, double maskshift_alpha, stm_stream_t stream);
+int stm_t2s_reduce_backward_f32(const float* grad_b, const float* grad_m, const float* bbox_reg, const float* reg_rows, const float* box_rows,
+                                const float* w_rows, const int* n_dev, const int* status, float* grad_bbox_reg, float* grad_bce, int n_rows,
+                                int B, int H, int W, double boxshift_alpha, double maskshift_alpha, stm_stream_t stream);
+size_t stm_lincomb_rows_backward_workspace_bytes(int n, int h, int w, int m);
+int stm_lincomb_rows_backward_f32(const float* grad_out, const float* proto, int n_proto, const float* coeff, const float* boxes,
+                                  const int* row_proto, const int* n_dev, float* grad_coeff, int h, int w, int m, int n, int apply_tanh,
+                                  void* workspace, size_t workspace_bytes, stm_stream_t stream);
 
 #ifdef __cplusplus
 }

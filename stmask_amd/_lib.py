@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "stm_ohem_conf_workspace_bytes", "stm_ohem_select_neg_f32", "stm_ohem_conf_loss_f32", "stm_ohem_conf_loss_backward_f32",
     "stm_box_center_workspace_bytes", "stm_box_center_loss_f32", "stm_box_center_loss_backward_f32",
     "stm_track_loss_workspace_bytes", "stm_track_loss_f32", "stm_track_loss_backward_f32",
+    "stm_t2s_workspace_bytes", "stm_t2s_targets_f32", "stm_t2s_gather_f32", "stm_t2s_reduce_f32", "stm_t2s_reduce_backward_f32",
+    "stm_lincomb_rows_backward_workspace_bytes", "stm_lincomb_rows_backward_f32",
     "stm_mask_bce_workspace_bytes", "stm_mask_bce_upsampled_f32", "stm_mask_bce_upsampled_backward_f32",
 ]
 
@@ -97,7 +99,8 @@ def lib():
         for name in ("stm_deform_conv_workspace_bytes", "stm_gemm_workspace_bytes", "stm_mask_rle_workspace_bytes", "stm_detect_cc_workspace_bytes", "stm_fast_nms_workspace_bytes",
                      "stm_mask_iou_workspace_bytes", "stm_conv_packed_weight_bytes", "stm_conv_packed_weight_bytes_tiled", "stm_cc_fast_nms_workspace_bytes", "stm_conv_kxr_packed_bytes", "stm_stem_packed_weight_bytes", "stm_chain_tail_weight_bytes", "stm_chain_tail_weight_bytes_proj", "stm_fast_nms_batched_workspace_bytes", "stm_render_workspace_bytes",
                      "stm_lincomb_backward_workspace_bytes", "stm_match_workspace_bytes", "stm_mask_bce_workspace_bytes", "stm_ohem_conf_workspace_bytes",
-                     "stm_box_center_workspace_bytes", "stm_track_loss_workspace_bytes"):
+                     "stm_box_center_workspace_bytes", "stm_track_loss_workspace_bytes", "stm_t2s_workspace_bytes",
+                     "stm_lincomb_rows_backward_workspace_bytes"):
             getattr(_lib, name).restype = c_sz
         _lib.stm_struct_bytes.restype = c_sz
         _lib.stm_debug_reload_tunables.restype = None

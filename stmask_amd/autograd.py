@@ -1,12 +1,12 @@
 """Autograd for the drop-in deformable convolution, RoIAlign and correlation (the training path of dcn_v2 / mmcv.ops /
 spatial_correlation_sampler) and for the layer functions the reference's loss differentiates through -- generate_mask, decode, jaccard and
-the mask loss tail mask_bce_sum, the OHEM class-confidence loss ohem_conf_loss and the positive-prior terms box_center_loss and track_loss
-(INTEGRATION.md section 14).
+the mask loss tail mask_bce_sum, the OHEM class-confidence loss ohem_conf_loss, the positive-prior terms box_center_loss and track_loss and
+the pieces of track_to_segment_loss: the row-prototype form of generate_mask and the two weighted reductions.
 
 Each Function's forward is the launch the shim makes without autograd (ops.deform_conv / roi_align / corr_patch), so values under
 autograd are bit-identical to the no-grad call.  Only inputs are saved: the deformable columns are recomputed in backward with the
 forward's own im2col, the mask sigmoid from the prototypes and coefficients.  Backward runs the gfx950 kernels of csrc/deform_backward.hip,
-csrc/temporal_backward.hip, csrc/mask_backward.hip, csrc/mask_loss.hip, csrc/conf_loss.hip and csrc/pos_loss.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
+csrc/temporal_backward.hip, csrc/mask_backward.hip, csrc/mask_loss.hip, csrc/conf_loss.hip, csrc/pos_loss.hip and csrc/t2s_loss.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
 every backward is @first_order_only: a double backward (create_graph=True, then differentiating the result) raises instead of
 silently dropping the second-order term.
 """
@@ -284,6 +284,46 @@ class TrackLossFunction(torch.autograd.Function):
         return ops.track_loss_backward(grad_loss.contiguous(), track_data, conf_t, ids_t, ctx.alpha), None, None, None
 
 
+class LincombRowsFunction(torch.autograd.Function):
+    """generate_mask over the rows of many prototype sets: proto [S,h,w,M] (read detached), coeff [n,M], boxes [n,4], row_proto int32 [n],
+    n_dev int32 [1] or None -> [n,h,w].  Gradient w.r.t. the coefficients only."""
+
+    @staticmethod
+    def forward(ctx, coeff, proto, boxes, row_proto, n_dev):
+        ctx.save_for_backward(coeff, proto, boxes, row_proto, n_dev)
+        return ops.lincomb_sigmoid_crop(proto, coeff, boxes, apply_tanh=True, n_dev=n_dev, row_proto=row_proto)
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        coeff, proto, boxes, row_proto, n_dev = ctx.saved_tensors
+        return ops.lincomb_rows_backward(grad_out.contiguous(), proto, coeff, boxes, row_proto, n_dev, apply_tanh=True), None, None, None, None
+
+
+class T2sReduceFunction(torch.autograd.Function):
+    """The two weighted sums of track_to_segment_loss: bbox_reg [n,4], bce [n] and the rows of ops.t2s_gather -> (B_shift, M_shift).  Gradients
+    w.r.t. bbox_reg and bce only."""
+
+    @staticmethod
+    def forward(ctx, bbox_reg, bce, reg_rows, box_rows, w_rows, n_dev, status, bs, H, W, boxshift_alpha, maskshift_alpha):
+        ctx.args = (bs, H, W, boxshift_alpha, maskshift_alpha)
+        ctx.save_for_backward(bbox_reg, reg_rows, box_rows, w_rows, n_dev, status)
+        return ops.t2s_reduce(bbox_reg, reg_rows, bce, box_rows, w_rows, n_dev, status, *ctx.args)
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_b, grad_m):
+        nr, nb = ctx.needs_input_grad[:2]
+        if not (nr or nb):
+            return (None,) * 12
+        bbox_reg, reg_rows, box_rows, w_rows, n_dev, status = ctx.saved_tensors
+        g_reg, g_bce = ops.t2s_reduce_backward(grad_b, grad_m, bbox_reg, reg_rows, box_rows, w_rows, n_dev, status, *ctx.args, need_reg=nr,
+                                               need_bce=nb)
+        return (g_reg, g_bce) + (None,) * 10
+
+
 def modulated_deform_conv(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups):
     return ModulatedDeformConvFunction.apply(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups, False)
 
@@ -331,3 +371,11 @@ def box_center_loss(loc_data, priors, gt_boxes_t, conf_t, centerness_data=None, 
 
 def track_loss(track_data, conf_t, ids_t, track_alpha=1.0):
     return TrackLossFunction.apply(track_data, conf_t, ids_t, track_alpha)
+
+
+def lincomb_mask_rows(proto, coeff, boxes, row_proto, n_dev=None):
+    return LincombRowsFunction.apply(coeff, proto, boxes, row_proto, n_dev)
+
+
+def t2s_reduce(bbox_reg, bce, reg_rows, box_rows, w_rows, n_dev, status, bs, H, W, boxshift_alpha=1.0, maskshift_alpha=1.0):
+    return T2sReduceFunction.apply(bbox_reg, bce, reg_rows, box_rows, w_rows, n_dev, status, bs, H, W, boxshift_alpha, maskshift_alpha)

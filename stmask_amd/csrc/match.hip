@@ -63,17 +63,6 @@ __device__ __forceinline__ bool mt_image_range(const int* __restrict__ offs, int
     return ok;
 }
 
-// box_utils.py:223-233 (use_yolo_regressors=False).  Columns 0-1 in the reference's operand order; the log in double, rounded once.
-__device__ __forceinline__ float4 mt_encode(const float4 m, const float4 p)
-{
-    float4 o;
-    o.x = ((m.x + m.z) / 2.0f - p.x) / (0.1f * p.z);
-    o.y = ((m.y + m.w) / 2.0f - p.y) / (0.1f * p.w);
-    o.z = (float)log((double)((m.z - m.x) / p.z)) / 0.2f;
-    o.w = (float)log((double)((m.w - m.y) / p.w)) / 0.2f;
-    return o;
-}
-
 __global__ __launch_bounds__(MT_TILE) void match_overlap_kernel(const float4* __restrict__ boxes, const int64_t* __restrict__ labels,
                                                                 const int* __restrict__ offs, int G_total, int g_max,
                                                                 const float4* __restrict__ priors, int64_t prior_bstride, const float* __restrict__ conf,
@@ -317,7 +306,7 @@ __global__ __launch_bounds__(MT_TILE) void match_finalise_kernel(const float4* _
         id = 0;
     }
     if (best < neg2) c = 0;
-    loc_t[bp] = mt_encode(m, priors[(int64_t)b * prior_bstride + p]);
+    loc_t[bp] = stm_encode_one(m, priors[(int64_t)b * prior_bstride + p]);
     gt_boxes_t[bp] = m;
     conf_t[bp] = c;
     idx_t[bp] = g;
@@ -328,7 +317,7 @@ __global__ __launch_bounds__(256) void encode_kernel(const float4* __restrict__ 
                                                      int64_t n)
 {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n) out[t] = mt_encode(matched[t], priors[t]);
+    if (t < n) out[t] = stm_encode_one(matched[t], priors[t]);
 }
 
 bool mt_aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }

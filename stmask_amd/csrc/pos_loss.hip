@@ -37,11 +37,10 @@
 // at the n ~ 10^3 of training.  D <= 512 bounds the recomputation of the dots over the column slabs to 4 x.
 // Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): no kernel of this file uses scratch.
 #include "stm_common.h"
+#include "pos_index.h"
 
 namespace {
 
-constexpr int PL_TILE = 256;
-constexpr int PL_MAX_N = 1 << 22;
 constexpr int TL_MAX_D = 512;
 constexpr int TL_BLK = 64;             // positives per row / column block
 constexpr int TL_DC = 32;              // columns of track_data staged at a time
@@ -49,19 +48,6 @@ constexpr int TL_LD = TL_DC + 1;       // pitch of the staging tiles
 constexpr int TL_G = 256;              // workgroups of the persistent pair grid
 constexpr int TL_SLAB = 128;           // columns of grad_track per adjoint workgroup
 constexpr int TL_CLD = TL_BLK + 1;     // pitch of the coefficient tile
-
-enum { TM_N = 0, TM_W = 2, TM_WORDS = 4 };   // meta: n, then W as a double at word 2
-
-__device__ __forceinline__ float pl_weight(unsigned npos) { return (float)(1.0 / (double)(npos > 1u ? npos : 1u)); }
-
-// the tile's image, its first row in the flattened [B * P] order and how many of its 256 threads have a row
-__device__ __forceinline__ void pl_tile(int tpi, int P, int& img, int64_t& row0, int& rows)
-{
-    img = blockIdx.x / tpi;
-    const int p0 = (blockIdx.x - img * tpi) * PL_TILE;
-    row0 = (int64_t)img * P + p0;
-    rows = min(PL_TILE, P - p0);
-}
 
 // ------------------------------------------------------------------------------------------ DIoU
 struct Diou {
@@ -235,71 +221,6 @@ TrackLayout track_layout(int B, int P)
     L.wts = o;     o += N;
     L.words = o;
     return L;
-}
-
-__global__ __launch_bounds__(256) void pos_count_kernel(const int64_t* __restrict__ conf_t, unsigned* __restrict__ tilecnt, int P, int tpi)
-{
-    __shared__ unsigned sc[4];
-    int img, rows;
-    int64_t row0;
-    pl_tile(tpi, P, img, row0, rows);
-    const int tid = threadIdx.x;
-    const bool pos = tid < rows && conf_t[row0 + tid] > 0;
-    const unsigned long long m = __ballot(pos);
-    if ((tid & 63) == 0) sc[tid >> 6] = (unsigned)__popcll(m);
-    __syncthreads();
-    if (tid == 0) tilecnt[blockIdx.x] = sc[0] + sc[1] + sc[2] + sc[3];
-}
-
-__global__ __launch_bounds__(256) void pos_scan_kernel(const unsigned* __restrict__ tilecnt, unsigned* __restrict__ tilepre,
-                                                       unsigned* __restrict__ npos, unsigned* __restrict__ meta, int nT, int B, int tpi)
-{
-    __shared__ unsigned sw[4];
-    __shared__ double sd[4];
-    const int tid = threadIdx.x;
-    const int chunk = (nT + 255) / 256;
-    const int lo = min(nT, tid * chunk), hi = min(nT, lo + chunk);
-    unsigned s = 0, total;
-    for (int i = lo; i < hi; ++i) s += tilecnt[i];
-    unsigned a = stm_block_excl_scan(s, sw, total);
-    for (int i = lo; i < hi; ++i) {
-        tilepre[i] = a;
-        a += tilecnt[i];
-    }
-    double s1 = 0.0, s2 = 0.0;
-    for (int b = tid; b < B; b += 256) {
-        unsigned cnt = 0;
-        for (int t = 0; t < tpi; ++t) cnt += tilecnt[(size_t)b * tpi + t];
-        npos[b] = cnt;
-        const double w = (double)pl_weight(cnt);
-        s1 += (double)cnt * w;
-        s2 += (double)cnt * w * w;
-    }
-    s1 = stm_block_sum_f64(s1, sd);
-    s2 = stm_block_sum_f64(s2, sd);
-    if (tid == 0) {
-        meta[TM_N] = total;
-        meta[1] = 0u;
-        *reinterpret_cast<double*>(meta + TM_W) = total >= 2u ? (s1 * s1 - s2) / 2.0 : 0.0;
-    }
-}
-
-__global__ __launch_bounds__(256) void pos_index_kernel(const int64_t* __restrict__ conf_t, const unsigned* __restrict__ tilepre,
-                                                        const unsigned* __restrict__ npos, int* __restrict__ idx, float* __restrict__ wts, int P,
-                                                        int tpi)
-{
-    __shared__ unsigned sw[4];
-    int img, rows;
-    int64_t row0;
-    pl_tile(tpi, P, img, row0, rows);
-    const int tid = threadIdx.x;
-    const bool pos = tid < rows && conf_t[row0 + tid] > 0;
-    unsigned total;
-    const unsigned rank = tilepre[blockIdx.x] + stm_block_excl_scan(pos ? 1u : 0u, sw, total);
-    if (pos) {
-        idx[rank] = (int)(row0 + tid);
-        wts[rank] = pl_weight(npos[img]);
-    }
 }
 
 // Rows blk * 64 .. + 63 of the list, columns k0 .. k0 + TL_DC - 1 of track_data -> tile[64][TL_LD]; rows past n and columns past D are zeros.
@@ -529,7 +450,8 @@ int track_index(const int64_t* conf_t, int B, int P, unsigned* ws, const TrackLa
     const int tpi = stm_cdiv(P, PL_TILE), nT = B * tpi;
     hipLaunchKernelGGL(pos_count_kernel, dim3(nT), dim3(256), 0, st, conf_t, ws + L.tilecnt, P, tpi);
     STM_CHECK_LAUNCH("pos_count_kernel");
-    hipLaunchKernelGGL(pos_scan_kernel, dim3(1), dim3(256), 0, st, ws + L.tilecnt, ws + L.tilepre, ws + L.npos, ws + L.meta, nT, B, tpi);
+    hipLaunchKernelGGL(pos_scan_kernel, dim3(1), dim3(256), 0, st, ws + L.tilecnt, ws + L.tilepre, ws + L.npos, ws + L.meta,
+                       static_cast<int*>(nullptr), 0xFFFFFFFFu, nT, B, tpi);
     STM_CHECK_LAUNCH("pos_scan_kernel");
     hipLaunchKernelGGL(pos_index_kernel, dim3(nT), dim3(256), 0, st, conf_t, ws + L.tilepre, ws + L.npos, reinterpret_cast<int*>(ws + L.idx),
                        reinterpret_cast<float*>(ws + L.wts), P, tpi);

@@ -233,6 +233,29 @@ __device__ __forceinline__ void stm_sanitize(float x1, float x2, int size, int p
     hi = h > (float)size ? (float)size : h;
 }
 
+// box_utils.py:223-233 encode (use_yolo_regressors = False): m point form, p centre-size.  Columns 0-1 in the reference's operand order; the log in
+// double, rounded once.  Shared by the target assignment (match.hip) and the temporal-fusion targets (t2s_loss.hip).
+__device__ __forceinline__ float4 stm_encode_one(const float4 m, const float4 p)
+{
+    float4 o;
+    o.x = ((m.x + m.z) / 2.0f - p.x) / (0.1f * p.z);
+    o.y = ((m.y + m.w) / 2.0f - p.y) / (0.1f * p.w);
+    o.z = (float)log((double)((m.z - m.x) / p.z)) / 0.2f;
+    o.w = (float)log((double)((m.w - m.y) / p.w)) / 0.2f;
+    return o;
+}
+
+// bbox_feat_extractor's box -> RoI conversion: sanitize_coordinates_hw(box, fh, fw) with cast=False, padding 0 (box_utils.py:298-337), behind the
+// clip index.  Shared by CandidateShift's RoIs (tracker.hip) and the temporal-fusion loss (t2s_loss.hip).
+__device__ __forceinline__ void stm_roi_one(const float4 b, float clip, int fh, int fw, float* __restrict__ o)
+{
+    float x1, x2, y1, y2;
+    stm_sanitize(b.x, b.z, fw, 0, x1, x2);
+    stm_sanitize(b.y, b.w, fh, 0, y1, y2);
+    o[0] = clip;
+    o[1] = x1; o[2] = y1; o[3] = x2; o[4] = y2;
+}
+
 // Sum over the 16 lanes of a DPP row (lanes 16 q .. 16 q + 15): four data-parallel-primitive moves at VALU speed, every lane of the row ends with the
 // row's sum -- quad_perm [1, 0, 3, 2], quad_perm [2, 3, 0, 1], row_half_mirror, row_mirror.  (__shfl_xor goes through ds_bpermute: an LDS round trip
 // per step; the tail kernels that fold many small sums spent most of their time there.)  One fixed order: run-to-run identical.

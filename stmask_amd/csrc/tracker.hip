@@ -57,12 +57,7 @@ __global__ __launch_bounds__(256) void shift_rois_kernel(const float* __restrict
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= n) return;
     const float4 b = reinterpret_cast<const float4*>(box)[r];
-    float x1, x2, y1, y2;
-    stm_sanitize(b.x, b.z, fw, 0, x1, x2);
-    stm_sanitize(b.y, b.w, fh, 0, y1, y2);
-    float* o = rois + (int64_t)r * 5;
-    o[0] = (float)clip[r];
-    o[1] = x1; o[2] = y1; o[3] = x2; o[4] = y2;
+    stm_roi_one(b, (float)clip[r], fh, fw, rois + (int64_t)r * 5);
 }
 
 // box' = decode(loc_shift, center_size(box)) (box_utils.py:25-35,238-283); coeff' = coeff + coeff_shift; score' = score * 0.95

@@ -21,6 +21,20 @@ def generate_mask(proto_data, mask_coeff, bbox=None, use_sipmask=False):
     return ops.lincomb_sigmoid_crop(proto_data, mask_coeff, bbox, apply_tanh=True)
 
 
+def generate_mask_rows(proto_data, mask_coeff, bbox, row_proto, n_dev=None):
+    """generate_mask for rows of many clips in one launch: proto_data [bs,h,w,M] (read detached), mask_coeff [n,M], bbox [n,4], row_proto int32 [n]
+    (row i uses proto_data[row_proto[i]]), n_dev int32 [1] or None (rows past it are zeros) -> [n,h,w], bit-identical to per-clip generate_mask
+    calls.  Gradient w.r.t. mask_coeff only (autograd.LincombRowsFunction over csrc/t2s_loss.hip)."""
+    proto_data = proto_data.detach()
+    if proto_data.dim() != 4:
+        raise ValueError(f"generate_mask_rows: proto_data must be [bs,h,w,M], got {tuple(proto_data.shape)}")
+    if mask_coeff.shape[0] == 0:
+        return proto_data.new_zeros(0, proto_data.shape[1], proto_data.shape[2])
+    if autograd.wants_grad(mask_coeff):
+        return autograd.lincomb_mask_rows(proto_data, mask_coeff, bbox.detach(), row_proto, n_dev)
+    return ops.lincomb_sigmoid_crop(proto_data, mask_coeff, bbox, apply_tanh=True, n_dev=n_dev, row_proto=row_proto)
+
+
 def mask_bce_sum(pred_masks_soft, mask_gt, idx=None):
     """pred_masks_soft [n,h,w] (generate_mask's output), mask_gt [G,H,W] uint8 / bool / float32, idx [n] int64 or None (row i uses mask i) -> [n]:
         F.binary_cross_entropy(clamp(F.interpolate(pred[None], (H, W), mode="bilinear", align_corners=False)[0], 0, 1), mask_gt[idx].float(),

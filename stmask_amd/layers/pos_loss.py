@@ -4,7 +4,7 @@ indexing: no host synchronisation, the positives' weights 1 / max(npos_b, 1) of 
 ever built (the reference: three host round trips, decode and get_DIoU twice, a full n x n jaccard for its diagonal, and about eight n x n
 temporaries for the track loss).  Conventions: include/stmask_hip.h and INTEGRATION.md section 14.
 
-coeff_diversity_loss, semantic_segmentation_loss and track_to_segment_loss have no form here."""
+coeff_diversity_loss and semantic_segmentation_loss have no form here; track_to_segment_loss is layers/t2s_loss.py."""
 import torch
 
 from .. import autograd, ops

@@ -981,6 +981,148 @@ def track_loss_backward(grad_loss, track_data, conf_t, ids_t, track_alpha=1.0):
     return grad
 
 
+def _t2s_frames(who, boxes, ids, counts, B, dev):
+    counts = [int(c) for c in counts]
+    G = sum(counts)
+    if len(counts) != B:
+        raise StmError(f"{who}: {len(counts)} per-clip box counts for {B} clips")
+    if boxes.dtype != torch.float32 or tuple(boxes.shape) != (G, 4) or ids.dtype != torch.int64 or tuple(ids.shape) != (G,):
+        raise StmError(f"{who}: boxes {boxes.dtype} {tuple(boxes.shape)} / ids {ids.dtype} {tuple(ids.shape)} for {G} boxes (float32 [G,4], int64 [G])")
+    _dev(boxes, ids)
+    return boxes.contiguous(), ids.contiguous(), counts, G, (max(counts) if counts else 0)
+
+
+def t2s_targets(ids_t, boxes_ref, ids_ref, counts_ref, boxes_next, ids_next, counts_next, max_rows=None, offsets=None):
+    """The targets of track_to_segment_loss (multibox_loss.py:253-271, :291) for a batch in three launches (stm_t2s_targets_f32).  ids_t int64
+    [B,P]; the boxes (fp32 [G,4] point form) and ids (int64 [G]) of the reference and the next frames of all clips concatenated, counts_*: the
+    per-clip numbers of boxes (Python ints).  Returns (pos_t int64 [B,P], reg_t [B,P,4], idx_next int64 [B,P], prefix int32 [B+1], state); state
+    holds the ordered list of the shift-positive rows for t2s_gather.  No host synchronisation."""
+    if ids_t.dtype != torch.int64 or ids_t.dim() != 2 or ids_t.numel() == 0:
+        raise StmError(f"t2s_targets: ids_t must be a non-empty int64 [B,P], got {ids_t.dtype} {tuple(ids_t.shape)}")
+    _dev(ids_t)
+    B, P = ids_t.shape
+    dev = ids_t.device
+    boxes_ref, ids_ref, counts_ref, Gr, Gr_max = _t2s_frames("t2s_targets", boxes_ref, ids_ref, counts_ref, B, dev)
+    boxes_next, ids_next, counts_next, Gn, Gn_max = _t2s_frames("t2s_targets", boxes_next, ids_next, counts_next, B, dev)
+    if offsets is None:
+        acc = [[0], [0]]
+        for a, counts in zip(acc, (counts_ref, counts_next)):
+            for c in counts:
+                a.append(a[-1] + c)
+        both = torch.tensor(acc, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)      # one asynchronous copy, no synchronisation
+        offsets = (both[0], both[1])
+    ids_t = ids_t.contiguous()
+    pos_t = torch.empty(B, P, dtype=torch.int64, device=dev)
+    reg_t = torch.empty(B, P, 4, dtype=torch.float32, device=dev)
+    idx_next = torch.empty(B, P, dtype=torch.int64, device=dev)
+    prefix = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    nbytes = L.stm_t2s_workspace_bytes(c_i(B), c_i(P))
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)           # kept by the caller until the gather has run: not the shared scratch
+    check(L.stm_t2s_targets_f32(_p(ids_t), _p(boxes_ref), _p(ids_ref), _p(offsets[0]), c_i(Gr), c_i(Gr_max), _p(boxes_next), _p(ids_next),
+                                _p(offsets[1]), c_i(Gn), c_i(Gn_max), _p(pos_t), _p(reg_t), _p(idx_next), _p(prefix), c_i(B), c_i(P),
+                                c_i(int(max_rows) if max_rows else 0), _p(ws), c_sz(ws.numel()), _stream()), "stm_t2s_targets_f32")
+    return pos_t, reg_t, idx_next, prefix, ws
+
+
+def t2s_gather(state, n_rows, loc_ref, priors, coeff_ref, reg_t, idx_next, boxes_next, feat_h, feat_w):
+    """n_rows rows through t2s_targets' list in one launch (stm_t2s_gather_f32) -> dict of rois [n,5], reg [n,4], coeff [n,M], box [n,4], idx
+    int64 [n], clip int32 [n], w [n], n_dev int32 [1] (min(live count, n_rows)), status int32 [1] (1: more shift-positives than the cap given to
+    t2s_targets).  Rows past the live count are padding.  No host synchronisation."""
+    _dev(state, loc_ref, priors, coeff_ref, reg_t, idx_next, boxes_next)
+    loc_ref, priors, coeff_ref = _f32c(loc_ref), _f32c(priors), _f32c(coeff_ref)
+    if loc_ref.dim() != 3 or loc_ref.shape[2] != 4:
+        raise StmError(f"t2s_gather: loc_ref must be [B,P,4], got {tuple(loc_ref.shape)}")
+    B, P = loc_ref.shape[:2]
+    if tuple(priors.shape) != (P, 4) or coeff_ref.dim() != 3 or tuple(coeff_ref.shape[:2]) != (B, P) or tuple(reg_t.shape) != (B, P, 4) or \
+            tuple(idx_next.shape) != (B, P) or idx_next.dtype != torch.int64 or boxes_next.dim() != 2 or boxes_next.shape[0] < 1:
+        raise StmError(f"t2s_gather: priors {tuple(priors.shape)}, coeff_ref {tuple(coeff_ref.shape)}, reg_t {tuple(reg_t.shape)}, idx_next "
+                       f"{tuple(idx_next.shape)}, boxes_next {tuple(boxes_next.shape)} do not fit loc_ref {tuple(loc_ref.shape)}")
+    M = coeff_ref.shape[2]
+    n = int(n_rows)
+    dev = loc_ref.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = dict(rois=torch.empty(n, 5, **f32), reg=torch.empty(n, 4, **f32), coeff=torch.empty(n, M, **f32), box=torch.empty(n, 4, **f32),
+               idx=torch.empty(n, dtype=torch.int64, device=dev), clip=torch.empty(n, dtype=torch.int32, device=dev), w=torch.empty(n, **f32),
+               n_dev=torch.empty(1, dtype=torch.int32, device=dev), status=torch.empty(1, dtype=torch.int32, device=dev))
+    check(_lib.lib().stm_t2s_gather_f32(_p(loc_ref), _p(priors), _p(coeff_ref), _p(_f32c(reg_t)), _p(idx_next.contiguous()), _p(_f32c(boxes_next)),
+                                        c_i(boxes_next.shape[0]), _p(out["rois"]), _p(out["reg"]), _p(out["coeff"]), _p(out["box"]), _p(out["idx"]),
+                                        _p(out["clip"]), _p(out["w"]), _p(out["n_dev"]), _p(out["status"]), c_i(n), c_i(B), c_i(P), c_i(M),
+                                        c_i(feat_h), c_i(feat_w), _p(state), c_sz(state.numel()), _stream()), "stm_t2s_gather_f32")
+    return out
+
+
+def _t2s_rows(who, bbox_reg, reg_rows, bce, box_rows, w_rows, n_dev, status):
+    n = bbox_reg.shape[0]
+    for name, t, shp in (("bbox_reg", bbox_reg, (n, 4)), ("reg_rows", reg_rows, (n, 4)), ("bce", bce, (n,)), ("box_rows", box_rows, (n, 4)),
+                         ("w_rows", w_rows, (n,))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shp):
+            raise StmError(f"{who}: {name} must be float32 {shp}, got {t.dtype} {tuple(t.shape)}")
+    if n < 1 or n_dev.dtype != torch.int32 or status.dtype != torch.int32:
+        raise StmError(f"{who}: {n} rows, n_dev {n_dev.dtype}, status {status.dtype}")
+    _dev(bbox_reg, reg_rows, bce, box_rows, w_rows, n_dev, status)
+    return n
+
+
+def t2s_reduce(bbox_reg, reg_rows, bce, box_rows, w_rows, n_dev, status, bs, H, W, boxshift_alpha=1.0, maskshift_alpha=1.0):
+    """(B_shift, M_shift) as 0-dim fp32 from the rows of t2s_gather, TemporalNet's bbox_reg [n,4] and the mask BCE sums bce [n]
+    (stm_t2s_reduce_f32: one launch, sums in double in a fixed order)."""
+    n = _t2s_rows("t2s_reduce", bbox_reg, reg_rows, bce, box_rows, w_rows, n_dev, status)
+    b = torch.empty((), dtype=torch.float32, device=bbox_reg.device)
+    m = torch.empty((), dtype=torch.float32, device=bbox_reg.device)
+    check(_lib.lib().stm_t2s_reduce_f32(_p(bbox_reg.contiguous()), _p(reg_rows.contiguous()), _p(bce.contiguous()), _p(box_rows.contiguous()),
+                                        _p(w_rows.contiguous()), _p(n_dev), _p(status), _p(b), _p(m), c_i(n), c_i(bs), c_i(H), c_i(W),
+                                        ctypes.c_double(float(boxshift_alpha)), ctypes.c_double(float(maskshift_alpha)), _stream()),
+          "stm_t2s_reduce_f32")
+    return b, m
+
+
+def t2s_reduce_backward(grad_b, grad_m, bbox_reg, reg_rows, box_rows, w_rows, n_dev, status, bs, H, W, boxshift_alpha=1.0, maskshift_alpha=1.0,
+                        need_reg=True, need_bce=True):
+    """(grad_bbox_reg [n,4], grad_bce [n]) of t2s_reduce, written (stm_t2s_reduce_backward_f32: one launch); grad_b / grad_m: one fp32 each or
+    None (zero)."""
+    n = _t2s_rows("t2s_reduce_backward", bbox_reg, reg_rows, None, box_rows, w_rows, n_dev, status)
+    _dev(grad_b, grad_m)
+    for g in (grad_b, grad_m):
+        if g is not None and (g.dtype != torch.float32 or g.numel() != 1):
+            raise StmError(f"t2s_reduce_backward: a loss gradient must be one float32, got {g.dtype} {tuple(g.shape)}")
+    g_reg = torch.empty(n, 4, dtype=torch.float32, device=bbox_reg.device) if need_reg else None
+    g_bce = torch.empty(n, dtype=torch.float32, device=bbox_reg.device) if need_bce else None
+    check(_lib.lib().stm_t2s_reduce_backward_f32(_p(grad_b.contiguous() if grad_b is not None else None),
+                                                 _p(grad_m.contiguous() if grad_m is not None else None), _p(bbox_reg.contiguous()),
+                                                 _p(reg_rows.contiguous()), _p(box_rows.contiguous()), _p(w_rows.contiguous()), _p(n_dev), _p(status),
+                                                 _p(g_reg), _p(g_bce), c_i(n), c_i(bs), c_i(H), c_i(W), ctypes.c_double(float(boxshift_alpha)),
+                                                 ctypes.c_double(float(maskshift_alpha)), _stream()), "stm_t2s_reduce_backward_f32")
+    return g_reg, g_bce
+
+
+def lincomb_rows_backward(grad_out, proto, coeff, boxes, row_proto, n_dev=None, apply_tanh=True):
+    """grad_coeff [n,M] of lincomb_sigmoid_crop in its row_proto / n_dev form: proto [S,h,w,M], row i uses proto[row_proto[i]].  Two launches,
+    fixed-order sums, no atomics (stm_lincomb_rows_backward_f32); no gradient w.r.t. the prototypes or the boxes."""
+    _dev(grad_out, proto, coeff, boxes, row_proto, n_dev)
+    go, proto, coeff = _f32c(grad_out), _f32c(proto), _f32c(coeff)
+    if proto.dim() != 4:
+        raise StmError(f"lincomb_rows_backward: proto must be [S,h,w,M], got {tuple(proto.shape)}")
+    S, h, w, m = proto.shape
+    n = coeff.shape[0]
+    if tuple(go.shape) != (n, h, w) or coeff.shape[1] != m or (boxes is not None and tuple(boxes.shape) != (n, 4)) or \
+            (row_proto is not None and (row_proto.dtype != torch.int32 or row_proto.numel() != n)) or (row_proto is None and S != 1) or \
+            (n_dev is not None and n_dev.dtype != torch.int32):
+        raise StmError(f"lincomb_rows_backward: grad_out {tuple(go.shape)}, proto {tuple(proto.shape)}, coeff {tuple(coeff.shape)}, boxes / "
+                       "row_proto / n_dev do not match")
+    gc = torch.empty_like(coeff)
+    if n == 0:
+        return gc
+    bx = _f32c(boxes) if boxes is not None else None
+    rp = row_proto.contiguous() if row_proto is not None else None
+    L = _lib.lib()
+    need = L.stm_lincomb_rows_backward_workspace_bytes(c_i(n), c_i(h), c_i(w), c_i(m))
+    ws = _workspace(need, proto.device, "lcrb")
+    check(L.stm_lincomb_rows_backward_f32(_p(go), _p(proto), c_i(S), _p(coeff), _p(bx), _p(rp), _p(n_dev), _p(gc), c_i(h), c_i(w), c_i(m), c_i(n),
+                                          c_i(1 if apply_tanh else 0), _p(ws), c_sz(ws.numel()), _stream()), "stm_lincomb_rows_backward_f32")
+    return gc
+
+
 def mask_iou(m1, m2, thr=0.5, group1=None, group2=None):
     """box_utils.py:435-447 on (m > thr).  m1 [n1,h,w], m2 [n2,h,w] soft masks -> [n1,n2].  group1 / group2 (int32, any
     order; sorted rows skip whole workgroups): only pairs of the same group are computed, the others stay 0 (stm_mask_iou_grouped_f32)."""
