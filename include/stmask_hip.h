@@ -416,7 +416,15 @@ int stm_conv2d_planar_dual_f32(const void* x_planes, const void* x2_planes, int 
  * channels of group i (0 = all), n_levels / lvl_* or B, H, W as for stm_conv2d_planar_f32, fmt, out_scale, x_np / x_plane_stride /
  * out_ld / out_np / out_plane_stride; tile_n, res_* and planes are ignored.  Every 16-channel tile of a group is written whole:
  * channels [group_cout[i], 16 * ceil(group_cout[i] / 16)) of a group receive bias-only values.  No residual input.
- * Weights: stm_conv_pack_weights_kxr_f32 of the OIHW tensor [Cout, C, kh, kw] (its own layout; wscale as stm_conv_pack_weights_fmt_f32). */
+ * Weights: stm_conv_pack_weights_kxr_f32 of the OIHW tensor [Cout, C, kh, kw] (its own layout; wscale as stm_conv_pack_weights_fmt_f32).
+ * CENTRE-WINDOW launch (g->win_w > 0, no levels): one output pixel per image -- win_h = win_w = Ho = Wo = 1, win_y0 = win_x0 = 0, and ph / pw
+ * <= 0 as in stm_conv2d_planar_f32's window launches: the output of image b reads input (-ph + ky, -pw + kx) of its H x W map, every tap
+ * inside the map, and is row b of the output tensors (B rows).  Same packed weights, same ring, same K order: the value is, bit for bit, what
+ * the "same"-padding launch over the maps writes at pixel (-ph + (kh - 1) / 2, -pw + (kw - 1) / 2) where all of that pixel's taps are inside.
+ * A tile covers stm_conv_kxr_tile_pixels / kw images (the sparse head's output layers at the centre of its 5 x 5 patch maps).
+ * stm_conv_kxr_tile_pixels: flat pixels of a workgroup tile for kw, plane format fmt and a group of channel_tiles 16-channel tiles (0: the
+ * kernel does not take the combination). */
+int stm_conv_kxr_tile_pixels(int kw, int fmt, int channel_tiles);
 size_t stm_conv_kxr_packed_bytes(const struct stm_conv_geom* g);
 int stm_conv_pack_weights_kxr_f32(const float* weight, void* packed, const struct stm_conv_geom* g, float wscale, stm_stream_t stream);
 int stm_conv2d_planar_kxr_f32(const void* x_planes, const void* packed_weight, const float* bias, float* out_f32, void* out_planes,
@@ -589,11 +597,13 @@ int stm_head_assemble_f32(const float* const* small, const float* const* trk, co
  * kept positions.  All launches are sized by a capacity and steered by a control block of 8 ints on the device, so that they can live in
  * a captured graph: ctl[0] positions found, [1] positions listed (0 after an overflow), [2] patches covered (listed, rounded up to 256,
  * at most the capacity; the extra ones are zeros), [3] / [4] pixel gates of the patch launches (= [2] * patch_pixels_a / _b), [5] pixel
- * gate of the dense launches of the other branches (n_pixels after an overflow, else 0), [6] overflow flag.
+ * gate of the dense launches of the other branches (n_pixels after an overflow, else 0), [6] overflow flag, [7] position gate of the
+ * output layers' one-pixel window launches (= [1]: one output row per listed position).
  *
  * stm_conv_set_pixel_gate: the calling thread's NEXT stm_conv2d_planar_* / stm_conv2d_planar_kxr_f32 launch reads *valid_pixels on the
  * device, and its pixel tiles that start at or past that pixel leave at once (no split-K then).  One-shot: the launch call clears it.
- * The kxr kernel takes any gate on single-level launches; on multi-level ones 0 and >= all pixels are exact.
+ * The kxr kernel takes any gate on single-level launches; on multi-level ones 0 and >= all pixels are exact.  Its centre-window
+ * launches count the gate in images and write no row at or past it.
  *
  * stm_head_candidates_f32: cls_logits[k] [pixels][ld] = class logits of kernel shape k over the concatenated levels (level l: B images of
  * lvl_h[l] x lvl_w[l] from pixel lvl_start[l]; host arrays).  A pixel is listed when one of its K priors passes the candidate pass's own

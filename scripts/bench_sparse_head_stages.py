@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The shared head's stages timed alone on the benchmark's tensors (32 clips, eager, HIP events, nothing beside them): the eager trunk with
 the dense and the sparse head, then each launch group of PlanarGraph._sparse_head and of the dense head (best of four passes).
-Wrote profiles/sparse_head_stages.txt.   usage: bench_sparse_head_stages.py > profiles/sparse_head_stages.txt"""
+Wrote profiles/sparse_head_stages.txt and, run with STM_HEAD_CENTER=0 and 1 by scripts/ab_head_center.sh, profiles/head_center_stages.txt.
+usage: [STM_HEAD_CENTER=0] bench_sparse_head_stages.py > profiles/sparse_head_stages.txt"""
 import os, sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -63,6 +64,8 @@ cw, P = 256, 64
 NP, pdt = _planes_dtype(pg.fmt)
 capn = pg.sparse_capacity(B, sizes)
 head = pg.head
+CENTER = planar.head_center_default()      # STM_HEAD_CENTER=0: the output layers over all 25 pixels of each patch map
+print("output layers at the centre pixel only:", CENTER)
 stages = []
 def ev():
     e = torch.cuda.Event(enable_timing=True); e.record(); return e
@@ -81,14 +84,21 @@ def run_once(record):
     xq = torch.empty(NP, 3 * cw // 32, capn * 25, 32, device=dev, dtype=pdt)
     t2r(x1, ("img", capn, 7, 7), out="planes", out_planes=xq, window=(0, 0, 5, 5, 0, 0, 5, 5), gate=(ctl, 4)); m("t2 patches")
     ops.head_patch_mask(xq, 5, capn, B, sizes, lst, ctl); m("mask 5")
-    ql = ("levels", capn, [(5, 5)])
-    small = [c(xq, ql, out="f32", gate=(ctl, 4), kxr=True) for c in small_l]; m("small patches x3")
-    trk = [c(xq, ql, out="f32", x_ch_off=2 * cw, gate=(ctl, 4)) for c in trk_l]; m("trk patches x3")
+    if CENTER:      # one-pixel window launches at the centre of the 5 x 5 maps, one output row per position
+        def centre(c, **kw):
+            return c(xq, ("img", capn, 5, 5), out="f32", out_f32=torch.empty(capn, c.O, device=dev), window=(0, 0, 1, 1, c.ph - 2, c.pw - 2, 1, 1),
+                     gate=(ctl, ops.HEAD_CTL_GATE_POS), **kw)
+        small = [centre(c, kxr=True) for c in small_l]; m("small patches x3")
+        trk = [centre(c, x_ch_off=2 * cw, kxr=False) for c in trk_l]; m("trk patches x3")
+    else:
+        ql = ("levels", capn, [(5, 5)])
+        small = [c(xq, ql, out="f32", gate=(ctl, 4), kxr=True) for c in small_l]; m("small patches x3")
+        trk = [c(xq, ql, out="f32", x_ch_off=2 * cw, gate=(ctl, 4)) for c in trk_l]; m("trk patches x3")
     gd = (ctl, 5)
     xx = t1r(up, lv, out="planes", gate=gd); xx = t2r(xx, lv, out="planes", gate=gd); m("dense towers (empty)")
     small_d = [c(xx, lv, out="f32", gate=gd, kxr=True) for c in small_l]
     trk_d = [c(xx, lv, out="f32", x_ch_off=2 * cw, gate=gd) for c in trk_l]; m("dense outputs (empty)")
-    out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P, 25, 12, lst, ctl, capn); m("assemble")
+    out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P, *((1, 0) if CENTER else (25, 12)), lst, ctl, capn); m("assemble")
     torch.cuda.synchronize()
     if record:
         stages.append([(marks[i][0], marks[i - 1][1].elapsed_time(marks[i][1])) for i in range(1, len(marks))])

@@ -98,13 +98,21 @@ typedef const __attribute__((address_space(1))) void* glb_ptr;
 //   consumers:  barrier k -> fragments + MFMAs of stage k
 // DMA(s) goes into the buffer of stage s - D, which every consumer left before it reached barrier s - D + 1 -- the last barrier the
 // producers passed before issuing it.
-template <int KW, int NPL, int NC>
+//
+// CTR (centre-window launch, stm_conv_geom.win_*: one output pixel per H x W image -- the sparse head's output layers on its 5 x 5 patch maps): the
+// same ring, loop and sums over other staged pixels.  A tile covers TP = BM / KW images ("positions"); image g of the tile owns the staged rows
+// KW g + kx, which hold the taps (ky, kx) of its output pixel -- input pixels (-ph + ky, -pw + kx), all inside the map -- so output row KW g reads,
+// at rows KW g + kx, exactly what the dense launch reads for that pixel, in the same K order, and its accumulators hold the same sums bit for bit.
+// The other KW - 1 output rows of a group multiply whatever is staged and are never stored; the stored row is the position, and the gate counts
+// positions.
+template <int KW, int NPL, int NC, bool CTR>
 __device__ __forceinline__ void kxr_body(const KxrArgs& a, const KxrJob& jb, int tile_first, int n_seq, int tile_step, uint8_t* smem)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int PT = kx_pt(KW, NPL, NC), D = kx_depth(KW, NPL, NC);
     constexpr int BM = 64 * PT, XROWS = BM + 16, NRG = XROWS / 16;
     constexpr int HALO = KW - 1;
+    constexpr int TP = CTR ? BM / KW : BM;      // pixels (centre mode: positions) of a tile
     constexpr int XPL = XROWS * 64;             // bytes of one plane of the staged rows
     constexpr int XBUF = NPL * XPL;
     constexpr int WT = NC * 16 * 64;            // bytes of one (kx, plane) weight tile
@@ -127,14 +135,14 @@ __device__ __forceinline__ void kxr_body(const KxrArgs& a, const KxrJob& jb, int
         int per = jb.per_xcd;
         if (a.m_gate) {
             const int gate = *a.m_gate;
-            if (gate < a.M) per = ((gate + BM - 1) / BM + 7) >> 3;
+            if (gate < a.M) per = ((gate + TP - 1) / TP + 7) >> 3;
         }
         return per;
     };
     if (a.m_gate) {
         const int gate = *a.m_gate;
         if (gate < a.M) {
-            const int gt = (gate + BM - 1) / BM;                 // tiles below the gate
+            const int gt = (gate + TP - 1) / TP;                 // tiles below the gate
             const int per = (gt + 7) >> 3;
             const int j0 = tile_first >> 3, st = tile_step >> 3;
             const int jend = min(per, gt - (tile_first & 7) * per);     // this XCD's run: tiles [x per, x per + jend)
@@ -160,7 +168,7 @@ __device__ __forceinline__ void kxr_body(const KxrArgs& a, const KxrJob& jb, int
             if (l < a.n_lvl && tile >= jb.lvl_tile0[l]) lvl = l;
         TileGeo g;
         g.H = a.lvl_h[lvl]; g.W = a.lvl_w[lvl]; g.lstart = a.lvl_start[lvl]; g.lend = a.lvl_start[lvl + 1];
-        g.m0 = g.lstart + (tile - jb.lvl_tile0[lvl]) * BM;
+        g.m0 = g.lstart + (tile - jb.lvl_tile0[lvl]) * TP;
         return g;
     };
 
@@ -186,6 +194,17 @@ __device__ __forceinline__ void kxr_body(const KxrArgs& a, const KxrJob& jb, int
                 const int piece = min(pw_ + KX_PRODUCERS * i, NXD - 1);
                 const int rg = piece % NRG;
                 const int j = rg * 16 + (lane >> 2);
+                if constexpr (CTR) {
+                    // staged row j = tap kx = j % KW of position m0 + j / KW: pixel (-ph + ky, -pw + kx) of its map (a.ph / a.pw <= 0 here; the
+                    // entry point has checked that every tap lies inside the map, so a position's row is valid for every ky)
+                    const int grp = j / KW;
+                    const int pos = tg.m0 + grp;
+                    const bool okq = grp < TP && pos < tg.lend;
+                    const int q = (okq ? pos : 0) * HW - a.pw + (j - grp * KW);
+                    dmask[i] = okq ? (1u << a.kh) - 1u : 0u;
+                    dbase[i] = (q - a.ph * tg.W) * 64 + (((lane & 3) ^ swz(j)) << 4);
+                    continue;
+                }
                 const int q = tg.m0 - a.pw + j;
                 const bool okq = j < BM + HALO && q >= tg.lstart && q < tg.lend;
                 const int local = okq ? q - tg.lstart : 0;
@@ -318,7 +337,7 @@ __device__ __forceinline__ void kxr_body(const KxrArgs& a, const KxrJob& jb, int
         const int x = okm ? (m - lstart) % W : 0;
 #pragma unroll
         for (int kx = 0; kx < KW; ++kx) {
-            const bool v = okm && (unsigned)(x + kx - a.pw) < (unsigned)W;
+            const bool v = CTR || (okm && (unsigned)(x + kx - a.pw) < (unsigned)W);      // (centre mode: a stored row's taps are its own staged rows)
             boff[t][kx] = lds_off(v ? row0 + kx : BM + HALO, kc);
         }
     }
@@ -365,13 +384,22 @@ __device__ __forceinline__ void kxr_body(const KxrArgs& a, const KxrJob& jb, int
 
     // ---- epilogue, straight from the accumulators: lane holds channels 16 c + 4 kc .. + 3 of pixel m0 + 16 PT wave + 16 t + r16
     const float ls = NPL == 2 ? 1.0f / STM_F16_LOW_SCALE : 0.0f;
+    int lim = lend;                                        // centre mode: positions at or past the gate are not written
+    if constexpr (CTR) {
+        if (a.m_gate) lim = min(lim, *a.m_gate);
+    }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const int ch = 16 * c + 4 * kc;                    // channel within the group
 #pragma unroll
         for (int t = 0; t < PT; ++t) {
-            const int m = m0 + 16 * PT * wave + 16 * t + r16;
-            if (m >= lend) continue;
+            int m = m0 + 16 * PT * wave + 16 * t + r16;
+            if constexpr (CTR) {
+                const int row = 16 * PT * wave + 16 * t + r16, grp = row / KW;
+                if (row != grp * KW || grp >= TP) continue;      // the first row of a group is the position's output pixel
+                m = m0 + grp;
+            }
+            if (m >= lim) continue;
             float v[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -404,7 +432,7 @@ __device__ __forceinline__ void kxr_body(const KxrArgs& a, const KxrJob& jb, int
 // One launch covers every group (job) of a layer, whatever its channel-tile count: the jobs are numbered widest first (their tiles take
 // longest), the body is selected per run of tiles.  (Register budget 256: six waves per workgroup put two on two of the SIMDs.  With 512
 // the compiler splits the file into VGPRs and AGPRs and moves accumulators between them at every stage.)
-template <int KW, int NPL>
+template <int KW, int NPL, bool CTR>
 __global__ __launch_bounds__(KX_THREADS) void conv_kxr_kernel(const KxrArgs a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -423,10 +451,10 @@ __global__ __launch_bounds__(KX_THREADS) void conv_kxr_kernel(const KxrArgs a)
         const int n_seq = (jend - g + grid - 1) / grid;
         const int tile = g - jb.tile0;
         switch (jb.nc) {
-            case 1: kxr_body<KW, NPL, 1>(a, jb, tile, n_seq, grid, smem); break;
-            case 2: kxr_body<KW, NPL, 2>(a, jb, tile, n_seq, grid, smem); break;
-            case 3: kxr_body<KW, NPL, 3>(a, jb, tile, n_seq, grid, smem); break;
-            default: kxr_body<KW, NPL, 4>(a, jb, tile, n_seq, grid, smem); break;
+            case 1: kxr_body<KW, NPL, 1, CTR>(a, jb, tile, n_seq, grid, smem); break;
+            case 2: kxr_body<KW, NPL, 2, CTR>(a, jb, tile, n_seq, grid, smem); break;
+            case 3: kxr_body<KW, NPL, 3, CTR>(a, jb, tile, n_seq, grid, smem); break;
+            default: kxr_body<KW, NPL, 4, CTR>(a, jb, tile, n_seq, grid, smem); break;
         }
         g += n_seq * grid;
         __syncthreads();        // the next job's ring starts on LDS this one has left
@@ -480,7 +508,9 @@ bool kxr_plan(const stm_conv_geom* g, KxrPlan* pl, const char* who)
         stm_set_error("%s: C (%d) must be a multiple of 32, Cout (%d) a multiple of groups (%d <= %d)", who, g->C, g->Cout, groups, KX_MAX_JOBS);
         return false;
     }
-    if (!(g->kw == 3 || g->kw == 5) || g->kh < 1 || g->kh > 8 || g->sh != 1 || g->sw != 1 || g->ph < 0 || g->pw < 0 || g->pw >= g->kw || g->ph >= g->kh) {
+    const bool win = g->n_levels <= 0 && g->win_w > 0;      // centre-window launch: ph / pw are the window's (<= 0), checked by the entry point
+    if (!(g->kw == 3 || g->kw == 5) || g->kh < 1 || g->kh > 8 || g->sh != 1 || g->sw != 1 || (!win && (g->ph < 0 || g->pw < 0)) || g->pw >= g->kw ||
+        g->ph >= g->kh) {
         stm_set_error("%s: stride 1, kw = 3 or 5, kh <= 8, padding smaller than the kernel", who);
         return false;
     }
@@ -504,7 +534,7 @@ bool kxr_plan(const stm_conv_geom* g, KxrPlan* pl, const char* who)
     return true;
 }
 
-template <int KW, int NPL>
+template <int KW, int NPL, bool CTR>
 int kxr_launch(KxrArgs a, stm_stream_t stream)
 {
     std::stable_sort(a.job, a.job + a.n_jobs, [](const KxrJob& x, const KxrJob& y) { return x.nc > y.nc; });    // widest first
@@ -518,20 +548,28 @@ int kxr_launch(KxrArgs a, stm_stream_t stream)
         lds = std::max(lds, (size_t)d * kx_stage_bytes(KW, NPL, nc, pt));
         j.tile0 = a.total;
         int t0 = 0;
-        for (int l = 0; l < a.n_lvl; ++l) { j.lvl_tile0[l] = t0; t0 += stm_cdiv(a.lvl_start[l + 1] - a.lvl_start[l], 64 * pt); }
+        const int tp = CTR ? 64 * pt / KW : 64 * pt;     // pixels (centre mode: positions) of a tile
+        for (int l = 0; l < a.n_lvl; ++l) { j.lvl_tile0[l] = t0; t0 += stm_cdiv(a.lvl_start[l + 1] - a.lvl_start[l], tp); }
         j.lvl_tile0[a.n_lvl] = t0;
         j.per_xcd = (t0 + 7) / 8;
         a.total += 8 * j.per_xcd;
     }
-    const int rc = stm_reserve_lds<conv_kxr_kernel<KW, NPL>>(lds, "stm_conv2d_planar_kxr_f32");
+    const int rc = stm_reserve_lds<conv_kxr_kernel<KW, NPL, CTR>>(lds, "stm_conv2d_planar_kxr_f32");
     if (rc != STM_OK) return rc;
     const int cus = stm_cu_count();      // one persistent workgroup per CU (the ring takes most of a CU's LDS)
-    hipLaunchKernelGGL((conv_kxr_kernel<KW, NPL>), dim3(std::min(a.total, std::max(cus / 8 * 8, 8))), dim3(KX_THREADS), lds, stm_hs(stream), a);
+    hipLaunchKernelGGL((conv_kxr_kernel<KW, NPL, CTR>), dim3(std::min(a.total, std::max(cus / 8 * 8, 8))), dim3(KX_THREADS), lds, stm_hs(stream), a);
     STM_CHECK_LAUNCH("conv_kxr_kernel");
     return STM_OK;
 }
 
 }  // namespace
+
+extern "C" int stm_conv_kxr_tile_pixels(int kw, int fmt, int channel_tiles)
+{
+    if (!(kw == 3 || kw == 5) || !(fmt == 1 || fmt == 2) || channel_tiles < 1 || channel_tiles > 4) return 0;
+    const int npl = fmt == 1 ? 2 : 1;
+    return kxr_ring_fits(kw, npl, channel_tiles) ? 64 * kx_pt(kw, npl, channel_tiles) : 0;
+}
 
 extern "C" size_t stm_conv_kxr_packed_bytes(const stm_conv_geom* g)
 {
@@ -566,8 +604,20 @@ extern "C" int stm_conv2d_planar_kxr_f32(const void* x_planes, const void* packe
     if (!kxr_plan(g, &pl, who)) return STM_EINVAL;
     KxrArgs a;
     memset(&a, 0, sizeof(a));
-    int64_t M;
-    if (g->n_levels > 0) {
+    int64_t M, in_pixels;
+    const bool ctr = g->n_levels <= 0 && g->win_w > 0;
+    if (ctr) {
+        // centre-window launch: ONE output pixel per H x W image, output (0, 0) of a 1 x 1 output image reading input (-ph + ky, -pw + kx)
+        STM_REQUIRE(g->B > 0 && g->H > 0 && g->W > 0, STM_EINVAL, "%s: bad image batch", who);
+        STM_REQUIRE(g->win_h == 1 && g->win_w == 1 && g->win_y0 == 0 && g->win_x0 == 0 && g->Ho == 1 && g->Wo == 1, STM_EUNSUPPORTED,
+                    "%s: window launches compute one pixel per image (win_h = win_w = Ho = Wo = 1)", who);
+        STM_REQUIRE(g->ph <= 0 && g->pw <= 0 && g->kh - g->ph <= g->H && g->kw - g->pw <= g->W, STM_EUNSUPPORTED,
+                    "%s: a tap of the %dx%d window at (%d, %d) leaves the %dx%d map", who, g->kh, g->kw, -g->ph, -g->pw, g->H, g->W);
+        a.n_lvl = 1;
+        M = g->B;                                           // positions: the pixel axis of the tiles, the gate and the outputs
+        in_pixels = (int64_t)g->B * g->H * g->W;
+        a.lvl_start[0] = 0; a.lvl_start[1] = (int)M; a.lvl_h[0] = g->H; a.lvl_w[0] = g->W;
+    } else if (g->n_levels > 0) {
         STM_REQUIRE(g->n_levels <= 8 && g->lvl_start[0] == 0, STM_EINVAL, "%s: at most 8 levels, lvl_start[0] = 0", who);
         a.n_lvl = g->n_levels;
         for (int l = 0; l < g->n_levels; ++l) {
@@ -577,20 +627,20 @@ extern "C" int stm_conv2d_planar_kxr_f32(const void* x_planes, const void* packe
             a.lvl_start[l] = g->lvl_start[l]; a.lvl_h[l] = g->lvl_h[l]; a.lvl_w[l] = g->lvl_w[l];
         }
         a.lvl_start[g->n_levels] = g->lvl_start[g->n_levels];
-        M = g->lvl_start[g->n_levels];
+        M = in_pixels = g->lvl_start[g->n_levels];
     } else {
         STM_REQUIRE(g->B > 0 && g->H > 0 && g->W > 0, STM_EINVAL, "%s: bad image batch", who);
         STM_REQUIRE(g->Ho == g->H + 2 * g->ph - g->kh + 1 && g->Wo == g->W + 2 * g->pw - g->kw + 1 && g->Ho == g->H && g->Wo == g->W, STM_EUNSUPPORTED,
                     "%s: the kernel keeps the image size (padding (k - 1) / 2)", who);
         a.n_lvl = 1;
-        M = (int64_t)g->B * g->H * g->W;
+        M = in_pixels = (int64_t)g->B * g->H * g->W;
         a.lvl_start[0] = 0; a.lvl_start[1] = (int)M; a.lvl_h[0] = g->H; a.lvl_w[0] = g->W;
     }
-    STM_REQUIRE(2 * g->ph == g->kh - 1 && 2 * g->pw == g->kw - 1, STM_EUNSUPPORTED, "%s: same padding only", who);
-    STM_REQUIRE(M < ((int64_t)1 << 30), STM_EUNSUPPORTED, "%s: too many pixels", who);
+    STM_REQUIRE(ctr || (2 * g->ph == g->kh - 1 && 2 * g->pw == g->kw - 1), STM_EUNSUPPORTED, "%s: same padding only", who);
+    STM_REQUIRE(in_pixels < ((int64_t)1 << 30), STM_EUNSUPPORTED, "%s: too many pixels", who);
     const int groups = pl.n_jobs;
-    const int64_t x_np = g->x_np ? g->x_np : M, out_np = g->out_np ? g->out_np : M;
-    STM_REQUIRE(x_np >= M && out_np >= M, STM_EINVAL, "%s: x_np / out_np smaller than the pixel count", who);
+    const int64_t x_np = g->x_np ? g->x_np : in_pixels, out_np = g->out_np ? g->out_np : M;
+    STM_REQUIRE(x_np >= in_pixels && out_np >= M, STM_EINVAL, "%s: x_np / out_np smaller than the pixel count", who);
     const int64_t x_slabs = (int64_t)groups * (g->C / 32);
     const int64_t plane_bytes = x_slabs * x_np * 64;
     STM_REQUIRE(plane_bytes < ((int64_t)1 << 31), STM_EUNSUPPORTED, "%s: plane larger than 2 GiB", who);
@@ -629,6 +679,10 @@ extern "C" int stm_conv2d_planar_kxr_f32(const void* x_planes, const void* packe
     a.range_flag = stm_internal_range_flag();
     a.m_gate = gate; a.M = (int)M;
     (void)nc_max;
-    if (g->fmt == 1) return g->kw == 3 ? kxr_launch<3, 2>(a, stream) : kxr_launch<5, 2>(a, stream);
-    return g->kw == 3 ? kxr_launch<3, 1>(a, stream) : kxr_launch<5, 1>(a, stream);
+    if (ctr) {
+        if (g->fmt == 1) return g->kw == 3 ? kxr_launch<3, 2, true>(a, stream) : kxr_launch<5, 2, true>(a, stream);
+        return g->kw == 3 ? kxr_launch<3, 1, true>(a, stream) : kxr_launch<5, 1, true>(a, stream);
+    }
+    if (g->fmt == 1) return g->kw == 3 ? kxr_launch<3, 2, false>(a, stream) : kxr_launch<5, 2, false>(a, stream);
+    return g->kw == 3 ? kxr_launch<3, 1, false>(a, stream) : kxr_launch<5, 1, false>(a, stream);
 }

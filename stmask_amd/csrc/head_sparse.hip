@@ -29,6 +29,7 @@ enum { CTL_RAW = 0,      // positions found (may exceed the capacity)
        CTL_GATE_B = 4,   // CTL_FILL * output pixels of a patch in the second tower layer (= input pixels of the output layers)
        CTL_DENSE = 5,    // pixel gate of the dense launches of the three branches: all pixels after an overflow, else 0
        CTL_OVERFLOW = 6,
+       CTL_GATE_POS = 7, // CTL_N: position gate of the output layers' one-pixel window launches (one output row per listed position)
        CTL_INTS = 8 };
 
 struct Levels {
@@ -148,6 +149,7 @@ __global__ void head_control_kernel(int* ctl, int capacity, int n_pixels, int px
     ctl[CTL_GATE_B] = fill * px_b;
     ctl[CTL_DENSE] = over ? n_pixels : 0;
     ctl[CTL_OVERFLOW] = over ? 1 : 0;
+    ctl[CTL_GATE_POS] = n;
 }
 
 struct GatherArgs {

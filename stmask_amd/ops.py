@@ -1310,6 +1310,12 @@ def conv_kxr_supported(O, C, kh, kw, stride, padding, groups, group_cout, fmt, m
     return True
 
 
+def conv_kxr_tile_pixels(kw, fmt, channel_tiles):
+    """Flat pixels of a workgroup tile of the kx-reuse kernel for kw, the plane format and a group of channel_tiles 16-channel tiles (0: not
+    taken).  A centre-window launch covers tile_pixels // kw images per tile."""
+    return int(_lib.lib().stm_conv_kxr_tile_pixels(c_i(kw), c_i(fmt), c_i(channel_tiles)))
+
+
 def conv_pack_weights_kxr(weight, geom, wscale=None):
     """OIHW fp32 weights (grouped layers: group g = rows [g * O / groups, ...)) -> the image stm_conv2d_planar_kxr_f32 streams;
     geom: a ConvGeom with C (per group), Cout, kh, kw, groups, group_cout, fmt set.  Returns (packed, 1 / wscale)."""
@@ -1821,6 +1827,7 @@ def head_assemble(small, trk, B, sizes, n_cls, mask_dim, embed_dim, group_pad):
 
 # ---- sparse head (csrc/head_sparse.hip): control block indices as the header lists them
 HEAD_CTL_RAW, HEAD_CTL_N, HEAD_CTL_FILL, HEAD_CTL_GATE_A, HEAD_CTL_GATE_B, HEAD_CTL_DENSE, HEAD_CTL_OVERFLOW, HEAD_CTL_INTS = 0, 1, 2, 3, 4, 5, 6, 8
+HEAD_CTL_GATE_POS = 7
 
 
 def conv_set_pixel_gate(ctl, index):

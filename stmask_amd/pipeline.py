@@ -17,7 +17,7 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, planar
 from .layers import Track_TF, generate_candidate
 from .layers.box_utils import center_size, sanitize_coordinates_hw
 
@@ -229,6 +229,9 @@ class BatchedClipPipeline:
         # Results are the dense head's, bit for bit, at every row that is read.  STM_SPARSE_HEAD=0 keeps the dense head (A/B runs).  The
         # setting (head form, eval_conf_thresh, capacity) is baked into a captured trunk graph: when it changes, the graphs are captured again.
         self.sparse_head = os.environ.get("STM_SPARSE_HEAD", "1") != "0"
+        # ... with its output layers at the centre pixel of each position's 5 x 5 patch map only (one-pixel window launches: the other 24 pixels
+        # are never read).  STM_HEAD_CENTER=0 runs them over the whole maps (A/B runs); part of the setting baked into the graphs
+        self.head_center = planar.head_center_default()
         # batches from which it is on: a single-stream step is a chain of launches bound by their latency, and the sparse head has 22 more of them
         # (frames/s dense / sparse at 1 clip 812-817 / 713-733, 2 clips 1 073-1 075 / 1 058-1 064, 4 clips 1 301-1 305 / 1 321-1 324, 8 clips
         # 1 435 / 1 543: DESIGN.md section 6).  STM_SPARSE_MIN_CLIPS for A/B runs
@@ -242,7 +245,7 @@ class BatchedClipPipeline:
             return None
         if not getattr(self.net.Detect_TF, "use_cross_class_nms", True):
             return None
-        return (float(self.cfg.eval_conf_thresh), self.sparse_capacity)
+        return (float(self.cfg.eval_conf_thresh), self.sparse_capacity, self.head_center)
 
     # -- stage helpers ------------------------------------------------------------------------------------------------
     def _shift_prev(self, P4, T2S, proto, dev):

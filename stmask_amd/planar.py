@@ -15,6 +15,7 @@ planar sampler + planar 1x1 convolution over all levels (stm_deform_sample_plana
 on the track / mask branches keeps the module path for the head (FPN and proto-net still run planar).
 """
 import ctypes
+import functools
 import os
 
 import torch
@@ -164,7 +165,9 @@ class PlanarConv:
         groups*C channels starting at channel x_ch_off.  out: "planes" | "f32" | "both" allocates dense outputs
         ([3, O/32, M, 32] / [M, O]) unless out_planes / out_f32 are given, then pixels [out_off, ...) are written.
         gate = (int32 device tensor, index): only the pixel tiles below that device value run (ops.conv_set_pixel_gate; never split-K).
-        kxr: True / False decides the kx-reuse kernel for a layer it supports (None: by the pixel count); splitk = False: never split K."""
+        kxr: True / False decides the kx-reuse kernel for a layer it supports (None: by the pixel count); splitk = False: never split K.
+        window = (0, 0, 1, 1, ph, pw, 1, 1), ph / pw <= 0: ONE output pixel per image -- input (-ph + ky, -pw + kx) -- as row b of the outputs; the
+        only window form the kx-reuse kernel takes (its centre-window launch; the gate then counts images)."""
         NP, dt = _planes_dtype(self.fmt)
         if xp.dtype != dt or xp.dim() != 4 or xp.shape[0] < NP or xp.shape[3] != 32 or not xp.is_contiguous():
             raise StmError(f"PlanarConv: expected contiguous {dt} planes [{NP}, S, N, 32], got {xp.dtype} {tuple(xp.shape)}")
@@ -212,7 +215,8 @@ class PlanarConv:
         # measured against the 128 x 64 tiles (scripts/bench_kxr.py, 1 / 4 / 8 / 32 clips): the head's grouped output layers win from
         # ~20 000 pixels (x1.3-1.8), single-group layers of up to 48 channels from ~30 000 (x1.1-1.4); below that its 256-pixel tiles
         # leave CUs idle, and four channel tiles (layer1's 64 -> 64) stay on the general kernel (x0.65)
-        use_kxr = (self.kxr and residual is None and window is None and (shape[0] == "levels" or (Ho, Wo) == (H, W))
+        one_px = window is not None and tuple(window[:4]) == (0, 0, 1, 1) and tuple(window[6:]) == (1, 1)
+        use_kxr = (self.kxr and residual is None and (one_px if window is not None else (shape[0] == "levels" or (Ho, Wo) == (H, W)))
                    and (kxr if kxr is not None else M >= (self.kxr_min_pixels if self.kxr_min_pixels is not None else self.kxr_rule_pixels())))
         g.tile_n = 0 if use_kxr else self.pick_tile(M)
         dev = xp.device
@@ -332,6 +336,13 @@ def _nhwc(t):
 def _split(t_nhwc, fmt=None):
     """fp32 [B, H, W, C] -> planes [P, C/32, B*H*W, 32] in the current (or given) plane format."""
     return ops.split_planes(t_nhwc, FMT if fmt is None else fmt)
+
+
+@functools.lru_cache(maxsize=None)
+def head_center_default():
+    """STM_HEAD_CENTER (default on): the sparse head's output layers at the centre pixel of each patch map only; 0 = over the whole 5 x 5 maps.
+    The one place that reads the switch, once per process."""
+    return os.environ.get("STM_HEAD_CENTER", "1") != "0"
 
 
 class PlanarGraph:
@@ -479,7 +490,9 @@ class PlanarGraph:
         """conf for every prior; loc / mask_coeff / track / centerness at the rows of the positions with a prior that passes the class threshold
         (the other rows are not written).  No host read: launches are sized by the capacity and gated by device counts."""
         head = self.head
-        thresh, cap = self.sparse
+        thresh, cap = self.sparse[:2]
+        # output layers at the centre pixel of the 5 x 5 maps only (STM_HEAD_CENTER=0: over all 25 pixels, as before); part of the setting
+        center = self.sparse[2] if len(self.sparse) > 2 else head_center_default()
         if cap is None:
             cap = self.sparse_capacity(B, sizes)
         t1c, t1r, t2c, t2r, cls_l, small_l = self._build_sparse()
@@ -507,10 +520,27 @@ class PlanarGraph:
         xq = torch.empty(NP, 3 * cw // 32, cap * S2 * S2, 32, device=dev, dtype=pdt)
         t2r(x1, ("img", cap, S1, S1), out="planes", out_planes=xq, window=(0, 0, S2, S2, 0, 0, S2, S2), gate=gb)
         ops.head_patch_mask(xq, S2, cap, B, sizes, lst, ctl)
-        # ... and the output layers over the 5 x 5 maps (all that their windows at the centre pixel read), "same" padding
-        ql = ("levels", cap, [(S2, S2)])
-        small = [c(xq, ql, out="f32", gate=gb, kxr=kx) for c in small_l]
-        trk = [c(xq, ql, out="f32", x_ch_off=2 * cw, gate=gb) for c in trk_l]
+        if center:
+            # ... and the output layers at the centre pixel of the 5 x 5 maps, the only one that is read: one-pixel window launches, one output row
+            # per position, gated by the position count.  Each layer stays on the kernel family the dense head runs it on at this batch (kx): the
+            # kx-reuse kernel's centre-window launch stages the centre pixel's taps only (kw rows per position instead of 25), the planar
+            # kernel's window launch is the padded launch's sum at that pixel.  The track layers' 128 x 64 tiles (pick_tile at `cap` pixels) keep
+            # the chain of K-slabs on a workgroup short: gated launches never split K.
+            c2, gp = S2 // 2, (ctl, ops.HEAD_CTL_GATE_POS)
+            qi = ("img", cap, S2, S2)
+
+            def centre(c, **kw):
+                return c(xq, qi, out="f32", out_f32=torch.empty(cap, c.O, device=dev), window=(0, 0, 1, 1, c.ph - c2, c.pw - c2, 1, 1), gate=gp, **kw)
+
+            small = [centre(c, kxr=kx) for c in small_l]
+            trk = [centre(c, x_ch_off=2 * cw, kxr=False) for c in trk_l]
+            rows = (1, 0)
+        else:
+            # ... and the output layers over the 5 x 5 maps (all that their windows at the centre pixel read), "same" padding
+            ql = ("levels", cap, [(S2, S2)])
+            small = [c(xq, ql, out="f32", gate=gb, kxr=kx) for c in small_l]
+            trk = [c(xq, ql, out="f32", x_ch_off=2 * cw, gate=gb) for c in trk_l]
+            rows = (S2 * S2, (S2 * S2) // 2)
         # 4. more positions than the capacity: the same layers over every pixel (empty launches otherwise)
         gd = (ctl, ops.HEAD_CTL_DENSE)
         x = t1r(up, lv, out="planes", gate=gd)
@@ -519,7 +549,7 @@ class PlanarGraph:
         trk_d = [c(x, lv, out="f32", x_ch_off=2 * cw, gate=gd) for c in trk_l]
         toc("head_finals")
         out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P,
-                                       S2 * S2, (S2 * S2) // 2, lst, ctl, cap)
+                                       rows[0], rows[1], lst, ctl, cap)
         self.sparse_ctl, self.sparse_list = ctl, lst       # (tests, diagnosis: the step's counts and positions)
         return out
 
