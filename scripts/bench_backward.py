@@ -25,8 +25,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from stmask_amd import _lib, ops  # noqa: E402
-from stmask_amd._lib import c_f, c_i, c_l, c_p, check  # noqa: E402
+from stmask_amd import ops  # noqa: E402
+from stmask_amd._lib import c_p, call  # noqa: E402
 
 R50 = [("L1.0", 128, 96, 160, 2), ("L1.2", 128, 48, 80, 1), ("L2.0", 256, 48, 80, 2), ("L2.2", 256, 24, 40, 1), ("L2.4", 256, 24, 40, 1),
        ("L3.0", 512, 24, 40, 2), ("L3.2", 512, 12, 20, 1)]
@@ -64,9 +64,8 @@ def deform_layer(name, B, C, H, W, kh, kw, stride, pad, fused, reps, out):
     cols = torch.empty(B, CK, HWo, device=dev)
     gcols = torch.randn(B, CK, HWo, device=dev)
     gx = torch.zeros_like(x)
-    L = _lib.lib()
     o_t, obs, _, mk_ptr, mbs = ops._offset_mask_views(off, mask, g, om)
-    logit = c_i(1 if fused else 0)
+    logit = 1 if fused else 0
     goff = torch.empty(B, P, g.Ho, g.Wo, device=dev)
     wT = w.view(C, CK).t().contiguous()
     gemm_flops = 2.0 * C * CK * B * HWo
@@ -84,13 +83,12 @@ def deform_layer(name, B, C, H, W, kh, kw, stride, pad, fused, reps, out):
         ops.gemm_bias(wT, go.view(B, C, HWo))
 
     def col2im():
-        check(L.stm_deform_col2im_f32(ops._p(gcols), ops._p(o_t), c_l(obs), c_p(mk_ptr), c_l(mbs), logit, ops._p(gx), ctypes.byref(g),
-                                      ops._stream()), "stm_deform_col2im_f32")
+        call("stm_deform_col2im_f32", ops._p(gcols), ops._p(o_t), obs, c_p(mk_ptr), mbs, logit, ops._p(gx), ctypes.byref(g), ops._stream())
 
     def coord():
         gm_ptr = c_p(goff.data_ptr() + 4 * 2 * K * HWo) if P == 3 * K else c_p(0)
-        check(L.stm_deform_col2im_coord_f32(ops._p(gcols), ops._p(x), ops._p(o_t), c_l(obs), c_p(mk_ptr), c_l(mbs), logit, ops._p(goff),
-                                            c_l(P * HWo), gm_ptr, c_l(P * HWo), ctypes.byref(g), ops._stream()), "stm_deform_col2im_coord_f32")
+        call("stm_deform_col2im_coord_f32", ops._p(gcols), ops._p(x), ops._p(o_t), obs, c_p(mk_ptr), mbs, logit, ops._p(goff), P * HWo, gm_ptr,
+             P * HWo, ctypes.byref(g), ops._stream())
 
     def whole():
         ops.deform_conv_backward(go, x, off, mask, w, stride, pad, 1, 1, fused_om=om)
@@ -144,11 +142,9 @@ def main():
     rois = torch.cat([torch.zeros(n, 1), xy, xy + wh], 1).cuda()
     go = torch.randn(n, C, 7, 7, device="cuda")
     gfeat = torch.zeros(1, C, H, W, device="cuda")
-    L = _lib.lib()
 
     def roi():
-        check(L.stm_roi_align_backward_f32(ops._p(go), ops._p(rois), ops._p(gfeat), c_i(1), c_i(C), c_i(H), c_i(W), c_i(n), c_i(7), c_i(7),
-                                           c_f(1.0), c_i(0), c_i(1), ops._stream()), "stm_roi_align_backward_f32")
+        call("stm_roi_align_backward_f32", ops._p(go), ops._p(rois), ops._p(gfeat), 1, C, H, W, n, 7, 7, 1.0, 0, 1, ops._stream())
     us = timed(roi, args.reps)
     out(f"  roi_align_backward         {us:9.1f} us  {4.0 * (n * C * 49 + C * H * W) / us / 1e3:8.1f} GB/s")
     out("## correlation backward: P = 11, 256 x 48 x 80, batch 1")
@@ -158,8 +154,7 @@ def main():
     g1, g2 = torch.empty_like(f1), torch.empty_like(f2)
     for label, a, b in (("grad_in1", g1, None), ("grad_in2", None, g2)):
         def corr(a=a, b=b):
-            check(L.stm_corr_backward_f32(ops._p(gc), ops._p(f1), ops._p(f2), ops._p(a), ops._p(b), c_i(1), c_i(C), c_i(H), c_i(W), c_i(P),
-                                          c_i(1), ops._stream()), "stm_corr_backward_f32")
+            call("stm_corr_backward_f32", ops._p(gc), ops._p(f1), ops._p(f2), ops._p(a), ops._p(b), 1, C, H, W, P, 1, ops._stream())
         us = timed(corr, args.reps)
         out(f"  corr_backward {label:<12} {us:9.1f} us  {4.0 * (P * P * H * W + 2 * C * H * W) / us / 1e3:8.1f} GB/s")
     if args.out:

@@ -9,36 +9,147 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STM_LIBRARY") or os.path.join(_HERE, "libstmask_hip.so")   # STM_LIBRARY: an -DSTM_ABLATE build, for timing runs
 _lib = None
+_calls = {}   # name -> (function, argument count) for call(); lib() fills it
 
 c_i, c_l, c_f, c_p, c_sz = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-# every symbol include/stmask_hip.h declares (tests/test_abi.py checks the library exports all of them)
+# include/stmask_hip.h restated: return kind and parameter kinds of every entry point, in the header's words (tests/test_abi.py parses the
+# header and compares every argument).  lib() sets restype / argtypes from this table, so a plain Python int reaches an int64_t or size_t
+# parameter at full width and a wrong type is a ctypes.ArgumentError; call() adds the argument count, which ctypes does not check.
+# p: any pointer or array, and stm_stream_t; i: int; l: int64_t; q: long long; f: float; d: double; z: size_t; returns also v: void, s: const char*
+_KINDS = {"p": c_p, "i": c_i, "l": c_l, "q": ctypes.c_longlong, "f": c_f, "d": ctypes.c_double, "z": c_sz, "v": None, "s": ctypes.c_char_p}
 ABI_VERSION = 6   # include/stmask_hip.h STM_ABI_VERSION
-ABI_SYMBOLS = [
-    "stm_version", "stm_last_error_string", "stm_struct_bytes", "stm_debug_reload_tunables", "stm_debug_launch_count", "stm_conv_kxr_tile_pixels", "stm_conv_kxr_packed_bytes", "stm_conv_pack_weights_kxr_f32", "stm_conv2d_planar_kxr_f32", "stm_conv2d_planar_dual_f32", "stm_conv2d_planar_windows_f32", "stm_conv2d_planar_windows_pool_f32", "stm_temporal_pool_fc_f32", "stm_stem_packed_weight_bytes", "stm_stem_pack_weights_f32", "stm_stem_fused_f32", "stm_chain_tail_weight_bytes", "stm_chain_tail_weight_bytes_proj", "stm_chain_pack_tail_f32", "stm_chain_pack_tail_proj_f32", "stm_bottleneck_chain_f32", "stm_bottleneck_chain_proj_f32", "stm_deform_im2col_f32", "stm_deform_conv_workspace_bytes",
-    "stm_deform_conv_fwd_f32", "stm_gemm_bias_f32", "stm_gemm_workspace_bytes", "stm_gemm_bias_ws_f32", "stm_fcb_ali_offsets_f32", "stm_corr_patch_f32", "stm_corr_patch_nhwc_f32",
-    "stm_roi_align_avg_f32", "stm_decode_boxes_f32", "stm_generate_candidates_f32", "stm_cc_fast_nms_f32",
-    "stm_detect_cc_workspace_bytes", "stm_detect_cc_f32", "stm_detect_cc_logits_f32", "stm_fast_nms_workspace_bytes", "stm_fast_nms_f32",
-    "stm_jaccard_f32", "stm_lincomb_sigmoid_crop_f32", "stm_mask_iou_workspace_bytes", "stm_mask_iou_f32",
-    "stm_bias_act_f32", "stm_mask_rle_workspace_bytes", "stm_mask_resize_rle_f32",
-    "stm_conv_packed_weight_bytes", "stm_conv_pack_weights_f32",
-    "stm_split_bf16_planes_f32", "stm_conv2d_planar_f32", "stm_conv_packed_weight_bytes_tiled",
-    "stm_conv_pack_weights_tiled_f32", "stm_preprocess_u8_f32", "stm_head_assemble_f32", "stm_conv2d_planar_ws_f32", "stm_dcn_sample_planar_f32", "stm_conv_pack_weights_fmt_f32", "stm_split_planes_fmt_f32", "stm_dcn_sample_planar_fmt_f32", "stm_planar_set_range_flag", "stm_resize_bilinear_planes_f32", "stm_bias_relu_maxpool_planes_f32", "stm_roi_align_planes_f32", "stm_roi_align_planes_nhwc_f32", "stm_deform_sample_planar_f32", "stm_stem_rows_planes_f32", "stm_mask_iou_grouped_f32", "stm_cc_fast_nms_workspace_bytes", "stm_cc_fast_nms_ws_f32",
-    "stm_gather_detections_f32", "stm_shift_rois_f32", "stm_shift_apply_f32", "stm_match_scores_f32", "stm_match_scores_embed_f32", "stm_gather_rows2", "stm_pack_tracked_f32", "stm_pack_tracked_bits_f32",
-    "stm_lincomb_sigmoid_crop_bits_f32", "stm_mask_iou_bits_f32", "stm_split_planes_f16", "stm_conv_pack_weights_f16", "stm_conv2d_planar_f16", "stm_dcn_sample_planar_f16",
-    "stm_deform_conv_fused_planar_supported", "stm_deform_conv_fused_planar_f32", "stm_fast_nms_batched_workspace_bytes", "stm_fast_nms_batched_f32", "stm_rle_strings_host",
-    "stm_preprocess_u8_multi_f32", "stm_render_workspace_bytes", "stm_render_overlay_u8",
-    "stm_deform_col2im_f32", "stm_deform_col2im_coord_f32", "stm_roi_align_backward_f32", "stm_corr_backward_f32",
-    "stm_conv_set_pixel_gate", "stm_head_candidates_f32", "stm_head_patch_gather", "stm_head_patch_mask", "stm_head_assemble_sparse_f32",
-    "stm_lincomb_backward_workspace_bytes", "stm_lincomb_backward_f32", "stm_decode_boxes_backward_f32", "stm_jaccard_backward_f32",
-    "stm_match_workspace_bytes", "stm_match_priors_f32", "stm_encode_boxes_f32",
-    "stm_ohem_conf_workspace_bytes", "stm_ohem_select_neg_f32", "stm_ohem_conf_loss_f32", "stm_ohem_conf_loss_backward_f32",
-    "stm_box_center_workspace_bytes", "stm_box_center_loss_f32", "stm_box_center_loss_backward_f32",
-    "stm_track_loss_workspace_bytes", "stm_track_loss_f32", "stm_track_loss_backward_f32",
-    "stm_t2s_workspace_bytes", "stm_t2s_targets_f32", "stm_t2s_gather_f32", "stm_t2s_reduce_f32", "stm_t2s_reduce_backward_f32",
-    "stm_lincomb_rows_backward_workspace_bytes", "stm_lincomb_rows_backward_f32",
-    "stm_mask_bce_workspace_bytes", "stm_mask_bce_upsampled_f32", "stm_mask_bce_upsampled_backward_f32",
-]
+SIGNATURES = {
+    "stm_version": ("i", ""),
+    "stm_last_error_string": ("s", ""),
+    "stm_struct_bytes": ("z", "i"),
+    "stm_debug_reload_tunables": ("v", ""),
+    "stm_debug_launch_count": ("q", "i"),
+    "stm_conv_kxr_tile_pixels": ("i", "iii"),
+    "stm_conv_kxr_packed_bytes": ("z", "p"),
+    "stm_conv_pack_weights_kxr_f32": ("i", "pppfp"),
+    "stm_conv2d_planar_kxr_f32": ("i", "ppppppip"),
+    "stm_conv2d_planar_dual_f32": ("i", "ppiiiiqqpppppppipzp"),
+    "stm_conv2d_planar_windows_f32": ("i", "pppippppip"),
+    "stm_conv2d_planar_windows_pool_f32": ("i", "pppipppp"),
+    "stm_temporal_pool_fc_f32": ("i", "piiippiipppip"),
+    "stm_stem_packed_weight_bytes": ("z", "ii"),
+    "stm_stem_pack_weights_f32": ("i", "ppiifp"),
+    "stm_stem_fused_f32": ("i", "ppppiiiiiifp"),
+    "stm_chain_tail_weight_bytes": ("z", ""),
+    "stm_chain_tail_weight_bytes_proj": ("z", ""),
+    "stm_chain_pack_tail_f32": ("i", "pppffp"),
+    "stm_chain_pack_tail_proj_f32": ("i", "ppppffp"),
+    "stm_bottleneck_chain_f32": ("i", "pppppppppfffiiip"),
+    "stm_bottleneck_chain_proj_f32": ("i", "pppppppppfffiiip"),
+    "stm_deform_im2col_f32": ("i", "pplplippip"),
+    "stm_deform_conv_workspace_bytes": ("z", "p"),
+    "stm_deform_conv_fwd_f32": ("i", "pplplipppiippzp"),
+    "stm_gemm_bias_f32": ("i", "ppppiiiillip"),
+    "stm_gemm_workspace_bytes": ("z", "iii"),
+    "stm_gemm_bias_ws_f32": ("i", "ppppiiiillipzp"),
+    "stm_fcb_ali_offsets_f32": ("i", "ppiiiiip"),
+    "stm_corr_patch_f32": ("i", "pppiiiiiiffp"),
+    "stm_corr_patch_nhwc_f32": ("i", "pppiiiiiiffiip"),
+    "stm_roi_align_avg_f32": ("i", "pppiiiiiiifiip"),
+    "stm_decode_boxes_f32": ("i", "ppplp"),
+    "stm_generate_candidates_f32": ("i", "pppiifipppp"),
+    "stm_cc_fast_nms_f32": ("i", "pppiipfiipppppp"),
+    "stm_detect_cc_workspace_bytes": ("z", "ii"),
+    "stm_detect_cc_f32": ("i", "ppppiiffiippppppzp"),
+    "stm_detect_cc_logits_f32": ("i", "ppppiiffiippppppzp"),
+    "stm_fast_nms_workspace_bytes": ("z", "iii"),
+    "stm_fast_nms_f32": ("i", "pppiipfifippppppzp"),
+    "stm_jaccard_f32": ("i", "pipipp"),
+    "stm_lincomb_sigmoid_crop_f32": ("i", "ppppiiiiippp"),
+    "stm_mask_iou_workspace_bytes": ("z", "iii"),
+    "stm_mask_iou_f32": ("i", "pipiifppzp"),
+    "stm_bias_act_f32": ("i", "ppplilip"),
+    "stm_mask_rle_workspace_bytes": ("z", "iiii"),
+    "stm_mask_resize_rle_f32": ("i", "piiiiiiifpippzp"),
+    "stm_conv_packed_weight_bytes": ("z", "iiiii"),
+    "stm_conv_pack_weights_f32": ("i", "ppiiiiip"),
+    "stm_split_bf16_planes_f32": ("i", "pplip"),
+    "stm_conv2d_planar_f32": ("i", "ppppppppip"),
+    "stm_conv_packed_weight_bytes_tiled": ("z", "iiiiii"),
+    "stm_conv_pack_weights_tiled_f32": ("i", "ppiiiiiip"),
+    "stm_preprocess_u8_f32": ("i", "ppiiiiiiippip"),
+    "stm_head_assemble_f32": ("i", "ppppppppp"),
+    "stm_conv2d_planar_ws_f32": ("i", "ppppppppipzp"),
+    "stm_dcn_sample_planar_f32": ("i", "ppipiqpp"),
+    "stm_conv_pack_weights_fmt_f32": ("i", "ppiiiiiifp"),
+    "stm_split_planes_fmt_f32": ("i", "ppliip"),
+    "stm_dcn_sample_planar_fmt_f32": ("i", "ppipiqpip"),
+    "stm_planar_set_range_flag": ("i", "p"),
+    "stm_resize_bilinear_planes_f32": ("i", "ppiiiiiiip"),
+    "stm_bias_relu_maxpool_planes_f32": ("i", "pppiiiiip"),
+    "stm_roi_align_planes_f32": ("i", "pppppiiiiiiiiip"),
+    "stm_roi_align_planes_nhwc_f32": ("i", "pppippiiiiiiiiip"),
+    "stm_deform_sample_planar_f32": ("i", "pipiipiiqpip"),
+    "stm_stem_rows_planes_f32": ("i", "ppiiiiiiiip"),
+    "stm_mask_iou_grouped_f32": ("i", "pipiifppppzp"),
+    "stm_cc_fast_nms_workspace_bytes": ("z", "ii"),
+    "stm_cc_fast_nms_ws_f32": ("i", "pppiifiippppppzp"),
+    "stm_gather_detections_f32": ("i", "ppppppppiiiiiipppppppp"),
+    "stm_shift_rois_f32": ("i", "pppiiip"),
+    "stm_shift_apply_f32": ("i", "pppppiifp"),
+    "stm_match_scores_f32": ("i", "pppppppppiipfpp"),
+    "stm_match_scores_embed_f32": ("i", "ppippppppppiipfpp"),
+    "stm_gather_rows2": ("i", "ppppipiip"),
+    "stm_pack_tracked_f32": ("i", "pppppppiiiiiiifppp"),
+    "stm_pack_tracked_bits_f32": ("i", "pippppppiiiiiifppp"),
+    "stm_lincomb_sigmoid_crop_bits_f32": ("i", "ppppiiiiipppfp"),
+    "stm_mask_iou_bits_f32": ("i", "pipiipppp"),
+    "stm_split_planes_f16": ("i", "pplip"),
+    "stm_conv_pack_weights_f16": ("i", "ppiiiiifp"),
+    "stm_conv2d_planar_f16": ("i", "ppppppppipzp"),
+    "stm_dcn_sample_planar_f16": ("i", "ppipiqpp"),
+    "stm_deform_conv_fused_planar_supported": ("i", "piii"),
+    "stm_deform_conv_fused_planar_f32": ("i", "pipiipppiiqiifpiip"),
+    "stm_fast_nms_batched_workspace_bytes": ("z", "iiii"),
+    "stm_fast_nms_batched_f32": ("i", "plpppliipfifiippppppzp"),
+    "stm_rle_strings_host": ("i", "pipipip"),
+    "stm_preprocess_u8_multi_f32": ("i", "pipiiiippip"),
+    "stm_render_workspace_bytes": ("z", "i"),
+    "stm_render_overlay_u8": ("i", "pipiiippfpzp"),
+    "stm_deform_col2im_f32": ("i", "pplplippp"),
+    "stm_deform_col2im_coord_f32": ("i", "ppplpliplplpp"),
+    "stm_roi_align_backward_f32": ("i", "pppiiiiiiifiip"),
+    "stm_corr_backward_f32": ("i", "pppppiiiiiip"),
+    "stm_conv_set_pixel_gate": ("v", "p"),
+    "stm_head_candidates_f32": ("i", "piiifiiiiippppppp"),
+    "stm_head_patch_gather": ("i", "pqpiiiiiipppppp"),
+    "stm_head_patch_mask": ("i", "piiiiiipppppp"),
+    "stm_head_assemble_sparse_f32": ("i", "pipppppiippipppppp"),
+    "stm_lincomb_backward_workspace_bytes": ("z", "iiii"),
+    "stm_lincomb_backward_f32": ("i", "ppppppiiiiipzp"),
+    "stm_decode_boxes_backward_f32": ("i", "ppppplp"),
+    "stm_jaccard_backward_f32": ("i", "ppipippp"),
+    "stm_match_workspace_bytes": ("z", "iiii"),
+    "stm_match_priors_f32": ("i", "ppppiiipiipiddpppppppzp"),
+    "stm_encode_boxes_f32": ("i", "ppplp"),
+    "stm_ohem_conf_workspace_bytes": ("z", "iii"),
+    "stm_ohem_select_neg_f32": ("i", "pppiiiipzp"),
+    "stm_ohem_conf_loss_f32": ("i", "pppppiiiidipzp"),
+    "stm_ohem_conf_loss_backward_f32": ("i", "ppppppiiiidp"),
+    "stm_box_center_workspace_bytes": ("z", "ii"),
+    "stm_box_center_loss_f32": ("i", "ppippppppiiddpzp"),
+    "stm_box_center_loss_backward_f32": ("i", "ppppippppppiiddp"),
+    "stm_track_loss_workspace_bytes": ("z", "iii"),
+    "stm_track_loss_f32": ("i", "ppppiiidpzp"),
+    "stm_track_loss_backward_f32": ("i", "pppppiiidpzp"),
+    "stm_t2s_workspace_bytes": ("z", "ii"),
+    "stm_t2s_targets_f32": ("i", "ppppiipppiippppiiipzp"),
+    "stm_t2s_gather_f32": ("i", "ppppppipppppppppiiiiiipzp"),
+    "stm_t2s_reduce_f32": ("i", "pppppppppiiiiddp"),
+    "stm_t2s_reduce_backward_f32": ("i", "ppppppppppiiiiddp"),
+    "stm_lincomb_rows_backward_workspace_bytes": ("z", "iiii"),
+    "stm_lincomb_rows_backward_f32": ("i", "ppipppppiiiiipzp"),
+    "stm_mask_bce_workspace_bytes": ("z", "iii"),
+    "stm_mask_bce_upsampled_f32": ("i", "ppippiiiiiipzp"),
+    "stm_mask_bce_upsampled_backward_f32": ("i", "pppippiiiiiip"),
+}
+ABI_SYMBOLS = list(SIGNATURES)
 
 
 class StmError(RuntimeError):
@@ -94,30 +205,21 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback on the product path.")
         _lib = ctypes.CDLL(LIB_PATH)
-        _lib.stm_last_error_string.restype = ctypes.c_char_p
-        _lib.stm_version.restype = c_i
-        for name in ("stm_deform_conv_workspace_bytes", "stm_gemm_workspace_bytes", "stm_mask_rle_workspace_bytes", "stm_detect_cc_workspace_bytes", "stm_fast_nms_workspace_bytes",
-                     "stm_mask_iou_workspace_bytes", "stm_conv_packed_weight_bytes", "stm_conv_packed_weight_bytes_tiled", "stm_cc_fast_nms_workspace_bytes", "stm_conv_kxr_packed_bytes", "stm_stem_packed_weight_bytes", "stm_chain_tail_weight_bytes", "stm_chain_tail_weight_bytes_proj", "stm_fast_nms_batched_workspace_bytes", "stm_render_workspace_bytes",
-                     "stm_lincomb_backward_workspace_bytes", "stm_match_workspace_bytes", "stm_mask_bce_workspace_bytes", "stm_ohem_conf_workspace_bytes",
-                     "stm_box_center_workspace_bytes", "stm_track_loss_workspace_bytes", "stm_t2s_workspace_bytes",
-                     "stm_lincomb_rows_backward_workspace_bytes"):
-            getattr(_lib, name).restype = c_sz
-        _lib.stm_struct_bytes.restype = c_sz
-        _lib.stm_debug_reload_tunables.restype = None
-        _lib.stm_debug_launch_count.restype = ctypes.c_longlong
+        missing = [n for n in SIGNATURES if not hasattr(_lib, n)]
+        if missing:
+            _lib = None
+            raise StmError(f"{LIB_PATH} lacks {', '.join(missing)}: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")
+        for name, (ret, params) in SIGNATURES.items():
+            fn = getattr(_lib, name)
+            fn.restype, fn.argtypes = _KINDS[ret], [_KINDS[k] for k in params]
+            _calls[name] = (fn, len(params))
         # this binding and the library must describe the same structs (a stale .so would read garbage past a shorter struct)
-        if _lib.stm_version() != ABI_VERSION or _lib.stm_struct_bytes(0) != ctypes.sizeof(DeformGeom) or \
-                _lib.stm_struct_bytes(1) != ctypes.sizeof(ConvGeom) or _lib.stm_struct_bytes(2) != ctypes.sizeof(ConvWindow) or \
-                _lib.stm_struct_bytes(3) != ctypes.sizeof(HeadLayout) or _lib.stm_struct_bytes(4) != ctypes.sizeof(FrameDesc) or \
-                _lib.stm_struct_bytes(5) != ctypes.sizeof(RenderFrame):
+        structs = [DeformGeom, ConvGeom, ConvWindow, HeadLayout, FrameDesc, RenderFrame]
+        if _lib.stm_version() != ABI_VERSION or any(_lib.stm_struct_bytes(i) != ctypes.sizeof(s) for i, s in enumerate(structs)):
             v = _lib.stm_version()
             _lib = None
             raise StmError(f"{LIB_PATH} has ABI version {v}, this binding was written for {ABI_VERSION} (or a struct size "
                            "differs): rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")
-        missing = [n for n in ABI_SYMBOLS if not hasattr(_lib, n)]
-        if missing:
-            _lib = None
-            raise StmError(f"{LIB_PATH} lacks {', '.join(missing)}: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")
     return _lib
 
 
@@ -125,3 +227,15 @@ def check(rc, what):
     if rc != 0:
         msg = lib().stm_last_error_string().decode(errors="replace")
         raise StmError(f"{what} failed with code {rc}: {msg}")
+
+
+def call(name, *args):
+    """Call the status-returning entry point `name`; a wrong argument count or a non-zero code raises StmError."""
+    if _lib is None:
+        lib()
+    fn, n = _calls[name]
+    if len(args) != n:
+        raise StmError(f"{name} takes {n} arguments, got {len(args)}")
+    rc = fn(*args)
+    if rc != 0:
+        check(rc, name)

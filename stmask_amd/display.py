@@ -140,14 +140,13 @@ def render_batch(dets, bases, metas, mode="source", palette=None, alpha=0.45, bo
     else:
         mask_t = color_t = box_t = None
     mh, mw = mask_hw if mask_hw else (0, 0)
-    L = _lib.lib()
-    ws = torch.empty(int(L.stm_render_workspace_bytes(n_rows)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_lib.lib().stm_render_workspace_bytes(n_rows), dtype=torch.uint8, device=dev)
     arr = (_lib.RenderFrame * len(frames))(*frames)
     stream = torch.cuda.current_stream(dev).cuda_stream
 
     def ptr(t):
         return None if t is None else ctypes.c_void_p(t.data_ptr())
 
-    _lib.check(L.stm_render_overlay_u8(arr, len(frames), ptr(mask_t), n_rows, mh, mw, ptr(color_t), ptr(box_t), ctypes.c_float(alpha),
-                                       ptr(ws), ctypes.c_size_t(ws.numel()), ctypes.c_void_p(stream)), "stm_render_overlay_u8")
+    _lib.call("stm_render_overlay_u8", arr, len(frames), ptr(mask_t), n_rows, mh, mw, ptr(color_t), ptr(box_t), alpha, ptr(ws), ws.numel(),
+              ctypes.c_void_p(stream))
     return results

@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import DeformGeom, StmError, c_f, c_i, c_l, c_p, c_sz, check
+from ._lib import DeformGeom, StmError, c_p, call
 
 
 def _pair(v):
@@ -85,10 +85,8 @@ def deform_im2col(x, offset, mask, kernel_size, stride=1, padding=0, dilation=1,
     g = _geom(x, kernel_size, stride, padding, dilation, deform_groups)
     off, obs, mk, mk_ptr, mbs = _offset_mask_views(offset, mask, g, fused_om)
     cols = out if out is not None else torch.empty(g.B, g.C * g.kh * g.kw, g.Ho * g.Wo, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().stm_deform_im2col_f32(_p(x), _p(off), c_l(obs), c_p(mk_ptr), c_l(mbs),
-                                          c_i(1 if (mask_is_logit or fused_om is not None) else 0), _p(cols),
-                                          ctypes.byref(g), c_i(variant), _stream())
-    check(rc, "stm_deform_im2col_f32")
+    call("stm_deform_im2col_f32", _p(x), _p(off), obs, c_p(mk_ptr), mbs, 1 if (mask_is_logit or fused_om is not None) else 0, _p(cols),
+         ctypes.byref(g), variant, _stream())
     return cols
 
 
@@ -215,25 +213,20 @@ def deform_conv(x, offset, mask, weight, bias=None, stride=1, padding=0, dilatio
     need = _lib.lib().stm_deform_conv_workspace_bytes(ctypes.byref(g))
     ws = _workspace(need, x.device, "cols")
     if _im2col_timing is not None:  # same two kernels, launched separately so the im2col can be bracketed by events
-        logit = c_i(1 if (mask_is_logit or fused_om is not None) else 0)
+        logit = 1 if (mask_is_logit or fused_om is not None) else 0
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        check(_lib.lib().stm_deform_im2col_f32(_p(x), _p(off), c_l(obs), c_p(mk_ptr), c_l(mbs), logit, _p(ws),
-                                               ctypes.byref(g), c_i(0), _stream()), "stm_deform_im2col_f32")
+        call("stm_deform_im2col_f32", _p(x), _p(off), obs, c_p(mk_ptr), mbs, logit, _p(ws), ctypes.byref(g), 0, _stream())
         e1.record()
         _im2col_timing.append((e0, e1, im2col_algorithmic_bytes(g, mk_ptr != 0)))
         CK, HWo = g.C * g.kh * g.kw, g.Ho * g.Wo
         cols_bytes = (g.B * CK * HWo * 4 + 255) // 256 * 256   # same split of the workspace as stm_deform_conv_fwd_f32
         part = ws[cols_bytes:]
-        check(_lib.lib().stm_gemm_bias_ws_f32(_p(weight), _p(ws), _p(bias), _p(y), c_i(O), c_i(HWo), c_i(CK), c_i(g.B),
-                                              c_l(CK * HWo), c_l(O * HWo), c_i(1 if relu else 0), _p(part),
-                                              c_sz(part.numel()), _stream()), "stm_gemm_bias_ws_f32")
+        call("stm_gemm_bias_ws_f32", _p(weight), _p(ws), _p(bias), _p(y), O, HWo, CK, g.B, CK * HWo, O * HWo, 1 if relu else 0, _p(part),
+             part.numel(), _stream())
         return y
-    rc = _lib.lib().stm_deform_conv_fwd_f32(_p(x), _p(off), c_l(obs), c_p(mk_ptr), c_l(mbs),
-                                            c_i(1 if (mask_is_logit or fused_om is not None) else 0), _p(weight),
-                                            _p(bias), _p(y), c_i(O), c_i(1 if relu else 0), ctypes.byref(g), _p(ws),
-                                            c_sz(ws.numel()), _stream())
-    check(rc, "stm_deform_conv_fwd_f32")
+    call("stm_deform_conv_fwd_f32", _p(x), _p(off), obs, c_p(mk_ptr), mbs, 1 if (mask_is_logit or fused_om is not None) else 0, _p(weight),
+         _p(bias), _p(y), O, 1 if relu else 0, ctypes.byref(g), _p(ws), ws.numel(), _stream())
     return y
 
 
@@ -248,11 +241,9 @@ def gemm_bias(A, Bm, bias=None, relu=False):
     M = A.shape[0]
     assert A.shape[1] == K
     C = torch.empty(batch, M, N, device=A.device, dtype=torch.float32)
-    ws = _workspace(_lib.lib().stm_gemm_workspace_bytes(c_i(M), c_i(N), c_i(batch)), A.device, "gemm")
-    rc = _lib.lib().stm_gemm_bias_ws_f32(_p(A), _p(Bm), _p(_f32c(bias) if bias is not None else None), _p(C), c_i(M),
-                                         c_i(N), c_i(K), c_i(batch), c_l(K * N), c_l(M * N), c_i(1 if relu else 0),
-                                         _p(ws), c_sz(ws.numel()), _stream())
-    check(rc, "stm_gemm_bias_ws_f32")
+    ws = _workspace(_lib.lib().stm_gemm_workspace_bytes(M, N, batch), A.device, "gemm")
+    call("stm_gemm_bias_ws_f32", _p(A), _p(Bm), _p(_f32c(bias) if bias is not None else None), _p(C), M, N, K, batch, K * N, M * N,
+         1 if relu else 0, _p(ws), ws.numel(), _stream())
     return C[0] if squeeze else C
 
 
@@ -272,9 +263,8 @@ def deform_sample_planar(x_pix, B, H, W, C, offsets, kernel_size, padding, out, 
     if out.dim() != 4 or out.shape[1] * 32 != kh * kw * C or not out.is_contiguous():
         raise StmError(f"deform_sample_planar: planes {tuple(out.shape)} do not hold {kh * kw * C} column channels")
     g = DeformGeom(B, C, H, W, kh, kw, 1, 1, ph, pw, 1, 1, 1, H, W)
-    check(_lib.lib().stm_deform_sample_planar_f32(_p(x_pix), c_i(x_pix.stride(0)), _p(offsets), c_i(offsets.shape[1]), c_i(0), _p(out),
-                                                  c_i(out.shape[2]), c_i(out_off), c_l(0), ctypes.byref(g), c_i(fmt), _stream()),
-          "stm_deform_sample_planar_f32")
+    call("stm_deform_sample_planar_f32", _p(x_pix), x_pix.stride(0), _p(offsets), offsets.shape[1], 0, _p(out), out.shape[2], out_off, 0,
+         ctypes.byref(g), fmt, _stream())
     return out
 
 
@@ -285,8 +275,7 @@ def fcb_ali_offsets(loc, kh, kw):
     B, four, H, W = loc.shape
     assert four == 4
     off = torch.empty(B, 2 * kh * kw, H, W, device=loc.device, dtype=torch.float32)
-    check(_lib.lib().stm_fcb_ali_offsets_f32(_p(loc), _p(off), c_i(B), c_i(H), c_i(W), c_i(kh), c_i(kw), _stream()),
-          "stm_fcb_ali_offsets_f32")
+    call("stm_fcb_ali_offsets_f32", _p(loc), _p(off), B, H, W, kh, kw, _stream())
     return off
 
 
@@ -298,8 +287,7 @@ def corr_patch(f1, f2, patch_size=11, dilation_patch=1, scale=1.0, leaky_slope=1
         raise StmError(f"correlation inputs differ in shape: {tuple(f1.shape)} vs {tuple(f2.shape)}")
     B, C, H, W = f1.shape
     out = torch.empty(B, patch_size, patch_size, H, W, device=f1.device, dtype=torch.float32)
-    check(_lib.lib().stm_corr_patch_f32(_p(f1), _p(f2), _p(out), c_i(B), c_i(C), c_i(H), c_i(W), c_i(patch_size),
-                                        c_i(dilation_patch), c_f(scale), c_f(leaky_slope), _stream()), "stm_corr_patch_f32")
+    call("stm_corr_patch_f32", _p(f1), _p(f2), _p(out), B, C, H, W, patch_size, dilation_patch, scale, leaky_slope, _stream())
     return out
 
 
@@ -317,8 +305,7 @@ def corr_patch_nhwc(f1, f2, patch_size=11, scale=1.0, leaky_slope=1.0, ld=None):
         f1, f2 = _f32c(f1), _f32c(f2)
     ld = ld or -(-patch_size * patch_size // 8) * 8
     out = torch.empty(B, H, W, ld, device=f1.device, dtype=torch.float32)
-    check(_lib.lib().stm_corr_patch_nhwc_f32(_p(f1), _p(f2), _p(out), c_i(B), c_i(C), c_i(H), c_i(W), c_i(patch_size), c_i(1), c_f(scale),
-                                             c_f(leaky_slope), c_i(ld), c_i(1 if cl else 0), _stream()), "stm_corr_patch_nhwc_f32")
+    call("stm_corr_patch_nhwc_f32", _p(f1), _p(f2), _p(out), B, C, H, W, patch_size, 1, scale, leaky_slope, ld, 1 if cl else 0, _stream())
     return out
 
 
@@ -331,9 +318,7 @@ def roi_align(feat, rois, output_size, spatial_scale=1.0, sampling_ratio=0, alig
     if n and rois.shape[1] != 5:
         raise StmError("rois must be [n,5] = (batch, x1, y1, x2, y2)")
     out = torch.empty(n, C, ph, pw, device=feat.device, dtype=torch.float32)
-    check(_lib.lib().stm_roi_align_avg_f32(_p(feat), _p(rois), _p(out), c_i(B), c_i(C), c_i(H), c_i(W), c_i(n), c_i(ph),
-                                           c_i(pw), c_f(spatial_scale), c_i(sampling_ratio), c_i(1 if aligned else 0),
-                                           _stream()), "stm_roi_align_avg_f32")
+    call("stm_roi_align_avg_f32", _p(feat), _p(rois), _p(out), B, C, H, W, n, ph, pw, spatial_scale, sampling_ratio, 1 if aligned else 0, _stream())
     return out
 
 
@@ -343,8 +328,7 @@ def deform_col2im(grad_cols, offset, mask, g, fused_om=None):
     grad_cols = _f32c(grad_cols)
     off, obs, _, mk_ptr, mbs = _offset_mask_views(offset, mask, g, fused_om)
     gx = torch.zeros(g.B, g.C, g.H, g.W, device=grad_cols.device, dtype=torch.float32)
-    check(_lib.lib().stm_deform_col2im_f32(_p(grad_cols), _p(off), c_l(obs), c_p(mk_ptr), c_l(mbs), c_i(1 if fused_om is not None else 0),
-                                           _p(gx), ctypes.byref(g), _stream()), "stm_deform_col2im_f32")
+    call("stm_deform_col2im_f32", _p(grad_cols), _p(off), obs, c_p(mk_ptr), mbs, 1 if fused_om is not None else 0, _p(gx), ctypes.byref(g), _stream())
     return gx
 
 
@@ -355,21 +339,18 @@ def deform_col2im_coord(grad_cols, x, offset, mask, g, fused_om=None, want_offse
     grad_cols, x = _f32c(grad_cols), _f32c(x)
     off, obs, _, mk_ptr, mbs = _offset_mask_views(offset, mask, g, fused_om)
     K, HWo = g.kh * g.kw, g.Ho * g.Wo
-    L = _lib.lib()
     if fused_om is not None:
         gom = torch.zeros_like(off) if not (want_offset and want_mask) else torch.empty_like(off)
         bs = g.dg * 3 * K * HWo
-        check(L.stm_deform_col2im_coord_f32(_p(grad_cols), _p(x), _p(off), c_l(obs), c_p(mk_ptr), c_l(mbs), c_i(1),
-                                            _p(gom) if want_offset else c_p(0), c_l(bs),
-                                            c_p(gom.data_ptr() + 4 * g.dg * 2 * K * HWo) if want_mask else c_p(0), c_l(bs),
-                                            ctypes.byref(g), _stream()), "stm_deform_col2im_coord_f32")
+        call("stm_deform_col2im_coord_f32", _p(grad_cols), _p(x), _p(off), obs, c_p(mk_ptr), mbs, 1, _p(gom) if want_offset else c_p(0), bs,
+             c_p(gom.data_ptr() + 4 * g.dg * 2 * K * HWo) if want_mask else c_p(0), bs, ctypes.byref(g), _stream())
         return gom
     goff = torch.empty(g.B, g.dg * 2 * K, g.Ho, g.Wo, device=x.device, dtype=torch.float32) if want_offset else None
     gmask = torch.empty(g.B, g.dg * K, g.Ho, g.Wo, device=x.device, dtype=torch.float32) if (want_mask and mk_ptr) else None
     if goff is None and gmask is None:
         return None, None
-    check(L.stm_deform_col2im_coord_f32(_p(grad_cols), _p(x), _p(off), c_l(obs), c_p(mk_ptr), c_l(mbs), c_i(0), _p(goff), c_l(g.dg * 2 * K * HWo),
-                                        _p(gmask), c_l(g.dg * K * HWo), ctypes.byref(g), _stream()), "stm_deform_col2im_coord_f32")
+    call("stm_deform_col2im_coord_f32", _p(grad_cols), _p(x), _p(off), obs, c_p(mk_ptr), mbs, 0, _p(goff), g.dg * 2 * K * HWo, _p(gmask),
+         g.dg * K * HWo, ctypes.byref(g), _stream())
     return goff, gmask
 
 
@@ -420,9 +401,8 @@ def roi_align_backward(grad_out, rois, feat_shape, output_size, spatial_scale=1.
     if tuple(go.shape) != (n, C, ph, pw):
         raise StmError(f"roi_align_backward: grad_out {tuple(go.shape)} != {(n, C, ph, pw)}")
     gfeat = torch.zeros(B, C, H, W, device=go.device, dtype=torch.float32)
-    check(_lib.lib().stm_roi_align_backward_f32(_p(go), _p(rois), _p(gfeat), c_i(B), c_i(C), c_i(H), c_i(W), c_i(n), c_i(ph), c_i(pw),
-                                                c_f(spatial_scale), c_i(sampling_ratio), c_i(1 if aligned else 0), _stream()),
-          "stm_roi_align_backward_f32")
+    call("stm_roi_align_backward_f32", _p(go), _p(rois), _p(gfeat), B, C, H, W, n, ph, pw, spatial_scale, sampling_ratio, 1 if aligned else 0,
+         _stream())
     return gfeat
 
 
@@ -438,8 +418,7 @@ def corr_patch_backward(grad_out, f1, f2, dilation_patch=1, need1=True, need2=Tr
     g2 = torch.empty_like(f2) if need2 else None
     if g1 is None and g2 is None:
         return None, None
-    check(_lib.lib().stm_corr_backward_f32(_p(go), _p(f1), _p(f2), _p(g1), _p(g2), c_i(B), c_i(C), c_i(H), c_i(W), c_i(P),
-                                           c_i(dilation_patch), _stream()), "stm_corr_backward_f32")
+    call("stm_corr_backward_f32", _p(go), _p(f1), _p(f2), _p(g1), _p(g2), B, C, H, W, P, dilation_patch, _stream())
     return g1, g2
 
 
@@ -448,8 +427,7 @@ def decode(loc, priors):
     _dev(loc, priors)
     loc, priors = _f32c(loc), _f32c(priors)
     boxes = torch.empty_like(loc)
-    check(_lib.lib().stm_decode_boxes_f32(_p(loc), _p(priors), _p(boxes), c_l(loc.shape[0]), _stream()),
-          "stm_decode_boxes_f32")
+    call("stm_decode_boxes_f32", _p(loc), _p(priors), _p(boxes), loc.shape[0], _stream())
     return boxes
 
 
@@ -463,8 +441,7 @@ def decode_backward(grad_boxes, loc, priors, need_loc=True, need_priors=False):
     gp = torch.empty_like(priors) if need_priors else None
     if gl is None and gp is None:
         return None, None
-    check(_lib.lib().stm_decode_boxes_backward_f32(_p(gb), _p(loc), _p(priors), _p(gl), _p(gp), c_l(loc.shape[0]), _stream()),
-          "stm_decode_boxes_backward_f32")
+    call("stm_decode_boxes_backward_f32", _p(gb), _p(loc), _p(priors), _p(gl), _p(gp), loc.shape[0], _stream())
     return gl, gp
 
 
@@ -477,9 +454,7 @@ def generate_candidates(loc, priors, conf, thresh=0.05):
     keep_idx = torch.empty(B, N, dtype=torch.int64, device=conf.device)
     cand_box = torch.empty(B, N, 4, dtype=torch.float32, device=conf.device)
     count = torch.empty(B, dtype=torch.int32, device=conf.device)
-    check(_lib.lib().stm_generate_candidates_f32(_p(loc), _p(priors), _p(conf), c_i(N), c_i(ncls), c_f(thresh), c_i(B),
-                                                 _p(keep_idx), _p(cand_box), _p(count), _stream()),
-          "stm_generate_candidates_f32")
+    call("stm_generate_candidates_f32", _p(loc), _p(priors), _p(conf), N, ncls, thresh, B, _p(keep_idx), _p(cand_box), _p(count), _stream())
     return keep_idx, cand_box, count
 
 
@@ -505,14 +480,12 @@ def cc_fast_nms(conf, boxes, centerness, iou_thr=0.5, top_k=200, k_dev=None):
     cnt = torch.empty(B, dtype=torch.int32, device=dev)
     if K > NMS_LDS_KEYS and k_dev is None:
         # more candidate rows than the one-workgroup LDS sort holds: scores to a workspace, exact top-k select in the kernel
-        ws = _workspace(_lib.lib().stm_cc_fast_nms_workspace_bytes(c_i(K), c_i(B)), dev, "ccnms")
-        check(_lib.lib().stm_cc_fast_nms_ws_f32(_p(conf), _p(boxes), _p(cen), c_i(K), c_i(ncls), c_f(iou_thr), c_i(top_k), c_i(B),
-                                                _p(idx), _p(cls), _p(sc), _p(bx), _p(cnt), _p(ws), c_sz(ws.numel()), _stream()),
-              "stm_cc_fast_nms_ws_f32")
+        ws = _workspace(_lib.lib().stm_cc_fast_nms_workspace_bytes(K, B), dev, "ccnms")
+        call("stm_cc_fast_nms_ws_f32", _p(conf), _p(boxes), _p(cen), K, ncls, iou_thr, top_k, B, _p(idx), _p(cls), _p(sc), _p(bx), _p(cnt), _p(ws),
+             ws.numel(), _stream())
     else:
-        check(_lib.lib().stm_cc_fast_nms_f32(_p(conf), _p(boxes), _p(cen), c_i(K), c_i(ncls), _p(k_dev), c_f(iou_thr),
-                                             c_i(top_k), c_i(B), _p(idx), _p(cls), _p(sc), _p(bx), _p(cnt), _stream()),
-              "stm_cc_fast_nms_f32")
+        call("stm_cc_fast_nms_f32", _p(conf), _p(boxes), _p(cen), K, ncls, _p(k_dev), iou_thr, top_k, B, _p(idx), _p(cls), _p(sc), _p(bx), _p(cnt),
+             _stream())
     if squeeze:
         return idx[0], cls[0], sc[0], bx[0], cnt[0]
     return idx, cls, sc, bx, cnt
@@ -532,11 +505,10 @@ def detect_cc(loc, priors, conf, centerness, conf_thresh=0.05, iou_thr=0.5, top_
     sc = torch.empty(B, top_k, dtype=torch.float32, device=dev)
     bx = torch.empty(B, top_k, 4, dtype=torch.float32, device=dev)
     cnt = torch.empty(B, dtype=torch.int32, device=dev)
-    need = _lib.lib().stm_detect_cc_workspace_bytes(c_i(N), c_i(B))
+    need = _lib.lib().stm_detect_cc_workspace_bytes(N, B)
     ws = _workspace(need, dev, "detect")
-    fn = _lib.lib().stm_detect_cc_logits_f32 if logits else _lib.lib().stm_detect_cc_f32
-    check(fn(_p(loc), _p(priors), _p(conf), _p(cen), c_i(N), c_i(ncls), c_f(conf_thresh), c_f(iou_thr), c_i(top_k), c_i(B), _p(idx), _p(cls),
-             _p(sc), _p(bx), _p(cnt), _p(ws), c_sz(ws.numel()), _stream()), "stm_detect_cc_f32")
+    call("stm_detect_cc_logits_f32" if logits else "stm_detect_cc_f32", _p(loc), _p(priors), _p(conf), _p(cen), N, ncls, conf_thresh, iou_thr,
+         top_k, B, _p(idx), _p(cls), _p(sc), _p(bx), _p(cnt), _p(ws), ws.numel(), _stream())
     return idx, cls, sc, bx, cnt
 
 
@@ -552,11 +524,10 @@ def fast_nms(conf, boxes, centerness, iou_thr=0.5, top_k=200, conf_thresh=0.05, 
     sc = torch.empty(max_det, dtype=torch.float32, device=dev)
     bx = torch.empty(max_det, 4, dtype=torch.float32, device=dev)
     cnt = torch.empty(1, dtype=torch.int32, device=dev)
-    need = _lib.lib().stm_fast_nms_workspace_bytes(c_i(K), c_i(ncls), c_i(top_k))
+    need = _lib.lib().stm_fast_nms_workspace_bytes(K, ncls, top_k)
     ws = _workspace(need, dev, "pcnms")
-    check(_lib.lib().stm_fast_nms_f32(_p(conf), _p(boxes), _p(cen), c_i(K), c_i(ncls), _p(k_dev), c_f(iou_thr), c_i(top_k),
-                                      c_f(conf_thresh), c_i(max_det), _p(idx), _p(cls), _p(sc), _p(bx), _p(cnt), _p(ws),
-                                      c_sz(ws.numel()), _stream()), "stm_fast_nms_f32")
+    call("stm_fast_nms_f32", _p(conf), _p(boxes), _p(cen), K, ncls, _p(k_dev), iou_thr, top_k, conf_thresh, max_det, _p(idx), _p(cls), _p(sc), _p(bx),
+         _p(cnt), _p(ws), ws.numel(), _stream())
     return idx, cls, sc, bx, cnt[0]
 
 
@@ -578,10 +549,9 @@ def detect_pc(loc, priors, conf, centerness, conf_thresh=0.05, iou_thr=0.5, top_
     sc = torch.empty(B, max_det, dtype=torch.float32, device=dev)
     bx = torch.empty(B, max_det, 4, dtype=torch.float32, device=dev)
     cnt = torch.empty(B, dtype=torch.int32, device=dev)
-    ws = _workspace(_lib.lib().stm_fast_nms_batched_workspace_bytes(c_i(N), c_i(ncls), c_i(top_k), c_i(B)), dev, "pcnms_b")
-    check(_lib.lib().stm_fast_nms_batched_f32(_p(conf), c_l(N * ncls), _p(keep_idx), _p(cand_box), _p(cen), c_l(N), c_i(N), c_i(ncls), _p(count), c_f(iou_thr),
-                                              c_i(top_k), c_f(conf_thresh), c_i(max_det), c_i(B), _p(idx), _p(cls), _p(sc), _p(bx), _p(cnt), _p(ws),
-                                              c_sz(ws.numel()), _stream()), "stm_fast_nms_batched_f32")
+    ws = _workspace(_lib.lib().stm_fast_nms_batched_workspace_bytes(N, ncls, top_k, B), dev, "pcnms_b")
+    call("stm_fast_nms_batched_f32", _p(conf), N * ncls, _p(keep_idx), _p(cand_box), _p(cen), N, N, ncls, _p(count), iou_thr, top_k, conf_thresh,
+         max_det, B, _p(idx), _p(cls), _p(sc), _p(bx), _p(cnt), _p(ws), ws.numel(), _stream())
     return idx, cls, sc, bx, cnt
 
 
@@ -593,7 +563,7 @@ def encode(matched, priors):
     if matched.dim() != 2 or matched.shape[1] != 4 or priors.shape != matched.shape:
         raise StmError(f"encode: matched {tuple(matched.shape)} and priors {tuple(priors.shape)} must both be [n, 4]")
     out = torch.empty_like(matched)
-    check(_lib.lib().stm_encode_boxes_f32(_p(matched), _p(priors), _p(out), c_l(matched.shape[0]), _stream()), "stm_encode_boxes_f32")
+    call("stm_encode_boxes_f32", _p(matched), _p(priors), _p(out), matched.shape[0], _stream())
     return out
 
 
@@ -647,13 +617,11 @@ def match_priors(boxes, labels, ids, counts, priors, conf, pos_thresh, neg_thres
             if t.dtype != dt or t.numel() != B * P * (4 if len(shp) == 3 else 1) or not t.is_contiguous() or t.device != dev:
                 raise StmError(f"match_priors: output {tuple(t.shape)} {t.dtype} must be contiguous {dt} with the elements of {shp}")
     status = torch.empty(B, dtype=torch.int32, device=dev) if want_status else None
-    L = _lib.lib()
-    nbytes = L.stm_match_workspace_bytes(c_i(B), c_i(P), c_i(G_total), c_i(G_max))
+    nbytes = _lib.lib().stm_match_workspace_bytes(B, P, G_total, G_max)
     ws = _workspace(nbytes, dev, "match")
-    check(L.stm_match_priors_f32(_p(boxes), _p(labels), _p(ids), _p(offsets), c_i(B), c_i(G_total), c_i(G_max), _p(priors),
-                                 c_i(1 if priors.dim() == 3 else 0), c_i(P), _p(conf), c_i(C), ctypes.c_double(float(pos_thresh)),
-                                 ctypes.c_double(float(neg_thresh)), _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _p(out[4]), _p(status),
-                                 _p(ws), c_sz(nbytes), _stream()), "stm_match_priors_f32")
+    call("stm_match_priors_f32", _p(boxes), _p(labels), _p(ids), _p(offsets), B, G_total, G_max, _p(priors), 1 if priors.dim() == 3 else 0, P,
+         _p(conf), C, float(pos_thresh), float(neg_thresh), _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _p(out[4]), _p(status), _p(ws), nbytes,
+         _stream())
     return tuple(out) + ((status,) if want_status else ())
 
 
@@ -662,7 +630,7 @@ def jaccard(a, b):
     _dev(a, b)
     a, b = _f32c(a), _f32c(b)
     out = torch.empty(a.shape[0], b.shape[0], dtype=torch.float32, device=a.device)
-    check(_lib.lib().stm_jaccard_f32(_p(a), c_i(a.shape[0]), _p(b), c_i(b.shape[0]), _p(out), _stream()), "stm_jaccard_f32")
+    call("stm_jaccard_f32", _p(a), a.shape[0], _p(b), b.shape[0], _p(out), _stream())
     return out
 
 
@@ -676,8 +644,7 @@ def jaccard_backward(grad_out, a, b, need_a=True, need_b=True):
     gb = torch.empty_like(b) if need_b else None
     if ga is None and gb is None:
         return None, None
-    check(_lib.lib().stm_jaccard_backward_f32(_p(go), _p(a), c_i(a.shape[0]), _p(b), c_i(b.shape[0]), _p(ga), _p(gb), _stream()),
-          "stm_jaccard_backward_f32")
+    call("stm_jaccard_backward_f32", _p(go), _p(a), a.shape[0], _p(b), b.shape[0], _p(ga), _p(gb), _stream())
     return ga, gb
 
 
@@ -691,9 +658,8 @@ def lincomb_sigmoid_crop_bits(proto, coeff, boxes, row_proto, thr=0.5, apply_tan
     n = coeff.shape[0]
     out = torch.empty(n, h, w, dtype=torch.float32, device=proto.device)
     bits = torch.empty(n, (h * w + 63) // 64, dtype=torch.int64, device=proto.device)
-    check(_lib.lib().stm_lincomb_sigmoid_crop_bits_f32(_p(proto), _p(coeff), _p(_f32c(boxes)), _p(out), c_i(h), c_i(w), c_i(m), c_i(n),
-                                                       c_i(1 if apply_tanh else 0), c_p(0), _p(row_proto), _p(bits), c_f(thr), _stream()),
-          "stm_lincomb_sigmoid_crop_bits_f32")
+    call("stm_lincomb_sigmoid_crop_bits_f32", _p(proto), _p(coeff), _p(_f32c(boxes)), _p(out), h, w, m, n, 1 if apply_tanh else 0, c_p(0),
+         _p(row_proto), _p(bits), thr, _stream())
     return out, bits
 
 
@@ -706,9 +672,8 @@ def mask_iou_bits(bits1, bits2, hw, group1=None, group2=None):
     out = torch.empty(n1, n2, dtype=torch.float32, device=bits1.device)     # (the kernel writes every element: zeros for pairs of different groups)
     if bits1.dtype != torch.int64 or bits2.dtype != torch.int64 or bits1.shape[1] != (hw + 63) // 64 or bits2.shape[1] != bits1.shape[1]:
         raise StmError("mask_iou_bits: bit tables must be int64 [n, ceil(hw / 64)]")
-    check(_lib.lib().stm_mask_iou_bits_f32(_p(bits1.contiguous()), c_i(n1), _p(bits2.contiguous()), c_i(n2), c_i(hw), _p(out),
-                                           _p(group1.contiguous()) if group1 is not None else c_p(0),
-                                           _p(group2.contiguous()) if group2 is not None else c_p(0), _stream()), "stm_mask_iou_bits_f32")
+    call("stm_mask_iou_bits_f32", _p(bits1.contiguous()), n1, _p(bits2.contiguous()), n2, hw, _p(out),
+         _p(group1.contiguous()) if group1 is not None else c_p(0), _p(group2.contiguous()) if group2 is not None else c_p(0), _stream())
     return out
 
 
@@ -725,9 +690,8 @@ def lincomb_sigmoid_crop(proto, coeff, boxes=None, apply_tanh=True, n_dev=None, 
     n = coeff.shape[0]
     bx = _f32c(boxes) if boxes is not None else None
     out = torch.empty(n, h, w, dtype=torch.float32, device=proto.device)
-    check(_lib.lib().stm_lincomb_sigmoid_crop_f32(_p(proto), _p(coeff), _p(bx), _p(out), c_i(h), c_i(w), c_i(m), c_i(n),
-                                                  c_i(1 if apply_tanh else 0), _p(n_dev), _p(row_proto), _stream()),
-          "stm_lincomb_sigmoid_crop_f32")
+    call("stm_lincomb_sigmoid_crop_f32", _p(proto), _p(coeff), _p(bx), _p(out), h, w, m, n, 1 if apply_tanh else 0, _p(n_dev), _p(row_proto),
+         _stream())
     return out
 
 
@@ -745,10 +709,10 @@ def lincomb_sigmoid_crop_backward(grad_out, proto, coeff, boxes=None, apply_tanh
     if gp is None and gc is None:
         return None, None
     bx = _f32c(boxes) if boxes is not None else None
-    need = _lib.lib().stm_lincomb_backward_workspace_bytes(c_i(n), c_i(h), c_i(w), c_i(m))
+    need = _lib.lib().stm_lincomb_backward_workspace_bytes(n, h, w, m)
     ws = _workspace(need, proto.device, "lcb")
-    check(_lib.lib().stm_lincomb_backward_f32(_p(go), _p(proto), _p(coeff), _p(bx), _p(gp), _p(gc), c_i(h), c_i(w), c_i(m), c_i(n),
-                                              c_i(1 if apply_tanh else 0), _p(ws), c_sz(ws.numel()), _stream()), "stm_lincomb_backward_f32")
+    call("stm_lincomb_backward_f32", _p(go), _p(proto), _p(coeff), _p(bx), _p(gp), _p(gc), h, w, m, n, 1 if apply_tanh else 0, _p(ws), ws.numel(),
+         _stream())
     return gp, gc
 
 
@@ -786,10 +750,9 @@ def mask_bce_upsampled(pred, target, idx=None):
     loss = torch.empty(n, dtype=torch.float32, device=pred.device)
     if n == 0:
         return loss
-    need = _lib.lib().stm_mask_bce_workspace_bytes(c_i(n), c_i(H), c_i(W))
+    need = _lib.lib().stm_mask_bce_workspace_bytes(n, H, W)
     ws = _workspace(need, pred.device, "mbce")
-    check(_lib.lib().stm_mask_bce_upsampled_f32(_p(pred), _p(target), c_i(1 if is_f32 else 0), _p(idx), _p(loss), c_i(n), c_i(h), c_i(w), c_i(G),
-                                                c_i(H), c_i(W), _p(ws), c_sz(ws.numel()), _stream()), "stm_mask_bce_upsampled_f32")
+    call("stm_mask_bce_upsampled_f32", _p(pred), _p(target), 1 if is_f32 else 0, _p(idx), _p(loss), n, h, w, G, H, W, _p(ws), ws.numel(), _stream())
     return loss
 
 
@@ -802,9 +765,8 @@ def mask_bce_upsampled_backward(grad_loss, pred, target, idx=None):
     grad_pred = torch.empty_like(pred)
     if n == 0:
         return grad_pred
-    check(_lib.lib().stm_mask_bce_upsampled_backward_f32(_p(_f32c(grad_loss)), _p(pred), _p(target), c_i(1 if is_f32 else 0), _p(idx), _p(grad_pred),
-                                                         c_i(n), c_i(h), c_i(w), c_i(G), c_i(H), c_i(W), _stream()),
-          "stm_mask_bce_upsampled_backward_f32")
+    call("stm_mask_bce_upsampled_backward_f32", _p(_f32c(grad_loss)), _p(pred), _p(target), 1 if is_f32 else 0, _p(idx), _p(grad_pred), n, h, w, G, H,
+         W, _stream())
     return grad_pred
 
 
@@ -835,11 +797,9 @@ def ohem_select_neg(conf_data, conf_t, negpos_ratio=3):
     conventions are in include/stmask_hip.h and INTEGRATION.md section 14).  7 launches, no host synchronisation."""
     x, t, B, P, C, ratio = _ohem_args("ohem_select_neg", conf_data.detach(), conf_t, negpos_ratio)
     neg = torch.empty(B * P, dtype=torch.float32, device=x.device)
-    L = _lib.lib()
-    nbytes = L.stm_ohem_conf_workspace_bytes(c_i(B), c_i(P), c_i(C))
+    nbytes = _lib.lib().stm_ohem_conf_workspace_bytes(B, P, C)
     ws = _workspace(nbytes, x.device, "ohem")
-    check(L.stm_ohem_select_neg_f32(_p(x), _p(t), _p(neg), c_i(B), c_i(P), c_i(C), c_i(ratio), _p(ws), c_sz(ws.numel()), _stream()),
-          "stm_ohem_select_neg_f32")
+    call("stm_ohem_select_neg_f32", _p(x), _p(t), _p(neg), B, P, C, ratio, _p(ws), ws.numel(), _stream())
     return neg
 
 
@@ -856,11 +816,10 @@ def ohem_conf_loss(conf_data, conf_t, negpos_ratio=3, conf_alpha=1.0, weights="r
     loss = torch.empty((), dtype=torch.float32, device=dev)
     lse = torch.empty(B * P, dtype=torch.float32, device=dev)
     w = torch.empty(B * P, dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    nbytes = L.stm_ohem_conf_workspace_bytes(c_i(B), c_i(P), c_i(C))
+    nbytes = _lib.lib().stm_ohem_conf_workspace_bytes(B, P, C)
     ws = _workspace(nbytes, dev, "ohem")
-    check(L.stm_ohem_conf_loss_f32(_p(x), _p(t), _p(loss), _p(lse), _p(w), c_i(B), c_i(P), c_i(C), c_i(ratio), ctypes.c_double(float(conf_alpha)),
-                                   c_i(OHEM_WEIGHTS[weights]), _p(ws), c_sz(ws.numel()), _stream()), "stm_ohem_conf_loss_f32")
+    call("stm_ohem_conf_loss_f32", _p(x), _p(t), _p(loss), _p(lse), _p(w), B, P, C, ratio, float(conf_alpha), OHEM_WEIGHTS[weights], _p(ws),
+         ws.numel(), _stream())
     return loss, lse, w
 
 
@@ -875,9 +834,8 @@ def ohem_conf_loss_backward(grad_loss, conf_data, conf_t, lse, w, negpos_ratio=3
     if lse.dtype != torch.float32 or w.dtype != torch.float32 or lse.numel() != N or w.numel() != N:
         raise StmError(f"ohem_conf_loss_backward: lse and w must be float32 [{N}]")
     grad = torch.empty(conf_data.shape, dtype=torch.float32, device=x.device)
-    check(_lib.lib().stm_ohem_conf_loss_backward_f32(_p(grad_loss.contiguous()), _p(x), _p(t), _p(lse.contiguous()), _p(w.contiguous()), _p(grad),
-                                                     c_i(B), c_i(P), c_i(C), c_i(ratio), ctypes.c_double(float(conf_alpha)), _stream()),
-          "stm_ohem_conf_loss_backward_f32")
+    call("stm_ohem_conf_loss_backward_f32", _p(grad_loss.contiguous()), _p(x), _p(t), _p(lse.contiguous()), _p(w.contiguous()), _p(grad), B, P, C,
+         ratio, float(conf_alpha), _stream())
     return grad
 
 
@@ -914,11 +872,9 @@ def box_center_loss(loc_data, priors, gt_boxes_t, conf_t, centerness_data=None, 
     biou = torch.empty((), dtype=torch.float32, device=dev)
     center = torch.empty((), dtype=torch.float32, device=dev) if cent is not None else None
     npos = torch.empty(B, dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    ws = _workspace(L.stm_box_center_workspace_bytes(c_i(B), c_i(P)), dev, "bcl")
-    check(L.stm_box_center_loss_f32(_p(loc), _p(pri), c_i(per_img), _p(gt), _p(t), _p(cent), _p(biou), _p(center), _p(npos), c_i(B), c_i(P),
-                                    ctypes.c_double(float(bboxiou_alpha)), ctypes.c_double(float(center_alpha)), _p(ws), c_sz(ws.numel()),
-                                    _stream()), "stm_box_center_loss_f32")
+    ws = _workspace(_lib.lib().stm_box_center_workspace_bytes(B, P), dev, "bcl")
+    call("stm_box_center_loss_f32", _p(loc), _p(pri), per_img, _p(gt), _p(t), _p(cent), _p(biou), _p(center), _p(npos), B, P, float(bboxiou_alpha),
+         float(center_alpha), _p(ws), ws.numel(), _stream())
     return biou, center, npos
 
 
@@ -935,10 +891,8 @@ def box_center_loss_backward(grad_biou, grad_center, loc_data, priors, gt_boxes_
         raise StmError(f"box_center_loss_backward: npos must be int32 [{B}]")
     grad_loc = torch.empty(B, P, 4, dtype=torch.float32, device=loc.device)
     grad_cent = torch.empty(centerness_data.shape, dtype=torch.float32, device=loc.device) if cent is not None and need_centerness else None
-    check(_lib.lib().stm_box_center_loss_backward_f32(_p(grad_biou), _p(grad_center), _p(loc), _p(pri), c_i(per_img), _p(gt), _p(t), _p(cent),
-                                                      _p(npos.contiguous()), _p(grad_loc), _p(grad_cent), c_i(B), c_i(P),
-                                                      ctypes.c_double(float(bboxiou_alpha)), ctypes.c_double(float(center_alpha)), _stream()),
-          "stm_box_center_loss_backward_f32")
+    call("stm_box_center_loss_backward_f32", _p(grad_biou), _p(grad_center), _p(loc), _p(pri), per_img, _p(gt), _p(t), _p(cent),
+         _p(npos.contiguous()), _p(grad_loc), _p(grad_cent), B, P, float(bboxiou_alpha), float(center_alpha), _stream())
     return grad_loc, grad_cent
 
 
@@ -960,10 +914,8 @@ def track_loss(track_data, conf_t, ids_t, track_alpha=1.0):
     (stm_track_loss_f32)."""
     x, t, ids, B, P, D = _track_args("track_loss", track_data, conf_t, ids_t)
     loss = torch.empty((), dtype=torch.float32, device=x.device)
-    L = _lib.lib()
-    ws = _workspace(L.stm_track_loss_workspace_bytes(c_i(B), c_i(P), c_i(D)), x.device, "trl")
-    check(L.stm_track_loss_f32(_p(x), _p(t), _p(ids), _p(loss), c_i(B), c_i(P), c_i(D), ctypes.c_double(float(track_alpha)), _p(ws),
-                               c_sz(ws.numel()), _stream()), "stm_track_loss_f32")
+    ws = _workspace(_lib.lib().stm_track_loss_workspace_bytes(B, P, D), x.device, "trl")
+    call("stm_track_loss_f32", _p(x), _p(t), _p(ids), _p(loss), B, P, D, float(track_alpha), _p(ws), ws.numel(), _stream())
     return loss
 
 
@@ -974,10 +926,9 @@ def track_loss_backward(grad_loss, track_data, conf_t, ids_t, track_alpha=1.0):
     if grad_loss.dtype != torch.float32 or grad_loss.numel() != 1:
         raise StmError(f"track_loss_backward: grad_loss must be one float32, got {grad_loss.dtype} {tuple(grad_loss.shape)}")
     grad = torch.empty(B, P, D, dtype=torch.float32, device=x.device)
-    L = _lib.lib()
-    ws = _workspace(L.stm_track_loss_workspace_bytes(c_i(B), c_i(P), c_i(D)), x.device, "trl")
-    check(L.stm_track_loss_backward_f32(_p(grad_loss.contiguous()), _p(x), _p(t), _p(ids), _p(grad), c_i(B), c_i(P), c_i(D),
-                                        ctypes.c_double(float(track_alpha)), _p(ws), c_sz(ws.numel()), _stream()), "stm_track_loss_backward_f32")
+    ws = _workspace(_lib.lib().stm_track_loss_workspace_bytes(B, P, D), x.device, "trl")
+    call("stm_track_loss_backward_f32", _p(grad_loss.contiguous()), _p(x), _p(t), _p(ids), _p(grad), B, P, D, float(track_alpha), _p(ws), ws.numel(),
+         _stream())
     return grad
 
 
@@ -1016,12 +967,10 @@ def t2s_targets(ids_t, boxes_ref, ids_ref, counts_ref, boxes_next, ids_next, cou
     reg_t = torch.empty(B, P, 4, dtype=torch.float32, device=dev)
     idx_next = torch.empty(B, P, dtype=torch.int64, device=dev)
     prefix = torch.empty(B + 1, dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    nbytes = L.stm_t2s_workspace_bytes(c_i(B), c_i(P))
+    nbytes = _lib.lib().stm_t2s_workspace_bytes(B, P)
     ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)           # kept by the caller until the gather has run: not the shared scratch
-    check(L.stm_t2s_targets_f32(_p(ids_t), _p(boxes_ref), _p(ids_ref), _p(offsets[0]), c_i(Gr), c_i(Gr_max), _p(boxes_next), _p(ids_next),
-                                _p(offsets[1]), c_i(Gn), c_i(Gn_max), _p(pos_t), _p(reg_t), _p(idx_next), _p(prefix), c_i(B), c_i(P),
-                                c_i(int(max_rows) if max_rows else 0), _p(ws), c_sz(ws.numel()), _stream()), "stm_t2s_targets_f32")
+    call("stm_t2s_targets_f32", _p(ids_t), _p(boxes_ref), _p(ids_ref), _p(offsets[0]), Gr, Gr_max, _p(boxes_next), _p(ids_next), _p(offsets[1]), Gn,
+         Gn_max, _p(pos_t), _p(reg_t), _p(idx_next), _p(prefix), B, P, int(max_rows) if max_rows else 0, _p(ws), ws.numel(), _stream())
     return pos_t, reg_t, idx_next, prefix, ws
 
 
@@ -1045,10 +994,9 @@ def t2s_gather(state, n_rows, loc_ref, priors, coeff_ref, reg_t, idx_next, boxes
     out = dict(rois=torch.empty(n, 5, **f32), reg=torch.empty(n, 4, **f32), coeff=torch.empty(n, M, **f32), box=torch.empty(n, 4, **f32),
                idx=torch.empty(n, dtype=torch.int64, device=dev), clip=torch.empty(n, dtype=torch.int32, device=dev), w=torch.empty(n, **f32),
                n_dev=torch.empty(1, dtype=torch.int32, device=dev), status=torch.empty(1, dtype=torch.int32, device=dev))
-    check(_lib.lib().stm_t2s_gather_f32(_p(loc_ref), _p(priors), _p(coeff_ref), _p(_f32c(reg_t)), _p(idx_next.contiguous()), _p(_f32c(boxes_next)),
-                                        c_i(boxes_next.shape[0]), _p(out["rois"]), _p(out["reg"]), _p(out["coeff"]), _p(out["box"]), _p(out["idx"]),
-                                        _p(out["clip"]), _p(out["w"]), _p(out["n_dev"]), _p(out["status"]), c_i(n), c_i(B), c_i(P), c_i(M),
-                                        c_i(feat_h), c_i(feat_w), _p(state), c_sz(state.numel()), _stream()), "stm_t2s_gather_f32")
+    call("stm_t2s_gather_f32", _p(loc_ref), _p(priors), _p(coeff_ref), _p(_f32c(reg_t)), _p(idx_next.contiguous()), _p(_f32c(boxes_next)),
+         boxes_next.shape[0], _p(out["rois"]), _p(out["reg"]), _p(out["coeff"]), _p(out["box"]), _p(out["idx"]), _p(out["clip"]), _p(out["w"]),
+         _p(out["n_dev"]), _p(out["status"]), n, B, P, M, feat_h, feat_w, _p(state), state.numel(), _stream())
     return out
 
 
@@ -1070,10 +1018,8 @@ def t2s_reduce(bbox_reg, reg_rows, bce, box_rows, w_rows, n_dev, status, bs, H, 
     n = _t2s_rows("t2s_reduce", bbox_reg, reg_rows, bce, box_rows, w_rows, n_dev, status)
     b = torch.empty((), dtype=torch.float32, device=bbox_reg.device)
     m = torch.empty((), dtype=torch.float32, device=bbox_reg.device)
-    check(_lib.lib().stm_t2s_reduce_f32(_p(bbox_reg.contiguous()), _p(reg_rows.contiguous()), _p(bce.contiguous()), _p(box_rows.contiguous()),
-                                        _p(w_rows.contiguous()), _p(n_dev), _p(status), _p(b), _p(m), c_i(n), c_i(bs), c_i(H), c_i(W),
-                                        ctypes.c_double(float(boxshift_alpha)), ctypes.c_double(float(maskshift_alpha)), _stream()),
-          "stm_t2s_reduce_f32")
+    call("stm_t2s_reduce_f32", _p(bbox_reg.contiguous()), _p(reg_rows.contiguous()), _p(bce.contiguous()), _p(box_rows.contiguous()),
+         _p(w_rows.contiguous()), _p(n_dev), _p(status), _p(b), _p(m), n, bs, H, W, float(boxshift_alpha), float(maskshift_alpha), _stream())
     return b, m
 
 
@@ -1088,11 +1034,9 @@ def t2s_reduce_backward(grad_b, grad_m, bbox_reg, reg_rows, box_rows, w_rows, n_
             raise StmError(f"t2s_reduce_backward: a loss gradient must be one float32, got {g.dtype} {tuple(g.shape)}")
     g_reg = torch.empty(n, 4, dtype=torch.float32, device=bbox_reg.device) if need_reg else None
     g_bce = torch.empty(n, dtype=torch.float32, device=bbox_reg.device) if need_bce else None
-    check(_lib.lib().stm_t2s_reduce_backward_f32(_p(grad_b.contiguous() if grad_b is not None else None),
-                                                 _p(grad_m.contiguous() if grad_m is not None else None), _p(bbox_reg.contiguous()),
-                                                 _p(reg_rows.contiguous()), _p(box_rows.contiguous()), _p(w_rows.contiguous()), _p(n_dev), _p(status),
-                                                 _p(g_reg), _p(g_bce), c_i(n), c_i(bs), c_i(H), c_i(W), ctypes.c_double(float(boxshift_alpha)),
-                                                 ctypes.c_double(float(maskshift_alpha)), _stream()), "stm_t2s_reduce_backward_f32")
+    call("stm_t2s_reduce_backward_f32", _p(grad_b.contiguous() if grad_b is not None else None),
+         _p(grad_m.contiguous() if grad_m is not None else None), _p(bbox_reg.contiguous()), _p(reg_rows.contiguous()), _p(box_rows.contiguous()),
+         _p(w_rows.contiguous()), _p(n_dev), _p(status), _p(g_reg), _p(g_bce), n, bs, H, W, float(boxshift_alpha), float(maskshift_alpha), _stream())
     return g_reg, g_bce
 
 
@@ -1115,11 +1059,10 @@ def lincomb_rows_backward(grad_out, proto, coeff, boxes, row_proto, n_dev=None, 
         return gc
     bx = _f32c(boxes) if boxes is not None else None
     rp = row_proto.contiguous() if row_proto is not None else None
-    L = _lib.lib()
-    need = L.stm_lincomb_rows_backward_workspace_bytes(c_i(n), c_i(h), c_i(w), c_i(m))
+    need = _lib.lib().stm_lincomb_rows_backward_workspace_bytes(n, h, w, m)
     ws = _workspace(need, proto.device, "lcrb")
-    check(L.stm_lincomb_rows_backward_f32(_p(go), _p(proto), c_i(S), _p(coeff), _p(bx), _p(rp), _p(n_dev), _p(gc), c_i(h), c_i(w), c_i(m), c_i(n),
-                                          c_i(1 if apply_tanh else 0), _p(ws), c_sz(ws.numel()), _stream()), "stm_lincomb_rows_backward_f32")
+    call("stm_lincomb_rows_backward_f32", _p(go), _p(proto), S, _p(coeff), _p(bx), _p(rp), _p(n_dev), _p(gc), h, w, m, n, 1 if apply_tanh else 0,
+         _p(ws), ws.numel(), _stream())
     return gc
 
 
@@ -1133,16 +1076,15 @@ def mask_iou(m1, m2, thr=0.5, group1=None, group2=None):
     if n1 == 0 or n2 == 0:
         return out
     hw = m1[0].numel()
-    need = _lib.lib().stm_mask_iou_workspace_bytes(c_i(n1), c_i(n2), c_i(hw))
+    need = _lib.lib().stm_mask_iou_workspace_bytes(n1, n2, hw)
     ws = _workspace(need, m1.device, "miou")
     if group1 is not None:
         if group1.dtype != torch.int32 or group2.dtype != torch.int32 or group1.numel() != n1 or group2.numel() != n2:
             raise StmError("mask_iou: group arrays must be int32 of lengths n1 and n2")
-        check(_lib.lib().stm_mask_iou_grouped_f32(_p(m1), c_i(n1), _p(m2), c_i(n2), c_i(hw), c_f(thr), _p(out), _p(group1.contiguous()),
-                                                  _p(group2.contiguous()), _p(ws), c_sz(ws.numel()), _stream()), "stm_mask_iou_grouped_f32")
+        call("stm_mask_iou_grouped_f32", _p(m1), n1, _p(m2), n2, hw, thr, _p(out), _p(group1.contiguous()), _p(group2.contiguous()), _p(ws),
+             ws.numel(), _stream())
         return out
-    check(_lib.lib().stm_mask_iou_f32(_p(m1), c_i(n1), _p(m2), c_i(n2), c_i(hw), c_f(thr), _p(out), _p(ws), c_sz(ws.numel()),
-                                      _stream()), "stm_mask_iou_f32")
+    call("stm_mask_iou_f32", _p(m1), n1, _p(m2), n2, hw, thr, _p(out), _p(ws), ws.numel(), _stream())
     return out
 
 
@@ -1162,8 +1104,7 @@ def bias_act_(y, bias, residual=None, relu=True):
     if residual is not None:
         if residual.shape != y.shape or residual.stride() != y.stride():
             residual = residual.contiguous(memory_format=torch.channels_last if inner == 1 else torch.contiguous_format)
-    check(_lib.lib().stm_bias_act_f32(_p(y), _p(_f32c(bias)), _p(residual), c_l(y.numel()), c_i(C), c_l(inner),
-                                      c_i(1 if relu else 0), _stream()), "stm_bias_act_f32")
+    call("stm_bias_act_f32", _p(y), _p(_f32c(bias)), _p(residual), y.numel(), C, inner, 1 if relu else 0, _stream())
     return y
 
 
@@ -1177,11 +1118,10 @@ def mask_resize_rle(masks, crop_h, crop_w, out_h, out_w, thr=0.5, max_runs=4096)
     n_runs = torch.zeros(n, dtype=torch.int32, device=masks.device)
     if n == 0:
         return counts, n_runs
-    need = _lib.lib().stm_mask_rle_workspace_bytes(c_i(n), c_i(out_h), c_i(out_w), c_i(max_runs))
+    need = _lib.lib().stm_mask_rle_workspace_bytes(n, out_h, out_w, max_runs)
     ws = _workspace(need, masks.device, "rle")
-    check(_lib.lib().stm_mask_resize_rle_f32(_p(masks), c_i(n), c_i(mh), c_i(mw), c_i(crop_h), c_i(crop_w), c_i(out_h),
-                                             c_i(out_w), c_f(thr), _p(counts), c_i(max_runs), _p(n_runs), _p(ws),
-                                             c_sz(ws.numel()), _stream()), "stm_mask_resize_rle_f32")
+    call("stm_mask_resize_rle_f32", _p(masks), n, mh, mw, crop_h, crop_w, out_h, out_w, thr, _p(counts), max_runs, _p(n_runs), _p(ws), ws.numel(),
+         _stream())
     return counts, n_runs
 
 
@@ -1195,7 +1135,7 @@ def conv_pack_weights(weight, planes=3, tile_n=128, fmt=0, wscale=None):
     O, C, kh, kw = weight.shape
     if fmt >= 1:
         planes = 2 if fmt == 1 else 1
-    nbytes = _lib.lib().stm_conv_packed_weight_bytes_tiled(c_i(O), c_i(C), c_i(kh), c_i(kw), c_i(planes), c_i(tile_n))
+    nbytes = _lib.lib().stm_conv_packed_weight_bytes_tiled(O, C, kh, kw, planes, tile_n)
     if nbytes == 0:
         raise StmError(f"conv_pack_weights: unsupported weight shape {tuple(weight.shape)} (Cin must be a multiple of 32)")
     packed = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
@@ -1204,11 +1144,9 @@ def conv_pack_weights(weight, planes=3, tile_n=128, fmt=0, wscale=None):
         if wscale is None:          # (given: several weight tensors packed under one scale, e.g. the sub-kernels of a window set)
             wmax = float(weight.abs().max())
             wscale = 2.0 ** (10 - math.floor(math.log2(wmax))) if wmax > 0 else 1.0
-        check(_lib.lib().stm_conv_pack_weights_fmt_f32(_p(weight), _p(packed), c_i(O), c_i(C), c_i(kh), c_i(kw), c_i(tile_n), c_i(fmt),
-                                                       c_f(wscale), _stream()), "stm_conv_pack_weights_fmt_f32")
+        call("stm_conv_pack_weights_fmt_f32", _p(weight), _p(packed), O, C, kh, kw, tile_n, fmt, wscale, _stream())
         return packed, 1.0 / wscale
-    check(_lib.lib().stm_conv_pack_weights_tiled_f32(_p(weight), _p(packed), c_i(O), c_i(C), c_i(kh), c_i(kw), c_i(planes),
-                                                     c_i(tile_n), _stream()), "stm_conv_pack_weights_tiled_f32")
+    call("stm_conv_pack_weights_tiled_f32", _p(weight), _p(packed), O, C, kh, kw, planes, tile_n, _stream())
     return packed
 
 
@@ -1234,9 +1172,8 @@ def conv2d_planar_windows(xp, packed_list, windows, bias, B, H, W, C, O, out_h, 
     for i, wv in enumerate(windows):
         wins[i].kh, wins[i].kw, wins[i].ph, wins[i].pw, wins[i].Ho, wins[i].Wo, wins[i].y0, wins[i].x0 = wv
     ptrs = (ctypes.c_void_p * n)(*[p.data_ptr() for p in packed_list])
-    check(_lib.lib().stm_conv2d_planar_windows_f32(_p(xp), ptrs, wins, c_i(n), _p(bias) if bias is not None else None,
-                                                   _p(out_f32) if out_f32 is not None else None, _p(out_planes) if out_planes is not None else None,
-                                                   ctypes.byref(g), c_i(1 if relu else 0), _stream()), "stm_conv2d_planar_windows_f32")
+    call("stm_conv2d_planar_windows_f32", _p(xp), ptrs, wins, n, _p(bias) if bias is not None else None, _p(out_f32) if out_f32 is not None else None,
+         _p(out_planes) if out_planes is not None else None, ctypes.byref(g), 1 if relu else 0, _stream())
     return out_f32 if out_f32 is not None else out_planes
 
 
@@ -1257,8 +1194,8 @@ def conv2d_planar_windows_pool(xp, packed_list, windows, bias, B, H, W, C, O, ou
     for i, wv in enumerate(windows):
         wins[i].kh, wins[i].kw, wins[i].ph, wins[i].pw, wins[i].Ho, wins[i].Wo, wins[i].y0, wins[i].x0 = wv
     ptrs = (ctypes.c_void_p * n)(*[p.data_ptr() for p in packed_list])
-    check(_lib.lib().stm_conv2d_planar_windows_pool_f32(_p(xp), ptrs, wins, c_i(n), _p(bias) if bias is not None else None, _p(pool_fix),
-                                                        ctypes.byref(g), _stream()), "stm_conv2d_planar_windows_pool_f32")
+    call("stm_conv2d_planar_windows_pool_f32", _p(xp), ptrs, wins, n, _p(bias) if bias is not None else None, _p(pool_fix), ctypes.byref(g),
+         _stream())
     return pool_fix
 
 
@@ -1278,10 +1215,8 @@ def temporal_pool_fc(pool_fix, n, npix, weight, bias, n_first=None, clear=True, 
     out = torch.empty(n, nf, device=dev, dtype=torch.float32)
     out2 = torch.empty(n, n_out - nf, device=dev, dtype=torch.float32) if n_first is not None else None
     pooled = torch.empty(n, C, device=dev, dtype=torch.float32) if want_pooled else None
-    check(_lib.lib().stm_temporal_pool_fc_f32(_p(pool_fix), c_i(n), c_i(C), c_i(npix), _p(weight), _p(_f32c(bias)) if bias is not None else None,
-                                              c_i(n_out), c_i(nf), _p(out), _p(out2) if out2 is not None else None,
-                                              _p(pooled) if pooled is not None else None, c_i(1 if clear else 0), _stream()),
-          "stm_temporal_pool_fc_f32")
+    call("stm_temporal_pool_fc_f32", _p(pool_fix), n, C, npix, _p(weight), _p(_f32c(bias)) if bias is not None else None, n_out, nf, _p(out),
+         _p(out2) if out2 is not None else None, _p(pooled) if pooled is not None else None, 1 if clear else 0, _stream())
     res = (out, out2) if n_first is not None else (out,)
     if want_pooled:
         res = res + (pooled,)
@@ -1313,7 +1248,7 @@ def conv_kxr_supported(O, C, kh, kw, stride, padding, groups, group_cout, fmt, m
 def conv_kxr_tile_pixels(kw, fmt, channel_tiles):
     """Flat pixels of a workgroup tile of the kx-reuse kernel for kw, the plane format and a group of channel_tiles 16-channel tiles (0: not
     taken).  A centre-window launch covers tile_pixels // kw images per tile."""
-    return int(_lib.lib().stm_conv_kxr_tile_pixels(c_i(kw), c_i(fmt), c_i(channel_tiles)))
+    return int(_lib.lib().stm_conv_kxr_tile_pixels(kw, fmt, channel_tiles))
 
 
 def conv_pack_weights_kxr(weight, geom, wscale=None):
@@ -1327,8 +1262,7 @@ def conv_pack_weights_kxr(weight, geom, wscale=None):
     packed = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
     if wscale is None:          # (given: a layer that holds some of the groups of another one and must round its weights as that one does)
         wscale = _pow2_wscale(weight)
-    check(_lib.lib().stm_conv_pack_weights_kxr_f32(_p(weight), _p(packed), ctypes.byref(geom), c_f(wscale), _stream()),
-          "stm_conv_pack_weights_kxr_f32")
+    call("stm_conv_pack_weights_kxr_f32", _p(weight), _p(packed), ctypes.byref(geom), wscale, _stream())
     return packed, 1.0 / wscale
 
 
@@ -1355,9 +1289,9 @@ def chain_pack_tail(w3, w1_next=None, wds=None):
     packed = torch.zeros(L.stm_chain_tail_weight_bytes_proj() if wds is not None else L.stm_chain_tail_weight_bytes(), device=w3.device, dtype=torch.uint8)
     pw1 = _p(w1_next) if w1_next is not None else None
     if wds is not None:
-        check(L.stm_chain_pack_tail_proj_f32(_p(w3), _p(wds), pw1, _p(packed), c_f(ws3), c_f(ws1), _stream()), "stm_chain_pack_tail_proj_f32")
+        call("stm_chain_pack_tail_proj_f32", _p(w3), _p(wds), pw1, _p(packed), ws3, ws1, _stream())
     else:
-        check(L.stm_chain_pack_tail_f32(_p(w3), pw1, _p(packed), c_f(ws3), c_f(ws1), _stream()), "stm_chain_pack_tail_f32")
+        call("stm_chain_pack_tail_f32", _p(w3), pw1, _p(packed), ws3, ws1, _stream())
     return packed, 1.0 / ws3, 1.0 / ws1
 
 
@@ -1377,11 +1311,9 @@ def bottleneck_chain(mid1, x, w2_packed, tail_packed, b2, b3, b1_next, scales, B
     if want_z and z is None:
         z = torch.empty(2, 2, n, 32, device=mid1.device, dtype=torch.float16)
     s2, s3, s1 = scales
-    fn = _lib.lib().stm_bottleneck_chain_proj_f32 if proj else _lib.lib().stm_bottleneck_chain_f32
-    check(fn(_p(mid1), _p(x), _p(y), _p(z) if want_z else None, _p(w2_packed), _p(tail_packed),
-             _p(b2) if b2 is not None else None, _p(b3) if b3 is not None else None,
-             _p(b1_next) if (want_z and b1_next is not None) else None, c_f(s2), c_f(s3), c_f(s1),
-             c_i(B), c_i(H), c_i(W), _stream()), "stm_bottleneck_chain_proj_f32" if proj else "stm_bottleneck_chain_f32")
+    call("stm_bottleneck_chain_proj_f32" if proj else "stm_bottleneck_chain_f32", _p(mid1), _p(x), _p(y), _p(z) if want_z else None, _p(w2_packed),
+         _p(tail_packed), _p(b2) if b2 is not None else None, _p(b3) if b3 is not None else None,
+         _p(b1_next) if (want_z and b1_next is not None) else None, s2, s3, s1, B, H, W, _stream())
     return y, (z if want_z else None)
 
 
@@ -1410,7 +1342,7 @@ def split_planes(x, fmt=0):
     if C % 32:
         raise StmError(f"split_planes: channel count {C} is not a multiple of 32")
     planes = _empty_planes(fmt, C // 32, N, x.device)
-    check(_lib.lib().stm_split_planes_fmt_f32(_p(x), _p(planes), c_l(N), c_i(C), c_i(fmt), _stream()), "stm_split_planes_fmt_f32")
+    call("stm_split_planes_fmt_f32", _p(x), _p(planes), N, C, fmt, _stream())
     return planes
 
 
@@ -1427,7 +1359,7 @@ def planar_range_flag():
     if flag is None:
         flag = torch.zeros(1, device=f"cuda:{dev}", dtype=torch.int32)
         with torch.cuda.device(dev):         # the library keeps one flag per device: register on the device that owns it
-            check(_lib.lib().stm_planar_set_range_flag(_p(flag)), "stm_planar_set_range_flag")
+            call("stm_planar_set_range_flag", _p(flag))
         _range_flags[dev] = flag
     return flag
 
@@ -1497,10 +1429,9 @@ def gather_detections(idx, cls, score, box, cnt, mask_coeff, track, centerness, 
            "mask_coeff": torch.empty(D, mdim, device=dev), "track": torch.empty(D, edim, device=dev), "centerness": torch.empty(D, device=dev),
            "clip": torch.empty(D, dtype=torch.int32, device=dev)}
     cen = _f32c(centerness.reshape(B, N)) if centerness is not None else None
-    check(_lib.lib().stm_gather_detections_f32(_p(idx), _p(cls), _p(_f32c(score)), _p(_f32c(box)), _p(cnt), _p(_f32c(mask_coeff)), _p(_f32c(track)),
-                                               _p(cen), c_i(B), c_i(top_k), c_i(N), c_i(mdim), c_i(edim), c_i(D), _p(out["box"]), _p(out["class"]),
-                                               _p(out["score"]), _p(out["mask_coeff"]), _p(out["track"]), _p(out["centerness"]), _p(out["clip"]),
-                                               _stream()), "stm_gather_detections_f32")
+    call("stm_gather_detections_f32", _p(idx), _p(cls), _p(_f32c(score)), _p(_f32c(box)), _p(cnt), _p(_f32c(mask_coeff)), _p(_f32c(track)), _p(cen),
+         B, top_k, N, mdim, edim, D, _p(out["box"]), _p(out["class"]), _p(out["score"]), _p(out["mask_coeff"]), _p(out["track"]),
+         _p(out["centerness"]), _p(out["clip"]), _stream())
     return out
 
 
@@ -1509,7 +1440,7 @@ def shift_rois(box, clip, feat_h, feat_w):
     _dev(box, clip)
     n = box.shape[0]
     rois = torch.empty(n, 5, device=box.device)
-    check(_lib.lib().stm_shift_rois_f32(_p(_f32c(box)), _p(clip), _p(rois), c_i(n), c_i(feat_h), c_i(feat_w), _stream()), "stm_shift_rois_f32")
+    call("stm_shift_rois_f32", _p(_f32c(box)), _p(clip), _p(rois), n, feat_h, feat_w, _stream())
     return rois
 
 
@@ -1519,8 +1450,8 @@ def shift_apply_(loc_shift, coeff_shift, box, mask_coeff, score, decay=0.95):
     for t in (box, mask_coeff, score):
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise StmError("shift_apply_: box / mask_coeff / score must be contiguous fp32 (modified in place)")
-    check(_lib.lib().stm_shift_apply_f32(_p(_f32c(loc_shift)), _p(_f32c(coeff_shift)), _p(box), _p(mask_coeff), _p(score), c_i(box.shape[0]),
-                                         c_i(mask_coeff.shape[1]), c_f(decay), _stream()), "stm_shift_apply_f32")
+    call("stm_shift_apply_f32", _p(_f32c(loc_shift)), _p(_f32c(coeff_shift)), _p(box), _p(mask_coeff), _p(score), box.shape[0], mask_coeff.shape[1],
+         decay, _stream())
 
 
 def match_scores(cos, miou, det_box, prev_box, det_score, det_cls, prev_cls, det_clip, prev_offsets, match_coeff, dummy_iou=0.3):
@@ -1529,9 +1460,8 @@ def match_scores(cos, miou, det_box, prev_box, det_score, det_cls, prev_cls, det
     D, Pn = det_box.shape[0], prev_box.shape[0]
     match = torch.empty(D, dtype=torch.int32, device=det_box.device)
     c4 = (ctypes.c_float * 4)(*[float(v) for v in match_coeff])
-    check(_lib.lib().stm_match_scores_f32(_p(_f32c(cos)), _p(_f32c(miou)), _p(_f32c(det_box)), _p(_f32c(prev_box)), _p(_f32c(det_score)),
-                                          _p(det_cls), _p(prev_cls), _p(det_clip), _p(prev_offsets), c_i(D), c_i(Pn), c4, c_f(dummy_iou),
-                                          _p(match), _stream()), "stm_match_scores_f32")
+    call("stm_match_scores_f32", _p(_f32c(cos)), _p(_f32c(miou)), _p(_f32c(det_box)), _p(_f32c(prev_box)), _p(_f32c(det_score)), _p(det_cls),
+         _p(prev_cls), _p(det_clip), _p(prev_offsets), D, Pn, c4, dummy_iou, _p(match), _stream())
     return match
 
 
@@ -1543,10 +1473,9 @@ def match_scores_embed(det_track, prev_track, miou, det_box, prev_box, det_score
     D, Pn = det_box.shape[0], prev_box.shape[0]
     match = torch.empty(D, dtype=torch.int32, device=det_box.device)
     c4 = (ctypes.c_float * 4)(*[float(v) for v in match_coeff])
-    check(_lib.lib().stm_match_scores_embed_f32(_p(_f32c(det_track)), _p(_f32c(prev_track)), c_i(det_track.shape[1]), _p(_f32c(miou)),
-                                                _p(_f32c(det_box)), _p(_f32c(prev_box)), _p(_f32c(det_score)), _p(det_cls), _p(prev_cls),
-                                                _p(det_clip), _p(prev_offsets), c_i(D), c_i(Pn), c4, c_f(dummy_iou), _p(match), _stream()),
-          "stm_match_scores_embed_f32")
+    call("stm_match_scores_embed_f32", _p(_f32c(det_track)), _p(_f32c(prev_track)), det_track.shape[1], _p(_f32c(miou)), _p(_f32c(det_box)),
+         _p(_f32c(prev_box)), _p(_f32c(det_score)), _p(det_cls), _p(prev_cls), _p(det_clip), _p(prev_offsets), D, Pn, c4, dummy_iou, _p(match),
+         _stream())
     return match
 
 
@@ -1566,7 +1495,7 @@ def gather_rows2(a_rows, b_rows, plan, n_a):
         pb = (ctypes.c_void_p * n)(*[t.data_ptr() for t in bb])
         po = (ctypes.c_void_p * n)(*[t.data_ptr() for t in oo])
         prb = (ctypes.c_int * n)(*rb)
-        check(_lib.lib().stm_gather_rows2(pa, pb, po, prb, c_i(n), _p(plan), c_i(R), c_i(n_a), _stream()), "stm_gather_rows2")
+        call("stm_gather_rows2", pa, pb, po, prb, n, _p(plan), R, n_a, _stream())
         outs += oo
     return outs
 
@@ -1578,9 +1507,8 @@ def pack_tracked(mask, score, tracked, offsets, box, cls, mask_coeff, B, top_k, 
     out = torch.empty(B, top_k, cols, device=offsets.device, dtype=torch.float32)
     keep = torch.empty(max(n, 1), dtype=torch.int32, device=offsets.device)
     hw = mask[0].numel() if n else 1
-    check(_lib.lib().stm_pack_tracked_f32(_p(_f32c(mask)) if n else c_p(0), _p(score), _p(tracked), _p(offsets), _p(box), _p(cls), _p(mask_coeff),
-                                          c_i(n), c_i(hw), c_i(B), c_i(top_k), c_i(cols), c_i(mask_coeff.shape[1] if n else cols - 8), c_i(max_age),
-                                          c_f(score_thr), _p(keep), _p(out), _stream()), "stm_pack_tracked_f32")
+    call("stm_pack_tracked_f32", _p(_f32c(mask)) if n else c_p(0), _p(score), _p(tracked), _p(offsets), _p(box), _p(cls), _p(mask_coeff), n, hw, B,
+         top_k, cols, mask_coeff.shape[1] if n else cols - 8, max_age, score_thr, _p(keep), _p(out), _stream())
     return out
 
 
@@ -1592,10 +1520,8 @@ def pack_tracked_bits(bits, score, tracked, offsets, box, cls, mask_coeff, B, to
     keep = torch.empty(max(n, 1), dtype=torch.int32, device=offsets.device)
     if n and (bits.dtype != torch.int64 or bits.shape[0] != n or not bits.is_contiguous()):
         raise StmError("pack_tracked_bits: bits must be contiguous int64 words [n, words]")
-    check(_lib.lib().stm_pack_tracked_bits_f32(_p(bits) if n else c_p(0), c_i(bits.shape[1] if n else 1), _p(score), _p(tracked), _p(offsets), _p(box),
-                                               _p(cls), _p(mask_coeff), c_i(n), c_i(B), c_i(top_k), c_i(cols),
-                                               c_i(mask_coeff.shape[1] if n else cols - 8), c_i(max_age), c_f(score_thr), _p(keep), _p(out), _stream()),
-          "stm_pack_tracked_bits_f32")
+    call("stm_pack_tracked_bits_f32", _p(bits) if n else c_p(0), bits.shape[1] if n else 1, _p(score), _p(tracked), _p(offsets), _p(box), _p(cls),
+         _p(mask_coeff), n, B, top_k, cols, mask_coeff.shape[1] if n else cols - 8, max_age, score_thr, _p(keep), _p(out), _stream())
     return out
 
 
@@ -1609,8 +1535,7 @@ def resize_bilinear_planes(x_nhwc, size, fmt=0):
     if C % 32:
         raise StmError(f"resize_bilinear_planes: channel count {C} is not a multiple of 32")
     planes = _empty_planes(fmt, C // 32, B * Ho * Wo, x.device)
-    check(_lib.lib().stm_resize_bilinear_planes_f32(_p(x), _p(planes), c_i(B), c_i(H), c_i(W), c_i(C), c_i(Ho), c_i(Wo), c_i(fmt), _stream()),
-          "stm_resize_bilinear_planes_f32")
+    call("stm_resize_bilinear_planes_f32", _p(x), _p(planes), B, H, W, C, Ho, Wo, fmt, _stream())
     return planes
 
 
@@ -1624,8 +1549,7 @@ def bias_relu_maxpool_planes(x_nhwc, bias, fmt=0):
         raise StmError(f"bias_relu_maxpool_planes: channel count {C} is not a multiple of 32")
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     planes = _empty_planes(fmt, C // 32, B * Ho * Wo, x.device)
-    check(_lib.lib().stm_bias_relu_maxpool_planes_f32(_p(x), _p(_f32c(bias)) if bias is not None else c_p(0), _p(planes), c_i(B), c_i(H), c_i(W),
-                                                      c_i(C), c_i(fmt), _stream()), "stm_bias_relu_maxpool_planes_f32")
+    call("stm_bias_relu_maxpool_planes_f32", _p(x), _p(_f32c(bias)) if bias is not None else c_p(0), _p(planes), B, H, W, C, fmt, _stream())
     return planes, (Ho, Wo)
 
 
@@ -1644,9 +1568,8 @@ def roi_align_planes(t2s_prev_nhwc, t2s_nhwc, corr, rois, output_size=7, fmt=0, 
     cpad = -(-(2 * C1 + Cc) // 32) * 32
     planes = _empty_planes(fmt, cpad // 32, n * ph * pw, a.device)
     if n:
-        check(_lib.lib().stm_roi_align_planes_nhwc_f32(_p(a), _p(b), _p(c), c_i(c.shape[3] if corr_nhwc else 0), _p(rois), _p(planes), c_i(B),
-                                                       c_i(H), c_i(W), c_i(C1), c_i(Cc), c_i(n), c_i(ph), c_i(pw), c_i(fmt), _stream()),
-              "stm_roi_align_planes_f32")
+        call("stm_roi_align_planes_nhwc_f32", _p(a), _p(b), _p(c), c.shape[3] if corr_nhwc else 0, _p(rois), _p(planes), B, H, W, C1, Cc, n, ph, pw,
+             fmt, _stream())
     return planes
 
 
@@ -1658,8 +1581,7 @@ def stem_rows_planes(x_nhwc, kw, sw, pw, fmt=0):
     B, H, W, Cin = x.shape
     Wo = (W + 2 * pw - kw) // sw + 1
     planes = _empty_planes(fmt, 1, B * H * Wo, x.device)
-    check(_lib.lib().stm_stem_rows_planes_f32(_p(x), _p(planes), c_i(B), c_i(H), c_i(W), c_i(Cin), c_i(kw), c_i(sw), c_i(pw), c_i(fmt),
-                                              _stream()), "stm_stem_rows_planes_f32")
+    call("stm_stem_rows_planes_f32", _p(x), _p(planes), B, H, W, Cin, kw, sw, pw, fmt, _stream())
     return planes, Wo
 
 
@@ -1668,14 +1590,14 @@ def stem_pack_weights(weight, fmt):
     _dev(weight)
     weight = _f32c(weight)
     O = weight.shape[0]
-    nbytes = _lib.lib().stm_stem_packed_weight_bytes(c_i(O), c_i(fmt))
+    nbytes = _lib.lib().stm_stem_packed_weight_bytes(O, fmt)
     if nbytes == 0 or tuple(weight.shape[1:]) != (3, 7, 7):
         raise StmError(f"stem_pack_weights: unsupported stem {tuple(weight.shape)} / format {fmt}")
     import math
     wmax = float(weight.abs().max())
     wscale = 2.0 ** (10 - math.floor(math.log2(wmax))) if wmax > 0 else 1.0
     packed = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
-    check(_lib.lib().stm_stem_pack_weights_f32(_p(weight), _p(packed), c_i(O), c_i(fmt), c_f(wscale), _stream()), "stm_stem_pack_weights_f32")
+    call("stm_stem_pack_weights_f32", _p(weight), _p(packed), O, fmt, wscale, _stream())
     return packed, 1.0 / wscale
 
 
@@ -1691,8 +1613,8 @@ def stem_fused(x_nhwc, packed, out_scale, bias, fmt, out_fmt=None):
     Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
     planes = _empty_planes(out_fmt, 2, B * Hp * Wp, x.device)
-    check(_lib.lib().stm_stem_fused_f32(_p(x), _p(packed), _p(_f32c(bias)) if bias is not None else c_p(0), _p(planes), c_i(B), c_i(H), c_i(W),
-                                        c_i(64), c_i(fmt), c_i(out_fmt), c_f(out_scale), _stream()), "stm_stem_fused_f32")
+    call("stm_stem_fused_f32", _p(x), _p(packed), _p(_f32c(bias)) if bias is not None else c_p(0), _p(planes), B, H, W, 64, fmt, out_fmt, out_scale,
+         _stream())
     return planes, (Hp, Wp)
 
 
@@ -1741,9 +1663,8 @@ def conv2d_planar(xp, packed, weight_shape, hw, bias=None, residual=None, stride
                 raise StmError(f"conv2d_planar: residual has {r32.numel()} elements, output {M * O}")
     g = _lib.ConvGeom(B, H, W, C, Ho, Wo, O, kh, kw, sh, sw, ph, pw, 0, 0, 0, planes)
     g.tile_n, g.fmt, g.out_scale = tile_n, fmt, out_scale
-    check(_lib.lib().stm_conv2d_planar_f32(_p(xp), _p(packed), _p(_f32c(bias) if bias is not None else None), _p(r32), _p(rpl),
-                                           _p(y32), _p(ypl), ctypes.byref(g), c_i(1 if relu else 0), _stream()),
-          "stm_conv2d_planar_f32")
+    call("stm_conv2d_planar_f32", _p(xp), _p(packed), _p(_f32c(bias) if bias is not None else None), _p(r32), _p(rpl), _p(y32), _p(ypl),
+         ctypes.byref(g), 1 if relu else 0, _stream())
     return (y32, ypl) if out == "both" else (y32 if out == "f32" else ypl)
 
 
@@ -1759,8 +1680,7 @@ def preprocess_frames(img_u8, size=(640, 360), divisor=32, mean=(123.675, 116.28
     Hp, Wp = -(-h // divisor) * divisor, -(-w // divisor) * divisor
     out = torch.empty(n, 3, Hp, Wp, device=img.device, dtype=torch.float32)
     m3, s3 = (ctypes.c_double * 3)(*mean), (ctypes.c_double * 3)(*std)
-    check(_lib.lib().stm_preprocess_u8_f32(_p(img), _p(out), c_i(n), c_i(H0), c_i(W0), c_i(h), c_i(w), c_i(Hp), c_i(Wp), m3, s3,
-                                           c_i(mode), _stream()), "stm_preprocess_u8_f32")
+    call("stm_preprocess_u8_f32", _p(img), _p(out), n, H0, W0, h, w, Hp, Wp, m3, s3, mode, _stream())
     return out
 
 
@@ -1790,8 +1710,7 @@ def preprocess_frames_multi(frames, out=None, size=(640, 360), divisor=32, mean=
     elif out.dtype != torch.float32 or tuple(out.shape) != (n, 3, Hp, Wp) or not out.is_contiguous() or out.device != dev:
         raise StmError(f"preprocess_frames_multi: out must be contiguous fp32 {(n, 3, Hp, Wp)} on {dev}, got {out.dtype} {tuple(out.shape)}")
     m3, s3 = (ctypes.c_double * 3)(*mean), (ctypes.c_double * 3)(*std)
-    check(_lib.lib().stm_preprocess_u8_multi_f32(desc, c_i(n), _p(out), c_i(h), c_i(w), c_i(Hp), c_i(Wp), m3, s3, c_i(mode), _stream()),
-          "stm_preprocess_u8_multi_f32")
+    call("stm_preprocess_u8_multi_f32", desc, n, _p(out), h, w, Hp, Wp, m3, s3, mode, _stream())
     return out
 
 
@@ -1801,13 +1720,7 @@ def head_assemble(small, trk, B, sizes, n_cls, mask_dim, embed_dim, group_pad):
     -> conf [B,N,n_cls], loc [B,N,4], mask [B,N,mask_dim], track [B,N,embed] (normalised), centerness [B,N,1] (tanh)."""
     _dev(*small, *trk)
     K = len(small)
-    L = _lib.HeadLayout()
-    L.B, L.K, L.n_levels, L.n_cls, L.mask_dim, L.embed_dim, L.group_pad = B, K, len(sizes), n_cls, mask_dim, embed_dim, group_pad
-    L.small_ld, L.trk_ld = small[0].shape[-1], trk[0].shape[-1]
-    start = 0
-    for l, (h, w) in enumerate(sizes):
-        L.lvl_start[l], L.lvl_hw[l] = start, h * w
-        start += B * h * w
+    L, start = _head_layout(B, K, sizes, n_cls, mask_dim, embed_dim, group_pad, small[0].shape[-1], trk[0].shape[-1])
     N = K * sum(h * w for h, w in sizes)
     for t in list(small) + list(trk):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[0] != start:
@@ -1818,10 +1731,7 @@ def head_assemble(small, trk, B, sizes, n_cls, mask_dim, embed_dim, group_pad):
     mask = torch.empty(B, N, mask_dim, device=dev)
     track = torch.empty(B, N, embed_dim, device=dev)
     cen = torch.empty(B, N, 1, device=dev)
-    sp = (ctypes.c_void_p * 4)(*([t.data_ptr() for t in small] + [0] * (4 - K)))
-    tp = (ctypes.c_void_p * 4)(*([t.data_ptr() for t in trk] + [0] * (4 - K)))
-    check(_lib.lib().stm_head_assemble_f32(sp, tp, ctypes.byref(L), _p(conf), _p(loc), _p(mask), _p(track), _p(cen), _stream()),
-          "stm_head_assemble_f32")
+    call("stm_head_assemble_f32", _ptr4(small), _ptr4(trk), ctypes.byref(L), _p(conf), _p(loc), _p(mask), _p(track), _p(cen), _stream())
     return conf, loc, mask, track, cen
 
 
@@ -1832,7 +1742,7 @@ HEAD_CTL_GATE_POS = 7
 
 def conv_set_pixel_gate(ctl, index):
     """The next planar convolution launch of this thread runs only the pixel tiles below the device int ctl[index] (stm_conv_set_pixel_gate)."""
-    _lib.lib().stm_conv_set_pixel_gate(ctypes.c_void_p(ctl.data_ptr() + 4 * index))
+    _lib.lib().stm_conv_set_pixel_gate(ctl.data_ptr() + 4 * index)
 
 
 def _level_arrays(B, sizes):
@@ -1844,6 +1754,18 @@ def _level_arrays(B, sizes):
         start += B * h * w
     st[n] = start
     return n, st, hh, ww, start
+
+
+def _head_layout(B, K, sizes, n_cls, mask_dim, embed_dim, group_pad, small_ld, trk_ld):
+    """HeadLayout of K kernel shapes over the concatenated levels `sizes` with B images each, and the pixels of all levels."""
+    L = _lib.HeadLayout()
+    L.B, L.K, L.n_levels, L.n_cls, L.mask_dim, L.embed_dim, L.group_pad = B, K, len(sizes), n_cls, mask_dim, embed_dim, group_pad
+    L.small_ld, L.trk_ld = small_ld, trk_ld
+    start = 0
+    for l, (h, w) in enumerate(sizes):
+        L.lvl_start[l], L.lvl_hw[l] = start, h * w
+        start += B * h * w
+    return L, start
 
 
 def _ptr4(ts):
@@ -1864,9 +1786,8 @@ def head_candidates(cls_logits, n_cls, conf_thresh, capacity, patch_pixels_a, pa
     lst = torch.empty(capacity, dtype=torch.int32, device=dev)
     ctl = torch.empty(HEAD_CTL_INTS, dtype=torch.int32, device=dev)
     flags = torch.empty(n_px, dtype=torch.int32, device=dev)
-    check(_lib.lib().stm_head_candidates_f32(_ptr4(cls_logits), c_i(len(cls_logits)), c_i(ld), c_i(n_cls), c_f(conf_thresh), c_i(capacity),
-                                             c_i(patch_pixels_a), c_i(patch_pixels_b), c_i(n), c_i(B), st, hh, ww, _p(flags), _p(lst), _p(ctl), _stream()),
-          "stm_head_candidates_f32")
+    call("stm_head_candidates_f32", _ptr4(cls_logits), len(cls_logits), ld, n_cls, conf_thresh, capacity, patch_pixels_a, patch_pixels_b, n, B, st,
+         hh, ww, _p(flags), _p(lst), _p(ctl), _stream())
     return lst, ctl
 
 
@@ -1877,8 +1798,8 @@ def head_patch_gather(src, dst, side, capacity, B, sizes, lst, ctl):
             or not dst.is_contiguous() or tuple(dst.shape) != (src.shape[0], src.shape[1], capacity * side * side, 32)):
         raise StmError(f"head_patch_gather: planes {tuple(src.shape)} -> {tuple(dst.shape)} do not fit capacity {capacity}, side {side}")
     n, st, hh, ww, _ = _level_arrays(B, sizes)
-    check(_lib.lib().stm_head_patch_gather(_p(src), ctypes.c_longlong(src.shape[2]), _p(dst), c_i(side), c_i(src.shape[0]), c_i(src.shape[1]),
-                                           c_i(capacity), c_i(n), c_i(B), st, hh, ww, _p(lst), _p(ctl), _stream()), "stm_head_patch_gather")
+    call("stm_head_patch_gather", _p(src), src.shape[2], _p(dst), side, src.shape[0], src.shape[1], capacity, n, B, st, hh, ww, _p(lst), _p(ctl),
+         _stream())
     return dst
 
 
@@ -1888,8 +1809,7 @@ def head_patch_mask(planes, side, capacity, B, sizes, lst, ctl):
     if planes.dim() != 4 or planes.shape[3] != 32 or planes.element_size() != 2 or not planes.is_contiguous() or planes.shape[2] != capacity * side * side:
         raise StmError(f"head_patch_mask: planes {tuple(planes.shape)} do not fit capacity {capacity}, side {side}")
     n, st, hh, ww, _ = _level_arrays(B, sizes)
-    check(_lib.lib().stm_head_patch_mask(_p(planes), c_i(side), c_i(planes.shape[0]), c_i(planes.shape[1]), c_i(capacity), c_i(n), c_i(B), st, hh, ww,
-                                         _p(lst), _p(ctl), _stream()), "stm_head_patch_mask")
+    call("stm_head_patch_mask", _p(planes), side, planes.shape[0], planes.shape[1], capacity, n, B, st, hh, ww, _p(lst), _p(ctl), _stream())
     return planes
 
 
@@ -1899,13 +1819,7 @@ def head_assemble_sparse(cls_logits, small, trk, small_dense, trk_dense, B, size
     rows of the listed pixels only (every row after an overflow), the other rows are NOT written."""
     _dev(*cls_logits, *small, *trk, *small_dense, *trk_dense)
     K = len(cls_logits)
-    L = _lib.HeadLayout()
-    L.B, L.K, L.n_levels, L.n_cls, L.mask_dim, L.embed_dim, L.group_pad = B, K, len(sizes), n_cls, mask_dim, embed_dim, group_pad
-    L.small_ld, L.trk_ld = small[0].shape[-1], trk[0].shape[-1]
-    start = 0
-    for l, (h, w) in enumerate(sizes):
-        L.lvl_start[l], L.lvl_hw[l] = start, h * w
-        start += B * h * w
+    L, start = _head_layout(B, K, sizes, n_cls, mask_dim, embed_dim, group_pad, small[0].shape[-1], trk[0].shape[-1])
     N = K * sum(h * w for h, w in sizes)
     for t in list(cls_logits) + list(small_dense) + list(trk_dense):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[0] != start:
@@ -1919,9 +1833,8 @@ def head_assemble_sparse(cls_logits, small, trk, small_dense, trk_dense, B, size
     mask = torch.empty(B, N, mask_dim, device=dev)
     track = torch.empty(B, N, embed_dim, device=dev)
     cen = torch.empty(B, N, 1, device=dev)
-    check(_lib.lib().stm_head_assemble_sparse_f32(_ptr4(cls_logits), c_i(cls_logits[0].shape[-1]), _ptr4(small), _ptr4(trk), _ptr4(small_dense), _ptr4(trk_dense),
-                                                  ctypes.byref(L), c_i(row_mul), c_i(row_add), _p(lst), _p(ctl), c_i(capacity), _p(conf), _p(loc), _p(mask),
-                                                  _p(track), _p(cen), _stream()), "stm_head_assemble_sparse_f32")
+    call("stm_head_assemble_sparse_f32", _ptr4(cls_logits), cls_logits[0].shape[-1], _ptr4(small), _ptr4(trk), _ptr4(small_dense), _ptr4(trk_dense),
+         ctypes.byref(L), row_mul, row_add, _p(lst), _p(ctl), capacity, _p(conf), _p(loc), _p(mask), _p(track), _p(cen), _stream())
     return conf, loc, mask, track, cen
 
 
@@ -1930,7 +1843,7 @@ def deform_conv_fused_supported(C, O, kernel_size, has_mask, fmt, deformable_gro
     O % 128 == 0, an fp16 plane format)."""
     kh, kw = _pair(kernel_size)
     g = DeformGeom(1, C, 8, 8, kh, kw, 1, 1, kh // 2, kw // 2, 1, 1, deformable_groups, 8, 8)
-    return bool(_lib.lib().stm_deform_conv_fused_planar_supported(ctypes.byref(g), c_i(O), c_i(1 if has_mask else 0), c_i(fmt)))
+    return bool(_lib.lib().stm_deform_conv_fused_planar_supported(ctypes.byref(g), O, 1 if has_mask else 0, fmt))
 
 
 def deform_conv_fused_tiles(B, Ho, Wo, O):
@@ -1984,10 +1897,8 @@ def deform_conv_fused_planar(x_pix, B, H, W, C, om, packed, out_scale, bias, O, 
     if timing is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    check(_lib.lib().stm_deform_conv_fused_planar_f32(_p(x_pix), c_i(x_pix.stride(0)), _p(om), c_i(om.shape[1]), c_i(1 if has_mask else 0), _p(packed),
-                                                      _p(bias), _p(out), c_i(out.shape[2]), c_i(out_off), c_l(0), c_i(O), c_i(1 if relu else 0),
-                                                      c_f(out_scale), ctypes.byref(g), c_i(fmt), c_i(out_fmt), _stream()),
-          "stm_deform_conv_fused_planar_f32")
+    call("stm_deform_conv_fused_planar_f32", _p(x_pix), x_pix.stride(0), _p(om), om.shape[1], 1 if has_mask else 0, _p(packed), _p(bias), _p(out),
+         out.shape[2], out_off, 0, O, 1 if relu else 0, out_scale, ctypes.byref(g), fmt, out_fmt, _stream())
     if timing is not None:
         e1.record()
         # SURVEY.md section 8(d), fused form: input once, offsets (+ mask) per output pixel, output planes, weights (as packed planes); no columns
@@ -2015,8 +1926,7 @@ def dcn_sample_planar(x_nhwc, om, stride=1, padding=1, dilation=1, fmt=0):
     if timing is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    check(_lib.lib().stm_dcn_sample_planar_fmt_f32(_p(x), _p(om), c_i(om.shape[1]), _p(out), c_i(M), c_l(0), ctypes.byref(g),
-                                                   c_i(fmt), _stream()), "stm_dcn_sample_planar_fmt_f32")
+    call("stm_dcn_sample_planar_fmt_f32", _p(x), _p(om), om.shape[1], _p(out), M, 0, ctypes.byref(g), fmt, _stream())
     if timing is not None:
         e1.record()
         # algorithmic bytes: input once, 27 offset/mask values per output pixel, columns as planes (6 or 4 B / element)

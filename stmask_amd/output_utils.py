@@ -61,12 +61,13 @@ def rle_strings(counts_host, n_runs_host):
     while True:
         out = np.empty((n, out_ld), dtype=np.uint8)
         lens = np.empty(n, dtype=np.int32)
-        rc = _lib.lib().stm_rle_strings_host(c.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(width), nr.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(n),
-                                             out.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(out_ld), lens.ctypes.data_as(ctypes.c_void_p))
-        if rc == 0:
+        try:
+            _lib.call("stm_rle_strings_host", c.ctypes.data_as(ctypes.c_void_p), width, nr.ctypes.data_as(ctypes.c_void_p), n,
+                      out.ctypes.data_as(ctypes.c_void_p), out_ld, lens.ctypes.data_as(ctypes.c_void_p))
             break
-        if int(lens.max()) <= out_ld:
-            _lib.check(rc, "stm_rle_strings_host")
+        except _lib.StmError:
+            if int(lens.max()) <= out_ld:
+                raise
         out_ld = int(lens.max())
     return [out[i, :lens[i]].tobytes() for i in range(n)]
 

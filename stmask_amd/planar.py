@@ -22,11 +22,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
-from ._lib import StmError, c_i, check
-
-
-def _pair(v):
-    return (v, v) if isinstance(v, int) else tuple(v)
+from ._lib import StmError, call
+from .ops import _pair
 
 
 # Plane format of the graphs built next (fuse.optimize_for_inference sets it): 0 = three bf16 planes, six MFMA products per
@@ -265,9 +262,7 @@ class PlanarConv:
             packed, g.out_scale = self._packed["kxr"]
             if gate is not None:
                 ops.conv_set_pixel_gate(*gate)
-            rc = _lib.lib().stm_conv2d_planar_kxr_f32(ctypes.c_void_p(x_ptr), ops._p(packed), ops._p(self.bias), ctypes.c_void_p(p_f32),
-                                                      ctypes.c_void_p(p_pl), ctypes.byref(g), c_i(1 if self.relu else 0), ops._stream())
-            check(rc, "stm_conv2d_planar_kxr_f32")
+            call("stm_conv2d_planar_kxr_f32", x_ptr, ops._p(packed), ops._p(self.bias), p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0, ops._stream())
             return self._finish(timing, e0 if timing is not None else None, M, shape, g, NP, NPo, dt, out, out_f32, out_planes, residual)
         packed = self.packed(g.tile_n)                     # (sets self.out_scale for the fp16 format)
         g.fmt, g.out_scale = self.fmt, self.out_scale
@@ -281,19 +276,11 @@ class PlanarConv:
             p2, H2, W2, s2 = x2
             if p2.dtype != dt or p2.dim() != 4 or p2.shape[0] < NP or p2.shape[3] != 32 or not p2.is_contiguous() or shape[0] != "img":
                 raise StmError("PlanarConv: the second source must be contiguous planes of this layer's format over one image size")
-            rc = _lib.lib().stm_conv2d_planar_dual_f32(ctypes.c_void_p(x_ptr), ops._p(p2), c_i(p2.shape[1] * 32), c_i(H2), c_i(W2), c_i(s2),
-                                                       ctypes.c_longlong(p2.shape[2]), ctypes.c_longlong(p2.shape[1] * p2.shape[2] * 32),
-                                                       ops._p(packed), ops._p(self.bias), ctypes.c_void_p(r32), ctypes.c_void_p(rpl),
-                                                       ctypes.c_void_p(p_f32), ctypes.c_void_p(p_pl), ctypes.byref(g), c_i(1 if self.relu else 0),
-                                                       ops._p(ws), ctypes.c_size_t(ws.numel()), ops._stream())
-            check(rc, "stm_conv2d_planar_dual_f32")
+            call("stm_conv2d_planar_dual_f32", x_ptr, ops._p(p2), p2.shape[1] * 32, H2, W2, s2, p2.shape[2], p2.shape[1] * p2.shape[2] * 32,
+                 ops._p(packed), ops._p(self.bias), r32, rpl, p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0, ops._p(ws), ws.numel(), ops._stream())
             return self._finish(timing, e0 if timing is not None else None, M, shape, g, NP, NPo, dt, out, out_f32, out_planes, residual)
-        rc = _lib.lib().stm_conv2d_planar_ws_f32(ctypes.c_void_p(x_ptr), ops._p(packed),
-                                                 ops._p(self.bias), ctypes.c_void_p(r32), ctypes.c_void_p(rpl),
-                                                 ctypes.c_void_p(p_f32), ctypes.c_void_p(p_pl), ctypes.byref(g),
-                                                 c_i(1 if self.relu else 0), ops._p(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0),
-                                                 ops._stream())
-        check(rc, "stm_conv2d_planar_f32")
+        call("stm_conv2d_planar_ws_f32", x_ptr, ops._p(packed), ops._p(self.bias), r32, rpl, p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0,
+             ops._p(ws), ws.numel() if ws is not None else 0, ops._stream())
         return self._finish(timing, e0 if timing is not None else None, M, shape, g, NP, NPo, dt, out, out_f32, out_planes, residual)
 
     def deform(self, x32, B, H, W, om, stride, padding, dilation, has_mask, out=None, out_off=0):

@@ -11,14 +11,64 @@ from conftest import ROOT
 from stmask_amd import _lib, ops
 
 
+def _header_text():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "stmask_hip.h")).read(), flags=re.S)
+
+
 def _header_symbols():
-    text = open(os.path.join(ROOT, "include", "stmask_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(stm_[a-z0-9_]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(stm_[a-z0-9_]+)\s*\(", _header_text())))
 
 
-def test_header_and_binding_list_agree():
+_C_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "long long": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p}
+
+
+def _header_prototypes():
+    """{name: (restype, [argtypes])} of every `ret stm_name(params);` of the header.  A `*` or `[` anywhere in a parameter, or the type
+    stm_stream_t, makes it a pointer; every other parameter is `type name` with type one of the six scalar kinds."""
+    protos = {}
+    for ret, name, params in re.findall(r"^[ \t]*([A-Za-z_][A-Za-z0-9_ ]*?\**)\s*\b(stm_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header_text(), flags=re.M):
+        args = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            words = p.split()
+            pointer = "*" in p or "[" in p or words[0] == "stm_stream_t"
+            args.append(ctypes.c_void_p if pointer else _C_TYPES[" ".join(words[:-1])])
+        assert name not in protos, name
+        protos[name] = (_C_TYPES[" ".join(ret.split())], args)
+    return protos
+
+
+def test_header_and_signature_table_agree():
+    """Every argument of every entry point: the table lib() takes restype / argtypes from says what include/stmask_hip.h says."""
     assert _header_symbols() == sorted(_lib.ABI_SYMBOLS)
+    assert _lib.ABI_SYMBOLS == list(_lib.SIGNATURES)
+    protos = _header_prototypes()
+    assert len(protos) == len(_lib.SIGNATURES) == 128         # a prototype the expression misses fails here instead of skipping a function
+    lib = _lib.lib()
+    for name in _lib.SIGNATURES:
+        ret, args = protos[name]
+        fn = getattr(lib, name)
+        assert fn.restype == ret, (name, fn.restype, ret)
+        assert len(fn.argtypes) == len(args), (name, len(fn.argtypes), len(args))
+        for i, (got, want) in enumerate(zip(fn.argtypes, args)):
+            assert got == want, (name, i, got, want)
+
+
+def test_counts_keep_their_width():
+    """stm_encode_boxes_f32 returns 0 for n == 0 before it looks at its pointers: a count cut to 32 bits would make 2**32 that (no launch happens)."""
+    assert _lib.lib().stm_encode_boxes_f32(None, None, None, 2**32, None) == -2
+
+
+def test_type_and_arity_errors_are_python_errors():
+    with pytest.raises(ctypes.ArgumentError):
+        _lib.lib().stm_encode_boxes_f32(None, None, None, ctypes.c_int(5), None)
+    with pytest.raises(_lib.StmError):
+        _lib.call("stm_encode_boxes_f32", None, None, None, 5)
+    with pytest.raises(_lib.StmError):
+        _lib.call("stm_encode_boxes_f32", None, None, None, 5, None, None)
+    with pytest.raises(_lib.StmError) as e:
+        _lib.call("stm_encode_boxes_f32", None, None, None, 5, None)
+    assert "stm_encode_boxes_f32" in str(e.value) and "-2" in str(e.value) and "non-NULL" in str(e.value)
 
 
 def test_library_loads_and_exports_every_symbol():

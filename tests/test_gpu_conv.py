@@ -562,7 +562,7 @@ def test_f16_entry_points_are_plane_format_2():
     cols_ref = ops.dcn_sample_planar(xs, om, 1, 1, 1, fmt=2)
     cols = torch.empty_like(cols_ref)
     dg = _lib.DeformGeom(1, 128, 8, 10, 3, 3, 1, 1, 1, 1, 1, 1, 1, 8, 10)
-    _lib.check(lib.stm_dcn_sample_planar_f16(c_p(xs.data_ptr()), c_p(om.data_ptr()), c_i(27), c_p(cols.data_ptr()), c_i(80), c_l(0), ctypes.byref(dg),
+    _lib.check(lib.stm_dcn_sample_planar_f16(c_p(xs.data_ptr()), c_p(om.data_ptr()), c_i(27), c_p(cols.data_ptr()), c_i(80), ctypes.c_longlong(0), ctypes.byref(dg),
                                              stream), "stm_dcn_sample_planar_f16")
     assert cols.shape[0] == 1 and torch.equal(cols, cols_ref)
 

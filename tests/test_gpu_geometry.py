@@ -16,7 +16,7 @@ import torch
 import geometry_cases as G
 import oracle
 from stmask_amd import _lib, ops
-from stmask_amd._lib import DeformGeom, StmError, c_f, c_i, c_l, c_p
+from stmask_amd._lib import DeformGeom, StmError, c_f, c_i, c_p
 from stmask_amd.dcn_v2 import DCN, DCNv2
 from stmask_amd.mmcv_ops import DeformConv2d, RoIAlign, roi_align
 from stmask_amd.spatial_correlation_sampler import SpatialCorrelationSampler, spatial_correlation_sample
@@ -180,7 +180,7 @@ def test_dcn_sample_planar_equals_im2col_at_unequal_pairs(c, tunables):
         f16 = torch.empty_like(planes[2])
         geo = DeformGeom(B, C, c["H"], c["W"], 3, 3, *c["st"], *c["pad"], *c["dl"], 1, Ho, Wo)
         _lib.check(_lib.lib().stm_dcn_sample_planar_f16(c_p(x_nhwc.data_ptr()), c_p(om_pix.data_ptr()), c_i(27), c_p(f16.data_ptr()), c_i(B * Ho * Wo),
-                                                        c_l(0), ctypes.byref(geo), ops._stream()), "stm_dcn_sample_planar_f16")
+                                                        ctypes.c_longlong(0), ctypes.byref(geo), ops._stream()), "stm_dcn_sample_planar_f16")
         assert torch.equal(f16, planes[2])
         tunables.set(STM_DCN_LDS="1")
         for fmt in (0, 1, 2):
@@ -367,7 +367,7 @@ def test_refusals_of_unimplemented_arguments(tunables):
     def sampler(C, k, dg, has_mask, om_ld=27):
         geo = DeformGeom(p["B"], C, p["H"], p["W"], *k, *p["st"], *p["pad"], *p["dl"], dg, Ho, Wo)
         return lib.stm_deform_sample_planar_f32(c_p(x_nhwc.data_ptr()), c_i(p["C"]), c_p(om_pix.data_ptr()), c_i(om_ld), c_i(has_mask),
-                                                c_p(planes.data_ptr()), c_i(M), c_i(0), c_l(0), ctypes.byref(geo), c_i(0), stream)
+                                                c_p(planes.data_ptr()), c_i(M), c_i(0), ctypes.c_longlong(0), ctypes.byref(geo), c_i(0), stream)
     for args, what in (((p["C"], (3, 3), 2, 1), "one deformable group"), ((p["C"], (7, 7), 1, 0), "3x3 taps"), ((p["C"], (3, 5), 1, 1), "without mask"),
                        ((p["C"], (3, 3), 1, 0), "mask-free form is built for C = 256"), ((96, (3, 3), 1, 1), "C must be 128, 256 or 512")):
         with pytest.raises(StmError, match=what):
@@ -398,7 +398,7 @@ def test_refusals_of_unimplemented_arguments(tunables):
     out = torch.zeros(2, f["O"] // 32, om_pix.shape[0], 32, device=DEV, dtype=torch.float16)
     geo = DeformGeom(f["B"], f["C"], f["H"], f["W"], 3, 3, *f["st"], *f["pad"], *f["dl"], 2, fHo, fWo)
     rc = lib.stm_deform_conv_fused_planar_f32(c_p(x_pix.data_ptr()), c_i(f["C"]), c_p(om_pix.data_ptr()), c_i(27), c_i(1), c_p(packed.data_ptr()), c_p(0),
-                                              c_p(out.data_ptr()), c_i(om_pix.shape[0]), c_i(0), c_l(0), c_i(f["O"]), c_i(0), c_f(sc), ctypes.byref(geo),
+                                              c_p(out.data_ptr()), c_i(om_pix.shape[0]), c_i(0), ctypes.c_longlong(0), c_i(f["O"]), c_i(0), c_f(sc), ctypes.byref(geo),
                                               c_i(1), c_i(1), stream)
     with pytest.raises(StmError, match="one deformable group"):
         _lib.check(rc, "stm_deform_conv_fused_planar_f32")
