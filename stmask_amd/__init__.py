@@ -7,6 +7,9 @@ Layout (DESIGN.md):
                            drop-ins for the reference's third-party imports (shims/ exposes them by name)
   layers/, backbone.py, model.py, config.py
                            host-side mirror of the reference's layer API (same names, state-dict keys)
-  pipeline.py, dist.py     batched clip pipeline and clip sharding over GPUs (RCCL all-gather of detections)
+  pipeline.py, trunk.py, track_host.py
+                           batched clip pipeline: the step and the tracker state / trunk scheduling (graph ring, side streams) /
+                           the tracker's host decisions as pure functions
+  dist.py                  clip sharding over GPUs (RCCL all-gather of detections)
 """
 __version__ = "0.1.0"

@@ -23,10 +23,12 @@ def batches():
 
 def drive(net, xs, firsts, actives):
     pipe = BatchedClipPipeline(net, 3)
+    declared = set(vars(pipe))
     out = []
     for t, x in enumerate(xs):
         y = pipe.step(x, is_first=firsts[t], active=actives[t])
         out.append((y.clone(), pipe.detections(), list(pipe.prev_n)))
+    assert set(vars(pipe)) == declared          # all state is declared in __init__: no step creates an attribute
     return out
 
 
