@@ -10,7 +10,6 @@ import torch
 import bench
 from benchlib.runner import build_net, Runner
 from stmask_amd import ops, planar
-from stmask_amd.planar import _planes_dtype
 
 args = bench.parse_args([])
 B = 32
@@ -59,9 +58,9 @@ planar.PlanarConv.__call__ = orig
 up = ups[0][1] if isinstance(ups[0], tuple) else ups[0]
 lv = ("levels", B, sizes)
 t1c, t1r, t2c, t2r, cls_l, small_l = pg._build_sparse()
-trk_l = [t for _, t in pg.finals]
+trk_l = [f.trk for f in pg.finals]
 cw, P = 256, 64
-NP, pdt = _planes_dtype(pg.fmt)
+NP, pdt = ops.plane_layout(pg.fmt)
 capn = pg.sparse_capacity(B, sizes)
 head = pg.head
 CENTER = planar.head_center_default()      # STM_HEAD_CENTER=0: the output layers over all 25 pixels of each patch map
@@ -118,7 +117,7 @@ def dense_once(record):
         marks.append((name, ev()))
     t1 = pg.tower1(up, lv, out="planes"); m("tower1")
     t2 = pg.tower2(t1, lv, out="planes"); m("tower2")
-    outs = [(s(t2, lv, out="f32"), t(t2, lv, out="f32", x_ch_off=3 * cw)) for s, t in pg.finals]; m("outputs")
+    outs = [(f.small(t2, lv, out="f32"), f.trk(t2, lv, out="f32", x_ch_off=3 * cw)) for f in pg.finals]; m("outputs")
     ops.head_assemble([o[0] for o in outs], [o[1] for o in outs], B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P); m("assemble")
     torch.cuda.synchronize()
     if record:

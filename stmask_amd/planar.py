@@ -17,6 +17,7 @@ on the track / mask branches keeps the module path for the head (FPN and proto-n
 import ctypes
 import functools
 import os
+from typing import Any, NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -35,7 +36,8 @@ FMT = 0
 BACKBONE_FMT = None
 
 # Graph-construction choices.  Plain module constants since round 6 (environment switches STM_* in rounds 2-5; every default has held since it was
-# measured -- DESIGN.md section 9 keeps the A/B figures): tests that want the other form of a layer set the attribute.
+# measured -- DESIGN.md section 9 keeps the A/B figures).  The tests reach the other form of a layer by setting FCB_PLANAR, TN_POOL, DCN_FUSED,
+# FCB_FUSED, DCN_FUSED_MIN_TILES and TRUNK_BRANCHES (and FMT); no test sets the others.
 TILE64_MAX_SLABS = 8      # K-slab limit of the short-K rule of the 128 x 64 tiles
 FCB_PLANAR = True         # FCB class branch on the planar kernels
 STEM_PLANAR = True        # stem on the planar kernels
@@ -81,8 +83,24 @@ def set_format(fmt, backbone_fmt=None):
     FMT, BACKBONE_FMT = fmt, backbone_fmt
 
 
-def _planes_dtype(fmt):
-    return ops.plane_layout(fmt)
+def _timing_start():
+    """Launch record of the live roofline (ops.conv_timing; bench.py --full), first half: the record list and the start event of the launch
+    that follows, or None with timing off -- the default, which creates no event."""
+    timing = ops._conv_timing
+    if timing is None:
+        return None
+    e0 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return timing, e0
+
+
+def _timing_stop(started, flops, key, products, role, nbytes, *issued):
+    """... second half: (start, end, algorithmic flops, layer key, MFMA products per product of the reference: 6 bf16x3 / 3 fp16x2 / 1 fp16x1,
+    role, algorithmic HBM bytes[, share of those products that is issued: the border layers' eighth field])."""
+    timing, e0 = started
+    e1 = torch.cuda.Event(enable_timing=True)
+    e1.record()
+    timing.append((e0, e1, flops, key, products, role, float(nbytes)) + issued)
 
 
 class PlanarConv:
@@ -165,7 +183,7 @@ class PlanarConv:
         kxr: True / False decides the kx-reuse kernel for a layer it supports (None: by the pixel count); splitk = False: never split K.
         window = (0, 0, 1, 1, ph, pw, 1, 1), ph / pw <= 0: ONE output pixel per image -- input (-ph + ky, -pw + kx) -- as row b of the outputs; the
         only window form the kx-reuse kernel takes (its centre-window launch; the gate then counts images)."""
-        NP, dt = _planes_dtype(self.fmt)
+        NP, dt = ops.plane_layout(self.fmt)
         if xp.dtype != dt or xp.dim() != 4 or xp.shape[0] < NP or xp.shape[3] != 32 or not xp.is_contiguous():
             raise StmError(f"PlanarConv: expected contiguous {dt} planes [{NP}, S, N, 32], got {xp.dtype} {tuple(xp.shape)}")
         # (a fp16x1 layer handed a two-plane fp16 tensor reads plane 0 = RN16(x): the one-plane tensor of the same values)
@@ -217,7 +235,7 @@ class PlanarConv:
                    and (kxr if kxr is not None else M >= (self.kxr_min_pixels if self.kxr_min_pixels is not None else self.kxr_rule_pixels())))
         g.tile_n = 0 if use_kxr else self.pick_tile(M)
         dev = xp.device
-        NPo, dto = _planes_dtype(self.out_fmt)
+        NPo, dto = ops.plane_layout(self.out_fmt)
         if window is not None and ((out in ("planes", "both") and out_planes is None) or (out in ("f32", "both") and out_f32 is None)):
             raise StmError("PlanarConv: a window launch writes into caller-provided full-size outputs")
         if out in ("planes", "both") and out_planes is None:
@@ -249,10 +267,7 @@ class PlanarConv:
             else:
                 g.res_ld = residual.shape[-1]
                 r32 = residual.data_ptr()
-        timing = ops._conv_timing
-        if timing is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        started = _timing_start()
         x_ptr = xp.data_ptr() + ((x_ch_off // 32) * N + x_off) * 64
         if use_kxr:
             g.fmt = self.fmt
@@ -263,25 +278,31 @@ class PlanarConv:
             if gate is not None:
                 ops.conv_set_pixel_gate(*gate)
             call("stm_conv2d_planar_kxr_f32", x_ptr, ops._p(packed), ops._p(self.bias), p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0, ops._stream())
-            return self._finish(timing, e0 if timing is not None else None, M, shape, g, NP, NPo, dt, out, out_f32, out_planes, residual)
-        packed = self.packed(g.tile_n)                     # (sets self.out_scale for the fp16 format)
-        g.fmt, g.out_scale = self.fmt, self.out_scale
-        g.out_fmt_plus1 = 0 if self.out_fmt == self.fmt else self.out_fmt + 1
-        ws = ops._workspace(self.SPLITK_WS_BYTES, dev, "conv_splitk") if splitk and gate is None else None     # grow-only, shared: split-K partial sums
-        if gate is not None:
+        else:
+            packed = self.packed(g.tile_n)                     # (sets self.out_scale for the fp16 format)
+            g.fmt, g.out_scale = self.fmt, self.out_scale
+            g.out_fmt_plus1 = 0 if self.out_fmt == self.fmt else self.out_fmt + 1
+            ws = ops._workspace(self.SPLITK_WS_BYTES, dev, "conv_splitk") if splitk and gate is None else None     # grow-only, shared: split-K partial sums
+            if gate is not None:
+                if x2 is not None:
+                    raise StmError("PlanarConv: gated launches take no second source")
+                ops.conv_set_pixel_gate(*gate)
             if x2 is not None:
-                raise StmError("PlanarConv: gated launches take no second source")
-            ops.conv_set_pixel_gate(*gate)
-        if x2 is not None:
-            p2, H2, W2, s2 = x2
-            if p2.dtype != dt or p2.dim() != 4 or p2.shape[0] < NP or p2.shape[3] != 32 or not p2.is_contiguous() or shape[0] != "img":
-                raise StmError("PlanarConv: the second source must be contiguous planes of this layer's format over one image size")
-            call("stm_conv2d_planar_dual_f32", x_ptr, ops._p(p2), p2.shape[1] * 32, H2, W2, s2, p2.shape[2], p2.shape[1] * p2.shape[2] * 32,
-                 ops._p(packed), ops._p(self.bias), r32, rpl, p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0, ops._p(ws), ws.numel(), ops._stream())
-            return self._finish(timing, e0 if timing is not None else None, M, shape, g, NP, NPo, dt, out, out_f32, out_planes, residual)
-        call("stm_conv2d_planar_ws_f32", x_ptr, ops._p(packed), ops._p(self.bias), r32, rpl, p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0,
-             ops._p(ws), ws.numel() if ws is not None else 0, ops._stream())
-        return self._finish(timing, e0 if timing is not None else None, M, shape, g, NP, NPo, dt, out, out_f32, out_planes, residual)
+                p2, H2, W2, s2 = x2
+                if p2.dtype != dt or p2.dim() != 4 or p2.shape[0] < NP or p2.shape[3] != 32 or not p2.is_contiguous() or shape[0] != "img":
+                    raise StmError("PlanarConv: the second source must be contiguous planes of this layer's format over one image size")
+                call("stm_conv2d_planar_dual_f32", x_ptr, ops._p(p2), p2.shape[1] * 32, H2, W2, s2, p2.shape[2], p2.shape[1] * p2.shape[2] * 32,
+                     ops._p(packed), ops._p(self.bias), r32, rpl, p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0, ops._p(ws), ws.numel(), ops._stream())
+            else:
+                call("stm_conv2d_planar_ws_f32", x_ptr, ops._p(packed), ops._p(self.bias), r32, rpl, p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0,
+                     ops._p(ws), ws.numel() if ws is not None else 0, ops._stream())
+        if started is not None:
+            # layer key: tile 0 = the kx-reuse kernel
+            _timing_stop(started, 2.0 * M * self.O * self.C * self.kh * self.kw * self.algo_frac, (M, self.C, self.O, self.kh, self.sh, self.groups, g.tile_n),
+                         {0: 6 if self.planes == 3 else 3, 1: 3, 2: 1}[self.fmt], self.role, self._algo_bytes(M, shape, NP, NPo, dt, out_f32, out_planes, residual))
+        if out == "both":
+            return out_f32, out_planes
+        return out_f32 if out == "f32" else out_planes
 
     def deform(self, x32, B, H, W, om, stride, padding, dilation, has_mask, out=None, out_off=0):
         """This layer as a DEFORMABLE convolution in one kernel (ops.deform_conv_fused_planar, csrc/dcn_fused.hip): x32 fp32 pixel-major
@@ -291,28 +312,18 @@ class PlanarConv:
         return ops.deform_conv_fused_planar(x32, B, H, W, self.C, om, packed, self.out_scale, self.bias, self.O, (self.kh, self.kw), stride, padding,
                                             dilation, has_mask=has_mask, relu=self.relu, fmt=self.fmt, out_fmt=self.out_fmt, out=out, out_off=out_off)
 
-    def _finish(self, timing, e0, M, shape, g, NP, NPo, dt, out, out_f32, out_planes, residual):
-        if timing is not None:
-            e1 = torch.cuda.Event(enable_timing=True)
-            e1.record()
-            # algorithmic HBM bytes of the launch: every input / residual / output element and every weight once, in the
-            # formats they are stored in (planes 2 B per plane and element, fp32 4 B)
-            in_px = M if shape[0] == "levels" else shape[1] * shape[2] * shape[3]
-            nbytes = in_px * self.groups * self.C * 2 * NP + self.weight.numel() * 2 * NP
-            if out_planes is not None:
-                nbytes += M * self.O * 2 * NPo
-            if out_f32 is not None:
-                nbytes += M * self.O * 4
-            if residual is not None:
-                nbytes += M * self.O * (2 * NP if residual.dtype == dt else 4)
-            # (start, end, algorithmic flops, layer key [tile 0 = the kx-reuse kernel], MFMA products per product of the reference: 6 bf16x3 /
-            # 3 fp16x2 / 1 fp16x1, role, algorithmic bytes)
-            timing.append((e0, e1, 2.0 * M * self.O * self.C * self.kh * self.kw * self.algo_frac,
-                           (M, self.C, self.O, self.kh, self.sh, self.groups, g.tile_n),
-                           {0: 6 if self.planes == 3 else 3, 1: 3, 2: 1}[self.fmt], self.role, float(nbytes)))
-        if out == "both":
-            return out_f32, out_planes
-        return out_f32 if out == "f32" else out_planes
+    def _algo_bytes(self, M, shape, NP, NPo, dt, out_f32, out_planes, residual):
+        """Algorithmic HBM bytes of a launch: every input / residual / output element and every weight once, in the formats they are stored in
+        (planes 2 B per plane and element, fp32 4 B)."""
+        in_px = M if shape[0] == "levels" else shape[1] * shape[2] * shape[3]
+        nbytes = in_px * self.groups * self.C * 2 * NP + self.weight.numel() * 2 * NP
+        if out_planes is not None:
+            nbytes += M * self.O * 2 * NPo
+        if out_f32 is not None:
+            nbytes += M * self.O * 4
+        if residual is not None:
+            nbytes += M * self.O * (2 * NP if residual.dtype == dt else 4)
+        return nbytes
 
 
 def _nhwc(t):
@@ -330,6 +341,29 @@ def head_center_default():
     """STM_HEAD_CENTER (default on): the sparse head's output layers at the centre pixel of each patch map only; 0 = over the whole 5 x 5 maps.
     The one place that reads the switch, once per process."""
     return os.environ.get("STM_HEAD_CENTER", "1") != "0"
+
+
+class HeadOutputs(NamedTuple):
+    """The shared head's output layers of one kernel shape (PlanarGraph.finals).  The last four are the FCB class branch's (use_dcn_class)."""
+    small: PlanarConv                      # [conf (FCA) |] centerness+bbox | mask as one grouped launch, GROUP_PAD output channels per group
+    trk: PlanarConv                        # the track layer
+    fa: Optional[Any] = None               # FeatureAlign module of the class branch
+    fconv: Optional[PlanarConv] = None     # ... its trailing convolution (class logits)
+    adconv: Optional[PlanarConv] = None    # ... its DeformConv2d as a 1x1 product over the planar sampler's columns, where that form is built
+    adfused: Optional[PlanarConv] = None   # ... or as one kernel (csrc/dcn_fused.hip), where that one is
+
+
+class _Levels(NamedTuple):
+    """What every stage of one PlanarGraph.run call needs to know about its batch (per call, not on self: run is re-entered for other batch sizes)."""
+    B: int            # images
+    sizes: tuple      # (h, w) of P3 .. P7
+    starts: tuple     # first pixel of each level on the concatenated pixel axis, and the total
+    ntot: int         # pixels of all levels
+    dev: torch.device
+
+    @property
+    def lv(self):
+        return ("levels", self.B, self.sizes)
 
 
 class PlanarGraph:
@@ -362,6 +396,14 @@ class PlanarGraph:
         # used by any STMask config (config.py:698-701, 793-807) and keeps the module path
         self.head_planar = not (cfg.use_dcn_track or cfg.use_dcn_mask) and cfg.share_prediction_module
         self.fcb = bool(cfg.use_dcn_class)
+        # Sparse head (csrc/head_sparse.hip): set by the caller for the calls it wants it on -- BatchedClipPipeline, whose detection stage reads loc /
+        # centerness / mask_coeff / track at the priors that pass generate_candidate's class threshold only -- as (eval_conf_thresh, capacity in
+        # positions or None).  None: every branch densely (forward_single, the layer API, the per-clip pipeline).  FCA heads with one prior per
+        # kernel shape only: under FCB the class branch reads the dense box regression.
+        self.sparse = None
+        self._sparse_layers = None
+        self.sparse_ctl = self.sparse_list = None      # (tests, diagnosis: the last sparse step's counts and positions)
+        self._side = None                              # second stream of run()'s branches (_side_stream)
         if not self.head_planar:
             return
         convs = lambda seq: [m for m in seq.children() if isinstance(m, torch.nn.Conv2d)]
@@ -376,64 +418,57 @@ class PlanarGraph:
         w2 = torch.cat([t[1].weight for t in towers], 0)
         b2 = torch.cat([t[1].bias for t in towers], 0)
         self.tower2 = PlanarConv(w2, b2, 1, towers[0][1].padding, relu=True, groups=4)     # 4 x (256 -> 256)
-        # output layers, per kernel shape k: the conf / centerness+bbox / mask layers read three consecutive 256-channel
-        # groups of the tower output -> one grouped launch with 64 output channels per group (41 / 5 / 32 real ones);
-        # the track layer (128 channels) reads the fourth group -> its own launch
-        self.finals = []
-        P = self.GROUP_PAD
         self.dims = (head.num_priors * head.num_classes, head.num_priors * 4, head.num_priors * head.mask_dim,
                      head.num_priors * head.embed_dim)
-        for k in range(len(cfg.head_layer_params)):
-            mods = [[head.centerness_layer[k], head.bbox_layer[k]], [head.mask_layer[k]]]
-            if not self.fcb:
-                mods = [[head.conf_layer[k]]] + mods
-            ws, bs = [], []
-            for grp in mods:
-                w = torch.cat([m.weight for m in grp], 0)
-                b = torch.cat([m.bias for m in grp], 0)
-                assert w.shape[0] <= P
-                ws.append(F.pad(w, (0, 0, 0, 0, 0, 0, 0, P - w.shape[0])))
-                bs.append(F.pad(b, (0, P - b.shape[0])))
-            m0 = mods[0][0]
-            real = sum(m.weight.shape[0] for grp in mods for m in grp)
-            small = PlanarConv(torch.cat(ws, 0), torch.cat(bs, 0), 1, m0.padding, relu=False, groups=len(mods),
-                               algo_frac=real / (len(mods) * float(P)), tile_n=64,
-                               group_cout=[sum(m.weight.shape[0] for m in grp) for grp in mods])
-            tr = head.track_layer[k]
-            entry = [small, PlanarConv(tr.weight, tr.bias, 1, tr.padding, relu=False)]
-            if self.fcb:
-                # FeatureAlign (Featurealign.py:6-74): offsets from the box regression, DeformConv2d + ReLU on the existing
-                # deformable kernels (NCHW fp32), then its trailing conv on the planar kernel over all levels at once
-                fa = head.conf_layer[k]
-                entry.append(fa)
-                # (41 class channels in rows of 48: whole 16-channel tiles for the kx-reuse kernel; the rows land in the 64-column
-                # class group of the output buffer)
-                n_c = fa.conv.weight.shape[0]
-                n_cp = -(-n_c // 16) * 16
-                assert n_cp <= P
-                entry.append(PlanarConv(F.pad(fa.conv.weight, (0, 0, 0, 0, 0, 0, 0, n_cp - n_c)), F.pad(fa.conv.bias, (0, n_cp - n_c)), 1, fa.conv.padding,
-                                        relu=False, tile_n=64, group_cout=[n_c], algo_frac=n_c / n_cp))
-                # FeatureAlign's DeformConv2d as planar sampler (columns [pixel][tap*C + c] for all levels) + planar 1x1
-                # convolution over kh*kw*C channels (+ ReLU); offsets as one [pixels, 4] x [4, 2K] product (ada)
-                ad = fa.conv_adaption
-                O, Cin, akh, akw = ad.weight.shape
-                if ad.deform_groups == 1 and Cin == 256 and akh * akw in (9, 15):
-                    wk = ad.weight.detach().permute(0, 2, 3, 1).reshape(O, akh * akw * Cin, 1, 1)
-                    entry.append(PlanarConv(wk, None, 1, 0, relu=True))
-                    # ... or, level by level where the grid is large enough, the whole DeformConv2d + ReLU as one kernel (csrc/dcn_fused.hip)
-                    entry.append(PlanarConv(ad.weight, None, 1, fa.padding, relu=True)
-                                 if DCN_FUSED and FCB_FUSED and self.fmt in (1, 2) and ops.deform_conv_fused_supported(Cin, O, (akh, akw), False, self.fmt) else None)
-                else:
-                    entry.append(None)
-                    entry.append(None)
-            self.finals.append(tuple(entry))
+        self.finals = [self._head_outputs(head, k) for k in range(len(cfg.head_layer_params))]
         self.head = head
-        # Sparse head (csrc/head_sparse.hip): set by the caller for the calls it wants it on -- BatchedClipPipeline, whose detection stage reads loc /
-        # centerness / mask_coeff / track at the priors that pass generate_candidate's class threshold only -- as (eval_conf_thresh, capacity in
-        # positions or None).  None: every branch densely (forward_single, the layer API, the per-clip pipeline).  FCA heads with one prior per
-        # kernel shape only: under FCB the class branch reads the dense box regression.
-        self.sparse = None
-        self._sparse_layers = None
+
+    def _head_outputs(self, head, k):
+        """Output layers of kernel shape k: the conf / centerness+bbox / mask layers read three consecutive 256-channel
+        groups of the tower output -> one grouped launch with 64 output channels per group (41 / 5 / 32 real ones);
+        the track layer (128 channels) reads the fourth group -> its own launch."""
+        P = self.GROUP_PAD
+        mods = [[head.centerness_layer[k], head.bbox_layer[k]], [head.mask_layer[k]]]
+        if not self.fcb:
+            mods = [[head.conf_layer[k]]] + mods
+        ws, bs = [], []
+        for grp in mods:
+            w = torch.cat([m.weight for m in grp], 0)
+            b = torch.cat([m.bias for m in grp], 0)
+            assert w.shape[0] <= P
+            ws.append(F.pad(w, (0, 0, 0, 0, 0, 0, 0, P - w.shape[0])))
+            bs.append(F.pad(b, (0, P - b.shape[0])))
+        m0 = mods[0][0]
+        real = sum(m.weight.shape[0] for grp in mods for m in grp)
+        small = PlanarConv(torch.cat(ws, 0), torch.cat(bs, 0), 1, m0.padding, relu=False, groups=len(mods),
+                           algo_frac=real / (len(mods) * float(P)), tile_n=64,
+                           group_cout=[sum(m.weight.shape[0] for m in grp) for grp in mods])
+        tr = head.track_layer[k]
+        trk = PlanarConv(tr.weight, tr.bias, 1, tr.padding, relu=False)
+        if not self.fcb:
+            return HeadOutputs(small, trk)
+        # FeatureAlign (Featurealign.py:6-74): offsets from the box regression, DeformConv2d + ReLU on the existing
+        # deformable kernels (NCHW fp32), then its trailing conv on the planar kernel over all levels at once
+        fa = head.conf_layer[k]
+        # (41 class channels in rows of 48: whole 16-channel tiles for the kx-reuse kernel; the rows land in the 64-column
+        # class group of the output buffer)
+        n_c = fa.conv.weight.shape[0]
+        n_cp = -(-n_c // 16) * 16
+        assert n_cp <= P
+        fconv = PlanarConv(F.pad(fa.conv.weight, (0, 0, 0, 0, 0, 0, 0, n_cp - n_c)), F.pad(fa.conv.bias, (0, n_cp - n_c)), 1, fa.conv.padding,
+                           relu=False, tile_n=64, group_cout=[n_c], algo_frac=n_c / n_cp)
+        # FeatureAlign's DeformConv2d as planar sampler (columns [pixel][tap*C + c] for all levels) + planar 1x1
+        # convolution over kh*kw*C channels (+ ReLU); offsets as one [pixels, 4] x [4, 2K] product (ada)
+        ad = fa.conv_adaption
+        O, Cin, akh, akw = ad.weight.shape
+        adconv = adfused = None
+        if ad.deform_groups == 1 and Cin == 256 and akh * akw in (9, 15):
+            wk = ad.weight.detach().permute(0, 2, 3, 1).reshape(O, akh * akw * Cin, 1, 1)
+            adconv = PlanarConv(wk, None, 1, 0, relu=True)
+            # ... or, level by level where the grid is large enough, the whole DeformConv2d + ReLU as one kernel (csrc/dcn_fused.hip)
+            if DCN_FUSED and FCB_FUSED and self.fmt in (1, 2) and ops.deform_conv_fused_supported(Cin, O, (akh, akw), False, self.fmt):
+                adfused = PlanarConv(ad.weight, None, 1, fa.padding, relu=True)
+        return HeadOutputs(small, trk, fa, fconv, adconv, adfused)
 
     # a kept position costs a 9 x 9 patch: 7 x 7 output pixels of the first tower layer (valid convolution), 5 x 5 of the second -- against
     # 2 sum(h w) pixel-layers per frame of the dense launches: the paper break-even is 2 sum(h w) / 74 positions per frame (138 at 384 x 640);
@@ -466,30 +501,30 @@ class PlanarGraph:
         t1c, t1r = cut(self.tower1, slice(0, cw)), cut(self.tower1, slice(cw, 4 * cw))
         t2c, t2r = cut(self.tower2, slice(0, cw)), cut(self.tower2, slice(cw, 4 * cw), groups=3)
         cls, small = [], []
-        for sm, _ in self.finals:
+        for sm in (f.small for f in self.finals):
             gc = sm.group_cout
             cls.append(cut(sm, slice(0, P), tile_n=64, group_cout=gc[:1], algo_frac=gc[0] / float(P)))
             small.append(cut(sm, slice(P, 3 * P), groups=2, tile_n=64, group_cout=gc[1:], algo_frac=sum(gc[1:]) / (2.0 * P)))
         self._sparse_layers = (t1c, t1r, t2c, t2r, cls, small)
         return self._sparse_layers
 
-    def _sparse_head(self, up, B, sizes, ntot, dev, toc):
+    def _sparse_head(self, up, g, toc):
         """conf for every prior; loc / mask_coeff / track / centerness at the rows of the positions with a prior that passes the class threshold
         (the other rows are not written).  No host read: launches are sized by the capacity and gated by device counts."""
-        head = self.head
+        head, (B, sizes, _, ntot, dev) = self.head, g
         thresh, cap = self.sparse[:2]
         # output layers at the centre pixel of the 5 x 5 maps only (STM_HEAD_CENTER=0: over all 25 pixels, as before); part of the setting
         center = self.sparse[2] if len(self.sparse) > 2 else head_center_default()
         if cap is None:
             cap = self.sparse_capacity(B, sizes)
         t1c, t1r, t2c, t2r, cls_l, small_l = self._build_sparse()
-        trk_l = [trk for _, trk in self.finals]
-        lv = ("levels", B, sizes)
+        trk_l = [f.trk for f in self.finals]
+        lv = g.lv
         cw, P = self.tower2.O // 4, self.GROUP_PAD
         S0, S1, S2 = self.SPARSE_SIDES
-        NP, pdt = _planes_dtype(self.fmt)
+        NP, pdt = ops.plane_layout(self.fmt)
         # the output layers run on the kernel the dense head would pick for them (the kx-reuse kernel forms its sums with other operand roles)
-        kx = ntot >= self.finals[0][0].kxr_rule_pixels()
+        kx = ntot >= self.finals[0].small.kxr_rule_pixels()
         # 1. the class branch, dense
         x = t1c(up, lv, out="planes", splitk=False)
         x = t2c(x, lv, out="planes", splitk=False)
@@ -544,11 +579,55 @@ class PlanarGraph:
     def run(self, bb_outs, planes=None):
         """bb_outs: the selected backbone outputs (C3, C4, C5) as fp32 NCHW tensors, or -- planes given -- their planar
         form [(planes, B, H, W), ...] from PlanarBackbone (bb_outs may then hold None).  Returns (fpn_outs, pred) as
-        STMask.forward_single."""
-        net, fpn = self.net, self.net.fpn
-        n = self.n_lat
+        STMask.forward_single.  Stages: laterals -> prediction / downsample levels -> proto-net -> `up` -> sparse or dense head -> assembly."""
         toc = self.timer.toc if self.timer is not None else (lambda name: None)
         toc("backbone")
+        lat, latp, B, sizes = self._fpn_laterals(bb_outs, planes)
+        toc("fpn_lateral")
+        for d in self.fpn_down:
+            h, w = sizes[-1]
+            sizes.append(ops.conv_out_hw(h, w, d.kh, d.kw, d.sh, d.sw, d.ph, d.pw, 1, 1))
+        starts = [0]
+        for h, w in sizes:
+            starts.append(starts[-1] + B * h * w)
+        g = _Levels(B, tuple(sizes), tuple(starts), starts[-1], (latp[0] if latp[0] is not None else lat[0]).device)
+        # Second-stream branches (TRUNK_BRANCHES), only while a HIP graph is captured: the graph then holds parallel paths, and on small batches --
+        # where a launch fills a fraction of the 256 CUs -- the GPU runs them side by side.  Same kernels on the same data: bit-equal to the plain order.
+        side = self._side_stream(g.dev, B)
+        feat, fpn_outs = self._fpn_levels(g, lat, latp, side)
+        toc("fpn_pred_down")
+        proto_side = side is not None and TRUNK_BRANCHES >= 1 and self.head_planar
+        if proto_side:
+            # proto-net and the shared head both start from `feat` and meet in the detection stage: proto-net on the side stream, joined at the end
+            main = torch.cuda.current_stream()
+            side.wait_stream(main)
+            with torch.cuda.stream(side), ops.workspace_branch("proto"):
+                proto = self._proto_net(g, feat)
+        else:
+            proto = self._proto_net(g, feat)
+        toc("proto_net")
+        if not self.head_planar:
+            return fpn_outs, self._module_head(fpn_outs, proto)
+        # ---- shared prediction head, all levels per launch -------------------------------------------------------
+        if self.cor_idx is not None:
+            up32, up = self.up(feat, g.lv, out="both")
+        else:
+            up32, up = None, self.up(feat, g.lv, out="planes")
+        if self.sparse is not None and self.sparse_supported():
+            outs, assembled = None, self._sparse_head(up, g, toc)
+        else:
+            outs, assembled = self._dense_head(up, g, toc), None
+        toc("head_finals")
+        pred = self._assemble(g, up32, outs, assembled)
+        pred["proto"] = proto
+        if proto_side:
+            torch.cuda.current_stream().wait_stream(side)
+        toc("head_assemble")
+        return fpn_outs, pred
+
+    def _fpn_laterals(self, bb_outs, planes):
+        """FPN laterals + top-down pathway (FPN.py:84-93) -> (fp32 NCHW laterals, planar laterals, B, level sizes); one of the two lists is filled."""
+        fpn, n = self.net.fpn, self.n_lat
         lat, latp, x = [None] * n, [None] * n, None
         if planes is not None:
             # laterals + top-down pathway on the planar kernel: lat_j = conv1x1(C_j) + upsample(lat_{j+1}) in one epilogue
@@ -584,16 +663,13 @@ class PlanarGraph:
                     x = F.interpolate(x, size=(h, w), mode=fpn.interpolation_mode, align_corners=False) + lateral
                 lat[j] = x
             sizes = [tuple(t.shape[2:]) for t in lat]
-        toc("fpn_lateral")
-        for d in self.fpn_down:
-            h, w = sizes[-1]
-            sizes.append(ops.conv_out_hw(h, w, d.kh, d.kw, d.sh, d.sw, d.ph, d.pw, 1, 1))
-        starts = [0]
-        for h, w in sizes:
-            starts.append(starts[-1] + B * h * w)
-        ntot, nf = starts[-1], self.fpn_pred[0].O
-        dev = (latp[0] if latp[0] is not None else lat[0]).device
-        NP, pdt = _planes_dtype(self.fmt)
+        return lat, latp, B, sizes
+
+    def _fpn_levels(self, g, lat, latp, side):
+        """Prediction convolutions of P3 .. P5 and the downsample convolutions to P6 / P7 into one planar buffer over all levels -> (feat,
+        fpn_outs: the fp32 NCHW levels a later stage reads -- all of them for the module-path head, else the correlation level only)."""
+        (B, sizes, starts, ntot, dev), n, nf = g, self.n_lat, self.fpn_pred[0].O
+        NP, pdt = ops.plane_layout(self.fmt)
         feat = torch.empty(NP, nf // 32, ntot, 32, device=dev, dtype=pdt)   # P3..P7, all levels, planar
         feat32 = torch.empty(ntot, nf, device=dev, dtype=torch.float32) if not self.head_planar else None
         fpn_outs = [None] * len(sizes)
@@ -623,9 +699,6 @@ class PlanarGraph:
                 else:
                     conv(feat, ("img", B, h, w), out="planes", x_off=starts[j - 1], out_planes=feat, out_off=starts[j])
 
-        # Second-stream branches (TRUNK_BRANCHES), only while a HIP graph is captured: the graph then holds parallel paths, and on small batches --
-        # where a launch fills a fraction of the 256 CUs -- the GPU runs them side by side.  Same kernels on the same data: bit-equal to the plain order.
-        side = self._side_stream(dev, B)
         if side is not None and TRUNK_BRANCHES >= 2 and len(self.fpn_down) > 0:
             # coarsest level first on the main stream, then P6 / P7 (which only need it) on the side stream beside the finer levels
             pred_level(0)
@@ -644,148 +717,144 @@ class PlanarGraph:
             # fp32 NCHW view of the correlation level, rebuilt from its planes (exact)
             j = self.cor_idx
             fpn_outs[j] = ops.planes_to_f32(feat[:, :, starts[j]:starts[j + 1]]).view(B, *sizes[j], nf).permute(0, 3, 1, 2)
+        return feat, fpn_outs
 
-        toc("fpn_pred_down")
+    def _proto_net(self, g, feat):
+        """proto-net on P3 (mask_proto_src) -> fp32 [B, 2h, 2w, 32], ReLU applied by the last layer (STMask.py:227)."""
+        B, src = g.B, self.net.proto_src
+        h, w = g.sizes[src]
+        xp, x_off, cur = feat, g.starts[src], None
+        n_layers = len(self.proto)
+        for li, layer in enumerate(self.proto):
+            last = li == n_layers - 1
+            if isinstance(layer, PlanarConv):
+                nxt_is_interp = (not last) and not isinstance(self.proto[li + 1], PlanarConv)
+                if cur is not None:            # fp32 NHWC tensor pending a split
+                    xp, x_off = _split(cur, self.fmt), 0
+                    cur = None
+                if last or nxt_is_interp:
+                    y = layer(xp, ("img", B, h, w), out="f32", x_off=x_off)
+                    cur = y.view(B, h, w, layer.O)
+                else:
+                    xp, x_off = layer(xp, ("img", B, h, w), out="planes", x_off=x_off), 0
+            else:                              # bilinear upsample
+                kw = layer.kwargs
+                sf = kw.get("scale_factor")
+                nxt_conv = (not last) and isinstance(self.proto[li + 1], PlanarConv)
+                if (nxt_conv and not layer.args and kw.get("mode") == "bilinear" and not kw.get("align_corners", False)
+                        and isinstance(sf, (int, float)) and float(sf).is_integer() and set(kw) <= {"scale_factor", "mode", "align_corners"}):
+                    # ... straight into the next convolution's planes (no fp32 upsampled tensor)
+                    h, w = h * int(sf), w * int(sf)
+                    xp, x_off, cur = ops.resize_bilinear_planes(cur, (h, w), self.fmt), 0, None
+                else:
+                    t = layer(cur.permute(0, 3, 1, 2))
+                    h, w = t.shape[2:]
+                    cur = _nhwc(t)
+        return cur
 
-        # ---- proto-net on P3 (mask_proto_src) ------------------------------------------------------------------
-        def proto_net():
-            src = net.proto_src
-            h, w = sizes[src]
-            xp, x_off, cur = feat, starts[src], None
-            n_layers = len(self.proto)
-            for li, layer in enumerate(self.proto):
-                last = li == n_layers - 1
-                if isinstance(layer, PlanarConv):
-                    nxt_is_interp = (not last) and not isinstance(self.proto[li + 1], PlanarConv)
-                    if cur is not None:            # fp32 NHWC tensor pending a split
-                        xp, x_off = _split(cur, self.fmt), 0
-                        cur = None
-                    if last or nxt_is_interp:
-                        y = layer(xp, ("img", B, h, w), out="f32", x_off=x_off)
-                        cur = y.view(B, h, w, layer.O)
-                    else:
-                        xp, x_off = layer(xp, ("img", B, h, w), out="planes", x_off=x_off), 0
-                else:                              # bilinear upsample
-                    kw = layer.kwargs
-                    sf = kw.get("scale_factor")
-                    nxt_conv = (not last) and isinstance(self.proto[li + 1], PlanarConv)
-                    if (nxt_conv and not layer.args and kw.get("mode") == "bilinear" and not kw.get("align_corners", False)
-                            and isinstance(sf, (int, float)) and float(sf).is_integer() and set(kw) <= {"scale_factor", "mode", "align_corners"}):
-                        # ... straight into the next convolution's planes (no fp32 upsampled tensor)
-                        h, w = h * int(sf), w * int(sf)
-                        xp, x_off, cur = ops.resize_bilinear_planes(cur, (h, w), self.fmt), 0, None
-                    else:
-                        t = layer(cur.permute(0, 3, 1, 2))
-                        h, w = t.shape[2:]
-                        cur = _nhwc(t)
-            return cur                         # [B, 2h, 2w, 32], ReLU applied by the last layer (STMask.py:227)
+    _PRED_KEYS = ("mask_coeff", "priors", "loc", "T2S_feat", "centerness", "conf", "track")
 
-        proto_side = side is not None and TRUNK_BRANCHES >= 1 and self.head_planar
-        if proto_side:
-            # proto-net and the shared head both start from `feat` and meet in the detection stage: proto-net on the side stream, joined at the end
-            main = torch.cuda.current_stream()
-            side.wait_stream(main)
-            with torch.cuda.stream(side), ops.workspace_branch("proto"):
-                proto = proto_net()
-        else:
-            proto = proto_net()
-        toc("proto_net")
-
-        keys = ("mask_coeff", "priors", "loc", "T2S_feat", "centerness", "conf", "track")
+    def _module_head(self, fpn_outs, proto):
+        """The head as the net's own prediction modules, level by level (FCB on the track / mask branches, unshared heads)."""
+        net, keys = self.net, self._PRED_KEYS
         pred = {k: [] for k in keys}
-        if not self.head_planar:
-            for idx, layer in zip(net.selected_layers, net.prediction_layers):
-                p = layer(fpn_outs[idx])
-                for k in keys:
-                    pred[k].append(p[k])
+        for idx, layer in zip(net.selected_layers, net.prediction_layers):
+            p = layer(fpn_outs[idx])
             for k in keys:
-                if k != "T2S_feat":
-                    pred[k] = torch.cat(pred[k], 1)
-            pred["proto"] = proto
-            return fpn_outs, pred
+                pred[k].append(p[k])
+        for k in keys:
+            if k != "T2S_feat":
+                pred[k] = torch.cat(pred[k], 1)
+        pred["proto"] = proto
+        return pred
 
-        # ---- shared prediction head, all levels per launch -------------------------------------------------------
-        lv = ("levels", B, sizes)
-        head = self.head
-        if self.cor_idx is not None:
-            up32, up = self.up(feat, lv, out="both")
-        else:
-            up32, up = None, self.up(feat, lv, out="planes")
-        sparse_out = None
-        if self.sparse is not None and self.sparse_supported():
-            sparse_out = self._sparse_head(up, B, sizes, ntot, dev, toc)
-        t1 = self.tower1(up, lv, out="planes") if sparse_out is None else None
+    def _dense_head(self, up, g, toc):
+        """Towers and output layers over every pixel -> per kernel shape ([pixels, 3 * GROUP_PAD] conf | centerness+bbox | mask, [pixels, embed] track)."""
+        (B, sizes, starts, ntot, dev), lv = g, g.lv
+        t1 = self.tower1(up, lv, out="planes")
         cw = self.tower2.O // 4                                       # channels per branch in t2 (conf, bbox, mask, track)
-        P = self.GROUP_PAD
-        if sparse_out is not None:
-            outs = None
-        elif not self.fcb:
+        if not self.fcb:
             t2 = self.tower2(t1, lv, out="planes")
             toc("head_towers")
-            outs = [(small(t2, lv, out="f32"), trk(t2, lv, out="f32", x_ch_off=3 * cw)) for small, trk in self.finals]
-        else:
-            t2_32, t2 = self.tower2(t1, lv, out="both")               # the class branch also leaves as fp32 for the sampler
-            toc("head_towers")
-            # conf_x per level as NCHW fp32 (shared by the three kernel shapes)
-            conf_x = None
-            outs = []
-            for small, trk, fa, fconv, adconv, adfused in self.finals:
-                buf = torch.empty(ntot, 3 * P, device=dev, dtype=torch.float32)   # [conf | centerness+bbox | mask] groups
-                small(t2, lv, out="f32", out_f32=buf, x_ch_off=cw, out_ch_off=P)
-                npri = head.num_priors
-                if adconv is not None and npri == 1 and FCB_PLANAR:
-                    # all-planar class branch: offsets pixel-major, sampler per level into one column buffer, one 1x1 conv
-                    kh, kw = fa.kernel_size
-                    K = kh * kw
-                    bbox_pix = buf[:, P + npri:P + npri + 4]                       # [ntot, 4] box regression of this shape
-                    if fa.use_pred_offset:
-                        off = bbox_pix @ fa.conv_offset.weight.view(2 * K, 4).t()   # Featurealign.py:40-43 (1x1 conv, no bias)
-                    NP_, pdt_ = _planes_dtype(self.fmt)
-                    # levels whose grid fills the chip take the fused kernel (no columns); the coarser ones, contiguous at the end of the pixel axis,
-                    # share one column buffer and one 1x1 product as before -- both write the same feature planes
-                    n_fused = 0
-                    if adfused is not None:
-                        while n_fused < len(sizes) and ops.deform_conv_fused_tiles(B, sizes[n_fused][0], sizes[n_fused][1], adfused.O) >= DCN_FUSED_MIN_TILES:
-                            n_fused += 1
-                    c0 = starts[n_fused]                                         # first pixel of the column-buffer levels
-                    feat_pl = torch.empty(NP_, cw // 32, ntot, 32, device=dev, dtype=pdt_)
-                    cols = torch.empty(NP_, K * cw // 32, ntot - c0, 32, device=dev, dtype=pdt_) if ntot > c0 else None
-                    for l, (hh, ww) in enumerate(sizes):
-                        sl = slice(starts[l], starts[l + 1])
-                        if fa.use_pred_offset:
-                            off_l = off[sl]
-                        else:
-                            loc_l = bbox_pix[sl].reshape(B, hh, ww, 4).permute(0, 3, 1, 2).contiguous()
-                            off_l = ops.fcb_ali_offsets(loc_l, kh, kw).permute(0, 2, 3, 1).reshape(-1, 2 * K)
-                        if l < n_fused:
-                            adfused.deform(t2_32[sl, 0:cw], B, hh, ww, off_l, 1, fa.padding, 1, has_mask=False, out=feat_pl, out_off=starts[l])
-                        else:
-                            ops.deform_sample_planar(t2_32[sl, 0:cw], B, hh, ww, cw, off_l, (kh, kw), fa.padding, cols, starts[l] - c0, self.fmt)
-                    if cols is not None:
-                        adconv(cols, ("img", 1, 1, ntot - c0), out_planes=feat_pl, out_off=c0)      # DeformConv2d's GEMM + ReLU
-                    fconv(feat_pl, lv, out="f32", out_f32=buf)                   # conf logits into columns [0, n_cls)
-                    outs.append((buf, trk(t2, lv, out="f32", x_ch_off=3 * cw)))
-                    continue
+            return [(f.small(t2, lv, out="f32"), f.trk(t2, lv, out="f32", x_ch_off=3 * cw)) for f in self.finals]
+        t2_32, t2 = self.tower2(t1, lv, out="both")                   # the class branch also leaves as fp32 for the sampler
+        toc("head_towers")
+        P, npri = self.GROUP_PAD, self.head.num_priors
+        conf_x = None             # conf_x per level as NCHW fp32 (shared by the three kernel shapes)
+        outs = []
+        for f in self.finals:
+            buf = torch.empty(ntot, 3 * P, device=dev, dtype=torch.float32)   # [conf | centerness+bbox | mask] groups
+            f.small(t2, lv, out="f32", out_f32=buf, x_ch_off=cw, out_ch_off=P)
+            if f.adconv is not None and npri == 1 and FCB_PLANAR:
+                self._fcb_class_planar(f, g, t2_32, buf)
+            else:
                 if conf_x is None:
                     conf_x = [t2_32[starts[l]:starts[l + 1], 0:cw].reshape(B, hh, ww, cw).permute(0, 3, 1, 2).contiguous()
                               for l, (hh, ww) in enumerate(sizes)]
-                feat_k = torch.empty(ntot, cw, device=dev, dtype=torch.float32)
-                for l, (hh, ww) in enumerate(sizes):
-                    sl = slice(starts[l], starts[l + 1])
-                    bbox_cur = buf[sl, P + npri:P + npri + 4 * npri].reshape(B, hh, ww, 4 * npri).permute(0, 3, 1, 2).contiguous()
-                    if fa.use_pred_offset:
-                        offset = fa.conv_offset(bbox_cur)
-                    else:
-                        offset = ops.fcb_ali_offsets(bbox_cur, fa.kernel_size[0], fa.kernel_size[1])
-                    y = ops.deform_conv(conf_x[l], offset, None, fa.conv_adaption.weight, None, 1, fa.padding, 1,
-                                        fa.conv_adaption.deform_groups, relu=True)
-                    feat_k[sl] = y.permute(0, 2, 3, 1).reshape(-1, cw)
-                fconv(ops.split_planes(feat_k, self.fmt), lv, out="f32", out_f32=buf)        # conf logits into columns [0, n_cls)
-                outs.append((buf, trk(t2, lv, out="f32", x_ch_off=3 * cw)))
-        toc("head_finals")
-        P = self.GROUP_PAD
+                self._fcb_class_module(f, g, conf_x, buf)
+            outs.append((buf, f.trk(t2, lv, out="f32", x_ch_off=3 * cw)))
+        return outs
+
+    def _fcb_class_planar(self, f, g, t2_32, buf):
+        """FCB class branch of one kernel shape, all planar: offsets pixel-major, sampler per level into one column buffer, one 1x1 conv; the
+        class logits go into columns [0, n_cls) of buf, whose box-regression columns it reads."""
+        (B, sizes, starts, ntot, dev), lv, fa, adfused = g, g.lv, f.fa, f.adfused
+        cw, P, npri = self.tower2.O // 4, self.GROUP_PAD, self.head.num_priors
+        kh, kw = fa.kernel_size
+        K = kh * kw
+        bbox_pix = buf[:, P + npri:P + npri + 4]                       # [ntot, 4] box regression of this shape
+        if fa.use_pred_offset:
+            off = bbox_pix @ fa.conv_offset.weight.view(2 * K, 4).t()   # Featurealign.py:40-43 (1x1 conv, no bias)
+        NP, pdt = ops.plane_layout(self.fmt)
+        # levels whose grid fills the chip take the fused kernel (no columns); the coarser ones, contiguous at the end of the pixel axis,
+        # share one column buffer and one 1x1 product as before -- both write the same feature planes
+        n_fused = 0
+        if adfused is not None:
+            while n_fused < len(sizes) and ops.deform_conv_fused_tiles(B, sizes[n_fused][0], sizes[n_fused][1], adfused.O) >= DCN_FUSED_MIN_TILES:
+                n_fused += 1
+        c0 = starts[n_fused]                                         # first pixel of the column-buffer levels
+        feat_pl = torch.empty(NP, cw // 32, ntot, 32, device=dev, dtype=pdt)
+        cols = torch.empty(NP, K * cw // 32, ntot - c0, 32, device=dev, dtype=pdt) if ntot > c0 else None
+        for l, (hh, ww) in enumerate(sizes):
+            sl = slice(starts[l], starts[l + 1])
+            if fa.use_pred_offset:
+                off_l = off[sl]
+            else:
+                loc_l = bbox_pix[sl].reshape(B, hh, ww, 4).permute(0, 3, 1, 2).contiguous()
+                off_l = ops.fcb_ali_offsets(loc_l, kh, kw).permute(0, 2, 3, 1).reshape(-1, 2 * K)
+            if l < n_fused:
+                adfused.deform(t2_32[sl, 0:cw], B, hh, ww, off_l, 1, fa.padding, 1, has_mask=False, out=feat_pl, out_off=starts[l])
+            else:
+                ops.deform_sample_planar(t2_32[sl, 0:cw], B, hh, ww, cw, off_l, (kh, kw), fa.padding, cols, starts[l] - c0, self.fmt)
+        if cols is not None:
+            f.adconv(cols, ("img", 1, 1, ntot - c0), out_planes=feat_pl, out_off=c0)      # DeformConv2d's GEMM + ReLU
+        f.fconv(feat_pl, lv, out="f32", out_f32=buf)                   # conf logits into columns [0, n_cls)
+
+    def _fcb_class_module(self, f, g, conf_x, buf):
+        """... the same with FeatureAlign's deformable convolution level by level on the NCHW fp32 kernel (FCB_PLANAR off, an adaption layer
+        the planar sampler does not take, several priors); conf_x: the class tower's output per level, NCHW fp32."""
+        (B, sizes, starts, ntot, dev), lv, fa = g, g.lv, f.fa
+        cw, P, npri = self.tower2.O // 4, self.GROUP_PAD, self.head.num_priors
+        feat_k = torch.empty(ntot, cw, device=dev, dtype=torch.float32)
+        for l, (hh, ww) in enumerate(sizes):
+            sl = slice(starts[l], starts[l + 1])
+            bbox_cur = buf[sl, P + npri:P + npri + 4 * npri].reshape(B, hh, ww, 4 * npri).permute(0, 3, 1, 2).contiguous()
+            if fa.use_pred_offset:
+                offset = fa.conv_offset(bbox_cur)
+            else:
+                offset = ops.fcb_ali_offsets(bbox_cur, fa.kernel_size[0], fa.kernel_size[1])
+            y = ops.deform_conv(conf_x[l], offset, None, fa.conv_adaption.weight, None, 1, fa.padding, 1,
+                                fa.conv_adaption.deform_groups, relu=True)
+            feat_k[sl] = y.permute(0, 2, 3, 1).reshape(-1, cw)
+        f.fconv(ops.split_planes(feat_k, self.fmt), lv, out="f32", out_f32=buf)        # conf logits into columns [0, n_cls)
+
+    def _assemble(self, g, up32, outs, assembled):
+        """The prediction dict (without proto): priors, T2S_feat, and conf / loc / mask_coeff / track / centerness -- `assembled` from the sparse
+        head, else the dense head's `outs` through the reference's cat / view / tanh / normalize tail."""
+        (B, sizes, starts, _, dev), head, P = g, self.head, self.GROUP_PAD
         ncls, nbox, nmask, ntrk = self.dims
         npri = head.num_priors
+        pred = {k: [] for k in self._PRED_KEYS}
         t2s = [None] * len(sizes)
         if up32 is not None:
             l = self.cor_idx
@@ -793,8 +862,8 @@ class PlanarGraph:
         for hh, ww in sizes:
             pred["priors"].append(head.make_priors(hh, ww, dev))
         pred["priors"] = torch.cat(pred["priors"], 1)
-        if sparse_out is not None:
-            pred["conf"], pred["loc"], pred["mask_coeff"], pred["track"], pred["centerness"] = sparse_out
+        if assembled is not None:
+            pred["conf"], pred["loc"], pred["mask_coeff"], pred["track"], pred["centerness"] = assembled
         elif npri == 1:
             # one kernel for the reference's cat / view / tanh / normalize tail over all levels and kernel shapes
             conf, loc, mask, track, cen = ops.head_assemble([o[0] for o in outs], [o[1] for o in outs], B, sizes,
@@ -818,11 +887,7 @@ class PlanarGraph:
             pred["track"] = F.normalize(torch.cat(track, 1), dim=-1)
             pred["centerness"] = torch.tanh(torch.cat(cen, 1))
         pred["T2S_feat"] = t2s
-        pred["proto"] = proto
-        if proto_side:
-            torch.cuda.current_stream().wait_stream(side)
-        toc("head_assemble")
-        return fpn_outs, pred
+        return pred
 
     def _side_stream(self, dev, n_images):
         """The second stream of run()'s branches, or None: branches exist only inside a HIP-graph capture (eager passes keep the plain order: tensors
@@ -831,7 +896,7 @@ class PlanarGraph:
             return None
         if not torch.cuda.is_current_stream_capturing():
             return None
-        if getattr(self, "_side", None) is None or self._side.device != torch.device(dev):
+        if self._side is None or self._side.device != torch.device(dev):
             self._side = torch.cuda.Stream(device=dev)
         return self._side
 
@@ -903,8 +968,6 @@ class PlanarTemporalNet:
         x = F.pad(roi_feats.index_select(1, self.perm.to(roi_feats.device)).permute(0, 2, 3, 1), (0, self.cpad - c)).contiguous()   # NHWC, padded
         return self.forward_planes(ops.split_planes(x, self.fmt), n, h, w)
 
-    _CLASSES = _BORDER_CLASSES
-
     def _border_layer(self, li, xp, n, h, w, out):
         """One 3x3 layer as its nine border-class windows in one launch; returns planes [2, O/32, n*h*w, 32] or the fp32 matrix [n*h*w, O]."""
         L = self.border[li]
@@ -913,7 +976,7 @@ class PlanarTemporalNet:
             ops.planar_range_flag()
             wscale = ops._pow2_wscale(L["w"])
             L["packed"] = [ops.conv_pack_weights(L["w"][:, :, k0y:k1y, k0x:k1x].contiguous(), tile_n=128, fmt=1, wscale=wscale)[0]
-                           for _, _, k0y, k1y, k0x, k1x in self._CLASSES]
+                           for _, _, k0y, k1y, k0x, k1x in _BORDER_CLASSES]
             L["out_scale"] = 1.0 / wscale
         dev = xp.device
         out_planes = torch.empty(2, O // 32, n * h * w, 32, device=dev, dtype=torch.float16) if out == "planes" else None
@@ -925,10 +988,7 @@ class PlanarTemporalNet:
             wins.append(win)
             packed.append(L["packed"][ci])
             macs += win[4] * win[5] * win[0] * win[1]
-        timing = ops._conv_timing
-        if timing is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        started = _timing_start()
         if out == "pool":
             # the launch ADDS into the pooled sums and only the tail kernel re-zeroes them: a failure in between must not leave stale sums for the next step
             try:
@@ -938,13 +998,12 @@ class PlanarTemporalNet:
                 raise
         else:
             ops.conv2d_planar_windows(xp, packed, wins, L["b"], n, h, w, C, O, h, w, L["out_scale"], relu=True, out_f32=out_f32, out_planes=out_planes)
-        if timing is not None:
-            e1.record()
+        if started is not None:
             M = n * h * w
             nbytes = M * C * 4 + (n * O * 8 if out == "pool" else M * O * 4) + L["w"].numel() * 4
             # algorithmic flops as for every other layer: the reference's 2 M Cout Cin kh kw (its padded taps included), priced against the
             # format's peak (3 MFMA products per fp32 product); 8th field: share of those products that is actually issued (361 / 441 on 7x7)
-            timing.append((e0, e1, 2.0 * M * 9 * O * C * L["frac"], (M, C, O, 3, 1, 1, -2), 3, "temporal", float(nbytes), macs / (h * w * 9.0)))
+            _timing_stop(started, 2.0 * M * 9 * O * C * L["frac"], (M, C, O, 3, 1, 1, -2), 3, "temporal", nbytes, macs / (h * w * 9.0))
         return out_planes if out == "planes" else (self._pool if out == "pool" else out_f32)
 
     def forward_planes(self, xp, n, h=7, w=7):
@@ -1008,17 +1067,13 @@ class PlanarChain:
             tail, s3, s1 = ops.chain_pack_tail(self.w3, self.w1, self.wds)
             self._packed = (w2p, tail, (s2, s3, s1))
         w2p, tail, scales = self._packed
-        timing = ops._conv_timing
-        if timing is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        started = _timing_start()
         y, z = ops.bottleneck_chain(mid1, x, w2p, tail, self.b2, self.b3, self.b1, scales, B, H, W, want_z=self.w1 is not None, proj=self.wds is not None)
-        if timing is not None:
-            e1.record()
+        if started is not None:
             M = B * H * W
             macs = 64 * 64 * 9 + 256 * 64 * (2 if self.wds is not None else 1) + (256 * 64 if self.w1 is not None else 0)
             nbytes = M * 4 * (64 + (64 if self.wds is not None else 256) + 256 + (64 if self.w1 is not None else 0)) + 4 * macs
-            timing.append((e0, e1, 2.0 * M * macs, (M, 64, 256, 3, 1, 1, -1), 3, self.role, float(nbytes)))
+            _timing_stop(started, 2.0 * M * macs, (M, 64, 256, 3, 1, 1, -1), 3, self.role, nbytes)
         return y, z
 
 

@@ -136,7 +136,7 @@ class TrunkRunner:
 
     def _trunk(self, frames):
         pg = getattr(self.net, "_planar", None)
-        if pg is None or not hasattr(pg, "sparse"):
+        if pg is None:
             return self._trunk_run(frames)
         self._sparse_now = self._sparse_setting(pg)
         before, pg.sparse = pg.sparse, self._sparse_now

@@ -209,6 +209,47 @@ def test_planar_graph_matches_module_path_and_reference(name, tag, planes):
                     tol_rms=1e-4, tol_abs=2e-4)
 
 
+def test_planar_graph_fcb_class_branch_module_form_matches_reference(monkeypatch):
+    """The FCB class branch in its other form (planar.FCB_PLANAR off; also what runs for an adaption layer that is not 256 channels x 9 / 15 taps, or
+    with several priors): FeatureAlign's deformable convolution level by level on the NCHW fp32 kernel, only its trailing convolution planar.  Its
+    deformable product stays fp32, so it is held to the module path and the reference golden at the bound of the planar form above; and it is this
+    form that ran: fifteen NCHW deformable convolutions (3 kernel shapes x 5 levels), no launch of the fused kernel."""
+    from stmask_amd import planar, ops, _lib
+    from stmask_amd.fuse import optimize_for_inference
+    name, tag = CASES[1]
+    assert tag == "r50_ada"
+    monkeypatch.setattr(planar, "FCB_PLANAR", False)
+    g = load_golden(f"model_{tag}.npz")
+    h, w = [int(v) for v in g["frames_hw"]]
+    ref_net = build(name)
+    opt_net = build(name)
+    optimize_for_inference(opt_net, planar=True, planes="fp16x2")
+    opt_net = opt_net.to(memory_format=torch.channels_last)
+    opt_net.TemporalNet = opt_net.TemporalNet.to(memory_format=torch.contiguous_format)
+    assert opt_net._planar.head_planar and opt_net._planar.fcb
+    x = synthetic.synthetic_clip(2, h, w, seed=0).cuda()
+    with torch.no_grad():
+        fa, a = ref_net.forward_single(x)
+    nchw_calls, deform_conv = [], ops.deform_conv
+    monkeypatch.setattr(ops, "deform_conv", lambda *args, **kw: (nchw_calls.append(1), deform_conv(*args, **kw))[1])
+    n0 = _lib.lib().stm_debug_launch_count(1)
+    with torch.no_grad():
+        fb, b = opt_net.forward_single(x.contiguous(memory_format=torch.channels_last))
+    assert _lib.lib().stm_debug_launch_count(1) == n0
+    assert len(nchw_calls) == 3 * 5, len(nchw_calls)
+    assert torch.equal(a["priors"], b["priors"])
+    for k in ("loc", "conf", "mask_coeff", "centerness", "proto", "track"):
+        assert a[k].shape == b[k].shape, k
+        scale = max(1.0, a[k].abs().max().item())
+        err = (a[k] - b[k]).abs().max().item()
+        assert err < 5e-5 * scale, (k, err)
+    for k, gk in [("loc", "f0_loc"), ("conf", "f0_conf_logits"), ("mask_coeff", "f0_mask_coeff"),
+                  ("centerness", "f0_centerness"), ("proto", "f0_proto")]:
+        ref = g[gk]
+        err = (b[k][0].cpu() - ref).abs().max().item()
+        assert err < 5e-5 * max(1.0, ref.abs().max().item()), (k, err)
+
+
 @pytest.mark.parametrize("name,tag", CASES[:3])
 def test_planar_graph_with_fused_deformable_layers_matches_reference(name, tag, monkeypatch):
     """The same graph with every deformable convolution on the fused kernel (csrc/dcn_fused.hip: the DCN layers of the backbone and -- FCB
