@@ -4,9 +4,12 @@ sizes, served at each --slots count with graph-replayed trunks.  A measuring too
 
 Prints one JSON line: per slot count the frames/s (device-synchronised wall clock around the whole queue, after one warm-up queue), the slot
 occupancy (active slot-steps / all slot-steps) and the number of videos and frames.  --render: every busy slot's frame is also drawn on the
-device each step (VideoBatcher.run(on_frame=...), stmask_amd.display source mode); the annotated frames are dropped.
+device each step (VideoBatcher.run(on_frame=...), stmask_amd.display source mode); the annotated frames are dropped.  --batched-output: the
+output stage of a step is one batched device stage read one step late (VideoBatcher(batched_output=True)) instead of postprocess_ytbvis per
+slot.  After the timed queue the same queue runs once more with the synchronising calls wrapped (Tensor.cpu / tolist / item / nonzero,
+event and device synchronize): host_waits_per_step and d2h_bytes_per_step of the chosen mode come from that run.
 
-usage: python scripts/serve_videos.py [--videos 64] [--min-frames 8] [--max-frames 36] [--slots 8 32] [--render]"""
+usage: python scripts/serve_videos.py [--videos 64] [--min-frames 8] [--max-frames 36] [--slots 8 32] [--render] [--batched-output]"""
 import argparse
 import json
 import os
@@ -48,8 +51,39 @@ def build_net(config, dev):
     return net
 
 
-def measure(net, slots, queue, warm, render=False):
-    vb = VideoBatcher(net, slots, use_graph=True)
+class WaitCounter:
+    """Counts, while active, the calls that make the host wait for the device and the bytes they bring back."""
+
+    def __init__(self):
+        self.waits, self.bytes = 0, 0
+
+    def __enter__(self):
+        T = torch.Tensor
+        self.saved = [(T, "cpu", T.cpu), (T, "tolist", T.tolist), (T, "item", T.item), (torch, "nonzero", torch.nonzero),
+                      (torch.cuda.Event, "synchronize", torch.cuda.Event.synchronize), (torch.cuda, "synchronize", torch.cuda.synchronize)]
+
+        def wrap(fn, tensor_arg):
+            def counted(*args, **kw):
+                t = args[0] if tensor_arg and args and torch.is_tensor(args[0]) else None
+                if t is None or t.is_cuda:
+                    self.waits += 1
+                    if t is not None and fn is not torch.nonzero:
+                        self.bytes += t.numel() * t.element_size()
+                return fn(*args, **kw)
+            return counted
+
+        for owner, name, fn in self.saved:
+            setattr(owner, name, wrap(fn, owner is T or owner is torch))
+        return self
+
+    def __exit__(self, *exc):
+        for owner, name, fn in self.saved:
+            setattr(owner, name, fn)
+        return False
+
+
+def measure(net, slots, queue, warm, render=False, batched_output=False):
+    vb = VideoBatcher(net, slots, use_graph=True, batched_output=batched_output)
     on_frame = (lambda vid, fid, img: None) if render else None
     vb.run(warm, on_frame=on_frame)                   # warm-up queue: graph capture, workspaces, prior cache
     torch.cuda.synchronize()
@@ -58,7 +92,13 @@ def measure(net, slots, queue, warm, render=False):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     frames = sum(int(v.shape[0]) for _, v in queue)
-    return {"slots": slots, "frames_per_s": round(frames / dt, 1), "occupancy": round(vb.occupancy(), 4), "videos": len(queue),
+    copied0 = vb.output_stage.bytes_copied if batched_output else 0
+    with WaitCounter() as wc:
+        vb.run(queue, on_frame=on_frame)
+    torch.cuda.synchronize()
+    d2h = wc.bytes + (vb.output_stage.bytes_copied - copied0 if batched_output else 0)
+    return {"slots": slots, "batched_output": batched_output, "host_waits_per_step": round(wc.waits / vb.steps, 1),
+            "d2h_bytes_per_step": round(d2h / vb.steps), "frames_per_s": round(frames / dt, 1), "occupancy": round(vb.occupancy(), 4), "videos": len(queue),
             "frames": frames, "steps": vb.steps, "graph": vb.pipe.graph_active, "seconds": round(dt, 3), "render": render}
 
 
@@ -71,6 +111,7 @@ if __name__ == "__main__":
     ap.add_argument("--config", default="STMask_plus_resnet50_config")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--render", action="store_true", help="draw every served frame on the device (display source mode)")
+    ap.add_argument("--batched-output", action="store_true", help="one batched output stage per step, read one step late")
     a = ap.parse_args()
     dev = "cuda"
     net = build_net(a.config, dev)
@@ -78,5 +119,5 @@ if __name__ == "__main__":
     rows = []
     for s in a.slots:
         warm = make_queue(max(s, 4), a.min_frames, a.min_frames + 4, a.seed + 1, dev)
-        rows.append(measure(net, s, queue, warm, a.render))
+        rows.append(measure(net, s, queue, warm, a.render, a.batched_output))
     print(json.dumps({"tool": "serve_videos", "config": a.config, "runs": rows}))

@@ -150,6 +150,13 @@ SIGNATURES = {
     "stm_mask_bce_upsampled_backward_f32": ("i", "pppippiiiiiip"),
 }
 ABI_SYMBOLS = list(SIGNATURES)
+# include/stmask_hip_output.h restated the same way (tests/test_abi_output.py): the batched output stage, declared in a header of its own so that
+# the first header's prototype list and ABI_VERSION stay as they are.  Same library; lib() and call() treat both tables alike.
+OUTPUT_SIGNATURES = {
+    "stm_output_struct_bytes": ("z", "i"),
+    "stm_output_stage_workspace_bytes": ("z", "ili"),
+    "stm_output_stage_multi_f32": ("i", "piiipppipipppiffipzpzp"),
+}
 
 
 class StmError(RuntimeError):
@@ -183,6 +190,22 @@ class RenderFrame(ctypes.Structure):
                                     "crop_h", "crop_w", "reserved")])
 
 
+class OutputFrame(ctypes.Structure):
+    _fields_ = [(n, c_i) for n in ("crop_h", "crop_w", "out_h", "out_w")] + [(n, c_f) for n in ("s_w", "s_h", "inv_s_w", "inv_s_h")]
+
+
+class OutputRow(ctypes.Structure):
+    _fields_ = ([(n, c_i) for n in ("frame", "status", "n_runs", "str_off", "str_len", "cls", "box_id")] + [("score_bits", ctypes.c_uint32),
+                                                                                                         ("box", c_i * 4)])
+
+
+class OutputHeader(ctypes.Structure):
+    _fields_ = [(n, c_i) for n in ("n_rows", "total_bytes", "arena_bytes", "reserved")]
+
+
+ROW_KEPT, ROW_RUN_OVERFLOW, ROW_ARENA_OVERFLOW, ROW_BAD_FRAME = 1, 2, 4, 8   # OutputRow.status bits (include/stmask_hip_output.h)
+
+
 class HeadLayout(ctypes.Structure):
     _fields_ = ([(n, c_i) for n in ("B", "K", "n_levels", "n_cls", "mask_dim", "embed_dim", "group_pad", "small_ld", "trk_ld")] +
                 [("lvl_start", c_i * 8), ("lvl_hw", c_i * 8)])
@@ -205,17 +228,20 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback on the product path.")
         _lib = ctypes.CDLL(LIB_PATH)
-        missing = [n for n in SIGNATURES if not hasattr(_lib, n)]
+        tables = {**SIGNATURES, **OUTPUT_SIGNATURES}
+        missing = [n for n in tables if not hasattr(_lib, n)]
         if missing:
             _lib = None
             raise StmError(f"{LIB_PATH} lacks {', '.join(missing)}: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")
-        for name, (ret, params) in SIGNATURES.items():
+        for name, (ret, params) in tables.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = _KINDS[ret], [_KINDS[k] for k in params]
             _calls[name] = (fn, len(params))
         # this binding and the library must describe the same structs (a stale .so would read garbage past a shorter struct)
         structs = [DeformGeom, ConvGeom, ConvWindow, HeadLayout, FrameDesc, RenderFrame]
-        if _lib.stm_version() != ABI_VERSION or any(_lib.stm_struct_bytes(i) != ctypes.sizeof(s) for i, s in enumerate(structs)):
+        out_structs = [OutputFrame, OutputRow, OutputHeader]
+        if (_lib.stm_version() != ABI_VERSION or any(_lib.stm_struct_bytes(i) != ctypes.sizeof(s) for i, s in enumerate(structs))
+                or any(_lib.stm_output_struct_bytes(i) != ctypes.sizeof(s) for i, s in enumerate(out_structs))):
             v = _lib.stm_version()
             _lib = None
             raise StmError(f"{LIB_PATH} has ABI version {v}, this binding was written for {ABI_VERSION} (or a struct size "

@@ -13,6 +13,7 @@
 // Arithmetic follows ATen's bilinear kernel (align_corners=False) in fp32, operand order as in oracle/stm_oracle.c, so
 // the bits agree with the oracle exactly (-ffp-contract=off).
 #include "stm_common.h"
+#include "rle_common.h"
 
 namespace {
 
@@ -39,72 +40,16 @@ __global__ __launch_bounds__(256) void resize_threshold_pack_kernel(const float*
     if (lane == 0) bits[(int64_t)i * words + word] = bal;
 }
 
-// bits of word w that are real pixels (the last word is zero-padded: a 1 -> padding "transition" is not a run boundary)
-__device__ __forceinline__ unsigned long long valid_bits(int w, int64_t n_px)
-{
-    const int64_t rem = n_px - (int64_t)w * 64;
-    return rem >= 64 ? ~0ull : ((1ull << rem) - 1ull);
-}
-
-// one workgroup per mask; counts[i][0..n_runs[i]) (capacity max_runs; n_runs reports the true number)
+// one workgroup per mask; counts[i][0..n_runs[i]) (capacity max_runs; n_runs reports the true number): rle_common.h
 __global__ __launch_bounds__(1024) void rle_runs_kernel(const unsigned long long* __restrict__ bits, int words, int64_t n_px,
                                                         unsigned int* __restrict__ counts, int max_runs, int* __restrict__ n_runs,
                                                         unsigned int* __restrict__ trans_ws)
 {
     __shared__ int wave_tot[16];
-    __shared__ int block_base;
     const int i = blockIdx.x;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const unsigned long long* bw = bits + (int64_t)i * words;
-    unsigned int* T = trans_ws + (int64_t)i * max_runs;   // transition positions
-    unsigned int* cnt = counts + (int64_t)i * max_runs;
-    const int per = (words + 1023) / 1024;                // consecutive words per thread
-    const int w0 = tid * per, w1 = min(words, w0 + per);
-    // pass 1: transitions in my words
-    int mine = 0;
-    for (int w = w0; w < w1; ++w) {
-        const unsigned long long cur = bw[w];
-        const unsigned long long prev = w ? (bw[w - 1] >> 63) : 0ull;
-        mine += __popcll((cur ^ ((cur << 1) | prev)) & valid_bits(w, n_px));
-    }
-    // exclusive scan over the 1024 threads (wave scan + wave totals)
-    int incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    int base = 0, total = 0;
-    for (int w = 0; w < 16; ++w) {
-        if (w < wave) base += wave_tot[w];
-        total += wave_tot[w];
-    }
-    int pos = base + incl - mine;
-    // pass 2: emit transition positions in order
-    for (int w = w0; w < w1; ++w) {
-        const unsigned long long cur = bw[w];
-        const unsigned long long prev = w ? (bw[w - 1] >> 63) : 0ull;
-        unsigned long long d = (cur ^ ((cur << 1) | prev)) & valid_bits(w, n_px);
-        while (d) {
-            const int b = __ffsll((long long)d) - 1;
-            if (pos < max_runs) T[pos] = (unsigned int)(w * 64 + b);
-            ++pos;
-            d &= d - 1;
-        }
-    }
-    __threadfence_block();
-    __syncthreads();
-    // counts[j] = T[j] - T[j-1] (T[-1] = 0); last count = n_px - T[last]
-    const int nr = total + 1;
-    for (int j = tid; j < min(nr, max_runs); j += 1024) {
-        const unsigned int hi = (j < total) ? T[j] : (unsigned int)n_px;
-        const unsigned int lo = j ? T[j - 1] : 0u;
-        cnt[j] = hi - lo;
-    }
-    if (tid == 0) n_runs[i] = nr;
-    (void)block_base;
+    const int nr = stm_rle_runs_block(bits + (int64_t)i * words, words, n_px, trans_ws + (int64_t)i * max_runs, counts + (int64_t)i * max_runs,
+                                      max_runs, wave_tot);
+    if (threadIdx.x == 0) n_runs[i] = nr;
 }
 
 }  // namespace

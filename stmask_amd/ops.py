@@ -1125,6 +1125,65 @@ def mask_resize_rle(masks, crop_h, crop_w, out_h, out_w, thr=0.5, max_runs=4096)
     return counts, n_runs
 
 
+def output_frames(frames):
+    """[(crop_h, crop_w, out_h, out_w, s_w, s_h)] (s_w = img_w / pad_w, s_h = img_h / pad_h as Python floats) -> the stm_output_frame array of
+    output_stage_multi.  The fp32 values are the ones torch itself forms on the device from a Python float: a comparison rounds it to fp32,
+    tensor / float multiplies by the fp32 reciprocal of that fp32 value."""
+    import numpy as np
+    arr = (_lib.OutputFrame * max(1, len(frames)))()
+    one = np.float32(1.0)
+    for i, (crop_h, crop_w, out_h, out_w, s_w, s_h) in enumerate(frames):
+        sw, sh = np.float32(s_w), np.float32(s_h)
+        arr[i] = _lib.OutputFrame(int(crop_h), int(crop_w), int(out_h), int(out_w), float(sw), float(sh), float(one / sw), float(one / sh))
+    return arr
+
+
+def output_stage_bytes(n, arena_bytes):
+    """Bytes of the step buffer of n rows: header | n records | arena."""
+    return ctypes.sizeof(_lib.OutputHeader) + n * ctypes.sizeof(_lib.OutputRow) + int(arena_bytes)
+
+
+def output_stage_multi(masks, frame_of_row, score, cls, box_id, box, frames, row_keep=None, score_threshold=0.0, thr=0.5, max_runs=4096,
+                       out=None, arena_bytes=None, workspace=None):
+    """The output stage of a whole step (stm_output_stage_multi_f32, include/stmask_hip_output.h): masks [N,mh,mw] fp32 and, per row,
+    frame_of_row int32, score fp32, cls / box_id int32 or int64, box [N,4] fp32 normalised, row_keep uint8 / bool or None; frames: a list of
+    (crop_h, crop_w, out_h, out_w, s_w, s_h) or what output_frames made of one.  -> the step buffer, uint8 on the device: stm_output_header |
+    N stm_output_row | string arena (`out`, or a new tensor with arena_bytes of arena).  No host wait."""
+    _dev(masks, frame_of_row, score, cls, box_id, box, row_keep, out, workspace)
+    masks, score, box = _f32c(masks), _f32c(score), _f32c(box)
+    if masks.dim() != 3 or box.dim() != 2 or box.shape[1] != 4:
+        raise StmError(f"output_stage_multi: masks must be [N,mh,mw] and box [N,4], got {tuple(masks.shape)} and {tuple(box.shape)}")
+    n, mh, mw = masks.shape
+    if frame_of_row.dtype != torch.int32:
+        raise StmError(f"output_stage_multi: frame_of_row must be int32, got {frame_of_row.dtype}")
+    for name, t in (("cls", cls), ("box_id", box_id)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise StmError(f"output_stage_multi: {name} must be int32 or int64, got {t.dtype}")
+    if row_keep is not None:
+        if row_keep.dtype not in (torch.uint8, torch.bool):
+            raise StmError(f"output_stage_multi: row_keep must be uint8 or bool, got {row_keep.dtype}")
+        row_keep = row_keep.contiguous()
+    frame_of_row, cls, box_id = frame_of_row.contiguous(), cls.contiguous(), box_id.contiguous()
+    if any(t.numel() != n for t in (frame_of_row, score, cls, box_id) + (() if row_keep is None else (row_keep,))) or box.shape[0] != n:
+        raise StmError(f"output_stage_multi: every per-row tensor must have {n} rows")
+    n_frames = len(frames)
+    if not isinstance(frames, ctypes.Array):
+        frames = output_frames(frames)
+    if out is None:
+        out = torch.empty(output_stage_bytes(n, max(4096, 1024 * n) if arena_bytes is None else arena_bytes), dtype=torch.uint8, device=masks.device)
+    if out.dtype != torch.uint8 or not out.is_contiguous():
+        raise StmError("output_stage_multi: out must be a contiguous uint8 tensor")
+    if n == 0:
+        out[:ctypes.sizeof(_lib.OutputHeader)].zero_()          # (the library launches nothing for no rows: an empty header says so)
+        return out
+    max_px = max((int(f.out_h) * int(f.out_w) for f in frames[:n_frames]), default=0)
+    ws = workspace if workspace is not None else _workspace(_lib.lib().stm_output_stage_workspace_bytes(n, max_px, max_runs), masks.device, "outstage")
+    call("stm_output_stage_multi_f32", _p(masks), n, mh, mw, _p(frame_of_row), _p(score), _p(cls), int(cls.dtype == torch.int64), _p(box_id),
+         int(box_id.dtype == torch.int64), _p(box), _p(row_keep), ctypes.cast(frames, c_p), n_frames, float(score_threshold), float(thr),
+         int(max_runs), _p(out), out.numel(), _p(ws), ws.numel(), _stream())
+    return out
+
+
 def conv_pack_weights(weight, planes=3, tile_n=128, fmt=0, wscale=None):
     """OIHW fp32 weights -> the pre-split, pre-tiled image the convolution kernels stream (done once per layer).
     tile_n = 64 packs for the 128 x 64-tile planar kernel (stm_conv_geom.tile_n must say so too).

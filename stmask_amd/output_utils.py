@@ -6,6 +6,9 @@ The reference brings every full-resolution mask to the host (``masks[i].cpu()``)
 resize + threshold + run extraction run on the device (``stm_mask_resize_rle_f32``) and only the run lengths cross PCIe.
 The 5-bit string packing of COCO RLE (pycocotools maskApi.c ``rleToString``) is a few hundred bytes per mask and stays
 on the host.
+
+``OutputStageBatch`` (below) is the same stage for all frames of a step at once, string packing included, in a fixed number of
+launches and one device -> host copy (``stm_output_stage_multi_f32``); ``postprocess_ytbvis`` stays the per-frame form.
 """
 import torch
 
@@ -140,3 +143,154 @@ def postprocess_ytbvis(det_output, img_meta, interpolation_mode="bilinear", disp
         dets["segm"] = encode_masks(masks, crop_h, crop_w, out_h, out_w)
     dets["box"] = pixel_boxes(dets["box"], img_meta, preserve_aspect_ratio)
     return dets
+
+
+# ---- the batched output stage: every frame of a step at once (ops.output_stage_multi, include/stmask_hip_output.h) ----
+
+def frame_geometry(img_meta, mask_h, mask_w, preserve_aspect_ratio=True):
+    """(crop_h, crop_w, out_h, out_w, s_w, s_h) of one frame, as select_rows / pixel_boxes form them from its img_meta."""
+    ori_h, ori_w = img_meta["ori_shape"][:2]
+    img_h, img_w = img_meta["img_shape"][:2]
+    pad_h, pad_w = img_meta["pad_shape"][:2]
+    s_w, s_h = img_w / pad_w, img_h / pad_h
+    out_h, out_w = (ori_h, ori_w) if preserve_aspect_ratio else (img_h, img_w)
+    return int(s_h * mask_h), int(s_w * mask_w), out_h, out_w, s_w, s_h
+
+
+def unpack_step_buffer(buf, metas, classes, reencode=None):
+    """The host half of the batched output stage, a pure function of the copied bytes.  buf: uint8 numpy array, stm_output_header | records |
+    arena (the arena at least header.total_bytes long, unless a row says arena overflow).  metas: per frame its img_meta (with video_id and
+    frame_id), or None for a frame that is not there (an idle slot).  -> per frame the dict bbox2result_with_id(postprocess_ytbvis(...)) gives
+    (same keys in the same order, same value types), None for a None meta.  A kept row whose record carries the run-overflow bit has no string
+    on the device: reencode(row, frame) -> its RLE dict.  Raises StmError for a record no caller should see (arena overflow, a frame index
+    outside metas): OutputStageBatch resubmits the former before it unpacks."""
+    import ctypes
+    import numpy as np
+    from . import _lib
+    hb, rb = ctypes.sizeof(_lib.OutputHeader), ctypes.sizeof(_lib.OutputRow)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    n = int(buf[:hb].view(np.int32)[0]) if buf.size >= hb else 0
+    records = [None if m is None else {"video_id": m["video_id"], "frame_id": m["frame_id"]} for m in metas]
+    if n == 0:
+        return records
+    if buf.size < hb + n * rb:
+        raise _lib.StmError(f"unpack_step_buffer: {buf.size} bytes cannot hold {n} records")
+    table = buf[hb:hb + n * rb].view(np.int32).reshape(n, rb // 4)
+    arena = buf[hb + n * rb:]
+    frame, status, str_off, str_len, cls, box_id = (table[:, c] for c in (0, 1, 3, 4, 5, 6))
+    scores = np.ascontiguousarray(table[:, 7]).view(np.float32)
+    boxes = table[:, 8:12].astype(np.int64)
+    if np.any(status & _lib.ROW_BAD_FRAME) or np.any(status & _lib.ROW_ARENA_OVERFLOW):
+        raise _lib.StmError("unpack_step_buffer: a record carries the bad-frame or the arena-overflow bit")
+    labels = cls.astype(np.int64)
+    ids = box_id.astype(np.int64)
+    for r in np.flatnonzero(((status & _lib.ROW_KEPT) != 0) & (ids >= 0)):     # row order: a frame's objects in the order of its rows
+        f = int(frame[r])
+        if not 0 <= f < len(metas) or metas[f] is None:
+            raise _lib.StmError(f"unpack_step_buffer: row {r} belongs to frame {f}, which has no img_meta")
+        if status[r] & _lib.ROW_RUN_OVERFLOW:
+            if reencode is None:
+                raise _lib.StmError(f"unpack_step_buffer: row {r} has more runs than the device buffer held and no reencode hook was given")
+            segm = reencode(int(r), f)
+        else:
+            o, l = int(str_off[r]), int(str_len[r])
+            if o + l > arena.size:
+                raise _lib.StmError(f"unpack_step_buffer: row {r}'s string ends at byte {o + l} of an arena of {arena.size}")
+            segm = {"size": [metas[f]["ori_shape"][0], metas[f]["ori_shape"][1]], "counts": arena[o:o + l].tobytes()}
+        entry = {"bbox": boxes[r], "score": scores[r], "segm": segm, "label": labels[r], "category": classes[labels[r] - 1]}
+        records[f][ids[r]] = entry
+    return records
+
+
+class OutputStageBatch:
+    """Soft masks -> finished per-frame records for all frames of a step, the host one step behind the device.
+
+    ticket = submit(rows, metas): rows = what BatchedClipPipeline.tracked_rows() returns (dict of flat device tensors: mask, box, score, class,
+    frame, box_id, keep; or None for no rows), metas = per frame its img_meta with video_id / frame_id (None: idle).  Enqueues the kernels on
+    the current stream and one copy of header + records + a prefix of the arena into pinned memory on a side stream; does not wait.
+    collect(ticket) waits for that copy and returns per frame what postprocess_ytbvis -> bbox2result_with_id return (unpack_step_buffer).
+    Two device buffers and two pinned buffers alternate: at most two tickets may be outstanding."""
+
+    def __init__(self, classes, score_threshold=0, max_runs=4096, arena_bytes=1 << 20, prefix_bytes=1 << 16, thr=0.5):
+        self.classes, self.score_threshold, self.max_runs, self.thr = classes, score_threshold, int(max_runs), thr
+        self.arena_bytes, self.prefix_bytes = int(arena_bytes), int(prefix_bytes)
+        self.largest_total = 0           # the largest header.total_bytes seen: the copied arena prefix is sized from it
+        self._dev = [None, None]
+        self._pin = [None, None]
+        self._side = None
+        self._n_submitted = 0
+        self.bytes_copied = 0            # device -> host bytes of all collects so far
+        self.resubmits = 0               # steps run again with a larger arena
+        self.tail_copies = 0             # collects whose strings ran past the copied prefix
+        self.reencoded_rows = 0
+
+    def _buffers(self, slot, n, device):
+        need = ops.output_stage_bytes(n, self.arena_bytes)
+        room = ops.output_stage_bytes(n + n // 2, self.arena_bytes)         # (the tracked set grows from step to step: grow in strides)
+        if self._dev[slot] is None or self._dev[slot].numel() < need or self._dev[slot].device != device:
+            self._dev[slot] = torch.empty(room, dtype=torch.uint8, device=device)
+        if self._pin[slot] is None or self._pin[slot].numel() < need:
+            self._pin[slot] = torch.empty(room, dtype=torch.uint8).pin_memory()
+        return self._dev[slot][:need], self._pin[slot]
+
+    def _launch(self, t):
+        rows, n = t["rows"], t["n"]
+        dev_buf, pin = self._buffers(t["slot"], n, rows["mask"].device)
+        ops.output_stage_multi(rows["mask"], rows["frame"], rows["score"], rows["class"], rows["box_id"], rows["box"], t["frames"],
+                               row_keep=rows.get("keep"), score_threshold=self.score_threshold, thr=self.thr, max_runs=self.max_runs, out=dev_buf)
+        head = ops.output_stage_bytes(n, 0)
+        prefix = min(self.arena_bytes, max(self.prefix_bytes, self.largest_total + self.largest_total // 2))
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=dev_buf.device)
+        ready = torch.cuda.Event()
+        ready.record()
+        with torch.cuda.stream(self._side):
+            self._side.wait_event(ready)
+            pin[:head + prefix].copy_(dev_buf[:head + prefix], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+        t.update(dev=dev_buf, pin=pin, head=head, copied=head + prefix, done=done)
+
+    def submit(self, rows, metas):
+        metas = list(metas)
+        n = 0 if rows is None else int(rows["mask"].shape[0])
+        t = {"slot": self._n_submitted % 2, "n": n, "metas": metas, "rows": rows}
+        self._n_submitted += 1
+        if n:
+            mh, mw = rows["mask"].shape[1:]
+            geo = [(1, 1, 1, 1, 1.0, 1.0) if m is None else frame_geometry(m, mh, mw) for m in metas]   # (no row may name an idle frame)
+            t["frames"] = ops.output_frames(geo)
+            t["geo"] = geo
+            self._launch(t)
+        return t
+
+    def collect(self, t):
+        import ctypes
+        from . import _lib
+        if t["n"] == 0:
+            return [None if m is None else {"video_id": m["video_id"], "frame_id": m["frame_id"]} for m in t["metas"]]
+        while True:
+            t["done"].synchronize()
+            host = t["pin"].numpy()
+            self.bytes_copied += t["copied"]
+            hdr = _lib.OutputHeader.from_buffer_copy(host[:ctypes.sizeof(_lib.OutputHeader)].tobytes())
+            self.largest_total = max(self.largest_total, hdr.total_bytes)
+            if hdr.total_bytes <= hdr.arena_bytes:
+                break
+            # the strings of this step do not fit the device arena: grow it and run the step's output stage again
+            self.arena_bytes = max(2 * self.arena_bytes, 2 * hdr.total_bytes)
+            self.resubmits += 1
+            self._launch(t)
+        end = t["head"] + hdr.total_bytes
+        if end > t["copied"]:                                    # the strings ran past the copied prefix: fetch the rest
+            t["pin"][t["copied"]:end].copy_(t["dev"][t["copied"]:end])
+            self.bytes_copied += end - t["copied"]
+            self.tail_copies += 1
+        rows, geo = t["rows"], t["geo"]
+
+        def reencode(r, f):
+            self.reencoded_rows += 1
+            crop_h, crop_w, out_h, out_w = geo[f][:4]
+            return encode_masks(rows["mask"][r:r + 1], crop_h, crop_w, out_h, out_w, self.thr, self.max_runs)[0]
+
+        return unpack_step_buffer(host[:end], t["metas"], self.classes, reencode)

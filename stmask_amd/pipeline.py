@@ -587,3 +587,28 @@ class BatchedClipPipeline(TrunkRunner):
             d["box_ids"] = k
             outs.append(d)
         return outs
+
+    def tracked_rows(self):
+        """The rows detections() would report for the last step, flat over all clips and without a host wait -- the input of the batched output
+        stage (output_utils.OutputStageBatch): {"mask" [N,mh,mw] (soft; binary 0/1 on the non-TF path, as detections() hands them out), "box"
+        [N,4], "score" [N], "class" [N], "frame" int32 [N] (the clip), "box_id" [N], "keep" bool [N]}, or None when there are no rows.  With
+        temporal fusion the rows are the whole tracked set and "keep" is the rule detections() applies (track_TF.py:158-165); a kept row's
+        box_id is what detections() reports: its index among its clip's tracked rows.  box and score are copies (the next step shifts the
+        tracked set in place)."""
+        if not self.tf:
+            if self._last is None:
+                return None
+            det, det_mask, r_dev, b_dev, id_dev = self._last
+            if r_dev.numel() == 0:
+                return None
+            return {"mask": det_mask.index_select(0, r_dev).gt(0.5).float(), "box": det["box"].index_select(0, r_dev),
+                    "score": det["score"].index_select(0, r_dev), "class": det["class"].index_select(0, r_dev),
+                    "frame": b_dev.to(torch.int32), "box_id": id_dev, "keep": torch.ones_like(r_dev, dtype=torch.bool)}
+        prev = self.prev
+        if prev is None or sum(self.prev_n) == 0:
+            return None
+        mask, clip = prev["mask"], prev["clip"].to(torch.int32)
+        keep = (self._tm_dev <= 10) & (mask.gt(0.5).sum([1, 2]) > 1) & (prev["score"] > self.cfg.eval_conf_thresh)
+        box_id = torch.arange(clip.shape[0], device=clip.device, dtype=torch.int32) - self._off_dev.index_select(0, clip.long())
+        return {"mask": mask, "box": prev["box"].clone(), "score": prev["score"].clone(), "class": prev["class"], "frame": clip, "box_id": box_id,
+                "keep": keep}

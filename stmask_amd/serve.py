@@ -10,6 +10,10 @@ same slot on the next step (``is_first[b] = True``; the other slots keep their t
 The whole schedule is known before the first step, so the batches of the next ``pipe.prefetch_depth`` steps are pre-processed ahead and handed
 to the pipeline as ``next_frames`` (the same tensor objects the later steps pass as ``frames``): their trunks run beside the current step.
 
+``VideoBatcher(..., batched_output=True)`` replaces the per-slot output stage by one batched device stage per step
+(``pipeline.tracked_rows()`` -> ``output_utils.OutputStageBatch``): step s is submitted, step s + 1 runs, then step s's records are read, so the
+host never waits for the step it has just enqueued.  The records are the same.
+
 ``run(..., on_frame=f)`` also draws every busy slot's tracked instances onto that slot's own source frame on the device (display.render_batch,
 source mode: one launch per step) and calls f(video_id, frame_id, frame_u8) per slot; without it nothing is drawn.
 """
@@ -70,9 +74,11 @@ class VideoBatcher:
 
     videos: sequence of (video_id, frames_u8) with frames_u8 uint8 [T_i, H_i, W_i, 3] on the GPU or in pinned host memory (T_i >= 1; sizes may
     differ between videos).  prep(frames, frame_ids) -> (batch, metas) pre-processes one step (default: device_prep); pipeline: the
-    BatchedClipPipeline to drive (default: a new one on `net`) -- both injectable, so the scheduling can be exercised without a GPU."""
+    BatchedClipPipeline to drive (default: a new one on `net`) -- both injectable, so the scheduling can be exercised without a GPU; so is
+    output_stage (submit(rows, metas) -> ticket, collect(ticket) -> per-slot records), which batched_output=True uses."""
 
-    def __init__(self, net, n_slots, use_graph=True, lookahead=None, prep=None, pipeline=None, classes=None):
+    def __init__(self, net, n_slots, use_graph=True, lookahead=None, prep=None, pipeline=None, classes=None, batched_output=False,
+                 output_stage=None):
         if pipeline is None:
             from .pipeline import BatchedClipPipeline
             pipeline = BatchedClipPipeline(net, n_slots)
@@ -81,6 +87,12 @@ class VideoBatcher:
         self.lookahead = lookahead
         self.prep = prep if prep is not None else device_prep
         self.classes = classes if classes is not None else ["class_%d" % i for i in range(1, net.cfg.num_classes)]
+        # batched_output: one output stage per step for all busy slots (output_utils.OutputStageBatch on pipeline.tracked_rows(): a fixed number
+        # of launches and one device -> host copy, read one step late) instead of postprocess_ytbvis per slot; the records are the same
+        self.batched_output = bool(batched_output)
+        self.output_stage = output_stage
+        if self.batched_output and self.output_stage is None:
+            self.output_stage = output_utils.OutputStageBatch(self.classes)
         self.steps = 0            # steps of the last run
         self.busy_slot_steps = 0  # active (slot, step) pairs of the last run
 
@@ -105,6 +117,12 @@ class VideoBatcher:
 
         frame_results = [[] for _ in videos]
         self.steps, self.busy_slot_steps = len(plan), 0
+        pending = None                                     # batched output: (ticket, plan row) of the step whose records are still on the device
+
+        def collect(ticket, row):
+            for c, rec in zip(row, self.output_stage.collect(ticket)):
+                if c is not None:
+                    frame_results[c[0]].append(rec)
         for s, row in enumerate(plan):
             while len(ready) < 1 + depth and s + len(ready) < len(plan):
                 ready.append(prepare(s + len(ready)))
@@ -113,7 +131,14 @@ class VideoBatcher:
             active = [c is not None for c in row]
             nxt = [r[0] for r in list(ready)[:depth]] if depth > 0 else None
             self.pipe.step(batch, is_first=is_first, next_frames=nxt or None, active=active)
-            dets = self.pipe.detections()
+            if self.batched_output:
+                # this step's output stage is enqueued behind its kernels; the previous step's records are read while both run
+                step_metas = [None if c is None else dict(metas[b], video_id=videos[c[0]][0], frame_id=c[1]) for b, c in enumerate(row)]
+                ticket = self.output_stage.submit(self.pipe.tracked_rows(), step_metas)
+                if pending is not None:
+                    collect(*pending)
+                pending = (ticket, row)
+            dets = self.pipe.detections() if on_frame is not None or not self.batched_output else None
             if on_frame is not None:
                 busy = [b for b, c in enumerate(row) if c is not None]
                 dev = batch.device
@@ -126,6 +151,8 @@ class VideoBatcher:
                 if c is None:
                     continue
                 self.busy_slot_steps += 1
+                if self.batched_output:
+                    continue
                 vid = videos[c[0]][0]
                 meta = dict(metas[b], video_id=vid, frame_id=c[1])
                 if dets[b] and dets[b]["box"].shape[0]:
@@ -133,6 +160,8 @@ class VideoBatcher:
                     frame_results[c[0]].append(eval_utils.bbox2result_with_id(post, meta, self.classes))
                 else:
                     frame_results[c[0]].append({"video_id": vid, "frame_id": c[1]})     # (what bbox2result_with_id gives an empty frame)
+        if pending is not None:
+            collect(*pending)                              # the last step
         order = sorted(range(len(videos)), key=lambda i: videos[i][0])
         flat = [r for i in order for r in frame_results[i]]   # per video in frame order, videos by video_id (results2json_videoseg's input order)
         return eval_utils.video_records(flat) if out_file is None else eval_utils.results2json_videoseg(flat, out_file)
