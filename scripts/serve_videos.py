@@ -7,9 +7,11 @@ occupancy (active slot-steps / all slot-steps) and the number of videos and fram
 device each step (VideoBatcher.run(on_frame=...), stmask_amd.display source mode); the annotated frames are dropped.  --batched-output: the
 output stage of a step is one batched device stage read one step late (VideoBatcher(batched_output=True)) instead of postprocess_ytbvis per
 slot.  After the timed queue the same queue runs once more with the synchronising calls wrapped (Tensor.cpu / tolist / item / nonzero,
-event and device synchronize): host_waits_per_step and d2h_bytes_per_step of the chosen mode come from that run.
+event and device synchronize): host_waits_per_step and d2h_bytes_per_step of the chosen mode come from that run.  --device-tracker: the
+pipeline keeps the tracker's state and decisions on the device (BatchedClipPipeline(device_tracker=True)).
 
-usage: python scripts/serve_videos.py [--videos 64] [--min-frames 8] [--max-frames 36] [--slots 8 32] [--render] [--batched-output]"""
+usage: python scripts/serve_videos.py [--videos 64] [--min-frames 8] [--max-frames 36] [--slots 8 32] [--render] [--batched-output]
+                                      [--device-tracker]"""
 import argparse
 import json
 import os
@@ -23,6 +25,7 @@ from stmask_amd import synthetic  # noqa: E402
 from stmask_amd.config import get_cfg  # noqa: E402
 from stmask_amd.fuse import optimize_for_inference  # noqa: E402
 from stmask_amd.model import STMask  # noqa: E402
+from stmask_amd.pipeline import BatchedClipPipeline  # noqa: E402
 from stmask_amd.serve import VideoBatcher  # noqa: E402
 
 SIZES = [(720, 1280), (480, 854)]
@@ -82,8 +85,9 @@ class WaitCounter:
         return False
 
 
-def measure(net, slots, queue, warm, render=False, batched_output=False):
-    vb = VideoBatcher(net, slots, use_graph=True, batched_output=batched_output)
+def measure(net, slots, queue, warm, render=False, batched_output=False, device_tracker=False):
+    pipe = BatchedClipPipeline(net, slots, device_tracker=True) if device_tracker else None
+    vb = VideoBatcher(net, slots, use_graph=True, batched_output=batched_output, pipeline=pipe)
     on_frame = (lambda vid, fid, img: None) if render else None
     vb.run(warm, on_frame=on_frame)                   # warm-up queue: graph capture, workspaces, prior cache
     torch.cuda.synchronize()
@@ -97,7 +101,7 @@ def measure(net, slots, queue, warm, render=False, batched_output=False):
         vb.run(queue, on_frame=on_frame)
     torch.cuda.synchronize()
     d2h = wc.bytes + (vb.output_stage.bytes_copied - copied0 if batched_output else 0)
-    return {"slots": slots, "batched_output": batched_output, "host_waits_per_step": round(wc.waits / vb.steps, 1),
+    return {"slots": slots, "batched_output": batched_output, "device_tracker": device_tracker, "host_waits_per_step": round(wc.waits / vb.steps, 1),
             "d2h_bytes_per_step": round(d2h / vb.steps), "frames_per_s": round(frames / dt, 1), "occupancy": round(vb.occupancy(), 4), "videos": len(queue),
             "frames": frames, "steps": vb.steps, "graph": vb.pipe.graph_active, "seconds": round(dt, 3), "render": render}
 
@@ -112,6 +116,7 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--render", action="store_true", help="draw every served frame on the device (display source mode)")
     ap.add_argument("--batched-output", action="store_true", help="one batched output stage per step, read one step late")
+    ap.add_argument("--device-tracker", action="store_true", help="tracker state and decisions on the device (BatchedClipPipeline(device_tracker=True))")
     a = ap.parse_args()
     dev = "cuda"
     net = build_net(a.config, dev)
@@ -119,5 +124,5 @@ if __name__ == "__main__":
     rows = []
     for s in a.slots:
         warm = make_queue(max(s, 4), a.min_frames, a.min_frames + 4, a.seed + 1, dev)
-        rows.append(measure(net, s, queue, warm, a.render, a.batched_output))
+        rows.append(measure(net, s, queue, warm, a.render, a.batched_output, a.device_tracker))
     print(json.dumps({"tool": "serve_videos", "config": a.config, "runs": rows}))

@@ -157,6 +157,11 @@ OUTPUT_SIGNATURES = {
     "stm_output_stage_workspace_bytes": ("z", "ili"),
     "stm_output_stage_multi_f32": ("i", "piiipppipipppiffipzpzp"),
 }
+# include/stmask_hip_tracker.h, the third header (tests/test_abi_tracker.py): the tracker's decisions on the device
+TRACKER_SIGNATURES = {
+    "stm_track_resolve_tf": ("i", "pppppiiiipppp"),
+    "stm_track_drop_plan": ("i", "ppiippp"),
+}
 
 
 class StmError(RuntimeError):
@@ -228,7 +233,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback on the product path.")
         _lib = ctypes.CDLL(LIB_PATH)
-        tables = {**SIGNATURES, **OUTPUT_SIGNATURES}
+        tables = {**SIGNATURES, **OUTPUT_SIGNATURES, **TRACKER_SIGNATURES}
         missing = [n for n in tables if not hasattr(_lib, n)]
         if missing:
             _lib = None

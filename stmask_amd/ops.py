@@ -1584,6 +1584,47 @@ def pack_tracked_bits(bits, score, tracked, offsets, box, cls, mask_coeff, B, to
     return out
 
 
+def _i32c(who, *ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise StmError(f"{who}: expected contiguous int32 tensors, got {t.dtype}")
+
+
+# ---- the tracker's decisions on the device (csrc/track_resolve.hip, include/stmask_hip_tracker.h) ----------------------------------------
+def track_resolve_tf(match, det_score, det_count, prev_offsets, prev_tm, n_prev, n_det, cap=0):
+    """track_host.match_tf on the device, for all clips in one launch -> (plan, new offsets [B + 1], new counters), the plan and the counters
+    at the capacity n_prev + n_det: indices into cat(tracked rows, detection rows) clip after clip, compact from entry 0, then zeros (index 0
+    is a valid row, so gather_rows2 may run over the whole plan; new offsets[B] says how many rows are real).  match int32 [n_det] (0 or 1 +
+    the tracked row) or None = all 0; det_score fp32 [n_det]; det_count int32 [B]; prev_offsets int32 [B + 1]; prev_tm int32 [n_prev] (None
+    when n_prev is 0).  No host read."""
+    _dev(match, det_score, det_count, prev_offsets, prev_tm)
+    _i32c("track_resolve_tf", match, det_count, prev_offsets, prev_tm)
+    B, dev = det_count.shape[0], det_count.device
+    if prev_offsets.shape[0] != B + 1 or (match is not None and match.shape[0] != n_det) or (n_det and det_score.shape[0] != n_det) or (
+            n_prev and prev_tm.shape[0] < n_prev):
+        raise StmError("track_resolve_tf: tensor sizes do not fit n_prev / n_det / the clip count")
+    plan = torch.empty(n_prev + n_det, dtype=torch.int32, device=dev)
+    new_tm = torch.empty(n_prev + n_det, dtype=torch.int32, device=dev)
+    new_off = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    call("stm_track_resolve_tf", _p(match), _p(_f32c(det_score)) if n_det else c_p(0), _p(det_count), _p(prev_offsets), _p(prev_tm) if n_prev else c_p(0),
+         B, n_prev, n_det, int(cap), _p(plan), _p(new_off), _p(new_tm), _stream())
+    return plan, new_off, new_tm
+
+
+def track_drop_plan(offsets, drop, n_keep):
+    """track_host.keep_rows on the device -> (rows that stay int32 [n_keep], new offsets [B + 1]).  offsets int32 [B + 1]; drop int32 [B]
+    (non-zero: the clip's rows leave); n_keep: the kept clips' rows in all (the host knows every clip's row count)."""
+    _dev(offsets, drop)
+    _i32c("track_drop_plan", offsets, drop)
+    B = drop.shape[0]
+    if offsets.shape[0] != B + 1:
+        raise StmError("track_drop_plan: offsets must hold one entry more than drop")
+    keep = torch.empty(n_keep, dtype=torch.int32, device=offsets.device)
+    new_off = torch.empty(B + 1, dtype=torch.int32, device=offsets.device)
+    call("stm_track_drop_plan", _p(offsets), _p(drop), B, n_keep, _p(keep), _p(new_off), _stream())
+    return keep, new_off
+
+
 def resize_bilinear_planes(x_nhwc, size, fmt=0):
     """F.interpolate(x, size=size, mode="bilinear", align_corners=False) of an fp32 NHWC tensor [B,H,W,C], returned as planes
     [P, C/32, B*Ho*Wo, 32] (split_planes' format) without the fp32 intermediate."""

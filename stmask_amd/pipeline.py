@@ -138,9 +138,10 @@ class _TrackedRows(dict):
 
 
 class BatchedClipPipeline(TrunkRunner):
-    """All clips' tracker state concatenated (rows sorted by clip); per-clip row ranges are host integers."""
+    """All clips' tracker state concatenated (rows sorted by clip); per-clip row ranges are host integers.  device_tracker=True (temporal
+    fusion only): the tracker's counters and decisions stay on the device, the row counts reach the host one step late (_settle)."""
 
-    def __init__(self, net, n_clips):
+    def __init__(self, net, n_clips, device_tracker=False):
         # temporal-fusion configs (self.tf): Detect_TF + Track_TF (CandidateShift, soft masks, the keep rule) -- _step_tf; without the module the
         # reference runs Detect + Track (detection.py:98-137, track.py:56-179: binary masks, the (mask_ious > 0.3).sum() < 2 update gate, the
         # frame's own detections as output) -- _step_nontf
@@ -149,6 +150,18 @@ class BatchedClipPipeline(TrunkRunner):
         self.fell_back = False
         self._last = None           # non-TF: the last step's detections (rows, ids, clip ranges) for detections()
         self.t = 0
+        # device_tracker: the tracker's per-row state lives on the device alone (_tm_dev, _off_dev) and its decisions are kernels
+        # (ops.track_resolve_tf, ops.track_drop_plan): no per-row host structure is built in a step.  The new row counts come back one step
+        # late (_settle); until then the row tensors stand at their capacity, rows + detections.  Opt-in; temporal-fusion nets only.
+        self.device_tracker = bool(device_tracker)
+        if self.device_tracker and not self.tf:
+            raise ValueError("BatchedClipPipeline: device_tracker needs a temporal-fusion net (the tracker without the module decides on the host)")
+        self._unsettled = None      # device_tracker: (pinned new offsets [B + 1], event) of a step whose row counts the host has not read yet
+        self._off_pin = [None, None]
+        self._n_resolved = 0
+        self._cnt_dev = None        # device_tracker: this step's detection counts as they stand on the device (after the clamp and the idle mask)
+        self._drop_pin = []         # device_tracker: ring of (pinned int32 [B], event of the copy that last read it) for the per-clip drop flags
+        self._n_drops = 0
         self.prev = None            # dict of concatenated row tensors
         self.prev_n = [0] * n_clips  # tracked instances per clip
         self.prev_feat = None       # (P4 [B,256,h,w], T2S [B,256,h,w]) of the previous frame
@@ -164,6 +177,62 @@ class BatchedClipPipeline(TrunkRunner):
         # (the best-scoring ones: Fast NMS returns them sorted) and at most n tracked instances per clip (an unmatched detection
         # opens a new track only while the clip holds fewer).  0 = the reference's behaviour.
         self.max_instances = 0
+
+    # -- the state a reader outside a step sees: settled first (a no-op without device_tracker) ----------------------------
+    @property
+    def prev(self):
+        self._settle()
+        return self._prev
+
+    @prev.setter
+    def prev(self, v):
+        self._prev = v
+
+    @property
+    def prev_n(self):
+        self._settle()
+        return self._prev_n
+
+    @prev_n.setter
+    def prev_n(self, v):
+        self._prev_n = v
+
+    @property
+    def tracked(self):
+        """Per clip the frames-since-last-match counters of its rows (host lists; with device_tracker a read-back of _tm_dev)."""
+        if not self.device_tracker:
+            return self._tracked
+        self._settle()
+        if self._prev is None or self._tm_dev is None or sum(self._prev_n) == 0:
+            return [[] for _ in range(self.B)]
+        tm, off = self._tm_dev.tolist(), track_host.clip_offsets(self._prev_n)
+        return [tm[off[b]:off[b + 1]] for b in range(self.B)]
+
+    @tracked.setter
+    def tracked(self, v):
+        self._tracked = v
+
+    def _settle(self):
+        """device_tracker: take in the row counts of the last tracker update -- wait for the copy of its new offsets, set prev_n, and narrow
+        every row tensor, the bit words, the counters and a deferred mask plan to the real rows (views: nothing is copied).  Runs at the start
+        of the next step and whenever prev / prev_n / tracked are read."""
+        pend = self._unsettled
+        if pend is None:
+            return
+        self._unsettled = None
+        buf, ev = pend
+        ev.synchronize()
+        off = buf.tolist()
+        self._prev_n = [off[b + 1] - off[b] for b in range(self.B)]
+        R, prev = off[-1], self._prev
+        if prev is None:                                    # (the set was taken away from outside in the meantime)
+            return
+        for k in list(dict.keys(prev)):
+            dict.__setitem__(prev, k, dict.__getitem__(prev, k)[:R])
+        if prev._deferred is not None:
+            a, b_, plan, n_prev, host_plan = prev._deferred
+            prev._deferred = (a, b_, plan[:R], n_prev, host_plan)
+        self._bits, self._tm_dev = self._bits[:R], self._tm_dev[:R]
 
     # -- stage helpers ------------------------------------------------------------------------------------------------
     def _roi_feats(self, P4_prev, P4, T2S_prev, T2S, rois):
@@ -218,6 +287,9 @@ class BatchedClipPipeline(TrunkRunner):
         # masks of the shifted instances on the CURRENT prototypes, and their > 0.5 bits for this step's mask IoU (one pass)
         prev["mask"], self._prev_bits = ops.lincomb_sigmoid_crop_bits(proto, prev["mask_coeff"], prev["box"], clip_of_row)
         self.timer.toc("tf_masks")
+        if self.device_tracker:
+            self._tm_dev = self._tm_dev + 1                 # a new tensor: a snapshot of the old one stays valid
+            return
         for b in range(self.B):
             self.tracked[b] = [v + 1 for v in self.tracked[b]]
 
@@ -253,6 +325,7 @@ class BatchedClipPipeline(TrunkRunner):
         first host read (ops.RangeError).  The step is then NOT lost: the tracker state it had touched is put back, the inference graph is rebuilt
         with bf16x3 planes (fp32's range; weights repacked from the same modules, in-process), the step is repeated on it and the pipeline stays
         there (`fell_back`; logged once on stderr).  range_fallback = False restores the raise."""
+        self._settle()
         first, resets = self._first_flags(is_first)
         idle = self._idle_flags(active, frames.device)
         if first:
@@ -312,6 +385,8 @@ class BatchedClipPipeline(TrunkRunner):
         intact for _fall_back.  The clips then hold nothing, and the pn == 0 branches of the tracker apply the first-frame rule to them."""
         if not clips:
             return
+        if self.device_tracker:
+            return self._drop_clips_dev(clips, dev)
         prev_n = list(self.prev_n)
         for b in clips:
             self.tracked[b] = []
@@ -347,6 +422,55 @@ class BatchedClipPipeline(TrunkRunner):
                 kept.defer_mask(m, m[:0], keep_dev, n_rows, keep)
         self.prev, self._bits, self._prev_bits = kept, rows[-1], None
 
+    def _drop_clips_dev(self, clips, dev):
+        """_drop_clips with device_tracker: the keep plan is ops.track_drop_plan's (the host sizes it from the clips' row counts and uploads
+        one flag per clip, cached per pattern), the counters are gathered with the rows, and a deferred soft-mask gather stays deferred with
+        its plan composed on the device."""
+        prev_n = list(self._prev_n)
+        for b in clips:
+            self._prev_n[b] = 0
+        if self._prev is None or not any(prev_n[b] for b in clips):
+            return
+        n_rows, n_keep = sum(prev_n), sum(self._prev_n)
+        if not n_keep:
+            self._prev, self._bits, self._prev_bits, self._tm_dev, self._off_dev = None, None, None, None, None
+            return
+        keep_dev, self._off_dev = ops.track_drop_plan(self._off_dev, self._drop_flags(clips, dev), n_keep)
+        prev = self._prev
+        deferred = prev.deferred_mask() if isinstance(prev, _TrackedRows) else None
+        keys = [k for k in dict.keys(prev) if k != "mask"]
+        srcs = [dict.__getitem__(prev, k) for k in keys] + [self._bits, self._tm_dev]
+        rows = ops.gather_rows2(srcs, [t[:0] for t in srcs], keep_dev, n_rows)
+        kept = _TrackedRows()
+        for k, t in zip(keys, rows[:-2]):
+            kept[k] = t
+        if deferred is not None:
+            a, b_, plan, n_prev, _ = deferred
+            kept.defer_mask(a, b_, plan.index_select(0, keep_dev.long()), n_prev)
+        elif dict.__contains__(prev, "mask"):
+            m = dict.__getitem__(prev, "mask")
+            kept.defer_mask(m, m[:0], keep_dev, n_rows)
+        self._prev, self._bits, self._tm_dev, self._prev_bits = kept, rows[-2], rows[-1], None
+
+    def _drop_flags(self, clips, dev):
+        """Device int32 [B], 1 where the clip drops its rows: B ints through one of four pinned buffers, copied without a wait (a buffer is
+        written again only after the copy that read it has finished: an event four drops old).  Nothing is cached per pattern -- a server's
+        slots reset in ever new combinations."""
+        slot = self._n_drops % 4
+        self._n_drops += 1
+        if len(self._drop_pin) <= slot:
+            self._drop_pin.append([torch.empty(self.B, dtype=torch.int32).pin_memory(), None])
+        buf, ev = self._drop_pin[slot]
+        if ev is not None:
+            ev.synchronize()
+        gone = set(clips)
+        buf.copy_(torch.tensor([int(b in gone) for b in range(self.B)], dtype=torch.int32))
+        flags = buf.to(dev, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._drop_pin[slot][1] = ev
+        return flags
+
     def _range_guarded(self):
         g = getattr(self.net, "_planar", None)
         return g is not None and getattr(self.net, "_planar_planes", "bf16x3") != "bf16x3"
@@ -360,6 +484,8 @@ class BatchedClipPipeline(TrunkRunner):
             rows = tuple(prev[k].clone() for k in ("box", "mask_coeff", "score"))
         # (a per-clip reset replaces the tracked set by new tensors before the step: the set, its counts, bit words and offsets are kept as they were)
         state = (prev, list(self.prev_n), self._bits, self._prev_bits, self._off_dev)
+        if self.device_tracker:
+            return rows, self._tm_dev, self.t, state        # (the counters are a device tensor no step writes in place)
         return rows, [list(t) for t in self.tracked], self.t, state
 
     def _fall_back(self, snap):
@@ -380,7 +506,10 @@ class BatchedClipPipeline(TrunkRunner):
         if rows is not None:
             for k, v in zip(("box", "mask_coeff", "score"), rows):
                 self.prev[k].copy_(v)
-        self.tracked, self.t = tracked, t
+        if self.device_tracker:
+            self._tm_dev, self.t = tracked, t
+        else:
+            self.tracked, self.t = tracked, t
         self.fell_back = True
 
     def _step(self, frames, first, next_frames):
@@ -397,10 +526,16 @@ class BatchedClipPipeline(TrunkRunner):
             cnt = torch.clamp(cnt, max=max_instances)
         if self._idle_dev is not None:
             cnt = cnt.masked_fill(self._idle_dev, 0)                   # inactive slots detect nothing
-        counts, host_scores = ops.counts_to_host(cnt, extra=score)  # host read 1: B counts + the fp16 range flag + the NMS scores
+        if self.device_tracker:
+            counts, host_scores = ops.counts_to_host(cnt), None       # host read 1 without the scores: the resolution reads det["score"] on the device
+            self._cnt_dev = cnt
+        else:
+            counts, host_scores = ops.counts_to_host(cnt, extra=score)  # host read 1: B counts + the fp16 range flag + the NMS scores
         self.timer.toc("detect")
         top_k = idx.shape[1]                              # slots per frame of the detector's outputs (nms_top_k, or max_num_detections per class-wise NMS)
         det = ops.gather_detections(idx, cls, score, box, cnt, mask_coeff, pred["track"], pred["centerness"], sum(counts))
+        if host_scores is None:
+            return det, counts, None
         det_scores = [float(host_scores[b * top_k + j]) for b in range(self.B) for j in range(counts[b])]   # row order of det
         return det, counts, det_scores
 
@@ -449,6 +584,8 @@ class BatchedClipPipeline(TrunkRunner):
         else:
             det["mask"], det_bits = proto.new_zeros(0, proto.shape[1], proto.shape[2]), None
         tmr.toc("det_gather_masks")
+        if self.device_tracker:
+            return self._update_dev(det, det_bits, counts, Pn, P4, T2S, proto, dev)
 
         if self.prev is None:
             # first frame of every clip (track_TF.py:88-93): the detections become the tracked set
@@ -483,6 +620,53 @@ class BatchedClipPipeline(TrunkRunner):
         self.prev_feat = (P4, T2S)
         self.t += 1
         out = self._pack_outputs(dev)
+        tmr.toc("pack")
+        return out
+
+    def _update_dev(self, det, det_bits, counts, Pn, P4, T2S, proto, dev):
+        """The tracker update of _step_tf with device_tracker: the resolution is a kernel on device inputs, the row counts it decides are
+        copied to pinned memory behind it and read by _settle, and this step's gather and packing run at the capacity Pn + D (the plan's
+        padding names row 0; pack_tracked walks the clips' new offsets, so a padding row is never packed).  Nothing here reads self.prev /
+        prev_n through their properties once the resolution is enqueued: that would settle, i.e. wait."""
+        tmr, D = self.timer, sum(counts)
+        cnt = self._cnt_dev
+        if self._prev is None:
+            # first frame of every clip: the detections become the tracked set (counts are host integers already)
+            self._prev, self._bits, self._prev_n = det, det_bits, list(counts)
+            self._off_dev = F.pad(torch.cumsum(cnt, 0, dtype=torch.int32), (1, 0))
+            self._tm_dev = torch.zeros(D, dtype=torch.int32, device=dev)
+        elif D:
+            prev = self._prev
+            match = self._match_scores(det, det_bits, self._prev_bits, proto.shape[1] * proto.shape[2])[0] if Pn else None
+            tmr.toc("match_scores")
+            plan, new_off, new_tm = ops.track_resolve_tf(match, det["score"], cnt, self._off_dev, self._tm_dev if Pn else None, Pn, D, self.max_instances)
+            slot = self._n_resolved % 2
+            self._n_resolved += 1
+            if self._off_pin[slot] is None:
+                self._off_pin[slot] = torch.empty(self.B + 1, dtype=torch.int32).pin_memory()
+            self._off_pin[slot].copy_(new_off, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            keys = tuple(k for k in _ROW_KEYS if k != "mask") + ("clip",)
+            pbits = self._prev_bits if Pn else det_bits[:0]
+            rows = ops.gather_rows2([prev[k] for k in keys] + [pbits], [det[k] for k in keys] + [det_bits], plan, Pn)
+            merged = _TrackedRows()
+            for k, t in zip(keys, rows[:-1]):
+                merged[k] = t
+            merged.defer_mask(prev["mask"], det["mask"], plan, Pn)
+            self._prev, self._bits, self._tm_dev, self._off_dev = merged, rows[-1], new_tm, new_off
+            self._unsettled = (self._off_pin[slot], ev)
+        else:
+            self._bits = self._prev_bits if Pn else None
+        tmr.toc("tracker_update")
+        self.prev_feat = (P4, T2S)
+        self.t += 1
+        prev = self._prev
+        if prev is None or prev["box"].shape[0] == 0:
+            out = torch.zeros(self.B, self.cfg.nms_top_k, DET_COLS, device=dev)
+        else:
+            out = ops.pack_tracked_bits(self._bits, prev["score"], self._tm_dev, self._off_dev, prev["box"], prev["class"], prev["mask_coeff"], self.B,
+                                        self.cfg.nms_top_k, DET_COLS, 10, self.cfg.eval_conf_thresh)
         tmr.toc("pack")
         return out
 
@@ -604,11 +788,13 @@ class BatchedClipPipeline(TrunkRunner):
             return {"mask": det_mask.index_select(0, r_dev).gt(0.5).float(), "box": det["box"].index_select(0, r_dev),
                     "score": det["score"].index_select(0, r_dev), "class": det["class"].index_select(0, r_dev),
                     "frame": b_dev.to(torch.int32), "box_id": id_dev, "keep": torch.ones_like(r_dev, dtype=torch.bool)}
-        prev = self.prev
-        if prev is None or sum(self.prev_n) == 0:
+        prev = self._prev       # (not the property: with device_tracker an unsettled step's rows stand at their capacity, and this must not wait)
+        if prev is None or (prev["box"].shape[0] if self._unsettled is not None else sum(self._prev_n)) == 0:
             return None
         mask, clip = prev["mask"], prev["clip"].to(torch.int32)
         keep = (self._tm_dev <= 10) & (mask.gt(0.5).sum([1, 2]) > 1) & (prev["score"] > self.cfg.eval_conf_thresh)
+        if self._unsettled is not None:                     # padding rows past the new row count (known to the device alone) are never reported
+            keep = keep & (torch.arange(keep.shape[0], device=keep.device, dtype=torch.int32) < self._off_dev[-1])
         box_id = torch.arange(clip.shape[0], device=clip.device, dtype=torch.int32) - self._off_dev.index_select(0, clip.long())
         return {"mask": mask, "box": prev["box"].clone(), "score": prev["score"].clone(), "class": prev["class"], "frame": clip, "box_id": box_id,
                 "keep": keep}
