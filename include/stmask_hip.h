@@ -615,7 +615,20 @@ int stm_head_assemble_f32(const float* const* small, const float* const* trk, co
  * stm_head_patch_mask: zeroes, in place, the pixels of the listed patches that lie outside their level's map.
  * stm_head_assemble_sparse_f32: stm_head_assemble_f32's outputs -- conf for every prior from cls_logits; loc / mask / track / centerness
  * at the K rows of each listed pixel from small[k] [.][small_ld] (centerness + bbox at column 0, mask at column group_pad) and trk[k], row
- * i * row_mul + row_add for list entry i; after an overflow at every row from small_dense[k] / trk_dense[k] (one row per pixel). */
+ * i * row_mul + row_add for list entry i; after an overflow at every row from small_dense[k] / trk_dense[k] (one row per pixel).
+ *
+ * Split form: a NEGATIVE capacity at stm_head_candidates_f32 and stm_head_assemble_sparse_f32 (rejected before it existed; a positive one is
+ * everything above, 8 control ints, unchanged) means |capacity| positions and
+ *   - flags holds pixels + 2 ints, ctl 16 ints: ctl[0..7] as above over all listed positions, ctl[8..15] the same fields over the OWN
+ *     positions -- the pixels with a kept prior of their own: [8] their count as found, [9] listed, [10] rounded up to 256 (at most the
+ *     capacity), [11] / [12] the two pixel gates, [15] the position gate; [13] / [14] repeat [5] / [6];
+ *   - the list is ordered: list[0, ctl[9]) the own positions, list[ctl[9], ctl[1]) the positions that are listed only as the r % (h w)
+ *     centerness partner of a kept prior; a pixel that is both is an own position, listed once; the order inside each part is free;
+ *   - stm_head_assemble_sparse_f32 writes all four tensors for the entries below ctl[9], and centerness and loc only for the others: for
+ *     those it reads columns 0..4 of small[k] and neither the mask columns nor trk[k].
+ * Only centerness is read at a partner-only position, and it comes out of the bbox branch: the mask and track branches need the own
+ * positions only.  Their launches take ctl + 8 wherever the launches over all positions take ctl (stm_head_patch_mask,
+ * stm_conv_set_pixel_gate(ctl + 8 + 3 | 4 | 7)) and are otherwise the same calls; stm_head_patch_gather takes ctl. */
 void stm_conv_set_pixel_gate(const int* valid_pixels);
 int stm_head_candidates_f32(const float* const* cls_logits, int K, int ld, int n_cls, float conf_thresh, int capacity,
                             int patch_pixels_a, int patch_pixels_b, int n_levels, int B, const int* lvl_start, const int* lvl_h,

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """The shared head's stages timed alone on the benchmark's tensors (32 clips, eager, HIP events, nothing beside them): the eager trunk with
 the dense and the sparse head, then each launch group of PlanarGraph._sparse_head and of the dense head (best of four passes).
-Wrote profiles/sparse_head_stages.txt and, run with STM_HEAD_CENTER=0 and 1 by scripts/ab_head_center.sh, profiles/head_center_stages.txt.
-usage: [STM_HEAD_CENTER=0] bench_sparse_head_stages.py > profiles/sparse_head_stages.txt"""
+Wrote profiles/sparse_head_stages.txt and, run with STM_HEAD_CENTER / STM_HEAD_SPLIT = 0 and 1 by scripts/ab_head_switch.sh,
+profiles/head_center_stages.txt / profiles/head_split_stages.txt.
+usage: [STM_HEAD_CENTER=0] [STM_HEAD_SPLIT=0] bench_sparse_head_stages.py > profiles/sparse_head_stages.txt"""
 import os, sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -64,7 +65,17 @@ NP, pdt = ops.plane_layout(pg.fmt)
 capn = pg.sparse_capacity(B, sizes)
 head = pg.head
 CENTER = planar.head_center_default()      # STM_HEAD_CENTER=0: the output layers over all 25 pixels of each patch map
-print("output layers at the centre pixel only:", CENTER)
+SPLIT = planar.head_split_default()        # STM_HEAD_SPLIT=0: the mask and track branches at every listed position
+OWN = ops.HEAD_CTL_OWN if SPLIT else 0
+print("output layers at the centre pixel only:", CENTER, " mask / track branches at the own positions only:", SPLIT)
+# the other form of the split head's cen+bbox | mask output layers: two single-group launches per kernel shape (cen+bbox over all positions, mask
+# over the own ones) instead of one grouped launch over all positions -- timed beside it, not used by PlanarGraph._sparse_head
+def cut_group(sm, g):
+    c = planar.PlanarConv(sm.weight[g * P:(g + 1) * P], sm.bias[g * P:(g + 1) * P], 1, (sm.ph, sm.pw), relu=False, fmt=sm.fmt, tile_n=64,
+                          group_cout=sm.group_cout[g:g + 1], algo_frac=sm.group_cout[g] / float(P))
+    c.wscale = ops._pow2_wscale(sm.weight) if sm.fmt >= 1 else None
+    return c
+small_1g = [(cut_group(c, 0), cut_group(c, 1)) for c in small_l] if SPLIT and CENTER else []
 stages = []
 def ev():
     e = torch.cuda.Event(enable_timing=True); e.record(); return e
@@ -75,29 +86,46 @@ def run_once(record):
     xx = t1c(up, lv, out="planes", splitk=False); m("t1 class")
     xx = t2c(xx, lv, out="planes", splitk=False); m("t2 class")
     cls = [c(xx, lv, out="f32", splitk=False, kxr=True) for c in cls_l]; m("class output layers x3")
-    lst, ctl = ops.head_candidates(cls, head.num_classes, thr, capn, 49, 25, B, sizes); m("candidates")
+    lst, ctl = ops.head_candidates(cls, head.num_classes, thr, capn, 49, 25, B, sizes, split=SPLIT); m("candidates")
     patch = ops.head_patch_gather(up, torch.empty(NP, cw // 32, capn * 81, 32, device=dev, dtype=pdt), 9, capn, B, sizes, lst, ctl); m("gather 9x9")
     x1 = torch.empty(NP, 3 * cw // 32, capn * 49, 32, device=dev, dtype=pdt)
-    t1r(patch, ("img", capn, 9, 9), out="planes", out_planes=x1, window=(0, 0, 7, 7, 0, 0, 7, 7), gate=(ctl, 3)); m("t1 patches")
-    ops.head_patch_mask(x1, 7, capn, B, sizes, lst, ctl); m("mask 7")
     xq = torch.empty(NP, 3 * cw // 32, capn * 25, 32, device=dev, dtype=pdt)
-    t2r(x1, ("img", capn, 7, 7), out="planes", out_planes=xq, window=(0, 0, 5, 5, 0, 0, 5, 5), gate=(ctl, 4)); m("t2 patches")
+    w1, w2 = (0, 0, 7, 7, 0, 0, 7, 7), (0, 0, 5, 5, 0, 0, 5, 5)
+    if SPLIT:       # bbox towers over all listed patches, mask + track towers over the own ones
+        t1b, t1m, t2b, t2m = pg._split_layers
+        t1b(patch, ("img", capn, 9, 9), out="planes", out_planes=x1, window=w1, gate=(ctl, 3)); m("t1 patches bbox")
+        t1m(patch, ("img", capn, 9, 9), out="planes", out_planes=x1, out_slab_off=cw // 32, window=w1, gate=(ctl, OWN + 3)); m("t1 patches mask+track")
+    else:
+        t1r(patch, ("img", capn, 9, 9), out="planes", out_planes=x1, window=w1, gate=(ctl, 3)); m("t1 patches")
+    ops.head_patch_mask(x1, 7, capn, B, sizes, lst, ctl); m("mask 7")
+    if SPLIT:
+        t2b(x1, ("img", capn, 7, 7), out="planes", out_planes=xq, window=w2, gate=(ctl, 4)); m("t2 patches bbox")
+        t2m(x1, ("img", capn, 7, 7), out="planes", out_planes=xq, x_ch_off=cw, out_slab_off=cw // 32, window=w2, gate=(ctl, OWN + 4)); m("t2 patches mask+track")
+    else:
+        t2r(x1, ("img", capn, 7, 7), out="planes", out_planes=xq, window=w2, gate=(ctl, 4)); m("t2 patches")
     ops.head_patch_mask(xq, 5, capn, B, sizes, lst, ctl); m("mask 5")
     if CENTER:      # one-pixel window launches at the centre of the 5 x 5 maps, one output row per position
-        def centre(c, **kw):
+        def centre(c, blk, **kw):
             return c(xq, ("img", capn, 5, 5), out="f32", out_f32=torch.empty(capn, c.O, device=dev), window=(0, 0, 1, 1, c.ph - 2, c.pw - 2, 1, 1),
-                     gate=(ctl, ops.HEAD_CTL_GATE_POS), **kw)
-        small = [centre(c, kxr=True) for c in small_l]; m("small patches x3")
-        trk = [centre(c, x_ch_off=2 * cw, kxr=False) for c in trk_l]; m("trk patches x3")
+                     gate=(ctl, blk + ops.HEAD_CTL_GATE_POS), **kw)
+        small = [centre(c, 0, kxr=True) for c in small_l]; m("small patches x3")
+        if small_1g:
+            for cb, cm in small_1g:
+                o = torch.empty(capn, 2 * P, device=dev)
+                cb(xq, ("img", capn, 5, 5), out="f32", out_f32=o, window=(0, 0, 1, 1, cb.ph - 2, cb.pw - 2, 1, 1), gate=(ctl, ops.HEAD_CTL_GATE_POS), kxr=True)
+                cm(xq, ("img", capn, 5, 5), out="f32", out_f32=o, out_ch_off=P, x_ch_off=cw, window=(0, 0, 1, 1, cm.ph - 2, cm.pw - 2, 1, 1),
+                   gate=(ctl, OWN + ops.HEAD_CTL_GATE_POS), kxr=True)
+            m("(small patches as 2 x 3 single-group launches, unused)")
+        trk = [centre(c, OWN, x_ch_off=2 * cw, kxr=False) for c in trk_l]; m("trk patches x3")
     else:
         ql = ("levels", capn, [(5, 5)])
         small = [c(xq, ql, out="f32", gate=(ctl, 4), kxr=True) for c in small_l]; m("small patches x3")
-        trk = [c(xq, ql, out="f32", x_ch_off=2 * cw, gate=(ctl, 4)) for c in trk_l]; m("trk patches x3")
+        trk = [c(xq, ql, out="f32", x_ch_off=2 * cw, gate=(ctl, OWN + 4)) for c in trk_l]; m("trk patches x3")
     gd = (ctl, 5)
     xx = t1r(up, lv, out="planes", gate=gd); xx = t2r(xx, lv, out="planes", gate=gd); m("dense towers (empty)")
     small_d = [c(xx, lv, out="f32", gate=gd, kxr=True) for c in small_l]
     trk_d = [c(xx, lv, out="f32", x_ch_off=2 * cw, gate=gd) for c in trk_l]; m("dense outputs (empty)")
-    out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P, *((1, 0) if CENTER else (25, 12)), lst, ctl, capn); m("assemble")
+    out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P, *((1, 0) if CENTER else (25, 12)), lst, ctl, capn, split=SPLIT); m("assemble")
     torch.cuda.synchronize()
     if record:
         stages.append([(marks[i][0], marks[i - 1][1].elapsed_time(marks[i][1])) for i in range(1, len(marks))])

@@ -7,6 +7,7 @@
 //
 //   head_candidates_kernel    class logits of the K kernel shapes -> list of the pixels with a kept prior (arithmetic of row_stats_kernel<true>,
 //                             postproc.hip, value for value), their count
+//   head_list_kernel          (split form) flags -> the list, positions with a kept prior of their own in front
 //   head_control_kernel       count -> the control block the other launches read (below); more positions than the capacity -> the patch
 //                             launches are empty and the dense launches of the three branches run instead (the convolution launches are gated
 //                             by stm_conv_set_pixel_gate)
@@ -15,6 +16,7 @@
 //   head_assemble_*           prediction_head_FC.py:168-195 as head_assemble_kernel (mask_ops.hip) does it, same arithmetic: conf for every prior,
 //                             the four other tensors at the kept positions' rows (or, after an overflow, at every row from the dense launches)
 #include <algorithm>
+#include <climits>
 
 #include "stm_common.h"
 
@@ -30,7 +32,12 @@ enum { CTL_RAW = 0,      // positions found (may exceed the capacity)
        CTL_DENSE = 5,    // pixel gate of the dense launches of the three branches: all pixels after an overflow, else 0
        CTL_OVERFLOW = 6,
        CTL_GATE_POS = 7, // CTL_N: position gate of the output layers' one-pixel window launches (one output row per listed position)
-       CTL_INTS = 8 };
+       CTL_INTS = 8,
+       // Split form (a negative capacity at the entry points): a second block of the same fields over the OWN positions -- the pixels with a kept
+       // prior of their own, list[0, n_own); list[n_own, n) are the partner-only positions, where only centerness is read, so only the bbox branch
+       // runs there.  A launch of the mask / track branches takes ctl + CTL_OWN as its control block or gate and is otherwise the same launch.
+       CTL_OWN = 8 };
+enum { FLAG_OWN = 1, FLAG_PARTNER = 2 };
 
 struct Levels {
     int n, B;
@@ -56,15 +63,16 @@ struct CandArgs {
     float thresh;
     int* list;
     int* ctl;
-    int* flags;            // [n_pixels], zero on entry: 1 = the pixel is listed
+    int* flags;            // [n_pixels], zero on entry: 1 = the pixel is listed; split form: FLAG_OWN | FLAG_PARTNER, and two list cursors behind them
+    int split;
     Levels L;
 };
 
-__global__ __launch_bounds__(256) void head_clear_kernel(int* ctl, int* flags, int n_pixels)
+__global__ __launch_bounds__(256) void head_clear_kernel(int* ctl, int* flags, int n_flags, int n_ctl)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n_pixels) flags[i] = 0;
-    else if (i < n_pixels + CTL_INTS) ctl[i - n_pixels] = 0;
+    if (i < n_flags) flags[i] = 0;
+    else if (i < n_flags + n_ctl) ctl[i - n_flags] = 0;
 }
 
 __device__ __forceinline__ void list_pixel(const CandArgs& a, int m)
@@ -72,6 +80,15 @@ __device__ __forceinline__ void list_pixel(const CandArgs& a, int m)
     if (atomicCAS(a.flags + m, 0, 1) != 0) return;
     const int i = atomicAdd(a.ctl + CTL_RAW, 1);
     if (i < a.capacity) a.list[i] = m;
+}
+
+// split form: the first thread to make a flag non-zero counts the position, the first to set the own bit counts an own position; head_list_kernel
+// writes the list
+__device__ __forceinline__ void flag_pixel(const CandArgs& a, int m, int bit)
+{
+    const int old = atomicOr(a.flags + m, bit);
+    if (old == 0) atomicAdd(a.ctl + CTL_RAW, 1);
+    if (bit == FLAG_OWN && !(old & FLAG_OWN)) atomicAdd(a.ctl + CTL_OWN + CTL_RAW, 1);
 }
 
 // CAND_PX pixels per workgroup; the class logits of their K priors (one per kernel shape) are copied coalesced into LDS (rows of an odd stride), then
@@ -128,28 +145,56 @@ __global__ __launch_bounds__(256) void head_candidates_kernel(const CandArgs a, 
     const unsigned kept = kept_s[threadIdx.x];
     if (!kept) return;
     const int m = m0 + threadIdx.x;
-    list_pixel(a, m);
+    if (a.split) flag_pixel(a, m, FLAG_OWN);
+    else list_pixel(a, m);
     int l, b, y, x;
     decode_pixel(a.L, m, l, b, y, x);
     const int hw = a.L.h[l] * a.L.w[l], pix = y * a.L.w[l] + x;
     for (int kk = 0; kk < a.K; ++kk)
-        if (kept >> kk & 1) list_pixel(a, a.L.start[l] + b * hw + (pix * a.K + kk) % hw);
+        if (kept >> kk & 1) {
+            const int pm = a.L.start[l] + b * hw + (pix * a.K + kk) % hw;
+            if (a.split) flag_pixel(a, pm, FLAG_PARTNER);
+            else list_pixel(a, pm);
+        }
 }
 
-__global__ void head_control_kernel(int* ctl, int capacity, int n_pixels, int px_a, int px_b)
+// blocks = 1: the block over all listed positions; 2: and the block over the own positions behind it (split form; its CTL_RAW holds their count)
+__global__ void head_control_kernel(int* ctl, int capacity, int n_pixels, int px_a, int px_b, int blocks)
 {
-    if (threadIdx.x || blockIdx.x) return;
-    const int raw = ctl[CTL_RAW];
-    const bool over = raw > capacity;
-    const int n = over ? 0 : raw;
+    if (blockIdx.x || (int)threadIdx.x >= blocks) return;
+    const bool over = ctl[CTL_RAW] > capacity;
+    int* c = ctl + threadIdx.x * CTL_OWN;
+    const int n = over ? 0 : c[CTL_RAW];
     const int fill = min(capacity, (n + 255) & ~255);
-    ctl[CTL_N] = n;
-    ctl[CTL_FILL] = fill;
-    ctl[CTL_GATE_A] = fill * px_a;
-    ctl[CTL_GATE_B] = fill * px_b;
-    ctl[CTL_DENSE] = over ? n_pixels : 0;
-    ctl[CTL_OVERFLOW] = over ? 1 : 0;
-    ctl[CTL_GATE_POS] = n;
+    c[CTL_N] = n;
+    c[CTL_FILL] = fill;
+    c[CTL_GATE_A] = fill * px_a;
+    c[CTL_GATE_B] = fill * px_b;
+    c[CTL_DENSE] = over ? n_pixels : 0;
+    c[CTL_OVERFLOW] = over ? 1 : 0;
+    c[CTL_GATE_POS] = n;
+}
+
+// Split form, after head_control_kernel: own positions to list[0, n_own), partner-only positions to list[n_own, n).  A workgroup counts its 256
+// pixels of each class, takes its ranges with one atomic per class from the two cursors behind the flags, and writes; the order inside a class is
+// the order of arrival (results land in rows fixed by the position).  Nothing is listed after an overflow (n = 0).
+__global__ __launch_bounds__(256) void head_list_kernel(const int* flags, int* cursors, int n_pixels, int capacity, int* list, const int* ctl)
+{
+    __shared__ int cnt_s[2], base_s[2];
+    if (threadIdx.x < 2) cnt_s[threadIdx.x] = 0;
+    __syncthreads();
+    const int n = ctl[CTL_N], n_own = ctl[CTL_OWN + CTL_N];
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    const int f = m < n_pixels && n > 0 ? flags[m] : 0;
+    const int cls = f & FLAG_OWN ? 0 : (f ? 1 : -1);
+    int rank = 0;
+    if (cls >= 0) rank = atomicAdd(&cnt_s[cls], 1);
+    __syncthreads();
+    if (threadIdx.x < 2) base_s[threadIdx.x] = cnt_s[threadIdx.x] ? atomicAdd(cursors + threadIdx.x, cnt_s[threadIdx.x]) : 0;
+    __syncthreads();
+    if (cls < 0) return;
+    const int i = (cls ? n_own : 0) + base_s[cls] + rank;
+    if (i < n && i < capacity) list[i] = m;
 }
 
 struct GatherArgs {
@@ -227,6 +272,7 @@ struct AsmArgs {
     const int* list;
     const int* ctl;
     int capacity;
+    int split;                 // list entries from ctl[CTL_OWN + CTL_N] on are partner-only positions: centerness and loc only
 };
 
 // the tail of head_assemble_kernel (mask_ops.hip) for one (image, prior) row, 16 lanes per row: same expressions, same summation order
@@ -295,6 +341,7 @@ __global__ __launch_bounds__(256) void head_assemble_rows_kernel(const AsmArgs a
 __global__ __launch_bounds__(256) void head_assemble_listed_kernel(const AsmArgs a)
 {
     const int n_pos = a.ctl[CTL_N];
+    const int n_own = a.split ? a.ctl[CTL_OWN + CTL_N] : n_pos;
     const int sub = threadIdx.x & 15;
     const int64_t units = (int64_t)n_pos * a.K;
     for (int64_t u = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); u < units; u += (int64_t)gridDim.x * 16) {
@@ -310,7 +357,15 @@ __global__ __launch_bounds__(256) void head_assemble_listed_kernel(const AsmArgs
         const int nn = a.lvl_off[l] + p * a.K + k;
         const int64_t o = (int64_t)b * a.N + nn;
         const int64_t src = (int64_t)i * a.row_mul + a.row_add;
-        assemble_rest(a, a.small[k] + src * a.small_ld, a.trk[k] + src * a.trk_ld, o, (int64_t)b * a.N + a.lvl_off[l] + (int64_t)k * hw + p, sub);
+        const int64_t cen_idx = (int64_t)b * a.N + a.lvl_off[l] + (int64_t)k * hw + p;
+        if (i >= n_own) {
+            // partner-only position: the mask and track branches did not run here -- the centerness + bbox columns only
+            const float* sm = a.small[k] + src * a.small_ld;
+            if (sub < 4) a.loc[o * 4 + sub] = sm[1 + sub];
+            if (sub == 0) a.cen[cen_idx] = tanhf(sm[0]);
+            continue;
+        }
+        assemble_rest(a, a.small[k] + src * a.small_ld, a.trk[k] + src * a.trk_ld, o, cen_idx, sub);
     }
 }
 
@@ -340,6 +395,10 @@ extern "C" int stm_head_candidates_f32(const float* const* cls_logits, int K, in
     CandArgs a;
     STM_REQUIRE(fill_levels(a.L, n_levels, B, lvl_start, lvl_h, lvl_w), STM_EINVAL, "%s: bad level table", who);
     const int n_pixels = a.L.start[n_levels];
+    // a negative capacity selects the split form: |capacity| positions, own positions in front, 16 control ints, n_pixels + 2 flag ints
+    const int split = capacity < 0;
+    STM_REQUIRE(capacity != INT_MIN, STM_EINVAL, "%s: bad sizes", who);
+    if (split) capacity = -capacity;
     STM_REQUIRE(K > 0 && K <= 4 && n_cls >= 2 && ld >= n_cls && n_pixels > 0 && capacity > 0 && patch_pixels_a > 0 && patch_pixels_b > 0 &&
                     (int64_t)capacity * std::max(patch_pixels_a, patch_pixels_b) < ((int64_t)1 << 30), STM_EINVAL, "%s: bad sizes", who);
     for (int k = 0; k < 4; ++k) {
@@ -347,9 +406,10 @@ extern "C" int stm_head_candidates_f32(const float* const* cls_logits, int K, in
         STM_REQUIRE(k >= K || a.cls[k], STM_ENULL, "%s: input %d is NULL", who, k);
     }
     a.K = K; a.ld = ld; a.n_cls = n_cls; a.n_pixels = n_pixels; a.capacity = capacity; a.thresh = conf_thresh; a.list = list; a.ctl = ctl;
-    a.flags = flags;
+    a.flags = flags; a.split = split;
+    const int n_flags = n_pixels + (split ? 2 : 0), n_ctl = split ? 2 * CTL_INTS : CTL_INTS;
     // (cleared by a kernel, not by memset nodes: the launches are captured into a graph that is replayed many times)
-    hipLaunchKernelGGL(head_clear_kernel, dim3(stm_cdiv(n_pixels + CTL_INTS, 256)), dim3(256), 0, stm_hs(stream), ctl, flags, n_pixels);
+    hipLaunchKernelGGL(head_clear_kernel, dim3(stm_cdiv(n_flags + n_ctl, 256)), dim3(256), 0, stm_hs(stream), ctl, flags, n_flags, n_ctl);
     STM_CHECK_LAUNCH("head_clear_kernel");
     int vec = ld % 4 == 0 && 4 * ((n_cls + 3) / 4) <= ld;
     for (int k = 0; k < K; ++k) vec = vec && ((uintptr_t)a.cls[k] % 16) == 0;
@@ -357,8 +417,13 @@ extern "C" int stm_head_candidates_f32(const float* const* cls_logits, int K, in
     STM_REQUIRE(lds <= 48 * 1024, STM_EUNSUPPORTED, "%s: %d classes x %d shapes do not fit the staging buffer", who, n_cls, K);
     hipLaunchKernelGGL(head_candidates_kernel, dim3(stm_cdiv(n_pixels, CAND_PX)), dim3(256), lds, stm_hs(stream), a, vec);
     STM_CHECK_LAUNCH("head_candidates_kernel");
-    hipLaunchKernelGGL(head_control_kernel, dim3(1), dim3(64), 0, stm_hs(stream), ctl, capacity, n_pixels, patch_pixels_a, patch_pixels_b);
+    hipLaunchKernelGGL(head_control_kernel, dim3(1), dim3(64), 0, stm_hs(stream), ctl, capacity, n_pixels, patch_pixels_a, patch_pixels_b,
+                       split ? 2 : 1);
     STM_CHECK_LAUNCH("head_control_kernel");
+    if (split) {
+        hipLaunchKernelGGL(head_list_kernel, dim3(stm_cdiv(n_pixels, 256)), dim3(256), 0, stm_hs(stream), flags, flags + n_pixels, n_pixels, capacity, list, ctl);
+        STM_CHECK_LAUNCH("head_list_kernel");
+    }
     return STM_OK;
 }
 
@@ -407,11 +472,14 @@ extern "C" int stm_head_assemble_sparse_f32(const float* const* cls_logits, int 
                 "%s: NULL argument", who);
     STM_REQUIRE(L->B > 0 && L->K > 0 && L->K <= 4 && L->n_levels > 0 && L->n_levels <= 8 && L->n_cls > 0 && cls_ld >= L->n_cls && L->mask_dim > 0 &&
                     L->mask_dim <= L->group_pad && L->embed_dim > 0 && L->group_pad >= 5 && L->small_ld >= L->group_pad + L->mask_dim &&
-                    L->trk_ld >= L->embed_dim && capacity > 0 && row_mul > 0 && row_add >= 0 && row_add < row_mul, STM_EINVAL, "%s: bad layout", who);
+                    L->trk_ld >= L->embed_dim && capacity != 0 && capacity != INT_MIN && row_mul > 0 && row_add >= 0 && row_add < row_mul, STM_EINVAL, "%s: bad layout", who);
     AsmArgs a;
     a.conf = conf; a.loc = loc; a.mask = mask; a.track = track; a.cen = centerness;
     a.B = L->B; a.K = L->K; a.n_levels = L->n_levels; a.n_cls = L->n_cls; a.mask_dim = L->mask_dim; a.embed = L->embed_dim;
     a.gpad = L->group_pad; a.cls_ld = cls_ld; a.small_ld = L->small_ld; a.trk_ld = L->trk_ld;
+    // (a negative capacity: the split form of stm_head_candidates_f32 -- ordered list, 16 control ints)
+    a.split = capacity < 0;
+    if (a.split) capacity = -capacity;
     a.row_mul = row_mul; a.row_add = row_add; a.list = list; a.ctl = ctl; a.capacity = capacity;
     int off = 0, start = 0;
     for (int l = 0; l < 8; ++l) {

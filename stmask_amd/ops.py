@@ -1838,6 +1838,7 @@ def head_assemble(small, trk, B, sizes, n_cls, mask_dim, embed_dim, group_pad):
 # ---- sparse head (csrc/head_sparse.hip): control block indices as the header lists them
 HEAD_CTL_RAW, HEAD_CTL_N, HEAD_CTL_FILL, HEAD_CTL_GATE_A, HEAD_CTL_GATE_B, HEAD_CTL_DENSE, HEAD_CTL_OVERFLOW, HEAD_CTL_INTS = 0, 1, 2, 3, 4, 5, 6, 8
 HEAD_CTL_GATE_POS = 7
+HEAD_CTL_OWN = 8      # split form: first int of the second block, the same fields over the positions with a kept prior of their own
 
 
 def conv_set_pixel_gate(ctl, index):
@@ -1872,10 +1873,11 @@ def _ptr4(ts):
     return (ctypes.c_void_p * 4)(*([t.data_ptr() for t in ts] + [0] * (4 - len(ts))))
 
 
-def head_candidates(cls_logits, n_cls, conf_thresh, capacity, patch_pixels_a, patch_pixels_b, B, sizes):
+def head_candidates(cls_logits, n_cls, conf_thresh, capacity, patch_pixels_a, patch_pixels_b, B, sizes, split=False):
     """stm_head_candidates_f32: cls_logits = per-kernel-shape [pixels, ld] fp32 class logits over the concatenated levels -> (list int32 [capacity] of
     the pixels whose rows the detection stage reads for the priors that pass generate_candidate's test, control block int32 [8]: see
-    include/stmask_hip.h)."""
+    include/stmask_hip.h).  split: the pixels with a kept prior of their own in front, list[:ctl[HEAD_CTL_OWN + HEAD_CTL_N]], the pixels that are
+    only another prior's centerness partner behind them; control block int32 [16], the second block over the own positions."""
     _dev(*cls_logits)
     n_px, ld = cls_logits[0].shape
     n, st, hh, ww, total = _level_arrays(B, sizes)
@@ -1884,9 +1886,9 @@ def head_candidates(cls_logits, n_cls, conf_thresh, capacity, patch_pixels_a, pa
             raise StmError("head_candidates: inputs must be contiguous fp32 matrices over all level pixels")
     dev = cls_logits[0].device
     lst = torch.empty(capacity, dtype=torch.int32, device=dev)
-    ctl = torch.empty(HEAD_CTL_INTS, dtype=torch.int32, device=dev)
-    flags = torch.empty(n_px, dtype=torch.int32, device=dev)
-    call("stm_head_candidates_f32", _ptr4(cls_logits), len(cls_logits), ld, n_cls, conf_thresh, capacity, patch_pixels_a, patch_pixels_b, n, B, st,
+    ctl = torch.empty(HEAD_CTL_INTS * (2 if split else 1), dtype=torch.int32, device=dev)
+    flags = torch.empty(n_px + (2 if split else 0), dtype=torch.int32, device=dev)
+    call("stm_head_candidates_f32", _ptr4(cls_logits), len(cls_logits), ld, n_cls, conf_thresh, -capacity if split else capacity, patch_pixels_a, patch_pixels_b, n, B, st,
          hh, ww, _p(flags), _p(lst), _p(ctl), _stream())
     return lst, ctl
 
@@ -1914,9 +1916,12 @@ def head_patch_mask(planes, side, capacity, B, sizes, lst, ctl):
 
 
 def head_assemble_sparse(cls_logits, small, trk, small_dense, trk_dense, B, sizes, n_cls, mask_dim, embed_dim, group_pad, row_mul, row_add, lst, ctl,
-                         capacity):
+                         capacity, split=False):
     """stm_head_assemble_sparse_f32 -> (conf, loc, mask, track, centerness) as head_assemble; loc / mask / track / centerness hold values at the
-    rows of the listed pixels only (every row after an overflow), the other rows are NOT written."""
+    rows of the listed pixels only (every row after an overflow), the other rows are NOT written.  split (list and ctl from
+    head_candidates(split=True)): mask / track at the rows of the own positions only, and their matrices are not read for the others."""
+    if ctl.numel() < HEAD_CTL_INTS * (2 if split else 1):
+        raise StmError("head_assemble_sparse: the split form reads a control block of 16 ints")
     _dev(*cls_logits, *small, *trk, *small_dense, *trk_dense)
     K = len(cls_logits)
     L, start = _head_layout(B, K, sizes, n_cls, mask_dim, embed_dim, group_pad, small[0].shape[-1], trk[0].shape[-1])
@@ -1934,7 +1939,7 @@ def head_assemble_sparse(cls_logits, small, trk, small_dense, trk_dense, B, size
     track = torch.empty(B, N, embed_dim, device=dev)
     cen = torch.empty(B, N, 1, device=dev)
     call("stm_head_assemble_sparse_f32", _ptr4(cls_logits), cls_logits[0].shape[-1], _ptr4(small), _ptr4(trk), _ptr4(small_dense), _ptr4(trk_dense),
-         ctypes.byref(L), row_mul, row_add, _p(lst), _p(ctl), capacity, _p(conf), _p(loc), _p(mask), _p(track), _p(cen), _stream())
+         ctypes.byref(L), row_mul, row_add, _p(lst), _p(ctl), -capacity if split else capacity, _p(conf), _p(loc), _p(mask), _p(track), _p(cen), _stream())
     return conf, loc, mask, track, cen
 
 

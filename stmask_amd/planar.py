@@ -174,7 +174,7 @@ class PlanarConv:
         return 128
 
     def __call__(self, xp, shape, out="planes", x_off=0, out_planes=None, out_f32=None, out_off=0, residual=None, x_ch_off=0,
-                 out_ch_off=0, x2=None, window=None, gate=None, kxr=None, splitk=True):
+                 out_ch_off=0, x2=None, window=None, gate=None, kxr=None, splitk=True, out_slab_off=0):
         """xp: [P, S, N, 32] planes in this layer's format (channel-slab major; 2 x fp16 or 3 x bf16).  shape: ("img", B, H, W) -> pixels [x_off, x_off + B*H*W)
         of xp are one image batch; ("levels", B, [(H, W), ...]) -> all of xp, concatenated levels.  The layer reads
         groups*C channels starting at channel x_ch_off.  out: "planes" | "f32" | "both" allocates dense outputs
@@ -182,7 +182,8 @@ class PlanarConv:
         gate = (int32 device tensor, index): only the pixel tiles below that device value run (ops.conv_set_pixel_gate; never split-K).
         kxr: True / False decides the kx-reuse kernel for a layer it supports (None: by the pixel count); splitk = False: never split K.
         window = (0, 0, 1, 1, ph, pw, 1, 1), ph / pw <= 0: ONE output pixel per image -- input (-ph + ky, -pw + kx) -- as row b of the outputs; the
-        only window form the kx-reuse kernel takes (its centre-window launch; the gate then counts images)."""
+        only window form the kx-reuse kernel takes (its centre-window launch; the gate then counts images).
+        out_slab_off: the plane output starts at that 32-channel slab of out_planes (a layer cut out of a wider one writes its own channels)."""
         NP, dt = ops.plane_layout(self.fmt)
         if xp.dtype != dt or xp.dim() != 4 or xp.shape[0] < NP or xp.shape[3] != 32 or not xp.is_contiguous():
             raise StmError(f"PlanarConv: expected contiguous {dt} planes [{NP}, S, N, 32], got {xp.dtype} {tuple(xp.shape)}")
@@ -253,7 +254,9 @@ class PlanarConv:
         p_pl = p_f32 = 0
         if out_planes is not None:
             g.out_np, g.out_plane_stride = out_planes.shape[2], out_planes.shape[1] * out_planes.shape[2] * 32
-            p_pl = out_planes.data_ptr() + out_off_p * 64
+            if out_slab_off < 0 or out_slab_off + -(-self.O // 32) > out_planes.shape[1]:
+                raise StmError(f"PlanarConv: {self.O} output channels from slab {out_slab_off} run past the {out_planes.shape[1]} slabs of out_planes")
+            p_pl = out_planes.data_ptr() + (out_slab_off * g.out_np + out_off_p) * 64
         if out_f32 is not None:
             g.out_ld = out_f32.shape[-1]
             p_f32 = out_f32.data_ptr() + (out_off_f * g.out_ld + out_ch_off) * 4   # fp32 output may start at a column
@@ -337,6 +340,13 @@ def _split(t_nhwc, fmt=None):
 
 
 @functools.lru_cache(maxsize=None)
+def head_split_default():
+    """STM_HEAD_SPLIT (default on): the sparse head's mask and track branches only at the positions with a kept prior of their own; 0 = at every
+    listed position, the centerness partners included.  The one place that reads the switch, once per process."""
+    return os.environ.get("STM_HEAD_SPLIT", "1") != "0"
+
+
+@functools.lru_cache(maxsize=None)
 def head_center_default():
     """STM_HEAD_CENTER (default on): the sparse head's output layers at the centre pixel of each patch map only; 0 = over the whole 5 x 5 maps.
     The one place that reads the switch, once per process."""
@@ -401,7 +411,7 @@ class PlanarGraph:
         # positions or None).  None: every branch densely (forward_single, the layer API, the per-clip pipeline).  FCA heads with one prior per
         # kernel shape only: under FCB the class branch reads the dense box regression.
         self.sparse = None
-        self._sparse_layers = None
+        self._sparse_layers = self._split_layers = None
         self.sparse_ctl = self.sparse_list = None      # (tests, diagnosis: the last sparse step's counts and positions)
         self._side = None                              # second stream of run()'s branches (_side_stream)
         if not self.head_planar:
@@ -506,6 +516,9 @@ class PlanarGraph:
             cls.append(cut(sm, slice(0, P), tile_n=64, group_cout=gc[:1], algo_frac=gc[0] / float(P)))
             small.append(cut(sm, slice(P, 3 * P), groups=2, tile_n=64, group_cout=gc[1:], algo_frac=sum(gc[1:]) / (2.0 * P)))
         self._sparse_layers = (t1c, t1r, t2c, t2r, cls, small)
+        # split form: the towers of the three branches cut once more, bbox | mask + track (the output layers stay one grouped launch)
+        self._split_layers = (cut(self.tower1, slice(cw, 2 * cw)), cut(self.tower1, slice(2 * cw, 4 * cw)),
+                              cut(self.tower2, slice(cw, 2 * cw)), cut(self.tower2, slice(2 * cw, 4 * cw), groups=2))
         return self._sparse_layers
 
     def _sparse_head(self, up, g, toc):
@@ -515,6 +528,12 @@ class PlanarGraph:
         thresh, cap = self.sparse[:2]
         # output layers at the centre pixel of the 5 x 5 maps only (STM_HEAD_CENTER=0: over all 25 pixels, as before); part of the setting
         center = self.sparse[2] if len(self.sparse) > 2 else head_center_default()
+        # Split (a fourth element; a setting without it keeps the unsplit form): half the listed positions are there only as the centerness
+        # partner of a kept prior -- centerness comes out of the bbox branch, so the mask and track branches run at the positions with a kept
+        # prior of their own only.  Those are in front of the list, and the second control block (ops.HEAD_CTL_OWN) counts them: the same
+        # launches, gated by that block.
+        split = len(self.sparse) > 3 and bool(self.sparse[3])
+        own = ops.HEAD_CTL_OWN if split else 0
         if cap is None:
             cap = self.sparse_capacity(B, sizes)
         t1c, t1r, t2c, t2r, cls_l, small_l = self._build_sparse()
@@ -531,16 +550,28 @@ class PlanarGraph:
         cls = [c(x, lv, out="f32", splitk=False, kxr=kx) for c in cls_l]
         toc("head_towers")
         # 2. positions whose rows the detection stage will read
-        lst, ctl = ops.head_candidates(cls, head.num_classes, thresh, cap, S1 * S1, S2 * S2, B, sizes)
+        lst, ctl = ops.head_candidates(cls, head.num_classes, thresh, cap, S1 * S1, S2 * S2, B, sizes, split=split)
         # 3. their 9 x 9 patches through the two tower layers of the other branches as valid convolutions (window launches with no padding:
         # 9 x 9 -> 7 x 7 -> 5 x 5); after each layer the pixels outside the level's map become zero -- the padding the dense launch reads there
         patch = ops.head_patch_gather(up, torch.empty(NP, cw // 32, cap * S0 * S0, 32, device=dev, dtype=pdt), S0, cap, B, sizes, lst, ctl)
         x1 = torch.empty(NP, 3 * cw // 32, cap * S1 * S1, 32, device=dev, dtype=pdt)
-        t1r(patch, ("img", cap, S0, S0), out="planes", out_planes=x1, window=(0, 0, S1, S1, 0, 0, S1, S1), gate=(ctl, ops.HEAD_CTL_GATE_A))
-        ops.head_patch_mask(x1, S1, cap, B, sizes, lst, ctl)
-        gb = (ctl, ops.HEAD_CTL_GATE_B)
         xq = torch.empty(NP, 3 * cw // 32, cap * S2 * S2, 32, device=dev, dtype=pdt)
-        t2r(x1, ("img", cap, S1, S1), out="planes", out_planes=xq, window=(0, 0, S2, S2, 0, 0, S2, S2), gate=gb)
+        gb = (ctl, ops.HEAD_CTL_GATE_B)
+        w1, w2 = (0, 0, S1, S1, 0, 0, S1, S1), (0, 0, S2, S2, 0, 0, S2, S2)
+        if split:
+            # the bbox tower over all listed patches, the mask + track towers over the own ones: each launch writes its own channels of x1 / xq.
+            # The mask / track channels of the patches past the own ones' fill hold nothing of this step; the masking pass (one launch per layer over
+            # all listed patches, as in the unsplit form) only writes zeros there, in patches that cross a border, and reads nothing, and the grouped output launch below forms rows from them that are never assembled.
+            t1b, t1m, t2b, t2m = self._split_layers
+            t1b(patch, ("img", cap, S0, S0), out="planes", out_planes=x1, window=w1, gate=(ctl, ops.HEAD_CTL_GATE_A))
+            t1m(patch, ("img", cap, S0, S0), out="planes", out_planes=x1, out_slab_off=cw // 32, window=w1, gate=(ctl, own + ops.HEAD_CTL_GATE_A))
+            ops.head_patch_mask(x1, S1, cap, B, sizes, lst, ctl)
+            t2b(x1, ("img", cap, S1, S1), out="planes", out_planes=xq, window=w2, gate=gb)
+            t2m(x1, ("img", cap, S1, S1), out="planes", out_planes=xq, x_ch_off=cw, out_slab_off=cw // 32, window=w2, gate=(ctl, own + ops.HEAD_CTL_GATE_B))
+        else:
+            t1r(patch, ("img", cap, S0, S0), out="planes", out_planes=x1, window=w1, gate=(ctl, ops.HEAD_CTL_GATE_A))
+            ops.head_patch_mask(x1, S1, cap, B, sizes, lst, ctl)
+            t2r(x1, ("img", cap, S1, S1), out="planes", out_planes=xq, window=w2, gate=gb)
         ops.head_patch_mask(xq, S2, cap, B, sizes, lst, ctl)
         if center:
             # ... and the output layers at the centre pixel of the 5 x 5 maps, the only one that is read: one-pixel window launches, one output row
@@ -548,20 +579,23 @@ class PlanarGraph:
             # kx-reuse kernel's centre-window launch stages the centre pixel's taps only (kw rows per position instead of 25), the planar
             # kernel's window launch is the padded launch's sum at that pixel.  The track layers' 128 x 64 tiles (pick_tile at `cap` pixels) keep
             # the chain of K-slabs on a workgroup short: gated launches never split K.
-            c2, gp = S2 // 2, (ctl, ops.HEAD_CTL_GATE_POS)
+            c2 = S2 // 2
             qi = ("img", cap, S2, S2)
 
-            def centre(c, **kw):
-                return c(xq, qi, out="f32", out_f32=torch.empty(cap, c.O, device=dev), window=(0, 0, 1, 1, c.ph - c2, c.pw - c2, 1, 1), gate=gp, **kw)
+            def centre(c, blk, **kw):
+                return c(xq, qi, out="f32", out_f32=torch.empty(cap, c.O, device=dev), window=(0, 0, 1, 1, c.ph - c2, c.pw - c2, 1, 1),
+                         gate=(ctl, blk + ops.HEAD_CTL_GATE_POS), **kw)
 
-            small = [centre(c, kxr=kx) for c in small_l]
-            trk = [centre(c, x_ch_off=2 * cw, kxr=False) for c in trk_l]
+            # (split: the grouped cen+bbox | mask launch covers all positions, its mask group is read at the own ones only; the track launches
+            # cover the own positions)
+            small = [centre(c, 0, kxr=kx) for c in small_l]
+            trk = [centre(c, own, x_ch_off=2 * cw, kxr=False) for c in trk_l]
             rows = (1, 0)
         else:
             # ... and the output layers over the 5 x 5 maps (all that their windows at the centre pixel read), "same" padding
             ql = ("levels", cap, [(S2, S2)])
             small = [c(xq, ql, out="f32", gate=gb, kxr=kx) for c in small_l]
-            trk = [c(xq, ql, out="f32", x_ch_off=2 * cw, gate=gb) for c in trk_l]
+            trk = [c(xq, ql, out="f32", x_ch_off=2 * cw, gate=(ctl, own + ops.HEAD_CTL_GATE_B)) for c in trk_l]
             rows = (S2 * S2, (S2 * S2) // 2)
         # 4. more positions than the capacity: the same layers over every pixel (empty launches otherwise)
         gd = (ctl, ops.HEAD_CTL_DENSE)
@@ -571,7 +605,7 @@ class PlanarGraph:
         trk_d = [c(x, lv, out="f32", x_ch_off=2 * cw, gate=gd) for c in trk_l]
         toc("head_finals")
         out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P,
-                                       rows[0], rows[1], lst, ctl, cap)
+                                       rows[0], rows[1], lst, ctl, cap, split=split)
         self.sparse_ctl, self.sparse_list = ctl, lst       # (tests, diagnosis: the step's counts and positions)
         return out
 

@@ -102,6 +102,10 @@ class TrunkRunner:
         # ... with its output layers at the centre pixel of each position's 5 x 5 patch map only (one-pixel window launches: the other 24 pixels
         # are never read).  STM_HEAD_CENTER=0 runs them over the whole maps (A/B runs); part of the setting baked into the graphs
         self.head_center = planar.head_center_default()
+        # ... and its mask / track branches only at the positions with a kept prior of their own: about half the listed positions are there as
+        # the centerness partner of a kept prior, and centerness comes out of the bbox branch.  STM_HEAD_SPLIT=0: all three branches at every
+        # listed position (A/B runs); part of the setting baked into the graphs
+        self.head_split = planar.head_split_default()
         # batches from which it is on: a single-stream step is a chain of launches bound by their latency, and the sparse head has 22 more of them
         # (frames/s dense / sparse at 1 clip 812-817 / 713-733, 2 clips 1 073-1 075 / 1 058-1 064, 4 clips 1 301-1 305 / 1 321-1 324, 8 clips
         # 1 435 / 1 543: DESIGN.md section 6).  STM_SPARSE_MIN_CLIPS for A/B runs
@@ -132,7 +136,7 @@ class TrunkRunner:
             return None
         if not getattr(self.net.Detect_TF, "use_cross_class_nms", True):
             return None
-        return (float(self.cfg.eval_conf_thresh), self.sparse_capacity, self.head_center)
+        return (float(self.cfg.eval_conf_thresh), self.sparse_capacity, self.head_center, self.head_split)
 
     def _trunk(self, frames):
         pg = getattr(self.net, "_planar", None)
