@@ -162,6 +162,17 @@ TRACKER_SIGNATURES = {
     "stm_track_resolve_tf": ("i", "pppppiiiipppp"),
     "stm_track_drop_plan": ("i", "ppiippp"),
 }
+# include/stmask_hip_train.h, the fourth header (tests/test_abi_train.py): the batched mask term of the training criterion
+TRAIN_SIGNATURES = {
+    "stm_mbox_workspace_bytes": ("z", "ii"),
+    "stm_mbox_positives": ("i", "ppiiipzp"),
+    "stm_mbox_gather_f32": ("i", "ppipppipppppppiiiiiipzp"),
+    "stm_mbox_reduce_f32": ("i", "pppppidp"),
+    "stm_mbox_reduce_backward_f32": ("i", "pppppidp"),
+    "stm_lincomb_rows_proto_backward_workspace_bytes": ("z", "iiii"),
+    "stm_lincomb_rows_proto_backward_f32": ("i", "ppipppppiiiipzp"),
+    "stm_mbox_scatter_coeff_f32": ("i", "pppppiiiipzp"),
+}
 
 
 class StmError(RuntimeError):
@@ -233,7 +244,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback on the product path.")
         _lib = ctypes.CDLL(LIB_PATH)
-        tables = {**SIGNATURES, **OUTPUT_SIGNATURES, **TRACKER_SIGNATURES}
+        tables = {**SIGNATURES, **OUTPUT_SIGNATURES, **TRACKER_SIGNATURES, **TRAIN_SIGNATURES}
         missing = [n for n in tables if not hasattr(_lib, n)]
         if missing:
             _lib = None

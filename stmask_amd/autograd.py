@@ -1,12 +1,14 @@
 """Autograd for the drop-in deformable convolution, RoIAlign and correlation (the training path of dcn_v2 / mmcv.ops /
 spatial_correlation_sampler) and for the layer functions the reference's loss differentiates through -- generate_mask, decode, jaccard and
 the mask loss tail mask_bce_sum, the OHEM class-confidence loss ohem_conf_loss, the positive-prior terms box_center_loss and track_loss and
-the pieces of track_to_segment_loss: the row-prototype form of generate_mask and the two weighted reductions.
+the pieces of track_to_segment_loss: the row-prototype form of generate_mask and the two weighted reductions, and the pieces of the batched
+mask term lincomb_mask_loss: its gather, the row-prototype mask with a prototype gradient and its reduction.
 
 Each Function's forward is the launch the shim makes without autograd (ops.deform_conv / roi_align / corr_patch), so values under
 autograd are bit-identical to the no-grad call.  Only inputs are saved: the deformable columns are recomputed in backward with the
 forward's own im2col, the mask sigmoid from the prototypes and coefficients.  Backward runs the gfx950 kernels of csrc/deform_backward.hip,
-csrc/temporal_backward.hip, csrc/mask_backward.hip, csrc/mask_loss.hip, csrc/conf_loss.hip, csrc/pos_loss.hip and csrc/t2s_loss.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
+csrc/temporal_backward.hip, csrc/mask_backward.hip, csrc/mask_loss.hip, csrc/conf_loss.hip, csrc/pos_loss.hip, csrc/t2s_loss.hip and
+csrc/mbox_loss.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
 every backward is @first_order_only: a double backward (create_graph=True, then differentiating the result) raises instead of
 silently dropping the second-order term.
 """
@@ -324,6 +326,69 @@ class T2sReduceFunction(torch.autograd.Function):
         return (g_reg, g_bce) + (None,) * 10
 
 
+class MboxGatherFunction(torch.autograd.Function):
+    """The gather of lincomb_mask_loss: mask_data [B,P,M] through the list of positives -> (coeff [n,M], box [n,4], img, idx, scale, n_dev,
+    status) of ops.mbox_gather.  Gradient w.r.t. mask_data only, from the coefficient rows: list rows are unique, so every row of grad mask_data
+    is written once and the rows that are not positive are exact zeros."""
+
+    @staticmethod
+    def forward(ctx, mask_data, loc_data, priors, idx_t, conf_t, mask_offs, state, n_rows, G_total, H, W):
+        rows = ops.mbox_gather(state, n_rows, loc_data, priors, mask_data, idx_t, mask_offs, G_total, H, W)
+        ctx.save_for_backward(conf_t, state, rows["n_dev"], rows["status"])
+        outs = tuple(rows[k] for k in ("coeff", "box", "img", "idx", "scale", "n_dev", "status"))
+        ctx.mark_non_differentiable(*outs[1:])
+        return outs
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_coeff, *unused):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 11
+        conf_t, state, n_dev, status = ctx.saved_tensors
+        return (ops.mbox_scatter_coeff(grad_coeff.contiguous(), conf_t, state, n_dev, status),) + (None,) * 10
+
+
+class LincombRowsProtoFunction(torch.autograd.Function):
+    """generate_mask over the rows of many prototype sets, the rows sorted by set: proto [S,h,w,M], coeff [n,M], boxes [n,4], row_proto int32
+    [n], n_dev int32 [1], prefix int32 [S+1] (rows prefix[s] .. prefix[s+1] use set s), status int32 [1] -> [n,h,w].  Gradients w.r.t. the
+    coefficients (csrc/t2s_loss.hip) and the prototypes (csrc/mbox_loss.hip)."""
+
+    @staticmethod
+    def forward(ctx, coeff, proto, boxes, row_proto, n_dev, prefix, status):
+        ctx.save_for_backward(coeff, proto, boxes, row_proto, n_dev, prefix, status)
+        return ops.lincomb_sigmoid_crop(proto, coeff, boxes, apply_tanh=True, n_dev=n_dev, row_proto=row_proto)
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_out):
+        nc, np_ = ctx.needs_input_grad[:2]
+        if not (nc or np_):
+            return (None,) * 7
+        coeff, proto, boxes, row_proto, n_dev, prefix, status = ctx.saved_tensors
+        go = grad_out.contiguous()
+        gc = ops.lincomb_rows_backward(go, proto, coeff, boxes, row_proto, n_dev, apply_tanh=True) if nc else None
+        gp = ops.lincomb_rows_proto_backward(go, proto, coeff, boxes, prefix, status) if np_ else None
+        return (gc, gp) + (None,) * 5
+
+
+class MboxReduceFunction(torch.autograd.Function):
+    """The weighted sum of lincomb_mask_loss: bce [n] and the scale rows of ops.mbox_gather -> losses['M'].  Gradient w.r.t. bce only."""
+
+    @staticmethod
+    def forward(ctx, bce, scale_rows, n_dev, status, mask_alpha):
+        ctx.alpha = mask_alpha
+        ctx.save_for_backward(scale_rows, n_dev, status)
+        return ops.mbox_reduce(bce, scale_rows, n_dev, status, mask_alpha)
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 5
+        scale_rows, n_dev, status = ctx.saved_tensors
+        return (ops.mbox_reduce_backward(grad_loss.contiguous(), scale_rows, n_dev, status, ctx.alpha),) + (None,) * 4
+
+
 def modulated_deform_conv(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups):
     return ModulatedDeformConvFunction.apply(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups, False)
 
@@ -379,3 +444,15 @@ def lincomb_mask_rows(proto, coeff, boxes, row_proto, n_dev=None):
 
 def t2s_reduce(bbox_reg, bce, reg_rows, box_rows, w_rows, n_dev, status, bs, H, W, boxshift_alpha=1.0, maskshift_alpha=1.0):
     return T2sReduceFunction.apply(bbox_reg, bce, reg_rows, box_rows, w_rows, n_dev, status, bs, H, W, boxshift_alpha, maskshift_alpha)
+
+
+def mbox_gather(mask_data, loc_data, priors, idx_t, conf_t, mask_offs, state, n_rows, G_total, H, W):
+    return MboxGatherFunction.apply(mask_data, loc_data, priors, idx_t, conf_t, mask_offs, state, n_rows, G_total, H, W)
+
+
+def lincomb_mask_rows_proto(proto, coeff, boxes, row_proto, n_dev, prefix, status):
+    return LincombRowsProtoFunction.apply(coeff, proto, boxes, row_proto, n_dev, prefix, status)
+
+
+def mbox_reduce(bce, scale_rows, n_dev, status, mask_alpha=1.0):
+    return MboxReduceFunction.apply(bce, scale_rows, n_dev, status, mask_alpha)

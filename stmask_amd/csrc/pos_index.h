@@ -1,5 +1,5 @@
-// pos_index.h -- the ordered list of the positive priors of a batch, shared by pos_loss.hip (track loss: positive iff conf_t > 0) and t2s_loss.hip
-// (temporal-fusion loss: positive iff pos_t > 0).  Three steps over tiles of 256 consecutive priors of ONE image (tiles do not straddle images):
+// pos_index.h -- the ordered list of the positive priors of a batch, shared by pos_loss.hip (track loss: positive iff conf_t > 0), t2s_loss.hip
+// (temporal-fusion loss: positive iff pos_t > 0) and mbox_loss.hip (mask term: positive iff conf_t > 0).  Three steps over tiles of 256 consecutive priors of ONE image (tiles do not straddle images):
 //   count   positives per tile (t2s_loss.hip's target kernel writes these counts itself and skips this launch)
 //   scan    one workgroup: the tiles' exclusive prefix, n, npos_b, the track loss's W; optionally the [B + 1] prefix of the per-image counts and
 //           the status word n > cap

@@ -8,5 +8,6 @@ from .functions import CandidateShift, Detect, Detect_TF, Track, Track_TF, compu
 from .mask_utils import generate_mask, generate_mask_rows, lincomb_mask_loss_image, mask_bce_sum  # noqa: F401
 from .pos_loss import box_center_loss, track_loss  # noqa: F401
 from .t2s_loss import track_to_segment_loss  # noqa: F401
+from .multibox_loss import MultiBoxLoss, lincomb_mask_loss  # noqa: F401
 from .modules import FPN, FeatureAlign, InterpolateModule, PredictionModule_FC, TemporalNet, bbox_feat_extractor, \
     correlate, make_net  # noqa: F401

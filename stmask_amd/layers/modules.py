@@ -1,7 +1,8 @@
 """nn.Modules of the hot path -- host-side mirror of the reference's layers/modules/{FPN,make_net,prediction_head_FC,
 Featurealign,track_to_segment_head}.py with identical module / parameter names (state-dict compatible, SURVEY.md
 Appendix B).  Dense convs, bilinear interpolation and activations stay torch (MIOpen); deformable convs, correlation
-and RoIAlign are the hand-written kernels.
+and RoIAlign are the hand-written kernels.  MultiBoxLoss (layers/multibox_loss.py) is reachable here as in the reference's
+layers.modules.
 """
 import torch
 import torch.nn as nn
@@ -236,3 +237,6 @@ def bbox_feat_extractor(feature_maps, boxes_w_norm, h, w, pool_size):
         feature_maps = feature_maps.unsqueeze(0)
     rois = torch.cat([boxes.new_zeros(boxes.size(0), 1), boxes], dim=1)
     return roi_align(feature_maps, rois, pool_size)
+
+
+from .multibox_loss import MultiBoxLoss  # noqa: E402,F401  (the reference's `from layers.modules import MultiBoxLoss`)

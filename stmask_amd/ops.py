@@ -1066,6 +1066,132 @@ def lincomb_rows_backward(grad_out, proto, coeff, boxes, row_proto, n_dev=None, 
     return gc
 
 
+def mbox_check_shapes(who, B, P, M=None, n_rows=None):
+    """What include/stmask_hip_train.h refuses from the shapes, raised before anything touches the device."""
+    if B < 1 or P < 1:
+        raise StmError(f"{who}: B={B} P={P}")
+    if B * P > 1 << 22:
+        raise StmError(f"{who}: B*P={B * P} > {1 << 22} rows")
+    if M is not None and M not in (8, 32, 64):
+        raise StmError(f"{who}: mask_dim {M} not in {{8,32,64}}")
+    if n_rows is not None and not 1 <= n_rows <= 65535:
+        raise StmError(f"{who}: {n_rows} rows (1 to 65535)")
+
+
+def mbox_positives(conf_t, max_rows=None):
+    """The ordered list of the positives (conf_t > 0) of a batch in three launches (stm_mbox_positives): conf_t int64 [B,P] -> (prefix int32
+    [B+1], the exclusive prefix of the per-image counts with prefix[B] = n, and the list state for mbox_gather / mbox_scatter_coeff).  No host
+    synchronisation."""
+    if conf_t.dtype != torch.int64 or conf_t.dim() != 2:
+        raise StmError(f"mbox_positives: conf_t must be int64 [B,P], got {conf_t.dtype} {tuple(conf_t.shape)}")
+    B, P = conf_t.shape
+    mbox_check_shapes("mbox_positives", B, P, n_rows=None if max_rows is None else int(max_rows))
+    _dev(conf_t)
+    dev = conf_t.device
+    prefix = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    nbytes = _lib.lib().stm_mbox_workspace_bytes(B, P)
+    state = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)        # kept by the caller until the scatter has run: not the shared scratch
+    call("stm_mbox_positives", _p(conf_t.contiguous()), _p(prefix), B, P, int(max_rows) if max_rows else 0, _p(state), state.numel(), _stream())
+    return prefix, state
+
+
+def mbox_gather(state, n_rows, loc_data, priors, mask_data, idx_t, mask_offs, G_total, H, W):
+    """n_rows rows through mbox_positives' list in one launch (stm_mbox_gather_f32) -> dict of coeff [n,M], box [n,4] (the crop box of
+    multibox_loss.py:559-563), img int32 [n], idx int64 [n] (row of the concatenated masks), scale [n] (w_r / max(bw W, 1) / max(bh H, 1)),
+    n_dev int32 [1], status int32 [1].  Rows past the live count are padding.  No host synchronisation."""
+    if loc_data.dim() != 3 or loc_data.shape[2] != 4 or mask_data.dim() != 3:
+        raise StmError(f"mbox_gather: loc_data {tuple(loc_data.shape)} / mask_data {tuple(mask_data.shape)} must be [B,P,4] / [B,P,M]")
+    B, P = loc_data.shape[:2]
+    M = mask_data.shape[2]
+    n = int(n_rows)
+    mbox_check_shapes("mbox_gather", B, P, M, n)
+    if tuple(mask_data.shape[:2]) != (B, P) or tuple(priors.shape) not in ((P, 4), (B, P, 4)) or tuple(idx_t.shape) != (B, P) or \
+            idx_t.dtype != torch.int64 or mask_offs.dtype != torch.int32 or mask_offs.numel() != B + 1 or G_total < 1:
+        raise StmError(f"mbox_gather: priors {tuple(priors.shape)}, mask_data {tuple(mask_data.shape)}, idx_t {idx_t.dtype} {tuple(idx_t.shape)}, "
+                       f"mask_offs {mask_offs.dtype} {tuple(mask_offs.shape)}, {G_total} masks do not fit loc_data {tuple(loc_data.shape)}")
+    _dev(state, loc_data, priors, mask_data, idx_t, mask_offs)
+    loc_data, priors, mask_data = _f32c(loc_data), _f32c(priors), _f32c(mask_data)
+    dev = loc_data.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = dict(coeff=torch.empty(n, M, **f32), box=torch.empty(n, 4, **f32), img=torch.empty(n, dtype=torch.int32, device=dev),
+               idx=torch.empty(n, dtype=torch.int64, device=dev), scale=torch.empty(n, **f32),
+               n_dev=torch.empty(1, dtype=torch.int32, device=dev), status=torch.empty(1, dtype=torch.int32, device=dev))
+    call("stm_mbox_gather_f32", _p(loc_data), _p(priors), 1 if priors.dim() == 3 else 0, _p(mask_data), _p(idx_t.contiguous()), _p(mask_offs),
+         int(G_total), _p(out["coeff"]), _p(out["box"]), _p(out["img"]), _p(out["idx"]), _p(out["scale"]), _p(out["n_dev"]), _p(out["status"]), n,
+         B, P, M, int(H), int(W), _p(state), state.numel(), _stream())
+    return out
+
+
+def _mbox_rows(who, scale_rows, n_dev, status, other=None):
+    n = scale_rows.shape[0]
+    for name, t in (("scale_rows", scale_rows), ("bce", other)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (n,)):
+            raise StmError(f"{who}: {name} must be float32 [{n}], got {t.dtype} {tuple(t.shape)}")
+    if n_dev.dtype != torch.int32 or status.dtype != torch.int32:
+        raise StmError(f"{who}: n_dev {n_dev.dtype}, status {status.dtype}")
+    mbox_check_shapes(who, 1, 1, n_rows=n)
+    _dev(scale_rows, n_dev, status, other)
+    return n
+
+
+def mbox_reduce(bce, scale_rows, n_dev, status, mask_alpha=1.0):
+    """losses['M'] before the division by the batch size, 0-dim fp32: mask_alpha * sum_r scale_r bce_r (stm_mbox_reduce_f32: one launch, products
+    and sums in double in a fixed order)."""
+    n = _mbox_rows("mbox_reduce", scale_rows, n_dev, status, bce)
+    loss = torch.empty((), dtype=torch.float32, device=bce.device)
+    call("stm_mbox_reduce_f32", _p(bce.contiguous()), _p(scale_rows.contiguous()), _p(n_dev), _p(status), _p(loss), n, float(mask_alpha), _stream())
+    return loss
+
+
+def mbox_reduce_backward(grad_loss, scale_rows, n_dev, status, mask_alpha=1.0):
+    """grad_bce [n] of mbox_reduce, written (stm_mbox_reduce_backward_f32: one launch)."""
+    n = _mbox_rows("mbox_reduce_backward", scale_rows, n_dev, status)
+    _dev(grad_loss)
+    if grad_loss.dtype != torch.float32 or grad_loss.numel() != 1:
+        raise StmError(f"mbox_reduce_backward: grad_loss must be one float32, got {grad_loss.dtype} {tuple(grad_loss.shape)}")
+    g_bce = torch.empty(n, dtype=torch.float32, device=scale_rows.device)
+    call("stm_mbox_reduce_backward_f32", _p(grad_loss.contiguous()), _p(scale_rows.contiguous()), _p(n_dev), _p(status), _p(g_bce), n,
+         float(mask_alpha), _stream())
+    return g_bce
+
+
+def lincomb_rows_proto_backward(grad_out, proto, coeff, boxes, prefix, status=None):
+    """grad_proto [S,h,w,M] of lincomb_sigmoid_crop in its row_proto form with the rows sorted by prototype set: rows prefix[s] .. prefix[s+1]
+    (int32 [S+1] on the device) use proto[s].  One or two launches, fixed-order sums, no atomics (stm_lincomb_rows_proto_backward_f32); a set
+    without rows gets exact zeros; status int32 [1]: NaN everywhere when it is not 0."""
+    _dev(grad_out, proto, coeff, boxes, prefix, status)
+    go, proto, coeff, boxes = _f32c(grad_out), _f32c(proto), _f32c(coeff), _f32c(boxes)
+    if proto.dim() != 4:
+        raise StmError(f"lincomb_rows_proto_backward: proto must be [S,h,w,M], got {tuple(proto.shape)}")
+    S, h, w, m = proto.shape
+    n = coeff.shape[0]
+    mbox_check_shapes("lincomb_rows_proto_backward", 1, 1, m, n)
+    if tuple(go.shape) != (n, h, w) or coeff.shape[1] != m or tuple(boxes.shape) != (n, 4) or prefix.dtype != torch.int32 or \
+            prefix.numel() != S + 1 or (status is not None and status.dtype != torch.int32):
+        raise StmError(f"lincomb_rows_proto_backward: grad_out {tuple(go.shape)}, proto {tuple(proto.shape)}, coeff {tuple(coeff.shape)}, boxes / "
+                       "prefix / status do not match")
+    gp = torch.empty_like(proto)
+    need = _lib.lib().stm_lincomb_rows_proto_backward_workspace_bytes(S, h, w, m)
+    ws = _workspace(need, proto.device, "lcrp")
+    call("stm_lincomb_rows_proto_backward_f32", _p(go), _p(proto), S, _p(coeff), _p(boxes), _p(prefix.contiguous()), _p(status), _p(gp), h, w, m, n,
+         _p(ws), ws.numel(), _stream())
+    return gp
+
+
+def mbox_scatter_coeff(grad_rows, conf_t, state, n_dev, status):
+    """grad mask_data [B,P,M] from the gradient of mbox_gather's coefficient rows: one launch, no atomics (stm_mbox_scatter_coeff_f32); rows
+    that are not positive are exact zeros."""
+    _dev(grad_rows, conf_t, state, n_dev, status)
+    grad_rows = _f32c(grad_rows)
+    B, P = conf_t.shape
+    n, M = grad_rows.shape
+    mbox_check_shapes("mbox_scatter_coeff", B, P, M, n)
+    grad = torch.empty(B, P, M, dtype=torch.float32, device=grad_rows.device)
+    call("stm_mbox_scatter_coeff_f32", _p(grad_rows), _p(conf_t.contiguous()), _p(n_dev), _p(status), _p(grad), n, B, P, M, _p(state),
+         state.numel(), _stream())
+    return grad
+
+
 def mask_iou(m1, m2, thr=0.5, group1=None, group2=None):
     """box_utils.py:435-447 on (m > thr).  m1 [n1,h,w], m2 [n2,h,w] soft masks -> [n1,n2].  group1 / group2 (int32, any
     order; sorted rows skip whole workgroups): only pairs of the same group are computed, the others stay 0 (stm_mask_iou_grouped_f32)."""
