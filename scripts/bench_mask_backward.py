@@ -9,7 +9,7 @@ and the launches alone (ops.*, no autograd), with algorithmic bytes (fp32; A = p
   backward  4*(2*h*w*M + 2*n*M + A)                prototypes, coefficients and grad_out inside the rectangles read; both gradients written
   (the backward's partial sums -- [pixel block][n][M] and, when rows are split, [split][h*w][M] -- are not algorithmic bytes)
 `--splits` also times the backward with the row split forced to 1 (STM_LCB_SPLITS): the measurement behind the split rule of
-csrc/mask_backward.hip.  Each figure: HIP events around `--reps` back-to-back calls after a warm-up, median of 5 groups.
+csrc/lincomb_backward.hip.  Each figure: HIP events around `--reps` back-to-back calls after a warm-up, median of 5 groups.
 Usage: python scripts/bench_mask_backward.py [--reps 20] [--splits] [--out FILE] [--once]     (--once: one pass per shape, for a profiler run)
 """
 import argparse

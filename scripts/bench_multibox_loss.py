@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""layers.MultiBoxLoss (the whole training criterion on the device, csrc/mbox_loss.hip for its batched mask term) forward + backward with the
+"""layers.MultiBoxLoss (the whole training criterion on the device, csrc/mbox_loss.hip and csrc/lincomb_backward.hip for its batched mask term) forward + backward with the
 stand-in TemporalNet of tests/t2s_loss_restate.py, against two baselines on the same card in the same process:
 
   P = 15 345, 41 classes, B = 2 / 8 / 16 images (B / 2 clips of two frames), 5 wide boxes per frame with 20 planted priors each (about 100

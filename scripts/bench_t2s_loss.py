@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""layers.track_to_segment_loss (csrc/t2s_loss.hip) with the real TemporalNet against a torch-op restatement of the reference's per-clip loop
+"""layers.track_to_segment_loss (csrc/t2s_loss.hip, csrc/lincomb_backward.hip) with the real TemporalNet against a torch-op restatement of the reference's per-clip loop
 (multibox_loss.py:247-326), forward + backward, on the same card in the same process:
 
   C = 633, 48 x 80 feature map, P = 15 345, prototypes 96 x 160, M = 32, masks 384 x 640; bs = 2 / 8 / 16 clips; 20 and 100 shift-positives

@@ -7,7 +7,7 @@ mask term lincomb_mask_loss: its gather, the row-prototype mask with a prototype
 Each Function's forward is the launch the shim makes without autograd (ops.deform_conv / roi_align / corr_patch), so values under
 autograd are bit-identical to the no-grad call.  Only inputs are saved: the deformable columns are recomputed in backward with the
 forward's own im2col, the mask sigmoid from the prototypes and coefficients.  Backward runs the gfx950 kernels of csrc/deform_backward.hip,
-csrc/temporal_backward.hip, csrc/mask_backward.hip, csrc/mask_loss.hip, csrc/conf_loss.hip, csrc/pos_loss.hip, csrc/t2s_loss.hip and
+csrc/temporal_backward.hip, csrc/mask_backward.hip, csrc/lincomb_backward.hip, csrc/mask_loss.hip, csrc/conf_loss.hip, csrc/pos_loss.hip, csrc/t2s_loss.hip and
 csrc/mbox_loss.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
 every backward is @first_order_only: a double backward (create_graph=True, then differentiating the result) raises instead of
 silently dropping the second-order term.
@@ -351,7 +351,7 @@ class MboxGatherFunction(torch.autograd.Function):
 class LincombRowsProtoFunction(torch.autograd.Function):
     """generate_mask over the rows of many prototype sets, the rows sorted by set: proto [S,h,w,M], coeff [n,M], boxes [n,4], row_proto int32
     [n], n_dev int32 [1], prefix int32 [S+1] (rows prefix[s] .. prefix[s+1] use set s), status int32 [1] -> [n,h,w].  Gradients w.r.t. the
-    coefficients (csrc/t2s_loss.hip) and the prototypes (csrc/mbox_loss.hip)."""
+    coefficients and the prototypes (both csrc/lincomb_backward.hip)."""
 
     @staticmethod
     def forward(ctx, coeff, proto, boxes, row_proto, n_dev, prefix, status):

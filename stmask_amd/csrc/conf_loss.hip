@@ -67,7 +67,6 @@ ConfLayout conf_layout(int B, int N)
     return L;
 }
 
-__device__ __forceinline__ float nan_f32() { return __builtin_bit_cast(float, 0x7FC00000u); }
 
 // (stm_block_excl_scan, stm_block_sum_f64: stm_common.h)
 
@@ -161,7 +160,7 @@ __global__ __launch_bounds__(256) void ohem_score_kernel(const float* __restrict
                 sc = fmaxf((float)(l - (double)p[0]), 0.0f);
                 cev = sc;
             } else if (ti > 0) {
-                cev = ti < C ? (float)(l - (double)p[(int)ti]) : nan_f32();
+                cev = ti < C ? (float)(l - (double)p[(int)ti]) : stm_nan_f32();
                 atomicAdd(&npos[row / P], 1u);
                 atomicAdd(&st[ST_NUM_POS], 1u);
             }
@@ -387,7 +386,7 @@ __global__ __launch_bounds__(256) void ohem_backward_kernel(const float* __restr
                 const float wi = s_w[r];
                 if (wi != 0.0f) {
                     const int ti = s_t[r];
-                    v[j] = ti >= C ? nan_f32() : gs * wi * (expf(src[e + j] - s_l[r]) - (c == ti ? 1.0f : 0.0f));
+                    v[j] = ti >= C ? stm_nan_f32() : gs * wi * (expf(src[e + j] - s_l[r]) - (c == ti ? 1.0f : 0.0f));
                 }
             }
             if (++c == C) c = 0, ++r;

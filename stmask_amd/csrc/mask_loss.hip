@@ -58,7 +58,6 @@ __device__ __forceinline__ float bce_term(float pc, float t)
 // t = 0 or 1 exactly: the same value with one logarithm (the other product is 0 * a finite number)
 __device__ __forceinline__ float bce_term_bit(float pc, bool t) { return -fmaxf(logf(t ? pc : 1.0f - pc), -100.0f); }
 
-__device__ __forceinline__ float nan_f32() { return __builtin_bit_cast(float, 0x7FC00000u); }
 
 template <bool F32>
 __global__ __launch_bounds__(256) void mask_bce_forward_kernel(const float* __restrict__ pred, const void* __restrict__ target,
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(256) void mask_bce_forward_kernel(const float* __re
     float* out = part + (int64_t)d * gridDim.x + tile;
     const int64_t g = idx ? idx[d] : (int64_t)d;
     if (g < 0 || g >= G) {                               // workgroup-uniform
-        if (tid == 0) *out = nan_f32();
+        if (tid == 0) *out = stm_nan_f32();
         return;
     }
     const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
@@ -184,7 +183,7 @@ __global__ __launch_bounds__(256) void mask_bce_backward_kernel(const float* __r
     float* out = grad_pred + ((int64_t)d * h + y) * w + x;
     const int64_t g = idx ? idx[d] : (int64_t)d;
     if (g < 0 || g >= G) {                               // workgroup-uniform
-        if (live) *out = nan_f32();
+        if (live) *out = stm_nan_f32();
         return;
     }
     const float* pd = pred + (int64_t)d * h * w;

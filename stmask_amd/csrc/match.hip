@@ -320,7 +320,6 @@ __global__ __launch_bounds__(256) void encode_kernel(const float4* __restrict__ 
     if (t < n) out[t] = stm_encode_one(matched[t], priors[t]);
 }
 
-bool mt_aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
 }  // namespace
 
@@ -349,10 +348,10 @@ extern "C" int stm_match_priors_f32(const float* boxes, const int64_t* labels, c
                 "stm_match_priors_f32: boxes/labels/ids/offsets/priors/conf must be non-NULL");
     STM_REQUIRE(loc_t && gt_boxes_t && conf_t && idx_t && ids_t, STM_ENULL,
                 "stm_match_priors_f32: loc_t/gt_boxes_t/conf_t/idx_t/ids_t must be non-NULL");
-    STM_REQUIRE(mt_aligned16(boxes) && mt_aligned16(priors) && mt_aligned16(loc_t) && mt_aligned16(gt_boxes_t), STM_EINVAL,
+    STM_REQUIRE(stm_aligned16(boxes) && stm_aligned16(priors) && stm_aligned16(loc_t) && stm_aligned16(gt_boxes_t), STM_EINVAL,
                 "stm_match_priors_f32: boxes, priors, loc_t and gt_boxes_t must be 16-byte aligned");
     const size_t need = mt_ws_bytes(B, P, G_total);
-    STM_REQUIRE(workspace && workspace_bytes >= need && mt_aligned16(workspace), STM_EWORKSPACE,
+    STM_REQUIRE(workspace && workspace_bytes >= need && stm_aligned16(workspace), STM_EWORKSPACE,
                 "stm_match_priors_f32: workspace of %zu bytes (16-byte aligned) needed, got %zu", need, workspace_bytes);
     const MatchWs w = mt_carve(workspace, B, P, G_total);
     const float4* b4 = reinterpret_cast<const float4*>(boxes);
@@ -378,7 +377,7 @@ extern "C" int stm_encode_boxes_f32(const float* matched, const float* priors, f
     STM_REQUIRE(n >= 0, STM_EINVAL, "stm_encode_boxes_f32: n=%lld", (long long)n);
     if (n == 0) return STM_OK;
     STM_REQUIRE(matched && priors && out, STM_ENULL, "stm_encode_boxes_f32: matched/priors/out must be non-NULL");
-    STM_REQUIRE(mt_aligned16(matched) && mt_aligned16(priors) && mt_aligned16(out), STM_EINVAL,
+    STM_REQUIRE(stm_aligned16(matched) && stm_aligned16(priors) && stm_aligned16(out), STM_EINVAL,
                 "stm_encode_boxes_f32: pointers must be 16-byte aligned");
     hipLaunchKernelGGL(encode_kernel, dim3(stm_cdiv(n, 256)), dim3(256), 0, stm_hs(stream), reinterpret_cast<const float4*>(matched),
                        reinterpret_cast<const float4*>(priors), reinterpret_cast<float4*>(out), n);

@@ -4,7 +4,8 @@
 //   scan    one workgroup: the tiles' exclusive prefix, n, npos_b, the track loss's W; optionally the [B + 1] prefix of the per-image counts and
 //           the status word n > cap
 //   index   the flattened rows of the positives in order, and their weights 1 / max(npos_b, 1)
-// Integer sums only: the list is the same from run to run.
+// Integer sums only: the list is the same from run to run.  The workspace layout (pos_layout), the shape check (pos_check) and the launch
+// sequence (pos_list) of the three users are here too.
 #pragma once
 #include "stm_common.h"
 
@@ -14,6 +15,34 @@ constexpr int PL_TILE = 256;
 constexpr int PL_MAX_N = 1 << 22;
 
 enum { TM_N = 0, TM_STATUS = 1, TM_W = 2, TM_WORDS = 4 };   // meta: n, the status word (1: n exceeds the caller's cap), then W as a double at word 2
+
+// the list's workspace, in 32-bit words; `extra` is the user's own block (the track loss's partial doubles), 8-byte aligned behind the 4 meta words
+struct PosLayout {
+    size_t meta, extra, tilecnt, tilepre, npos, idx, wts, words;
+};
+
+PosLayout pos_layout(int B, int P, size_t extra_words = 0)
+{
+    const size_t nT = (size_t)B * stm_cdiv(P, PL_TILE), N = (size_t)B * P;
+    PosLayout L;
+    size_t o = 0;
+    L.meta = o;    o += TM_WORDS;
+    L.extra = o;   o += extra_words;
+    L.tilecnt = o; o += nT;
+    L.tilepre = o; o += nT;
+    L.npos = o;    o += (size_t)B;
+    L.idx = o;     o += N;
+    L.wts = o;     o += N;
+    L.words = o;
+    return L;
+}
+
+int pos_check(const char* who, int B, int P)
+{
+    STM_REQUIRE(B >= 1 && P >= 1, STM_EINVAL, "%s: B=%d P=%d", who, B, P);
+    STM_REQUIRE((int64_t)B * P <= PL_MAX_N, STM_EUNSUPPORTED, "%s: B*P=%lld > %d rows", who, (long long)B * P, PL_MAX_N);
+    return STM_OK;
+}
 
 __device__ __forceinline__ float pl_weight(unsigned npos) { return (float)(1.0 / (double)(npos > 1u ? npos : 1u)); }
 
@@ -94,6 +123,24 @@ __global__ __launch_bounds__(256) void pos_index_kernel(const int64_t* __restric
         idx[rank] = (int)(row0 + tid);
         wts[rank] = pl_weight(npos[img]);
     }
+}
+
+// The launches count (unless the caller's own kernel wrote the tiles' counts), scan, index over a workspace laid out by pos_layout(B, P, ...).
+// flag: a prior is listed iff flag > 0.  prefix: null or [B + 1] ints.  max_rows: the caller's cap behind the status word, 0 for none.
+int pos_list(const int64_t* flag, bool count, int* prefix, int max_rows, int B, int P, unsigned* ws, const PosLayout& L, hipStream_t st)
+{
+    const int tpi = stm_cdiv(P, PL_TILE), nT = B * tpi;
+    if (count) {
+        hipLaunchKernelGGL(pos_count_kernel, dim3(nT), dim3(256), 0, st, flag, ws + L.tilecnt, P, tpi);
+        STM_CHECK_LAUNCH("pos_count_kernel");
+    }
+    hipLaunchKernelGGL(pos_scan_kernel, dim3(1), dim3(256), 0, st, ws + L.tilecnt, ws + L.tilepre, ws + L.npos, ws + L.meta, prefix,
+                       max_rows > 0 ? (unsigned)max_rows : 0xFFFFFFFFu, nT, B, tpi);
+    STM_CHECK_LAUNCH("pos_scan_kernel");
+    hipLaunchKernelGGL(pos_index_kernel, dim3(nT), dim3(256), 0, st, flag, ws + L.tilepre, ws + L.npos, reinterpret_cast<int*>(ws + L.idx),
+                       reinterpret_cast<float*>(ws + L.wts), P, tpi);
+    STM_CHECK_LAUNCH("pos_index_kernel");
+    return STM_OK;
 }
 
 }  // namespace

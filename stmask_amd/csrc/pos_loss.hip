@@ -202,26 +202,8 @@ __global__ __launch_bounds__(256) void box_center_backward_kernel(const float* _
 }
 
 // ------------------------------------------------------------------------------------------ track loss
-// workspace, in 32-bit words
-struct TrackLayout {
-    size_t meta, tilecnt, tilepre, npos, idx, wts, part, words;
-};
-
-TrackLayout track_layout(int B, int P)
-{
-    const size_t nT = (size_t)B * stm_cdiv(P, PL_TILE), N = (size_t)B * P;
-    TrackLayout L;
-    size_t o = 0;
-    L.meta = o;    o += TM_WORDS;
-    L.part = o;    o += 2 * (size_t)TL_G;                    // doubles: 8-byte aligned (meta is 4 words)
-    L.tilecnt = o; o += nT;
-    L.tilepre = o; o += nT;
-    L.npos = o;    o += (size_t)B;
-    L.idx = o;     o += N;
-    L.wts = o;     o += N;
-    L.words = o;
-    return L;
-}
+// the list's workspace (pos_index.h) with the TL_G partial doubles of the pairs kernel as its extra block
+PosLayout track_layout(int B, int P) { return pos_layout(B, P, 2 * (size_t)TL_G); }
 
 // Rows blk * 64 .. + 63 of the list, columns k0 .. k0 + TL_DC - 1 of track_data -> tile[64][TL_LD]; rows past n and columns past D are zeros.
 // A thread's 8 loads run along rows (32 consecutive lanes, 32 consecutive floats).
@@ -429,13 +411,6 @@ __global__ __launch_bounds__(256) void track_backward_kernel(const float* __rest
     }
 }
 
-int pos_check(const char* who, int B, int P)
-{
-    STM_REQUIRE(B >= 1 && P >= 1, STM_EINVAL, "%s: B=%d P=%d", who, B, P);
-    STM_REQUIRE((int64_t)B * P <= PL_MAX_N, STM_EUNSUPPORTED, "%s: B*P=%lld > %d rows", who, (long long)B * P, PL_MAX_N);
-    return STM_OK;
-}
-
 int track_check(const char* who, int B, int P, int D)
 {
     const int rc = pos_check(who, B, P);
@@ -445,18 +420,9 @@ int track_check(const char* who, int B, int P, int D)
 }
 
 // launches 1-3 of the track loss: the ordered list of positives, their weights, n and W in the workspace
-int track_index(const int64_t* conf_t, int B, int P, unsigned* ws, const TrackLayout& L, hipStream_t st)
+int track_index(const int64_t* conf_t, int B, int P, unsigned* ws, const PosLayout& L, hipStream_t st)
 {
-    const int tpi = stm_cdiv(P, PL_TILE), nT = B * tpi;
-    hipLaunchKernelGGL(pos_count_kernel, dim3(nT), dim3(256), 0, st, conf_t, ws + L.tilecnt, P, tpi);
-    STM_CHECK_LAUNCH("pos_count_kernel");
-    hipLaunchKernelGGL(pos_scan_kernel, dim3(1), dim3(256), 0, st, ws + L.tilecnt, ws + L.tilepre, ws + L.npos, ws + L.meta,
-                       static_cast<int*>(nullptr), 0xFFFFFFFFu, nT, B, tpi);
-    STM_CHECK_LAUNCH("pos_scan_kernel");
-    hipLaunchKernelGGL(pos_index_kernel, dim3(nT), dim3(256), 0, st, conf_t, ws + L.tilepre, ws + L.npos, reinterpret_cast<int*>(ws + L.idx),
-                       reinterpret_cast<float*>(ws + L.wts), P, tpi);
-    STM_CHECK_LAUNCH("pos_index_kernel");
-    return STM_OK;
+    return pos_list(conf_t, true, nullptr, 0, B, P, ws, L, st);
 }
 
 }  // namespace
@@ -533,12 +499,12 @@ extern "C" int stm_track_loss_f32(const float* track, const int64_t* conf_t, con
     STM_REQUIRE(track && conf_t && ids_t && loss, STM_ENULL, "%s: track/conf_t/ids_t/loss must be non-NULL", who);
     STM_REQUIRE(workspace && workspace_bytes >= stm_track_loss_workspace_bytes(B, P, D), STM_EWORKSPACE, "%s: workspace too small", who);
     STM_REQUIRE((uintptr_t)workspace % 8 == 0, STM_EINVAL, "%s: the workspace must be 8-byte aligned", who);
-    const TrackLayout L = track_layout(B, P);
+    const PosLayout L = track_layout(B, P);
     unsigned* ws = reinterpret_cast<unsigned*>(workspace);
     hipStream_t st = stm_hs(stream);
     const int ri = track_index(conf_t, B, P, ws, L, st);
     if (ri != STM_OK) return ri;
-    double* part = reinterpret_cast<double*>(ws + L.part);
+    double* part = reinterpret_cast<double*>(ws + L.extra);
     hipLaunchKernelGGL(track_pairs_kernel, dim3(TL_G), dim3(256), 0, st, track, ids_t, ws + L.meta, reinterpret_cast<const int*>(ws + L.idx),
                        reinterpret_cast<const float*>(ws + L.wts), part, D);
     STM_CHECK_LAUNCH("track_pairs_kernel");
@@ -558,7 +524,7 @@ extern "C" int stm_track_loss_backward_f32(const float* grad_loss, const float* 
     STM_REQUIRE(workspace && workspace_bytes >= stm_track_loss_workspace_bytes(B, P, D), STM_EWORKSPACE, "%s: workspace too small", who);
     STM_REQUIRE((uintptr_t)workspace % 8 == 0 && (uintptr_t)grad_track % 16 == 0, STM_EINVAL,
                 "%s: the workspace must be 8-byte and grad_track 16-byte aligned", who);
-    const TrackLayout L = track_layout(B, P);
+    const PosLayout L = track_layout(B, P);
     unsigned* ws = reinterpret_cast<unsigned*>(workspace);
     hipStream_t st = stm_hs(stream);
     const int ri = track_index(conf_t, B, P, ws, L, st);

@@ -50,6 +50,11 @@ static inline hipStream_t stm_hs(stm_stream_t s) { return reinterpret_cast<hipSt
 
 static inline int stm_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+static inline bool stm_aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
+// the quiet NaN a loss and its gradients are set to when a status word is set
+__device__ __forceinline__ float stm_nan_f32() { return __int_as_float(0x7FC00000); }
+
 // ---- launch plumbing: what the host keeps per device ---------------------------------------------
 constexpr int STM_MAX_DEVICES = 32;
 

@@ -1,8 +1,8 @@
 // t2s_loss.hip -- the reference's track_to_segment_loss (layers/modules/multibox_loss.py:247-326, called at :102-110), the loss that trains
 // TemporalNet (losses['B_shift'] and losses['M_shift']), for gfx950: the target construction across the two frames of a clip, the batch-wide
 // ordered list of shift-positive priors with everything the later stages gather through it, the two weighted reductions with their adjoint, and
-// the coefficient gradient of the row-prototype form of stm_lincomb_sigmoid_crop_f32.  RoIAlign, TemporalNet, the mask itself and the mask BCE
-// are the existing kernels (temporal.hip, mask_ops.hip, mask_loss.hip).  Conventions: include/stmask_hip.h.
+// nothing else: RoIAlign, TemporalNet, the mask itself, the mask BCE and the mask's coefficient gradient (stm_lincomb_rows_backward_f32) are the
+// existing kernels (temporal.hip, mask_ops.hip, mask_loss.hip, lincomb_backward.hip).  Conventions: include/stmask_hip.h.
 //
 // Prior p of clip i is shift-positive iff ids_t[i,p] > 0 and that id occurs among the clip's reference-frame ids AND its next-frame ids (int64
 // equality).  Its regression target is encode(box_next(id), center_size(box_ref(id))) (stm_encode_one), its mask target the next frame's mask of
@@ -22,11 +22,6 @@
 //   (0; 0, 0, 1, 1), box (0, 0, 1, 1), zero coefficients, target row 0).
 // stm_t2s_reduce_f32 (1 launch, one workgroup): fp32 terms, weighted and added in double, thread t takes rows t, t + 256, ... whatever n_rows is,
 //   so the padded and the exact form add the same numbers in the same order.  stm_t2s_reduce_backward_f32 (1 launch): one thread per row, written.
-// stm_lincomb_rows_backward_f32 (2 launches): grid (pixel blocks of 256, rows).  A workgroup whose pixel span misses the row's crop rectangle
-//   (the forward's, padding 1) writes M zeros and leaves; otherwise z = grad_out * e / (1 + e)^2 per pixel inside the rectangle (grad_out is not
-//   read outside), then the products z * proto are added per group of M pixels in pixel order and the 256 / M groups in group order, which is
-//   the order of lincomb_backward_kernel (mask_backward.hip); the second launch adds the pixel blocks in block order and applies
-//   1 - tanh^2 = 4 e / (1 + e)^2.  No atomics; with one prototype set the result equals stm_lincomb_backward_f32's bit for bit.
 // No float atomics, no integer atomics, every grid depends on the shapes only, outputs are written, not accumulated.
 // Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): no kernel of this file uses scratch.
 #include "stm_common.h"
@@ -36,26 +31,7 @@ namespace {
 
 constexpr int TS_GMAX = 128;           // most boxes of one frame
 constexpr int TS_LANES = 16;           // lanes per row of the gather
-constexpr int TS_MAX_ROWS = 65535;     // rows of the list the later stages take (grid.y of the mask kernels)
-
-struct T2sLayout {
-    size_t meta, tilecnt, tilepre, npos, idx, wts, words;
-};
-
-T2sLayout t2s_layout(int B, int P)
-{
-    const size_t nT = (size_t)B * stm_cdiv(P, PL_TILE), N = (size_t)B * P;
-    T2sLayout L;
-    size_t o = 0;
-    L.meta = o;    o += TM_WORDS;
-    L.tilecnt = o; o += nT;
-    L.tilepre = o; o += nT;
-    L.npos = o;    o += (size_t)B;
-    L.idx = o;     o += N;
-    L.wts = o;     o += N;
-    L.words = o;
-    return L;
-}
+constexpr int TS_MAX_ROWS = 65535;     // rows of the list the later stages take (grid.y of the mask kernels: lincomb_backward.hip's LC_MAX_ROWS)
 
 // rows [g0, g0 + G) of clip b's frame, whatever the offsets hold: never outside [0, G_total), never more than TS_GMAX rows
 __device__ __forceinline__ void ts_frame_range(const int* __restrict__ offs, int b, int G_total, int& g0, int& G)
@@ -214,7 +190,7 @@ __global__ __launch_bounds__(256) void t2s_reduce_kernel(const float* __restrict
     sm = stm_block_sum_f64(sm, sd);
     if (threadIdx.x == 0) {
         const bool over = *status != 0;
-        const float nan = __int_as_float(0x7FC00000);
+        const float nan = stm_nan_f32();
         *b_shift = over ? nan : (float)(scale_b * sb);
         if (m_shift) *m_shift = over ? nan : (float)(scale_m * sm);
     }
@@ -232,7 +208,7 @@ __global__ __launch_bounds__(256) void t2s_reduce_backward_kernel(const float* _
     const int n = min(max(*n_dev, 0), n_rows);
     float gr[4] = {0.0f, 0.0f, 0.0f, 0.0f}, gm = 0.0f;
     if (*status != 0) {
-        gr[0] = gr[1] = gr[2] = gr[3] = gm = __int_as_float(0x7FC00000);
+        gr[0] = gr[1] = gr[2] = gr[3] = gm = stm_nan_f32();
     } else if (r < n) {
         const double w = (double)w_rows[r];
         if (grad_reg && g_b) {
@@ -256,129 +232,12 @@ __global__ __launch_bounds__(256) void t2s_reduce_backward_kernel(const float* _
     if (grad_bce) grad_bce[r] = gm;
 }
 
-// ------------------------------------------------------------------------------------------ grad_coeff of the row-prototype mask
-template <int M>
-__global__ __launch_bounds__(256) void lincomb_rows_backward_kernel(const float* __restrict__ grad_out, const float* __restrict__ proto,
-                                                                    const float* __restrict__ coeff, const float* __restrict__ boxes,
-                                                                    const int* __restrict__ row_proto, const int* __restrict__ n_dev,
-                                                                    float* __restrict__ part, int h, int w, int n, int n_proto, int apply_tanh)
-{
-    constexpr int G = 256 / M;
-    static_assert(256 % M == 0 && M % 4 == 0, "layout");
-    __shared__ float sc[M];
-    __shared__ float zs[256];
-    __shared__ float gs[256];
-    const int r = blockIdx.y;
-    const int nv = n_dev ? min(max(*n_dev, 0), n) : n;
-    if (r >= nv) return;                                     // workgroup-uniform; the reduce writes this row's zeros without reading part
-    const int hw = h * w, tid = threadIdx.x;
-    const int p0 = blockIdx.x * 256;
-    float x1 = 0.f, x2 = (float)w, y1 = 0.f, y2 = (float)h;
-    if (boxes) {
-        const float* b = boxes + (int64_t)r * 4;
-        stm_sanitize(b[0], b[2], w, 1, x1, x2);
-        stm_sanitize(b[1], b[3], h, 1, y1, y2);
-    }
-    float* out = part + ((int64_t)blockIdx.x * n + r) * M;
-    {   // does the rectangle touch this workgroup's pixel span at all (the forward's test)
-        const int pl = min(p0 + 255, hw - 1);
-        const int ya = p0 / w, yb = pl / w;
-        bool t = (float)yb >= y1 && (float)ya < y2;
-        if (t && ya == yb) t = (float)(pl - ya * w) >= x1 && (float)(p0 - ya * w) < x2;
-        if (!t) {                                            // workgroup-uniform
-            if (tid < M) out[tid] = 0.0f;
-            return;
-        }
-    }
-    int set = row_proto ? row_proto[r] : 0;
-    set = set < 0 ? 0 : (set >= n_proto ? n_proto - 1 : set);
-    const float* pset = proto + (int64_t)set * hw * M;
-    if (tid < M) {
-        const float v = coeff[(int64_t)r * M + tid];
-        sc[tid] = apply_tanh ? tanhf(v) : v;
-    }
-    __syncthreads();
-    const int pix = p0 + tid;
-    const int y = pix / w, x = pix - y * w;
-    const float fx = (float)x, fy = (float)y;
-    float z = 0.0f;
-    if (pix < hw && fx >= x1 && fx < x2 && fy >= y1 && fy < y2) {
-        const float4* pr = reinterpret_cast<const float4*>(pset + (int64_t)pix * M);
-        float a = 0.0f;
-#pragma unroll
-        for (int q = 0; q < M / 4; ++q) {
-            const float4 v = pr[q];
-            a = fmaf(v.x, sc[4 * q], a);
-            a = fmaf(v.y, sc[4 * q + 1], a);
-            a = fmaf(v.z, sc[4 * q + 2], a);
-            a = fmaf(v.w, sc[4 * q + 3], a);
-        }
-        const float e = expf(-fabsf(a));
-        const float ope = 1.0f + e;
-        z = grad_out[(int64_t)r * hw + pix] * (e / (ope * ope));
-    }
-    zs[tid] = z;
-    __syncthreads();
-    const int kk = tid % M, g = tid / M;                     // prototype kk of pixels p0 + g * M + j, added in pixel order
-    float acc = 0.0f;
-#pragma unroll 8
-    for (int j = 0; j < M; ++j) {
-        const int pj = p0 + g * M + j;
-        const float pv = pj < hw ? pset[(int64_t)pj * M + kk] : 0.0f;
-        acc = fmaf(zs[g * M + j], pv, acc);
-    }
-    gs[g * M + kk] = acc;
-    __syncthreads();
-    if (tid < M) {
-        float s = 0.0f;
-#pragma unroll
-        for (int g2 = 0; g2 < G; ++g2) s += gs[g2 * M + tid];
-        out[tid] = s;
-    }
-}
-
-// grad_coeff[r] = (sum over the pixel blocks, in block order, of part[b][r]) * (1 - tanh(coeff[r])^2); rows past the live count: zeros
-__global__ __launch_bounds__(256) void lincomb_rows_reduce_kernel(const float* __restrict__ part, const float* __restrict__ coeff,
-                                                                  const int* __restrict__ n_dev, float* __restrict__ grad_coeff, int n, int M,
-                                                                  int blocks, int apply_tanh)
-{
-    const int64_t total = (int64_t)n * M;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int nv = n_dev ? min(max(*n_dev, 0), n) : n;
-    float s = 0.0f;
-    if (i / M < nv) {
-        for (int b0 = 0; b0 < blocks; b0 += 8) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = b0 + j < blocks ? part[(int64_t)(b0 + j) * total + i] : 0.0f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s += v[j];
-        }
-        if (apply_tanh) {                                    // 1 - tanh(c)^2 = 4 e / (1 + e)^2, e = exp(-2 |c|)
-            const float e = expf(-2.0f * fabsf(coeff[i]));
-            const float ope = 1.0f + e;
-            s = s * (4.0f * e / (ope * ope));
-        }
-    }
-    grad_coeff[i] = s;
-}
-
-int t2s_check(const char* who, int B, int P)
-{
-    STM_REQUIRE(B >= 1 && P >= 1, STM_EINVAL, "%s: B=%d P=%d", who, B, P);
-    STM_REQUIRE((int64_t)B * P <= PL_MAX_N, STM_EUNSUPPORTED, "%s: B*P=%lld > %d rows", who, (long long)B * P, PL_MAX_N);
-    return STM_OK;
-}
-
-bool ts_aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
-
 }  // namespace
 
 extern "C" size_t stm_t2s_workspace_bytes(int B, int P)
 {
     if (B <= 0 || P <= 0 || (int64_t)B * P > PL_MAX_N) return 64;
-    return t2s_layout(B, P).words * sizeof(unsigned) + 64;
+    return pos_layout(B, P).words * sizeof(unsigned) + 64;
 }
 
 extern "C" int stm_t2s_targets_f32(const int64_t* ids_t, const float* boxes_ref, const int64_t* ids_ref, const int* offs_ref, int G_ref_total,
@@ -387,7 +246,7 @@ extern "C" int stm_t2s_targets_f32(const int64_t* ids_t, const float* boxes_ref,
                                    void* workspace, size_t workspace_bytes, stm_stream_t stream)
 {
     const char* who = "stm_t2s_targets_f32";
-    const int rc = t2s_check(who, B, P);
+    const int rc = pos_check(who, B, P);
     if (rc != STM_OK) return rc;
     STM_REQUIRE(G_ref_total >= 0 && G_next_total >= 0 && G_ref_max >= 0 && G_next_max >= 0 && G_ref_max <= G_ref_total &&
                     G_next_max <= G_next_total, STM_EINVAL, "%s: box counts %d (max %d) / %d (max %d)", who, G_ref_total, G_ref_max, G_next_total,
@@ -398,11 +257,11 @@ extern "C" int stm_t2s_targets_f32(const int64_t* ids_t, const float* boxes_ref,
                 "%s: ids_t/offs_ref/offs_next/pos_t/reg_t/idx_next must be non-NULL", who);
     STM_REQUIRE((G_ref_total == 0 || (boxes_ref && ids_ref)) && (G_next_total == 0 || (boxes_next && ids_next)), STM_ENULL,
                 "%s: boxes and ids of a frame set with rows must be non-NULL", who);
-    STM_REQUIRE(ts_aligned16(boxes_ref) && ts_aligned16(boxes_next) && ts_aligned16(reg_t), STM_EINVAL,
+    STM_REQUIRE(stm_aligned16(boxes_ref) && stm_aligned16(boxes_next) && stm_aligned16(reg_t), STM_EINVAL,
                 "%s: boxes_ref, boxes_next and reg_t must be 16-byte aligned", who);
     STM_REQUIRE(workspace && workspace_bytes >= stm_t2s_workspace_bytes(B, P) && (uintptr_t)workspace % 8 == 0, STM_EWORKSPACE,
                 "%s: workspace missing, too small or not 8-byte aligned", who);
-    const T2sLayout L = t2s_layout(B, P);
+    const PosLayout L = pos_layout(B, P);
     unsigned* ws = reinterpret_cast<unsigned*>(workspace);
     const int tpi = stm_cdiv(P, PL_TILE), nT = B * tpi;
     hipStream_t st = stm_hs(stream);
@@ -410,13 +269,7 @@ extern "C" int stm_t2s_targets_f32(const int64_t* ids_t, const float* boxes_ref,
                        G_ref_total, reinterpret_cast<const float4*>(boxes_next), ids_next, offs_next, G_next_total, pos_t,
                        reinterpret_cast<float4*>(reg_t), idx_next, ws + L.tilecnt, P, tpi);
     STM_CHECK_LAUNCH("t2s_targets_kernel");
-    hipLaunchKernelGGL(pos_scan_kernel, dim3(1), dim3(256), 0, st, ws + L.tilecnt, ws + L.tilepre, ws + L.npos, ws + L.meta, prefix,
-                       max_rows > 0 ? (unsigned)max_rows : 0xFFFFFFFFu, nT, B, tpi);
-    STM_CHECK_LAUNCH("pos_scan_kernel");
-    hipLaunchKernelGGL(pos_index_kernel, dim3(nT), dim3(256), 0, st, pos_t, ws + L.tilepre, ws + L.npos, reinterpret_cast<int*>(ws + L.idx),
-                       reinterpret_cast<float*>(ws + L.wts), P, tpi);
-    STM_CHECK_LAUNCH("pos_index_kernel");
-    return STM_OK;
+    return pos_list(pos_t, false, prefix, max_rows, B, P, ws, L, st);   // (the target kernel wrote the tiles' counts)
 }
 
 extern "C" int stm_t2s_gather_f32(const float* loc_ref, const float* priors, const float* coeff_ref, const float* reg_t, const int64_t* idx_next,
@@ -425,7 +278,7 @@ extern "C" int stm_t2s_gather_f32(const float* loc_ref, const float* priors, con
                                   int feat_h, int feat_w, const void* workspace, size_t workspace_bytes, stm_stream_t stream)
 {
     const char* who = "stm_t2s_gather_f32";
-    const int rc = t2s_check(who, B, P);
+    const int rc = pos_check(who, B, P);
     if (rc != STM_OK) return rc;
     STM_REQUIRE(n_rows >= 1 && G_next_total >= 1 && feat_h >= 1 && feat_w >= 1, STM_EINVAL, "%s: n_rows=%d G_next_total=%d feature map %dx%d", who,
                 n_rows, G_next_total, feat_h, feat_w);
@@ -433,12 +286,12 @@ extern "C" int stm_t2s_gather_f32(const float* loc_ref, const float* priors, con
     STM_REQUIRE(M == 8 || M == 32 || M == 64, STM_EUNSUPPORTED, "%s: mask_dim %d not in {8,32,64}", who, M);
     STM_REQUIRE(loc_ref && priors && coeff_ref && reg_t && idx_next && boxes_next && rois && reg_rows && coeff_rows && box_rows && idx_rows &&
                     row_clip && w_rows && n_dev && status, STM_ENULL, "%s: NULL argument", who);
-    STM_REQUIRE(ts_aligned16(loc_ref) && ts_aligned16(priors) && ts_aligned16(coeff_ref) && ts_aligned16(reg_t) && ts_aligned16(boxes_next) &&
-                    ts_aligned16(reg_rows) && ts_aligned16(coeff_rows) && ts_aligned16(box_rows), STM_EINVAL,
+    STM_REQUIRE(stm_aligned16(loc_ref) && stm_aligned16(priors) && stm_aligned16(coeff_ref) && stm_aligned16(reg_t) && stm_aligned16(boxes_next) &&
+                    stm_aligned16(reg_rows) && stm_aligned16(coeff_rows) && stm_aligned16(box_rows), STM_EINVAL,
                 "%s: the fp32 inputs and the row outputs must be 16-byte aligned", who);
     STM_REQUIRE(workspace && workspace_bytes >= stm_t2s_workspace_bytes(B, P) && (uintptr_t)workspace % 8 == 0, STM_EWORKSPACE,
                 "%s: workspace missing, too small or not 8-byte aligned (it is the one stm_t2s_targets_f32 filled)", who);
-    const T2sLayout L = t2s_layout(B, P);
+    const PosLayout L = pos_layout(B, P);
     const unsigned* ws = reinterpret_cast<const unsigned*>(workspace);
     GatherArgs a;
     a.loc = reinterpret_cast<const float4*>(loc_ref);
@@ -494,46 +347,5 @@ extern "C" int stm_t2s_reduce_backward_f32(const float* grad_b, const float* gra
                        box_rows, w_rows, n_dev, status, grad_bbox_reg, grad_bce, n_rows, H, W, boxshift_alpha / (double)B,
                        maskshift_alpha / (double)B);
     STM_CHECK_LAUNCH("t2s_reduce_backward_kernel");
-    return STM_OK;
-}
-
-extern "C" size_t stm_lincomb_rows_backward_workspace_bytes(int n, int h, int w, int m)
-{
-    if (n <= 0 || h <= 0 || w <= 0 || m <= 0) return 64;
-    const size_t pb = (size_t)(((int64_t)h * w + 255) / 256);
-    return pb * (size_t)n * m * sizeof(float) + 64;
-}
-
-extern "C" int stm_lincomb_rows_backward_f32(const float* grad_out, const float* proto, int n_proto, const float* coeff, const float* boxes,
-                                             const int* row_proto, const int* n_dev, float* grad_coeff, int h, int w, int m, int n, int apply_tanh,
-                                             void* workspace, size_t workspace_bytes, stm_stream_t stream)
-{
-    const char* who = "stm_lincomb_rows_backward_f32";
-    STM_REQUIRE(n >= 0 && n_proto >= 1, STM_EINVAL, "%s: n=%d n_proto=%d", who, n, n_proto);
-    STM_REQUIRE(h > 0 && w > 0 && (int64_t)h * w * n_proto < (1ll << 31) - 256, STM_EINVAL, "%s: bad mask size %dx%d x %d sets", who, h, w, n_proto);
-    STM_REQUIRE(m == 8 || m == 32 || m == 64, STM_EUNSUPPORTED, "%s: mask_dim %d not in {8,32,64}", who, m);
-    STM_REQUIRE(n <= TS_MAX_ROWS, STM_EUNSUPPORTED, "%s: n=%d > %d", who, n, TS_MAX_ROWS);
-    if (n == 0 || !grad_coeff) return STM_OK;
-    STM_REQUIRE(grad_out && proto && coeff, STM_ENULL, "%s: grad_out/proto/coeff must be non-NULL", who);
-    STM_REQUIRE(ts_aligned16(proto), STM_EINVAL, "%s: proto must be 16-byte aligned", who);
-    STM_REQUIRE(workspace && workspace_bytes >= stm_lincomb_rows_backward_workspace_bytes(n, h, w, m) && (uintptr_t)workspace % 4 == 0,
-                STM_EWORKSPACE, "%s: workspace missing or too small", who);
-    const int pb = stm_cdiv((int64_t)h * w, 256);
-    float* part = reinterpret_cast<float*>(workspace);
-    const dim3 grid(pb, n);
-    hipStream_t st = stm_hs(stream);
-    if (m == 32)
-        hipLaunchKernelGGL((lincomb_rows_backward_kernel<32>), grid, dim3(256), 0, st, grad_out, proto, coeff, boxes, row_proto, n_dev, part, h, w, n,
-                           n_proto, apply_tanh);
-    else if (m == 8)
-        hipLaunchKernelGGL((lincomb_rows_backward_kernel<8>), grid, dim3(256), 0, st, grad_out, proto, coeff, boxes, row_proto, n_dev, part, h, w, n,
-                           n_proto, apply_tanh);
-    else
-        hipLaunchKernelGGL((lincomb_rows_backward_kernel<64>), grid, dim3(256), 0, st, grad_out, proto, coeff, boxes, row_proto, n_dev, part, h, w, n,
-                           n_proto, apply_tanh);
-    STM_CHECK_LAUNCH("lincomb_rows_backward_kernel");
-    hipLaunchKernelGGL(lincomb_rows_reduce_kernel, dim3(stm_cdiv((int64_t)n * m, 256)), dim3(256), 0, st, part, coeff, n_dev, grad_coeff, n, m, pb,
-                       apply_tanh);
-    STM_CHECK_LAUNCH("lincomb_rows_reduce_kernel");
     return STM_OK;
 }

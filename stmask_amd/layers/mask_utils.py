@@ -1,7 +1,7 @@
 """generate_mask (reference layers/mask_utils.py:111-128): tanh(coeff) -> proto @ coeff^T -> sigmoid -> crop -> [n,h,w],
 as ONE fused gfx950 kernel (the reference: matmul + 2 activations + 8 element-wise kernels + permute copy).
 When an input requires grad the call goes through autograd.LincombMaskFunction: the same launch, with the backward of
-csrc/mask_backward.hip behind it.
+csrc/lincomb_backward.hip behind it.
 
 mask_bce_sum and lincomb_mask_loss_image: the tail of the reference's lincomb_mask_loss (layers/modules/multibox_loss.py:594-616, and :293-317 of
 track_to_segment_loss) over csrc/mask_loss.hip -- target gather, bilinear upsampling, clamp, BCE and the per-instance sum in one kernel, its adjoint
@@ -24,7 +24,7 @@ def generate_mask(proto_data, mask_coeff, bbox=None, use_sipmask=False):
 def generate_mask_rows(proto_data, mask_coeff, bbox, row_proto, n_dev=None):
     """generate_mask for rows of many clips in one launch: proto_data [bs,h,w,M] (read detached), mask_coeff [n,M], bbox [n,4], row_proto int32 [n]
     (row i uses proto_data[row_proto[i]]), n_dev int32 [1] or None (rows past it are zeros) -> [n,h,w], bit-identical to per-clip generate_mask
-    calls.  Gradient w.r.t. mask_coeff only (autograd.LincombRowsFunction over csrc/t2s_loss.hip)."""
+    calls.  Gradient w.r.t. mask_coeff only (autograd.LincombRowsFunction over csrc/lincomb_backward.hip)."""
     proto_data = proto_data.detach()
     if proto_data.dim() != 4:
         raise ValueError(f"generate_mask_rows: proto_data must be [bs,h,w,M], got {tuple(proto_data.shape)}")

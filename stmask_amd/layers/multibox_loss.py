@@ -1,5 +1,5 @@
 """The reference's training criterion (layers/modules/multibox_loss.py) on the device: lincomb_mask_loss, the batched form of losses['M']
-(:544-616, :636) over csrc/mbox_loss.hip, and MultiBoxLoss, the module that turns `predictions` and the ground-truth lists into the
+(:544-616, :636) over csrc/mbox_loss.hip and csrc/lincomb_backward.hip, and MultiBoxLoss, the module that turns `predictions` and the ground-truth lists into the
 reference's dict of losses from the device functions of this package.  The reference forms the mask term image by image -- a boolean gather
 (a host round trip), a decode, a mask, an interpolation, four [n,H,W] fp32 tensors and its own backward per image; here the positives of the
 whole batch are listed once on the device, one gather builds every per-row input, and the mask (generate_mask_rows' kernel), its BCE

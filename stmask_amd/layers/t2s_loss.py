@@ -1,4 +1,4 @@
-"""The reference's track_to_segment_loss (layers/modules/multibox_loss.py:247-326, called at :102-110) over csrc/t2s_loss.hip: losses['B_shift'] and
+"""The reference's track_to_segment_loss (layers/modules/multibox_loss.py:247-326, called at :102-110) over csrc/t2s_loss.hip and csrc/lincomb_backward.hip: losses['B_shift'] and
 losses['M_shift'], the loss that trains TemporalNet.  The reference works clip by clip with a Python loop over the ground-truth ids, a device-to-host
 read per id, boolean gathers, a list.index per positive prior, one tiny-batch TemporalNet call per clip and four fp32 [n,H,W] tensors for the mask
 term.  Here the targets of the whole batch come from three launches, one gather builds every per-row input, and RoIAlign, TemporalNet, the mask

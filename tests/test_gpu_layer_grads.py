@@ -1,5 +1,5 @@
 """Gradients of the rebound layer functions on the MI355X -- layers.mask_utils.generate_mask, layers.box_utils.decode and jaccard (stmask_amd/autograd.py
-over csrc/mask_backward.hip) -- held to the fp64 restatements of tests/layer_grad_restate.py, which test_layer_grads_cpu.py pins to the reference's own
+over csrc/lincomb_backward.hip and csrc/mask_backward.hip) -- held to the fp64 restatements of tests/layer_grad_restate.py, which test_layer_grads_cpu.py pins to the reference's own
 fp64 autograd.  The tests call only stmask_amd.layers and the restatements: on a tree without the backward kernels every case fails with "no gradient".
 
 Tolerance (the project's form): |g - g64| <= rel * sum|terms| + 1e-7, sum|terms| being the same gradient on absolute values.

@@ -1,4 +1,4 @@
-"""The batched mask term (csrc/mbox_loss.hip behind layers.lincomb_mask_loss and the ops.mbox_* entries) and the criterion module
+"""The batched mask term (csrc/mbox_loss.hip and csrc/lincomb_backward.hip behind layers.lincomb_mask_loss and the ops.mbox_* entries) and the criterion module
 layers.MultiBoxLoss on the MI355X, held to the fp64 restatement of tests/mbox_loss_restate.py (which tests/test_mbox_loss_cpu.py pins to the
 reference's own run) with its derived bounds, to bit-level contracts against the kernels the project already has, and term by term to the
 reference's golden forward (tests/golden/mbox_loss_cases.npz).
@@ -226,6 +226,10 @@ def test_rows_proto_backward_against_the_single_set_kernel(M, sizes, hw):
         (gp64, _), (mag, _) = ref
         single, _ = ops.lincomb_sigmoid_crop_backward(g[sl], p[s], c[sl], b[sl], need_coeff=False)     # stm_lincomb_backward_f32, set by set
         worst = max(worst, LR.worst_ratio(gp[s], gp64, mag), LR.worst_ratio(gp[s], single.cpu().double(), mag))
+        if hw == (128, 176):
+            # 88 pixel blocks x 3 sets: no row splits here, one 16-row chunk and so no splits in the single-set kernel either; both add the
+            # rows in row order through the one fmaf chain of csrc/lincomb_backward.hip: the same bits
+            assert torch.equal(gp[s], single), s
     print(f"\nM={M} {hw[0]}x{hw[1]}: grad_proto of the row kernel, worst |g - g64| and |g - single-set kernel| / (1e-5 * sum|terms| + 1e-7) = {worst:.3f}")
     assert worst <= 1.0
     # a prefix that lies (rows past n, a negative start): clamped, never read outside

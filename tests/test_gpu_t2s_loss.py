@@ -1,4 +1,4 @@
-"""The temporal-fusion loss (csrc/t2s_loss.hip behind layers.track_to_segment_loss, layers.generate_mask_rows and the ops.t2s_* entries) on the
+"""The temporal-fusion loss (csrc/t2s_loss.hip and csrc/lincomb_backward.hip behind layers.track_to_segment_loss, layers.generate_mask_rows and the ops.t2s_* entries) on the
 MI355X, held to the fp64 restatement of tests/t2s_loss_restate.py (which tests/test_t2s_loss_cpu.py pins to the reference's own run) with its
 derived bounds, and end to end -- RoIAlign, the stand-in TemporalNet, the mask, its BCE and the reductions -- to the fp64 composition.
 
