@@ -372,7 +372,14 @@ typedef struct stm_conv_geom {
  * outputs have B * win_h * win_w rows); its kh / kw / ph / pw / Ho / Wo / win_y0 / win_x0 are ignored.  At most 9 windows.
  * Use: the border classes of a "same" 3x3 convolution on small maps (TemporalNet, track_to_segment_head.py:10-37: three 3x3 / pad-1 layers on
  * 7x7 RoI maps) -- rows {0}, {1..H-2}, {H-1} x columns likewise, each with the taps that can be inside the map: 361 of 441 tap-pixels are
- * multiplied instead of 441, and the results are the same sums (bit-equal to the padded launch). */
+ * multiplied instead of 441, and the results are the same sums (bit-equal to the padded launch).
+ * GATED window set (stm_conv_set_pixel_gate(gate) in front of the call; rejected before this form existed): the B images are n_windows equal
+ * SEGMENTS, window i is computed for the images of segment i only ([i B / n, (i + 1) B / n): B must divide) and reads its own device gate
+ * gate[16 i], counted in output pixels of window i (images x Ho_i x Wo_i): its 256-pixel tiles at or past that count leave before they stage
+ * anything.  Every window carries the layer's whole kernel (kh / kw of window 0, ONE packed weight given n times) with all its taps inside the
+ * H x W input (a valid convolution: ph = -y0, pw = -x0), and g->groups / g->group_cout are honoured as by stm_conv2d_planar_f32.  One grid, per
+ * output pixel the products of the single gated window launch in the same order.  Use: the sparse head's patch towers in the shapes form below,
+ * one window per kernel shape, the gates 16 ints apart as that form's control blocks are. */
 typedef struct stm_conv_window { int kh, kw, ph, pw, Ho, Wo, y0, x0; } stm_conv_window;
 int stm_conv2d_planar_windows_f32(const void* x_planes, const void* const* packed_weights, const stm_conv_window* windows, int n_windows,
                                   const float* bias, float* out_f32, void* out_planes, const stm_conv_geom* g, int relu, stm_stream_t stream);
@@ -628,7 +635,21 @@ int stm_head_assemble_f32(const float* const* small, const float* const* trk, co
  *     those it reads columns 0..4 of small[k] and neither the mask columns nor trk[k].
  * Only centerness is read at a partner-only position, and it comes out of the bbox branch: the mask and track branches need the own
  * positions only.  Their launches take ctl + 8 wherever the launches over all positions take ctl (stm_head_patch_mask,
- * stm_conv_set_pixel_gate(ctl + 8 + 3 | 4 | 7)) and are otherwise the same calls; stm_head_patch_gather takes ctl. */
+ * stm_conv_set_pixel_gate(ctl + 8 + 3 | 4 | 7)) and are otherwise the same calls; stm_head_patch_gather takes ctl.
+ *
+ * Shapes form: K << 28 ADDED to |capacity| of the split form at stm_head_candidates_f32 and stm_head_assemble_sparse_f32 (K <= 3), and the number
+ * of segments << 28 added to the capacity of stm_head_patch_gather / stm_head_patch_mask (values rejected before it existed).  A kept prior
+ * (pixel, shape k) is read at output layer k only, and the centerness that goes with the prior of row r is shape r / (h w) at pixel r % (h w): the
+ * list holds (pixel, shape) ENTRIES, K segments of `capacity` entries each, segment k = list[k capacity, (k + 1) capacity) = the entries of shape
+ * k, own entries (prior (pixel, k) is kept) in front of the partner-only ones; a pixel with two needed shapes is listed in two segments.
+ *   - flags holds pixels + 2 K ints, ctl 16 (K + 1) ints: ctl[16 (k + 1) ..] is segment k's pair of blocks (all entries, own entries) with the
+ *     fields of the split form, its pixel gates [3] / [4] counted in pixels of shape k's WINDOW of the two tower layers -- patch_pixels_a / _b carry
+ *     one 8-bit count per segment, segment k's in bits [8 k, 8 k + 8); ctl[0..15] hold the sums over the segments ([0] / [1] / [7] entries, [2]
+ *     patches, [3] / [4] pixels) and [5] / [6], the dense launches' gate and the overflow flag: ONE segment over its capacity empties every segment;
+ *   - patch i of segment k is slot k capacity + i of the patch buffers (stm_head_patch_gather, stm_head_patch_mask; dst_planes holds segments x
+ *     capacity patches), so a tower layer is one gated window set (stm_conv2d_planar_windows_f32) with gate = ctl + 16 + 3 | 4 (+ 8: own entries);
+ *   - stm_head_assemble_sparse_f32 reads row i * row_mul + row_add of small[k] / trk[k] for entry i of segment k and writes that prior's row (loc
+ *     and the centerness slot of (pixel, k); mask and track for own entries only). */
 void stm_conv_set_pixel_gate(const int* valid_pixels);
 int stm_head_candidates_f32(const float* const* cls_logits, int K, int ld, int n_cls, float conf_thresh, int capacity,
                             int patch_pixels_a, int patch_pixels_b, int n_levels, int B, const int* lvl_start, const int* lvl_h,

@@ -1,6 +1,7 @@
 #!/bin/bash
-# Same-box A/B of one switch of the sparse head, off / on: STM_HEAD_CENTER (output layers at the centre pixel) or STM_HEAD_SPLIT (mask and track
-# branches at the positions with a kept prior of their own only).  Parts, in this order, each optional:
+# Same-box A/B of one switch of the sparse head, off / on: STM_HEAD_CENTER (output layers at the centre pixel), STM_HEAD_SPLIT (mask and track
+# branches at the positions with a kept prior of their own only) or STM_HEAD_SHAPES (patch towers over each entry's own kernel footprint).
+# Parts, in this order, each optional:
 #   stages  the head's stages timed alone both ways (scripts/bench_sparse_head_stages.py)                      -> <tag>_stages.txt
 #   bench   one plain run of bench.py that is not recorded (the first run on a box is slow), alternating plain runs at 32 clips, then -- where a
 #           built checkout of the parent commit is given -- one run of it and one of this tree with their detections.npy compared, and one
@@ -8,10 +9,10 @@
 #   small   alternating plain runs at 8 and 4 clips                                                             -> <tag>_ab.txt (appended)
 #   trace   one rocprofv3 kernel trace of each side through scripts/summarize_trace.py                          -> bench_kernel_stats_<tag>_<0|1>.md
 # <tag> is the switch's name in lower case without STM_.  Every GPU step runs under its own time limit, and the script stops at the first failure.
-# usage: ab_head_switch.sh STM_HEAD_CENTER|STM_HEAD_SPLIT [out dir] [pairs at 32 clips] [pairs at 8 and 4 clips] [parent checkout] [parts]
+# usage: ab_head_switch.sh STM_HEAD_CENTER|STM_HEAD_SPLIT|STM_HEAD_SHAPES [out dir] [pairs at 32 clips] [pairs at 8 and 4 clips] [parent checkout] [parts]
 set -o pipefail
-SW=${1:?usage: ab_head_switch.sh STM_HEAD_CENTER|STM_HEAD_SPLIT [out dir] [pairs] [pairs at 8 and 4 clips] [parent checkout] [parts]}
-case "$SW" in STM_HEAD_CENTER|STM_HEAD_SPLIT) ;; *) echo "unknown switch $SW"; exit 2 ;; esac
+SW=${1:?usage: ab_head_switch.sh STM_HEAD_CENTER|STM_HEAD_SPLIT|STM_HEAD_SHAPES [out dir] [pairs] [pairs at 8 and 4 clips] [parent checkout] [parts]}
+case "$SW" in STM_HEAD_CENTER|STM_HEAD_SPLIT|STM_HEAD_SHAPES) ;; *) echo "unknown switch $SW"; exit 2 ;; esac
 TAG=$(echo "${SW#STM_}" | tr 'A-Z' 'a-z')
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${2:-$R/profiles}
@@ -41,7 +42,7 @@ if has stages; then
             env $SW=$side timeout -k 10 300 python3 scripts/bench_sparse_head_stages.py 2> "$OUT/ab_err.txt" || fail "bench_sparse_head_stages.py"
         done
     } > "$OUT/${TAG}_stages.txt"
-    grep -E "^==|patches|candidates|^assemble|^sum" "$OUT/${TAG}_stages.txt"
+    grep -E "^==|patches|candidates|^assemble|^sum|shape" "$OUT/${TAG}_stages.txt"
 fi
 if has bench; then
     : > "$OUT/${TAG}_ab.txt"

@@ -45,6 +45,11 @@ def main():
                 row["positions_last_capture"] = ctl[ops.HEAD_CTL_RAW]
                 row["capacity"] = net._planar.sparse_capacity(args.clips, [(48, 80), (24, 40), (12, 20), (6, 10), (3, 5)]) if (args.height, args.width) == (384, 640) else None
                 row["overflow_last_capture"] = ctl[ops.HEAD_CTL_OVERFLOW]
+                if net._planar.sparse_segments is not None:     # shapes form: "positions" are (pixel, shape) entries; per kernel shape, and the segments' size
+                    full, _, seg_cap = net._planar.sparse_segments
+                    full = full.tolist()
+                    row["entries_per_shape"] = [full[ops.HEAD_CTL_SEG * (k + 1) + ops.HEAD_CTL_RAW] for k in range(len(full) // ops.HEAD_CTL_SEG - 1)]
+                    row["segment_capacity"] = seg_cap
             del r
             torch.cuda.synchronize()
             torch.cuda.empty_cache()

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """The shared head's stages timed alone on the benchmark's tensors (32 clips, eager, HIP events, nothing beside them): the eager trunk with
 the dense and the sparse head, then each launch group of PlanarGraph._sparse_head and of the dense head (best of four passes).
-Wrote profiles/sparse_head_stages.txt and, run with STM_HEAD_CENTER / STM_HEAD_SPLIT = 0 and 1 by scripts/ab_head_switch.sh,
-profiles/head_center_stages.txt / profiles/head_split_stages.txt.
-usage: [STM_HEAD_CENTER=0] [STM_HEAD_SPLIT=0] bench_sparse_head_stages.py > profiles/sparse_head_stages.txt"""
+Wrote profiles/sparse_head_stages.txt and, run with STM_HEAD_CENTER / STM_HEAD_SPLIT / STM_HEAD_SHAPES = 0 and 1 by scripts/ab_head_switch.sh,
+profiles/head_center_stages.txt / profiles/head_split_stages.txt / profiles/head_shapes_stages.txt.  Also prints the shape mix of the listed
+(position, kernel shape) entries, which the shapes form's gain follows from.
+usage: [STM_HEAD_CENTER=0] [STM_HEAD_SPLIT=0] [STM_HEAD_SHAPES=0] bench_sparse_head_stages.py > profiles/sparse_head_stages.txt"""
 import os, sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -67,7 +68,14 @@ head = pg.head
 CENTER = planar.head_center_default()      # STM_HEAD_CENTER=0: the output layers over all 25 pixels of each patch map
 SPLIT = planar.head_split_default()        # STM_HEAD_SPLIT=0: the mask and track branches at every listed position
 OWN = ops.HEAD_CTL_OWN if SPLIT else 0
-print("output layers at the centre pixel only:", CENTER, " mask / track branches at the own positions only:", SPLIT)
+SHAPES = planar.head_shapes_default() and SPLIT and CENTER and pg.fmt == 1      # STM_HEAD_SHAPES=0: the towers over the whole maps of every listed pixel
+print("output layers at the centre pixel only:", CENTER, " mask / track branches at the own positions only:", SPLIT,
+      " towers over each entry's kernel footprint:", SHAPES)
+K, SEG = len(pg.finals), ops.HEAD_CTL_SEG
+SHP = [(c.kh, c.kw) for c in small_l]
+W1 = [(kh + 2, kw + 2, (5 - kh) // 2, (5 - kw) // 2) for kh, kw in SHP]
+W2 = [(kh, kw, (5 - kh) // 2, (5 - kw) // 2) for kh, kw in SHP]
+segn = pg.sparse_segment_capacity(capn)
 # the other form of the split head's cen+bbox | mask output layers: two single-group launches per kernel shape (cen+bbox over all positions, mask
 # over the own ones) instead of one grouped launch over all positions -- timed beside it, not used by PlanarGraph._sparse_head
 def cut_group(sm, g):
@@ -79,6 +87,31 @@ small_1g = [(cut_group(c, 0), cut_group(c, 1)) for c in small_l] if SPLIT and CE
 stages = []
 def ev():
     e = torch.cuda.Event(enable_timing=True); e.record(); return e
+def shapes_rest(cls, m):
+    # PlanarGraph._sparse_head_shapes from the candidates on: entries in one segment per kernel shape, the towers as gated window sets
+    lst, ctl = ops.head_candidates(cls, head.num_classes, thr, segn, [h * w for h, w, _, _ in W1], [h * w for h, w, _, _ in W2], B, sizes, split=True, shapes=True); m("candidates")
+    tot = K * segn
+    patch = ops.head_patch_gather(up, torch.empty(NP, cw // 32, tot * 81, 32, device=dev, dtype=pdt), 9, segn, B, sizes, lst, ctl, segs=K); m("gather 9x9")
+    x1 = torch.empty(NP, 3 * cw // 32, tot * 49, 32, device=dev, dtype=pdt)
+    xq = torch.empty(NP, 3 * cw // 32, tot * 25, 32, device=dev, dtype=pdt)
+    t1b, t1m, t2b, t2m = pg._split_layers
+    t1b.window_segments(patch, tot, 9, 9, W1, x1, 7, (ctl, SEG + 3)); m("t1 patches bbox")
+    t1m.window_segments(patch, tot, 9, 9, W1, x1, 7, (ctl, SEG + OWN + 3), out_slab_off=cw // 32); m("t1 patches mask+track")
+    ops.head_patch_mask(x1, 7, segn, B, sizes, lst, ctl, segs=K); m("mask 7")
+    t2b.window_segments(x1, tot, 7, 7, W2, xq, 5, (ctl, SEG + 4)); m("t2 patches bbox")
+    t2m.window_segments(x1, tot, 7, 7, W2, xq, 5, (ctl, SEG + OWN + 4), x_ch_off=cw, out_slab_off=cw // 32); m("t2 patches mask+track")
+    ops.head_patch_mask(xq, 5, segn, B, sizes, lst, ctl, segs=K); m("mask 5")
+    def centre(c, k, blk, **kw):
+        return c(xq, ("img", segn, 5, 5), x_off=k * segn * 25, out="f32", out_f32=torch.empty(segn, c.O, device=dev),
+                 window=(0, 0, 1, 1, c.ph - 2, c.pw - 2, 1, 1), gate=(ctl, SEG * (k + 1) + blk + ops.HEAD_CTL_GATE_POS), **kw)
+    small = [centre(c, k, 0, kxr=True) for k, c in enumerate(small_l)]; m("small patches x3")
+    trk = [centre(c, k, OWN, x_ch_off=2 * cw, kxr=False) for k, c in enumerate(trk_l)]; m("trk patches x3")
+    gd = (ctl, 5)
+    xx = t1r(up, lv, out="planes", gate=gd); xx = t2r(xx, lv, out="planes", gate=gd); m("dense towers (empty)")
+    small_d = [c(xx, lv, out="f32", gate=gd, kxr=True) for c in small_l]
+    trk_d = [c(xx, lv, out="f32", x_ch_off=2 * cw, gate=gd) for c in trk_l]; m("dense outputs (empty)")
+    ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P, 1, 0, lst, ctl, segn, split=True, shapes=True); m("assemble")
+    return ctl
 def run_once(record):
     marks = [("start", ev())]
     def m(name):
@@ -86,6 +119,12 @@ def run_once(record):
     xx = t1c(up, lv, out="planes", splitk=False); m("t1 class")
     xx = t2c(xx, lv, out="planes", splitk=False); m("t2 class")
     cls = [c(xx, lv, out="f32", splitk=False, kxr=True) for c in cls_l]; m("class output layers x3")
+    if SHAPES:
+        ctl = shapes_rest(cls, m)
+        torch.cuda.synchronize()
+        if record:
+            stages.append([(marks[i][0], marks[i - 1][1].elapsed_time(marks[i][1])) for i in range(1, len(marks))])
+        return ctl.tolist()
     lst, ctl = ops.head_candidates(cls, head.num_classes, thr, capn, 49, 25, B, sizes, split=SPLIT); m("candidates")
     patch = ops.head_patch_gather(up, torch.empty(NP, cw // 32, capn * 81, 32, device=dev, dtype=pdt), 9, capn, B, sizes, lst, ctl); m("gather 9x9")
     x1 = torch.empty(NP, 3 * cw // 32, capn * 49, 32, device=dev, dtype=pdt)
@@ -134,6 +173,27 @@ with torch.no_grad():
     for i in range(6):
         c = run_once(i >= 2)
 print("ctl", c)
+# the shape mix of this frame's entries (the candidate pass in the shapes form, whatever form is timed): entry (pixel, shape k) is OWN where prior
+# (pixel, k) is kept, PARTNER-only where shape k's centerness at that pixel is read with a kept prior elsewhere
+if pg.fmt == 1:
+    with torch.no_grad():
+        xx = t2c(t1c(up, lv, out="planes", splitk=False), lv, out="planes", splitk=False)
+        cls = [c_(xx, lv, out="f32", splitk=False, kxr=True) for c_ in cls_l]
+        lst_s, ctl_s = ops.head_candidates(cls, head.num_classes, thr, segn, [h * w for h, w, _, _ in W1], [h * w for h, w, _, _ in W2], B, sizes, split=True, shapes=True)
+        lst_p, ctl_p = ops.head_candidates(cls, head.num_classes, thr, capn, 49, 25, B, sizes, split=True)
+    cs, cp = ctl_s.tolist(), ctl_p.tolist()
+    n_k = [cs[SEG * (k + 1) + ops.HEAD_CTL_RAW] for k in range(K)]
+    o_k = [cs[SEG * (k + 1) + ops.HEAD_CTL_OWN + ops.HEAD_CTL_RAW] for k in range(K)]
+    from collections import Counter
+    seen = Counter(m_ for k in range(K) for m_ in lst_s[k * segn:k * segn + cs[SEG * (k + 1) + ops.HEAD_CTL_N]].tolist())
+    print("shape mix: positions", cp[ops.HEAD_CTL_RAW], "(own", cp[ops.HEAD_CTL_OWN + ops.HEAD_CTL_RAW], ") entries", sum(n_k), "(own", sum(o_k), ") segment capacity", segn)
+    for k in range(K):
+        print("  shape %dx%d: entries %d = own %d + partner-only %d" % (SHP[k][0], SHP[k][1], n_k[k], o_k[k], n_k[k] - o_k[k]))
+    print("  positions with more than one shape:", sum(1 for v in seen.values() if v > 1), "of", len(seen))
+    # tower pixel-layers per step: whole maps (49 + 25 per position; mask + track towers at the own ones) against the windows of each entry's shape
+    whole = (49 + 25) * (cp[ops.HEAD_CTL_RAW] + 2 * cp[ops.HEAD_CTL_OWN + ops.HEAD_CTL_RAW])
+    wins = sum((W1[k][0] * W1[k][1] + W2[k][0] * W2[k][1]) * (n_k[k] + 2 * o_k[k]) for k in range(K))
+    print("  tower pixel-layers x 256-channel branches: whole maps %d, windows %d (%.3f)" % (whole, wins, wins / whole))
 for j, (name, _) in enumerate(stages[0]):
     print("%-28s %8.3f ms" % (name, min(s[j][1] for s in stages)))
 print("sum", sum(min(s[j][1] for s in stages) for j in range(len(stages[0]))))

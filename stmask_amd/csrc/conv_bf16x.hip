@@ -95,6 +95,17 @@ struct PlanarArgsCls : PlanarArgs {
     int pool_ld;
     struct Cls { const uint8_t* wp; int kh, kw, ph, pw, Ho, Wo, M, slabs, win_off, tile0; float inv_hw, inv_w; } cls[9];
 };
+// ... whose classes run over SEGMENTS of the image batch (CLS = 2 instantiation; the sparse head's patch towers, one class per kernel shape): class c
+// covers its own run of images -- x_off[c] = byte offset of the run's first image inside a channel slab of the input, the output rows' offset is part
+// of win_off -- and reads its own device gate: tiles at or past *gate[c] pixels of the class leave before they stage anything.  (A type of its own
+// again: the table of TemporalNet's launches stays what it was.)
+struct PlanarArgsSeg : PlanarArgsCls {
+    const int* gate[9];
+    int x_off[9];
+};
+template <int CLS> struct planar_args { typedef PlanarArgs type; };
+template <> struct planar_args<1> { typedef PlanarArgsCls type; };
+template <> struct planar_args<2> { typedef PlanarArgsSeg type; };
 
 // Epilogue shared by the planar kernels: bias + residual (+ReLU) in fp32, then fp32 NHWC and/or the three bf16 planes.
 // Each wave first parks its 64 x (32*NJ) accumulator tile in LDS (free now) -- park32 / park16 know the C/D register layout
@@ -360,8 +371,8 @@ __device__ __forceinline__ void pooled_epilogue(const PlanarArgs& a, unsigned lo
 // expanding 1x1 convolutions, 337 vs 345 us, for 32 more live registers and one wave per SIMD less; and resident workgroups
 // walking the tiles instead of one workgroup per tile -- 404 -> 451 us.  Neither the epilogue's second memory round trip nor
 // workgroup launch overhead is what holds these layers at 3.3 TB/s.)
-template <int NPL, int MG, int NJ, int DT = 0, int ST = 2, int ABL = 0, bool DUAL = false, bool CLS = false>
-__global__ __launch_bounds__(512, 1) void conv_planar_kernel(const typename std::conditional<CLS, PlanarArgsCls, PlanarArgs>::type a_in)
+template <int NPL, int MG, int NJ, int DT = 0, int ST = 2, int ABL = 0, bool DUAL = false, int CLS = 0>
+__global__ __launch_bounds__(512, 1) void conv_planar_kernel(const typename planar_args<CLS>::type a_in)
 {
 #if defined(__HIP_DEVICE_COMPILE__)   // the LDS-DMA builtins exist only in the device pass; the host pass needs just the launch stub
     extern __shared__ __align__(16) uint8_t smem[];
@@ -407,6 +418,11 @@ __global__ __launch_bounds__(512, 1) void conv_planar_kernel(const typename std:
         a_cls.Ho = a_in.cls[c].Ho; a_cls.Wo = a_in.cls[c].Wo; a_cls.M = a_in.cls[c].M;
         a_cls.slabs = a_in.cls[c].slabs; a_cls.kslabs = a_in.cls[c].slabs; a_cls.win_off = a_in.cls[c].win_off;
         a_cls.inv_hw = a_in.cls[c].inv_hw; a_cls.inv_w = a_in.cls[c].inv_w;
+        if constexpr (CLS == 2) {
+            a_cls.xp = a_in.xp + a_in.x_off[c];
+            a_cls.plane_bytes = a_in.plane_bytes - (unsigned)a_in.x_off[c];
+            a_cls.m_gate = a_in.gate[c];
+        }
         logical -= a_in.cls[c].tile0;
         ap = &a_cls;
     }
@@ -830,7 +846,7 @@ __global__ __launch_bounds__(512, 1) void conv_planar_kernel(const typename std:
     __syncthreads();                                   // all fragment reads of the last slab are done
     constexpr float LS = DT == 1 ? 1.0f / STM_F16_LOW_SCALE : 1.0f;   // fp16 planes: the corrections carry the low-plane scale
     park16<NJ>(acc16, accl16, smem, wave, lane, LS);
-    if constexpr (CLS && NJ == 2) {
+    if constexpr (CLS == 1 && NJ == 2) {
         if (a_in.pool) {
             pooled_epilogue(a, a_in.pool, a_in.pool_ld, smem, wave, lane, m0 + wm * 64, nt * BN + wn * 64 + lane);
             return;
@@ -1248,8 +1264,8 @@ const ConvTunables& tunables()
     return t;
 }
 
-template <int NPL, int MG, int NJ, int DT = 0, int ST = 2, int ABL = 0, bool DUAL = false, bool CLS = false>
-int launch_planar(const typename std::conditional<CLS, PlanarArgsCls, PlanarArgs>::type& a, int tiles, stm_stream_t stream)
+template <int NPL, int MG, int NJ, int DT = 0, int ST = 2, int ABL = 0, bool DUAL = false, int CLS = 0>
+int launch_planar(const typename planar_args<CLS>::type& a, int tiles, stm_stream_t stream)
 {
     size_t lds = (size_t)ST * (NPL * CV_BM * MG * 64 + NPL * (64 * NJ) * 64);
     const size_t park = (size_t)4 * MG * 64 * (32 * NJ + 4) * sizeof(float);   // the epilogue parks one 64 x 32NJ tile per wave
@@ -1296,6 +1312,7 @@ extern "C" int stm_planar_set_range_flag(int* device_flag)
 }
 
 namespace {
+constexpr int STM_GATE_STRIDE = 16;      // ints between the gates of a gated window set's windows (the sparse head's control blocks: head_sparse.hip, CTL_SEG)
 struct WinSet { const void* const* packed; const stm_conv_window* win; int n; unsigned long long* pool; };
 struct DualSrc { const void* x2; int C2, H2, W2, s2; long long x2_np, x2_plane_stride; };
 int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const float* bias, const float* residual_f32,
@@ -1340,8 +1357,9 @@ extern "C" int stm_conv2d_planar_windows_f32(const void* x_planes, const void* c
     const char* who = "stm_conv2d_planar_windows_f32";
     STM_REQUIRE(packed_weights && windows && g, STM_ENULL, "%s: NULL argument", who);
     STM_REQUIRE(n_windows >= 1 && n_windows <= 9, STM_EINVAL, "%s: 1 .. 9 windows", who);
-    STM_REQUIRE(g->win_w > 0 && g->win_h > 0 && g->fmt == 1 && g->sh == 1 && g->sw == 1 && (g->groups <= 1) && g->n_levels <= 0 &&
-                (g->tile_n == 0 || g->tile_n == 128), STM_EUNSUPPORTED, "%s: fp16x2 planes, stride 1, one group, 128-channel tiles, win_h / win_w set", who);
+    // (groups: the gated form only, checked where the gate is taken)
+    STM_REQUIRE(g->win_w > 0 && g->win_h > 0 && g->fmt == 1 && g->sh == 1 && g->sw == 1 && g->n_levels <= 0 &&
+                (g->tile_n == 0 || g->tile_n == 128), STM_EUNSUPPORTED, "%s: fp16x2 planes, stride 1, 128-channel tiles, win_h / win_w set", who);
     for (int i = 0; i < n_windows; ++i) STM_REQUIRE(packed_weights[i], STM_ENULL, "%s: packed weight %d is NULL", who, i);
     stm_conv_geom g0 = *g;                       // window 0 stands in for the common checks and fields
     g0.kh = windows[0].kh; g0.kw = windows[0].kw; g0.ph = windows[0].ph; g0.pw = windows[0].pw;
@@ -1471,7 +1489,7 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
                 want_planes, g->planes);
     a.splitk = 1; a.kslabs = a.slabs; a.partial = nullptr; a.ldp = a.n_tiles * bn;
     a.m_gate = gate;
-    STM_REQUIRE(!gate || !wset, STM_EUNSUPPORTED, "%s: window sets take no pixel gate", who);
+    STM_REQUIRE(!gate || !wset || !wset->pool, STM_EUNSUPPORTED, "%s: pooled window sets take no pixel gate", who);
     a.xp2 = nullptr; a.x2_pstride = 0; a.plane2_bytes = 0; a.c1_slabs = a.slabs; a.x2_np = 0; a.H2 = a.W2 = 0; a.s2 = 1;
     if (dual) {
         const int64_t in2 = (int64_t)g->B * dual->H2 * dual->W2;
@@ -1527,8 +1545,51 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
         STM_CHECK_LAUNCH("planar_splitk_finish_kernel");
         return STM_OK;
     };
-    if (wset) {
+    if (wset && gate) {
+        // Gated window set = SEGMENTED window set (the sparse head's patch towers, one window per kernel shape): the B images are n equal runs, window i
+        // is computed for the images of run i only and gated by the device int gate[STM_GATE_STRIDE i], which counts output pixels of that window
+        // (images x Ho_i x Wo_i).  One grid of conv_planar_kernel<..., CLS = 2> for all of them: per output pixel the products, and their order, of the
+        // single gated window launch.  Groups as in that launch (every class has all the channel tiles).
         STM_REQUIRE(bn == 128 && a.fmt == 1 && !dual && win, STM_EUNSUPPORTED, "%s: window sets run on the 256 x 128 ring tiles of the fp16x2 format", who);
+        STM_REQUIRE(g->B % wset->n == 0, STM_EINVAL, "%s: %d images are not %d equal segments", who, g->B, wset->n);
+        const int seg_b = g->B / wset->n;
+        PlanarArgsSeg as;
+        static_cast<PlanarArgs&>(as) = a;
+        as.m_gate = nullptr;
+        as.pool = nullptr; as.pool_ld = 0;
+        int t0 = 0;
+        for (int i = 0; i < 9; ++i) {
+            const int wi = i < wset->n ? i : 0;
+            const stm_conv_window& w = wset->win[wi];
+            if (i < wset->n) {
+                STM_REQUIRE(w.kh == g->kh && w.kw == g->kw, STM_EUNSUPPORTED, "%s: the windows of a gated set share the layer's %dx%d kernel", who, g->kh, g->kw);
+                STM_REQUIRE(w.Ho > 0 && w.Wo > 0 && w.y0 >= 0 && w.x0 >= 0 && w.y0 + w.Ho <= g->win_h && w.x0 + w.Wo <= g->win_w, STM_EINVAL,
+                            "%s: window %d (%dx%d at %d, %d) is not inside the %dx%d output", who, i, w.Ho, w.Wo, w.y0, w.x0, g->win_h, g->win_w);
+                // every tap of every window pixel inside the input image: a segment's rows never read another segment's images
+                STM_REQUIRE(-w.ph >= 0 && -w.ph + (w.Ho - 1) + (w.kh - 1) <= g->H - 1 && -w.pw >= 0 && -w.pw + (w.Wo - 1) + (w.kw - 1) <= g->W - 1, STM_EINVAL,
+                            "%s: window %d reads outside the %dx%d input image", who, i, g->H, g->W);
+                STM_REQUIRE((uintptr_t)wset->packed[i] % 16 == 0, STM_EINVAL, "%s: packed weight %d is not 16-byte aligned", who, i);
+            }
+            const int64_t Mc = (int64_t)seg_b * w.Ho * w.Wo;
+            PlanarArgsCls::Cls& c = as.cls[i];
+            c.wp = static_cast<const uint8_t*>(wset->packed[wi]);
+            c.kh = w.kh; c.kw = w.kw; c.ph = w.ph; c.pw = w.pw; c.Ho = w.Ho; c.Wo = w.Wo; c.M = (int)Mc;
+            c.slabs = w.kh * w.kw * (g->C / CV_BK);
+            c.win_off = wi * seg_b * g->win_h * g->win_w + w.y0 * g->win_w + w.x0;
+            c.inv_hw = 1.0f / (float)(w.Ho * w.Wo); c.inv_w = 1.0f / (float)w.Wo;
+            c.tile0 = t0;
+            as.gate[i] = gate + STM_GATE_STRIDE * wi;
+            as.x_off[i] = (int)((int64_t)wi * seg_b * g->H * g->W * 64);
+            if (i < wset->n) t0 += stm_cdiv(Mc, 2 * CV_BM) * a.n_tiles;
+        }
+        as.n_cls = wset->n;
+        as.cls_tiles = t0;
+        as.m_tiles = 0;
+        return launch_planar<2, 2, 2, 1, 3, 0, false, 2>(as, stm_cdiv(t0 / a.n_tiles, 8) * 8 * a.n_tiles, stream);
+    }
+    if (wset) {
+        STM_REQUIRE(bn == 128 && a.fmt == 1 && !dual && win && groups == 1, STM_EUNSUPPORTED,
+                    "%s: window sets run on the 256 x 128 ring tiles of the fp16x2 format, one group unless gated", who);
         // Two grids: the windows whose sub-kernel has all three column taps inside the map (kw = 3: the interior-column border classes, 79 % of the
         // products of a 3x3 layer on 7x7 maps) take conv_planar_kx3_kernel<., WIN> -- one staged run per (channel slab, ky) and window row serves the
         // three taps -- the others (two column taps: the left / right columns) stay on conv_planar_kernel<..., CLS>.  Disjoint output rows.
@@ -1568,7 +1629,7 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
 #ifndef CLS_ABL
 #define CLS_ABL 0     // timing build (RESULTS WRONG): 16 = the window-set kernel issues its activation DMAs on every third K-slab only
 #endif
-                const int rc0 = launch_planar<2, 2, 2, 1, 3, CLS_ABL, false, true>(ac[0], stm_cdiv(t0[0] / a.n_tiles, 8) * 8 * a.n_tiles, stream);
+                const int rc0 = launch_planar<2, 2, 2, 1, 3, CLS_ABL, false, 1>(ac[0], stm_cdiv(t0[0] / a.n_tiles, 8) * 8 * a.n_tiles, stream);
                 if (rc0 != STM_OK) return rc0;
             } else {
                 constexpr size_t lds = 2 * 2 * 384 * 64 + 3 * KX3_WBUF;      // two 48-KB activation buffers + the weight ring (the epilogue's park needs less)

@@ -11,6 +11,8 @@
 //   head_control_kernel       count -> the control block the other launches read (below); more positions than the capacity -> the patch
 //                             launches are empty and the dense launches of the three branches run instead (the convolution launches are gated
 //                             by stm_conv_set_pixel_gate)
+//   head_control_segs_kernel, head_list_segs_kernel   (shapes form) the same for (pixel, kernel shape) entries in one segment per shape, each
+//                             with its own counts and gates: the patch towers then run over the rectangle that shape's output layers read
 //   head_patch_gather_kernel  S x S neighbourhoods of the listed positions from the level maps (zeros outside the map)
 //   head_patch_mask_kernel    zeroes the patch pixels outside the map in place (after each tower layer: the next layer's padding)
 //   head_assemble_*           prediction_head_FC.py:168-195 as head_assemble_kernel (mask_ops.hip) does it, same arithmetic: conf for every prior,
@@ -36,8 +38,30 @@ enum { CTL_RAW = 0,      // positions found (may exceed the capacity)
        // Split form (a negative capacity at the entry points): a second block of the same fields over the OWN positions -- the pixels with a kept
        // prior of their own, list[0, n_own); list[n_own, n) are the partner-only positions, where only centerness is read, so only the bbox branch
        // runs there.  A launch of the mask / track branches takes ctl + CTL_OWN as its control block or gate and is otherwise the same launch.
-       CTL_OWN = 8 };
+       CTL_OWN = 8,
+       // Shapes form (K << 28 added to the capacity at the entry points): the list holds (pixel, kernel shape) ENTRIES in K segments of `capacity`
+       // entries each, segment k = list[k capacity, (k + 1) capacity), own entries in front of the partner-only ones as in the split form.  Segment k
+       // has a pair of blocks of its own at ctl + CTL_SEG (k + 1) (all entries, own entries); the pair at ctl keeps CTL_RAW / CTL_N as the sums over
+       // the segments and CTL_DENSE / CTL_OVERFLOW for the dense launches (any segment over its capacity is an overflow of the step).
+       CTL_SEG = 16 };
 enum { FLAG_OWN = 1, FLAG_PARTNER = 2 };
+constexpr int SEG_SHIFT = 28, SEG_CAP_MASK = (1 << SEG_SHIFT) - 1;      // capacity argument = entries per segment + (segments << 28)
+
+// cumulative index j over the segments' counts c[0 .. n_seg) -> (segment, index inside it); false past the last one
+__device__ __forceinline__ bool seg_locate(const int (&c)[4], int n_seg, int j, int& k, int& i)
+{
+    k = 0; i = j;
+    int lim = c[0];
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+        if (k == s && s + 1 < n_seg && i >= c[s]) { i -= c[s]; k = s + 1; lim = c[s + 1]; }
+    return i < lim;
+}
+__device__ __forceinline__ void seg_counts(const int* ctl, int n_seg, int field, int (&c)[4])
+{
+#pragma unroll
+    for (int s = 0; s < 4; ++s) c[s] = s < n_seg ? ctl[CTL_SEG * (s + 1) + field] : 0;
+}
 
 struct Levels {
     int n, B;
@@ -89,6 +113,16 @@ __device__ __forceinline__ void flag_pixel(const CandArgs& a, int m, int bit)
     const int old = atomicOr(a.flags + m, bit);
     if (old == 0) atomicAdd(a.ctl + CTL_RAW, 1);
     if (bit == FLAG_OWN && !(old & FLAG_OWN)) atomicAdd(a.ctl + CTL_OWN + CTL_RAW, 1);
+}
+
+// shapes form: a flag holds one own bit (1 << k) and one partner bit (16 << k) per kernel shape; the first thread to set either bit of shape k counts
+// the entry (pixel, k) in segment k's block, the first to set the own bit counts an own entry
+__device__ __forceinline__ void flag_entry(const CandArgs& a, int m, int k, bool own)
+{
+    const int old = atomicOr(a.flags + m, (own ? 1 : 16) << k);
+    int* c = a.ctl + CTL_SEG * (k + 1);
+    if (!(old & (17 << k))) atomicAdd(c + CTL_RAW, 1);
+    if (own && !(old & (1 << k))) atomicAdd(c + CTL_OWN + CTL_RAW, 1);
 }
 
 // CAND_PX pixels per workgroup; the class logits of their K priors (one per kernel shape) are copied coalesced into LDS (rows of an odd stride), then
@@ -145,11 +179,21 @@ __global__ __launch_bounds__(256) void head_candidates_kernel(const CandArgs a, 
     const unsigned kept = kept_s[threadIdx.x];
     if (!kept) return;
     const int m = m0 + threadIdx.x;
-    if (a.split) flag_pixel(a, m, FLAG_OWN);
-    else list_pixel(a, m);
     int l, b, y, x;
     decode_pixel(a.L, m, l, b, y, x);
     const int hw = a.L.h[l] * a.L.w[l], pix = y * a.L.w[l] + x;
+    if (a.split == 2) {
+        // entries: the kept prior's own (pixel, shape), and the (pixel, shape) whose centerness lands in the prior's row
+        for (int kk = 0; kk < a.K; ++kk)
+            if (kept >> kk & 1) {
+                const int r = pix * a.K + kk;
+                flag_entry(a, m, kk, true);
+                flag_entry(a, a.L.start[l] + b * hw + r % hw, r / hw, false);
+            }
+        return;
+    }
+    if (a.split) flag_pixel(a, m, FLAG_OWN);
+    else list_pixel(a, m);
     for (int kk = 0; kk < a.K; ++kk)
         if (kept >> kk & 1) {
             const int pm = a.L.start[l] + b * hw + (pix * a.K + kk) % hw;
@@ -197,6 +241,60 @@ __global__ __launch_bounds__(256) void head_list_kernel(const int* flags, int* c
     if (i < n && i < capacity) list[i] = m;
 }
 
+// Shapes form: thread o = 0 / 1 writes the blocks over all / over the own entries -- segment k's at ctl + CTL_SEG (k + 1) + o CTL_OWN, gates in pixels
+// of shape k's window of a patch map (px_a / px_b: one 8-bit pixel count per segment), and at ctl + o CTL_OWN the sums over the segments, which no
+// launch reads but the dense launches' gate.  One segment over its capacity empties every segment.
+__global__ void head_control_segs_kernel(int* ctl, int K, int capacity, int n_pixels, int px_a, int px_b)
+{
+    const int o = threadIdx.x;
+    if (blockIdx.x || o >= 2) return;
+    bool over = false;
+    for (int k = 0; k < K; ++k) over = over || ctl[CTL_SEG * (k + 1) + CTL_RAW] > capacity;
+    int sum[CTL_INTS] = {0, 0, 0, 0, 0, over ? n_pixels : 0, over ? 1 : 0, 0};
+    for (int k = 0; k < K; ++k) {
+        int* c = ctl + CTL_SEG * (k + 1) + o * CTL_OWN;
+        const int raw = c[CTL_RAW], n = over ? 0 : raw;
+        const int fill = min(capacity, (n + 255) & ~255);
+        c[CTL_N] = n;
+        c[CTL_FILL] = fill;
+        c[CTL_GATE_A] = fill * (px_a >> 8 * k & 255);
+        c[CTL_GATE_B] = fill * (px_b >> 8 * k & 255);
+        c[CTL_DENSE] = sum[CTL_DENSE];
+        c[CTL_OVERFLOW] = sum[CTL_OVERFLOW];
+        c[CTL_GATE_POS] = n;
+        sum[CTL_RAW] += raw; sum[CTL_N] += n; sum[CTL_FILL] += fill; sum[CTL_GATE_A] += c[CTL_GATE_A]; sum[CTL_GATE_B] += c[CTL_GATE_B];
+        sum[CTL_GATE_POS] += n;
+    }
+#pragma unroll
+    for (int i = 0; i < CTL_INTS; ++i) ctl[o * CTL_OWN + i] = sum[i];
+}
+
+// Shapes form, after head_control_segs_kernel: head_list_kernel per segment -- cursors[2 k] / [2 k + 1] are segment k's own / partner-only cursors;
+// a pixel with several needed shapes is listed in several segments.
+__global__ __launch_bounds__(256) void head_list_segs_kernel(const int* flags, int* cursors, int n_pixels, int K, int capacity, int* list, const int* ctl)
+{
+    __shared__ int cnt_s[8], base_s[8];
+    if (threadIdx.x < 8) cnt_s[threadIdx.x] = 0;
+    __syncthreads();
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    const int f = m < n_pixels ? flags[m] : 0;
+    int rank[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < K && (f & (17 << k))) rank[k] = atomicAdd(&cnt_s[2 * k + ((f >> k & 1) ? 0 : 1)], 1);
+    __syncthreads();
+    if ((int)threadIdx.x < 2 * K) base_s[threadIdx.x] = cnt_s[threadIdx.x] ? atomicAdd(cursors + threadIdx.x, cnt_s[threadIdx.x]) : 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < K && (f & (17 << k))) {
+            const int* c = ctl + CTL_SEG * (k + 1);
+            const int n = c[CTL_N], part = (f >> k & 1) ? 0 : 1;
+            const int i = (part ? c[CTL_OWN + CTL_N] : 0) + base_s[2 * k + part] + rank[k];
+            if (i < n && i < capacity) list[(int64_t)k * capacity + i] = m;
+        }
+}
+
 struct GatherArgs {
     const uint8_t* src;    // planes [P][slabs][src_np][32] of 2-byte elements
     uint8_t* dst;          // planes [P][slabs][capacity * S * S][32]
@@ -205,29 +303,37 @@ struct GatherArgs {
     int S;                 // side of the patches written
     const int* list;
     const int* ctl;
+    int segs, seg_cap;     // shapes form: that many segments of seg_cap patches, each with its own counts (0: one list under ctl)
     Levels L;
 };
 
 // One wave per patch pixel and 16 (plane, slab) rows: lane = (row of the 16, 16-byte chunk).  Persistent grid over the patch pixels of the
-// CTL_FILL patches this step covers.
+// CTL_FILL patches this step covers (shapes form: of every segment's CTL_FILL patches, patch i of segment k at slot k seg_cap + i).
 __global__ __launch_bounds__(256) void head_patch_gather_kernel(const GatherArgs a)
 {
-    const int n = a.ctl[CTL_N], fill = a.ctl[CTL_FILL];
+    int fills[4] = {a.ctl[CTL_FILL], 0, 0, 0};
+    if (a.segs) seg_counts(a.ctl, a.segs, CTL_FILL, fills);
+    const int fill = fills[0] + fills[1] + fills[2] + fills[3];
     const int SS = a.S * a.S, half = a.S >> 1;
     const int row_groups = (a.rows + 15) >> 4;
     const int64_t units = (int64_t)fill * SS * row_groups;
     const int lane = threadIdx.x & 63;
     const int sub_row = lane >> 2, chunk = lane & 3;
     for (int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < units; u += (int64_t)gridDim.x * 4) {
-        const int64_t pp = u / row_groups;                 // patch pixel
+        int64_t pp = u / row_groups;                       // patch pixel
         const int rg = (int)(u - pp * row_groups);
-        const int i = (int)(pp / SS), q = (int)(pp - (int64_t)i * SS);
+        int i = (int)(pp / SS), k = 0;
+        const int q = (int)(pp - (int64_t)i * SS);
+        if (a.segs) seg_locate(fills, a.segs, i, k, i);
+        const int n = a.ctl[(a.segs ? CTL_SEG * (k + 1) : 0) + CTL_N];
+        const int slot = k * a.seg_cap + i;
+        pp = (int64_t)slot * SS + q;
         const int row = rg * 16 + sub_row;
         if (row >= a.rows) continue;
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
         if (i < n) {
             int l, b, y, x;
-            decode_pixel(a.L, a.list[i], l, b, y, x);
+            decode_pixel(a.L, a.list[slot], l, b, y, x);
             const int dy = q / a.S - half, dx = q - (q / a.S) * a.S - half;
             const int yy = y + dy, xx = x + dx;
             if ((unsigned)yy < (unsigned)a.L.h[l] && (unsigned)xx < (unsigned)a.L.w[l]) {
@@ -241,11 +347,16 @@ __global__ __launch_bounds__(256) void head_patch_gather_kernel(const GatherArgs
 
 // In place: the patch pixels of the first CTL_N patches that lie outside their level's map become zero.  One workgroup per patch at a time; a
 // patch that lies inside the map (nearly all of them on the fine levels) is left after the test.
-__global__ __launch_bounds__(256) void head_patch_mask_kernel(uint8_t* planes, int rows, int64_t np, int S, const int* list, const int* ctl, const Levels L)
+__global__ __launch_bounds__(256) void head_patch_mask_kernel(uint8_t* planes, int rows, int64_t np, int S, const int* list, const int* ctl, const Levels L,
+                                                              int segs, int seg_cap)
 {
-    const int n = ctl[CTL_N];
+    int ns[4] = {ctl[CTL_N], 0, 0, 0};
+    if (segs) seg_counts(ctl, segs, CTL_N, ns);
+    const int n = ns[0] + ns[1] + ns[2] + ns[3];
     const int SS = S * S, half = S >> 1;
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    for (int j = blockIdx.x; j < n; j += gridDim.x) {
+        int i = j, k = 0;
+        if (segs) { seg_locate(ns, segs, j, k, i); i += k * seg_cap; }      // (shapes form: the patch's slot)
         int l, b, y, x;
         decode_pixel(L, list[i], l, b, y, x);
         if (y - half >= 0 && y + half < L.h[l] && x - half >= 0 && x + half < L.w[l]) continue;
@@ -273,6 +384,7 @@ struct AsmArgs {
     const int* ctl;
     int capacity;
     int split;                 // list entries from ctl[CTL_OWN + CTL_N] on are partner-only positions: centerness and loc only
+    int segs;                  // shapes form: K segments of `capacity` (pixel, shape) entries (0: a list of pixels)
 };
 
 // the tail of head_assemble_kernel (mask_ops.hip) for one (image, prior) row, 16 lanes per row: same expressions, same summation order
@@ -341,12 +453,21 @@ __global__ __launch_bounds__(256) void head_assemble_rows_kernel(const AsmArgs a
 __global__ __launch_bounds__(256) void head_assemble_listed_kernel(const AsmArgs a)
 {
     const int n_pos = a.ctl[CTL_N];
-    const int n_own = a.split ? a.ctl[CTL_OWN + CTL_N] : n_pos;
+    int n_own = a.split ? a.ctl[CTL_OWN + CTL_N] : n_pos;
     const int sub = threadIdx.x & 15;
-    const int64_t units = (int64_t)n_pos * a.K;
+    // shapes form: one unit per entry -- entry i of segment k is kernel shape k at pixel list[k capacity + i], row i of small[k] / trk[k]
+    int ns[4] = {0, 0, 0, 0};
+    if (a.segs) seg_counts(a.ctl, a.segs, CTL_N, ns);
+    const int64_t units = a.segs ? n_pos : (int64_t)n_pos * a.K;
     for (int64_t u = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); u < units; u += (int64_t)gridDim.x * 16) {
-        const int i = (int)(u / a.K), k = (int)(u - (int64_t)i * a.K);
-        const int m = a.list[i];
+        int i = (int)(u / a.K), k = (int)(u - (int64_t)i * a.K);
+        int slot = i;
+        if (a.segs) {
+            seg_locate(ns, a.segs, (int)u, k, i);
+            n_own = a.ctl[CTL_SEG * (k + 1) + CTL_OWN + CTL_N];
+            slot = k * a.capacity + i;
+        }
+        const int m = a.list[slot];
         int l = 0;
 #pragma unroll
         for (int j = 1; j < 8; ++j)
@@ -396,18 +517,29 @@ extern "C" int stm_head_candidates_f32(const float* const* cls_logits, int K, in
     STM_REQUIRE(fill_levels(a.L, n_levels, B, lvl_start, lvl_h, lvl_w), STM_EINVAL, "%s: bad level table", who);
     const int n_pixels = a.L.start[n_levels];
     // a negative capacity selects the split form: |capacity| positions, own positions in front, 16 control ints, n_pixels + 2 flag ints
-    const int split = capacity < 0;
+    int split = capacity < 0;
     STM_REQUIRE(capacity != INT_MIN, STM_EINVAL, "%s: bad sizes", who);
     if (split) capacity = -capacity;
+    // ... and K << 28 added to it the shapes form: (pixel, shape) entries in K segments of that many each, 16 (K + 1) control ints, n_pixels + 2 K flag ints
+    const int segs = capacity >> SEG_SHIFT;
+    if (segs) {
+        STM_REQUIRE(split && segs == K && K <= 3, STM_EINVAL, "%s: the shapes form takes a negative capacity with K << 28 added, K <= 3", who);
+        capacity &= SEG_CAP_MASK;
+        split = 2;
+        // (patch_pixels_a / _b: segment k's pixel count in bits [8 k, 8 k + 8) -- the pixels of shape k's window of the two tower layers)
+        for (int k = 0; k < K; ++k)
+            STM_REQUIRE((patch_pixels_a >> 8 * k & 255) > 0 && (patch_pixels_b >> 8 * k & 255) > 0, STM_EINVAL, "%s: segment %d has no patch pixels", who, k);
+        STM_REQUIRE((int64_t)capacity * 255 < ((int64_t)1 << 30), STM_EINVAL, "%s: bad sizes", who);
+    }
     STM_REQUIRE(K > 0 && K <= 4 && n_cls >= 2 && ld >= n_cls && n_pixels > 0 && capacity > 0 && patch_pixels_a > 0 && patch_pixels_b > 0 &&
-                    (int64_t)capacity * std::max(patch_pixels_a, patch_pixels_b) < ((int64_t)1 << 30), STM_EINVAL, "%s: bad sizes", who);
+                    (segs || (int64_t)capacity * std::max(patch_pixels_a, patch_pixels_b) < ((int64_t)1 << 30)), STM_EINVAL, "%s: bad sizes", who);
     for (int k = 0; k < 4; ++k) {
         a.cls[k] = k < K ? cls_logits[k] : nullptr;
         STM_REQUIRE(k >= K || a.cls[k], STM_ENULL, "%s: input %d is NULL", who, k);
     }
     a.K = K; a.ld = ld; a.n_cls = n_cls; a.n_pixels = n_pixels; a.capacity = capacity; a.thresh = conf_thresh; a.list = list; a.ctl = ctl;
     a.flags = flags; a.split = split;
-    const int n_flags = n_pixels + (split ? 2 : 0), n_ctl = split ? 2 * CTL_INTS : CTL_INTS;
+    const int n_flags = n_pixels + (segs ? 2 * K : split ? 2 : 0), n_ctl = segs ? CTL_SEG * (K + 1) : split ? 2 * CTL_INTS : CTL_INTS;
     // (cleared by a kernel, not by memset nodes: the launches are captured into a graph that is replayed many times)
     hipLaunchKernelGGL(head_clear_kernel, dim3(stm_cdiv(n_flags + n_ctl, 256)), dim3(256), 0, stm_hs(stream), ctl, flags, n_flags, n_ctl);
     STM_CHECK_LAUNCH("head_clear_kernel");
@@ -417,6 +549,13 @@ extern "C" int stm_head_candidates_f32(const float* const* cls_logits, int K, in
     STM_REQUIRE(lds <= 48 * 1024, STM_EUNSUPPORTED, "%s: %d classes x %d shapes do not fit the staging buffer", who, n_cls, K);
     hipLaunchKernelGGL(head_candidates_kernel, dim3(stm_cdiv(n_pixels, CAND_PX)), dim3(256), lds, stm_hs(stream), a, vec);
     STM_CHECK_LAUNCH("head_candidates_kernel");
+    if (segs) {
+        hipLaunchKernelGGL(head_control_segs_kernel, dim3(1), dim3(64), 0, stm_hs(stream), ctl, K, capacity, n_pixels, patch_pixels_a, patch_pixels_b);
+        STM_CHECK_LAUNCH("head_control_segs_kernel");
+        hipLaunchKernelGGL(head_list_segs_kernel, dim3(stm_cdiv(n_pixels, 256)), dim3(256), 0, stm_hs(stream), flags, flags + n_pixels, n_pixels, K, capacity, list, ctl);
+        STM_CHECK_LAUNCH("head_list_segs_kernel");
+        return STM_OK;
+    }
     hipLaunchKernelGGL(head_control_kernel, dim3(1), dim3(64), 0, stm_hs(stream), ctl, capacity, n_pixels, patch_pixels_a, patch_pixels_b,
                        split ? 2 : 1);
     STM_CHECK_LAUNCH("head_control_kernel");
@@ -433,6 +572,11 @@ extern "C" int stm_head_patch_gather(const void* src_planes, long long src_np, v
 {
     const char* who = "stm_head_patch_gather";
     STM_REQUIRE(src_planes && dst_planes && list && ctl, STM_ENULL, "%s: NULL argument", who);
+    // (shapes form: segments << 28 added to the capacity, which then counts the patches of ONE segment)
+    const int segs = capacity > 0 ? capacity >> SEG_SHIFT : 0;
+    STM_REQUIRE(segs <= 4, STM_EINVAL, "%s: at most 4 segments", who);
+    const int seg_cap = capacity & SEG_CAP_MASK;
+    if (segs) capacity = segs * seg_cap;
     STM_REQUIRE(n_planes > 0 && slabs > 0 && capacity > 0 && side > 0 && (side & 1) && src_np > 0 &&
                     (uintptr_t)src_planes % 16 == 0 && (uintptr_t)dst_planes % 16 == 0, STM_EINVAL, "%s: bad sizes or alignment", who);
     GatherArgs a;
@@ -440,7 +584,7 @@ extern "C" int stm_head_patch_gather(const void* src_planes, long long src_np, v
     STM_REQUIRE(src_np >= a.L.start[n_levels], STM_EINVAL, "%s: the source planes hold fewer pixels than the levels", who);
     a.src = static_cast<const uint8_t*>(src_planes); a.dst = static_cast<uint8_t*>(dst_planes);
     a.rows = n_planes * slabs; a.src_np = src_np; a.dst_np = (int64_t)capacity * side * side; a.S = side;
-    a.list = list; a.ctl = ctl;
+    a.list = list; a.ctl = ctl; a.segs = segs; a.seg_cap = seg_cap;
     const int64_t units = (int64_t)capacity * side * side * ((a.rows + 15) / 16);
     const unsigned grid = (unsigned)std::min<int64_t>((units + 3) / 4, 16384);
     hipLaunchKernelGGL(head_patch_gather_kernel, dim3(grid), dim3(256), 0, stm_hs(stream), a);
@@ -453,11 +597,15 @@ extern "C" int stm_head_patch_mask(void* planes, int side, int n_planes, int sla
 {
     const char* who = "stm_head_patch_mask";
     STM_REQUIRE(planes && list && ctl, STM_ENULL, "%s: NULL argument", who);
+    const int segs = capacity > 0 ? capacity >> SEG_SHIFT : 0;      // (shapes form, as stm_head_patch_gather)
+    STM_REQUIRE(segs <= 4, STM_EINVAL, "%s: at most 4 segments", who);
+    const int seg_cap = capacity & SEG_CAP_MASK;
+    if (segs) capacity = segs * seg_cap;
     STM_REQUIRE(n_planes > 0 && slabs > 0 && capacity > 0 && side > 0 && (side & 1) && (uintptr_t)planes % 16 == 0, STM_EINVAL, "%s: bad sizes or alignment", who);
     Levels L;
     STM_REQUIRE(fill_levels(L, n_levels, B, lvl_start, lvl_h, lvl_w), STM_EINVAL, "%s: bad level table", who);
     hipLaunchKernelGGL(head_patch_mask_kernel, dim3(std::min(capacity, 2048)), dim3(256), 0, stm_hs(stream), static_cast<uint8_t*>(planes), n_planes * slabs,
-                       (int64_t)capacity * side * side, side, list, ctl, L);
+                       (int64_t)capacity * side * side, side, list, ctl, L, segs, seg_cap);
     STM_CHECK_LAUNCH("head_patch_mask_kernel");
     return STM_OK;
 }
@@ -480,6 +628,11 @@ extern "C" int stm_head_assemble_sparse_f32(const float* const* cls_logits, int 
     // (a negative capacity: the split form of stm_head_candidates_f32 -- ordered list, 16 control ints)
     a.split = capacity < 0;
     if (a.split) capacity = -capacity;
+    // (... with K << 28 added: the shapes form -- small[k] / trk[k] hold one row per entry of segment k)
+    a.segs = capacity >> SEG_SHIFT;
+    STM_REQUIRE(!a.segs || (a.split && a.segs == L->K), STM_EINVAL, "%s: the shapes form takes a negative capacity with K << 28 added", who);
+    capacity &= SEG_CAP_MASK;
+    STM_REQUIRE(capacity > 0, STM_EINVAL, "%s: bad capacity", who);
     a.row_mul = row_mul; a.row_add = row_add; a.list = list; a.ctl = ctl; a.capacity = capacity;
     int off = 0, start = 0;
     for (int l = 0; l < 8; ++l) {

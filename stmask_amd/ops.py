@@ -1965,6 +1965,17 @@ def head_assemble(small, trk, B, sizes, n_cls, mask_dim, embed_dim, group_pad):
 HEAD_CTL_RAW, HEAD_CTL_N, HEAD_CTL_FILL, HEAD_CTL_GATE_A, HEAD_CTL_GATE_B, HEAD_CTL_DENSE, HEAD_CTL_OVERFLOW, HEAD_CTL_INTS = 0, 1, 2, 3, 4, 5, 6, 8
 HEAD_CTL_GATE_POS = 7
 HEAD_CTL_OWN = 8      # split form: first int of the second block, the same fields over the positions with a kept prior of their own
+# shapes form: segment k (the entries of kernel shape k) has its pair of blocks at HEAD_CTL_SEG * (k + 1); at the entry points the capacity counts
+# the entries of ONE segment and carries the number of segments from bit 28 on
+HEAD_CTL_SEG = 16
+HEAD_SEG_SHIFT = 28
+
+
+def head_seg_capacity(capacity, segs):
+    """The capacity argument of the stm_head_* entry points: entries per segment + (segments << 28) in the shapes form, else the capacity."""
+    if segs and not 0 < capacity < (1 << HEAD_SEG_SHIFT):
+        raise StmError(f"sparse head: a segment of {capacity} entries")
+    return capacity + (segs << HEAD_SEG_SHIFT) if segs else capacity
 
 
 def conv_set_pixel_gate(ctl, index):
@@ -1999,11 +2010,21 @@ def _ptr4(ts):
     return (ctypes.c_void_p * 4)(*([t.data_ptr() for t in ts] + [0] * (4 - len(ts))))
 
 
-def head_candidates(cls_logits, n_cls, conf_thresh, capacity, patch_pixels_a, patch_pixels_b, B, sizes, split=False):
+def head_candidates(cls_logits, n_cls, conf_thresh, capacity, patch_pixels_a, patch_pixels_b, B, sizes, split=False, shapes=False):
     """stm_head_candidates_f32: cls_logits = per-kernel-shape [pixels, ld] fp32 class logits over the concatenated levels -> (list int32 [capacity] of
     the pixels whose rows the detection stage reads for the priors that pass generate_candidate's test, control block int32 [8]: see
     include/stmask_hip.h).  split: the pixels with a kept prior of their own in front, list[:ctl[HEAD_CTL_OWN + HEAD_CTL_N]], the pixels that are
-    only another prior's centerness partner behind them; control block int32 [16], the second block over the own positions."""
+    only another prior's centerness partner behind them; control block int32 [16], the second block over the own positions.
+    shapes (with split): (pixel, kernel shape) entries instead of pixels -- list int32 [K * capacity], segment k = the entries of shape k, each
+    ordered as the split list; control block int32 [16 (K + 1)], segment k's pair of blocks at HEAD_CTL_SEG * (k + 1)."""
+    if shapes and not split:
+        raise StmError("head_candidates: the shapes form is a form of the split form")
+    if shapes:      # patch_pixels_a / _b: one pixel count per kernel shape (its window of the two tower layers), packed 8 bits each
+        if len(patch_pixels_a) != len(cls_logits) or len(patch_pixels_b) != len(cls_logits) or not all(0 < v < 256 for v in list(patch_pixels_a) + list(patch_pixels_b)):
+            raise StmError("head_candidates: the shapes form takes one patch pixel count per kernel shape")
+        patch_pixels_a = sum(v << 8 * k for k, v in enumerate(patch_pixels_a))
+        patch_pixels_b = sum(v << 8 * k for k, v in enumerate(patch_pixels_b))
+    segs = len(cls_logits) if shapes else 0
     _dev(*cls_logits)
     n_px, ld = cls_logits[0].shape
     n, st, hh, ww, total = _level_arrays(B, sizes)
@@ -2011,43 +2032,47 @@ def head_candidates(cls_logits, n_cls, conf_thresh, capacity, patch_pixels_a, pa
         if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (n_px, ld) or n_px != total:
             raise StmError("head_candidates: inputs must be contiguous fp32 matrices over all level pixels")
     dev = cls_logits[0].device
-    lst = torch.empty(capacity, dtype=torch.int32, device=dev)
-    ctl = torch.empty(HEAD_CTL_INTS * (2 if split else 1), dtype=torch.int32, device=dev)
-    flags = torch.empty(n_px + (2 if split else 0), dtype=torch.int32, device=dev)
-    call("stm_head_candidates_f32", _ptr4(cls_logits), len(cls_logits), ld, n_cls, conf_thresh, -capacity if split else capacity, patch_pixels_a, patch_pixels_b, n, B, st,
+    lst = torch.empty(capacity * max(segs, 1), dtype=torch.int32, device=dev)
+    ctl = torch.empty(HEAD_CTL_SEG * (segs + 1) if segs else HEAD_CTL_INTS * (2 if split else 1), dtype=torch.int32, device=dev)
+    flags = torch.empty(n_px + (2 * segs if segs else 2 if split else 0), dtype=torch.int32, device=dev)
+    cap_arg = head_seg_capacity(capacity, segs)
+    call("stm_head_candidates_f32", _ptr4(cls_logits), len(cls_logits), ld, n_cls, conf_thresh, -cap_arg if split else cap_arg, patch_pixels_a, patch_pixels_b, n, B, st,
          hh, ww, _p(flags), _p(lst), _p(ctl), _stream())
     return lst, ctl
 
 
-def head_patch_gather(src, dst, side, capacity, B, sizes, lst, ctl):
-    """stm_head_patch_gather: side x side neighbourhoods of the listed pixels from the level maps (zeros outside a map), planes [P, S, pixels, 32] in and [P, S, capacity * side^2, 32] out."""
+def head_patch_gather(src, dst, side, capacity, B, sizes, lst, ctl, segs=0):
+    """stm_head_patch_gather: side x side neighbourhoods of the listed pixels from the level maps (zeros outside a map), planes [P, S, pixels, 32] in and [P, S, capacity * side^2, 32] out.
+    segs (shapes form): that many segments of `capacity` patches each, patch i of segment k at slot k * capacity + i."""
     _dev(src, dst)
     if (src.dim() != 4 or dst.dim() != 4 or src.shape[3] != 32 or src.element_size() != 2 or dst.dtype != src.dtype or not src.is_contiguous()
-            or not dst.is_contiguous() or tuple(dst.shape) != (src.shape[0], src.shape[1], capacity * side * side, 32)):
+            or not dst.is_contiguous() or tuple(dst.shape) != (src.shape[0], src.shape[1], max(segs, 1) * capacity * side * side, 32)):
         raise StmError(f"head_patch_gather: planes {tuple(src.shape)} -> {tuple(dst.shape)} do not fit capacity {capacity}, side {side}")
     n, st, hh, ww, _ = _level_arrays(B, sizes)
-    call("stm_head_patch_gather", _p(src), src.shape[2], _p(dst), side, src.shape[0], src.shape[1], capacity, n, B, st, hh, ww, _p(lst), _p(ctl),
+    call("stm_head_patch_gather", _p(src), src.shape[2], _p(dst), side, src.shape[0], src.shape[1], head_seg_capacity(capacity, segs), n, B, st, hh, ww, _p(lst), _p(ctl),
          _stream())
     return dst
 
 
-def head_patch_mask(planes, side, capacity, B, sizes, lst, ctl):
-    """stm_head_patch_mask: zero, in place, the pixels of the listed patches that lie outside their level's map."""
+def head_patch_mask(planes, side, capacity, B, sizes, lst, ctl, segs=0):
+    """stm_head_patch_mask: zero, in place, the pixels of the listed patches that lie outside their level's map (segs: as head_patch_gather)."""
     _dev(planes)
-    if planes.dim() != 4 or planes.shape[3] != 32 or planes.element_size() != 2 or not planes.is_contiguous() or planes.shape[2] != capacity * side * side:
+    if planes.dim() != 4 or planes.shape[3] != 32 or planes.element_size() != 2 or not planes.is_contiguous() or planes.shape[2] != max(segs, 1) * capacity * side * side:
         raise StmError(f"head_patch_mask: planes {tuple(planes.shape)} do not fit capacity {capacity}, side {side}")
     n, st, hh, ww, _ = _level_arrays(B, sizes)
-    call("stm_head_patch_mask", _p(planes), side, planes.shape[0], planes.shape[1], capacity, n, B, st, hh, ww, _p(lst), _p(ctl), _stream())
+    call("stm_head_patch_mask", _p(planes), side, planes.shape[0], planes.shape[1], head_seg_capacity(capacity, segs), n, B, st, hh, ww, _p(lst), _p(ctl), _stream())
     return planes
 
 
 def head_assemble_sparse(cls_logits, small, trk, small_dense, trk_dense, B, sizes, n_cls, mask_dim, embed_dim, group_pad, row_mul, row_add, lst, ctl,
-                         capacity, split=False):
+                         capacity, split=False, shapes=False):
     """stm_head_assemble_sparse_f32 -> (conf, loc, mask, track, centerness) as head_assemble; loc / mask / track / centerness hold values at the
     rows of the listed pixels only (every row after an overflow), the other rows are NOT written.  split (list and ctl from
-    head_candidates(split=True)): mask / track at the rows of the own positions only, and their matrices are not read for the others."""
-    if ctl.numel() < HEAD_CTL_INTS * (2 if split else 1):
-        raise StmError("head_assemble_sparse: the split form reads a control block of 16 ints")
+    head_candidates(split=True)): mask / track at the rows of the own positions only, and their matrices are not read for the others.
+    shapes (list and ctl from head_candidates(shapes=True)): small[k] / trk[k] hold one row per entry of segment k, `capacity` of them."""
+    segs = len(cls_logits) if shapes else 0
+    if ctl.numel() < (HEAD_CTL_SEG * (segs + 1) if segs else HEAD_CTL_INTS * (2 if split else 1)) or (shapes and not split):
+        raise StmError("head_assemble_sparse: the split form reads a control block of 16 ints, the shapes form one of 16 (K + 1)")
     _dev(*cls_logits, *small, *trk, *small_dense, *trk_dense)
     K = len(cls_logits)
     L, start = _head_layout(B, K, sizes, n_cls, mask_dim, embed_dim, group_pad, small[0].shape[-1], trk[0].shape[-1])
@@ -2065,7 +2090,7 @@ def head_assemble_sparse(cls_logits, small, trk, small_dense, trk_dense, B, size
     track = torch.empty(B, N, embed_dim, device=dev)
     cen = torch.empty(B, N, 1, device=dev)
     call("stm_head_assemble_sparse_f32", _ptr4(cls_logits), cls_logits[0].shape[-1], _ptr4(small), _ptr4(trk), _ptr4(small_dense), _ptr4(trk_dense),
-         ctypes.byref(L), row_mul, row_add, _p(lst), _p(ctl), -capacity if split else capacity, _p(conf), _p(loc), _p(mask), _p(track), _p(cen), _stream())
+         ctypes.byref(L), row_mul, row_add, _p(lst), _p(ctl), -head_seg_capacity(capacity, segs) if split else capacity, _p(conf), _p(loc), _p(mask), _p(track), _p(cen), _stream())
     return conf, loc, mask, track, cen
 
 

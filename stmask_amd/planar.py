@@ -307,6 +307,41 @@ class PlanarConv:
             return out_f32, out_planes
         return out_f32 if out == "f32" else out_planes
 
+    def window_segments(self, xp, B, H, W, windows, out_planes, out_hw, gate, x_ch_off=0, out_slab_off=0):
+        """This layer as a GATED window set (stm_conv2d_planar_windows_f32 after ops.conv_set_pixel_gate; fp16x2 planes, 256 x 128 tiles): the B
+        images of H x W in xp are len(windows) equal segments, segment i gets window i = (ho, wo, y0, x0) of its out_hw x out_hw VALID
+        convolution only, and gate = (ctl, index) -> ctl[index + 16 i] output pixels of window i are computed.  One grid; per output pixel the
+        products of the single gated window launch in the same order.  Writes the layer's channels from slab out_slab_off of out_planes."""
+        if self.fmt != 1 or self.out_fmt != 1 or (self.sh, self.sw) != (1, 1):
+            raise StmError("PlanarConv.window_segments: fp16x2 planes and stride 1 only")
+        S, N = xp.shape[1], xp.shape[2]
+        n = len(windows)
+        if xp.dim() != 4 or not xp.is_contiguous() or B % n or B * H * W > N or x_ch_off % 32 or S * 32 < x_ch_off + self.groups * self.C:
+            raise StmError(f"PlanarConv.window_segments: {B} images of {H}x{W} in {n} segments do not fit planes {tuple(xp.shape)}")
+        if (out_planes.shape[2] < B * out_hw * out_hw or out_slab_off < 0 or out_slab_off + self.O // 32 > out_planes.shape[1] or self.O % 128
+                or (H - self.kh + 1, W - self.kw + 1) != (out_hw, out_hw)):
+            raise StmError("PlanarConv.window_segments: the output planes do not hold the layer's valid convolution")
+        packed = self.packed(128)
+        g = _lib.ConvGeom()
+        g.B, g.H, g.W, g.C, g.Cout, g.sh, g.sw, g.planes, g.fmt, g.tile_n = B, H, W, self.C, self.O, 1, 1, 2, 1, 128
+        g.groups, g.win_h, g.win_w, g.out_scale = self.groups, out_hw, out_hw, self.out_scale
+        g.x_np, g.x_plane_stride = N, S * N * 32
+        g.out_np, g.out_plane_stride = out_planes.shape[2], out_planes.shape[1] * out_planes.shape[2] * 32
+        wins = (_lib.ConvWindow * n)()
+        for i, (ho, wo, y0, x0) in enumerate(windows):
+            wins[i].kh, wins[i].kw, wins[i].ph, wins[i].pw, wins[i].Ho, wins[i].Wo, wins[i].y0, wins[i].x0 = self.kh, self.kw, -y0, -x0, ho, wo, y0, x0
+        g.kh, g.kw, g.Ho, g.Wo = self.kh, self.kw, windows[0][0], windows[0][1]
+        ptrs = (ctypes.c_void_p * n)(*[packed.data_ptr()] * n)
+        started = _timing_start()
+        ops.conv_set_pixel_gate(*gate)
+        call("stm_conv2d_planar_windows_f32", xp.data_ptr() + (x_ch_off // 32) * N * 64, ptrs, wins, n, ops._p(self.bias), None,
+             out_planes.data_ptr() + out_slab_off * g.out_np * 64, ctypes.byref(g), 1 if self.relu else 0, ops._stream())
+        if started is not None:
+            M = sum(B // n * ho * wo for ho, wo, _, _ in windows)
+            _timing_stop(started, 2.0 * M * self.O * self.C * self.kh * self.kw * self.algo_frac, (M, self.C, self.O, self.kh, self.sh, self.groups, 128), 3,
+                         self.role, M * (self.groups * self.C + self.O) * 4 + self.weight.numel() * 4)
+        return out_planes
+
     def deform(self, x32, B, H, W, om, stride, padding, dilation, has_mask, out=None, out_off=0):
         """This layer as a DEFORMABLE convolution in one kernel (ops.deform_conv_fused_planar, csrc/dcn_fused.hip): x32 fp32 pixel-major
         [B*H*W, C] (a channel slice of a wider tensor is fine), om fp32 [B*Ho*Wo, 2K (+K)]; the weight is this layer's own kh x kw weight
@@ -344,6 +379,14 @@ def head_split_default():
     """STM_HEAD_SPLIT (default on): the sparse head's mask and track branches only at the positions with a kept prior of their own; 0 = at every
     listed position, the centerness partners included.  The one place that reads the switch, once per process."""
     return os.environ.get("STM_HEAD_SPLIT", "1") != "0"
+
+
+@functools.lru_cache(maxsize=None)
+def head_shapes_default():
+    """STM_HEAD_SHAPES (default on): the sparse head lists (pixel, kernel shape) entries and runs the patch towers over each entry's own kernel
+    footprint only; 0 = the towers over the whole 7 x 7 / 5 x 5 maps of every listed pixel.  A form of the split form with centre-pixel output
+    layers on fp16x2 planes: with either of those off, or another plane format, the head runs as if this were 0.  Read once per process."""
+    return os.environ.get("STM_HEAD_SHAPES", "1") != "0"
 
 
 @functools.lru_cache(maxsize=None)
@@ -413,6 +456,7 @@ class PlanarGraph:
         self.sparse = None
         self._sparse_layers = self._split_layers = None
         self.sparse_ctl = self.sparse_list = None      # (tests, diagnosis: the last sparse step's counts and positions)
+        self.sparse_segments = None                    # (... shapes form: (whole control block, entry list, entries per segment))
         self._side = None                              # second stream of run()'s branches (_side_stream)
         if not self.head_planar:
             return
@@ -495,6 +539,14 @@ class PlanarGraph:
         per_frame = max(1, 2 * sum(h * w for h, w in sizes) // (s1 * s1 + s2 * s2))
         return -(-per_frame * B // 256) * 256
 
+    @staticmethod
+    def sparse_segment_capacity(cap):
+        """Entries per kernel shape of the shapes form for a capacity of `cap` positions: HALF of it (whole groups of 256 patches), for each of
+        the three segments.  The shapes are not equally frequent -- the benchmark's kept priors are all of one shape, which so holds 54 % of the
+        entries -- and one segment over its capacity sends the whole step to the dense launches; with thirds that happened at 50 kept priors
+        per frame, where the patch launches still pay.  Patch buffers of 1.5 x the position form's."""
+        return min(cap, -(-cap // (2 * 256)) * 256)
+
     def _build_sparse(self):
         """The head's layers cut into the class branch and the three other branches.  Same weights, rounded under the scale of the layer they are
         cut from, same K order: each output value is the sum the uncut layer forms."""
@@ -536,6 +588,11 @@ class PlanarGraph:
         own = ops.HEAD_CTL_OWN if split else 0
         if cap is None:
             cap = self.sparse_capacity(B, sizes)
+        # Shapes (a fifth element): a kept prior (pixel, shape k) is read at output layer k only, and so is its centerness partner -- the list
+        # holds (pixel, shape) entries, one segment per shape, and the towers run over the rectangle that shape's output layer reads at the
+        # centre: kh x kw of tower 2, (kh + 2) x (kw + 2) of tower 1.
+        if len(self.sparse) > 4 and bool(self.sparse[4]) and split and center and self.fmt == 1:
+            return self._sparse_head_shapes(up, g, toc, thresh, self.sparse_segment_capacity(cap))
         t1c, t1r, t2c, t2r, cls_l, small_l = self._build_sparse()
         trk_l = [f.trk for f in self.finals]
         lv = g.lv
@@ -608,6 +665,82 @@ class PlanarGraph:
                                        rows[0], rows[1], lst, ctl, cap, split=split)
         self.sparse_ctl, self.sparse_list = ctl, lst       # (tests, diagnosis: the step's counts and positions)
         return out
+
+    def _sparse_head_shapes(self, up, g, toc, thresh, cap):
+        """_sparse_head in the shapes form (split, centre-pixel output layers): `cap` entries per kernel shape.  Patch slot k * cap + i belongs to
+        entry i of shape k; the four tower launches are gated window sets with one window per shape (PlanarConv.window_segments), shape k's
+        output launches read segment k and are gated by its blocks."""
+        head, (B, sizes, _, ntot, dev) = self.head, g
+        _, _, _, _, cls_l, small_l = self._build_sparse()
+        t1c, t1r, t2c, t2r = self._sparse_layers[:4]
+        t1b, t1m, t2b, t2m = self._split_layers
+        trk_l = [f.trk for f in self.finals]
+        K, lv = len(self.finals), g.lv
+        cw, P = self.tower2.O // 4, self.GROUP_PAD
+        S0, S1, S2 = self.SPARSE_SIDES
+        NP, pdt = ops.plane_layout(self.fmt)
+        kx = ntot >= self.finals[0].small.kxr_rule_pixels()
+        x = t1c(up, lv, out="planes", splitk=False)
+        x = t2c(x, lv, out="planes", splitk=False)
+        cls = [c(x, lv, out="f32", splitk=False, kxr=kx) for c in cls_l]
+        toc("head_towers")
+        shp = [(c.kh, c.kw) for c in small_l]
+        if any(c.kh > S2 or c.kw > S2 or not (c.kh & c.kw & 1) or (t.kh, t.kw) != (c.kh, c.kw) for c, t in zip(small_l, trk_l)):
+            raise StmError("sparse head: an output layer's kernel does not fit the patch maps")
+        # shape k's windows: the kh x kw taps of its output layers at the centre of the 5 x 5 map, and what those read of the 7 x 7 map; a segment's
+        # pixel gates count the pixels of its windows
+        w1 = [(kh + 2, kw + 2, (S2 - kh) // 2, (S2 - kw) // 2) for kh, kw in shp]
+        w2 = [(kh, kw, (S2 - kh) // 2, (S2 - kw) // 2) for kh, kw in shp]
+        lst, ctl = ops.head_candidates(cls, head.num_classes, thresh, cap, [h * w for h, w, _, _ in w1], [h * w for h, w, _, _ in w2], B, sizes,
+                                       split=True, shapes=True)
+        tot = K * cap
+        patch = ops.head_patch_gather(up, torch.empty(NP, cw // 32, tot * S0 * S0, 32, device=dev, dtype=pdt), S0, cap, B, sizes, lst, ctl, segs=K)
+        x1 = torch.empty(NP, 3 * cw // 32, tot * S1 * S1, 32, device=dev, dtype=pdt)
+        xq = torch.empty(NP, 3 * cw // 32, tot * S2 * S2, 32, device=dev, dtype=pdt)
+        seg, own = ops.HEAD_CTL_SEG, ops.HEAD_CTL_OWN
+        t1b.window_segments(patch, tot, S0, S0, w1, x1, S1, (ctl, seg + ops.HEAD_CTL_GATE_A))
+        t1m.window_segments(patch, tot, S0, S0, w1, x1, S1, (ctl, seg + own + ops.HEAD_CTL_GATE_A), out_slab_off=cw // 32)
+        ops.head_patch_mask(x1, S1, cap, B, sizes, lst, ctl, segs=K)
+        t2b.window_segments(x1, tot, S1, S1, w2, xq, S2, (ctl, seg + ops.HEAD_CTL_GATE_B))
+        t2m.window_segments(x1, tot, S1, S1, w2, xq, S2, (ctl, seg + own + ops.HEAD_CTL_GATE_B), x_ch_off=cw, out_slab_off=cw // 32)
+        ops.head_patch_mask(xq, S2, cap, B, sizes, lst, ctl, segs=K)
+        c2 = S2 // 2
+
+        def centre(c, k, blk, **kw):
+            return c(xq, ("img", cap, S2, S2), x_off=k * cap * S2 * S2, out="f32", out_f32=torch.empty(cap, c.O, device=dev),
+                     window=(0, 0, 1, 1, c.ph - c2, c.pw - c2, 1, 1), gate=(ctl, seg * (k + 1) + blk + ops.HEAD_CTL_GATE_POS), **kw)
+
+        small = [centre(c, k, 0, kxr=kx) for k, c in enumerate(small_l)]
+        trk = [centre(c, k, own, x_ch_off=2 * cw, kxr=False) for k, c in enumerate(trk_l)]
+        gd = (ctl, ops.HEAD_CTL_DENSE)
+        x = t1r(up, lv, out="planes", gate=gd)
+        x = t2r(x, lv, out="planes", gate=gd)
+        small_d = [c(x, lv, out="f32", gate=gd, kxr=kx) for c in small_l]
+        trk_d = [c(x, lv, out="f32", x_ch_off=2 * cw, gate=gd) for c in trk_l]
+        toc("head_finals")
+        out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P,
+                                       1, 0, lst, ctl, cap, split=True, shapes=True)
+        # (tests, diagnosis: the two blocks of sums read as the split form's -- counts of entries -- and sparse_list the entries' pixels)
+        self.sparse_ctl, self.sparse_list, self.sparse_segments = ctl[:ops.HEAD_CTL_SEG], None, (ctl, lst, cap)
+        return out
+
+    @property
+    def sparse_list(self):
+        """Pixels the last sparse step listed (a host read: tests and diagnosis).  Shapes form: the pixels of all entries, own entries in front,
+        so that a pixel with several needed shapes appears once per shape."""
+        if self._sparse_list is not None or self.sparse_segments is None:
+            return self._sparse_list
+        ctl, lst, cap = self.sparse_segments
+        c, seg, own = ctl.tolist(), ops.HEAD_CTL_SEG, ops.HEAD_CTL_OWN
+        K = len(c) // seg - 1
+        n = [(c[seg * (k + 1) + own + ops.HEAD_CTL_N], c[seg * (k + 1) + ops.HEAD_CTL_N]) for k in range(K)]
+        return torch.cat([lst[k * cap:k * cap + no] for k, (no, _) in enumerate(n)] + [lst[k * cap + no:k * cap + na] for k, (no, na) in enumerate(n)])
+
+    @sparse_list.setter
+    def sparse_list(self, lst):
+        self._sparse_list = lst
+        if lst is not None:
+            self.sparse_segments = None
 
     # ------------------------------------------------------------------------------------------------------------
     def run(self, bb_outs, planes=None):

@@ -106,6 +106,9 @@ class TrunkRunner:
         # the centerness partner of a kept prior, and centerness comes out of the bbox branch.  STM_HEAD_SPLIT=0: all three branches at every
         # listed position (A/B runs); part of the setting baked into the graphs
         self.head_split = planar.head_split_default()
+        # ... and its patch towers over each entry's own kernel footprint: the list holds (pixel, kernel shape) entries, and shape k's output layers
+        # read kh x kw pixels of tower 2.  STM_HEAD_SHAPES=0: the towers over the whole maps of every listed pixel (A/B runs); part of the setting
+        self.head_shapes = planar.head_shapes_default()
         # batches from which it is on: a single-stream step is a chain of launches bound by their latency, and the sparse head has 22 more of them
         # (frames/s dense / sparse at 1 clip 812-817 / 713-733, 2 clips 1 073-1 075 / 1 058-1 064, 4 clips 1 301-1 305 / 1 321-1 324, 8 clips
         # 1 435 / 1 543: DESIGN.md section 6).  STM_SPARSE_MIN_CLIPS for A/B runs
@@ -136,7 +139,9 @@ class TrunkRunner:
             return None
         if not getattr(self.net.Detect_TF, "use_cross_class_nms", True):
             return None
-        return (float(self.cfg.eval_conf_thresh), self.sparse_capacity, self.head_center, self.head_split)
+        return (float(self.cfg.eval_conf_thresh), self.sparse_capacity, self.head_center, self.head_split,
+                # (a capacity given by the caller counts POSITIONS and keeps the list of positions; the segments of entries are sized by the default rule)
+                self.head_shapes and self.sparse_capacity is None)
 
     def _trunk(self, frames):
         pg = getattr(self.net, "_planar", None)
