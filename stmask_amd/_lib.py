@@ -173,6 +173,13 @@ TRAIN_SIGNATURES = {
     "stm_lincomb_rows_proto_backward_f32": ("i", "ppipppppiiiipzp"),
     "stm_mbox_scatter_coeff_f32": ("i", "pppppiiiipzp"),
 }
+# include/stmask_hip_eval.h, the fifth header (tests/test_abi_eval.py): video mask AP -- RLE string decode, tube IoU, greedy matching (vis_eval.py)
+EVAL_SIGNATURES = {
+    "stm_vis_rle_decode": ("i", "pppilppppp"),
+    "stm_vis_rle_check": ("i", "pppilpppp"),
+    "stm_vis_tube_iou": ("i", "pplppiipppplpppp"),
+    "stm_vis_match": ("i", "ppppiiippppipipppp"),
+}
 
 
 class StmError(RuntimeError):
@@ -244,7 +251,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback on the product path.")
         _lib = ctypes.CDLL(LIB_PATH)
-        tables = {**SIGNATURES, **OUTPUT_SIGNATURES, **TRACKER_SIGNATURES, **TRAIN_SIGNATURES}
+        tables = {**SIGNATURES, **OUTPUT_SIGNATURES, **TRACKER_SIGNATURES, **TRAIN_SIGNATURES, **EVAL_SIGNATURES}
         missing = [n for n in tables if not hasattr(_lib, n)]
         if missing:
             _lib = None

@@ -5,12 +5,17 @@ dict the reference keeps per frame; `results2json_videoseg` folds the ordered pe
 YouTube-VIS records: per object the mean score over its frames (float32 mean, as `np.array(scores).mean()` of float32
 scalars gives), the majority-vote category (`np.bincount(...).argmax()`), and the per-frame RLE list with None for frames
 the object is absent from.  Host-side bookkeeping on the all-gathered detections; no device work.
+
+`calc_metrics` (layers/eval_utils.py:109-119) and `VisEval` score such records against YouTube-VIS annotations; they live in vis_eval.py
+(the mask work of the evaluation runs on the device) and are re-exported here under the reference's names.
 """
 import itertools
 import json
 import os
 
 import numpy as np
+
+from .vis_eval import VisEval, calc_metrics  # noqa: F401  (the reference's eval_utils.calc_metrics)
 
 
 def bbox2result_with_id(preds, img_meta, classes):
