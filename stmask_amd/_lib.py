@@ -180,6 +180,11 @@ EVAL_SIGNATURES = {
     "stm_vis_tube_iou": ("i", "pplppiipppplpppp"),
     "stm_vis_match": ("i", "ppppiiippppipipppp"),
 }
+# include/stmask_hip_t2s_feat.h, the sixth header (tests/test_abi_t2s_feat.py): T2S_concat_feat of the train-mode forward and its adjoint
+T2S_FEAT_SIGNATURES = {
+    "stm_t2s_feat_forward_f32": ("i", "pppiiiiiip"),
+    "stm_t2s_feat_backward_f32": ("i", "ppppppiiiiiip"),
+}
 
 
 class StmError(RuntimeError):
@@ -251,7 +256,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback on the product path.")
         _lib = ctypes.CDLL(LIB_PATH)
-        tables = {**SIGNATURES, **OUTPUT_SIGNATURES, **TRACKER_SIGNATURES, **TRAIN_SIGNATURES, **EVAL_SIGNATURES}
+        tables = {**SIGNATURES, **OUTPUT_SIGNATURES, **TRACKER_SIGNATURES, **TRAIN_SIGNATURES, **EVAL_SIGNATURES, **T2S_FEAT_SIGNATURES}
         missing = [n for n in tables if not hasattr(_lib, n)]
         if missing:
             _lib = None

@@ -2,7 +2,8 @@
 spatial_correlation_sampler) and for the layer functions the reference's loss differentiates through -- generate_mask, decode, jaccard and
 the mask loss tail mask_bce_sum, the OHEM class-confidence loss ohem_conf_loss, the positive-prior terms box_center_loss and track_loss and
 the pieces of track_to_segment_loss: the row-prototype form of generate_mask and the two weighted reductions, and the pieces of the batched
-mask term lincomb_mask_loss: its gather, the row-prototype mask with a prototype gradient and its reduction.
+mask term lincomb_mask_loss: its gather, the row-prototype mask with a prototype gradient and its reduction; and for
+T2S_concat_feat of the train-mode forward in its fused form (csrc/t2s_feat.hip).
 
 Each Function's forward is the launch the shim makes without autograd (ops.deform_conv / roi_align / corr_patch), so values under
 autograd are bit-identical to the no-grad call.  Only inputs are saved: the deformable columns are recomputed in backward with the
@@ -146,6 +147,28 @@ class CorrelationFunction(torch.autograd.Function):
         in1, in2 = ctx.saved_tensors
         g1, g2 = ops.corr_patch_backward(grad_out.contiguous(), in1, in2, ctx.dil, need1=n1, need2=n2)
         return g1, g2, None, None
+
+
+class T2sConcatFeatFunction(torch.autograd.Function):
+    """layers.t2s_concat_feat(fused=True): the interleaved fpn / t2s maps of a batch of frame pairs -> T2S_concat_feat (csrc/t2s_feat.hip).  Saved:
+    the two inputs and the output, whose sign is the correlation channels' gate."""
+
+    @staticmethod
+    def forward(ctx, fpn, t2s, patch_size):
+        ctx.patch_size = patch_size
+        out = ops.t2s_concat_feat(fpn, t2s, patch_size)
+        ctx.save_for_backward(fpn, t2s, out)
+        return out
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_out):
+        n_fpn, n_t2s = ctx.needs_input_grad[:2]
+        if not (n_fpn or n_t2s):
+            return None, None, None
+        fpn, t2s, out = ctx.saved_tensors
+        g_fpn, g_t2s = ops.t2s_concat_feat_backward(grad_out, out, fpn, t2s, ctx.patch_size, need_fpn=n_fpn, need_t2s=n_t2s)
+        return g_fpn, g_t2s, None
 
 
 class LincombMaskFunction(torch.autograd.Function):
@@ -407,6 +430,10 @@ def roi_align(feat, rois, output_size, spatial_scale, sampling_ratio, aligned):
 
 def correlation(in1, in2, patch_size, dilation_patch):
     return CorrelationFunction.apply(in1, in2, patch_size, dilation_patch)
+
+
+def t2s_concat_feat(fpn, t2s, patch_size=11):
+    return T2sConcatFeatFunction.apply(fpn, t2s, patch_size)
 
 
 def lincomb_mask(proto, coeff, boxes=None, apply_tanh=True):

@@ -11,3 +11,4 @@ from .t2s_loss import track_to_segment_loss  # noqa: F401
 from .multibox_loss import MultiBoxLoss, lincomb_mask_loss  # noqa: F401
 from .modules import FPN, FeatureAlign, InterpolateModule, PredictionModule_FC, TemporalNet, bbox_feat_extractor, \
     correlate, make_net  # noqa: F401
+from .t2s_feat import t2s_concat_feat  # noqa: F401

@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops
+from .. import autograd, ops
 from ..config import cfg as _default_cfg
 from ..mmcv_ops import DeformConv2d, roi_align
 from .box_utils import sanitize_coordinates_hw
@@ -95,12 +95,16 @@ class FeatureAlign(nn.Module):
         self.conv = nn.Conv2d(in_channels, out_channels, kernel_size=ks, padding=self.padding)
 
     def forward(self, x, shape):
+        shape = shape.detach()  # Featurealign.py:44: the box regression shapes the sampling grid and gets no gradient from it
         if self.use_pred_offset:
             offset = self.conv_offset(shape)
         else:
             offset = ops.fcb_ali_offsets(shape, self.kernel_size[0], self.kernel_size[1])
-        x = ops.deform_conv(x, offset, None, self.conv_adaption.weight, None, 1, self.padding, 1,
-                            self.conv_adaption.deform_groups, relu=True)  # ReLU fused into the GEMM epilogue
+        if autograd.wants_grad(x, offset, self.conv_adaption.weight):
+            x = torch.relu(self.conv_adaption(x, offset))  # DeformConvFunction carries the gradient
+        else:
+            x = ops.deform_conv(x, offset, None, self.conv_adaption.weight, None, 1, self.padding, 1,
+                                self.conv_adaption.deform_groups, relu=True)  # ReLU fused into the GEMM epilogue
         return self.conv(x)
 
 
@@ -162,6 +166,7 @@ class PredictionModule_FC(nn.Module):
             cen.append(nhwc(src.centerness_layer[k](bbox_x)))
             bbox_cur = src.bbox_layer[k](bbox_x)
             bbox.append(nhwc(bbox_cur))
+            bbox_cur = bbox_cur.detach()  # prediction_head_FC.py:167,174,180: the FCB layers read the boxes, they do not train them
             conf.append(nhwc(src.conf_layer[k](conf_x, bbox_cur) if cfg.use_dcn_class else src.conf_layer[k](conf_x)))
             track.append(nhwc(src.track_layer[k](track_x, bbox_cur) if cfg.use_dcn_track else src.track_layer[k](track_x)))
             mask.append(nhwc(src.mask_layer[k](mask_x, bbox_cur) if cfg.use_dcn_mask else src.mask_layer[k](mask_x)))
@@ -224,8 +229,12 @@ class TemporalNet(nn.Module):
 
 def correlate(x1, x2, patch_size=11, dilation_patch=1):
     """Reference track_to_segment_head.py:40-62: patch correlation, / C, leaky_relu(0.1) -> [B, P*P, H, W].
-    The division and the activation are fused into the correlation kernel's epilogue."""
+    Without grad the division and the activation are fused into the correlation kernel's epilogue; under grad the correlation is
+    autograd.correlation and the two follow in torch."""
     b, c, h, w = x1.shape
+    if autograd.wants_grad(x1, x2):
+        out = autograd.correlation(x1, x2, patch_size, dilation_patch).view(b, patch_size * patch_size, h, w)
+        return F.leaky_relu(out / c, 0.1)
     out = ops.corr_patch(x1, x2, patch_size, dilation_patch, scale=1.0 / c, leaky_slope=0.1)
     return out.view(b, patch_size * patch_size, h, w)
 

@@ -422,6 +422,59 @@ def corr_patch_backward(grad_out, f1, f2, dilation_patch=1, need1=True, need2=Tr
     return g1, g2
 
 
+def t2s_check_shapes(who, fpn, t2s, patch_size):
+    """What include/stmask_hip_t2s_feat.h refuses, and what its contiguous fp32 layout asks of the tensors, raised from the shapes before anything
+    touches the device.  Returns (bs, C, Cu, H, W)."""
+    if fpn.dim() != 4 or t2s.dim() != 4:
+        raise StmError(f"{who}: fpn {tuple(fpn.shape)} and t2s {tuple(t2s.shape)} must be [2 bs, C, h, w] and [2 bs, Cu, h, w]")
+    n, C, H, W = fpn.shape
+    if n < 2 or n % 2:
+        raise StmError(f"{who}: {n} images; the two frames of every clip are expected (an even count)")
+    if t2s.shape[0] != n or tuple(t2s.shape[2:]) != (H, W):
+        raise StmError(f"{who}: t2s {tuple(t2s.shape)} does not fit fpn {tuple(fpn.shape)}")
+    if fpn.dtype != torch.float32 or t2s.dtype != torch.float32:
+        raise StmError(f"{who}: expected float32, got {fpn.dtype} and {t2s.dtype}")
+    if fpn.device != t2s.device:
+        raise StmError(f"{who}: fpn on {fpn.device}, t2s on {t2s.device}")
+    P, Cu = int(patch_size), t2s.shape[1]
+    if P < 1 or P % 2 == 0:
+        raise StmError(f"{who}: patch size {patch_size} must be odd and positive")
+    if min(C, Cu, H, W) < 1:
+        raise StmError(f"{who}: empty maps {tuple(fpn.shape)} / {tuple(t2s.shape)}")
+    if not fpn.is_contiguous() or not t2s.is_contiguous():
+        raise StmError(f"{who}: fpn and t2s must be contiguous (the halves are read in place through the batch stride)")
+    if max(P * P, C, Cu) * H * W >= 1 << 31:
+        raise StmError(f"{who}: P*P*h*w, C*h*w and Cu*h*w must stay below 2^31")
+    return n // 2, C, Cu, H, W
+
+
+def t2s_concat_feat(fpn, t2s, patch_size=11):
+    """T2S_concat_feat of STMask.py:291-296 in two launches (stm_t2s_feat_forward_f32): fpn [2 bs, C, h, w], t2s [2 bs, Cu, h, w], the reference frame
+    of clip b at image 2 b, the next frame at 2 b + 1 -> [bs, P*P + 2 Cu, h, w].  No workspace, no host synchronisation."""
+    bs, C, Cu, H, W = t2s_check_shapes("t2s_concat_feat", fpn, t2s, patch_size)
+    _dev(fpn, t2s)
+    out = torch.empty(bs, patch_size * patch_size + 2 * Cu, H, W, device=fpn.device, dtype=torch.float32)
+    call("stm_t2s_feat_forward_f32", _p(fpn), _p(t2s), _p(out), bs, C, Cu, H, W, int(patch_size), _stream())
+    return out
+
+
+def t2s_concat_feat_backward(grad_out, out, fpn, t2s, patch_size=11, need_fpn=True, need_t2s=True):
+    """(grad_fpn, grad_t2s) of t2s_concat_feat from grad_out and the saved inputs and output (stm_t2s_feat_backward_f32: two launches for grad_fpn,
+    one for grad_t2s); a gradient not needed is None and not computed."""
+    bs, C, Cu, H, W = t2s_check_shapes("t2s_concat_feat_backward", fpn, t2s, patch_size)
+    _dev(grad_out, out, fpn, t2s)
+    go = _f32c(grad_out)
+    if tuple(go.shape) != (bs, patch_size * patch_size + 2 * Cu, H, W) or out.shape != go.shape or out.dtype != torch.float32 or \
+            not out.is_contiguous():
+        raise StmError(f"t2s_concat_feat_backward: grad_out {tuple(go.shape)} / out {tuple(out.shape)} do not match the inputs")
+    if not (need_fpn or need_t2s):
+        return None, None
+    g_fpn = torch.empty_like(fpn) if need_fpn else None
+    g_t2s = torch.empty_like(t2s) if need_t2s else None
+    call("stm_t2s_feat_backward_f32", _p(go), _p(out), _p(fpn), _p(t2s), _p(g_fpn), _p(g_t2s), bs, C, Cu, H, W, int(patch_size), _stream())
+    return g_fpn, g_t2s
+
+
 def decode(loc, priors):
     """box_utils.py:238-283, bit-exact vs the oracle."""
     _dev(loc, priors)

@@ -128,3 +128,48 @@ def synthetic_clip(n_frames, h=384, w=640, seed=0, device="cpu"):
     for t in range(n_frames):
         frames.append(torch.roll(x0, shifts=(2 * t, 3 * t), dims=(1, 2)) + 0.05 * torch.randn(3, h, w, generator=g))
     return torch.stack(frames).to(device)
+
+
+def _shape_mask(kind, cy, cx, ry, rx, h, w):
+    ys = torch.arange(h, dtype=torch.float32).view(h, 1) + 0.5
+    xs = torch.arange(w, dtype=torch.float32).view(1, w) + 0.5
+    if kind == 0:                                                       # rectangle
+        return ((ys - cy).abs() <= ry) & ((xs - cx).abs() <= rx)
+    return ((ys - cy) / ry) ** 2 + ((xs - cx) / rx) ** 2 <= 1.0        # ellipse
+
+
+def synthetic_train_batch(bs, h=128, w=192, seed=0, device="cpu"):
+    """A training batch in the nesting MultiBoxLoss.forward takes: (images [bs, 2, 3, h, w] fp32, gt_bboxes, gt_labels, gt_masks, gt_ids), the four
+    ground-truth entries as lists over the clips of [frame 0, frame 1] tensors -- boxes [G, 4] fp32 (x1, y1, x2, y2 relative to the image), labels
+    int64 [G] in 1..40, masks uint8 [G, h, w], instance ids int64 [G].  Every clip holds two to four rectangles and ellipses on a noise background
+    that move by a few pixels between the frames and keep their ids; the last object of clip 0 has left in the second frame."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(7000 + seed)
+    images = 0.3 * torch.randn(bs, 2, 3, h, w, generator=g)
+    gt = ([], [], [], [])
+    for c in range(bs):
+        n = 2 + int(torch.randint(0, 3, (1,), generator=g))
+        u = torch.rand(n, 6, generator=g)
+        cy, cx = (0.3 + 0.4 * u[:, 0]) * h, (0.3 + 0.4 * u[:, 1]) * w
+        ry, rx = (0.10 + 0.12 * u[:, 2]) * h, (0.08 + 0.10 * u[:, 3]) * w
+        vy, vx = (u[:, 4] - 0.5) * 0.1 * h, (u[:, 5] - 0.5) * 0.1 * w
+        labels = torch.randint(1, NUM_CLASSES, (n,), generator=g)
+        colour = torch.randn(n, 3, generator=g)
+        ids = torch.arange(1, n + 1, dtype=torch.int64) + 10 * c
+        per = ([], [], [], [])
+        for t in range(2):
+            keep = n - 1 if (c == 0 and t == 1) else n
+            masks = torch.stack([_shape_mask(k % 2, float(cy[k] + t * vy[k]), float(cx[k] + t * vx[k]), float(ry[k]), float(rx[k]), h, w)
+                                 for k in range(keep)])
+            boxes = []
+            for k in range(keep):
+                images[c, t] = torch.where(masks[k], colour[k].view(3, 1, 1).expand(3, h, w), images[c, t])
+                yy, xx = torch.nonzero(masks[k], as_tuple=True)
+                boxes.append([float(xx.min()) / w, float(yy.min()) / h, float(xx.max() + 1) / w, float(yy.max() + 1) / h])
+            per[0].append(torch.tensor(boxes, dtype=torch.float32).to(device))
+            per[1].append(labels[:keep].clone().to(device))
+            per[2].append(masks.to(torch.uint8).to(device))
+            per[3].append(ids[:keep].clone().to(device))
+        for k in range(4):
+            gt[k].append(per[k])
+    return (images.to(device),) + gt
