@@ -185,6 +185,14 @@ T2S_FEAT_SIGNATURES = {
     "stm_t2s_feat_forward_f32": ("i", "pppiiiiiip"),
     "stm_t2s_feat_backward_f32": ("i", "ppppppiiiiiip"),
 }
+# include/stmask_hip_data.h, the seventh header (tests/test_abi_data.py): training batches -- frames, masks from run lengths, boxes (datasets.py)
+DATA_SIGNATURES = {
+    "stm_data_struct_bytes": ("z", "i"),
+    "stm_data_frames_u8_f32": ("i", "pipiiiippip"),
+    "stm_data_rle_starts": ("i", "pppppilppppp"),
+    "stm_data_masks_u8": ("i", "pppipilpiiiip"),
+    "stm_data_boxes_f32": ("i", "ppipiiiip"),
+}
 
 
 class StmError(RuntimeError):
@@ -209,6 +217,14 @@ class ConvWindow(ctypes.Structure):
 
 class FrameDesc(ctypes.Structure):
     _fields_ = [("ptr", c_p), ("H0", c_i), ("W0", c_i), ("row_stride_bytes", c_l)]
+
+
+class DataFrameDesc(ctypes.Structure):
+    _fields_ = [("ptr", c_p), ("H0", c_i), ("W0", c_i), ("row_stride_bytes", c_l), ("flip", c_i), ("reserved", c_i)]
+
+
+class DataMaskDesc(ctypes.Structure):
+    _fields_ = [(n, c_i) for n in ("H0", "W0", "flip", "list")]
 
 
 class RenderFrame(ctypes.Structure):
@@ -256,7 +272,8 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback on the product path.")
         _lib = ctypes.CDLL(LIB_PATH)
-        tables = {**SIGNATURES, **OUTPUT_SIGNATURES, **TRACKER_SIGNATURES, **TRAIN_SIGNATURES, **EVAL_SIGNATURES, **T2S_FEAT_SIGNATURES}
+        tables = {**SIGNATURES, **OUTPUT_SIGNATURES, **TRACKER_SIGNATURES, **TRAIN_SIGNATURES, **EVAL_SIGNATURES, **T2S_FEAT_SIGNATURES,
+                  **DATA_SIGNATURES}
         missing = [n for n in tables if not hasattr(_lib, n)]
         if missing:
             _lib = None
@@ -268,8 +285,10 @@ def lib():
         # this binding and the library must describe the same structs (a stale .so would read garbage past a shorter struct)
         structs = [DeformGeom, ConvGeom, ConvWindow, HeadLayout, FrameDesc, RenderFrame]
         out_structs = [OutputFrame, OutputRow, OutputHeader]
+        data_structs = [DataFrameDesc, DataMaskDesc]
         if (_lib.stm_version() != ABI_VERSION or any(_lib.stm_struct_bytes(i) != ctypes.sizeof(s) for i, s in enumerate(structs))
-                or any(_lib.stm_output_struct_bytes(i) != ctypes.sizeof(s) for i, s in enumerate(out_structs))):
+                or any(_lib.stm_output_struct_bytes(i) != ctypes.sizeof(s) for i, s in enumerate(out_structs))
+                or any(_lib.stm_data_struct_bytes(i) != ctypes.sizeof(s) for i, s in enumerate(data_structs))):
             v = _lib.stm_version()
             _lib = None
             raise StmError(f"{LIB_PATH} has ABI version {v}, this binding was written for {ABI_VERSION} (or a struct size "

@@ -14,6 +14,7 @@
 // the bits agree with the oracle exactly (-ffp-contract=off).
 #include "stm_common.h"
 #include "rle_common.h"
+#include "preprocess_common.h"
 
 namespace {
 
@@ -91,50 +92,9 @@ extern "C" int stm_mask_resize_rle_f32(const float* masks, int n, int mh, int mw
 // (im - MEANS) / STD in float64 -> zero pad to a multiple of 32 -> CHW fp32, as ONE pass over the output.  The 8-bit
 // bilinear arithmetic is OpenCV's fixed-point path, restated in oracle/stm_oracle.c (orc_resize_pixel_u8) with the
 // derivation; this kernel performs the identical integer / float / double operation sequence, so the two agree bit
-// for bit.  Thread = one output pixel, three channels; HBM-bound (2.8 MB in, 2.9 MB out per 720p frame).
+// for bit.  Thread = one output pixel, three channels; HBM-bound (2.8 MB in, 2.9 MB out per 720p frame).  The per-pixel sequence itself
+// (resize_coeffs, preprocess_pixel) lives in preprocess_common.h, shared with the training frames of train_data.hip.
 namespace {
-
-__device__ __forceinline__ void resize_coeffs(int src, int dst, int d, bool clamp_f, int& s, int& c0, int& c1)
-{
-    const double inv = (double)dst / (double)src;
-    const double scale = 1.0 / inv;
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    s = (int)floorf(f);
-    f -= (float)s;
-    if (clamp_f) {
-        if (s < 0) { f = 0.0f; s = 0; }
-        if (s >= src - 1) { f = 0.0f; s = src - 1; }
-    }
-    int a0 = (int)rintf((1.0f - f) * 2048.0f), a1 = (int)rintf(f * 2048.0f);   // cvRound: round half to even
-    c0 = min(max(a0, -32768), 32767);
-    c1 = min(max(a1, -32768), 32767);
-}
-
-// One output pixel (x, y) < (w, h) of an image whose source rows start at `img` with `row_stride` bytes between rows (3 bytes per pixel):
-// the fixed-point bilinear taps, then the mode's normalisation in double.  Both pre-processing kernels run exactly this sequence.
-__device__ __forceinline__ void preprocess_pixel(const uint8_t* __restrict__ img, int64_t row_stride, int H0, int W0, int h, int w, int x, int y,
-                                                 const double (&mean)[3], const double (&stdv)[3], int mode, float (&o)[3])
-{
-    int sx, sy, a0, a1, b0, b1;
-    resize_coeffs(W0, w, x, true, sx, a0, a1);
-    resize_coeffs(H0, h, y, false, sy, b0, b1);
-    const int sx1 = min(sx + 1, W0 - 1);
-    const int y0 = min(max(sy, 0), H0 - 1), y1 = min(max(sy + 1, 0), H0 - 1);
-    const uint8_t* r0 = img + (int64_t)y0 * row_stride;
-    const uint8_t* r1 = img + (int64_t)y1 * row_stride;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int D0 = r0[sx * 3 + c] * a0 + r0[sx1 * 3 + c] * a1;
-        const int D1 = r1[sx * 3 + c] * a0 + r1[sx1 * 3 + c] * a1;
-        int v = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2;
-        v = min(max(v, 0), 255);
-        double d = (double)v;
-        if (mode == 1) d = (d - mean[c]) / stdv[c];
-        else if (mode == 2) d = d - mean[c];
-        else if (mode == 3) d = d / 255.0;
-        o[c] = (float)d;
-    }
-}
 
 __global__ __launch_bounds__(256) void preprocess_u8_kernel(const uint8_t* __restrict__ img, float* __restrict__ out, int H0, int W0,
                                                             int h, int w, int Hp, int Wp, double m0, double m1, double m2, double s0,

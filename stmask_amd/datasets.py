@@ -1,0 +1,419 @@
+"""Training batches from a YouTube-VIS / OVIS annotation file: everything between the JSON and
+`criterion(net, net(images), gt_bboxes, gt_labels, gt_masks, gt_ids)`.  The reference does this per sample on the host, in DataLoader workers
+(datasets/ytvos.py prepare_train_img, datasets/transforms.py, detection_collate, train.py prepare_data): every instance's RLE decoded to a mask at
+source resolution, each resized with cv2, flipped, padded and stacked, both frames resized and normalised in numpy, then `G x Hp x Wp` mask bytes
+and the float images uploaded.  Here the host only samples and parses (`YTVISTrainSet`: a record of arrays, run lists as the JSON gave them,
+boxes, labels, ids and the flip flag) and `collate_device` uploads the uint8 frames and the run lists and renders the batch on the MI355X
+(csrc/train_data.hip, include/stmask_hip_data.h): frames resized / normalised / flipped / padded by the kernel of the inference pre-processing,
+masks drawn straight from their run lengths at the target size, boxes transformed in fp32.  No mask at source resolution exists anywhere.
+INTEGRATION.md section 20 is the contract.  There is no CPU fallback for the device part.
+
+Scope: the reference's training configs -- img_scale=[(640, 360)], resize_keep_ratio=False, size_divisor=32, flip_ratio=0.5, to_rgb=True,
+with_track=True, clip_frames=1, extra_aug=None.  Not built: ExtraAugmentation, aug_ref_bbox_param, proposals, keep_ratio=True, more than one
+img_scale, DataParallel, logging, checkpoints.
+"""
+import ctypes
+import os
+import random
+
+import numpy as np
+import torch
+
+from . import _lib, vis_eval
+from ._lib import StmError, c_p, call
+from .preprocess import MEANS, STD
+
+# launches of the stm_data_* / stm_vis_rle_decode entry points and bytes copied to the device since the last reset_counters()
+# (scripts/bench_train_data.py reports them); "uploads" counts the host -> device copies
+COUNTERS = {"launches": 0, "uploads": 0, "h2d_bytes": 0}
+
+
+def reset_counters():
+    for k in COUNTERS:
+        COUNTERS[k] = 0
+
+
+def _launch(name, launches, *args):
+    COUNTERS["launches"] += launches
+    call(name, *args)
+
+
+def _p(t):
+    return c_p(t.data_ptr()) if t is not None and t.numel() else c_p(0)
+
+
+def _stream():
+    return c_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _device(device):
+    if device is None:
+        if not torch.cuda.is_available():
+            raise StmError("datasets: the batch is rendered on the MI355X; there is no CPU fallback")
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise StmError(f"datasets: collate_device needs a GPU device, got {device}; there is no CPU fallback")
+    return device
+
+
+def _up(x, device):
+    """One host -> device copy through pinned memory, queued on the current stream (no host wait)."""
+    t = torch.from_numpy(np.ascontiguousarray(x))
+    if t.numel() == 0:
+        return torch.empty(t.shape, dtype=t.dtype, device=device)
+    COUNTERS["uploads"] += 1
+    COUNTERS["h2d_bytes"] += t.numel() * t.element_size()
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def padded_size(size, divisor):
+    """(h, w, Hp, Wp) of img_scale `size` = (w, h) padded to a multiple of `divisor` (mmcv.impad_to_multiple)."""
+    w, h = int(size[0]), int(size[1])
+    d = int(divisor) if divisor else 1
+    return h, w, -(-h // d) * d, -(-w // d) * d
+
+
+# ------------------------------------------------------------------------------------------------------------------ device stages
+def upload_frames(arrays, device=None):
+    """uint8 [H_i, W_i, 3] host arrays -> device views of ONE buffer, staged in pinned memory and copied once."""
+    device = _device(device)
+    sizes = []
+    for i, a in enumerate(arrays):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"frame {i}: expected a uint8 [H, W, 3] array, got {type(a).__name__} "
+                             f"{getattr(a, 'dtype', '')} {getattr(a, 'shape', '')}")
+        sizes.append(a.size)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    stage = torch.empty(int(off[-1]), dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    for a, o in zip(arrays, off[:-1]):
+        host[o:o + a.size] = a.reshape(-1)
+    COUNTERS["uploads"] += 1
+    COUNTERS["h2d_bytes"] += int(off[-1])
+    buf = stage.to(device, non_blocking=True)
+    return [buf[o:o + a.size].view(a.shape) for a, o in zip(arrays, off[:-1])]
+
+
+def train_frames(frames, flips, size=(640, 360), divisor=32, mean=MEANS, std=STD, to_rgb=True, out=None):
+    """stm_data_frames_u8_f32: frames = uint8 [H_i, W_i, 3] device tensors (BGR; rows may be strided, pixels and channels contiguous), flips = one
+    flag per frame -> fp32 [n, 3, Hp, Wp]: ImageTransform.__call__ with keep_ratio=False.  mean / std in the output's channel order.  With flip
+    off and to_rgb=False image i is bit-identical to ops.preprocess_frames_multi."""
+    frames = list(frames)
+    h, w, Hp, Wp = padded_size(size, divisor)
+    n = len(frames)
+    if len(flips) != n:
+        raise StmError(f"train_frames: {n} frames, {len(flips)} flip flags")
+    if n == 0:
+        raise StmError("train_frames: no frames")
+    dev = frames[0].device
+    _device(dev)
+    desc = (_lib.DataFrameDesc * n)()
+    keep = []                                       # contiguous copies made here live until the launch is enqueued (same stream)
+    for i, f in enumerate(frames):
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3 or f.device != dev:
+            raise StmError(f"train_frames: frame {i}: expected uint8 [H,W,3] on {dev}, got {f.dtype} {tuple(f.shape)} on {f.device}")
+        if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.shape[1]:
+            f = f.contiguous()
+            keep.append(f)
+        desc[i].ptr, desc[i].H0, desc[i].W0, desc[i].row_stride_bytes, desc[i].flip = f.data_ptr(), f.shape[0], f.shape[1], f.stride(0), int(bool(flips[i]))
+    if out is None:
+        out = torch.empty(n, 3, Hp, Wp, device=dev, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, 3, Hp, Wp) or not out.is_contiguous() or out.device != dev:
+        raise StmError(f"train_frames: out must be contiguous fp32 {(n, 3, Hp, Wp)} on {dev}, got {out.dtype} {tuple(out.shape)}")
+    m3, s3 = (ctypes.c_double * 3)(*mean), (ctypes.c_double * 3)(*std)
+    with torch.cuda.device(dev):
+        _launch("stm_data_frames_u8_f32", -(-n // 64), desc, n, _p(out), h, w, Hp, Wp, m3, s3, int(bool(to_rgb)), _stream())
+    return out
+
+
+class BatchStatus:
+    """The status words of a batch's masks on their way to the host: a copy into pinned memory queued behind the kernels, and an event.
+    `raise_if_bad()` waits for the event (already passed a step later) and raises ValueError naming the first flagged record."""
+
+    def __init__(self, status, pos, who):
+        self.pos, self.who = pos, who
+        self.host = torch.empty(status.shape, dtype=status.dtype, pin_memory=True) if status.numel() else None
+        self.event = None
+        if self.host is not None:
+            self.host.copy_(status, non_blocking=True)
+            self.event = torch.cuda.Event()
+            self.event.record()
+
+    def raise_if_bad(self):
+        if self.host is None:
+            return
+        self.event.synchronize()
+        vis_eval.raise_for_status(self.host.numpy(), self.pos, self.who)
+
+
+class GroundTruth:
+    """render_ground_truth's result.  masks uint8 [n, Hp, Wp], boxes fp32 [n, 4] (None without boxes), extra int64 [k, n] (the rows handed in),
+    area int64 [n] and n_runs int32 [n] in the lists' order (list of mask i: pos[i]), status: a BatchStatus; uploaded: the buffers the launches
+    read (launch_ground_truth(gt.uploaded) repeats them)."""
+
+    def __init__(self, masks, boxes, extra, area, n_runs, status, pos):
+        self.masks, self.boxes, self.extra, self.area, self.n_runs, self.status, self.pos = masks, boxes, extra, area, n_runs, status, pos
+        self.uploaded = None
+
+
+def render_ground_truth(rles, sizes, flips, boxes=None, extra=(), size=(640, 360), divisor=32, device=None, who=None):
+    """The ground truth of a batch on the device.  rles: n COCO RLE dicts {'size': [H0, W0], 'counts': list of run lengths | compressed string};
+    flips: n flags; boxes: float32 [n, 4] in source pixels or None; extra: rows of n integers to travel with the descriptors (labels, ids).
+    Uploads: the run lists, the characters of the compressed strings if there are any, one descriptor block, the boxes.  Launches: stm_vis_rle_decode
+    when a string is present, stm_data_rle_starts, stm_data_masks_u8, stm_data_boxes_f32.  No host wait: the status is read through the
+    BatchStatus returned."""
+    device = _device(device)
+    h, w, Hp, Wp = padded_size(size, divisor)
+    n = len(rles)
+    name = who or (lambda i: f"mask {i}")
+    if len(flips) != n or (boxes is not None and len(boxes) != n) or any(len(e) != n for e in extra):
+        raise StmError("render_ground_truth: the masks, flips, boxes and extra rows differ in length")
+    masks = torch.empty(n, Hp, Wp, dtype=torch.uint8, device=device)
+    if n == 0:
+        return GroundTruth(masks, None if boxes is None else torch.empty(0, 4, device=device), torch.empty(len(extra), 0, dtype=torch.int64, device=device),
+                           torch.empty(0, dtype=torch.int64, device=device), torch.empty(0, dtype=torch.int32, device=device),
+                           BatchStatus(torch.empty(0, dtype=torch.int32, device=device), np.zeros(0, np.int64), name), np.zeros(0, np.int64))
+    for i, r in enumerate(rles):
+        if not isinstance(r, dict) or "counts" not in r or "size" not in r:
+            raise ValueError(f"{name(i)}: the segmentation is not an RLE dict with 'size' and 'counts' (polygons are not built)")
+        if [int(v) for v in r["size"]] != [int(v) for v in sizes[i]]:
+            raise ValueError(f"{name(i)}: the RLE's size {list(r['size'])} is not the frame's {list(sizes[i])}")
+    hm = vis_eval.flatten_masks(rles, name)           # string masks first; checks h * w < 2^32 and every run length on the host
+    ns, total_c, total_l = hm.ns, int(hm.s_off[-1]), int(hm.l_off[-1])
+    total = total_c + total_l
+    k = len(extra)
+    # one descriptor block: int64 offsets [n + 1] | hw [n] | extra [k, n] | int32 n_runs [n] | status [n] | stm_data_mask_desc [n]
+    meta = np.zeros((2 + k) * n + 1 + 3 * n, dtype=np.int64)
+    meta[:ns] = hm.s_off[:-1]
+    meta[ns:n + 1] = total_c + hm.l_off
+    meta[n + 1:2 * n + 1] = hm.hw
+    for j, e in enumerate(extra):
+        meta[(2 + j) * n + 1:(3 + j) * n + 1] = np.asarray(e, dtype=np.int64)
+    i32 = meta[(2 + k) * n + 1:].view(np.int32)
+    i32[ns:n] = np.diff(hm.l_off)                     # the lists' run counts; stm_vis_rle_decode writes the strings'
+    desc = i32[2 * n:].reshape(n, 4)
+    desc[:, 0] = [s[0] for s in sizes]
+    desc[:, 1] = [s[1] for s in sizes]
+    desc[:, 2] = [1 if f else 0 for f in flips]
+    desc[:, 3] = hm.pos
+    with torch.cuda.device(device):
+        up = {"n": n, "ns": ns, "total_c": total_c, "total": total, "k": k, "dims": (h, w, Hp, Wp), "masks": masks}
+        up["meta"] = _up(meta, device)
+        up["runs"] = torch.empty(total, dtype=torch.int32, device=device)
+        if total_l:
+            COUNTERS["uploads"] += 1
+            COUNTERS["h2d_bytes"] += 4 * total_l
+            up["runs"][total_c:].copy_(torch.from_numpy(hm.flat.view(np.int32)).pin_memory(), non_blocking=True)
+        up["chars"] = _up(hm.chars, device) if total_c else None
+        up["boxes"] = None if boxes is None else _up(np.asarray(boxes, dtype=np.float32).reshape(n, 4), device)
+        boxes_d, extra_d, area, n_runs, status = launch_ground_truth(up)
+        st = BatchStatus(status, hm.pos, name)
+    gt = GroundTruth(masks, boxes_d, extra_d, area, n_runs, st, hm.pos)
+    gt.uploaded = up
+    return gt
+
+
+def launch_ground_truth(up):
+    """The device part of render_ground_truth over its uploaded buffers: at most four launches, nothing copied, nothing read.  (A function of its
+    own so that scripts/bench_train_data.py can time the launches alone.)"""
+    n, ns, total_c, total, k = up["n"], up["ns"], up["total_c"], up["total"], up["k"]
+    h, w, Hp, Wp = up["dims"]
+    meta_d, runs, device = up["meta"], up["runs"], up["meta"].device
+    off_d, hw_d = meta_d[:n + 1], meta_d[n + 1:2 * n + 1]
+    extra_d = meta_d[2 * n + 1:(2 + k) * n + 1].view(k, n)
+    i32_d = meta_d[(2 + k) * n + 1:].view(torch.int32)
+    n_runs, status, desc_d = i32_d[:n], i32_d[n:2 * n], i32_d[2 * n:]
+    starts = torch.empty(total, dtype=torch.int32, device=device)
+    area = torch.empty(n, dtype=torch.int64, device=device)
+    if ns:
+        _launch("stm_vis_rle_decode", 1, _p(up["chars"]), _p(off_d), _p(hw_d), ns, total_c, _p(runs), _p(n_runs), _p(area), _p(status), _stream())
+    _launch("stm_data_rle_starts", 1, _p(runs), _p(off_d), _p(n_runs), _p(status), _p(hw_d), n, total, _p(starts), _p(n_runs), _p(area), _p(status),
+            _stream())
+    _launch("stm_data_masks_u8", 1, _p(starts), _p(off_d), _p(n_runs), n, _p(desc_d), n, total, _p(up["masks"]), h, w, Hp, Wp, _stream())
+    boxes_d = None
+    if up["boxes"] is not None:
+        boxes_d = torch.empty(n, 4, dtype=torch.float32, device=device)
+        _launch("stm_data_boxes_f32", 1, _p(up["boxes"]), _p(desc_d), n, _p(boxes_d), h, w, Hp, Wp, _stream())
+    return boxes_d, extra_d, area, n_runs, status
+
+
+# ------------------------------------------------------------------------------------------------------------------ the dataset
+def read_frame(path):
+    """The default frame_reader: the file decoded with PIL, channels reversed to cv2's BGR.  The decoder is not cv2.imread's: JPEG decoders differ
+    in the last bit of some pixels, which is outside the contract."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, ::-1])
+
+
+class YTVISTrainSet:
+    """YTVOSDataset (datasets/ytvos.py) for test_mode=False, as far as the reference's training configs use it.  `ann`: a path or the loaded dict.
+    Item i is the frame pair of img_ids[i] as a host record (no pixel work):
+        frames [2] uint8 [H0, W0, 3] BGR arrays (frame_reader's), size (H0, W0), flip, video_id, frame_ids [2] (sorted),
+        bboxes [2] float32 [G, 4], labels [2] int64 [G], obj_ids [2] lists (the annotation ids), segms [2] lists of RLE dicts as the JSON holds them,
+        img_meta (the reference's dict; frame_id is the LAST frame of the sorted pair, its quirk), and the transform's settings.
+    Departure: the reference appends a crowd annotation's mask but not its box, which misaligns gt_masks and gt_bboxes for the criterion; here a
+    crowd annotation contributes neither."""
+
+    def __init__(self, ann, img_prefix=None, frame_reader=None, img_scale=(640, 360), size_divisor=32, flip_ratio=0.5, clip_frames=1, to_rgb=True,
+                 mean=MEANS, std=STD):
+        data = vis_eval._load(ann)
+        if isinstance(img_scale, list):
+            if len(img_scale) != 1:
+                raise ValueError("YTVISTrainSet: more than one img_scale is not built")
+            img_scale = img_scale[0]
+        if not 0 <= flip_ratio <= 1:
+            raise ValueError(f"YTVISTrainSet: flip_ratio={flip_ratio}")
+        self.img_prefix, self.frame_reader = img_prefix, frame_reader or read_frame
+        self.img_scale, self.size_divisor, self.flip_ratio, self.clip_frames = (int(img_scale[0]), int(img_scale[1])), size_divisor, flip_ratio, clip_frames
+        self.to_rgb, self.mean, self.std = bool(to_rgb), tuple(mean), tuple(std)
+        self.cat_ids = [c["id"] for c in data["categories"]]
+        self.cat2label = {cat_id: i + 1 for i, cat_id in enumerate(self.cat_ids)}
+        self.vid_ids = [v["id"] for v in data["videos"]]
+        self.vid_infos = {v["id"]: v for v in data["videos"]}
+        self.vid_anns = {v: [] for v in self.vid_ids}
+        for a in data.get("annotations") or []:
+            self.vid_anns[a["video_id"]].append(a)
+        self.img_ids = [(v, f) for v in self.vid_ids for f in range(len(self.vid_infos[v]["file_names"]))
+                        if len(self.get_ann_info(v, f)["bboxes"])]
+        self._valid = set(self.img_ids)
+
+    def __len__(self):
+        return len(self.img_ids)
+
+    def get_ann_info(self, vid_id, frame_id):
+        """_parse_ann_info for one frame: skip bbox None, area <= 0, w < 1, h < 1 (and crowd annotations: see the class)."""
+        bboxes, labels, obj_ids, segms = [], [], [], []
+        for ann in self.vid_anns[vid_id]:
+            bbox = ann["bboxes"][frame_id]
+            if bbox is None:
+                continue
+            area = ann["areas"][frame_id]
+            x1, y1, w, h = bbox
+            if area <= 0 or w < 1 or h < 1:
+                continue
+            if ann.get("iscrowd"):
+                continue
+            bboxes.append([x1, y1, x1 + w - 1, y1 + h - 1])
+            labels.append(self.cat2label[ann["category_id"]])
+            obj_ids.append(ann["id"])
+            segms.append(ann["segmentations"][frame_id])
+        return {"bboxes": np.array(bboxes, dtype=np.float32) if bboxes else np.zeros((0, 4), dtype=np.float32),
+                "labels": np.array(labels, dtype=np.int64), "obj_ids": obj_ids, "segms": segms}
+
+    def sample_ref(self, idx):
+        """Another frame of the video within +-2 * clip_frames that is itself in img_ids, drawn with Python's random; the frame itself if none."""
+        vid, frame_id = idx
+        valid = [frame_id + i for i in range(-2 * self.clip_frames, 2 * self.clip_frames + 1) if i != 0 and (vid, frame_id + i) in self._valid]
+        return random.sample(valid, 1) if valid else [frame_id]
+
+    def __getitem__(self, i):
+        vid, frame_id = self.img_ids[i]
+        info = self.vid_infos[vid]
+        clip = sorted(self.sample_ref((vid, frame_id)) + [frame_id])
+        flip = bool(np.random.rand() < self.flip_ratio)
+        frames = []
+        for f in clip:
+            name = info["file_names"][f]
+            frames.append(self.frame_reader(name if self.img_prefix is None else os.path.join(self.img_prefix, name)))
+        H0, W0 = int(frames[0].shape[0]), int(frames[0].shape[1])
+        anns = [self.get_ann_info(vid, f) for f in clip]
+        h, w, Hp, Wp = padded_size(self.img_scale, self.size_divisor)
+        last = clip[-1]
+        meta = dict(ori_shape=(info["height"], info["width"], 3), img_shape=(h, w, 3), pad_shape=(Hp, Wp, 3), video_id=vid, frame_id=last,
+                    is_first=(last == 0), scale_factor=np.array([w / W0, h / H0, w / W0, h / H0], dtype=np.float32), flip=flip)
+        return dict(frames=frames, size=(H0, W0), flip=flip, video_id=vid, frame_ids=clip, bboxes=[a["bboxes"] for a in anns],
+                    labels=[a["labels"] for a in anns], obj_ids=[a["obj_ids"] for a in anns],
+                    segms=[a["segms"] for a in anns], img_meta=meta, img_scale=self.img_scale, size_divisor=self.size_divisor, to_rgb=self.to_rgb,
+                    mean=self.mean, std=self.std)
+
+
+def collate_device(records, device=None, max_gt=None, check="raise"):
+    """Records of YTVISTrainSet -> (images [bs, 2, 3, Hp, Wp] fp32, gt_bboxes, gt_labels, gt_masks, gt_ids, img_meta) on the device, ready for
+    train.train_step, in the nesting synthetic.synthetic_train_batch documents: the four ground-truth entries are lists over the clips of
+    [frame 0, frame 1] tensors (boxes [G, 4] fp32 relative to the padded image, labels int64 [G], masks uint8 [G, Hp, Wp], ids int64 [G]), each a
+    view into one buffer per kind.  max_gt keeps the first max_gt objects of a frame.  One upload each for the frames (pinned staging), the run
+    lists, the descriptors (labels and ids ride along) and the boxes; at most 64 frames take 4 launches, plus one when a mask arrives as a
+    compressed string.  A flagged mask raises ValueError naming the video id, annotation id and frame: check="raise" waits for the status words
+    here; check="deferred" appends a BatchStatus to the tuple whose .raise_if_bad() the caller invokes a step later, so the call itself never
+    waits for the device."""
+    if check not in ("raise", "deferred"):
+        raise ValueError(f"collate_device: check={check!r}")
+    device = _device(device)
+    records = list(records)
+    if not records:
+        raise StmError("collate_device: no records")
+    r0 = records[0]
+    for r in records:
+        if any(r[k] != r0[k] for k in ("img_scale", "size_divisor", "to_rgb", "mean", "std")):
+            raise StmError("collate_device: the records come from datasets with different transforms")
+    frames, f_flips, rles, sizes, flips, names, counts = [], [], [], [], [], [], []
+    boxes, labels, ids = [], [], []
+    for r in records:
+        for t, f in enumerate(r["frames"]):
+            frames.append(f)
+            f_flips.append(r["flip"])
+            g = len(r["segms"][t]) if max_gt is None else min(len(r["segms"][t]), int(max_gt))
+            counts.append(g)
+            size = (int(f.shape[0]), int(f.shape[1]))
+            for j in range(g):
+                rles.append(r["segms"][t][j])
+                sizes.append(size)
+                flips.append(r["flip"])
+                names.append((r["video_id"], r["obj_ids"][t][j], r["frame_ids"][t]))
+            boxes.append(r["bboxes"][t][:g])
+            labels.append(r["labels"][t][:g])
+            ids.append(np.asarray(r["obj_ids"][t][:g], dtype=np.int64))
+    who = lambda i: "video %s, annotation %s, frame %s" % names[i]      # noqa: E731
+    with torch.cuda.device(device):
+        dev_frames = upload_frames(frames, device)
+        images = train_frames(dev_frames, f_flips, r0["img_scale"], r0["size_divisor"], r0["mean"], r0["std"], r0["to_rgb"])
+        gt = render_ground_truth(rles, sizes, flips, np.concatenate(boxes).reshape(-1, 4), (np.concatenate(labels), np.concatenate(ids)),
+                                 r0["img_scale"], r0["size_divisor"], device, who)
+    edges = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    per = lambda t: [[t[edges[2 * c + k]:edges[2 * c + k + 1]] for k in range(2)] for c in range(len(records))]   # noqa: E731
+    out = (images.view(len(records), 2, *images.shape[1:]), per(gt.boxes), per(gt.extra[0]), per(gt.masks), per(gt.extra[1]),
+           [r["img_meta"] for r in records])
+    if check == "deferred":
+        return out + (gt.status,)
+    gt.status.raise_if_bad()
+    return out
+
+
+class TrainLoader:
+    """An epoch of batches: torch.randperm with a seeded generator (seed + epoch), the last short batch dropped (len(dataset) // batch_size, the
+    reference's epoch_size).  No threads and no worker processes: next() reads and collates batch k + 1 on the host while the device still runs
+    the step the caller queued for batch k.  Batches are collated with check="deferred"; the status of batch k is looked at when batch k + 1 is
+    asked for (and that of the last batch when the epoch ends), so a loop with max_pos=K never waits for the device here."""
+
+    def __init__(self, dataset, batch_size, shuffle=True, seed=0, device=None, max_gt=None):
+        if batch_size < 1:
+            raise ValueError(f"TrainLoader: batch_size={batch_size}")
+        self.dataset, self.batch_size, self.shuffle, self.seed, self.device, self.max_gt = dataset, int(batch_size), shuffle, seed, device, max_gt
+        self.epoch = 0
+
+    def __len__(self):
+        return len(self.dataset) // self.batch_size
+
+    def order(self, epoch):
+        n = len(self.dataset)
+        if not self.shuffle:
+            return list(range(n))
+        g = torch.Generator(device="cpu")
+        g.manual_seed(self.seed + epoch)
+        return torch.randperm(n, generator=g).tolist()
+
+    def __iter__(self):
+        order = self.order(self.epoch)
+        self.epoch += 1
+        pending = None
+        for k in range(len(self)):
+            records = [self.dataset[i] for i in order[k * self.batch_size:(k + 1) * self.batch_size]]
+            *batch, status = collate_device(records, self.device, self.max_gt, check="deferred")
+            if pending is not None:
+                pending.raise_if_bad()
+            pending = status
+            yield tuple(batch)
+        if pending is not None:
+            pending.raise_if_bad()
