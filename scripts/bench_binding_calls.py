@@ -1,7 +1,7 @@
 """Host cost of one call through the ctypes binding, declared signatures against per-call casts.  No GPU: every call below returns before it
 touches a device.
 
-The library is opened twice in one process: `new` is stmask_amd._lib.lib() (restype / argtypes set from _lib.SIGNATURES, plain Python arguments),
+The library is opened twice in one process: `new` is stmask_amd._lib.lib() (restype / argtypes set from the tables of _lib.HEADERS, plain Python arguments),
 `old` a bare ctypes.CDLL handle used the way the package used it before the table existed (no argtypes, every scalar wrapped at the call site).
   query   stm_conv_kxr_tile_pixels(3, 1, 4): a 3-argument pure function
   refuse  stm_ohem_conf_loss_f32 with C = 1: 14 arguments, refused with STM_EUNSUPPORTED (-5) from the shapes alone

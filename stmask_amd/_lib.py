@@ -13,9 +13,10 @@ _calls = {}   # name -> (function, argument count) for call(); lib() fills it
 
 c_i, c_l, c_f, c_p, c_sz = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-# include/stmask_hip.h restated: return kind and parameter kinds of every entry point, in the header's words (tests/test_abi.py parses the
-# header and compares every argument).  lib() sets restype / argtypes from this table, so a plain Python int reaches an int64_t or size_t
-# parameter at full width and a wrong type is a ctypes.ArgumentError; call() adds the argument count, which ctypes does not check.
+# The headers under include/ restated, one table each (HEADERS below lists them): return kind and parameter kinds of every entry point, in the
+# header's words (tests/test_abi.py parses each header and compares every argument).  lib() sets restype / argtypes from these tables, so a plain
+# Python int reaches an int64_t or size_t parameter at full width and a wrong type is a ctypes.ArgumentError; call() adds the argument count,
+# which ctypes does not check.
 # p: any pointer or array, and stm_stream_t; i: int; l: int64_t; q: long long; f: float; d: double; z: size_t; returns also v: void, s: const char*
 _KINDS = {"p": c_p, "i": c_i, "l": c_l, "q": ctypes.c_longlong, "f": c_f, "d": ctypes.c_double, "z": c_sz, "v": None, "s": ctypes.c_char_p}
 ABI_VERSION = 6   # include/stmask_hip.h STM_ABI_VERSION
@@ -150,19 +151,15 @@ SIGNATURES = {
     "stm_mask_bce_upsampled_backward_f32": ("i", "pppippiiiiiip"),
 }
 ABI_SYMBOLS = list(SIGNATURES)
-# include/stmask_hip_output.h restated the same way (tests/test_abi_output.py): the batched output stage, declared in a header of its own so that
-# the first header's prototype list and ABI_VERSION stay as they are.  Same library; lib() and call() treat both tables alike.
 OUTPUT_SIGNATURES = {
     "stm_output_struct_bytes": ("z", "i"),
     "stm_output_stage_workspace_bytes": ("z", "ili"),
     "stm_output_stage_multi_f32": ("i", "piiipppipipppiffipzpzp"),
 }
-# include/stmask_hip_tracker.h, the third header (tests/test_abi_tracker.py): the tracker's decisions on the device
 TRACKER_SIGNATURES = {
     "stm_track_resolve_tf": ("i", "pppppiiiipppp"),
     "stm_track_drop_plan": ("i", "ppiippp"),
 }
-# include/stmask_hip_train.h, the fourth header (tests/test_abi_train.py): the batched mask term of the training criterion
 TRAIN_SIGNATURES = {
     "stm_mbox_workspace_bytes": ("z", "ii"),
     "stm_mbox_positives": ("i", "ppiiipzp"),
@@ -173,19 +170,16 @@ TRAIN_SIGNATURES = {
     "stm_lincomb_rows_proto_backward_f32": ("i", "ppipppppiiiipzp"),
     "stm_mbox_scatter_coeff_f32": ("i", "pppppiiiipzp"),
 }
-# include/stmask_hip_eval.h, the fifth header (tests/test_abi_eval.py): video mask AP -- RLE string decode, tube IoU, greedy matching (vis_eval.py)
 EVAL_SIGNATURES = {
     "stm_vis_rle_decode": ("i", "pppilppppp"),
     "stm_vis_rle_check": ("i", "pppilpppp"),
     "stm_vis_tube_iou": ("i", "pplppiipppplpppp"),
     "stm_vis_match": ("i", "ppppiiippppipipppp"),
 }
-# include/stmask_hip_t2s_feat.h, the sixth header (tests/test_abi_t2s_feat.py): T2S_concat_feat of the train-mode forward and its adjoint
 T2S_FEAT_SIGNATURES = {
     "stm_t2s_feat_forward_f32": ("i", "pppiiiiiip"),
     "stm_t2s_feat_backward_f32": ("i", "ppppppiiiiiip"),
 }
-# include/stmask_hip_data.h, the seventh header (tests/test_abi_data.py): training batches -- frames, masks from run lengths, boxes (datasets.py)
 DATA_SIGNATURES = {
     "stm_data_struct_bytes": ("z", "i"),
     "stm_data_frames_u8_f32": ("i", "pipiiiippip"),
@@ -193,6 +187,31 @@ DATA_SIGNATURES = {
     "stm_data_masks_u8": ("i", "pppipilpiiiip"),
     "stm_data_boxes_f32": ("i", "ppipiiiip"),
 }
+# The C boundary, stated once: every header of include/ and the table that restates it, in the order the headers were added.  All seven declare
+# entries of the one library; each newer one is a header of its own so that stmask_hip.h's prototype list and ABI_VERSION stay as they are.
+#   stmask_hip.h           the drop-in operators, the planar inference graph, the loss terms
+#   stmask_hip_output.h    the batched output stage (masks to RLE strings)
+#   stmask_hip_tracker.h   the tracker's decisions on the device
+#   stmask_hip_train.h     the batched mask term of the training criterion
+#   stmask_hip_eval.h      video mask AP: RLE string decode, tube IoU, greedy matching (vis_eval.py)
+#   stmask_hip_t2s_feat.h  T2S_concat_feat of the train-mode forward and its adjoint
+#   stmask_hip_data.h      training batches: frames, masks from run lengths, boxes (datasets.py)
+# lib(), __graft_entry__.build() and tests/test_abi.py walk this mapping.  A new header takes its table, an entry here and a row in EXPECTED of
+# tests/test_abi.py; structs that cross the boundary also take a size function and their mirrors in STRUCTS below.
+HEADERS = {
+    "stmask_hip.h": SIGNATURES,
+    "stmask_hip_output.h": OUTPUT_SIGNATURES,
+    "stmask_hip_tracker.h": TRACKER_SIGNATURES,
+    "stmask_hip_train.h": TRAIN_SIGNATURES,
+    "stmask_hip_eval.h": EVAL_SIGNATURES,
+    "stmask_hip_t2s_feat.h": T2S_FEAT_SIGNATURES,
+    "stmask_hip_data.h": DATA_SIGNATURES,
+}
+
+
+def all_signatures():
+    """{name: (return kind, parameter kinds)} of every header, read from the tables as they are now."""
+    return {name: sig for table in HEADERS.values() for name, sig in table.items()}
 
 
 class StmError(RuntimeError):
@@ -255,6 +274,14 @@ class HeadLayout(ctypes.Structure):
                 [("lvl_start", c_i * 8), ("lvl_hw", c_i * 8)])
 
 
+# size function of the library -> the mirrors of the structs it knows, by index: lib() refuses a library whose sizes differ
+STRUCTS = {
+    "stm_struct_bytes": [DeformGeom, ConvGeom, ConvWindow, HeadLayout, FrameDesc, RenderFrame],
+    "stm_output_struct_bytes": [OutputFrame, OutputRow, OutputHeader],
+    "stm_data_struct_bytes": [DataFrameDesc, DataMaskDesc],
+}
+
+
 def build(force=False):
     """Compile csrc/*.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
     cmd = ["make", "-C", os.path.join(_HERE, "csrc"), "-s", "-j4"]
@@ -272,8 +299,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback on the product path.")
         _lib = ctypes.CDLL(LIB_PATH)
-        tables = {**SIGNATURES, **OUTPUT_SIGNATURES, **TRACKER_SIGNATURES, **TRAIN_SIGNATURES, **EVAL_SIGNATURES, **T2S_FEAT_SIGNATURES,
-                  **DATA_SIGNATURES}
+        tables = all_signatures()
         missing = [n for n in tables if not hasattr(_lib, n)]
         if missing:
             _lib = None
@@ -283,12 +309,8 @@ def lib():
             fn.restype, fn.argtypes = _KINDS[ret], [_KINDS[k] for k in params]
             _calls[name] = (fn, len(params))
         # this binding and the library must describe the same structs (a stale .so would read garbage past a shorter struct)
-        structs = [DeformGeom, ConvGeom, ConvWindow, HeadLayout, FrameDesc, RenderFrame]
-        out_structs = [OutputFrame, OutputRow, OutputHeader]
-        data_structs = [DataFrameDesc, DataMaskDesc]
-        if (_lib.stm_version() != ABI_VERSION or any(_lib.stm_struct_bytes(i) != ctypes.sizeof(s) for i, s in enumerate(structs))
-                or any(_lib.stm_output_struct_bytes(i) != ctypes.sizeof(s) for i, s in enumerate(out_structs))
-                or any(_lib.stm_data_struct_bytes(i) != ctypes.sizeof(s) for i, s in enumerate(data_structs))):
+        if _lib.stm_version() != ABI_VERSION or any(getattr(_lib, size_fn)(i) != ctypes.sizeof(s)
+                                                    for size_fn, mirrors in STRUCTS.items() for i, s in enumerate(mirrors)):
             v = _lib.stm_version()
             _lib = None
             raise StmError(f"{LIB_PATH} has ABI version {v}, this binding was written for {ABI_VERSION} (or a struct size "

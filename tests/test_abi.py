@@ -1,5 +1,6 @@
-"""CPU-only checks of the drop-in boundary: the C-ABI library loads and exports every symbol the header declares,
-and the product path never touches the oracle."""
+"""CPU-only checks of the drop-in boundary: every header of include/ and the table of stmask_amd/_lib.py that restates it say the same thing
+(_lib.HEADERS lists them; EXPECTED below pins what each declares), the C-ABI library loads and exports every symbol, and the product path never
+touches the oracle.  What is about one header only (what its entries refuse without a device, its defines) is in tests/test_abi_<header>.py."""
 import ctypes
 import os
 import re
@@ -7,51 +8,107 @@ import re
 import pytest
 import torch
 
+from abi_header import assert_table_matches_header, header_raw, header_symbols, header_text, struct_field_names
 from conftest import ROOT
 from stmask_amd import _lib, ops
 
-
-def _header_text():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "stmask_hip.h")).read(), flags=re.S)
-
-
-def _header_symbols():
-    return sorted(set(re.findall(r"\b(stm_[a-z0-9_]+)\s*\(", _header_text())))
-
-
-_C_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "long long": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double,
-            "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p}
-
-
-def _header_prototypes():
-    """{name: (restype, [argtypes])} of every `ret stm_name(params);` of the header.  A `*` or `[` anywhere in a parameter, or the type
-    stm_stream_t, makes it a pointer; every other parameter is `type name` with type one of the six scalar kinds."""
-    protos = {}
-    for ret, name, params in re.findall(r"^[ \t]*([A-Za-z_][A-Za-z0-9_ ]*?\**)\s*\b(stm_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header_text(), flags=re.M):
-        args = []
-        for p in ([] if params.strip() in ("", "void") else params.split(",")):
-            words = p.split()
-            pointer = "*" in p or "[" in p or words[0] == "stm_stream_t"
-            args.append(ctypes.c_void_p if pointer else _C_TYPES[" ".join(words[:-1])])
-        assert name not in protos, name
-        protos[name] = (_C_TYPES[" ".join(ret.split())], args)
-    return protos
+# What every header declares, in the order of _lib.HEADERS: how many entries, and (but for the first header's 128) which.  The one place these live.
+EXPECTED = {
+    "stmask_hip.h": (128, None),
+    "stmask_hip_output.h": (3, ["stm_output_stage_multi_f32", "stm_output_stage_workspace_bytes", "stm_output_struct_bytes"]),
+    "stmask_hip_tracker.h": (2, ["stm_track_drop_plan", "stm_track_resolve_tf"]),
+    "stmask_hip_train.h": (8, ["stm_lincomb_rows_proto_backward_f32", "stm_lincomb_rows_proto_backward_workspace_bytes", "stm_mbox_gather_f32",
+                               "stm_mbox_positives", "stm_mbox_reduce_backward_f32", "stm_mbox_reduce_f32", "stm_mbox_scatter_coeff_f32",
+                               "stm_mbox_workspace_bytes"]),
+    "stmask_hip_eval.h": (4, ["stm_vis_match", "stm_vis_rle_check", "stm_vis_rle_decode", "stm_vis_tube_iou"]),
+    "stmask_hip_t2s_feat.h": (2, ["stm_t2s_feat_backward_f32", "stm_t2s_feat_forward_f32"]),
+    "stmask_hip_data.h": (5, ["stm_data_boxes_f32", "stm_data_frames_u8_f32", "stm_data_masks_u8", "stm_data_rle_starts", "stm_data_struct_bytes"]),
+}
+# mirror -> sizeof, where a size is part of the contract (ConvWindow is passed as an array: the size is the stride)
+STRUCT_SIZES = {"ConvWindow": 32, "OutputFrame": 32, "OutputRow": 48, "OutputHeader": 16, "DataFrameDesc": 32, "DataMaskDesc": 16}
+# mirror -> (header, struct) whose field names, in the header's order, are the mirror's
+STRUCT_FIELDS = {"OutputFrame": ("stmask_hip_output.h", "stm_output_frame"), "OutputRow": ("stmask_hip_output.h", "stm_output_row"),
+                 "OutputHeader": ("stmask_hip_output.h", "stm_output_header"), "DataFrameDesc": ("stmask_hip_data.h", "stm_data_frame_desc"),
+                 "DataMaskDesc": ("stmask_hip_data.h", "stm_data_mask_desc")}
 
 
-def test_header_and_signature_table_agree():
-    """Every argument of every entry point: the table lib() takes restype / argtypes from says what include/stmask_hip.h says."""
-    assert _header_symbols() == sorted(_lib.ABI_SYMBOLS)
+def test_headers_tables_and_expectations_are_the_same_list():
+    assert list(_lib.HEADERS) == list(EXPECTED) == ["stmask_hip" + s + ".h" for s in ("", "_output", "_tracker", "_train", "_eval", "_t2s_feat", "_data")]
+    assert sorted(_lib.HEADERS) == sorted(os.listdir(os.path.join(ROOT, "include")))          # a header nobody binds fails here
+    tables = [_lib.SIGNATURES, _lib.OUTPUT_SIGNATURES, _lib.TRACKER_SIGNATURES, _lib.TRAIN_SIGNATURES, _lib.EVAL_SIGNATURES, _lib.T2S_FEAT_SIGNATURES,
+              _lib.DATA_SIGNATURES]
+    assert all(a is b for a, b in zip(_lib.HEADERS.values(), tables))                         # the module-level names are the tables lib() reads
     assert _lib.ABI_SYMBOLS == list(_lib.SIGNATURES)
-    protos = _header_prototypes()
-    assert len(protos) == len(_lib.SIGNATURES) == 128         # a prototype the expression misses fails here instead of skipping a function
-    lib = _lib.lib()
-    for name in _lib.SIGNATURES:
-        ret, args = protos[name]
-        fn = getattr(lib, name)
-        assert fn.restype == ret, (name, fn.restype, ret)
-        assert len(fn.argtypes) == len(args), (name, len(fn.argtypes), len(args))
-        for i, (got, want) in enumerate(zip(fn.argtypes, args)):
-            assert got == want, (name, i, got, want)
+    merged = _lib.all_signatures()
+    assert len(merged) == sum(count for count, _ in EXPECTED.values()) and list(merged) == [n for t in tables for n in t]
+
+
+@pytest.mark.parametrize("header", list(_lib.HEADERS))
+def test_header_and_signature_table_agree(header):
+    """Every argument of every entry point: the table lib() takes restype / argtypes from says what the header says."""
+    assert_table_matches_header(header, _lib.HEADERS[header])
+
+
+@pytest.mark.parametrize("header", list(EXPECTED))
+def test_header_declares_what_is_expected(header):
+    count, names = EXPECTED[header]
+    table = _lib.HEADERS[header]
+    assert len(table) == len(header_symbols(header)) == count
+    if names is not None:
+        assert sorted(table) == header_symbols(header) == names and len(names) == count
+    else:   # the first header: one prototype per line that starts with one of its return types
+        assert len(re.findall(r"^[ \t]*(?:int|size_t|void|long long|const char\*)\s+stm_[a-z0-9_]+\s*\(", header_raw(header), flags=re.M)) == count
+
+
+@pytest.mark.parametrize("header", list(_lib.HEADERS))
+def test_no_entry_is_named_in_another_header(header):
+    """Every entry belongs to one table and one header.  A newer header may mention an older entry in a comment; nothing else names another
+    header's entry."""
+    order = list(_lib.HEADERS)
+    for other in order:
+        if other == header:
+            continue
+        assert not set(_lib.HEADERS[header]) & set(_lib.HEADERS[other]), (header, other)
+        text = header_raw(other) if order.index(other) < order.index(header) else header_text(other)
+        assert not [name for name in _lib.HEADERS[header] if name in text], (header, other)
+
+
+def test_abi_version_is_six_everywhere():
+    assert _lib.lib().stm_version() == 6 == _lib.ABI_VERSION == int(re.search(r"#define STM_ABI_VERSION (\d+)", header_raw("stmask_hip.h")).group(1))
+
+
+@pytest.mark.parametrize("header", list(_lib.HEADERS))
+def test_a_library_without_an_entry_of_a_table_is_refused(header, monkeypatch):
+    """lib() walks every table and lists the entries a stale library lacks: an StmError at load, not an AttributeError at the first call."""
+    name = "stm_%s_not_there" % (header[len("stmask_hip_"):-2] or "first")
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setitem(_lib.HEADERS[header], name, ("i", "p"))
+    with pytest.raises(_lib.StmError) as e:
+        _lib.lib()
+    assert name in str(e.value) and "rebuild" in str(e.value)
+    monkeypatch.undo()
+    assert _lib.lib() is not None
+
+
+@pytest.mark.parametrize("size_fn", list(_lib.STRUCTS))
+def test_struct_layouts_of_binding_and_library_agree(size_fn):
+    """A client built against another header revision passes a struct of another size: the *_struct_bytes functions let it find out
+    (stm_conv_geom grew a trailing field in round 2 while the version stayed 1)."""
+    mirrors = _lib.STRUCTS[size_fn]
+    fn = getattr(ctypes.CDLL(_lib.LIB_PATH), size_fn)
+    fn.restype = ctypes.c_size_t
+    for i, mirror in enumerate(mirrors):
+        assert fn(i) == ctypes.sizeof(mirror) == STRUCT_SIZES.get(mirror.__name__, ctypes.sizeof(mirror)), (size_fn, i, mirror.__name__)
+        if mirror.__name__ in STRUCT_FIELDS:
+            assert struct_field_names(*STRUCT_FIELDS[mirror.__name__]) == [f[0] for f in mirror._fields_], mirror.__name__
+    assert fn(len(mirrors)) == 0 and fn(7) == 0
+
+
+def test_every_pinned_struct_is_checked():
+    checked = [m.__name__ for mirrors in _lib.STRUCTS.values() for m in mirrors]
+    assert checked == ["DeformGeom", "ConvGeom", "ConvWindow", "HeadLayout", "FrameDesc", "RenderFrame", "OutputFrame", "OutputRow", "OutputHeader",
+                       "DataFrameDesc", "DataMaskDesc"]
+    assert set(STRUCT_SIZES) | set(STRUCT_FIELDS) <= set(checked)
 
 
 def test_counts_keep_their_width():
@@ -74,25 +131,12 @@ def test_type_and_arity_errors_are_python_errors():
 def test_library_loads_and_exports_every_symbol():
     _lib.build()
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in _header_symbols():
-        assert hasattr(lib, name), f"{name} declared in include/stmask_hip.h but not exported"
+    for header in _lib.HEADERS:
+        for name in header_symbols(header):
+            assert hasattr(lib, name), f"{name} declared in include/{header} but not exported"
     lib.stm_version.restype = ctypes.c_int
     assert lib.stm_version() == _lib.ABI_VERSION
-    header = open(os.path.join(ROOT, "include", "stmask_hip.h")).read()
-    assert int(re.search(r"#define STM_ABI_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION
-
-
-def test_struct_layouts_of_binding_and_library_agree():
-    """A client built against another header revision passes a struct of another size: stm_struct_bytes lets it find out
-    (stm_conv_geom grew a trailing field in round 2 while the version stayed 1)."""
-    _lib.build()
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    lib.stm_struct_bytes.restype = ctypes.c_size_t
-    assert lib.stm_struct_bytes(0) == ctypes.sizeof(_lib.DeformGeom)
-    assert lib.stm_struct_bytes(1) == ctypes.sizeof(_lib.ConvGeom)
-    assert lib.stm_struct_bytes(2) == ctypes.sizeof(_lib.ConvWindow) == 32         # passed as an array: the size is the stride
-    assert lib.stm_struct_bytes(3) == ctypes.sizeof(_lib.HeadLayout)
-    assert lib.stm_struct_bytes(7) == 0
+    assert int(re.search(r"#define STM_ABI_VERSION (\d+)", header_raw("stmask_hip.h")).group(1)) == _lib.ABI_VERSION
 
 
 def test_library_targets_gfx950():
