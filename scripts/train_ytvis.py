@@ -1,25 +1,42 @@
 #!/usr/bin/env python3
-"""Train on a YouTube-VIS / OVIS annotation file and its folder of frames: stmask_amd.datasets (YTVISTrainSet, TrainLoader) -> NetLoss -> SGD with
-the reference's defaults (lr 1e-3, momentum 0.9, weight decay 1e-4, gamma 0.1, lr_steps 150000 / 200000, warm-up from 1e-4 over 500 iterations,
-250000 iterations: config.py:397-415, :625), train.lr_at each iteration, the loss terms printed every 10 iterations (the one host read of the loop:
-the criterion runs with max_pos, the loader defers its status check).  No DataParallel, no logging beyond the print, no checkpoints.
-    python scripts/train_ytvis.py ANN IMG_PREFIX [--config STMask_plus_resnet50_config] [--batch_size 4] [--iters 250000] [--backbone PATH]"""
+"""Train on a YouTube-VIS / OVIS annotation file and its folder of frames: stmask_amd.datasets (YTVISTrainSet, TrainLoader) -> NetLoss ->
+optim.GuardedSGD with the reference's defaults (lr 1e-3, momentum 0.9, weight decay 1e-4, gamma 0.1, lr_steps 150000 / 200000, warm-up from 1e-4
+over 500 iterations, 250000 iterations: config.py:397-415, :625), train.lr_at each iteration.  A run that can be left alone:
+  - a batch whose loss (--guard loss) or whose gradients (--guard grads) are not finite is skipped on the device and counted, where the reference
+    waits for torch.isfinite(loss).item() in every iteration (train.py:314-316); --guard off always applies;
+  - the loss terms go to a train.LossLog on the device every iteration and are read every 10 iterations for the printed line (last value and the
+    mean over the last 100 finite values, the reference's MovingAverage) -- the one host read of the loop: the criterion runs with max_pos, the
+    loader defers its status check.  --log FILE adds one JSON line per iteration, written at those reads;
+  - weights are saved under the reference's names, {config name}_{epoch}_{iteration}.pth in --save_folder, every --save_interval iterations and at
+    the end, with the optimizer / loader state beside them (stmask_amd.checkpoint); --keep_latest deletes the previous save as the reference does;
+    Ctrl-C writes ..._{iteration}_interrupt.pth.  The reference saves at the interval only from epoch 7 on (train.py:353); that condition is not
+    reproduced: every interval saves;
+  - --resume PATH|latest|interrupt continues such a run, bit for bit when the sidecar is there; with a bare .pth it is the reference's resume
+    (weights only, --start_iter -1 takes the iteration from the file name).
+No DataParallel, no ExtraAugmentation, no validation-mAP hook.
+    python scripts/train_ytvis.py ANN IMG_PREFIX [--config STMask_plus_resnet50_config] [--batch_size 4] [--iters 250000] [--backbone PATH]
+                                  [--save_folder weights/] [--resume latest] [--guard loss] [--log train.jsonl]"""
 import argparse
+import json
 import math
 import os
 import sys
+import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from stmask_amd import datasets, layers  # noqa: E402
+from stmask_amd import checkpoint, datasets, layers  # noqa: E402
 from stmask_amd.config import get_cfg  # noqa: E402
 from stmask_amd.model import STMask  # noqa: E402
-from stmask_amd.train import NetLoss, autoscale, lr_at, train_step  # noqa: E402
+from stmask_amd.optim import GuardedSGD  # noqa: E402
+from stmask_amd.train import LossLog, NetLoss, autoscale, lr_at, train_step  # noqa: E402
+
+READ_EVERY = 10
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("ann")
     ap.add_argument("img_prefix")
@@ -37,7 +54,20 @@ def main():
     ap.add_argument("--max_pos", type=int, default=4096, help="row capacity of the criterion's positive lists: no host read inside the step")
     ap.add_argument("--backbone", default=None, help="backbone weights for init_weights (a state dict file)")
     ap.add_argument("--seed", type=int, default=0)
-    args = ap.parse_args()
+    ap.add_argument("--save_folder", default="weights/", help="where checkpoints are written and where --resume latest|interrupt looks")
+    ap.add_argument("--save_interval", type=int, default=10000, help="iterations between checkpoints (0: only at the end)")
+    ap.add_argument("--keep_latest", action="store_true", help="delete the previous checkpoint after each save")
+    ap.add_argument("--keep_latest_interval", type=int, default=100000,
+                    help="with --keep_latest, keep the saves at these intervals (a multiple of --save_interval, or 0)")
+    ap.add_argument("--resume", default=None, help="a checkpoint file, 'latest' or 'interrupt'")
+    ap.add_argument("--start_iter", type=int, default=-1, help="iteration to resume at; -1 takes it from the checkpoint")
+    ap.add_argument("--guard", choices=["loss", "grads", "off"], default="loss", help="what makes the optimizer skip a step, on the device")
+    ap.add_argument("--log", default=None, help="a file of one JSON line per iteration (appended to when resuming)")
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
     dev = "cuda:0"
     lr, max_iter, lr_steps = (autoscale(args.lr, args.iters, args.lr_steps, args.batch_size) if args.autoscale
                               else (args.lr, args.iters, args.lr_steps))
@@ -49,24 +79,97 @@ def main():
     net = net.to(dev).train()
     crit = layers.MultiBoxLoss(cfg.num_classes, 0.5, 0.4, 3, temporal_fusion=cfg.temporal_fusion_module, max_pos=args.max_pos)
     net_loss = NetLoss(net, crit)
-    opt = torch.optim.SGD(net.parameters(), lr=lr, momentum=args.momentum, weight_decay=args.decay)
+    opt = GuardedSGD(net.parameters(), lr=lr, momentum=args.momentum, weight_decay=args.decay, guard=None if args.guard == "off" else args.guard)
     loader = datasets.TrainLoader(datasets.YTVISTrainSet(args.ann, args.img_prefix), args.batch_size, seed=args.seed, device=dev)
     if len(loader) == 0:
         raise SystemExit(f"{len(loader.dataset)} frame pairs do not fill one batch of {args.batch_size}")
     print(f"{len(loader.dataset)} frame pairs, {len(loader)} iterations per epoch, {math.ceil(max_iter / len(loader))} epochs")
+    os.makedirs(args.save_folder, exist_ok=True)
+
     iteration = 0
-    while iteration < max_iter:
-        for batch in loader:
-            if iteration >= max_iter:
-                break
-            cur = lr_at(iteration, lr, args.gamma, lr_steps, args.lr_warmup_until, args.lr_warmup_init)
-            for group in opt.param_groups:
-                group["lr"] = cur
-            losses = train_step(net_loss, opt, batch)
-            if iteration % 10 == 0:
-                vals = {k: v.item() for k, v in losses.items()}
-                print(f"iter {iteration} lr {cur:.3e}: " + "  ".join(f"{k} {v:.4f}" for k, v in vals.items()) + f"  sum {sum(vals.values()):.4f}")
-            iteration += 1
+    resume = args.resume
+    if resume == "interrupt":
+        resume = checkpoint.get_interrupt(args.save_folder)
+    elif resume == "latest":
+        resume = checkpoint.get_latest(args.save_folder, cfg.name)
+    if resume is not None:
+        got = checkpoint.load(resume, net, opt, loader)
+        iteration = got["iteration"] if args.start_iter < 0 else args.start_iter
+        if not got["sidecar"]:
+            # the reference's resume: the weights alone; the loader continues in the epoch the iteration falls into
+            loader.load_state({"seed": args.seed, "epoch": iteration // len(loader), "batch": iteration % len(loader)})
+        print(f"resumed {resume} at iteration {iteration}" + ("" if got["sidecar"] else " (weights only: momentum starts at zero)"))
+    elif args.start_iter > 0:
+        iteration = args.start_iter
+    elif args.resume is not None:
+        print(f"--resume {args.resume}: nothing to resume in {args.save_folder}, starting at iteration 0")
+
+    log_file = open(args.log, "a" if resume is not None else "w") if args.log else None
+    loss_log, pending, skipped_seen = None, [], opt.counters()[1]
+    last_time = time.time()
+
+    def flush():
+        """The loop's host read: the rows of the LossLog since the last one -> the printed line, the JSON lines, the skipped count."""
+        nonlocal skipped_seen
+        if loss_log is None or not pending:
+            return
+        stats = loss_log.read()
+        if log_file:
+            for (it, ep, cur, elapsed), row in zip(pending, loss_log.rows):
+                log_file.write(json.dumps({"type": "train", "iter": it, "epoch": ep, "lr": round(cur, 10),
+                                           "loss": {k: round(v, 5) if math.isfinite(v) else repr(v) for k, v in zip(loss_log.names, row)},
+                                           "elapsed": elapsed}) + "\n")
+            log_file.flush()
+        it, ep, cur, elapsed = pending[-1]
+        print(f"[{ep:3d}] {it:7d} || " + " | ".join(f"{k}: {avg:.3f}" for k, (_, avg) in stats.items()) + f" || lr {cur:.3e} || timer: {elapsed:.3f}",
+              flush=True)
+        skipped = opt.counters()[1]
+        if skipped > skipped_seen:
+            print(f"guard: {skipped - skipped_seen} step(s) skipped since the last line, {skipped} in all", flush=True)
+            skipped_seen = skipped
+        pending.clear()
+
+    def save(path):
+        flush()
+        print(f"saving {path}", flush=True)
+        checkpoint.save(path, net, opt, iteration, epoch, loader)
+
+    epoch = loader.state()["epoch"]
+    try:
+        while iteration < max_iter:
+            epoch = loader.state()["epoch"]
+            for batch in loader:
+                if iteration >= max_iter:
+                    break
+                cur = lr_at(iteration, lr, args.gamma, lr_steps, args.lr_warmup_until, args.lr_warmup_init)
+                for group in opt.param_groups:
+                    group["lr"] = cur
+                losses = train_step(net_loss, opt, batch)
+                if loss_log is None:
+                    loss_log = LossLog(list(losses), capacity=4 * READ_EVERY)
+                loss_log.append(losses)
+                now = time.time()
+                pending.append((iteration, epoch, cur, now - last_time))
+                last_time = now
+                if iteration % READ_EVERY == 0:
+                    flush()
+                iteration += 1
+                if args.save_interval > 0 and iteration % args.save_interval == 0 and iteration < max_iter:
+                    latest = checkpoint.get_latest(args.save_folder, cfg.name) if args.keep_latest else None
+                    path = checkpoint.save_path(cfg.name, epoch, iteration, args.save_folder)
+                    save(path)
+                    if latest is not None and latest != path and (args.keep_latest_interval <= 0 or
+                                                                  iteration % args.keep_latest_interval != args.save_interval):
+                        print(f"deleting {latest}", flush=True)
+                        checkpoint.remove(latest)
+    except KeyboardInterrupt:
+        print("interrupted: saving", flush=True)
+        checkpoint.remove_interrupt(args.save_folder)
+        save(checkpoint.save_path(cfg.name, epoch, iteration, args.save_folder, interrupt=True))
+        raise SystemExit(130)
+    save(checkpoint.save_path(cfg.name, epoch, iteration, args.save_folder))
+    if log_file:
+        log_file.close()
 
 
 if __name__ == "__main__":

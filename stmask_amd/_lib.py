@@ -208,6 +208,14 @@ HEADERS = {
     "stmask_hip_data.h": DATA_SIGNATURES,
 }
 
+# Package-private entry points of the same library: declared in csrc/optim.h, not under include/, so HEADERS, all_signatures() and ABI_VERSION do
+# not count them (an optimizer step is nothing a C client of the drop-in boundary calls).  private_call() binds them on first use.
+PRIVATE_SIGNATURES = {
+    "stm_sgd_step_multi_f32": ("i", "ppppipppifffp"),
+    "stm_grads_nonfinite_multi_f32": ("i", "ppipip"),
+}
+_private_calls = {}   # name -> (function, argument count) for private_call()
+
 
 def all_signatures():
     """{name: (return kind, parameter kinds)} of every header, read from the tables as they are now."""
@@ -329,6 +337,24 @@ def call(name, *args):
     if _lib is None:
         lib()
     fn, n = _calls[name]
+    if len(args) != n:
+        raise StmError(f"{name} takes {n} arguments, got {len(args)}")
+    rc = fn(*args)
+    if rc != 0:
+        check(rc, name)
+
+
+def private_call(name, *args):
+    """call() for an entry of PRIVATE_SIGNATURES: restype / argtypes are set from the table when the entry is first used."""
+    got = _private_calls.get(name)
+    if got is None:
+        ret, params = PRIVATE_SIGNATURES[name]
+        fn = getattr(lib(), name, None)
+        if fn is None:
+            raise StmError(f"{LIB_PATH} lacks {name}: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")
+        fn.restype, fn.argtypes = _KINDS[ret], [_KINDS[k] for k in params]
+        got = _private_calls[name] = (fn, len(params))
+    fn, n = got
     if len(args) != n:
         raise StmError(f"{name} takes {n} arguments, got {len(args)}")
     rc = fn(*args)

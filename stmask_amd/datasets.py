@@ -385,13 +385,34 @@ class TrainLoader:
     """An epoch of batches: torch.randperm with a seeded generator (seed + epoch), the last short batch dropped (len(dataset) // batch_size, the
     reference's epoch_size).  No threads and no worker processes: next() reads and collates batch k + 1 on the host while the device still runs
     the step the caller queued for batch k.  Batches are collated with check="deferred"; the status of batch k is looked at when batch k + 1 is
-    asked for (and that of the last batch when the epoch ends), so a loop with max_pos=K never waits for the device here."""
+    asked for (and that of the last batch when the epoch ends), so a loop with max_pos=K never waits for the device here.
+    state() is where the run stands -- seed, epoch, batches of that epoch already handed out -- and the next __iter__ after load_state(state)
+    continues there: the order is a pure function of seed + epoch, and the records of the batches passed over are neither read nor collated."""
 
     def __init__(self, dataset, batch_size, shuffle=True, seed=0, device=None, max_gt=None):
         if batch_size < 1:
             raise ValueError(f"TrainLoader: batch_size={batch_size}")
         self.dataset, self.batch_size, self.shuffle, self.seed, self.device, self.max_gt = dataset, int(batch_size), shuffle, seed, device, max_gt
         self.epoch = 0
+        self.batch = 0          # batches of the running epoch (self.epoch - 1) handed out so far
+        self._resume = None     # (epoch, batch) load_state asked the next __iter__ to continue at
+
+    def state(self):
+        """Inside an epoch: that epoch and the batches handed out.  After its last batch (or before the first epoch): the next epoch, batch 0."""
+        if self._resume is not None:
+            epoch, batch = self._resume
+        elif self.epoch > 0 and self.batch < len(self):
+            epoch, batch = self.epoch - 1, self.batch
+        else:
+            epoch, batch = self.epoch, 0
+        return {"seed": self.seed, "epoch": epoch, "batch": batch}
+
+    def load_state(self, state):
+        epoch, batch = int(state["epoch"]), int(state["batch"])
+        if epoch < 0 or not 0 <= batch <= len(self):
+            raise ValueError(f"TrainLoader.load_state: epoch={epoch} batch={batch}, an epoch has {len(self)} batches")
+        self.seed = state["seed"]
+        self.epoch, self.batch, self._resume = epoch, 0, (epoch, batch)
 
     def __len__(self):
         return len(self.dataset) // self.batch_size
@@ -405,10 +426,15 @@ class TrainLoader:
         return torch.randperm(n, generator=g).tolist()
 
     def __iter__(self):
+        first = 0
+        if self._resume is not None:
+            (self.epoch, first), self._resume = self._resume, None
         order = self.order(self.epoch)
         self.epoch += 1
+        self.batch = first
         pending = None
-        for k in range(len(self)):
+        for k in range(first, len(self)):
+            self.batch = k + 1
             records = [self.dataset[i] for i in order[k * self.batch_size:(k + 1) * self.batch_size]]
             *batch, status = collate_device(records, self.device, self.max_gt, check="deferred")
             if pending is not None:

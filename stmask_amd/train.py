@@ -1,8 +1,14 @@
 """The reference's training step (train.py:134-150, :290-320) over this package: NetLoss ties the train-mode STMask.forward to layers.MultiBoxLoss,
 train_step runs one optimizer step; lr_at and autoscale restate its learning-rate schedule (train.py:88-96, :293-302) as pure functions.  The
 batches come from stmask_amd.datasets (YTVISTrainSet, TrainLoader, collate_device) or synthetic.synthetic_train_batch; scripts/train_ytvis.py
-puts the pieces together.  ExtraAugmentation, DataParallel, logging and checkpoints are not built."""
+puts the pieces together with optim.GuardedSGD (the step guarded on the device), LossLog below and stmask_amd.checkpoint.  ExtraAugmentation,
+DataParallel and the validation-mAP hook are not built."""
+import math
+
+import torch
 import torch.nn as nn
+
+from .optim import GuardedSGD
 
 
 class NetLoss(nn.Module):
@@ -20,12 +26,62 @@ class NetLoss(nn.Module):
 
 def train_step(net_loss, optimizer, batch):
     """One step on batch = (images, gt_bboxes, gt_labels, gt_masks, gt_ids[, img_meta]): zero the gradients, forward, backward through the sum of
-    the loss terms, optimizer step.  Returns the dict of loss terms (detached 0-dim device tensors: reading them is the caller's synchronisation)."""
+    the loss terms, optimizer step.  A GuardedSGD is handed that sum: it skips the update on the device when the loss (or, with guard="grads", a
+    gradient) is not finite.  Returns the dict of loss terms (detached 0-dim device tensors: reading them is the caller's synchronisation)."""
     optimizer.zero_grad()
     losses = net_loss(*batch)
-    sum(losses.values()).backward()
-    optimizer.step()
+    total = sum(losses.values())
+    total.backward()
+    if isinstance(optimizer, GuardedSGD):
+        optimizer.step(total.detach())
+    else:
+        optimizer.step()
     return {k: v.detach() for k, v in losses.items()}
+
+
+class LossLog:
+    """The loss terms of the last iterations in a ring [capacity, len(keys) + 1] on the device of the first append (last column: their sum).
+    append() is one stack and one row copy, no host wait; read() fetches the rows appended since the last read() in one transfer and returns
+    {key: (last value, mean over the last `window` finite values)}, plus "Total" -- the reference's MovingAverage(100) (utils/functions.py), which
+    ignores values that are not finite.  A mean over no finite value yet is NaN.  `rows` holds what the last read() fetched: one list per append, in
+    the order of `names` (the keys, then "Total")."""
+
+    def __init__(self, keys, capacity=1024, window=100):
+        if capacity < 1 or window < 1 or not keys:
+            raise ValueError(f"LossLog: keys={keys!r} capacity={capacity} window={window}")
+        self.keys, self.capacity, self.window = list(keys), int(capacity), int(window)
+        self.names = self.keys + ["Total"]
+        self.ring = None
+        self.appended = self.fetched = 0
+        self.last = [math.nan] * len(self.names)
+        self.rows = []
+        self.recent = [[] for _ in self.names]       # the last `window` finite values of each column
+
+    def append(self, losses):
+        terms = [losses[k].detach().reshape(()) for k in self.keys]
+        row = torch.stack(terms + [sum(terms)])               # the sum in train_step's order: the value the guard saw
+        if self.ring is None:
+            self.ring = torch.zeros(self.capacity, len(self.names), dtype=row.dtype, device=row.device)
+        self.ring[self.appended % self.capacity] = row
+        self.appended += 1
+
+    def read(self):
+        n = self.appended - self.fetched
+        if n > self.capacity:
+            raise RuntimeError(f"LossLog.read: {n} rows appended since the last read, the ring holds {self.capacity}: the oldest are overwritten")
+        self.rows = []
+        if n:
+            at = torch.arange(self.fetched, self.appended) % self.capacity
+            rows = self.ring[at.to(self.ring.device)].cpu().tolist()
+            self.fetched = self.appended
+            for row in rows:
+                for c, v in enumerate(row):
+                    if math.isfinite(v):
+                        self.recent[c].append(v)
+                        del self.recent[c][:-self.window]
+            self.last, self.rows = rows[-1], rows
+        return {name: (self.last[c], sum(self.recent[c]) / len(self.recent[c]) if self.recent[c] else math.nan)
+                for c, name in enumerate(self.names)}
 
 
 def lr_at(iteration, lr, gamma, lr_steps, lr_warmup_until, lr_warmup_init):
