@@ -13,9 +13,12 @@ over 500 iterations, 250000 iterations: config.py:397-415, :625), train.lr_at ea
     reproduced: every interval saves;
   - --resume PATH|latest|interrupt continues such a run, bit for bit when the sidecar is there; with a bare .pth it is the reference's resume
     (weights only, --start_iter -1 takes the iteration from the file name).
-No DataParallel, no ExtraAugmentation, no validation-mAP hook.
+  - --extra_aug photo,expand,crop (any subset) turns the reference's ExtraAugmentation on, with the settings its training configs carry: the
+    parameters are drawn on the host, the pixels are augmented inside the batch kernels.  The numpy RNG state is not
+    part of a checkpoint: a resumed run continues with fresh draws, as the flip does.
+No DataParallel, no validation-mAP hook.
     python scripts/train_ytvis.py ANN IMG_PREFIX [--config STMask_plus_resnet50_config] [--batch_size 4] [--iters 250000] [--backbone PATH]
-                                  [--save_folder weights/] [--resume latest] [--guard loss] [--log train.jsonl]"""
+                                  [--save_folder weights/] [--resume latest] [--guard loss] [--log train.jsonl] [--extra_aug photo,expand,crop]"""
 import argparse
 import json
 import math
@@ -29,8 +32,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from stmask_amd import checkpoint, datasets, layers  # noqa: E402
 from stmask_amd.config import get_cfg  # noqa: E402
+from stmask_amd.extra_aug import config_from_names  # noqa: E402
 from stmask_amd.model import STMask  # noqa: E402
 from stmask_amd.optim import GuardedSGD  # noqa: E402
+from stmask_amd.preprocess import MEANS  # noqa: E402
 from stmask_amd.train import LossLog, NetLoss, autoscale, lr_at, train_step  # noqa: E402
 
 READ_EVERY = 10
@@ -62,6 +67,7 @@ def parse_args(argv=None):
     ap.add_argument("--resume", default=None, help="a checkpoint file, 'latest' or 'interrupt'")
     ap.add_argument("--start_iter", type=int, default=-1, help="iteration to resume at; -1 takes it from the checkpoint")
     ap.add_argument("--guard", choices=["loss", "grads", "off"], default="loss", help="what makes the optimizer skip a step, on the device")
+    ap.add_argument("--extra_aug", default="", help="comma list of photo, expand, crop: ExtraAugmentation with the reference's settings for each")
     ap.add_argument("--log", default=None, help="a file of one JSON line per iteration (appended to when resuming)")
     return ap.parse_args(argv)
 
@@ -80,7 +86,8 @@ def main():
     crit = layers.MultiBoxLoss(cfg.num_classes, 0.5, 0.4, 3, temporal_fusion=cfg.temporal_fusion_module, max_pos=args.max_pos)
     net_loss = NetLoss(net, crit)
     opt = GuardedSGD(net.parameters(), lr=lr, momentum=args.momentum, weight_decay=args.decay, guard=None if args.guard == "off" else args.guard)
-    loader = datasets.TrainLoader(datasets.YTVISTrainSet(args.ann, args.img_prefix), args.batch_size, seed=args.seed, device=dev)
+    extra_aug = config_from_names(args.extra_aug, MEANS)
+    loader = datasets.TrainLoader(datasets.YTVISTrainSet(args.ann, args.img_prefix, extra_aug=extra_aug), args.batch_size, seed=args.seed, device=dev)
     if len(loader) == 0:
         raise SystemExit(f"{len(loader.dataset)} frame pairs do not fill one batch of {args.batch_size}")
     print(f"{len(loader.dataset)} frame pairs, {len(loader)} iterations per epoch, {math.ceil(max_iter / len(loader))} epochs")

@@ -214,6 +214,16 @@ PRIVATE_SIGNATURES = {
     "stm_sgd_step_multi_f32": ("i", "ppppipppifffp"),
     "stm_grads_nonfinite_multi_f32": ("i", "ppipip"),
 }
+# ... and those of csrc/extra_aug.h: ExtraAugmentation inside the training-batch kernels (datasets.py).  A second private table, so that
+# PRIVATE_SIGNATURES stays the restatement of csrc/optim.h alone; private_call() resolves both.
+AUG_SIGNATURES = {
+    "stm_aug_struct_bytes": ("z", "i"),
+    "stm_aug_frames_u8_f32": ("i", "ppipiiiippip"),
+    "stm_aug_masks_u8": ("i", "pppipppiilpiiiip"),
+    "stm_aug_source_u8": ("i", "pppp"),
+}
+PRIVATE_TABLES = {"optim.h": PRIVATE_SIGNATURES, "extra_aug.h": AUG_SIGNATURES}   # header under csrc/ -> its table
+AUG_FRAMES_PER_LAUNCH = 64   # csrc/extra_aug.h STM_AUG_FRAMES_PER_LAUNCH
 _private_calls = {}   # name -> (function, argument count) for private_call()
 
 
@@ -282,6 +292,15 @@ class HeadLayout(ctypes.Structure):
                 [("lvl_start", c_i * 8), ("lvl_hw", c_i * 8)])
 
 
+class AugDesc(ctypes.Structure):
+    """stm_aug_desc of csrc/extra_aug.h (package-private: its size is checked against stm_aug_struct_bytes(0) where it is first used and in
+    tests/test_extra_aug_cpu.py, not through STRUCTS)."""
+    _fields_ = ([("ptr", c_p), ("row_stride_bytes", c_l), ("H0", c_i), ("W0", c_i), ("flip", c_i), ("photo", c_i)] +
+                [(n, c_f) for n in ("delta", "alpha_pre", "saturation", "hue", "alpha_post")] + [("perm", c_i * 3)] +
+                [(n, c_i) for n in ("Hc", "Wc", "top", "left")] + [("fill", c_f * 3)] +
+                [(n, c_i) for n in ("x0", "y0", "x1", "y1", "cast_clip")])
+
+
 # size function of the library -> the mirrors of the structs it knows, by index: lib() refuses a library whose sizes differ
 STRUCTS = {
     "stm_struct_bytes": [DeformGeom, ConvGeom, ConvWindow, HeadLayout, FrameDesc, RenderFrame],
@@ -345,10 +364,10 @@ def call(name, *args):
 
 
 def private_call(name, *args):
-    """call() for an entry of PRIVATE_SIGNATURES: restype / argtypes are set from the table when the entry is first used."""
+    """call() for an entry of PRIVATE_SIGNATURES or AUG_SIGNATURES: restype / argtypes are set from the table when the entry is first used."""
     got = _private_calls.get(name)
     if got is None:
-        ret, params = PRIVATE_SIGNATURES[name]
+        ret, params = PRIVATE_SIGNATURES[name] if name in PRIVATE_SIGNATURES else AUG_SIGNATURES[name]
         fn = getattr(lib(), name, None)
         if fn is None:
             raise StmError(f"{LIB_PATH} lacks {name}: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")

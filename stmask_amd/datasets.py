@@ -9,8 +9,9 @@ masks drawn straight from their run lengths at the target size, boxes transforme
 INTEGRATION.md section 20 is the contract.  There is no CPU fallback for the device part.
 
 Scope: the reference's training configs -- img_scale=[(640, 360)], resize_keep_ratio=False, size_divisor=32, flip_ratio=0.5, to_rgb=True,
-with_track=True, clip_frames=1, extra_aug=None.  Not built: ExtraAugmentation, aug_ref_bbox_param, proposals, keep_ratio=True, more than one
-img_scale, DataParallel, logging, checkpoints.
+with_track=True, clip_frames=1, and extra_aug=None or the reference's dict: ExtraAugmentation's parameters are drawn on the host (extra_aug.py)
+and its pixel work is done inside the frame and mask kernels (csrc/extra_aug.hip).  Not built: aug_ref_bbox_param,
+proposals, keep_ratio=True, more than one img_scale, DataParallel.
 """
 import ctypes
 import os
@@ -20,7 +21,9 @@ import numpy as np
 import torch
 
 from . import _lib, vis_eval
-from ._lib import StmError, c_p, call
+from . import extra_aug as _extra_aug
+from ._lib import StmError, c_p, call, private_call
+from .extra_aug import AugParams, ExtraAugmentation  # noqa: F401  (part of this module's interface)
 from .preprocess import MEANS, STD
 
 # launches of the stm_data_* / stm_vis_rle_decode entry points and bytes copied to the device since the last reset_counters()
@@ -36,6 +39,11 @@ def reset_counters():
 def _launch(name, launches, *args):
     COUNTERS["launches"] += launches
     call(name, *args)
+
+
+def _launch_private(name, launches, *args):
+    COUNTERS["launches"] += launches
+    private_call(name, *args)
 
 
 def _p(t):
@@ -95,10 +103,94 @@ def upload_frames(arrays, device=None):
     return [buf[o:o + a.size].view(a.shape) for a, o in zip(arrays, off[:-1])]
 
 
-def train_frames(frames, flips, size=(640, 360), divisor=32, mean=MEANS, std=STD, to_rgb=True, out=None):
+class AugBlock:
+    """The augmentation descriptors of a batch: `host`, a ctypes array of n _lib.AugDesc the entry points check before they launch, and `buf`,
+    the one device buffer the kernels read: the same n descriptors, then frame_of int32 [n_masks] (which descriptor augments mask i)."""
+
+    def __init__(self, host, buf, n, n_masks, keep):
+        self.host, self.buf, self.n, self.n_masks, self.keep = host, buf, n, n_masks, keep
+
+    @property
+    def desc_ptr(self):
+        return c_p(self.buf.data_ptr())
+
+    @property
+    def frame_of_ptr(self):
+        return c_p(self.buf.data_ptr() + self.n * ctypes.sizeof(_lib.AugDesc)) if self.n_masks else c_p(0)
+
+
+_aug_struct_checked = False
+
+
+def _rows_ok(f):
+    return f.stride(2) == 1 and f.stride(1) == 3 and f.stride(0) >= 3 * f.shape[1]
+
+
+def upload_aug(frames, flips, params, frame_of=(), device=None):
+    """One upload for a batch's augmentation: params = one extra_aug.AugParams per frame, frames = the uint8 [H0, W0, 3] device tensors they
+    augment (None entries: descriptors for masks only, no pointer), flips = one flag per frame, frame_of = for every mask the index of its
+    frame.  -> AugBlock."""
+    global _aug_struct_checked
+    if not _aug_struct_checked:
+        got = _lib.lib().stm_aug_struct_bytes
+        got.restype, got.argtypes = ctypes.c_size_t, [ctypes.c_int]
+        if got(0) != ctypes.sizeof(_lib.AugDesc):
+            raise StmError(f"{_lib.LIB_PATH}: stm_aug_desc has {got(0)} bytes, this binding's mirror {ctypes.sizeof(_lib.AugDesc)}: rebuild with "
+                           "`python -c 'import __graft_entry__ as g; g.build()'`")
+        _aug_struct_checked = True
+    n = len(params)
+    if len(frames) != n or len(flips) != n:
+        raise StmError(f"upload_aug: {len(frames)} frames, {len(flips)} flip flags, {n} parameter records")
+    if n == 0:
+        raise StmError("upload_aug: no frames")
+    frame_of = np.asarray(frame_of, dtype=np.int32).reshape(-1)
+    if frame_of.size and (frame_of.min() < 0 or frame_of.max() >= n):
+        raise StmError(f"upload_aug: frame_of names a frame outside [0, {n})")
+    host = (_lib.AugDesc * n)()
+    keep = []
+    for i, (f, p) in enumerate(zip(frames, params)):
+        d = host[i]
+        if f is not None:
+            if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3 or f.device.type != "cuda":
+                raise StmError(f"upload_aug: frame {i}: expected uint8 [H,W,3] on the GPU, got {f.dtype} {tuple(f.shape)} on {f.device}")
+            if (int(f.shape[0]), int(f.shape[1])) != (p.H0, p.W0):
+                raise StmError(f"upload_aug: frame {i} is {tuple(f.shape[:2])}, its augmentation was drawn for {(p.H0, p.W0)}")
+            if not _rows_ok(f):
+                f = f.contiguous()
+                keep.append(f)
+            d.ptr, d.row_stride_bytes = f.data_ptr(), f.stride(0)
+            device = f.device
+        d.H0, d.W0, d.flip, d.photo = p.H0, p.W0, int(bool(flips[i])), int(bool(p.photo))
+        d.delta, d.saturation, d.hue = p.delta, p.saturation, p.hue
+        d.alpha_pre, d.alpha_post = (p.alpha, 1.0) if p.contrast_mode == 1 else (1.0, p.alpha)
+        d.perm[:] = [int(v) for v in p.perm]
+        (d.Hc, d.Wc), (d.left, d.top) = (p.canvas, p.expand[1:]) if p.expand is not None else ((p.H0, p.W0), (0, 0))
+        d.fill[:] = [float(v) for v in p.fill]
+        x0, y0, x1, y1 = p.crop if p.crop is not None else (0, 0, p.W0, p.H0)
+        d.x0, d.x1 = (min(max(int(v), 0), p.W0) for v in (x0, x1))
+        d.y0, d.y1 = (min(max(int(v), 0), p.H0) for v in (y0, y1))
+        d.cast_clip = int(p.cast == "clip")
+    raw = np.concatenate([np.frombuffer(host, dtype=np.uint8), frame_of.view(np.uint8)])
+    return AugBlock(host, _up(raw, _device(device)), n, int(frame_of.size), keep)
+
+
+def augmented_source(frame, params):
+    """stm_aug_source_u8: the augmented image itself -- uint8 [H0, W0, 3] device tensor (BGR; rows may be strided) and the AugParams that
+    ExtraAugmentation.sample drew for it -> uint8 [H0, W0, 3]: what the reference's `imgs[i] = extra_aug(imgs[i], ...)` leaves, byte for byte.
+    The batch kernels never write this image; this is the tool for looking at what an augmentation did."""
+    block = upload_aug([frame], [False], [params])
+    out = torch.empty(params.H0, params.W0, 3, dtype=torch.uint8, device=frame.device)
+    with torch.cuda.device(frame.device):
+        _launch_private("stm_aug_source_u8", 1, block.host, block.desc_ptr, _p(out), _stream())
+    return out
+
+
+def train_frames(frames, flips, size=(640, 360), divisor=32, mean=MEANS, std=STD, to_rgb=True, out=None, aug=None):
     """stm_data_frames_u8_f32: frames = uint8 [H_i, W_i, 3] device tensors (BGR; rows may be strided, pixels and channels contiguous), flips = one
     flag per frame -> fp32 [n, 3, Hp, Wp]: ImageTransform.__call__ with keep_ratio=False.  mean / std in the output's channel order.  With flip
-    off and to_rgb=False image i is bit-identical to ops.preprocess_frames_multi."""
+    off and to_rgb=False image i is bit-identical to ops.preprocess_frames_multi.
+    aug: one AugParams per frame, or the AugBlock upload_aug made of them (its flips are the ones used) -> stm_aug_frames_u8_f32: the same
+    resize over the augmented image, whose bytes are computed at every tap instead of read; identity parameters give the bits of aug=None."""
     frames = list(frames)
     h, w, Hp, Wp = padded_size(size, divisor)
     n = len(frames)
@@ -108,6 +200,19 @@ def train_frames(frames, flips, size=(640, 360), divisor=32, mean=MEANS, std=STD
         raise StmError("train_frames: no frames")
     dev = frames[0].device
     _device(dev)
+    if aug is not None:
+        block = aug if isinstance(aug, AugBlock) else upload_aug(frames, flips, list(aug))
+        if block.n != n:
+            raise StmError(f"train_frames: {n} frames, {block.n} augmentation descriptors")
+        if out is None:
+            out = torch.empty(n, 3, Hp, Wp, device=dev, dtype=torch.float32)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (n, 3, Hp, Wp) or not out.is_contiguous() or out.device != dev:
+            raise StmError(f"train_frames: out must be contiguous fp32 {(n, 3, Hp, Wp)} on {dev}, got {out.dtype} {tuple(out.shape)}")
+        m3, s3 = (ctypes.c_double * 3)(*mean), (ctypes.c_double * 3)(*std)
+        with torch.cuda.device(dev):
+            _launch_private("stm_aug_frames_u8_f32", -(-n // _lib.AUG_FRAMES_PER_LAUNCH), block.host, block.desc_ptr, n, _p(out), h, w, Hp, Wp, m3, s3,
+                            int(bool(to_rgb)), _stream())
+        return out
     desc = (_lib.DataFrameDesc * n)()
     keep = []                                       # contiguous copies made here live until the launch is enqueued (same stream)
     for i, f in enumerate(frames):
@@ -157,12 +262,14 @@ class GroundTruth:
         self.uploaded = None
 
 
-def render_ground_truth(rles, sizes, flips, boxes=None, extra=(), size=(640, 360), divisor=32, device=None, who=None):
+def render_ground_truth(rles, sizes, flips, boxes=None, extra=(), size=(640, 360), divisor=32, device=None, who=None, aug=None):
     """The ground truth of a batch on the device.  rles: n COCO RLE dicts {'size': [H0, W0], 'counts': list of run lengths | compressed string};
     flips: n flags; boxes: float32 [n, 4] in source pixels or None; extra: rows of n integers to travel with the descriptors (labels, ids).
     Uploads: the run lists, the characters of the compressed strings if there are any, one descriptor block, the boxes.  Launches: stm_vis_rle_decode
     when a string is present, stm_data_rle_starts, stm_data_masks_u8, stm_data_boxes_f32.  No host wait: the status is read through the
-    BatchStatus returned."""
+    BatchStatus returned.
+    aug: (one AugParams per mask) or an AugBlock whose frame_of covers the n masks -> stm_aug_masks_u8 instead of stm_data_masks_u8: Expand's
+    and RandomCrop's pixel work between the target pixel and the run-list lookup.  The boxes are expected as ExtraAugmentation.sample left them."""
     device = _device(device)
     h, w, Hp, Wp = padded_size(size, divisor)
     n = len(rles)
@@ -170,6 +277,17 @@ def render_ground_truth(rles, sizes, flips, boxes=None, extra=(), size=(640, 360
     if len(flips) != n or (boxes is not None and len(boxes) != n) or any(len(e) != n for e in extra):
         raise StmError("render_ground_truth: the masks, flips, boxes and extra rows differ in length")
     masks = torch.empty(n, Hp, Wp, dtype=torch.uint8, device=device)
+    if aug is not None and n and not isinstance(aug, AugBlock):
+        aug = list(aug)
+        if len(aug) != n:
+            raise StmError("render_ground_truth: the masks and their augmentation parameters differ in length")
+        for i, p in enumerate(aug):
+            if (p.H0, p.W0) != (int(sizes[i][0]), int(sizes[i][1])):
+                raise StmError(f"render_ground_truth: mask {i} is {tuple(sizes[i])}, its augmentation was drawn for {(p.H0, p.W0)}")
+        with torch.cuda.device(device):
+            aug = upload_aug([None] * n, flips, aug, np.arange(n), device)
+    if aug is not None and n and aug.n_masks != n:
+        raise StmError(f"render_ground_truth: {n} masks, the augmentation block names the frames of {aug.n_masks}")
     if n == 0:
         return GroundTruth(masks, None if boxes is None else torch.empty(0, 4, device=device), torch.empty(len(extra), 0, dtype=torch.int64, device=device),
                            torch.empty(0, dtype=torch.int64, device=device), torch.empty(0, dtype=torch.int32, device=device),
@@ -198,7 +316,7 @@ def render_ground_truth(rles, sizes, flips, boxes=None, extra=(), size=(640, 360
     desc[:, 2] = [1 if f else 0 for f in flips]
     desc[:, 3] = hm.pos
     with torch.cuda.device(device):
-        up = {"n": n, "ns": ns, "total_c": total_c, "total": total, "k": k, "dims": (h, w, Hp, Wp), "masks": masks}
+        up = {"n": n, "ns": ns, "total_c": total_c, "total": total, "k": k, "dims": (h, w, Hp, Wp), "masks": masks, "aug": aug}
         up["meta"] = _up(meta, device)
         up["runs"] = torch.empty(total, dtype=torch.int32, device=device)
         if total_l:
@@ -230,7 +348,12 @@ def launch_ground_truth(up):
         _launch("stm_vis_rle_decode", 1, _p(up["chars"]), _p(off_d), _p(hw_d), ns, total_c, _p(runs), _p(n_runs), _p(area), _p(status), _stream())
     _launch("stm_data_rle_starts", 1, _p(runs), _p(off_d), _p(n_runs), _p(status), _p(hw_d), n, total, _p(starts), _p(n_runs), _p(area), _p(status),
             _stream())
-    _launch("stm_data_masks_u8", 1, _p(starts), _p(off_d), _p(n_runs), n, _p(desc_d), n, total, _p(up["masks"]), h, w, Hp, Wp, _stream())
+    block = up.get("aug")
+    if block is None:
+        _launch("stm_data_masks_u8", 1, _p(starts), _p(off_d), _p(n_runs), n, _p(desc_d), n, total, _p(up["masks"]), h, w, Hp, Wp, _stream())
+    else:
+        _launch_private("stm_aug_masks_u8", 1, _p(starts), _p(off_d), _p(n_runs), n, _p(desc_d), block.frame_of_ptr, block.desc_ptr, block.n, n, total,
+                        _p(up["masks"]), h, w, Hp, Wp, _stream())
     boxes_d = None
     if up["boxes"] is not None:
         boxes_d = torch.empty(n, 4, dtype=torch.float32, device=device)
@@ -254,11 +377,16 @@ class YTVISTrainSet:
         bboxes [2] float32 [G, 4], labels [2] int64 [G], obj_ids [2] lists (the annotation ids), segms [2] lists of RLE dicts as the JSON holds them,
         img_meta (the reference's dict; frame_id is the LAST frame of the sorted pair, its quirk), and the transform's settings.
     Departure: the reference appends a crowd annotation's mask but not its box, which misaligns gt_masks and gt_bboxes for the criterion; here a
-    crowd annotation contributes neither."""
+    crowd annotation contributes neither.
+    extra_aug: None, or the reference's dict(photo_metric_distortion=..., expand=..., random_crop=...) (or an ExtraAugmentation).  With None every
+    record and every random draw is what it is without the argument.  With a dict the frames are read first, frame 0's augmentation is drawn,
+    then frame 1's, THEN the clip's one flip (datasets/ytvos.py:243-248); the record gains aug = [AugParams, AugParams] and its bboxes / labels /
+    obj_ids / segms are what the augmentation left.  The pixels are augmented on the device by collate_device."""
 
     def __init__(self, ann, img_prefix=None, frame_reader=None, img_scale=(640, 360), size_divisor=32, flip_ratio=0.5, clip_frames=1, to_rgb=True,
-                 mean=MEANS, std=STD):
+                 mean=MEANS, std=STD, extra_aug=None, crop_boxes="reference", cast="reference"):
         data = vis_eval._load(ann)
+        self.extra_aug = _extra_aug.from_config(extra_aug, crop_boxes, cast)
         if isinstance(img_scale, list):
             if len(img_scale) != 1:
                 raise ValueError("YTVISTrainSet: more than one img_scale is not built")
@@ -312,21 +440,32 @@ class YTVISTrainSet:
         vid, frame_id = self.img_ids[i]
         info = self.vid_infos[vid]
         clip = sorted(self.sample_ref((vid, frame_id)) + [frame_id])
-        flip = bool(np.random.rand() < self.flip_ratio)
+        flip = bool(np.random.rand() < self.flip_ratio) if self.extra_aug is None else None
         frames = []
         for f in clip:
             name = info["file_names"][f]
             frames.append(self.frame_reader(name if self.img_prefix is None else os.path.join(self.img_prefix, name)))
         H0, W0 = int(frames[0].shape[0]), int(frames[0].shape[1])
         anns = [self.get_ann_info(vid, f) for f in clip]
+        aug = None
+        if self.extra_aug is not None:
+            aug = []
+            for t, a in enumerate(anns):
+                p, a["bboxes"], a["labels"], a["obj_ids"], a["segms"] = self.extra_aug.sample(frames[t].shape[0], frames[t].shape[1], a["bboxes"],
+                                                                                            a["labels"], a["obj_ids"], a["segms"])
+                aug.append(p)
+            flip = bool(np.random.rand() < self.flip_ratio)
         h, w, Hp, Wp = padded_size(self.img_scale, self.size_divisor)
         last = clip[-1]
         meta = dict(ori_shape=(info["height"], info["width"], 3), img_shape=(h, w, 3), pad_shape=(Hp, Wp, 3), video_id=vid, frame_id=last,
                     is_first=(last == 0), scale_factor=np.array([w / W0, h / H0, w / W0, h / H0], dtype=np.float32), flip=flip)
-        return dict(frames=frames, size=(H0, W0), flip=flip, video_id=vid, frame_ids=clip, bboxes=[a["bboxes"] for a in anns],
-                    labels=[a["labels"] for a in anns], obj_ids=[a["obj_ids"] for a in anns],
-                    segms=[a["segms"] for a in anns], img_meta=meta, img_scale=self.img_scale, size_divisor=self.size_divisor, to_rgb=self.to_rgb,
-                    mean=self.mean, std=self.std)
+        rec = dict(frames=frames, size=(H0, W0), flip=flip, video_id=vid, frame_ids=clip, bboxes=[a["bboxes"] for a in anns],
+                   labels=[a["labels"] for a in anns], obj_ids=[a["obj_ids"] for a in anns],
+                   segms=[a["segms"] for a in anns], img_meta=meta, img_scale=self.img_scale, size_divisor=self.size_divisor, to_rgb=self.to_rgb,
+                   mean=self.mean, std=self.std)
+        if aug is not None:
+            rec["aug"] = aug
+        return rec
 
 
 def collate_device(records, device=None, max_gt=None, check="raise"):
@@ -335,7 +474,8 @@ def collate_device(records, device=None, max_gt=None, check="raise"):
     [frame 0, frame 1] tensors (boxes [G, 4] fp32 relative to the padded image, labels int64 [G], masks uint8 [G, Hp, Wp], ids int64 [G]), each a
     view into one buffer per kind.  max_gt keeps the first max_gt objects of a frame.  One upload each for the frames (pinned staging), the run
     lists, the descriptors (labels and ids ride along) and the boxes; at most 64 frames take 4 launches, plus one when a mask arrives as a
-    compressed string.  A flagged mask raises ValueError naming the video id, annotation id and frame: check="raise" waits for the status words
+    compressed string.  Records that carry aug (YTVISTrainSet(extra_aug=...)) are augmented inside those same launches: one more upload (the
+    descriptors), no more launches; records with and without aug may not be mixed.  A flagged mask raises ValueError naming the video id, annotation id and frame: check="raise" waits for the status words
     here; check="deferred" appends a BatchStatus to the tuple whose .raise_if_bad() the caller invokes a step later, so the call itself never
     waits for the device."""
     if check not in ("raise", "deferred"):
@@ -348,10 +488,16 @@ def collate_device(records, device=None, max_gt=None, check="raise"):
     for r in records:
         if any(r[k] != r0[k] for k in ("img_scale", "size_divisor", "to_rgb", "mean", "std")):
             raise StmError("collate_device: the records come from datasets with different transforms")
+    augmented = "aug" in r0
+    if any(("aug" in r) != augmented for r in records):
+        raise StmError("collate_device: records with and without aug in one batch")
+    params, frame_of = [], []
     frames, f_flips, rles, sizes, flips, names, counts = [], [], [], [], [], [], []
     boxes, labels, ids = [], [], []
     for r in records:
         for t, f in enumerate(r["frames"]):
+            if augmented:
+                params.append(r["aug"][t])
             frames.append(f)
             f_flips.append(r["flip"])
             g = len(r["segms"][t]) if max_gt is None else min(len(r["segms"][t]), int(max_gt))
@@ -359,6 +505,7 @@ def collate_device(records, device=None, max_gt=None, check="raise"):
             size = (int(f.shape[0]), int(f.shape[1]))
             for j in range(g):
                 rles.append(r["segms"][t][j])
+                frame_of.append(len(frames) - 1)
                 sizes.append(size)
                 flips.append(r["flip"])
                 names.append((r["video_id"], r["obj_ids"][t][j], r["frame_ids"][t]))
@@ -368,9 +515,10 @@ def collate_device(records, device=None, max_gt=None, check="raise"):
     who = lambda i: "video %s, annotation %s, frame %s" % names[i]      # noqa: E731
     with torch.cuda.device(device):
         dev_frames = upload_frames(frames, device)
-        images = train_frames(dev_frames, f_flips, r0["img_scale"], r0["size_divisor"], r0["mean"], r0["std"], r0["to_rgb"])
+        block = upload_aug(dev_frames, f_flips, params, frame_of, device) if augmented else None
+        images = train_frames(dev_frames, f_flips, r0["img_scale"], r0["size_divisor"], r0["mean"], r0["std"], r0["to_rgb"], aug=block)
         gt = render_ground_truth(rles, sizes, flips, np.concatenate(boxes).reshape(-1, 4), (np.concatenate(labels), np.concatenate(ids)),
-                                 r0["img_scale"], r0["size_divisor"], device, who)
+                                 r0["img_scale"], r0["size_divisor"], device, who, aug=block)
     edges = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     per = lambda t: [[t[edges[2 * c + k]:edges[2 * c + k + 1]] for k in range(2)] for c in range(len(records))]   # noqa: E731
     out = (images.view(len(records), 2, *images.shape[1:]), per(gt.boxes), per(gt.extra[0]), per(gt.masks), per(gt.extra[1]),
