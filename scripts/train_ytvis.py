@@ -16,7 +16,12 @@ over 500 iterations, 250000 iterations: config.py:397-415, :625), train.lr_at ea
   - --extra_aug photo,expand,crop (any subset) turns the reference's ExtraAugmentation on, with the settings its training configs carry: the
     parameters are drawn on the host, the pixels are augmented inside the batch kernels.  The numpy RNG state is not
     part of a checkpoint: a resumed run continues with fresh draws, as the flip does.
-No DataParallel, no validation-mAP hook.
+  - --valid_ann FILE [--valid_img_prefix DIR] --validation_interval N: every N iterations, and at the final save, the validation split goes
+    through stmask_amd.validate.validation on an InferenceTwin of the net (the net itself stays in train mode): the results JSON and, when the
+    annotation file has annotations, the mAP file are written beside the weights under the reference's names -- the checkpoint's path with
+    .pth replaced by .json and .txt (train.py:369, eval.py:573) -- and --log gains a line {"kind": "valid", "iteration", "metrics"}.  The
+    reference also validates at iteration 100, a debugging leftover that is not reproduced.
+No DataParallel.
     python scripts/train_ytvis.py ANN IMG_PREFIX [--config STMask_plus_resnet50_config] [--batch_size 4] [--iters 250000] [--backbone PATH]
                                   [--save_folder weights/] [--resume latest] [--guard loss] [--log train.jsonl] [--extra_aug photo,expand,crop]"""
 import argparse
@@ -30,7 +35,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from stmask_amd import checkpoint, datasets, layers  # noqa: E402
+from stmask_amd import checkpoint, datasets, layers, validate  # noqa: E402
 from stmask_amd.config import get_cfg  # noqa: E402
 from stmask_amd.extra_aug import config_from_names  # noqa: E402
 from stmask_amd.model import STMask  # noqa: E402
@@ -69,6 +74,11 @@ def parse_args(argv=None):
     ap.add_argument("--guard", choices=["loss", "grads", "off"], default="loss", help="what makes the optimizer skip a step, on the device")
     ap.add_argument("--extra_aug", default="", help="comma list of photo, expand, crop: ExtraAugmentation with the reference's settings for each")
     ap.add_argument("--log", default=None, help="a file of one JSON line per iteration (appended to when resuming)")
+    ap.add_argument("--valid_ann", default=None, help="annotation file of the validation split (with or without annotations)")
+    ap.add_argument("--valid_img_prefix", default=None, help="folder of the validation split's frames")
+    ap.add_argument("--validation_interval", type=int, default=0, help="iterations between validations (0: off)")
+    ap.add_argument("--eval_slots", type=int, default=8, help="videos in flight while validating")
+    ap.add_argument("--eval_planes", choices=["fp16x2", "bf16x3", "fp16x1"], default="fp16x2", help="plane format of the twin's inference graph")
     return ap.parse_args(argv)
 
 
@@ -141,6 +151,26 @@ def main():
         print(f"saving {path}", flush=True)
         checkpoint.save(path, net, opt, iteration, epoch, loader)
 
+    twin = valid_set = None
+    if args.valid_ann and args.validation_interval > 0:
+        valid_set = datasets.YTVISValSet(args.valid_ann, args.valid_img_prefix, read_ahead=8)
+        twin = validate.InferenceTwin(net, planes=args.eval_planes)
+
+    def validate_at(path):
+        """The validation split under the names of the checkpoint `path`; the mAP file only when there is something to score."""
+        if twin is None:
+            return
+        flush()
+        out_json, metrics_file = validate.result_paths(path)
+        scored = valid_set.has_annotations
+        print(f"validating -> {out_json}", flush=True)
+        metrics = validate.validation(twin, valid_set, out_json, ann_file=args.valid_ann if scored else None,
+                                      metrics_file=metrics_file if scored else None, n_slots=args.eval_slots)
+        if log_file:
+            listed = None if metrics is None else [float(v) for v in metrics]      # calc_metrics: the 12 summary numbers
+            log_file.write(json.dumps({"kind": "valid", "iteration": iteration, "metrics": listed}) + "\n")
+            log_file.flush()
+
     epoch = loader.state()["epoch"]
     try:
         while iteration < max_iter:
@@ -169,12 +199,17 @@ def main():
                                                                   iteration % args.keep_latest_interval != args.save_interval):
                         print(f"deleting {latest}", flush=True)
                         checkpoint.remove(latest)
+                if twin is not None and iteration % args.validation_interval == 0 and iteration < max_iter:
+                    validate_at(checkpoint.save_path(cfg.name, epoch, iteration, args.save_folder))
     except KeyboardInterrupt:
         print("interrupted: saving", flush=True)
         checkpoint.remove_interrupt(args.save_folder)
         save(checkpoint.save_path(cfg.name, epoch, iteration, args.save_folder, interrupt=True))
         raise SystemExit(130)
     save(checkpoint.save_path(cfg.name, epoch, iteration, args.save_folder))
+    validate_at(checkpoint.save_path(cfg.name, epoch, iteration, args.save_folder))
+    if valid_set is not None:
+        valid_set.close()
     if log_file:
         log_file.close()
 

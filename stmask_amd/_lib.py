@@ -224,6 +224,22 @@ AUG_SIGNATURES = {
 }
 PRIVATE_TABLES = {"optim.h": PRIVATE_SIGNATURES, "extra_aug.h": AUG_SIGNATURES}   # header under csrc/ -> its table
 AUG_FRAMES_PER_LAUNCH = 64   # csrc/extra_aug.h STM_AUG_FRAMES_PER_LAUNCH
+# ... and those of csrc/fold.h: the parameter write of the inference twin (validate.py).  A third private table, kept beside PRIVATE_TABLES (which
+# stays the pair of the training loop's headers); private_tables() is all three, which is what private_call() and build() walk.
+FOLD_SIGNATURES = {
+    "stm_fold_struct_bytes": ("z", "i"),
+    "stm_fold_rows_f32": ("i", "pip"),
+}
+FOLD_MAX_ROWS = 64   # csrc/fold.h STM_FOLD_MAX_ROWS
+FOLD_CHUNK = 4096    # csrc/fold.h STM_FOLD_CHUNK
+FOLD_COPY, FOLD_WEIGHT, FOLD_BIAS = 0, 1, 2   # csrc/fold.h STM_FOLD_COPY / _WEIGHT / _BIAS
+
+
+def private_tables():
+    """{header under csrc/: its table} of every package-private header."""
+    return {**PRIVATE_TABLES, "fold.h": FOLD_SIGNATURES}
+
+
 _private_calls = {}   # name -> (function, argument count) for private_call()
 
 
@@ -301,6 +317,12 @@ class AugDesc(ctypes.Structure):
                 [(n, c_i) for n in ("x0", "y0", "x1", "y1", "cast_clip")])
 
 
+class FoldRow(ctypes.Structure):
+    """stm_fold_row of csrc/fold.h (package-private: its size is checked against stm_fold_struct_bytes(0) where it is first used and in
+    tests/test_validate_cpu.py, not through STRUCTS)."""
+    _fields_ = [(n, c_p) for n in ("dst", "src", "gamma", "beta", "mean", "var")] + [("numel", c_l), ("inner", c_l), ("kind", c_i), ("eps", c_f)]
+
+
 # size function of the library -> the mirrors of the structs it knows, by index: lib() refuses a library whose sizes differ
 STRUCTS = {
     "stm_struct_bytes": [DeformGeom, ConvGeom, ConvWindow, HeadLayout, FrameDesc, RenderFrame],
@@ -364,10 +386,11 @@ def call(name, *args):
 
 
 def private_call(name, *args):
-    """call() for an entry of PRIVATE_SIGNATURES or AUG_SIGNATURES: restype / argtypes are set from the table when the entry is first used."""
+    """call() for an entry of PRIVATE_SIGNATURES, AUG_SIGNATURES or FOLD_SIGNATURES: restype / argtypes are set from the table when the entry is
+    first used."""
     got = _private_calls.get(name)
     if got is None:
-        ret, params = PRIVATE_SIGNATURES[name] if name in PRIVATE_SIGNATURES else AUG_SIGNATURES[name]
+        ret, params = next(table[name] for table in (PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES) if name in table)
         fn = getattr(lib(), name, None)
         if fn is None:
             raise StmError(f"{LIB_PATH} lacks {name}: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")

@@ -12,6 +12,9 @@ Scope: the reference's training configs -- img_scale=[(640, 360)], resize_keep_r
 with_track=True, clip_frames=1, and extra_aug=None or the reference's dict: ExtraAugmentation's parameters are drawn on the host (extra_aug.py)
 and its pixel work is done inside the frame and mask kernels (csrc/extra_aug.hip).  Not built: aug_ref_bbox_param,
 proposals, keep_ratio=True, more than one img_scale, DataParallel.
+
+YTVISValSet / LazyVideo at the end of the file are the test-mode half: the videos of a validation split in the form
+serve.VideoBatcher.run takes, every frame read when the batcher asks for it.
 """
 import ctypes
 import os
@@ -591,3 +594,84 @@ class TrainLoader:
             yield tuple(batch)
         if pending is not None:
             pending.raise_if_bad()
+
+
+# ------------------------------------------------------------------------------------------------------------------ the validation split
+class LazyVideo:
+    """One video of a YTVISValSet in the form serve.VideoBatcher.run indexes: .shape is (T, H, W, 3) from the annotation, video[t] is frame t as a
+    uint8 [H, W, 3] tensor (pinned when there is a GPU), read when first asked for and dropped once `keep` later frames of the video have been
+    asked for (a frame asked for again after that is read again).  With a pool, asking for frame t also starts the reads of the next
+    `read_ahead` frames, in the video's own order."""
+
+    def __init__(self, names, height, width, frame_reader, keep=2, pool=None, read_ahead=0):
+        self.names, self.shape = list(names), (len(names), int(height), int(width), 3)
+        self.frame_reader, self.keep, self.pool, self.read_ahead = frame_reader, int(keep), pool, int(read_ahead)
+        self._held = {}        # frame index -> tensor, or the future of its read
+        self._asked = []       # distinct frame indices in the order they were first asked for, the held ones only
+
+    def __len__(self):
+        return self.shape[0]
+
+    def _read(self, t):
+        a = self.frame_reader(self.names[t])
+        if tuple(a.shape) != self.shape[1:]:
+            raise ValueError(f"{self.names[t]}: decoded to {tuple(a.shape)}, the annotation says {self.shape[1:]}")
+        f = torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))
+        return f.pin_memory() if torch.cuda.is_available() else f
+
+    def __getitem__(self, t):
+        t = int(t)
+        if not 0 <= t < self.shape[0]:
+            raise IndexError(f"frame {t} of a video of {self.shape[0]}")
+        if self.pool is not None:
+            for u in range(t + 1, min(t + 1 + self.read_ahead, self.shape[0])):
+                if u not in self._held:
+                    self._held[u] = self.pool.submit(self._read, u)
+        got = self._held.get(t)
+        if got is None:
+            got = self._read(t)
+        elif not isinstance(got, torch.Tensor):
+            got = got.result()
+        self._held[t] = got
+        if t not in self._asked:
+            self._asked.append(t)
+            while len(self._asked) > self.keep:         # `keep` later frames have been asked for: the oldest goes
+                self._held.pop(self._asked.pop(0), None)
+        return got
+
+
+class YTVISValSet:
+    """YTVOSDataset (datasets/ytvos.py) for test_mode=True, as far as the reference's validation uses it: the videos of an annotation file in
+    file order, each with id, filenames, height, width, length, with or without `annotations` (the official valid split has none).  videos() is
+    the list of (video_id, LazyVideo) serve.VideoBatcher.run takes: no frame is read before the batcher asks for it, and a video holds at most
+    keep + read_ahead frames.  read_ahead=k > 0: a thread pool of min(8, k) threads reads up to k frames ahead in each video's own order.
+    Not restated: several img_scales, test-time flip (commented out in the reference), proposals, clip_eval_mode."""
+
+    def __init__(self, ann, img_prefix=None, frame_reader=None, read_ahead=0):
+        data = vis_eval._load(ann)
+        self.img_prefix, self.frame_reader, self.read_ahead = img_prefix, frame_reader or read_frame, int(read_ahead)
+        if self.read_ahead < 0:
+            raise ValueError(f"YTVISValSet: read_ahead={read_ahead}")
+        self.has_annotations = bool(data.get("annotations"))
+        self.videos_info = []
+        for v in data["videos"]:
+            names = [n if img_prefix is None else os.path.join(img_prefix, n) for n in v["file_names"]]
+            if not names:
+                raise ValueError(f"YTVISValSet: video {v['id']} has no frames")
+            self.videos_info.append(dict(id=v["id"], filenames=names, height=int(v["height"]), width=int(v["width"]), length=len(names)))
+        self._pool = None
+
+    def __len__(self):
+        return len(self.videos_info)
+
+    def videos(self, keep=2):
+        if self.read_ahead > 0 and self._pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=min(8, self.read_ahead))
+        return [(v["id"], LazyVideo(v["filenames"], v["height"], v["width"], self.frame_reader, keep, self._pool, self.read_ahead))
+                for v in self.videos_info]
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None

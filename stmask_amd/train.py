@@ -1,8 +1,8 @@
 """The reference's training step (train.py:134-150, :290-320) over this package: NetLoss ties the train-mode STMask.forward to layers.MultiBoxLoss,
 train_step runs one optimizer step; lr_at and autoscale restate its learning-rate schedule (train.py:88-96, :293-302) as pure functions.  The
 batches come from stmask_amd.datasets (YTVISTrainSet, TrainLoader, collate_device) or synthetic.synthetic_train_batch; scripts/train_ytvis.py
-puts the pieces together with optim.GuardedSGD (the step guarded on the device), LossLog below and stmask_amd.checkpoint.  ExtraAugmentation,
-DataParallel and the validation-mAP hook are not built."""
+puts the pieces together with optim.GuardedSGD (the step guarded on the device), LossLog below, stmask_amd.checkpoint and the validation-mAP
+hook of stmask_amd.validate.  DataParallel is not built."""
 import math
 
 import torch
