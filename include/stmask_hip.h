@@ -388,8 +388,9 @@ int stm_conv2d_planar_windows_f32(const void* x_planes, const void* const* packe
  * AvgPool2d((7, 7)) (track_to_segment_head.py:30-33) without the per-pixel tensor.  pool_fix [B][Cout] (unsigned 64-bit, 32.32 fixed point, 8-byte
  * aligned) receives, ADDED to what it holds, the sum over the image's win_h x win_w pixels of relu(conv + bias): zero it before the first use;
  * stm_temporal_pool_fc_f32 zeroes what it consumes.  The accumulation is integer (each workgroup converts its fp32 partial sum exactly), so the
- * result does not depend on the order in which workgroups finish.  A partial sum of 2^32 or more (or NaN) raises the device's range flag.
- * g as for stm_conv2d_planar_windows_f32, Cout a multiple of 128; the out_* fields are ignored. */
+ * result does not depend on the order in which workgroups finish.  An image's sum must stay below 2^32 - win_h * win_w * 2^16: a NaN, a partial sum
+ * of 4e9 or more, and a total that reaches that limit (a word that wrapped included) raise the device's range flag.
+ * g as for stm_conv2d_planar_windows_f32, Cout a multiple of 128, win_h * win_w <= 32768; the out_* fields are ignored. */
 int stm_conv2d_planar_windows_pool_f32(const void* x_planes, const void* const* packed_weights, const stm_conv_window* windows, int n_windows,
                                        const float* bias, unsigned long long* pool_fix, const stm_conv_geom* g, stm_stream_t stream);
 

@@ -340,31 +340,58 @@ __global__ __launch_bounds__(256) void planar_splitk_finish_kernel(const PlanarA
 // fragment reads, 8 no wait for the DMAs, 16 activation DMA on every third slab only (the traffic of a kx-reuse staging), 32 no
 // activation DMA, 64 no weight DMA.
 // AvgPool2d over the whole output image folded into the epilogue of a window-set launch (TemporalNet: track_to_segment_head.py:30-33).  The wave owns 64
-// class pixels x 64 channels, parked in LDS: lane = channel, the rows are walked once; the pixels of one image are consecutive rows of a class (hw of
+// class pixels x 64 channels, parked in LDS: lane = channel, the rows are walked once (a second time only for the large pieces below); the pixels of one image are consecutive rows of a class (hw of
 // them), so the running sum is flushed whenever the image index advances, and at the end of the block (an image cut by a block or class boundary arrives
 // in several pieces).  Each piece is an fp32 sum in row order, converted exactly to 32.32 fixed point and added with an integer atomic: the total does
 // not depend on the order of arrival.  mw = first class pixel of the wave's rows, col = the lane's output channel.
-__device__ __forceinline__ void pooled_epilogue(const PlanarArgs& a, unsigned long long* pool, int pool_ld, uint8_t* smem, int wave, int lane, int mw, int col)
+// The range flag: a NaN or a piece of 4e9 or more raises it at once.  But a word wraps when the image's TOTAL reaches 2^32, which no single piece need do
+// (49 pixels of 2^27: the largest piece, the 25 interior ones, is below 4e9).  So a piece of POOL_BIG_PIECE or more is not added by the first walk: a second
+// walk (BIG = true, entered only by lanes that met one -- never by ordinary activations) adds it with a compare-and-swap loop, sees what the word held, and
+// raises the flag when the new total has wrapped or lies within win_hw * POOL_BIG_PIECE of 2^32: the image's smaller pieces, fewer than win_hw of them, add
+// less than that margin whenever they arrive, so no total wraps unflagged.  (Two walks, not a branch in one: with the returning atomic or the loop inside
+// the first walk's body -- which stays straight-line code around one atomic that returns nothing -- conv3 at 3584 RoIs took 1594 us instead of 1523.)
+constexpr int POOL_BIG_SHIFT = 16;
+constexpr float POOL_BIG_PIECE = (float)(1 << POOL_BIG_SHIFT);
+template <bool BIG>
+__device__ __forceinline__ bool pooled_walk(const PlanarArgs& a, unsigned long long* pool, int pool_ld, const float* park, int lane, int mw, int col)
 {
     constexpr int EP_LD = 32 * 2 + 4;
-    const float* park = park_base<2>(smem, wave);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     const int hw = a.Ho * a.Wo;
     const int rows = min(64, a.M - mw);
     int b = mw / hw, r = mw - b * hw;
     const float bias = a.bias ? a.bias[col] : 0.0f;
     float sum = 0.0f;
+    bool any_big = false;
     for (int row = 0; row < rows; ++row) {
-        sum += __builtin_fmaxf(__builtin_fmaf(park[row * EP_LD + lane], a.out_scale, bias), 0.0f);
+        // (IEEE 754-2019 maximum, v_maximum3_f32: fmaxf returns 0 for a NaN, which must reach the guard below)
+        sum += __builtin_elementwise_maximum(__builtin_fmaf(park[row * EP_LD + lane], a.out_scale, bias), 0.0f);
         if (++r == hw || row == rows - 1) {
-            if (!(sum < 4.0e9f) && a.range_flag) *reinterpret_cast<volatile int*>(a.range_flag) = 1;     // (also NaN)
+            const bool big = sum >= POOL_BIG_PIECE;
             const unsigned hi = (unsigned)sum;
             const unsigned lo = (unsigned)((sum - (float)hi) * 4294967296.0f);
-            __hip_atomic_fetch_add(pool + (size_t)b * pool_ld + col, ((unsigned long long)hi << 32) | lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long add = ((unsigned long long)hi << 32) | lo;
+            unsigned long long* word = pool + (size_t)b * pool_ld + col;
+            if (!BIG) {
+                if (!(sum < 4.0e9f) && a.range_flag) *reinterpret_cast<volatile int*>(a.range_flag) = 1;     // (also NaN)
+                __hip_atomic_fetch_add(word, big ? 0ull : add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                any_big |= big;
+            } else if (big) {
+                unsigned long long old = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                while (!__hip_atomic_compare_exchange_weak(word, &old, old + add, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {}
+                const unsigned long long now = old + add, margin = (unsigned long long)a.win_hw << (32 + POOL_BIG_SHIFT);   // (win_hw <= 2^15)
+                if ((now < old || now >= 0ull - margin) && a.range_flag) *reinterpret_cast<volatile int*>(a.range_flag) = 1;
+            }
             sum = 0.0f;
             if (r == hw) { r = 0; ++b; }
         }
     }
+    return any_big;
+}
+__device__ __forceinline__ void pooled_epilogue(const PlanarArgs& a, unsigned long long* pool, int pool_ld, uint8_t* smem, int wave, int lane, int mw, int col)
+{
+    const float* park = park_base<2>(smem, wave);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (pooled_walk<false>(a, pool, pool_ld, park, lane, mw, col)) pooled_walk<true>(a, pool, pool_ld, park, lane, mw, col);
 }
 
 // (Tried and removed, round 2: loading the residual planes of a 64-channel tile BEFORE the K loop -- no change on the HBM-bound
@@ -1372,7 +1399,7 @@ extern "C" int stm_conv2d_planar_windows_f32(const void* x_planes, const void* c
 // track_to_segment_head.py:30-33): nothing is written per pixel; pool_fix[image][channel] (row length Cout, unsigned 64-bit, 32.32 fixed point)
 // receives the SUM over the image's win_h x win_w pixels of relu(conv + bias), added to what it holds -- the caller zeroes it (stm_temporal_pool_fc_f32
 // does, when it consumes it).  Integer accumulation: the result does not depend on the order in which the workgroups finish.  Sums must stay below
-// 2^32 (the per-device range flag is raised otherwise, as for an fp16 overflow).
+// 2^32 - win_h * win_w * 2^16 (the per-device range flag is raised otherwise, as for an fp16 overflow: pooled_epilogue).
 extern "C" int stm_conv2d_planar_windows_pool_f32(const void* x_planes, const void* const* packed_weights, const stm_conv_window* windows, int n_windows,
                                                   const float* bias, unsigned long long* pool_fix, const stm_conv_geom* g, stm_stream_t stream)
 {
@@ -1382,6 +1409,7 @@ extern "C" int stm_conv2d_planar_windows_pool_f32(const void* x_planes, const vo
     STM_REQUIRE(g->win_w > 0 && g->win_h > 0 && g->fmt == 1 && g->sh == 1 && g->sw == 1 && (g->groups <= 1) && g->n_levels <= 0 &&
                 (g->tile_n == 0 || g->tile_n == 128) && g->Cout % 128 == 0, STM_EUNSUPPORTED,
                 "%s: fp16x2 planes, stride 1, one group, whole 128-channel tiles, win_h / win_w set", who);
+    STM_REQUIRE((int64_t)g->win_h * g->win_w <= 32768, STM_EUNSUPPORTED, "%s: pooled images of at most 32768 pixels", who);   // (pooled_epilogue's margin)
     STM_REQUIRE((uintptr_t)pool_fix % 8 == 0, STM_EINVAL, "%s: pool_fix must be 8-byte aligned", who);
     for (int i = 0; i < n_windows; ++i) STM_REQUIRE(packed_weights[i], STM_ENULL, "%s: packed weight %d is NULL", who, i);
     stm_conv_geom g0 = *g;

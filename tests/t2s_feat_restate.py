@@ -18,6 +18,10 @@ CASES = {
     "p4_384x640": dict(bs=2, C=32, Cu=16, h=24, w=40, P=11, seed=0, ref=False),
     "row_736x1280": dict(bs=1, C=16, Cu=8, h=4, w=80, P=11, seed=0, ref=False),
     "tile_cross": dict(bs=1, C=12, Cu=4, h=3, w=70, P=5, seed=0, ref=False),         # a row crossing a 64-column tile of the adjoint
+    # the adjoint's patch staging leaves LDS above 48 KB: P = 13 for the next-frame launch only (51 376 B; 43 264 B for the reference frame's),
+    # P = 15 for both (57 600 B), there with a row that crosses a 64-column tile.  Appended: draw_case seeds by position.
+    "mode1_global_p13": dict(bs=2, C=6, Cu=2, h=5, w=9, P=13, seed=0, ref=False),
+    "both_global_p15": dict(bs=1, C=5, Cu=2, h=4, w=70, P=15, seed=0, ref=False),
 }
 
 

@@ -172,7 +172,11 @@ def test_gemm_is_exact_fmaf_chain_on_integers():
 
 # ------------------------------------------------------------------------------------------ temporal
 @pytest.mark.parametrize("B,C,H,W", [(1, 256, 24, 40), (2, 32, 12, 20), (1, 20, 7, 9), (1, 8, 3, 5), (3, 20, 6, 8), (2, 40, 30, 44),
-                                     (2, 256, 46, 80), (1, 24, 13, 40), (2, 12, 9, 16), (1, 9, 5, 72)])
+                                     (2, 256, 46, 80), (1, 24, 13, 40), (2, 12, 9, 16), (1, 9, 5, 72),
+                                     # corr_patch_launch's switches: W = 48 is the first width on 8-channel chunks (16 * 11 * 12 units > 2048),
+                                     # 88 the widest the kernel was tuned for, 92 the last the staging plan admits (8 * 11 * 23 = 2024 units),
+                                     # 96 the first that falls to the generic kernel on size alone (2112 units)
+                                     (1, 16, 3, 48), (1, 8, 3, 88), (2, 8, 4, 92), (1, 8, 3, 96)])
 def test_correlation_vs_oracle(B, C, H, W):
     f1, f2 = rnd(B, C, H, W, seed=1), rnd(B, C, H, W, seed=2)
     ref = oracle.corr_patch(f1, f2, 11, 1)

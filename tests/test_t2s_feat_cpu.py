@@ -12,10 +12,10 @@ REF = [n for n, s in R.CASES.items() if s["ref"]]
 
 
 def test_case_table():
-    assert REF == ["smallest", "odd_clips"] and len(R.CASES) == 6
+    assert REF == ["smallest", "odd_clips"] and len(R.CASES) == 8
     shapes = [(s["bs"], s["C"], s["Cu"], s["h"], s["w"], s["P"]) for s in R.CASES.values()]
     assert shapes == [(1, 8, 4, 3, 4, 3), (3, 20, 8, 5, 8, 11), (2, 18, 6, 6, 37, 11), (2, 32, 16, 24, 40, 11), (1, 16, 8, 4, 80, 11),
-                      (1, 12, 4, 3, 70, 5)]
+                      (1, 12, 4, 3, 70, 5), (2, 6, 2, 5, 9, 13), (1, 5, 2, 4, 70, 15)]
     for name, s in R.CASES.items():
         c = R.draw_case(name)
         imgs = c["fpn"].flatten(1)
