@@ -22,18 +22,25 @@ def barrier():
 
 # ---------------------------------------------------------------------------------------------------------------------
 # self-launch: `python bench.py --gpus N` without a launcher
-def self_launch(args, argv, script):
-    """Parent of an N-rank run.  Touches no GPU API; starts torch.distributed.run as a child and relays its output."""
+def start_ranks(gpus, argv, script, **popen):
+    """torch.distributed.run with `gpus` ranks of `script argv` on this node, as a child process (the caller touches no GPU API) -> the Popen.
+    Shared by bench.py --gpus N and scripts/train_ytvis.py --gpus N."""
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(script)] + list(argv)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}",
+           "--master-addr", "127.0.0.1", "--master-port", str(port), "--", os.path.abspath(script)] + list(argv)
+    # "--": the script's own options are not the launcher's (argparse would call --log an ambiguous abbreviation of its --log-dir / --logs-specs)
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: RCCL needs it on this driver
-    env.setdefault("OMP_NUM_THREADS", str(max(1, (os.cpu_count() or 8) // args.gpus)))
-    proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True)
+    env.setdefault("OMP_NUM_THREADS", str(max(1, (os.cpu_count() or 8) // gpus)))
+    return subprocess.Popen(cmd, env=env, **popen)
+
+
+def self_launch(args, argv, script):
+    """Parent of an N-rank run.  Touches no GPU API; starts torch.distributed.run as a child and relays its output."""
+    proc = start_ranks(args.gpus, argv, script, stdout=subprocess.PIPE, text=True)
     line = None
     for out in proc.stdout:
         if out.lstrip().startswith("{") and '"metric"' in out:

@@ -21,15 +21,28 @@ over 500 iterations, 250000 iterations: config.py:397-415, :625), train.lr_at ea
     annotation file has annotations, the mAP file are written beside the weights under the reference's names -- the checkpoint's path with
     .pth replaced by .json and .txt (train.py:369, eval.py:573) -- and --log gains a line {"kind": "valid", "iteration", "metrics"}.  The
     reference also validates at iteration 100, a debugging leftover that is not reproduced.
-No DataParallel.
+  - --gpus N trains on N GPUs of this node, one process per GPU (stmask_amd.parallel): the parent touches no GPU
+    API and starts the ranks as child processes, as bench.py --gpus N does.  --batch_size stays the GLOBAL batch (what --autoscale sees); rank r
+    reads its equal share of each batch, or the slice --batch_alloc a,b,... gives it.  Every rank builds the net under the same seed, the
+    weights are broadcast from rank 0 and verified, and each step is forward, backward, ONE sum all-reduce over the flat gradient arena
+    (--backend nccl: RCCL; gloo: staged through the host) and the fused finish kernel of optim.DataParallelSGD; the printed loss terms are the
+    mean over the ranks.  Only rank 0 prints, logs, saves and validates; while it validates the others wait on a gloo side group.  --resume
+    loads the same file on every rank.  An augmented run seeds rank r's numpy stream with seed + r.  --share-gpu puts every rank on device 0
+    (gloo only: the form the tests use).  --gpus 1 is the single-process path, unchanged.
+Not built: overlap of the exchange with the backward pass, multi-GPU validation, more than one node.
     python scripts/train_ytvis.py ANN IMG_PREFIX [--config STMask_plus_resnet50_config] [--batch_size 4] [--iters 250000] [--backbone PATH]
-                                  [--save_folder weights/] [--resume latest] [--guard loss] [--log train.jsonl] [--extra_aug photo,expand,crop]"""
+                                  [--save_folder weights/] [--resume latest] [--guard loss] [--log train.jsonl] [--extra_aug photo,expand,crop]
+                                  [--gpus 8 [--backend nccl] [--batch_alloc 2,2,...]]"""
 import argparse
+import datetime
 import json
 import math
 import os
+import random
 import sys
 import time
+
+import numpy as np
 
 import torch
 
@@ -39,7 +52,8 @@ from stmask_amd import checkpoint, datasets, layers, validate  # noqa: E402
 from stmask_amd.config import get_cfg  # noqa: E402
 from stmask_amd.extra_aug import config_from_names  # noqa: E402
 from stmask_amd.model import STMask  # noqa: E402
-from stmask_amd.optim import GuardedSGD  # noqa: E402
+from stmask_amd.optim import DataParallelSGD, GuardedSGD  # noqa: E402
+from stmask_amd.parallel import DataParallelTrainer  # noqa: E402
 from stmask_amd.preprocess import MEANS  # noqa: E402
 from stmask_amd.train import LossLog, NetLoss, autoscale, lr_at, train_step  # noqa: E402
 
@@ -79,15 +93,72 @@ def parse_args(argv=None):
     ap.add_argument("--validation_interval", type=int, default=0, help="iterations between validations (0: off)")
     ap.add_argument("--eval_slots", type=int, default=8, help="videos in flight while validating")
     ap.add_argument("--eval_planes", choices=["fp16x2", "bf16x3", "fp16x1"], default="fp16x2", help="plane format of the twin's inference graph")
-    return ap.parse_args(argv)
+    ap.add_argument("--gpus", type=int, default=1, help="ranks of a data-parallel run on this node, one process per GPU")
+    ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="the gradient exchange of --gpus N > 1")
+    ap.add_argument("--batch_alloc", default=None, help="comma list, one entry per rank: the clips of each global batch a rank takes (default: equal)")
+    ap.add_argument("--share-gpu", action="store_true", help="every rank on device 0 (gloo only: the test form)")
+    args = ap.parse_args(argv)
+    if args.gpus < 1:
+        ap.error(f"--gpus {args.gpus}")
+    if args.batch_alloc is not None:
+        try:
+            args.batch_alloc = tuple(int(x) for x in args.batch_alloc.split(","))
+        except ValueError:
+            ap.error(f"--batch_alloc {args.batch_alloc}: a comma list of integers")
+        if len(args.batch_alloc) != args.gpus or min(args.batch_alloc) < 1 or sum(args.batch_alloc) != args.batch_size:
+            ap.error(f"--batch_alloc {args.batch_alloc}: one positive entry per rank of --gpus {args.gpus}, summing to --batch_size {args.batch_size}")
+    elif args.batch_size % args.gpus:
+        ap.error(f"--batch_size {args.batch_size} does not split evenly over --gpus {args.gpus} (give --batch_alloc)")
+    if args.share_gpu and args.gpus > 1 and args.backend != "gloo":
+        ap.error("--share-gpu needs --backend gloo (RCCL refuses two ranks on one device)")
+    return args
 
 
-def main():
-    args = parse_args()
+def make_optimizer(args, params, lr, rank=0):
+    """--gpus 1: the GuardedSGD of the single-process loop; more: one rank's DataParallelSGD."""
+    kw = dict(lr=lr, momentum=args.momentum, weight_decay=args.decay, guard=None if args.guard == "off" else args.guard)
+    return GuardedSGD(params, **kw) if args.gpus == 1 else DataParallelSGD(params, world=args.gpus, rank=rank, **kw)
+
+
+def make_loader(args, dataset, dev, rank=0):
+    shard = None if args.gpus == 1 else (rank, args.batch_alloc if args.batch_alloc is not None else args.gpus)
+    return datasets.TrainLoader(dataset, args.batch_size, seed=args.seed, device=dev, shard=shard)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    rank, world, side = 0, args.gpus, None
+    if world > 1 and "RANK" not in os.environ:
+        # the parent of the ranks: no GPU API here
+        from benchlib.launch import start_ranks
+        raise SystemExit(start_ranks(world, sys.argv[1:] if argv is None else argv, __file__).wait())
     dev = "cuda:0"
+    if world > 1:
+        import torch.distributed as dist
+        rank = int(os.environ["RANK"])
+        if int(os.environ["WORLD_SIZE"]) != world:
+            raise SystemExit(f"--gpus {world} under a launcher with WORLD_SIZE={os.environ['WORLD_SIZE']}")
+        dev = "cuda:0" if args.share_gpu else f"cuda:{int(os.environ.get('LOCAL_RANK', rank))}"
+        torch.cuda.set_device(dev)
+        dist.init_process_group(args.backend, timeout=datetime.timedelta(minutes=10))
+        # where the other ranks wait while rank 0 validates: gloo with a generous timeout (an RCCL barrier would hit the watchdog)
+        side = dist.new_group(backend="gloo", timeout=datetime.timedelta(hours=24))
+        np.random.seed(args.seed + rank)        # flip and ExtraAugmentation draws: each rank its own stream
+        random.seed(args.seed + rank)
+    chief = rank == 0
+
+    def say(*a):
+        if chief:
+            print(*a, flush=True)
+
+    def wait_for_chief():
+        if side is not None:
+            dist.barrier(group=side)
     lr, max_iter, lr_steps = (autoscale(args.lr, args.iters, args.lr_steps, args.batch_size) if args.autoscale
                               else (args.lr, args.iters, args.lr_steps))
     cfg = get_cfg(args.config)
+    if world > 1:
+        torch.manual_seed(args.seed)            # every rank builds the same net (the broadcast from rank 0 then changes nothing)
     net = STMask(cfg)
     torch.manual_seed(args.seed)
     if args.backbone:
@@ -95,12 +166,14 @@ def main():
     net = net.to(dev).train()
     crit = layers.MultiBoxLoss(cfg.num_classes, 0.5, 0.4, 3, temporal_fusion=cfg.temporal_fusion_module, max_pos=args.max_pos)
     net_loss = NetLoss(net, crit)
-    opt = GuardedSGD(net.parameters(), lr=lr, momentum=args.momentum, weight_decay=args.decay, guard=None if args.guard == "off" else args.guard)
+    opt = make_optimizer(args, net.parameters(), lr, rank)
+    trainer = DataParallelTrainer(net_loss, opt) if world > 1 else None      # weights from rank 0, verified equal
     extra_aug = config_from_names(args.extra_aug, MEANS)
-    loader = datasets.TrainLoader(datasets.YTVISTrainSet(args.ann, args.img_prefix, extra_aug=extra_aug), args.batch_size, seed=args.seed, device=dev)
+    loader = make_loader(args, datasets.YTVISTrainSet(args.ann, args.img_prefix, extra_aug=extra_aug), dev, rank)
     if len(loader) == 0:
         raise SystemExit(f"{len(loader.dataset)} frame pairs do not fill one batch of {args.batch_size}")
-    print(f"{len(loader.dataset)} frame pairs, {len(loader)} iterations per epoch, {math.ceil(max_iter / len(loader))} epochs")
+    say(f"{len(loader.dataset)} frame pairs, {len(loader)} iterations per epoch, {math.ceil(max_iter / len(loader))} epochs" +
+        (f", {world} ranks ({args.backend})" if world > 1 else ""))
     os.makedirs(args.save_folder, exist_ok=True)
 
     iteration = 0
@@ -115,13 +188,13 @@ def main():
         if not got["sidecar"]:
             # the reference's resume: the weights alone; the loader continues in the epoch the iteration falls into
             loader.load_state({"seed": args.seed, "epoch": iteration // len(loader), "batch": iteration % len(loader)})
-        print(f"resumed {resume} at iteration {iteration}" + ("" if got["sidecar"] else " (weights only: momentum starts at zero)"))
+        say(f"resumed {resume} at iteration {iteration}" + ("" if got["sidecar"] else " (weights only: momentum starts at zero)"))
     elif args.start_iter > 0:
         iteration = args.start_iter
     elif args.resume is not None:
-        print(f"--resume {args.resume}: nothing to resume in {args.save_folder}, starting at iteration 0")
+        say(f"--resume {args.resume}: nothing to resume in {args.save_folder}, starting at iteration 0")
 
-    log_file = open(args.log, "a" if resume is not None else "w") if args.log else None
+    log_file = open(args.log, "a" if resume is not None else "w") if args.log and chief else None
     loss_log, pending, skipped_seen = None, [], opt.counters()[1]
     last_time = time.time()
 
@@ -129,6 +202,9 @@ def main():
         """The loop's host read: the rows of the LossLog since the last one -> the printed line, the JSON lines, the skipped count."""
         nonlocal skipped_seen
         if loss_log is None or not pending:
+            return
+        if not chief:
+            pending.clear()
             return
         stats = loss_log.read()
         if log_file:
@@ -147,19 +223,32 @@ def main():
         pending.clear()
 
     def save(path):
+        if not chief:
+            return
         flush()
         print(f"saving {path}", flush=True)
         checkpoint.save(path, net, opt, iteration, epoch, loader)
 
     twin = valid_set = None
-    if args.valid_ann and args.validation_interval > 0:
+    validating = bool(args.valid_ann and args.validation_interval > 0)
+    if validating and chief:
         valid_set = datasets.YTVISValSet(args.valid_ann, args.valid_img_prefix, read_ahead=8)
         twin = validate.InferenceTwin(net, planes=args.eval_planes)
 
     def validate_at(path):
-        """The validation split under the names of the checkpoint `path`; the mAP file only when there is something to score."""
-        if twin is None:
+        """The validation split under the names of the checkpoint `path`; the mAP file only when there is something to score.  Rank 0 alone
+        validates; the other ranks wait for it on the side group."""
+        if not validating:
             return
+        if not chief:
+            wait_for_chief()
+            return
+        try:
+            validate_chief(path)
+        finally:
+            wait_for_chief()
+
+    def validate_chief(path):
         flush()
         out_json, metrics_file = validate.result_paths(path)
         scored = valid_set.has_annotations
@@ -181,17 +270,18 @@ def main():
                 cur = lr_at(iteration, lr, args.gamma, lr_steps, args.lr_warmup_until, args.lr_warmup_init)
                 for group in opt.param_groups:
                     group["lr"] = cur
-                losses = train_step(net_loss, opt, batch)
-                if loss_log is None:
-                    loss_log = LossLog(list(losses), capacity=4 * READ_EVERY)
-                loss_log.append(losses)
+                losses = train_step(net_loss, opt, batch) if trainer is None else trainer.step(batch)
+                if chief:
+                    if loss_log is None:
+                        loss_log = LossLog(list(losses), capacity=4 * READ_EVERY)
+                    loss_log.append(losses)
                 now = time.time()
                 pending.append((iteration, epoch, cur, now - last_time))
                 last_time = now
                 if iteration % READ_EVERY == 0:
                     flush()
                 iteration += 1
-                if args.save_interval > 0 and iteration % args.save_interval == 0 and iteration < max_iter:
+                if chief and args.save_interval > 0 and iteration % args.save_interval == 0 and iteration < max_iter:
                     latest = checkpoint.get_latest(args.save_folder, cfg.name) if args.keep_latest else None
                     path = checkpoint.save_path(cfg.name, epoch, iteration, args.save_folder)
                     save(path)
@@ -199,11 +289,12 @@ def main():
                                                                   iteration % args.keep_latest_interval != args.save_interval):
                         print(f"deleting {latest}", flush=True)
                         checkpoint.remove(latest)
-                if twin is not None and iteration % args.validation_interval == 0 and iteration < max_iter:
+                if validating and iteration % args.validation_interval == 0 and iteration < max_iter:
                     validate_at(checkpoint.save_path(cfg.name, epoch, iteration, args.save_folder))
     except KeyboardInterrupt:
-        print("interrupted: saving", flush=True)
-        checkpoint.remove_interrupt(args.save_folder)
+        say("interrupted: saving")
+        if chief:
+            checkpoint.remove_interrupt(args.save_folder)
         save(checkpoint.save_path(cfg.name, epoch, iteration, args.save_folder, interrupt=True))
         raise SystemExit(130)
     save(checkpoint.save_path(cfg.name, epoch, iteration, args.save_folder))
@@ -212,6 +303,9 @@ def main():
         valid_set.close()
     if log_file:
         log_file.close()
+    if world > 1:
+        wait_for_chief()                # the last save is on disk before any rank leaves
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -233,11 +233,24 @@ FOLD_SIGNATURES = {
 FOLD_MAX_ROWS = 64   # csrc/fold.h STM_FOLD_MAX_ROWS
 FOLD_CHUNK = 4096    # csrc/fold.h STM_FOLD_CHUNK
 FOLD_COPY, FOLD_WEIGHT, FOLD_BIAS = 0, 1, 2   # csrc/fold.h STM_FOLD_COPY / _WEIGHT / _BIAS
+# ... and that of csrc/dp_step.h: the finish of a data-parallel training step (optim.py DataParallelSGD).  A fourth private table, kept beside
+# the three above (private_tables() stays what the training loop and the twin bind); dp_tables() lists it, private_call() resolves it and
+# build() walks it too.
+DP_SIGNATURES = {
+    "stm_dp_sgd_finish_multi_f32": ("i", "ppppipppiffffp"),
+}
+DP_MAX_TENSORS = 64   # csrc/dp_step.h STM_DP_MAX_TENSORS
+DP_CHUNK = 4096       # csrc/dp_step.h STM_DP_CHUNK
 
 
 def private_tables():
     """{header under csrc/: its table} of every package-private header."""
     return {**PRIVATE_TABLES, "fold.h": FOLD_SIGNATURES}
+
+
+def dp_tables():
+    """{header under csrc/: its table} of the data-parallel step's package-private header."""
+    return {"dp_step.h": DP_SIGNATURES}
 
 
 _private_calls = {}   # name -> (function, argument count) for private_call()
@@ -386,11 +399,11 @@ def call(name, *args):
 
 
 def private_call(name, *args):
-    """call() for an entry of PRIVATE_SIGNATURES, AUG_SIGNATURES or FOLD_SIGNATURES: restype / argtypes are set from the table when the entry is
-    first used."""
+    """call() for an entry of PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES or DP_SIGNATURES: restype / argtypes are set from the table when
+    the entry is first used."""
     got = _private_calls.get(name)
     if got is None:
-        ret, params = next(table[name] for table in (PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES) if name in table)
+        ret, params = next(table[name] for table in (PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES, DP_SIGNATURES) if name in table)
         fn = getattr(lib(), name, None)
         if fn is None:
             raise StmError(f"{LIB_PATH} lacks {name}: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")

@@ -11,7 +11,7 @@ INTEGRATION.md section 20 is the contract.  There is no CPU fallback for the dev
 Scope: the reference's training configs -- img_scale=[(640, 360)], resize_keep_ratio=False, size_divisor=32, flip_ratio=0.5, to_rgb=True,
 with_track=True, clip_frames=1, and extra_aug=None or the reference's dict: ExtraAugmentation's parameters are drawn on the host (extra_aug.py)
 and its pixel work is done inside the frame and mask kernels (csrc/extra_aug.hip).  Not built: aug_ref_bbox_param,
-proposals, keep_ratio=True, more than one img_scale, DataParallel.
+proposals, keep_ratio=True, more than one img_scale.  One rank's share of a batch in a data-parallel run: TrainLoader(shard=...).
 
 YTVISValSet / LazyVideo at the end of the file are the test-mode half: the videos of a validation split in the form
 serve.VideoBatcher.run takes, every frame read when the batcher asks for it.
@@ -538,12 +538,30 @@ class TrainLoader:
     the step the caller queued for batch k.  Batches are collated with check="deferred"; the status of batch k is looked at when batch k + 1 is
     asked for (and that of the last batch when the epoch ends), so a loop with max_pos=K never waits for the device here.
     state() is where the run stands -- seed, epoch, batches of that epoch already handed out -- and the next __iter__ after load_state(state)
-    continues there: the order is a pure function of seed + epoch, and the records of the batches passed over are neither read nor collated."""
+    continues there: the order is a pure function of seed + epoch, and the records of the batches passed over are neither read nor collated.
+    shard=(rank, world) or shard=(rank, batch_alloc) is one rank of a data-parallel run (stmask_amd.parallel): batch_size stays the GLOBAL
+    batch, and the order, len(), state() and load_state() are those of the unsharded loader (one sidecar resumes every rank); the rank reads and
+    collates only its contiguous share of each global batch -- the equal split, or the slice batch_alloc = (a, b, ...) gives it (the reference's
+    --batch_alloc; the entries sum to batch_size).  share is that slice of a batch as (begin, end)."""
 
-    def __init__(self, dataset, batch_size, shuffle=True, seed=0, device=None, max_gt=None):
+    def __init__(self, dataset, batch_size, shuffle=True, seed=0, device=None, max_gt=None, shard=None):
         if batch_size < 1:
             raise ValueError(f"TrainLoader: batch_size={batch_size}")
         self.dataset, self.batch_size, self.shuffle, self.seed, self.device, self.max_gt = dataset, int(batch_size), shuffle, seed, device, max_gt
+        self.shard, self.share = shard, (0, self.batch_size)
+        if shard is not None:
+            rank, second = shard
+            if isinstance(second, int):
+                if second < 1 or self.batch_size % second:
+                    raise ValueError(f"TrainLoader: batch_size={batch_size} does not split evenly over {second} ranks (give a batch_alloc)")
+                alloc = [self.batch_size // second] * second
+            else:
+                alloc = [int(a) for a in second]
+                if not alloc or min(alloc) < 1 or sum(alloc) != self.batch_size:
+                    raise ValueError(f"TrainLoader: batch_alloc={tuple(second)} must be positive and sum to batch_size={batch_size}")
+            if not 0 <= rank < len(alloc):
+                raise ValueError(f"TrainLoader: rank={rank} of {len(alloc)}")
+            self.share = (sum(alloc[:rank]), sum(alloc[:rank + 1]))
         self.epoch = 0
         self.batch = 0          # batches of the running epoch (self.epoch - 1) handed out so far
         self._resume = None     # (epoch, batch) load_state asked the next __iter__ to continue at
@@ -576,6 +594,10 @@ class TrainLoader:
         g.manual_seed(self.seed + epoch)
         return torch.randperm(n, generator=g).tolist()
 
+    def indices(self, order, k):
+        """The dataset indices this loader reads for batch k of an epoch's `order`: the whole batch, or the rank's share of it."""
+        return order[k * self.batch_size + self.share[0]:k * self.batch_size + self.share[1]]
+
     def __iter__(self):
         first = 0
         if self._resume is not None:
@@ -586,7 +608,7 @@ class TrainLoader:
         pending = None
         for k in range(first, len(self)):
             self.batch = k + 1
-            records = [self.dataset[i] for i in order[k * self.batch_size:(k + 1) * self.batch_size]]
+            records = [self.dataset[i] for i in self.indices(order, k)]
             *batch, status = collate_device(records, self.device, self.max_gt, check="deferred")
             if pending is not None:
                 pending.raise_if_bad()

@@ -177,3 +177,130 @@ class GuardedSGD(torch.optim.Optimizer):
             if v.get("momentum_buffer") is not None:
                 state[k] = {"momentum_buffer": v["momentum_buffer"]}
         super().load_state_dict({"state": state, "param_groups": groups})
+
+
+class DataParallelSGD(GuardedSGD):
+    """GuardedSGD for one rank of a data-parallel run (stmask_amd.parallel): the same arguments and validation, plus world and rank.  It owns two
+    parallel.GradArena of one layout over the trainable parameters: `grads` (every p.grad is a view of its segment, so autograd accumulates in
+    place; the tail carries the loss) and `momentum` (its views are the momentum_buffer entries of the state, in torch.optim.SGD's layout, so a
+    checkpoint keeps its format and loads either way).  Between backward and step(), parallel.exchange(opt.grads) sums the arena over the ranks.
+    step() is then csrc/dp_step.hip: per element  g = s * inv_world;  g' = g + wd * p;  m = mu * m + g';  p = p - lr * m  with s the summed
+    gradient and inv_world the fp32 value of 1 / world, and 0.0f written back over every gradient element -- also when the guard skips the step,
+    so zero_grad() has nothing left to do and a NaN never survives into the next iteration.  The guard reads the reduced tail slot 0 (the sum of
+    the ranks' losses; not finite as soon as one rank's is) and, with guard="grads", a flag that one pass of stm_grads_nonfinite_multi_f32 over
+    the reduced arena sets: functions of the reduced buffer alone, so every rank decides alike and the weights cannot drift apart.
+    One difference from GuardedSGD: every trainable parameter steps in every applied iteration, with g = 0 when no gradient reached it, so weight
+    decay and momentum still act on it (as under torch's DistributedDataParallel, whose buckets are zero-filled)."""
+
+    def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, guard="loss", world=1, rank=0, n_tail=8):
+        super().__init__(params, lr, momentum=momentum, weight_decay=weight_decay, guard=guard)
+        if not (isinstance(world, int) and isinstance(rank, int) and world >= 1 and 0 <= rank < world):
+            raise ValueError(f"DataParallelSGD: world={world!r} rank={rank!r}")
+        if n_tail < 1:
+            raise ValueError(f"DataParallelSGD: n_tail={n_tail}, slot 0 carries the loss")
+        from .parallel import GradArena
+        import numpy as np
+        self.world, self.rank = world, rank
+        self.inv_world = float(np.float32(1.0) / np.float32(world))
+        self.trainable = [p for p in self._all_params() if p.requires_grad]
+        self.grads = GradArena(self.trainable, n_tail, self.device)
+        self.momentum = GradArena(self.trainable, 0, self.device)
+        self.grads.bind_grads()
+        for p, m in zip(self.trainable, self.momentum.views):
+            self.state[p]["momentum_buffer"] = m
+        self._tables = None      # (the parameters' addresses, [(group, [ctypes arrays and count per launch])])
+
+    def zero_grad(self, set_to_none=True):
+        """Nothing: the finish kernel has cleared the arena, and the views stay bound."""
+
+    def _build_tables(self, ptrs):
+        slot = {id(p): i for i, p in enumerate(self.trainable)}
+        out = []
+        for group in self.param_groups:
+            rows = [slot[id(p)] for p in group["params"] if id(p) in slot]
+            launches = []
+            for k in range(0, len(rows), MAX_TENSORS):
+                part = rows[k:k + MAX_TENSORS]
+                n = len(part)
+                launches.append(((c_p * n)(*[ptrs[i] for i in part]), (c_p * n)(*[self.grads.views[i].data_ptr() for i in part]),
+                                 (c_p * n)(*[self.momentum.views[i].data_ptr() for i in part]),
+                                 (ctypes.c_int64 * n)(*[self.trainable[i].numel() for i in part]), n))
+            if launches:
+                out.append((group, launches))
+        return out
+
+    @torch.no_grad()
+    def step(self, loss=None, closure=None):
+        """The finish of one iteration, after parallel.exchange(self.grads); no host synchronisation.  The loss is not an argument: it travels in
+        the arena's tail (train.train_step_dp writes it)."""
+        if closure is not None or loss is not None:
+            raise ValueError("DataParallelSGD.step: takes no loss and no closure (the loss travels in the tail of the gradient arena: "
+                             "train.train_step_dp)")
+        if self.device.type != "cuda":
+            raise StmError("DataParallelSGD.step: the parameters are on the CPU; the step is a HIP kernel for the MI355X and there is no CPU fallback")
+        for i, (p, g, m) in enumerate(zip(self.trainable, self.grads.views, self.momentum.views)):
+            if p.grad is not g or self.state[p].get("momentum_buffer") is not m:
+                raise ValueError(f"DataParallelSGD.step: trainable parameter {i}: its gradient or momentum buffer is no longer the arena's view "
+                                 "(zero the gradients through this optimizer, not with set_to_none on the module)")
+        ptrs = [p.data_ptr() for p in self.trainable]
+        if self._tables is None or self._tables[0] != ptrs:
+            for i, p in enumerate(self.trainable):
+                if not (_dense(p) and _layout(p) == _layout(self.grads.views[i])):
+                    raise ValueError(f"DataParallelSGD.step: trainable parameter {i} changed its layout since the arena was laid out")
+            self._tables = (ptrs, self._build_tables(ptrs))
+        counters = c_p(self.counters_tensor.data_ptr())
+        loss_ptr = c_p(self.grads.tail.data_ptr()) if self.guard is not None else None
+        bad_ptr = None
+        with torch.cuda.device(self.device):
+            stream = _raw_stream()
+            if self.guard == "grads":
+                if self._bad is None:
+                    self._bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+                bad_ptr = c_p(self._bad.data_ptr())
+                flat = self.grads.flat
+                _lib.private_call("stm_grads_nonfinite_multi_f32", (c_p * 1)(flat.data_ptr()), (ctypes.c_int64 * 1)(flat.numel()), 1, bad_ptr, 1,
+                                  stream)
+            first = 1
+            for group, launches in self._tables[1]:
+                lr, mu, wd = float(group["lr"]), float(group["momentum"]), float(group["weight_decay"])
+                for p_arr, g_arr, m_arr, n_arr, n in launches:
+                    _lib.private_call("stm_dp_sgd_finish_multi_f32", p_arr, g_arr, m_arr, n_arr, n, loss_ptr, bad_ptr, counters, first,
+                                      self.inv_world, lr, mu, wd, stream)
+                    first = 0
+        return None
+
+    # ---- state dicts: torch.optim.SGD's layout -------------------------------------------------------------------------------------
+    def state_dict(self):
+        """torch.optim.SGD's layout; the momentum buffers are copies (a saved view would carry the whole arena's storage)."""
+        sd = super().state_dict()
+        sd["state"] = {k: {"momentum_buffer": v["momentum_buffer"].clone()} for k, v in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """Takes its own, GuardedSGD's and torch.optim.SGD's state dict: the momentum is copied into the arena (a missing or None buffer: zeros),
+        group keys this class does not know are dropped; dampening != 0, nesterov and maximize are refused."""
+        saved = state_dict["param_groups"]
+        if len(saved) != len(self.param_groups) or any(len(s["params"]) != len(g["params"]) for s, g in zip(saved, self.param_groups)):
+            raise ValueError("DataParallelSGD.load_state_dict: the state dict's parameter groups do not match this optimizer's")
+        for gi, group in enumerate(saved):
+            if group.get("dampening", 0) != 0 or group.get("nesterov", False) or group.get("maximize", False):
+                raise ValueError(f"DataParallelSGD.load_state_dict: group {gi} has dampening={group.get('dampening', 0)} "
+                                 f"nesterov={group.get('nesterov', False)} maximize={group.get('maximize', False)}; the step is built for "
+                                 "dampening 0, no Nesterov term, minimize")
+        state = state_dict.get("state", {})
+        view = {id(p): m for p, m in zip(self.trainable, self.momentum.views)}
+        with torch.no_grad():
+            for group, mine in zip(saved, self.param_groups):
+                mine.update({k: v for k, v in group.items() if k != "params" and k in self.defaults})
+                for key, p in zip(group["params"], mine["params"]):
+                    m = view.get(id(p))
+                    if m is None:
+                        continue
+                    got = (state.get(key) or {}).get("momentum_buffer")
+                    if got is None:
+                        m.zero_()
+                    elif got.shape != m.shape:
+                        raise ValueError(f"DataParallelSGD.load_state_dict: momentum buffer {key} is {tuple(got.shape)}, the parameter "
+                                         f"{tuple(m.shape)}")
+                    else:
+                        m.copy_(got)

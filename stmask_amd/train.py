@@ -2,13 +2,15 @@
 train_step runs one optimizer step; lr_at and autoscale restate its learning-rate schedule (train.py:88-96, :293-302) as pure functions.  The
 batches come from stmask_amd.datasets (YTVISTrainSet, TrainLoader, collate_device) or synthetic.synthetic_train_batch; scripts/train_ytvis.py
 puts the pieces together with optim.GuardedSGD (the step guarded on the device), LossLog below, stmask_amd.checkpoint and the validation-mAP
-hook of stmask_amd.validate.  DataParallel is not built."""
+hook of stmask_amd.validate.  train_step_dp is the step of one rank of a data-parallel run (stmask_amd.parallel, optim.DataParallelSGD;
+scripts/train_ytvis.py --gpus N).  Not built: overlap of the gradient exchange with the backward pass, multi-GPU validation, more than one node."""
 import math
 
 import torch
 import torch.nn as nn
 
 from .optim import GuardedSGD
+from .parallel import exchange
 
 
 class NetLoss(nn.Module):
@@ -37,6 +39,26 @@ def train_step(net_loss, optimizer, batch):
     else:
         optimizer.step()
     return {k: v.detach() for k, v in losses.items()}
+
+
+def train_step_dp(net_loss, optimizer, batch, loss_log=None, group=None):
+    """One step of one rank, optimizer an optim.DataParallelSGD: forward on the rank's share of the batch, backward through the sum of the local
+    loss terms (into the gradient arena), the tail write (slot 0 that sum, slots 1.. the terms in the criterion's key order), parallel.exchange
+    -- the step's one collective -- and optimizer.step().  No host wait.  Returns the rank-MEAN loss terms (the reference's losses.mean(),
+    train.py:310): the reduced tail times the fp32 value of 1 / world, 0-dim device tensors; loss_log.append gets the same dict."""
+    losses = net_loss(*batch)
+    keys = list(losses)
+    total = sum(losses.values())
+    total.backward()
+    arena = optimizer.grads
+    arena.write_tail([total] + [losses[k] for k in keys])
+    exchange(arena, group)
+    mean = arena.tail[1:1 + len(keys)] * optimizer.inv_world
+    optimizer.step()
+    out = {k: mean[i] for i, k in enumerate(keys)}
+    if loss_log is not None:
+        loss_log.append(out)
+    return out
 
 
 class LossLog:

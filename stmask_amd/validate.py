@@ -15,7 +15,7 @@ stale, and the twin refuses to run it.
 the twin into the results JSON, score it with eval_utils.calc_metrics when there is an annotation file.  The live net is never switched to
 eval; its parameters, buffers, flags, the optimizer state and the random generators are as they were.
 
-Not built: DataParallel / multi-GPU validation, iouType='bbox', compute_validation_loss, in-place update of the packed planar weights."""
+Not built: multi-GPU validation, iouType='bbox', compute_validation_loss, in-place update of the packed planar weights."""
 import copy
 import ctypes
 
