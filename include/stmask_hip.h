@@ -87,6 +87,27 @@ void stm_debug_reload_tunables(void);
  * which = 0 conv_planar_kx3_kernel (kx-reuse staging of the 256 x 128 ring tiles), 1 dcn_fused_kernel (the fused deformable
  * convolution); -1 for anything else. */
 long long stm_debug_launch_count(int which);
+/* Diagnostics: dry run of stm_conv2d_planar_ws_f32 / _dual_f32 / _windows_f32 / _windows_pool_f32 (declared below; csrc/conv_plan.h has the rules).
+ * The arguments are those entries': windows non-NULL selects the window entries (packed_weights / windows / n_windows; pool_fix non-NULL the pooled
+ * one), else x2_planes non-NULL the two-source entry (C2 .. x2_plane_stride), else stm_conv2d_planar_ws_f32; gate non-NULL is a pixel gate set in
+ * front of the call (stm_conv_set_pixel_gate).  The same checks and the same launch plan run, nothing is launched and no tensor is read: only
+ * whether a pointer is NULL and how it is aligned matters (packed_weights and windows are host arrays and are read).  Returns the status the call
+ * would return, with its stm_last_error_string, and writes into text (text_bytes bytes, 0-terminated; STM_EINVAL if too short) one line per launch
+ * the call would make, in order:
+ *   conv_planar_kernel<NPL,MG,NJ,DT,ST,ABL,DUAL,CLS> grid=.. block=.. lds=.. splitk=.. kslabs=.. m_tiles=.. n_tiles=.. [cls=tile0:M,tile0:M,..]
+ *   conv_planar_kx3_kernel<ABL,WIN> grid=.. block=.. lds=.. splitk=.. kslabs=.. m_tiles=.. n_tiles=.. [cls=..]
+ *   planar_splitk_finish_kernel grid=.. block=256 lds=0
+ * (lds = dynamic LDS bytes; cls = first tile and pixel count of every class of a window set).  Needs no device.
+ * The calling thread's pixel gate is REPLACED by `gate` for the dry run and is unset when it returns, also when gate is NULL: a gate set with
+ * stm_conv_set_pixel_gate for a later real launch does not survive this call. */
+struct stm_conv_geom;
+struct stm_conv_window;
+int stm_debug_conv2d_planar_plan(const void* x_planes, const void* packed_weight, const float* bias, const float* residual_f32,
+                                 const void* residual_planes, float* out_f32, void* out_planes, const struct stm_conv_geom* g, int relu,
+                                 void* workspace, size_t workspace_bytes, const void* x2_planes, int C2, int H2, int W2, int s2,
+                                 long long x2_np, long long x2_plane_stride, const void* const* packed_weights,
+                                 const struct stm_conv_window* windows, int n_windows, unsigned long long* pool_fix, const int* gate, char* text,
+                                 size_t text_bytes);
 
 /* ---------------------------------------------------------------------------------------------------
  * Deformable convolution.

@@ -26,6 +26,7 @@ SIGNATURES = {
     "stm_struct_bytes": ("z", "i"),
     "stm_debug_reload_tunables": ("v", ""),
     "stm_debug_launch_count": ("q", "i"),
+    "stm_debug_conv2d_planar_plan": ("i", "ppppppppipzpiiiiqqppipppz"),
     "stm_conv_kxr_tile_pixels": ("i", "iii"),
     "stm_conv_kxr_packed_bytes": ("z", "p"),
     "stm_conv_pack_weights_kxr_f32": ("i", "pppfp"),

@@ -16,11 +16,17 @@
 // producer's epilogue, and staging a K-slab (one tap, 32 channels) is pure LDS-DMA.  Tiles: 128*MG pixels x 64*NJ channels, 4*MG
 // waves; LDS rows of 64 B with the 16-B chunk index XORed by f((row >> 2) & 3), conflict-free for the 16x16x32 fragment reads;
 // two LDS buffers, or a three-buffer ring with fragment prefetch (fp16 formats); split-K for grids that would idle the chip.
+// Which kernel a layer gets and how it is cut -- split-K, the pixel-tile choice, ring or two-buffer loop, the kx-reuse form -- is decided in
+// conv_plan.h (host only); conv2d_planar_impl below is validate, plan, run, and stm_debug_conv2d_planar_plan prints a call's plan.
 // DESIGN.md section 4 has the history of this kernel and what bounds it.  The producers of the plane layouts that are not
 // convolutions (split, resize, RoI features, stem patches) and the weight packer live in planar_prep.hip.
 #include "planar_common.h"
+#include "conv_plan.h"
+#include <stdarg.h>
 #include <algorithm>
+#include <array>
 #include <type_traits>
+#include <utility>
 #include <atomic>
 
 namespace {
@@ -932,6 +938,9 @@ constexpr int KX3_LDS_LOOP = KX3_W0 + 3 * KX3_WBUF;
 #ifndef KX3_ABL
 #define KX3_ABL 0        // timing builds (RESULTS WRONG): 1 no DMA at all, 2 no activation DMA, 4 no fragment reads, 8 every stage stages channel slab 0 (L2-resident rows), 16 activation pieces read weight bytes instead (same count of DMAs, hot lines), 32 activation pieces land behind the weight ring (another LDS region), 64 the ring pre-filled once with random fp16 values
 #endif
+#ifndef CLS_ABL
+#define CLS_ABL 0     // timing build (RESULTS WRONG): 16 = the window-set kernel issues its activation DMAs on every third K-slab only
+#endif
 template <int ABL = 0, bool WIN = false>
 __global__ __launch_bounds__(512, 1) void conv_planar_kx3_kernel(const typename std::conditional<WIN, PlanarArgsCls, PlanarArgs>::type a_in)
 {
@@ -1254,20 +1263,11 @@ __global__ __launch_bounds__(512, 1) void conv_planar_kx3_kernel(const typename 
 
 // Launch tunables: read from the environment ONCE (first launch), never per launch.  Defaults are the measured best (DESIGN.md
 // section 9); the variables exist for A/B runs.  stm_debug_reload_tunables() (capi.hip) makes the next launch re-read them.
+// ConvTunables itself, and every rule that reads it, is in conv_plan.h.
 std::atomic<long long> g_kx3_launches{0};      // stm_debug_launch_count(0)
-// Constants that were switches until round 6 (DESIGN.md section 9 keeps what their alternatives measured):
-constexpr int CV_RING64_SMALL = 512;   // grids up to this many workgroups take the ring on 128 x 64 tiles whatever K (round 2 sweep)
-constexpr int CV_SK_TARGET = 256;      // workgroups the split-K rule of the 64-wide tiles aims at (one per CU)
-// (removed with their code in round 7: round 1's split-K rule for every layer, nontemporal plane stores for large outputs -- no gain
-// measured in rounds 2-4 --, the element-wise epilogue as a cross-check form, the regrouped tile map)
-struct ConvTunables {
-    int ring = 3;          // STM_CONV_RING: 2 = two-buffer loop on the 128-wide tiles, 3 = three-buffer ring (fp16 formats)
-    int ring64 = 3;        // STM_CONV_RING64: 2 never / 4 always the ring on 128 x 64 tiles, 3 = by K length (rule below)
-    int splitk = 0;        // STM_CONV_SPLITK: force this many K parts (0 = rule)
-    int mg = 0;            // STM_CONV_MG: force 128 (1) or 256 (2) pixel tiles
-    int abl = 0;           // STM_CONV_ABL (builds with -DSTM_ABLATE only)
-    int kx3 = 1;           // STM_CONV_KX3: 0 = stride-1 kw = 3 layers on the 256 x 128 ring tiles stay on conv_planar_kernel (1: conv_planar_kx3_kernel, kx-reuse staging)
-};
+using conv_plan::ConvFacts;
+using conv_plan::ConvPlan;
+using conv_plan::ConvTunables;
 ConvTunables read_tunables()
 {
     ConvTunables t;
@@ -1291,17 +1291,111 @@ const ConvTunables& tunables()
     return t;
 }
 
-template <int NPL, int MG, int NJ, int DT = 0, int ST = 2, int ABL = 0, bool DUAL = false, int CLS = 0>
-int launch_planar(const typename planar_args<CLS>::type& a, int tiles, stm_stream_t stream)
+static_assert(conv_plan::BM == CV_BM && conv_plan::KX3_WBUF == KX3_WBUF && conv_plan::KX3_LDS_LOOP == KX3_LDS_LOOP, "conv_plan.h restates the kernels' tile constants");
+
+// One launch of this file's convolution kernels: the plan and the arguments.  PlanarArgsSeg has the argument type of every instantiation as a
+// base; a launcher passes the kernel its own part.  planned: the plan is set and the launch is to be made (a window set may leave one of its two empty).
+struct Launch { ConvPlan plan; PlanarArgsSeg args; bool planned = false; };
+using LaunchFn = int (*)(const Launch&, stm_stream_t);
+
+template <int NPL, int MG, int NJ, int DT, int ST, int ABL, bool DUAL, int CLS>
+int launch_planar(const Launch& l, stm_stream_t stream)
 {
-    size_t lds = (size_t)ST * (NPL * CV_BM * MG * 64 + NPL * (64 * NJ) * 64);
-    const size_t park = (size_t)4 * MG * 64 * (32 * NJ + 4) * sizeof(float);   // the epilogue parks one 64 x 32NJ tile per wave
-    if (lds < park) lds = park;
-    const int rc = stm_reserve_lds<conv_planar_kernel<NPL, MG, NJ, DT, ST, ABL, DUAL, CLS>>(lds, "stm_conv2d_planar_f32");
+    const typename planar_args<CLS>::type& a = l.args;
+    const int rc = stm_reserve_lds<conv_planar_kernel<NPL, MG, NJ, DT, ST, ABL, DUAL, CLS>>(l.plan.lds, "stm_conv2d_planar_f32");
     if (rc != STM_OK) return rc;
-    hipLaunchKernelGGL((conv_planar_kernel<NPL, MG, NJ, DT, ST, ABL, DUAL, CLS>), dim3(8 * stm_cdiv(tiles, 8)), dim3(256 * MG), lds, stm_hs(stream), a);
+    hipLaunchKernelGGL((conv_planar_kernel<NPL, MG, NJ, DT, ST, ABL, DUAL, CLS>), dim3(l.plan.grid), dim3(l.plan.block), l.plan.lds, stm_hs(stream), a);
     STM_CHECK_LAUNCH("conv_planar_kernel");
     return STM_OK;
+}
+template <bool WIN>
+int launch_kx3(const Launch& l, stm_stream_t stream)
+{
+    const typename std::conditional<WIN, PlanarArgsCls, PlanarArgs>::type& a = l.args;
+    const int rc = stm_reserve_lds<conv_planar_kx3_kernel<KX3_ABL, WIN>>(l.plan.lds, "stm_conv2d_planar_f32");
+    if (rc != STM_OK) return rc;
+    hipLaunchKernelGGL((conv_planar_kx3_kernel<KX3_ABL, WIN>), dim3(l.plan.grid), dim3(512), l.plan.lds, stm_hs(stream), a);
+    STM_CHECK_LAUNCH(WIN ? "conv_planar_kx3_kernel<WIN>" : "conv_planar_kx3_kernel");
+    return STM_OK;
+}
+
+// ---- the kernels this library ships, written once -------------------------------------------------------------------------------------
+// conv_planar_kernel<NPL, MG, NJ, DT, ST, ABL, DUAL> for one layer: a row here is an instantiation in the code object, and a plan
+// (conv_plan.h: plan_conv) whose tuple has no row is refused.  Beside them four fixed entries: the window set (CLS = 1), the gated window
+// set (CLS = 2) and conv_planar_kx3_kernel for a layer and for a window set.
+struct PlanarRow { int npl, mg, nj, dt, st, abl; bool dual; };
+constexpr PlanarRow PLANAR_ROWS[] = {
+    // 128 x 64 tiles: bf16 x 3 / its three-product mode, fp16 x 2 and fp16 x 1 on the two-buffer loop and the ring, with a second source
+    {3, 1, 1, 0, 2, 0, false}, {2, 1, 1, 0, 2, 0, false},
+    {2, 1, 1, 1, 2, 0, false}, {2, 1, 1, 1, 3, 0, false}, {1, 1, 1, 1, 2, 0, false}, {1, 1, 1, 1, 3, 0, false},
+    {2, 1, 1, 1, 2, 0, true}, {2, 1, 1, 1, 3, 0, true}, {1, 1, 1, 1, 2, 0, true}, {1, 1, 1, 1, 3, 0, true},
+    // 128 and 256 x 128 tiles
+    {3, 1, 2, 0, 2, 0, false}, {3, 2, 2, 0, 2, 0, false}, {2, 1, 2, 0, 2, 0, false}, {2, 2, 2, 0, 2, 0, false},
+    {2, 1, 2, 1, 2, 0, false}, {2, 2, 2, 1, 2, 0, false}, {2, 1, 2, 1, 3, 0, false}, {2, 2, 2, 1, 3, 0, false},
+    {1, 1, 2, 1, 2, 0, false}, {1, 2, 2, 1, 2, 0, false}, {1, 1, 2, 1, 3, 0, false}, {1, 2, 2, 1, 3, 0, false},
+    {2, 1, 2, 1, 3, 0, true}, {2, 2, 2, 1, 3, 0, true}, {1, 1, 2, 1, 3, 0, true}, {1, 2, 2, 1, 3, 0, true},
+#ifdef STM_ABLATE
+    // timing ablations of the ring loop (STM_CONV_ABL): RESULTS ARE WRONG
+    {2, 2, 2, 1, 3, 1, false}, {2, 2, 2, 1, 3, 2, false}, {2, 2, 2, 1, 3, 3, false}, {2, 2, 2, 1, 3, 5, false}, {2, 2, 2, 1, 3, 7, false},
+    {2, 2, 2, 1, 3, 8, false}, {2, 2, 2, 1, 3, 16, false}, {2, 2, 2, 1, 3, 32, false}, {2, 2, 2, 1, 3, 64, false},
+#endif
+};
+constexpr size_t N_PLANAR_ROWS = sizeof(PLANAR_ROWS) / sizeof(PLANAR_ROWS[0]);
+template <size_t I>
+int launch_row(const Launch& l, stm_stream_t stream)
+{
+    constexpr PlanarRow r = PLANAR_ROWS[I];
+    return launch_planar<r.npl, r.mg, r.nj, r.dt, r.st, r.abl, r.dual, 0>(l, stream);
+}
+template <size_t... I>
+constexpr std::array<LaunchFn, sizeof...(I)> row_launchers(std::index_sequence<I...>) { return {{launch_row<I>...}}; }
+constexpr std::array<LaunchFn, N_PLANAR_ROWS> PLANAR_LAUNCHERS = row_launchers(std::make_index_sequence<N_PLANAR_ROWS>{});
+constexpr LaunchFn CLS_LAUNCHERS[2] = {launch_planar<2, 2, 2, 1, 3, CLS_ABL, false, 1>, launch_planar<2, 2, 2, 1, 3, 0, false, 2>};
+constexpr LaunchFn KX3_LAUNCHERS[2] = {launch_kx3<false>, launch_kx3<true>};
+
+// The dry run (stm_debug_conv2d_planar_plan): while the calling thread has a PlanText, a launch is written into it as one line and not made.
+struct PlanText {
+    char* buf; size_t cap, len; bool cut;
+    void add(const char* fmt, ...) __attribute__((format(printf, 2, 3)))
+    {
+        va_list ap;
+        va_start(ap, fmt);
+        const int n = vsnprintf(buf + len, cap - len, fmt, ap);
+        va_end(ap);
+        if (n < 0 || (size_t)n >= cap - len) { cut = true; len = cap - 1; } else len += (size_t)n;
+    }
+};
+thread_local PlanText* t_plan_text = nullptr;
+
+// a launch as a line: the kernel with its template arguments, the grid, what the kernel reads of the cut, a window set's classes as tile0:M
+void write_launch(PlanText& t, const Launch& l)
+{
+    const ConvPlan& p = l.plan;
+    if (p.kx3) t.add("conv_planar_kx3_kernel<%d,%d>", KX3_ABL, p.cls ? 1 : 0);
+    else t.add("conv_planar_kernel<%d,%d,%d,%d,%d,%d,%d,%d>", p.npl, p.mg, p.nj, p.dt, p.st, p.abl, (int)p.dual, p.cls);
+    t.add(" grid=%u block=%u lds=%zu splitk=%d kslabs=%d m_tiles=%d n_tiles=%d", p.grid, p.block, p.lds, l.args.splitk, l.args.kslabs, l.args.m_tiles,
+          l.args.n_tiles);
+    for (int i = 0; p.cls && i < l.args.n_cls; ++i) t.add("%s%d:%d", i ? "," : " cls=", l.args.cls[i].tile0, l.args.cls[i].M);
+    t.add("\n");
+}
+
+int run_launch(const Launch& l, stm_stream_t stream)
+{
+    const ConvPlan& p = l.plan;
+    LaunchFn fn = nullptr;
+    if (p.kx3) fn = KX3_LAUNCHERS[p.cls ? 1 : 0];
+    else if (p.cls) fn = CLS_LAUNCHERS[p.cls - 1];
+    else
+        for (size_t i = 0; i < N_PLANAR_ROWS && !fn; ++i) {
+            const PlanarRow& r = PLANAR_ROWS[i];
+            if (r.npl == p.npl && r.mg == p.mg && r.nj == p.nj && r.dt == p.dt && r.st == p.st && r.abl == p.abl && r.dual == p.dual) fn = PLANAR_LAUNCHERS[i];
+        }
+    STM_REQUIRE(fn, STM_EUNSUPPORTED, "stm_conv2d_planar_f32: this library has no conv_planar_kernel<%d, %d, %d, %d, %d, %d, %d>", p.npl, p.mg, p.nj, p.dt,
+                p.st, p.abl, (int)p.dual);
+    if (t_plan_text) { write_launch(*t_plan_text, l); return STM_OK; }
+    const int rc = fn(l, stream);
+    if (rc == STM_OK && p.kx3) g_kx3_launches.fetch_add(1, std::memory_order_relaxed);
+    return rc;
 }
 
 bool geom_ok(const stm_conv_geom* g, const char* who)
@@ -1342,91 +1436,20 @@ namespace {
 constexpr int STM_GATE_STRIDE = 16;      // ints between the gates of a gated window set's windows (the sparse head's control blocks: head_sparse.hip, CTL_SEG)
 struct WinSet { const void* const* packed; const stm_conv_window* win; int n; unsigned long long* pool; };
 struct DualSrc { const void* x2; int C2, H2, W2, s2; long long x2_np, x2_plane_stride; };
-int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const float* bias, const float* residual_f32,
-                       const void* residual_planes, float* out_f32, void* out_planes, const stm_conv_geom* g,
-                       int relu, void* workspace, size_t workspace_bytes, stm_stream_t stream, const DualSrc* dual, const WinSet* wset);
-}  // namespace
+// what a convolution entry was called with
+struct ConvCall {
+    const void* x_planes; const void* packed_weight; const float* bias; const float* residual_f32; const void* residual_planes;
+    float* out_f32; void* out_planes; const stm_conv_geom* g; int relu; void* workspace; size_t workspace_bytes;
+    const DualSrc* dual; const WinSet* wset;
+};
 
-extern "C" int stm_conv2d_planar_ws_f32(const void* x_planes, const void* packed_weight, const float* bias, const float* residual_f32,
-                                        const void* residual_planes, float* out_f32, void* out_planes, const stm_conv_geom* g,
-                                        int relu, void* workspace, size_t workspace_bytes, stm_stream_t stream)
+// ---- validate: the argument checks, in the order callers have seen them fail, and the fill of PlanarArgs and ConvFacts ------------------
+int planar_validate(const ConvCall& c, const char* who, const int* gate, PlanarArgs& a, ConvFacts& f)
 {
-    return conv2d_planar_impl(x_planes, packed_weight, bias, residual_f32, residual_planes, out_f32, out_planes, g, relu, workspace,
-                              workspace_bytes, stream, nullptr, nullptr);
-}
-
-// Two-source 1x1 convolution: y = W [x1 ; x2(stride s2)] + bias (+ residual) -- the last 1x1 convolution of a ResNet stage's first
-// bottleneck and its projection shortcut (backbone.py:38-58: out = conv3(...); out += downsample(x); relu) as ONE product over the
-// concatenated channels.  g describes the output (B, Ho, Wo = H, W of the first source; kh = kw = 1, stride 1, no padding; C = C1 + C2
-// = the weight's input channels); x_planes holds the first C1 = g->C - C2 channels at one pixel per output pixel (x_np / x_plane_stride
-// of g), x2_planes the other C2 channels as B images of H2 x W2 read at stride s2 (Ho = (H2 - 1) / s2 + 1).  The projection's output
-// tensor -- 4 * planes channels written, then read back as conv3's residual: 1 GB per launch pair in layer1 at batch 32 -- never exists.
-extern "C" int stm_conv2d_planar_dual_f32(const void* x_planes, const void* x2_planes, int C2, int H2, int W2, int s2, long long x2_np,
-                                          long long x2_plane_stride, const void* packed_weight, const float* bias, const float* residual_f32,
-                                          const void* residual_planes, float* out_f32, void* out_planes, const stm_conv_geom* g, int relu,
-                                          void* workspace, size_t workspace_bytes, stm_stream_t stream)
-{
-    STM_REQUIRE(x2_planes && g, STM_ENULL, "stm_conv2d_planar_dual_f32: x2_planes / geometry must be non-NULL");
-    DualSrc d{x2_planes, C2, H2, W2, s2, x2_np, x2_plane_stride};
-    return conv2d_planar_impl(x_planes, packed_weight, bias, residual_f32, residual_planes, out_f32, out_planes, g, relu, workspace,
-                              workspace_bytes, stream, &d, nullptr);
-}
-
-// Several window launches (stm_conv_geom.win_*) of ONE layer as one grid: window i has its own sub-kernel (kh x kw taps, packed weights
-// packed[i], all under the same weight scale) and its own Ho x Wo rectangle at (y0, x0) of every win_h x win_w output image.  g gives what
-// the windows share: B, H, W, C, Cout, sh = sw = 1, fmt 1, planes, tile_n 128, out_scale, win_h / win_w, the buffer geometry.  The tiles of
-// all windows form one grid, so the small windows (a row or a corner of a 7x7 RoI map) do not pay a launch and a partial last round each:
-// TemporalNet's 3x3 layers run their nine border classes -- the taps that can be inside the map, 361 of 441 tap-pixels -- at the
-// efficiency of the single padded launch.  Same sums as that launch (a skipped tap added exact zeros): bit-equal.
-extern "C" int stm_conv2d_planar_windows_f32(const void* x_planes, const void* const* packed_weights, const stm_conv_window* windows, int n_windows,
-                                             const float* bias, float* out_f32, void* out_planes, const stm_conv_geom* g, int relu, stm_stream_t stream)
-{
-    const char* who = "stm_conv2d_planar_windows_f32";
-    STM_REQUIRE(packed_weights && windows && g, STM_ENULL, "%s: NULL argument", who);
-    STM_REQUIRE(n_windows >= 1 && n_windows <= 9, STM_EINVAL, "%s: 1 .. 9 windows", who);
-    // (groups: the gated form only, checked where the gate is taken)
-    STM_REQUIRE(g->win_w > 0 && g->win_h > 0 && g->fmt == 1 && g->sh == 1 && g->sw == 1 && g->n_levels <= 0 &&
-                (g->tile_n == 0 || g->tile_n == 128), STM_EUNSUPPORTED, "%s: fp16x2 planes, stride 1, 128-channel tiles, win_h / win_w set", who);
-    for (int i = 0; i < n_windows; ++i) STM_REQUIRE(packed_weights[i], STM_ENULL, "%s: packed weight %d is NULL", who, i);
-    stm_conv_geom g0 = *g;                       // window 0 stands in for the common checks and fields
-    g0.kh = windows[0].kh; g0.kw = windows[0].kw; g0.ph = windows[0].ph; g0.pw = windows[0].pw;
-    g0.Ho = windows[0].Ho; g0.Wo = windows[0].Wo; g0.win_y0 = windows[0].y0; g0.win_x0 = windows[0].x0;
-    WinSet ws{packed_weights, windows, n_windows, nullptr};
-    return conv2d_planar_impl(x_planes, packed_weights[0], bias, nullptr, nullptr, out_f32, out_planes, &g0, relu, nullptr, 0, stream, nullptr, &ws);
-}
-
-// The same window set with ReLU and the average pool over each output image folded into the epilogue (TemporalNet's conv3 + ReLU + AvgPool2d((7, 7)):
-// track_to_segment_head.py:30-33): nothing is written per pixel; pool_fix[image][channel] (row length Cout, unsigned 64-bit, 32.32 fixed point)
-// receives the SUM over the image's win_h x win_w pixels of relu(conv + bias), added to what it holds -- the caller zeroes it (stm_temporal_pool_fc_f32
-// does, when it consumes it).  Integer accumulation: the result does not depend on the order in which the workgroups finish.  Sums must stay below
-// 2^32 - win_h * win_w * 2^16 (the per-device range flag is raised otherwise, as for an fp16 overflow: pooled_epilogue).
-extern "C" int stm_conv2d_planar_windows_pool_f32(const void* x_planes, const void* const* packed_weights, const stm_conv_window* windows, int n_windows,
-                                                  const float* bias, unsigned long long* pool_fix, const stm_conv_geom* g, stm_stream_t stream)
-{
-    const char* who = "stm_conv2d_planar_windows_pool_f32";
-    STM_REQUIRE(packed_weights && windows && g && pool_fix, STM_ENULL, "%s: NULL argument", who);
-    STM_REQUIRE(n_windows >= 1 && n_windows <= 9, STM_EINVAL, "%s: 1 .. 9 windows", who);
-    STM_REQUIRE(g->win_w > 0 && g->win_h > 0 && g->fmt == 1 && g->sh == 1 && g->sw == 1 && (g->groups <= 1) && g->n_levels <= 0 &&
-                (g->tile_n == 0 || g->tile_n == 128) && g->Cout % 128 == 0, STM_EUNSUPPORTED,
-                "%s: fp16x2 planes, stride 1, one group, whole 128-channel tiles, win_h / win_w set", who);
-    STM_REQUIRE((int64_t)g->win_h * g->win_w <= 32768, STM_EUNSUPPORTED, "%s: pooled images of at most 32768 pixels", who);   // (pooled_epilogue's margin)
-    STM_REQUIRE((uintptr_t)pool_fix % 8 == 0, STM_EINVAL, "%s: pool_fix must be 8-byte aligned", who);
-    for (int i = 0; i < n_windows; ++i) STM_REQUIRE(packed_weights[i], STM_ENULL, "%s: packed weight %d is NULL", who, i);
-    stm_conv_geom g0 = *g;
-    g0.kh = windows[0].kh; g0.kw = windows[0].kw; g0.ph = windows[0].ph; g0.pw = windows[0].pw;
-    g0.Ho = windows[0].Ho; g0.Wo = windows[0].Wo; g0.win_y0 = windows[0].y0; g0.win_x0 = windows[0].x0;
-    WinSet ws{packed_weights, windows, n_windows, pool_fix};
-    return conv2d_planar_impl(x_planes, packed_weights[0], bias, nullptr, nullptr, nullptr, nullptr, &g0, 1, nullptr, 0, stream, nullptr, &ws);
-}
-
-namespace {
-int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const float* bias, const float* residual_f32,
-                       const void* residual_planes, float* out_f32, void* out_planes, const stm_conv_geom* g,
-                       int relu, void* workspace, size_t workspace_bytes, stm_stream_t stream, const DualSrc* dual, const WinSet* wset)
-{
-    const char* who = dual ? "stm_conv2d_planar_dual_f32" : "stm_conv2d_planar_f32";
-    const int* const gate = stm_internal_take_pixel_gate();      // (one-shot: consumed by this call whatever it returns)
-    STM_REQUIRE(x_planes && packed_weight && (out_f32 || out_planes || (wset && wset->pool)), STM_ENULL,
+    const stm_conv_geom* const g = c.g;
+    const DualSrc* const dual = c.dual;
+    const WinSet* const wset = c.wset;
+    STM_REQUIRE(c.x_planes && c.packed_weight && (c.out_f32 || c.out_planes || (wset && wset->pool)), STM_ENULL,
                 "%s: x_planes/packed_weight and at least one output must be non-NULL", who);
     STM_REQUIRE(g, STM_ENULL, "%s: geometry is NULL", who);
     const int groups = g->groups > 0 ? g->groups : 1;
@@ -1458,9 +1481,9 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
     const bool win = g->n_levels <= 0 && g->win_w > 0;
     const int64_t out_rows = win ? (int64_t)g->B * g->win_h * g->win_w : M;       // rows of the output tensors
     const int64_t x_np = g->x_np ? g->x_np : in_pixels, out_np = g->out_np ? g->out_np : out_rows, res_np = g->res_np ? g->res_np : M;
-    STM_REQUIRE(!win || (!residual_f32 && !residual_planes && !dual), STM_EUNSUPPORTED, "%s: window launches take no residual / second source", who);
+    STM_REQUIRE(!win || (!c.residual_f32 && !c.residual_planes && !dual), STM_EUNSUPPORTED, "%s: window launches take no residual / second source", who);
     STM_REQUIRE(x_np >= in_pixels && out_np >= out_rows && res_np >= M, STM_EINVAL, "%s: x_np / out_np / res_np smaller than the pixel count", who);
-    STM_REQUIRE((uintptr_t)x_planes % 16 == 0 && (uintptr_t)packed_weight % 16 == 0, STM_EINVAL,
+    STM_REQUIRE((uintptr_t)c.x_planes % 16 == 0 && (uintptr_t)c.packed_weight % 16 == 0, STM_EINVAL,
                 "%s: x_planes and packed_weight must be 16-byte aligned", who);
     if (dual) {
         STM_REQUIRE(groups == 1 && g->n_levels <= 0 && g->kh == 1 && g->kw == 1 && g->sh == 1 && g->sw == 1 && g->ph == 0 && g->pw == 0 &&
@@ -1480,15 +1503,14 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
     const int64_t ops = g->out_plane_stride ? g->out_plane_stride : o_slabs * out_np * 32;
     const int64_t rps = g->res_plane_stride ? g->res_plane_stride : o_slabs * res_np * 32;
     STM_REQUIRE(xps % 8 == 0, STM_EINVAL, "%s: x_plane_stride must be a multiple of 8 elements", who);
-    PlanarArgs a;
-    a.xp = static_cast<const uint8_t*>(x_planes); a.wp = static_cast<const uint8_t*>(packed_weight); a.bias = bias;
-    a.res_f32 = residual_f32; a.res_pl = static_cast<const uint8_t*>(residual_planes);
-    a.out_f32 = out_f32; a.out_pl = static_cast<uint8_t*>(out_planes);
+    a.xp = static_cast<const uint8_t*>(c.x_planes); a.wp = static_cast<const uint8_t*>(c.packed_weight); a.bias = c.bias;
+    a.res_f32 = c.residual_f32; a.res_pl = static_cast<const uint8_t*>(c.residual_planes);
+    a.out_f32 = c.out_f32; a.out_pl = static_cast<uint8_t*>(c.out_planes);
     a.B = g->B; a.H = g->H; a.W = g->W; a.C = g->C; a.Ho = g->Ho; a.Wo = g->Wo; a.Cout = g->Cout;
     a.kh = g->kh; a.kw = g->kw; a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw;
-    a.out_ld = out_ld; a.res_ld = res_ld; a.relu = relu;
+    a.out_ld = out_ld; a.res_ld = res_ld; a.relu = c.relu;
     a.x_np = (int)x_np; a.out_np = (int)out_np; a.res_np = (int)res_np;
-    a.M = (int)M; a.n_tiles = stm_cdiv(g->Cout, bn); a.slabs = g->kh * g->kw * (g->C / CV_BK);
+    a.M = (int)M; a.n_tiles = stm_cdiv(g->Cout, bn); a.m_tiles = 0; a.slabs = g->kh * g->kw * (g->C / CV_BK);
     a.plane_bytes = (unsigned)plane_bytes;
     a.x_pstride = xps * 2; a.out_pstride = ops * 2; a.res_pstride = rps * 2;
     a.groups = groups; a.cout_g = cout_g; a.ntpg = stm_cdiv(cout_g, bn);
@@ -1496,9 +1518,8 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
     a.n_levels = g->n_levels > 0 ? g->n_levels : 0;
     for (int l = 0; l < 8; ++l) { a.lvl_start[l] = g->lvl_start[l]; a.lvl_h[l] = g->lvl_h[l]; a.lvl_w[l] = g->lvl_w[l]; }
     a.lvl_start[8] = g->lvl_start[8];
-    const ConvTunables& tn = tunables();
-    a.vec_epilogue = (cout_g % 8 == 0) && (!out_f32 || out_ld % 4 == 0) && (!residual_f32 || res_ld % 4 == 0) && ((uintptr_t)out_f32 % 16 == 0) &&
-                     ((uintptr_t)out_planes % 16 == 0) && ((uintptr_t)residual_f32 % 16 == 0) && ((uintptr_t)residual_planes % 16 == 0) &&
+    a.vec_epilogue = (cout_g % 8 == 0) && (!c.out_f32 || out_ld % 4 == 0) && (!c.residual_f32 || res_ld % 4 == 0) && ((uintptr_t)c.out_f32 % 16 == 0) &&
+                     ((uintptr_t)c.out_planes % 16 == 0) && ((uintptr_t)c.residual_f32 % 16 == 0) && ((uintptr_t)c.residual_planes % 16 == 0) &&
                      (ops % 8 == 0) && (rps % 8 == 0);
     STM_REQUIRE(g->kh * g->kw <= 32, STM_EUNSUPPORTED, "%s: more than 32 taps", who);
     a.pointwise = (g->n_levels <= 0 && !win && g->kh == 1 && g->kw == 1 && g->sh == 1 && g->sw == 1 && g->ph == 0 && g->pw == 0) ? 1 : 0;
@@ -1529,229 +1550,244 @@ int conv2d_planar_impl(const void* x_planes, const void* packed_weight, const fl
         a.xp2 = static_cast<const uint8_t*>(dual->x2); a.x2_pstride = ps2 * 2; a.plane2_bytes = (unsigned)(slabs2 * np2 * 64);
         a.c1_slabs = (int)x_slabs; a.x2_np = (int)np2; a.H2 = dual->H2; a.W2 = dual->W2; a.s2 = dual->s2;
     }
-    // split-K for grids that would leave most CUs idle over a long K (small feature maps: ResNet stages 3/4, P5-P7):
-    // parts write fp32 partial sums into the caller's workspace, planar_splitk_finish_kernel adds them and runs the epilogue.
-    // (A fused reduction -- the part drawing a tile's last ticket adds the parts -- was built and measured twice.  Round 1 with
-    // device-scope fences: an L2 write-back / invalidate per workgroup, 665 vs 919 frames/s.  Round 2 without any fence -- the
-    // parts' sums written and read as agent-scope relaxed atomics (sc1 accesses), store -> vmcnt(0) -> ticket ... ticket -> load
-    // -- to save the 47 finishing launches of a single-stream step (12 % of its GPU time): 359 vs 461 frames/s at 1 clip, 965 vs
-    // 1047 at 8, 1201 vs 1214 at 32.  One workgroup adding a tile's parts at the end of the kernel is a longer tail than the
-    // finishing kernel's few thousand threads after it; removed again.)
-    // (128 x 64 tiles) every group fills its 64-channel tiles: the layer can take the ring loop; the narrow ones (output layers
-    // with 41 / 5 / 32 real channels of 64, offset convolutions) keep the two-buffer loop with its skip of all-padding column tiles
     bool full = cout_g % 64 == 0;
     for (int gi = 0; gi < groups && gi < 8; ++gi) full = full && a.group_real[gi] == cout_g;
-    auto plan_splitk = [&](int tiles) {
-        if (a.m_gate) return;         // (the finishing kernel knows no gate, and a gated launch is sized for a capacity, not for its work)
-        int sk = tn.splitk;
-        if (sk <= 0) {
-            sk = 1;
-            if (bn == 64) {
-                // 128 x 64 tiles: grids of at most half a workgroup per CU are split until about one workgroup per CU exists,
-                // with at least 16 K-slabs per part (10 on the tiniest grids).  Re-measured in round 2 with every configuration
-                // replayed from a HIP graph (scripts/sweep_small_m.py; round 1's rule -- up to 256 tiles, three workgroups per
-                // CU, 10 slabs per part -- dated from before the ring loop took the small grids): 240 tiles x 32 slabs 31.9 us
-                // split in 3 vs 20.2 unsplit, 240 x 72 slabs 49.5 vs 39.8, 120 tiles x 64 slabs 29.8 (6 parts) vs 24.4 (2),
-                // 64 x 64 19.4 (6) vs 17.3 (4), 240 x 36 (layer2's 3x3 at 4 clips) 34.3 vs 20.0.
-                // The narrow layers (two-buffer loop) keep round 1's rule: 120 tiles x 72 slabs 36.8 us in 6 parts, 55.2 in 2.
-                if (!full) {
-                    if (tiles <= 256 && a.slabs >= 24) sk = (int)std::min<int64_t>(std::min<int64_t>(8, 768 / tiles), a.slabs / 10);
-                } else if (tiles <= 128 && a.slabs >= 24)
-                    sk = (int)std::min<int64_t>(std::min<int64_t>(8, CV_SK_TARGET / tiles), a.slabs / (tiles <= 40 ? 10 : 16));
-            } else if (tiles < 128 && a.slabs >= 24) sk = (int)std::min<int64_t>(std::min<int64_t>(8, 256 / tiles), a.slabs / 12);
-        }
-        if (sk < 2) return;
-        const int per = stm_cdiv(a.slabs, sk);
-        sk = stm_cdiv(a.slabs, per);
-        if (sk < 2 || !workspace || (size_t)sk * M * a.ldp * sizeof(float) > workspace_bytes || ((uintptr_t)workspace % 16)) return;
-        a.splitk = sk; a.kslabs = per; a.partial = static_cast<float*>(workspace);
-    };
-    auto finish_splitk = [&]() -> int {
-        if (a.splitk < 2) return STM_OK;
-        const int64_t total = M * groups * ((cout_g + 7) / 8);
-        hipLaunchKernelGGL(planar_splitk_finish_kernel, dim3(stm_cdiv(total, 256)), dim3(256), 0, stm_hs(stream), a, bn);
-        STM_CHECK_LAUNCH("planar_splitk_finish_kernel");
-        return STM_OK;
-    };
-    if (wset && gate) {
-        // Gated window set = SEGMENTED window set (the sparse head's patch towers, one window per kernel shape): the B images are n equal runs, window i
-        // is computed for the images of run i only and gated by the device int gate[STM_GATE_STRIDE i], which counts output pixels of that window
-        // (images x Ho_i x Wo_i).  One grid of conv_planar_kernel<..., CLS = 2> for all of them: per output pixel the products, and their order, of the
-        // single gated window launch.  Groups as in that launch (every class has all the channel tiles).
-        STM_REQUIRE(bn == 128 && a.fmt == 1 && !dual && win, STM_EUNSUPPORTED, "%s: window sets run on the 256 x 128 ring tiles of the fp16x2 format", who);
-        STM_REQUIRE(g->B % wset->n == 0, STM_EINVAL, "%s: %d images are not %d equal segments", who, g->B, wset->n);
-        const int seg_b = g->B / wset->n;
-        PlanarArgsSeg as;
-        static_cast<PlanarArgs&>(as) = a;
-        as.m_gate = nullptr;
-        as.pool = nullptr; as.pool_ld = 0;
-        int t0 = 0;
-        for (int i = 0; i < 9; ++i) {
-            const int wi = i < wset->n ? i : 0;
-            const stm_conv_window& w = wset->win[wi];
-            if (i < wset->n) {
-                STM_REQUIRE(w.kh == g->kh && w.kw == g->kw, STM_EUNSUPPORTED, "%s: the windows of a gated set share the layer's %dx%d kernel", who, g->kh, g->kw);
-                STM_REQUIRE(w.Ho > 0 && w.Wo > 0 && w.y0 >= 0 && w.x0 >= 0 && w.y0 + w.Ho <= g->win_h && w.x0 + w.Wo <= g->win_w, STM_EINVAL,
-                            "%s: window %d (%dx%d at %d, %d) is not inside the %dx%d output", who, i, w.Ho, w.Wo, w.y0, w.x0, g->win_h, g->win_w);
-                // every tap of every window pixel inside the input image: a segment's rows never read another segment's images
-                STM_REQUIRE(-w.ph >= 0 && -w.ph + (w.Ho - 1) + (w.kh - 1) <= g->H - 1 && -w.pw >= 0 && -w.pw + (w.Wo - 1) + (w.kw - 1) <= g->W - 1, STM_EINVAL,
-                            "%s: window %d reads outside the %dx%d input image", who, i, g->H, g->W);
-                STM_REQUIRE((uintptr_t)wset->packed[i] % 16 == 0, STM_EINVAL, "%s: packed weight %d is not 16-byte aligned", who, i);
-            }
-            const int64_t Mc = (int64_t)seg_b * w.Ho * w.Wo;
-            PlanarArgsCls::Cls& c = as.cls[i];
-            c.wp = static_cast<const uint8_t*>(wset->packed[wi]);
-            c.kh = w.kh; c.kw = w.kw; c.ph = w.ph; c.pw = w.pw; c.Ho = w.Ho; c.Wo = w.Wo; c.M = (int)Mc;
-            c.slabs = w.kh * w.kw * (g->C / CV_BK);
-            c.win_off = wi * seg_b * g->win_h * g->win_w + w.y0 * g->win_w + w.x0;
-            c.inv_hw = 1.0f / (float)(w.Ho * w.Wo); c.inv_w = 1.0f / (float)w.Wo;
-            c.tile0 = t0;
-            as.gate[i] = gate + STM_GATE_STRIDE * wi;
-            as.x_off[i] = (int)((int64_t)wi * seg_b * g->H * g->W * 64);
-            if (i < wset->n) t0 += stm_cdiv(Mc, 2 * CV_BM) * a.n_tiles;
-        }
-        as.n_cls = wset->n;
-        as.cls_tiles = t0;
-        as.m_tiles = 0;
-        return launch_planar<2, 2, 2, 1, 3, 0, false, 2>(as, stm_cdiv(t0 / a.n_tiles, 8) * 8 * a.n_tiles, stream);
-    }
-    if (wset) {
-        STM_REQUIRE(bn == 128 && a.fmt == 1 && !dual && win && groups == 1, STM_EUNSUPPORTED,
-                    "%s: window sets run on the 256 x 128 ring tiles of the fp16x2 format, one group unless gated", who);
-        // Two grids: the windows whose sub-kernel has all three column taps inside the map (kw = 3: the interior-column border classes, 79 % of the
-        // products of a 3x3 layer on 7x7 maps) take conv_planar_kx3_kernel<., WIN> -- one staged run per (channel slab, ky) and window row serves the
-        // three taps -- the others (two column taps: the left / right columns) stay on conv_planar_kernel<..., CLS>.  Disjoint output rows.
-        PlanarArgsCls ac[2];
-        int t0[2] = {0, 0}, ncls[2] = {0, 0};
-        for (int k = 0; k < 2; ++k) {
-            static_cast<PlanarArgs&>(ac[k]) = a;
-            ac[k].pool = wset->pool;
-            ac[k].pool_ld = g->Cout;
-        }
-        for (int i = 0; i < wset->n; ++i) {
-            const stm_conv_window& w = wset->win[i];
-            STM_REQUIRE(w.kh > 0 && w.kw > 0 && w.kh * w.kw <= 32 && w.Ho > 0 && w.Wo > 0 && w.y0 >= 0 && w.x0 >= 0 && w.y0 + w.Ho <= g->win_h &&
-                            w.x0 + w.Wo <= g->win_w, STM_EINVAL, "%s: window %d (%dx%d at %d, %d, kernel %dx%d) is not inside the %dx%d output", who, i, w.Ho,
-                        w.Wo, w.y0, w.x0, w.kh, w.kw, g->win_h, g->win_w);
+    f = ConvFacts{bn, a.fmt, g->planes, groups, cout_g, full, a.slabs, a.kh, a.kw, a.sh, a.sw, a.ph, a.pw, M, a.n_tiles, dual != nullptr, win, gate != nullptr,
+                  c.workspace && (uintptr_t)c.workspace % 16 == 0, c.workspace_bytes, a.ldp};
+    return STM_OK;
+}
+
+// ---- window sets ----------------------------------------------------------------------------------------------------------------------
+bool window_inside(const stm_conv_window& w, const stm_conv_geom* g)
+{
+    return w.Ho > 0 && w.Wo > 0 && w.y0 >= 0 && w.x0 >= 0 && w.y0 + w.Ho <= g->win_h && w.x0 + w.Wo <= g->win_w;
+}
+bool window_taps_inside(const stm_conv_window& w, const stm_conv_geom* g) { return conv_plan::taps_inside(w.kh, w.kw, w.ph, w.pw, w.Ho, w.Wo, g->H, g->W); }
+
+// class c = window w over `images` images, its output rows from row0 of the output tensors, its tiles from tile0; returns its pixels
+int64_t fill_cls(PlanarArgsCls::Cls& c, const void* packed, const stm_conv_window& w, const stm_conv_geom* g, int images, int row0, int tile0)
+{
+    const int64_t Mc = (int64_t)images * w.Ho * w.Wo;
+    c.wp = static_cast<const uint8_t*>(packed);
+    c.kh = w.kh; c.kw = w.kw; c.ph = w.ph; c.pw = w.pw; c.Ho = w.Ho; c.Wo = w.Wo; c.M = (int)Mc;
+    c.slabs = w.kh * w.kw * (g->C / CV_BK);
+    c.win_off = row0 + w.y0 * g->win_w + w.x0;
+    c.inv_hw = 1.0f / (float)(w.Ho * w.Wo); c.inv_w = 1.0f / (float)w.Wo;
+    c.tile0 = tile0;
+    return Mc;
+}
+
+// Gated window set = SEGMENTED window set (the sparse head's patch towers, one window per kernel shape): the B images are n equal runs, window i
+// is computed for the images of run i only and gated by the device int gate[STM_GATE_STRIDE i], which counts output pixels of that window
+// (images x Ho_i x Wo_i).  One grid of conv_planar_kernel<..., CLS = 2> for all of them: per output pixel the products, and their order, of the
+// single gated window launch.  Groups as in that launch (every class has all the channel tiles).
+int build_gated_set(const ConvCall& c, const char* who, const ConvFacts& f, const int* gate, Launch& l)
+{
+    const stm_conv_geom* const g = c.g;
+    const WinSet* const wset = c.wset;
+    PlanarArgsSeg& as = l.args;
+    STM_REQUIRE(f.bn == 128 && as.fmt == 1 && !c.dual && f.win, STM_EUNSUPPORTED, "%s: window sets run on the 256 x 128 ring tiles of the fp16x2 format", who);
+    STM_REQUIRE(g->B % wset->n == 0, STM_EINVAL, "%s: %d images are not %d equal segments", who, g->B, wset->n);
+    const int seg_b = g->B / wset->n;
+    as.m_gate = nullptr;
+    as.pool = nullptr; as.pool_ld = 0;
+    int t0 = 0;
+    for (int i = 0; i < 9; ++i) {
+        const int wi = i < wset->n ? i : 0;
+        const stm_conv_window& w = wset->win[wi];
+        if (i < wset->n) {
+            STM_REQUIRE(w.kh == g->kh && w.kw == g->kw, STM_EUNSUPPORTED, "%s: the windows of a gated set share the layer's %dx%d kernel", who, g->kh, g->kw);
+            STM_REQUIRE(window_inside(w, g), STM_EINVAL, "%s: window %d (%dx%d at %d, %d) is not inside the %dx%d output", who, i, w.Ho, w.Wo, w.y0, w.x0,
+                        g->win_h, g->win_w);
+            // every tap of every window pixel inside the input image: a segment's rows never read another segment's images
+            STM_REQUIRE(window_taps_inside(w, g), STM_EINVAL, "%s: window %d reads outside the %dx%d input image", who, i, g->H, g->W);
             STM_REQUIRE((uintptr_t)wset->packed[i] % 16 == 0, STM_EINVAL, "%s: packed weight %d is not 16-byte aligned", who, i);
-            const int64_t Mc = (int64_t)g->B * w.Ho * w.Wo;
-            STM_REQUIRE(Mc < ((int64_t)1 << 24), STM_EUNSUPPORTED, "%s: more than 2^24 output pixels in one window", who);
-            // kx-reuse form: every tap inside the input map (no zero fill to stage), and a tile's window rows with their two halo pixels fit 384 staged rows
-            const bool taps_inside = -w.ph >= 0 && -w.ph + (w.Ho - 1) + (w.kh - 1) <= g->H - 1 && -w.pw >= 0 && -w.pw + (w.Wo - 1) + (w.kw - 1) <= g->W - 1;
-            const int k = (tn.kx3 && w.kw == 3 && w.kh <= 6 && taps_inside && (255 / w.Wo + 2) * (w.Wo + 2) <= 384) ? 1 : 0;
-            PlanarArgsCls::Cls& c = ac[k].cls[ncls[k]++];
-            c.wp = static_cast<const uint8_t*>(wset->packed[i]);
-            c.kh = w.kh; c.kw = w.kw; c.ph = w.ph; c.pw = w.pw; c.Ho = w.Ho; c.Wo = w.Wo; c.M = (int)Mc;
-            c.slabs = w.kh * w.kw * (g->C / CV_BK); c.win_off = w.y0 * g->win_w + w.x0; c.tile0 = t0[k];
-            c.inv_hw = 1.0f / (float)(w.Ho * w.Wo); c.inv_w = 1.0f / (float)w.Wo;
-            t0[k] += stm_cdiv(Mc, 2 * CV_BM) * a.n_tiles;
         }
-        for (int k = 0; k < 2; ++k) {
-            if (!ncls[k]) continue;
-            for (int i = ncls[k]; i < 9; ++i) ac[k].cls[i] = ac[k].cls[0];
-            ac[k].n_cls = ncls[k];
-            ac[k].cls_tiles = t0[k];
-            ac[k].m_tiles = 0;
-            if (k == 0) {
-                // (grid: every XCD gets the same number of pixel tiles x all channel tiles; ids past the last tile leave at once)
-#ifndef CLS_ABL
-#define CLS_ABL 0     // timing build (RESULTS WRONG): 16 = the window-set kernel issues its activation DMAs on every third K-slab only
-#endif
-                const int rc0 = launch_planar<2, 2, 2, 1, 3, CLS_ABL, false, 1>(ac[0], stm_cdiv(t0[0] / a.n_tiles, 8) * 8 * a.n_tiles, stream);
-                if (rc0 != STM_OK) return rc0;
-            } else {
-                constexpr size_t lds = 2 * 2 * 384 * 64 + 3 * KX3_WBUF;      // two 48-KB activation buffers + the weight ring (the epilogue's park needs less)
-                const int rc1 = stm_reserve_lds<conv_planar_kx3_kernel<KX3_ABL, true>>(lds, who);
-                if (rc1 != STM_OK) return rc1;
-                hipLaunchKernelGGL((conv_planar_kx3_kernel<KX3_ABL, true>), dim3(stm_cdiv(t0[1] / a.n_tiles, 8) * 8 * a.n_tiles), dim3(512), lds, stm_hs(stream), ac[1]);
-                STM_CHECK_LAUNCH("conv_planar_kx3_kernel<WIN>");
-                g_kx3_launches.fetch_add(1, std::memory_order_relaxed);
-            }
-        }
-        return STM_OK;
+        const int64_t Mc = fill_cls(as.cls[i], wset->packed[wi], w, g, seg_b, wi * seg_b * g->win_h * g->win_w, t0);
+        as.gate[i] = gate + STM_GATE_STRIDE * wi;
+        as.x_off[i] = (int)((int64_t)wi * seg_b * g->H * g->W * 64);
+        if (i < wset->n) t0 += stm_cdiv(Mc, 2 * CV_BM) * as.n_tiles;
     }
-    int rc;
-    if (bn == 64) {
-        // 128 x 64 tiles, 72 KB of LDS: two independent workgroups per CU, each one's barrier / staging gaps filled by
-        // the other's MFMAs
-        a.m_tiles = stm_cdiv(M, CV_BM);
-        plan_splitk(a.m_tiles * a.n_tiles);
-        const int tiles = a.m_tiles * a.n_tiles * a.splitk;
-        // the three-buffer ring (72 KB: still two workgroups per CU) has no skip of zero-padded column tiles: `full` layers only
-        // measured in the graph (bench.py --layer-table): the ring wins on the short K loops (<= 36 slabs: 35 -> 30 us,
-        // 46 -> 36 us, 45 -> 37 us), where its two-slab head start hides the first DMA latency, and loses on the long and
-        // the split-K ones (100 -> 114 us at 72 slabs), where two resident two-buffer workgroups already cover each other;
-        // under 12 slabs the layer is HBM-bound and the two-buffer loop's 48 KB (three workgroups per CU) wins: 302 vs 389 us
-        // grids of at most two workgroups per CU (single-stream / small batches: every layer; layer4 at 8 clips) have no further
-        // resident workgroup to cover a workgroup's staging gaps: the ring whatever K.  Swept 0 / 128 / 256 / 512 / 1024 on one
-        // box (scripts/sweep_ring64_small.sh): 1 clip 399 / 421 / 436 / 456 / 452 frames/s, 2 clips 628 .. 662, 4 clips 836 ..
-        // 880, 8 clips flat (1053), 32 clips 1219 .. 1226.
-        const bool small_grid = tiles <= CV_RING64_SMALL;
-        const bool ring = full && (tn.ring64 == 3 ? (small_grid || (a.splitk == 1 && a.slabs >= 12 && a.slabs <= 40)) : tn.ring64 == 4);
-        if (dual) {
-            if (a.fmt == 2) rc = ring ? launch_planar<1, 1, 1, 1, 3, 0, true>(a, tiles, stream) : launch_planar<1, 1, 1, 1, 2, 0, true>(a, tiles, stream);
-            else rc = ring ? launch_planar<2, 1, 1, 1, 3, 0, true>(a, tiles, stream) : launch_planar<2, 1, 1, 1, 2, 0, true>(a, tiles, stream);
-        } else if (a.fmt == 2) rc = ring ? launch_planar<1, 1, 1, 1, 3>(a, tiles, stream) : launch_planar<1, 1, 1, 1>(a, tiles, stream);
-        else if (a.fmt == 1) rc = ring ? launch_planar<2, 1, 1, 1, 3>(a, tiles, stream) : launch_planar<2, 1, 1, 1>(a, tiles, stream);
-        else rc = g->planes == 3 ? launch_planar<3, 1, 1>(a, tiles, stream) : launch_planar<2, 1, 1>(a, tiles, stream);
-        return rc != STM_OK ? rc : finish_splitk();
+    as.n_cls = wset->n;
+    as.cls_tiles = t0;
+    l.plan = conv_plan::plan_window_set(false, 2, 0, t0, as.n_tiles, as.kslabs);
+    l.planned = true;
+    return STM_OK;
+}
+
+// Plain window set, two grids: the windows whose sub-kernel has all three column taps inside the map (kw = 3: the interior-column border classes, 79 % of
+// the products of a 3x3 layer on 7x7 maps) take conv_planar_kx3_kernel<., WIN> -- one staged run per (channel slab, ky) and window row serves the
+// three taps -- the others (two column taps: the left / right columns) stay on conv_planar_kernel<..., CLS>.  Disjoint output rows.
+// L[0] is the conv_planar_kernel grid, L[1] the kx-reuse one; either may be empty (it stays unplanned).
+int build_window_set(const ConvCall& c, const char* who, const ConvFacts& f, const ConvTunables& tn, Launch (&L)[2])
+{
+    const stm_conv_geom* const g = c.g;
+    const WinSet* const wset = c.wset;
+    STM_REQUIRE(f.bn == 128 && L[0].args.fmt == 1 && !c.dual && f.win && f.groups == 1, STM_EUNSUPPORTED,
+                "%s: window sets run on the 256 x 128 ring tiles of the fp16x2 format, one group unless gated", who);
+    static_cast<PlanarArgs&>(L[1].args) = static_cast<const PlanarArgs&>(L[0].args);
+    int t0[2] = {0, 0}, ncls[2] = {0, 0};
+    for (int i = 0; i < wset->n; ++i) {
+        const stm_conv_window& w = wset->win[i];
+        STM_REQUIRE(w.kh > 0 && w.kw > 0 && w.kh * w.kw <= 32 && window_inside(w, g), STM_EINVAL,
+                    "%s: window %d (%dx%d at %d, %d, kernel %dx%d) is not inside the %dx%d output", who, i, w.Ho, w.Wo, w.y0, w.x0, w.kh, w.kw, g->win_h, g->win_w);
+        STM_REQUIRE((uintptr_t)wset->packed[i] % 16 == 0, STM_EINVAL, "%s: packed weight %d is not 16-byte aligned", who, i);
+        STM_REQUIRE((int64_t)g->B * w.Ho * w.Wo < ((int64_t)1 << 24), STM_EUNSUPPORTED, "%s: more than 2^24 output pixels in one window", who);
+        const int k = conv_plan::window_takes_kx3(tn, w.kh, w.kw, w.ph, w.pw, w.Ho, w.Wo, g->H, g->W) ? 1 : 0;
+        const int64_t Mc = fill_cls(L[k].args.cls[ncls[k]++], wset->packed[i], w, g, g->B, 0, t0[k]);
+        t0[k] += stm_cdiv(Mc, 2 * CV_BM) * f.n_tiles;
     }
-    // 256-pixel tiles once there are enough of them, else 128-pixel tiles.  (A cost model of rounds x tile time x measured
-    // efficiency was tried for this choice and for the 64-channel tile: 478-483 frames/s against 502-509 with these plain
-    // thresholds in the same session -- rejected.  So was a kx-reuse kernel that stages each activation row once per kernel
-    // row: 1.8x fewer DMA bytes, no gain -- 654 vs 670 us on the 145-GF proto layer -- removed.  Round 2 rebuilt it on the
-    // three-buffer ring -- one staged copy of BM + 2 pixels per (channel slab, ky) serving kx = 0, 1, 2 at LDS row r + kx, an
-    // all-zero LDS row for the padding columns, stage parts spread over the three K-slabs, bit-identical results: half the
-    // activation DMA instructions, 1/2.8 of their L2 reads, and 1.5-2.5 % SLOWER on every 3x3 layer (proto 1465 vs 1440 us,
-    // tower 1850 vs 1807, TemporalNet conv3 2993 vs 2953).  Its own ablations: no stage DMA at all 1406 -> 1188 us, no
-    // per-tap register rotation 1379, never waiting for a stage to land 1378.  The cost of the activation staging follows
-    // the number of DMA instructions issued (~30 clocks of a wave's issue each), not the bytes they fetch or their latency,
-    // and the bookkeeping of the reuse eats what the fewer instructions give back -- removed again.  The three-slab body
-    // unrolled (compile-time taps, no rotation) made the register allocator migrate the accumulators: 53 quads, 54 spills.)
-    const int64_t t2 = (int64_t)stm_cdiv(M, 2 * CV_BM) * a.n_tiles;
-    const int mg = tn.mg ? tn.mg : (t2 >= 192 ? 2 : 1);
-    a.m_tiles = stm_cdiv(M, CV_BM * mg);
-    plan_splitk(a.m_tiles * a.n_tiles);
-    const int tiles = a.m_tiles * a.n_tiles * a.splitk;
-    const bool ring = tn.ring == 3;
-#ifdef STM_ABLATE
-    if (a.fmt == 1 && ring && mg == 2 && tn.abl) {      // timing ablations of the ring loop: RESULTS ARE WRONG
-        const int abl = tn.abl;
-        rc = abl == 1 ? launch_planar<2, 2, 2, 1, 3, 1>(a, tiles, stream) : abl == 2 ? launch_planar<2, 2, 2, 1, 3, 2>(a, tiles, stream)
-           : abl == 3 ? launch_planar<2, 2, 2, 1, 3, 3>(a, tiles, stream) : abl == 5 ? launch_planar<2, 2, 2, 1, 3, 5>(a, tiles, stream)
-           : abl == 8 ? launch_planar<2, 2, 2, 1, 3, 8>(a, tiles, stream) : abl == 16 ? launch_planar<2, 2, 2, 1, 3, 16>(a, tiles, stream)
-           : abl == 32 ? launch_planar<2, 2, 2, 1, 3, 32>(a, tiles, stream) : abl == 64 ? launch_planar<2, 2, 2, 1, 3, 64>(a, tiles, stream)
-                      : launch_planar<2, 2, 2, 1, 3, 7>(a, tiles, stream);
-        return rc != STM_OK ? rc : finish_splitk();
+    for (int k = 0; k < 2; ++k) {
+        if (!ncls[k]) continue;
+        PlanarArgsCls& ac = L[k].args;
+        for (int i = ncls[k]; i < 9; ++i) ac.cls[i] = ac.cls[0];
+        ac.pool = wset->pool;
+        ac.pool_ld = g->Cout;
+        ac.n_cls = ncls[k];
+        ac.cls_tiles = t0[k];
+        L[k].plan = conv_plan::plan_window_set(k == 1, 1, k == 0 ? CLS_ABL : 0, t0[k], f.n_tiles, ac.kslabs);
+        L[k].planned = true;
     }
-#endif
-    if (tn.kx3 && a.fmt == 1 && ring && mg == 2 && !dual && !win && a.splitk == 1 && a.kw == 3 && a.pw == 1 && a.sh == 1 && a.sw == 1 &&
-        a.slabs % 3 == 0 && a.kh <= 6 && 2 * a.ph == a.kh - 1 && full) {
-        // ("same" padding in height too: the kernel decodes a pixel index ONCE and uses it for the output and the staged input rows alike, so
-        // Ho == H and Wo == W are part of its contract -- a 3x3 layer with padding (0, 1) stays on conv_planar_kernel)
-        // kx-reuse staging (conv_planar_kx3_kernel): one staged run of BM + 2 pixels per (channel slab, ky) serves the three taps of a kernel row
-        constexpr size_t lds = 8 * 64 * (64 + 4) * sizeof(float) > (size_t)KX3_LDS_LOOP ? 8 * 64 * (64 + 4) * sizeof(float) : (size_t)KX3_LDS_LOOP;
-        rc = stm_reserve_lds<conv_planar_kx3_kernel<KX3_ABL, false>>(lds, who);
+    return STM_OK;
+}
+
+// ---- validate, plan, run ----------------------------------------------------------------------------------------------------------------
+int conv2d_planar_impl(const ConvCall& c, stm_stream_t stream)
+{
+    const char* who = c.dual ? "stm_conv2d_planar_dual_f32" : "stm_conv2d_planar_f32";
+    const int* const gate = stm_internal_take_pixel_gate();      // (one-shot: consumed by this call whatever it returns)
+    Launch L[2];                                                  // (a window set may be two grids)
+    PlanarArgs& a = L[0].args;
+    ConvFacts f;
+    int rc = planar_validate(c, who, gate, a, f);
+    if (rc != STM_OK) return rc;
+    if (c.wset) {
+        rc = gate ? build_gated_set(c, who, f, gate, L[0]) : build_window_set(c, who, f, tunables(), L);
         if (rc != STM_OK) return rc;
-        hipLaunchKernelGGL((conv_planar_kx3_kernel<KX3_ABL, false>), dim3(8 * stm_cdiv(tiles, 8)), dim3(512), lds, stm_hs(stream), a);
-        STM_CHECK_LAUNCH("conv_planar_kx3_kernel");
-        g_kx3_launches.fetch_add(1, std::memory_order_relaxed);
-        return STM_OK;
+    } else {
+        const ConvPlan& p = L[0].plan = conv_plan::plan_conv(f, tunables());
+        a.m_tiles = p.m_tiles; a.splitk = p.splitk; a.kslabs = p.kslabs;
+        if (p.splitk > 1) a.partial = static_cast<float*>(c.workspace);
+        L[0].planned = true;
     }
-    if (dual) {      // (the 128-wide tiles of the fp16 formats always take the ring loop here)
-        if (a.fmt == 2) rc = mg == 2 ? launch_planar<1, 2, 2, 1, 3, 0, true>(a, tiles, stream) : launch_planar<1, 1, 2, 1, 3, 0, true>(a, tiles, stream);
-        else rc = mg == 2 ? launch_planar<2, 2, 2, 1, 3, 0, true>(a, tiles, stream) : launch_planar<2, 1, 2, 1, 3, 0, true>(a, tiles, stream);
-    } else if (a.fmt == 2) {
-        if (ring) rc = mg == 2 ? launch_planar<1, 2, 2, 1, 3>(a, tiles, stream) : launch_planar<1, 1, 2, 1, 3>(a, tiles, stream);
-        else rc = mg == 2 ? launch_planar<1, 2, 2, 1>(a, tiles, stream) : launch_planar<1, 1, 2, 1>(a, tiles, stream);
-    } else if (a.fmt == 1) {
-        if (ring) rc = mg == 2 ? launch_planar<2, 2, 2, 1, 3>(a, tiles, stream) : launch_planar<2, 1, 2, 1, 3>(a, tiles, stream);
-        else rc = mg == 2 ? launch_planar<2, 2, 2, 1>(a, tiles, stream) : launch_planar<2, 1, 2, 1>(a, tiles, stream);
-    } else if (g->planes == 3) rc = mg == 2 ? launch_planar<3, 2, 2>(a, tiles, stream) : launch_planar<3, 1, 2>(a, tiles, stream);
-    else rc = mg == 2 ? launch_planar<2, 2, 2>(a, tiles, stream) : launch_planar<2, 1, 2>(a, tiles, stream);
-    return rc != STM_OK ? rc : finish_splitk();
+    for (const Launch& l : L) {
+        if (!l.planned) continue;
+        rc = run_launch(l, stream);
+        if (rc != STM_OK) return rc;
+    }
+    if (a.splitk < 2) return STM_OK;
+    // the parts' partial sums -> the epilogue
+    const int64_t total = (int64_t)a.M * a.groups * ((a.cout_g + 7) / 8);
+    if (t_plan_text) { t_plan_text->add("planar_splitk_finish_kernel grid=%d block=256 lds=0\n", stm_cdiv(total, 256)); return STM_OK; }
+    hipLaunchKernelGGL(planar_splitk_finish_kernel, dim3(stm_cdiv(total, 256)), dim3(256), 0, stm_hs(stream), a, f.bn);
+    STM_CHECK_LAUNCH("planar_splitk_finish_kernel");
+    return STM_OK;
+}
+
+// window 0 stands in for the common checks and fields of a window set
+stm_conv_geom window0_geom(const stm_conv_geom* g, const stm_conv_window& w)
+{
+    stm_conv_geom g0 = *g;
+    g0.kh = w.kh; g0.kw = w.kw; g0.ph = w.ph; g0.pw = w.pw;
+    g0.Ho = w.Ho; g0.Wo = w.Wo; g0.win_y0 = w.y0; g0.win_x0 = w.x0;
+    return g0;
 }
 }  // namespace
+
+extern "C" int stm_conv2d_planar_ws_f32(const void* x_planes, const void* packed_weight, const float* bias, const float* residual_f32,
+                                        const void* residual_planes, float* out_f32, void* out_planes, const stm_conv_geom* g,
+                                        int relu, void* workspace, size_t workspace_bytes, stm_stream_t stream)
+{
+    return conv2d_planar_impl({x_planes, packed_weight, bias, residual_f32, residual_planes, out_f32, out_planes, g, relu, workspace, workspace_bytes,
+                               nullptr, nullptr}, stream);
+}
+
+// Two-source 1x1 convolution: y = W [x1 ; x2(stride s2)] + bias (+ residual) -- the last 1x1 convolution of a ResNet stage's first
+// bottleneck and its projection shortcut (backbone.py:38-58: out = conv3(...); out += downsample(x); relu) as ONE product over the
+// concatenated channels.  g describes the output (B, Ho, Wo = H, W of the first source; kh = kw = 1, stride 1, no padding; C = C1 + C2
+// = the weight's input channels); x_planes holds the first C1 = g->C - C2 channels at one pixel per output pixel (x_np / x_plane_stride
+// of g), x2_planes the other C2 channels as B images of H2 x W2 read at stride s2 (Ho = (H2 - 1) / s2 + 1).  The projection's output
+// tensor -- 4 * planes channels written, then read back as conv3's residual: 1 GB per launch pair in layer1 at batch 32 -- never exists.
+extern "C" int stm_conv2d_planar_dual_f32(const void* x_planes, const void* x2_planes, int C2, int H2, int W2, int s2, long long x2_np,
+                                          long long x2_plane_stride, const void* packed_weight, const float* bias, const float* residual_f32,
+                                          const void* residual_planes, float* out_f32, void* out_planes, const stm_conv_geom* g, int relu,
+                                          void* workspace, size_t workspace_bytes, stm_stream_t stream)
+{
+    STM_REQUIRE(x2_planes && g, STM_ENULL, "stm_conv2d_planar_dual_f32: x2_planes / geometry must be non-NULL");
+    DualSrc d{x2_planes, C2, H2, W2, s2, x2_np, x2_plane_stride};
+    return conv2d_planar_impl({x_planes, packed_weight, bias, residual_f32, residual_planes, out_f32, out_planes, g, relu, workspace, workspace_bytes,
+                               &d, nullptr}, stream);
+}
+
+// Several window launches (stm_conv_geom.win_*) of ONE layer as one grid: window i has its own sub-kernel (kh x kw taps, packed weights
+// packed[i], all under the same weight scale) and its own Ho x Wo rectangle at (y0, x0) of every win_h x win_w output image.  g gives what
+// the windows share: B, H, W, C, Cout, sh = sw = 1, fmt 1, planes, tile_n 128, out_scale, win_h / win_w, the buffer geometry.  The tiles of
+// all windows form one grid, so the small windows (a row or a corner of a 7x7 RoI map) do not pay a launch and a partial last round each:
+// TemporalNet's 3x3 layers run their nine border classes -- the taps that can be inside the map, 361 of 441 tap-pixels -- at the
+// efficiency of the single padded launch.  Same sums as that launch (a skipped tap added exact zeros): bit-equal.
+extern "C" int stm_conv2d_planar_windows_f32(const void* x_planes, const void* const* packed_weights, const stm_conv_window* windows, int n_windows,
+                                             const float* bias, float* out_f32, void* out_planes, const stm_conv_geom* g, int relu, stm_stream_t stream)
+{
+    const char* who = "stm_conv2d_planar_windows_f32";
+    STM_REQUIRE(packed_weights && windows && g, STM_ENULL, "%s: NULL argument", who);
+    STM_REQUIRE(n_windows >= 1 && n_windows <= 9, STM_EINVAL, "%s: 1 .. 9 windows", who);
+    // (groups: the gated form only, checked where the gate is taken)
+    STM_REQUIRE(g->win_w > 0 && g->win_h > 0 && g->fmt == 1 && g->sh == 1 && g->sw == 1 && g->n_levels <= 0 &&
+                (g->tile_n == 0 || g->tile_n == 128), STM_EUNSUPPORTED, "%s: fp16x2 planes, stride 1, 128-channel tiles, win_h / win_w set", who);
+    for (int i = 0; i < n_windows; ++i) STM_REQUIRE(packed_weights[i], STM_ENULL, "%s: packed weight %d is NULL", who, i);
+    const stm_conv_geom g0 = window0_geom(g, windows[0]);
+    WinSet ws{packed_weights, windows, n_windows, nullptr};
+    return conv2d_planar_impl({x_planes, packed_weights[0], bias, nullptr, nullptr, out_f32, out_planes, &g0, relu, nullptr, 0, nullptr, &ws}, stream);
+}
+
+// The same window set with ReLU and the average pool over each output image folded into the epilogue (TemporalNet's conv3 + ReLU + AvgPool2d((7, 7)):
+// track_to_segment_head.py:30-33): nothing is written per pixel; pool_fix[image][channel] (row length Cout, unsigned 64-bit, 32.32 fixed point)
+// receives the SUM over the image's win_h x win_w pixels of relu(conv + bias), added to what it holds -- the caller zeroes it (stm_temporal_pool_fc_f32
+// does, when it consumes it).  Integer accumulation: the result does not depend on the order in which the workgroups finish.  Sums must stay below
+// 2^32 - win_h * win_w * 2^16 (the per-device range flag is raised otherwise, as for an fp16 overflow: pooled_epilogue).
+extern "C" int stm_conv2d_planar_windows_pool_f32(const void* x_planes, const void* const* packed_weights, const stm_conv_window* windows, int n_windows,
+                                                  const float* bias, unsigned long long* pool_fix, const stm_conv_geom* g, stm_stream_t stream)
+{
+    const char* who = "stm_conv2d_planar_windows_pool_f32";
+    STM_REQUIRE(packed_weights && windows && g && pool_fix, STM_ENULL, "%s: NULL argument", who);
+    STM_REQUIRE(n_windows >= 1 && n_windows <= 9, STM_EINVAL, "%s: 1 .. 9 windows", who);
+    STM_REQUIRE(g->win_w > 0 && g->win_h > 0 && g->fmt == 1 && g->sh == 1 && g->sw == 1 && (g->groups <= 1) && g->n_levels <= 0 &&
+                (g->tile_n == 0 || g->tile_n == 128) && g->Cout % 128 == 0, STM_EUNSUPPORTED,
+                "%s: fp16x2 planes, stride 1, one group, whole 128-channel tiles, win_h / win_w set", who);
+    STM_REQUIRE((int64_t)g->win_h * g->win_w <= 32768, STM_EUNSUPPORTED, "%s: pooled images of at most 32768 pixels", who);   // (pooled_epilogue's margin)
+    STM_REQUIRE((uintptr_t)pool_fix % 8 == 0, STM_EINVAL, "%s: pool_fix must be 8-byte aligned", who);
+    for (int i = 0; i < n_windows; ++i) STM_REQUIRE(packed_weights[i], STM_ENULL, "%s: packed weight %d is NULL", who, i);
+    const stm_conv_geom g0 = window0_geom(g, windows[0]);
+    WinSet ws{packed_weights, windows, n_windows, pool_fix};
+    return conv2d_planar_impl({x_planes, packed_weights[0], bias, nullptr, nullptr, nullptr, nullptr, &g0, 1, nullptr, 0, nullptr, &ws}, stream);
+}
+
+// Dry run of the four entries above (include/stmask_hip.h): the entry the arguments select runs with this thread's launches turned into lines of
+// `text` -- the same checks, the same plan, the same status and error string; no launch, no LDS reservation.
+extern "C" int stm_debug_conv2d_planar_plan(const void* x_planes, const void* packed_weight, const float* bias, const float* residual_f32,
+                                            const void* residual_planes, float* out_f32, void* out_planes, const stm_conv_geom* g, int relu,
+                                            void* workspace, size_t workspace_bytes, const void* x2_planes, int C2, int H2, int W2, int s2,
+                                            long long x2_np, long long x2_plane_stride, const void* const* packed_weights,
+                                            const stm_conv_window* windows, int n_windows, unsigned long long* pool_fix, const int* gate, char* text,
+                                            size_t text_bytes)
+{
+    STM_REQUIRE(text && text_bytes > 0, STM_ENULL, "stm_debug_conv2d_planar_plan: text must be a buffer");
+    PlanText t{text, text_bytes, 0, false};
+    text[0] = 0;
+    stm_conv_set_pixel_gate(gate);
+    t_plan_text = &t;
+    const int rc = windows ? (pool_fix ? stm_conv2d_planar_windows_pool_f32(x_planes, packed_weights, windows, n_windows, bias, pool_fix, g, nullptr)
+                                       : stm_conv2d_planar_windows_f32(x_planes, packed_weights, windows, n_windows, bias, out_f32, out_planes, g, relu, nullptr))
+                   : x2_planes ? stm_conv2d_planar_dual_f32(x_planes, x2_planes, C2, H2, W2, s2, x2_np, x2_plane_stride, packed_weight, bias, residual_f32,
+                                                            residual_planes, out_f32, out_planes, g, relu, workspace, workspace_bytes, nullptr)
+                               : stm_conv2d_planar_ws_f32(x_planes, packed_weight, bias, residual_f32, residual_planes, out_f32, out_planes, g, relu,
+                                                          workspace, workspace_bytes, nullptr);
+    t_plan_text = nullptr;
+    stm_internal_take_pixel_gate();      // (an entry that refused its arguments before the launcher did not take it)
+    STM_REQUIRE(rc != STM_OK || !t.cut, STM_EINVAL, "stm_debug_conv2d_planar_plan: the plan does not fit %zu bytes of text", text_bytes);
+    return rc;
+}
+
 
 extern "C" long long stm_debug_launch_count(int which)
 {
