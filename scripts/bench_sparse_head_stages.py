@@ -88,7 +88,7 @@ stages = []
 def ev():
     e = torch.cuda.Event(enable_timing=True); e.record(); return e
 def shapes_rest(cls, m):
-    # PlanarGraph._sparse_head_shapes from the candidates on: entries in one segment per kernel shape, the towers as gated window sets
+    # PlanarGraph._sparse_patches_shapes from the candidates on: entries in one segment per kernel shape, the towers as gated window sets
     lst, ctl = ops.head_candidates(cls, head.num_classes, thr, segn, [h * w for h, w, _, _ in W1], [h * w for h, w, _, _ in W2], B, sizes, split=True, shapes=True); m("candidates")
     tot = K * segn
     patch = ops.head_patch_gather(up, torch.empty(NP, cw // 32, tot * 81, 32, device=dev, dtype=pdt), 9, segn, B, sizes, lst, ctl, segs=K); m("gather 9x9")

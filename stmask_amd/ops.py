@@ -1388,13 +1388,19 @@ def conv_pack_weights(weight, planes=3, tile_n=128, fmt=0, wscale=None):
     return packed
 
 
-def conv2d_planar_windows(xp, packed_list, windows, bias, B, H, W, C, O, out_h, out_w, out_scale, relu=True, out_f32=None, out_planes=None):
-    """stm_conv2d_planar_windows_f32: several window launches of one fp16x2 layer as one grid.  xp [2, C/32, >= B*H*W, 32]; packed_list[i] /
-    windows[i] = (kh, kw, ph, pw, Ho, Wo, y0, x0): sub-kernel weights (conv_pack_weights(..., tile_n=128, fmt=1, wscale=common)) and window of
-    the out_h x out_w output image; out_f32 [B*out_h*out_w, O] and / or out_planes [2, O/32, B*out_h*out_w, 32] are written in place."""
-    _dev(xp)
-    if out_f32 is None and out_planes is None:
-        raise StmError("conv2d_planar_windows: no output given")
+def layer_geom(C, O, kh, kw, sh, sw, ph, pw, planes, groups, group_cout=None):
+    """ConvGeom of a plain layer: what PlanarConv knows of itself before it sees an input (C per group; group_cout: real channels of padded groups)."""
+    g = _lib.ConvGeom()
+    g.C, g.Cout, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, g.planes, g.groups = C, O, kh, kw, sh, sw, ph, pw, planes, groups
+    for i, c in enumerate(group_cout or ()):
+        g.group_cout[i] = c
+    return g
+
+
+def _window_set(xp, packed_list, windows, B, H, W, C, O, out_h, out_w, out_scale, out_f32=None, out_planes=None):
+    """(ConvGeom, weight pointers, ConvWindow array) of a window set: fp16x2 planes, stride 1, 256 x 128 tiles, windows[i] = (kh, kw, ph, pw, Ho, Wo,
+    y0, x0) of the out_h x out_w output image.  The one place that writes these fields: conv2d_planar_windows, conv2d_planar_windows_pool and
+    PlanarConv.window_segments (which adds its groups) launch what it returns."""
     n = len(windows)
     g = _lib.ConvGeom()
     g.B, g.H, g.W, g.C, g.Cout, g.sh, g.sw, g.planes, g.fmt, g.tile_n = B, H, W, C, O, 1, 1, 2, 1, 128
@@ -1409,9 +1415,19 @@ def conv2d_planar_windows(xp, packed_list, windows, bias, B, H, W, C, O, out_h, 
     wins = (_lib.ConvWindow * n)()
     for i, wv in enumerate(windows):
         wins[i].kh, wins[i].kw, wins[i].ph, wins[i].pw, wins[i].Ho, wins[i].Wo, wins[i].y0, wins[i].x0 = wv
-    ptrs = (ctypes.c_void_p * n)(*[p.data_ptr() for p in packed_list])
-    call("stm_conv2d_planar_windows_f32", _p(xp), ptrs, wins, n, _p(bias) if bias is not None else None, _p(out_f32) if out_f32 is not None else None,
-         _p(out_planes) if out_planes is not None else None, ctypes.byref(g), 1 if relu else 0, _stream())
+    return g, (ctypes.c_void_p * n)(*[p.data_ptr() for p in packed_list]), wins
+
+
+def conv2d_planar_windows(xp, packed_list, windows, bias, B, H, W, C, O, out_h, out_w, out_scale, relu=True, out_f32=None, out_planes=None):
+    """stm_conv2d_planar_windows_f32: several window launches of one fp16x2 layer as one grid.  xp [2, C/32, >= B*H*W, 32]; packed_list[i] /
+    windows[i] = (kh, kw, ph, pw, Ho, Wo, y0, x0): sub-kernel weights (conv_pack_weights(..., tile_n=128, fmt=1, wscale=common)) and window of
+    the out_h x out_w output image; out_f32 [B*out_h*out_w, O] and / or out_planes [2, O/32, B*out_h*out_w, 32] are written in place."""
+    _dev(xp)
+    if out_f32 is None and out_planes is None:
+        raise StmError("conv2d_planar_windows: no output given")
+    g, ptrs, wins = _window_set(xp, packed_list, windows, B, H, W, C, O, out_h, out_w, out_scale, out_f32, out_planes)
+    call("stm_conv2d_planar_windows_f32", _p(xp), ptrs, wins, len(windows), _p(bias) if bias is not None else None,
+         _p(out_f32) if out_f32 is not None else None, _p(out_planes) if out_planes is not None else None, ctypes.byref(g), 1 if relu else 0, _stream())
     return out_f32 if out_f32 is not None else out_planes
 
 
@@ -1421,18 +1437,8 @@ def conv2d_planar_windows_pool(xp, packed_list, windows, bias, B, H, W, C, O, ou
     _dev(xp)
     if pool_fix.dtype != torch.int64 or pool_fix.dim() != 2 or pool_fix.shape[0] < B or pool_fix.shape[1] != O or not pool_fix.is_contiguous():
         raise StmError("conv2d_planar_windows_pool: pool_fix must be a contiguous int64 [>= B, O] tensor")
-    n = len(windows)
-    g = _lib.ConvGeom()
-    g.B, g.H, g.W, g.C, g.Cout, g.sh, g.sw, g.planes, g.fmt, g.tile_n = B, H, W, C, O, 1, 1, 2, 1, 128
-    g.kh, g.kw, g.Ho, g.Wo = windows[0][0], windows[0][1], windows[0][4], windows[0][5]
-    g.win_h, g.win_w = out_h, out_w
-    g.out_scale = out_scale
-    g.x_np, g.x_plane_stride = xp.shape[2], xp.shape[1] * xp.shape[2] * 32
-    wins = (_lib.ConvWindow * n)()
-    for i, wv in enumerate(windows):
-        wins[i].kh, wins[i].kw, wins[i].ph, wins[i].pw, wins[i].Ho, wins[i].Wo, wins[i].y0, wins[i].x0 = wv
-    ptrs = (ctypes.c_void_p * n)(*[p.data_ptr() for p in packed_list])
-    call("stm_conv2d_planar_windows_pool_f32", _p(xp), ptrs, wins, n, _p(bias) if bias is not None else None, _p(pool_fix), ctypes.byref(g),
+    g, ptrs, wins = _window_set(xp, packed_list, windows, B, H, W, C, O, out_h, out_w, out_scale)
+    call("stm_conv2d_planar_windows_pool_f32", _p(xp), ptrs, wins, len(windows), _p(bias) if bias is not None else None, _p(pool_fix), ctypes.byref(g),
          _stream())
     return pool_fix
 
@@ -2004,12 +2010,7 @@ def head_assemble(small, trk, B, sizes, n_cls, mask_dim, embed_dim, group_pad):
     for t in list(small) + list(trk):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[0] != start:
             raise StmError("head_assemble: inputs must be contiguous fp32 matrices over all level pixels")
-    dev = small[0].device
-    conf = torch.empty(B, N, n_cls, device=dev)
-    loc = torch.empty(B, N, 4, device=dev)
-    mask = torch.empty(B, N, mask_dim, device=dev)
-    track = torch.empty(B, N, embed_dim, device=dev)
-    cen = torch.empty(B, N, 1, device=dev)
+    conf, loc, mask, track, cen = (torch.empty(B, N, n, device=small[0].device) for n in (n_cls, 4, mask_dim, embed_dim, 1))
     call("stm_head_assemble_f32", _ptr4(small), _ptr4(trk), ctypes.byref(L), _p(conf), _p(loc), _p(mask), _p(track), _p(cen), _stream())
     return conf, loc, mask, track, cen
 
@@ -2036,15 +2037,19 @@ def conv_set_pixel_gate(ctl, index):
     _lib.lib().stm_conv_set_pixel_gate(ctl.data_ptr() + 4 * index)
 
 
+def level_starts(B, sizes):
+    """First pixel of each level on the concatenated pixel axis -- levels `sizes` = [(h, w), ...] with B images each -- and, last, the pixels of
+    all levels.  The one place that lays the levels out: PlanarConv's multi-level launches, PlanarGraph.run and the head's entry points use it."""
+    starts = [0]
+    for h, w in sizes:
+        starts.append(starts[-1] + B * h * w)
+    return starts
+
+
 def _level_arrays(B, sizes):
-    n = len(sizes)
-    st, hh, ww = (ctypes.c_int * 9)(), (ctypes.c_int * 8)(), (ctypes.c_int * 8)()
-    start = 0
-    for l, (h, w) in enumerate(sizes):
-        st[l], hh[l], ww[l] = start, h, w
-        start += B * h * w
-    st[n] = start
-    return n, st, hh, ww, start
+    n, starts = len(sizes), level_starts(B, sizes)
+    st, hh, ww = (ctypes.c_int * 9)(*starts), (ctypes.c_int * 8)(*[h for h, _ in sizes]), (ctypes.c_int * 8)(*[w for _, w in sizes])
+    return n, st, hh, ww, starts[n]
 
 
 def _head_layout(B, K, sizes, n_cls, mask_dim, embed_dim, group_pad, small_ld, trk_ld):
@@ -2052,11 +2057,10 @@ def _head_layout(B, K, sizes, n_cls, mask_dim, embed_dim, group_pad, small_ld, t
     L = _lib.HeadLayout()
     L.B, L.K, L.n_levels, L.n_cls, L.mask_dim, L.embed_dim, L.group_pad = B, K, len(sizes), n_cls, mask_dim, embed_dim, group_pad
     L.small_ld, L.trk_ld = small_ld, trk_ld
-    start = 0
+    starts = level_starts(B, sizes)
     for l, (h, w) in enumerate(sizes):
-        L.lvl_start[l], L.lvl_hw[l] = start, h * w
-        start += B * h * w
-    return L, start
+        L.lvl_start[l], L.lvl_hw[l] = starts[l], h * w
+    return L, starts[-1]
 
 
 def _ptr4(ts):
@@ -2136,12 +2140,7 @@ def head_assemble_sparse(cls_logits, small, trk, small_dense, trk_dense, B, size
     for t, d in zip(list(small) + list(trk), list(small_dense) + list(trk_dense)):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[0] < capacity * row_mul or t.shape[-1] != d.shape[-1]:
             raise StmError("head_assemble_sparse: patch inputs must be contiguous fp32 matrices of capacity * row_mul rows, as wide as the dense ones")
-    dev = cls_logits[0].device
-    conf = torch.empty(B, N, n_cls, device=dev)
-    loc = torch.empty(B, N, 4, device=dev)
-    mask = torch.empty(B, N, mask_dim, device=dev)
-    track = torch.empty(B, N, embed_dim, device=dev)
-    cen = torch.empty(B, N, 1, device=dev)
+    conf, loc, mask, track, cen = (torch.empty(B, N, n, device=cls_logits[0].device) for n in (n_cls, 4, mask_dim, embed_dim, 1))
     call("stm_head_assemble_sparse_f32", _ptr4(cls_logits), cls_logits[0].shape[-1], _ptr4(small), _ptr4(trk), _ptr4(small_dense), _ptr4(trk_dense),
          ctypes.byref(L), row_mul, row_add, _p(lst), _p(ctl), -head_seg_capacity(capacity, segs) if split else capacity, _p(conf), _p(loc), _p(mask), _p(track), _p(cen), _stream())
     return conf, loc, mask, track, cen

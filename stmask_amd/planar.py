@@ -22,8 +22,8 @@ from typing import Any, NamedTuple, Optional
 import torch
 import torch.nn.functional as F
 
-from . import _lib, ops
-from ._lib import StmError, call
+from . import ops
+from ._lib import ConvGeom, StmError, call
 from .ops import _pair
 
 
@@ -131,8 +131,11 @@ class PlanarConv:
         # L2 -> LDS staging rate on the 128 x 64 tiles (head output layers, DCN offset convolutions, layer1's 3x3)
         self.kxr = CONV_KXR and self.out_fmt == self.fmt and ops.conv_kxr_supported(self.O, self.C, self.kh, self.kw, (self.sh, self.sw), (self.ph, self.pw),
                                                                                      self.groups, self.group_cout, self.fmt, max_tiles=3)
-        self.kxr_min_pixels = None   # None: the measured thresholds of __call__; tests set 0 to force the kernel on small inputs
+        self.kxr_min_pixels = None   # None: the measured thresholds of _pick_kernel; tests set 0 to force the kernel on small inputs
         self.bias = bias.detach().float().contiguous() if bias is not None else None
+        # the fields of a launch's ConvGeom that are the layer's own, filled once: every call starts from a copy
+        (self._np, self._dt), (self._npo, self._dto) = ops.plane_layout(self.fmt), ops.plane_layout(self.out_fmt)      # planes read / written
+        self._geom = ops.layer_geom(self.C, self.O, self.kh, self.kw, self.sh, self.sw, self.ph, self.pw, self.planes, self.groups, self.group_cout)
 
     def packed(self, tile_n):
         if tile_n not in self._packed:
@@ -144,7 +147,7 @@ class PlanarConv:
         return self._packed[tile_n]
 
     def kxr_rule_pixels(self):
-        """Pixels from which the kx-reuse kernel takes a layer it supports (measured: see __call__)."""
+        """Pixels from which the kx-reuse kernel takes a layer it supports (measured: see _pick_kernel)."""
         return 20000 if self.groups > 1 else 30000
 
     def pick_tile(self, M):
@@ -183,75 +186,87 @@ class PlanarConv:
         kxr: True / False decides the kx-reuse kernel for a layer it supports (None: by the pixel count); splitk = False: never split K.
         window = (0, 0, 1, 1, ph, pw, 1, 1), ph / pw <= 0: ONE output pixel per image -- input (-ph + ky, -pw + kx) -- as row b of the outputs; the
         only window form the kx-reuse kernel takes (its centre-window launch; the gate then counts images).
-        out_slab_off: the plane output starts at that 32-channel slab of out_planes (a layer cut out of a wider one writes its own channels)."""
-        NP, dt = ops.plane_layout(self.fmt)
+        out_slab_off: the plane output starts at that 32-channel slab of out_planes (a layer cut out of a wider one writes its own channels).
+        The steps: check the planes, geometry of the input side, kernel choice, outputs, residual, launch, timing record."""
+        S, N = self._check_input(xp, x_ch_off, x2)
+        g, M, full = self._input_geom(S, N, shape, x_off, window, residual is not None or x2 is not None)
+        g.tile_n = self._pick_kernel(M, full, window, residual is not None, kxr)
+        dev = xp.device
+        out_f32, out_planes, p_f32, p_pl = self._outputs(g, M, dev, out, out_planes, out_f32, out_off, out_ch_off, out_slab_off, window is not None)
+        r32, rpl = self._residual(g, residual) if residual is not None else (0, 0)
+        started = _timing_start()
+        x_ptr = xp.data_ptr() + ((x_ch_off // 32) * N + x_off) * 64
+        self._launch(g, x_ptr, p_f32, p_pl, r32, rpl, x2, gate, splitk, dev, shape[0] == "img")
+        if started is not None:
+            # layer key: tile 0 = the kx-reuse kernel
+            _timing_stop(started, 2.0 * M * self.O * self.C * self.kh * self.kw * self.algo_frac, (M, self.C, self.O, self.kh, self.sh, self.groups, g.tile_n),
+                         {0: 6 if self.planes == 3 else 3, 1: 3, 2: 1}[self.fmt], self.role, self._algo_bytes(M, shape, out_f32, out_planes, residual))
+        return (out_f32, out_planes) if out == "both" else (out_f32 if out == "f32" else out_planes)
+
+    def _check_input(self, xp, x_ch_off, x2):
+        """-> (channel slabs S, pixels N) of the planes xp, which are this layer's format and hold the channels it reads."""
+        NP, dt = self._np, self._dt
         if xp.dtype != dt or xp.dim() != 4 or xp.shape[0] < NP or xp.shape[3] != 32 or not xp.is_contiguous():
             raise StmError(f"PlanarConv: expected contiguous {dt} planes [{NP}, S, N, 32], got {xp.dtype} {tuple(xp.shape)}")
         # (a fp16x1 layer handed a two-plane fp16 tensor reads plane 0 = RN16(x): the one-plane tensor of the same values)
-        S, N = xp.shape[1], xp.shape[2]
-        g = _lib.ConvGeom()
-        g.C, g.Cout, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw = self.C, self.O, self.kh, self.kw, self.sh, self.sw, self.ph, self.pw
-        g.planes, g.groups = self.planes, self.groups
-        if self.group_cout:
-            for i, c in enumerate(self.group_cout):
-                g.group_cout[i] = c
         # x2 = (planes2, H2, W2, stride): a two-source 1x1 layer (stm_conv2d_planar_dual_f32) -- xp holds the first C - C2 input channels at
         # the output's resolution, planes2 the other C2 channels as B images of H2 x W2 read at `stride`
+        _, S, N, _ = xp.shape
         c_first = self.C - (x2[0].shape[1] * 32 if x2 is not None else 0)
         if S * 32 < x_ch_off + self.groups * c_first or x_ch_off % 32:
             raise StmError(f"PlanarConv: input has {S * 32} channels, layer reads {self.groups} x {c_first} from channel {x_ch_off}")
+        return S, N
+
+    def _input_geom(self, S, N, shape, x_off, window, extra_input):
+        """-> (ConvGeom of the layer and its input side, output pixels M, full: a multi-level launch or Ho x Wo = H x W); extra_input: a residual or x2 is given."""
+        g = ConvGeom.from_buffer_copy(self._geom)
+        g.x_np, g.x_plane_stride = N, S * N * 32
         if shape[0] == "levels":
             _, B, sizes = shape
             g.n_levels = len(sizes)
-            start = 0
+            starts = ops.level_starts(B, sizes)
             for l, (h, w) in enumerate(sizes):
-                g.lvl_start[l], g.lvl_h[l], g.lvl_w[l] = start, h, w
-                start += B * h * w
-            g.lvl_start[len(sizes)] = start
-            M = start
-            if x_off or N != start:
+                g.lvl_start[l], g.lvl_h[l], g.lvl_w[l] = starts[l], h, w
+            g.lvl_start[len(sizes)] = starts[-1]
+            if x_off or N != starts[-1]:
                 raise StmError("PlanarConv: a multi-level launch covers the whole plane buffer")
-        else:
-            _, B, H, W = shape
-            Ho, Wo = ops.conv_out_hw(H, W, self.kh, self.kw, self.sh, self.sw, self.ph, self.pw, 1, 1)
-            out_rows = None
-            if window is not None:
-                # window launch (stm_conv_geom.win_*): (y0, x0, ho, wo, ph, pw, full_h, full_w) -- only the ho x wo outputs from (y0, x0) of
-                # every full_h x full_w output image, written in place into the full output tensors; ph / pw may be negative
-                y0, x0, Ho, Wo, g.ph, g.pw, fh, fw = window
-                g.win_h, g.win_w, g.win_y0, g.win_x0 = fh, fw, y0, x0
-                out_rows = B * fh * fw
-                if residual is not None or x2 is not None:
-                    raise StmError("PlanarConv: window launches take no residual / second source")
-            g.B, g.H, g.W, g.Ho, g.Wo = B, H, W, Ho, Wo
-            M = B * Ho * Wo
-            if x_off + B * H * W > N:
-                raise StmError("PlanarConv: input slice runs past the plane buffer")
-        g.x_np, g.x_plane_stride = N, S * N * 32
+            return g, starts[-1], True
+        _, B, H, W = shape
+        Ho, Wo = ops.conv_out_hw(H, W, self.kh, self.kw, self.sh, self.sw, self.ph, self.pw, 1, 1)
+        full = (Ho, Wo) == (H, W)
+        if window is not None:
+            # window launch (stm_conv_geom.win_*): (y0, x0, ho, wo, ph, pw, full_h, full_w) -- only the ho x wo outputs from (y0, x0) of
+            # every full_h x full_w output image, written in place into the full output tensors; ph / pw may be negative
+            g.win_y0, g.win_x0, Ho, Wo, g.ph, g.pw, g.win_h, g.win_w = window
+            if extra_input:
+                raise StmError("PlanarConv: window launches take no residual / second source")
+        g.B, g.H, g.W, g.Ho, g.Wo = B, H, W, Ho, Wo
+        if x_off + B * H * W > N:
+            raise StmError("PlanarConv: input slice runs past the plane buffer")
+        return g, B * Ho * Wo, full
+
+    def _pick_kernel(self, M, full, window=None, has_residual=False, kxr=None):
+        """ConvGeom.tile_n for M output pixels: 0 = the kx-reuse kernel, else pick_tile(M).  Numbers and flags only (tests/planar_trace.py tabulates it)."""
         # measured against the 128 x 64 tiles (scripts/bench_kxr.py, 1 / 4 / 8 / 32 clips): the head's grouped output layers win from
         # ~20 000 pixels (x1.3-1.8), single-group layers of up to 48 channels from ~30 000 (x1.1-1.4); below that its 256-pixel tiles
         # leave CUs idle, and four channel tiles (layer1's 64 -> 64) stay on the general kernel (x0.65)
-        one_px = window is not None and tuple(window[:4]) == (0, 0, 1, 1) and tuple(window[6:]) == (1, 1)
-        use_kxr = (self.kxr and residual is None and (one_px if window is not None else (shape[0] == "levels" or (Ho, Wo) == (H, W)))
+        if window is not None:      # the one-pixel window is the only one the kernel takes
+            full = tuple(window[:4]) == (0, 0, 1, 1) and tuple(window[6:]) == (1, 1)
+        use_kxr = (self.kxr and not has_residual and full
                    and (kxr if kxr is not None else M >= (self.kxr_min_pixels if self.kxr_min_pixels is not None else self.kxr_rule_pixels())))
-        g.tile_n = 0 if use_kxr else self.pick_tile(M)
-        dev = xp.device
-        NPo, dto = ops.plane_layout(self.out_fmt)
-        if window is not None and ((out in ("planes", "both") and out_planes is None) or (out in ("f32", "both") and out_f32 is None)):
+        return 0 if use_kxr else self.pick_tile(M)
+
+    def _outputs(self, g, M, dev, out, out_planes, out_f32, out_off, out_ch_off, out_slab_off, is_window):
+        """Allocates the outputs `out` asks for or adopts the given ones from pixel out_off on -> (out_f32, out_planes, first fp32 / plane address written)."""
+        want_pl, want_32 = out in ("planes", "both"), out in ("f32", "both")
+        if is_window and ((want_pl and out_planes is None) or (want_32 and out_f32 is None)):
             raise StmError("PlanarConv: a window launch writes into caller-provided full-size outputs")
-        if out in ("planes", "both") and out_planes is None:
-            out_planes, out_off_p = torch.empty(NPo, -(-self.O // 32), M, 32, device=dev, dtype=dto), 0
-        else:
-            out_off_p = out_off
-        if out in ("f32", "both") and out_f32 is None:
+        out_off_p = out_off_f = out_off
+        if want_pl and out_planes is None:
+            out_planes, out_off_p = torch.empty(self._npo, -(-self.O // 32), M, 32, device=dev, dtype=self._dto), 0
+        if want_32 and out_f32 is None:
             out_f32, out_off_f = torch.empty(M, self.O, device=dev, dtype=torch.float32), 0
-        else:
-            out_off_f = out_off
-        if out == "planes":
-            out_f32 = None
-        if out == "f32":
-            out_planes = None
-        p_pl = p_f32 = 0
+        out_f32, out_planes, p_pl, p_f32 = (out_f32 if want_32 else None), (out_planes if want_pl else None), 0, 0
         if out_planes is not None:
             g.out_np, g.out_plane_stride = out_planes.shape[2], out_planes.shape[1] * out_planes.shape[2] * 32
             if out_slab_off < 0 or out_slab_off + -(-self.O // 32) > out_planes.shape[1]:
@@ -260,19 +275,21 @@ class PlanarConv:
         if out_f32 is not None:
             g.out_ld = out_f32.shape[-1]
             p_f32 = out_f32.data_ptr() + (out_off_f * g.out_ld + out_ch_off) * 4   # fp32 output may start at a column
-        r32 = rpl = 0
-        if residual is not None:
-            if residual.dtype == dt:
-                if residual.shape[0] < NP:
-                    raise StmError(f"PlanarConv: residual has {residual.shape[0]} plane(s), format {self.fmt} reads {NP}")
-                g.res_np, g.res_plane_stride = residual.shape[2], residual.shape[1] * residual.shape[2] * 32
-                rpl = residual.data_ptr()
-            else:
-                g.res_ld = residual.shape[-1]
-                r32 = residual.data_ptr()
-        started = _timing_start()
-        x_ptr = xp.data_ptr() + ((x_ch_off // 32) * N + x_off) * 64
-        if use_kxr:
+        return out_f32, out_planes, p_f32, p_pl
+
+    def _residual(self, g, residual):
+        """-> (address of an fp32 residual [M, ld], address of a residual in planes of this layer's format), one of them or both 0."""
+        if residual.dtype != self._dt:
+            g.res_ld = residual.shape[-1]
+            return residual.data_ptr(), 0
+        if residual.shape[0] < self._np:
+            raise StmError(f"PlanarConv: residual has {residual.shape[0]} plane(s), format {self.fmt} reads {self._np}")
+        g.res_np, g.res_plane_stride = residual.shape[2], residual.shape[1] * residual.shape[2] * 32
+        return 0, residual.data_ptr()
+
+    def _launch(self, g, x_ptr, p_f32, p_pl, r32, rpl, x2, gate, splitk, dev, is_img):
+        """Packs on first use, sets the gate and launches: the kx-reuse kernel (g.tile_n = 0), else the tiles with one source or two (x2)."""
+        if g.tile_n == 0:
             g.fmt = self.fmt
             if "kxr" not in self._packed:
                 ops.planar_range_flag()
@@ -280,32 +297,23 @@ class PlanarConv:
             packed, g.out_scale = self._packed["kxr"]
             if gate is not None:
                 ops.conv_set_pixel_gate(*gate)
-            call("stm_conv2d_planar_kxr_f32", x_ptr, ops._p(packed), ops._p(self.bias), p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0, ops._stream())
-        else:
-            packed = self.packed(g.tile_n)                     # (sets self.out_scale for the fp16 format)
-            g.fmt, g.out_scale = self.fmt, self.out_scale
-            g.out_fmt_plus1 = 0 if self.out_fmt == self.fmt else self.out_fmt + 1
-            ws = ops._workspace(self.SPLITK_WS_BYTES, dev, "conv_splitk") if splitk and gate is None else None     # grow-only, shared: split-K partial sums
-            if gate is not None:
-                if x2 is not None:
-                    raise StmError("PlanarConv: gated launches take no second source")
-                ops.conv_set_pixel_gate(*gate)
+            return call("stm_conv2d_planar_kxr_f32", x_ptr, ops._p(packed), ops._p(self.bias), p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0, ops._stream())
+        packed = self.packed(g.tile_n)                     # (sets self.out_scale for the fp16 format)
+        g.fmt, g.out_scale = self.fmt, self.out_scale
+        g.out_fmt_plus1 = 0 if self.out_fmt == self.fmt else self.out_fmt + 1
+        ws = ops._workspace(self.SPLITK_WS_BYTES, dev, "conv_splitk") if splitk and gate is None else None     # grow-only, shared: split-K partial sums
+        if gate is not None:
             if x2 is not None:
-                p2, H2, W2, s2 = x2
-                if p2.dtype != dt or p2.dim() != 4 or p2.shape[0] < NP or p2.shape[3] != 32 or not p2.is_contiguous() or shape[0] != "img":
-                    raise StmError("PlanarConv: the second source must be contiguous planes of this layer's format over one image size")
-                call("stm_conv2d_planar_dual_f32", x_ptr, ops._p(p2), p2.shape[1] * 32, H2, W2, s2, p2.shape[2], p2.shape[1] * p2.shape[2] * 32,
-                     ops._p(packed), ops._p(self.bias), r32, rpl, p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0, ops._p(ws), ws.numel(), ops._stream())
-            else:
-                call("stm_conv2d_planar_ws_f32", x_ptr, ops._p(packed), ops._p(self.bias), r32, rpl, p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0,
-                     ops._p(ws), ws.numel() if ws is not None else 0, ops._stream())
-        if started is not None:
-            # layer key: tile 0 = the kx-reuse kernel
-            _timing_stop(started, 2.0 * M * self.O * self.C * self.kh * self.kw * self.algo_frac, (M, self.C, self.O, self.kh, self.sh, self.groups, g.tile_n),
-                         {0: 6 if self.planes == 3 else 3, 1: 3, 2: 1}[self.fmt], self.role, self._algo_bytes(M, shape, NP, NPo, dt, out_f32, out_planes, residual))
-        if out == "both":
-            return out_f32, out_planes
-        return out_f32 if out == "f32" else out_planes
+                raise StmError("PlanarConv: gated launches take no second source")
+            ops.conv_set_pixel_gate(*gate)
+        if x2 is None:
+            return call("stm_conv2d_planar_ws_f32", x_ptr, ops._p(packed), ops._p(self.bias), r32, rpl, p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0,
+                        ops._p(ws), ws.numel() if ws is not None else 0, ops._stream())
+        p2, H2, W2, s2 = x2
+        if p2.dtype != self._dt or p2.dim() != 4 or p2.shape[0] < self._np or p2.shape[3] != 32 or not p2.is_contiguous() or not is_img:
+            raise StmError("PlanarConv: the second source must be contiguous planes of this layer's format over one image size")
+        call("stm_conv2d_planar_dual_f32", x_ptr, ops._p(p2), p2.shape[1] * 32, H2, W2, s2, p2.shape[2], p2.shape[1] * p2.shape[2] * 32,
+             ops._p(packed), ops._p(self.bias), r32, rpl, p_f32, p_pl, ctypes.byref(g), 1 if self.relu else 0, ops._p(ws), ws.numel(), ops._stream())
 
     def window_segments(self, xp, B, H, W, windows, out_planes, out_hw, gate, x_ch_off=0, out_slab_off=0):
         """This layer as a GATED window set (stm_conv2d_planar_windows_f32 after ops.conv_set_pixel_gate; fp16x2 planes, 256 x 128 tiles): the B
@@ -314,24 +322,16 @@ class PlanarConv:
         products of the single gated window launch in the same order.  Writes the layer's channels from slab out_slab_off of out_planes."""
         if self.fmt != 1 or self.out_fmt != 1 or (self.sh, self.sw) != (1, 1):
             raise StmError("PlanarConv.window_segments: fp16x2 planes and stride 1 only")
-        S, N = xp.shape[1], xp.shape[2]
-        n = len(windows)
+        S, N, n = xp.shape[1], xp.shape[2], len(windows)
         if xp.dim() != 4 or not xp.is_contiguous() or B % n or B * H * W > N or x_ch_off % 32 or S * 32 < x_ch_off + self.groups * self.C:
             raise StmError(f"PlanarConv.window_segments: {B} images of {H}x{W} in {n} segments do not fit planes {tuple(xp.shape)}")
         if (out_planes.shape[2] < B * out_hw * out_hw or out_slab_off < 0 or out_slab_off + self.O // 32 > out_planes.shape[1] or self.O % 128
                 or (H - self.kh + 1, W - self.kw + 1) != (out_hw, out_hw)):
             raise StmError("PlanarConv.window_segments: the output planes do not hold the layer's valid convolution")
         packed = self.packed(128)
-        g = _lib.ConvGeom()
-        g.B, g.H, g.W, g.C, g.Cout, g.sh, g.sw, g.planes, g.fmt, g.tile_n = B, H, W, self.C, self.O, 1, 1, 2, 1, 128
-        g.groups, g.win_h, g.win_w, g.out_scale = self.groups, out_hw, out_hw, self.out_scale
-        g.x_np, g.x_plane_stride = N, S * N * 32
-        g.out_np, g.out_plane_stride = out_planes.shape[2], out_planes.shape[1] * out_planes.shape[2] * 32
-        wins = (_lib.ConvWindow * n)()
-        for i, (ho, wo, y0, x0) in enumerate(windows):
-            wins[i].kh, wins[i].kw, wins[i].ph, wins[i].pw, wins[i].Ho, wins[i].Wo, wins[i].y0, wins[i].x0 = self.kh, self.kw, -y0, -x0, ho, wo, y0, x0
-        g.kh, g.kw, g.Ho, g.Wo = self.kh, self.kw, windows[0][0], windows[0][1]
-        ptrs = (ctypes.c_void_p * n)(*[packed.data_ptr()] * n)
+        g, ptrs, wins = ops._window_set(xp, [packed] * n, [(self.kh, self.kw, -y0, -x0, ho, wo, y0, x0) for ho, wo, y0, x0 in windows], B, H, W,
+                                        self.C, self.O, out_hw, out_hw, self.out_scale, out_planes=out_planes)
+        g.groups = self.groups
         started = _timing_start()
         ops.conv_set_pixel_gate(*gate)
         call("stm_conv2d_planar_windows_f32", xp.data_ptr() + (x_ch_off // 32) * N * 64, ptrs, wins, n, ops._p(self.bias), None,
@@ -350,9 +350,10 @@ class PlanarConv:
         return ops.deform_conv_fused_planar(x32, B, H, W, self.C, om, packed, self.out_scale, self.bias, self.O, (self.kh, self.kw), stride, padding,
                                             dilation, has_mask=has_mask, relu=self.relu, fmt=self.fmt, out_fmt=self.out_fmt, out=out, out_off=out_off)
 
-    def _algo_bytes(self, M, shape, NP, NPo, dt, out_f32, out_planes, residual):
+    def _algo_bytes(self, M, shape, out_f32, out_planes, residual):
         """Algorithmic HBM bytes of a launch: every input / residual / output element and every weight once, in the formats they are stored in
         (planes 2 B per plane and element, fp32 4 B)."""
+        NP, dt, NPo = self._np, self._dt, self._npo
         in_px = M if shape[0] == "levels" else shape[1] * shape[2] * shape[3]
         nbytes = in_px * self.groups * self.C * 2 * NP + self.weight.numel() * 2 * NP
         if out_planes is not None:
@@ -394,6 +395,15 @@ def head_center_default():
     """STM_HEAD_CENTER (default on): the sparse head's output layers at the centre pixel of each patch map only; 0 = over the whole 5 x 5 maps.
     The one place that reads the switch, once per process."""
     return os.environ.get("STM_HEAD_CENTER", "1") != "0"
+
+
+class SparseHead(NamedTuple):
+    """PlanarGraph.sparse: the sparse head's setting (any tuple assigned there becomes one, positional)."""
+    thresh: float                     # eval_conf_thresh: generate_candidate's class threshold
+    capacity: Optional[int] = None    # positions the patch launches are sized for; None: PlanarGraph.sparse_capacity
+    center: Optional[bool] = None     # output layers at the centre pixel of each patch map only; None: head_center_default()
+    split: bool = False               # mask and track branches at the positions with a kept prior of their own only
+    shapes: bool = False              # (pixel, kernel shape) entries; needs split, center and fp16x2 planes, else the position form runs
 
 
 class HeadOutputs(NamedTuple):
@@ -450,8 +460,8 @@ class PlanarGraph:
         self.head_planar = not (cfg.use_dcn_track or cfg.use_dcn_mask) and cfg.share_prediction_module
         self.fcb = bool(cfg.use_dcn_class)
         # Sparse head (csrc/head_sparse.hip): set by the caller for the calls it wants it on -- BatchedClipPipeline, whose detection stage reads loc /
-        # centerness / mask_coeff / track at the priors that pass generate_candidate's class threshold only -- as (eval_conf_thresh, capacity in
-        # positions or None).  None: every branch densely (forward_single, the layer API, the per-clip pipeline).  FCA heads with one prior per
+        # centerness / mask_coeff / track at the priors that pass generate_candidate's class threshold only -- as a SparseHead (a tuple assigned
+        # here is read as one).  None: every branch densely (forward_single, the layer API, the per-clip pipeline).  FCA heads with one prior per
         # kernel shape only: under FCB the class branch reads the dense box regression.
         self.sparse = None
         self._sparse_layers = self._split_layers = None
@@ -575,30 +585,23 @@ class PlanarGraph:
 
     def _sparse_head(self, up, g, toc):
         """conf for every prior; loc / mask_coeff / track / centerness at the rows of the positions with a prior that passes the class threshold
-        (the other rows are not written).  No host read: launches are sized by the capacity and gated by device counts."""
-        head, (B, sizes, _, ntot, dev) = self.head, g
-        thresh, cap = self.sparse[:2]
+        (the other rows are not written).  No host read: launches are sized by the capacity and gated by device counts.  Stages: class branch,
+        candidates and their patches (position or shapes form), dense fallback, assembly."""
+        head, (B, sizes, _, ntot, dev), s = self.head, g, self.sparse
         # output layers at the centre pixel of the 5 x 5 maps only (STM_HEAD_CENTER=0: over all 25 pixels, as before); part of the setting
-        center = self.sparse[2] if len(self.sparse) > 2 else head_center_default()
-        # Split (a fourth element; a setting without it keeps the unsplit form): half the listed positions are there only as the centerness
-        # partner of a kept prior -- centerness comes out of the bbox branch, so the mask and track branches run at the positions with a kept
-        # prior of their own only.  Those are in front of the list, and the second control block (ops.HEAD_CTL_OWN) counts them: the same
-        # launches, gated by that block.
-        split = len(self.sparse) > 3 and bool(self.sparse[3])
-        own = ops.HEAD_CTL_OWN if split else 0
-        if cap is None:
-            cap = self.sparse_capacity(B, sizes)
-        # Shapes (a fifth element): a kept prior (pixel, shape k) is read at output layer k only, and so is its centerness partner -- the list
-        # holds (pixel, shape) entries, one segment per shape, and the towers run over the rectangle that shape's output layer reads at the
-        # centre: kh x kw of tower 2, (kh + 2) x (kw + 2) of tower 1.
-        if len(self.sparse) > 4 and bool(self.sparse[4]) and split and center and self.fmt == 1:
-            return self._sparse_head_shapes(up, g, toc, thresh, self.sparse_segment_capacity(cap))
+        center = head_center_default() if s.center is None else s.center
+        # Split: half the listed positions are there only as the centerness partner of a kept prior -- centerness comes out of the bbox branch,
+        # so the mask and track branches run at the positions with a kept prior of their own only.  Those are in front of the list, and the
+        # second control block (ops.HEAD_CTL_OWN) counts them: the same launches, gated by that block.
+        split = bool(s.split)
+        cap = self.sparse_capacity(B, sizes) if s.capacity is None else s.capacity
+        # Shapes: a kept prior (pixel, shape k) is read at output layer k only, and so is its centerness partner -- the list holds (pixel, shape)
+        # entries, one segment per shape, and the towers run over the rectangle that shape's output layer reads at the centre: kh x kw of
+        # tower 2, (kh + 2) x (kw + 2) of tower 1.  A form of the split form with centre-pixel output layers on fp16x2 planes.
+        shapes = bool(s.shapes) and split and bool(center) and self.fmt == 1
         t1c, t1r, t2c, t2r, cls_l, small_l = self._build_sparse()
         trk_l = [f.trk for f in self.finals]
-        lv = g.lv
-        cw, P = self.tower2.O // 4, self.GROUP_PAD
-        S0, S1, S2 = self.SPARSE_SIDES
-        NP, pdt = ops.plane_layout(self.fmt)
+        lv, cw = g.lv, self.tower2.O // 4
         # the output layers run on the kernel the dense head would pick for them (the kx-reuse kernel forms its sums with other operand roles)
         kx = ntot >= self.finals[0].small.kxr_rule_pixels()
         # 1. the class branch, dense
@@ -606,9 +609,35 @@ class PlanarGraph:
         x = t2c(x, lv, out="planes", splitk=False)
         cls = [c(x, lv, out="f32", splitk=False, kxr=kx) for c in cls_l]
         toc("head_towers")
-        # 2. positions whose rows the detection stage will read
+        # 2. + 3. positions whose rows the detection stage will read, and the other branches over their patches
+        cap = self.sparse_segment_capacity(cap) if shapes else cap
+        lst, ctl, small, trk, rows = (self._sparse_patches_shapes if shapes else self._sparse_patches)(up, g, cls, s.thresh, cap, center, split, kx)
+        # 4. more positions than the capacity: the same layers over every pixel (empty launches otherwise)
+        gd = (ctl, ops.HEAD_CTL_DENSE)
+        x = t1r(up, lv, out="planes", gate=gd)
+        x = t2r(x, lv, out="planes", gate=gd)
+        small_d = [c(x, lv, out="f32", gate=gd, kxr=kx) for c in small_l]
+        trk_d = [c(x, lv, out="f32", x_ch_off=2 * cw, gate=gd) for c in trk_l]
+        toc("head_finals")
+        out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, self.GROUP_PAD,
+                                       rows[0], rows[1], lst, ctl, cap, split=split, shapes=shapes)
+        if shapes:
+            # (tests, diagnosis: the two blocks of sums read as the split form's -- counts of entries -- and sparse_list the entries' pixels)
+            self.sparse_ctl, self.sparse_list, self.sparse_segments = ctl[:ops.HEAD_CTL_SEG], None, (ctl, lst, cap)
+        else:
+            self.sparse_ctl, self.sparse_list = ctl, lst       # (tests, diagnosis: the step's counts and positions)
+        return out
+
+    def _sparse_patches(self, up, g, cls, thresh, cap, center, split, kx):
+        """Position form of stages 2 and 3 -> (list, control block, small / track rows per kernel shape, (rows per position, row read))."""
+        head, (B, sizes, _, _, dev) = self.head, g
+        _, t1r, _, t2r, _, small_l = self._sparse_layers
+        trk_l = [f.trk for f in self.finals]
+        cw, own = self.tower2.O // 4, ops.HEAD_CTL_OWN if split else 0
+        S0, S1, S2 = self.SPARSE_SIDES
+        NP, pdt = ops.plane_layout(self.fmt)
         lst, ctl = ops.head_candidates(cls, head.num_classes, thresh, cap, S1 * S1, S2 * S2, B, sizes, split=split)
-        # 3. their 9 x 9 patches through the two tower layers of the other branches as valid convolutions (window launches with no padding:
+        # their 9 x 9 patches through the two tower layers of the other branches as valid convolutions (window launches with no padding:
         # 9 x 9 -> 7 x 7 -> 5 x 5); after each layer the pixels outside the level's map become zero -- the padding the dense launch reads there
         patch = ops.head_patch_gather(up, torch.empty(NP, cw // 32, cap * S0 * S0, 32, device=dev, dtype=pdt), S0, cap, B, sizes, lst, ctl)
         x1 = torch.empty(NP, 3 * cw // 32, cap * S1 * S1, 32, device=dev, dtype=pdt)
@@ -630,60 +659,39 @@ class PlanarGraph:
             ops.head_patch_mask(x1, S1, cap, B, sizes, lst, ctl)
             t2r(x1, ("img", cap, S1, S1), out="planes", out_planes=xq, window=w2, gate=gb)
         ops.head_patch_mask(xq, S2, cap, B, sizes, lst, ctl)
-        if center:
-            # ... and the output layers at the centre pixel of the 5 x 5 maps, the only one that is read: one-pixel window launches, one output row
-            # per position, gated by the position count.  Each layer stays on the kernel family the dense head runs it on at this batch (kx): the
-            # kx-reuse kernel's centre-window launch stages the centre pixel's taps only (kw rows per position instead of 25), the planar
-            # kernel's window launch is the padded launch's sum at that pixel.  The track layers' 128 x 64 tiles (pick_tile at `cap` pixels) keep
-            # the chain of K-slabs on a workgroup short: gated launches never split K.
-            c2 = S2 // 2
-            qi = ("img", cap, S2, S2)
-
-            def centre(c, blk, **kw):
-                return c(xq, qi, out="f32", out_f32=torch.empty(cap, c.O, device=dev), window=(0, 0, 1, 1, c.ph - c2, c.pw - c2, 1, 1),
-                         gate=(ctl, blk + ops.HEAD_CTL_GATE_POS), **kw)
-
-            # (split: the grouped cen+bbox | mask launch covers all positions, its mask group is read at the own ones only; the track launches
-            # cover the own positions)
-            small = [centre(c, 0, kxr=kx) for c in small_l]
-            trk = [centre(c, own, x_ch_off=2 * cw, kxr=False) for c in trk_l]
-            rows = (1, 0)
-        else:
+        if not center:
             # ... and the output layers over the 5 x 5 maps (all that their windows at the centre pixel read), "same" padding
             ql = ("levels", cap, [(S2, S2)])
             small = [c(xq, ql, out="f32", gate=gb, kxr=kx) for c in small_l]
             trk = [c(xq, ql, out="f32", x_ch_off=2 * cw, gate=(ctl, own + ops.HEAD_CTL_GATE_B)) for c in trk_l]
-            rows = (S2 * S2, (S2 * S2) // 2)
-        # 4. more positions than the capacity: the same layers over every pixel (empty launches otherwise)
-        gd = (ctl, ops.HEAD_CTL_DENSE)
-        x = t1r(up, lv, out="planes", gate=gd)
-        x = t2r(x, lv, out="planes", gate=gd)
-        small_d = [c(x, lv, out="f32", gate=gd, kxr=kx) for c in small_l]
-        trk_d = [c(x, lv, out="f32", x_ch_off=2 * cw, gate=gd) for c in trk_l]
-        toc("head_finals")
-        out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P,
-                                       rows[0], rows[1], lst, ctl, cap, split=split)
-        self.sparse_ctl, self.sparse_list = ctl, lst       # (tests, diagnosis: the step's counts and positions)
-        return out
+            return lst, ctl, small, trk, (S2 * S2, (S2 * S2) // 2)
+        # ... and the output layers at the centre pixel of the 5 x 5 maps, the only one that is read: one-pixel window launches, one output row
+        # per position, gated by the position count.  Each layer stays on the kernel family the dense head runs it on at this batch (kx): the
+        # kx-reuse kernel's centre-window launch stages the centre pixel's taps only (kw rows per position instead of 25), the planar
+        # kernel's window launch is the padded launch's sum at that pixel.  The track layers' 128 x 64 tiles (pick_tile at `cap` pixels) keep
+        # the chain of K-slabs on a workgroup short: gated launches never split K.
+        # (split: the grouped cen+bbox | mask launch covers all positions, its mask group is read at the own ones only; the track launches
+        # cover the own positions)
+        small = [self._centre_rows(c, xq, cap, 0, (ctl, ops.HEAD_CTL_GATE_POS), kxr=kx) for c in small_l]
+        trk = [self._centre_rows(c, xq, cap, 0, (ctl, own + ops.HEAD_CTL_GATE_POS), x_ch_off=2 * cw, kxr=False) for c in trk_l]
+        return lst, ctl, small, trk, (1, 0)
 
-    def _sparse_head_shapes(self, up, g, toc, thresh, cap):
-        """_sparse_head in the shapes form (split, centre-pixel output layers): `cap` entries per kernel shape.  Patch slot k * cap + i belongs to
+    def _centre_rows(self, c, xq, cap, x_off, gate, **kw):
+        """Output layer c at the centre pixel of the `cap` 5 x 5 maps from pixel x_off of xq: a one-pixel window launch -> fp32 [cap, O]."""
+        S2 = self.SPARSE_SIDES[2]
+        return c(xq, ("img", cap, S2, S2), x_off=x_off, out="f32", out_f32=torch.empty(cap, c.O, device=xq.device),
+                 window=(0, 0, 1, 1, c.ph - S2 // 2, c.pw - S2 // 2, 1, 1), gate=gate, **kw)
+
+    def _sparse_patches_shapes(self, up, g, cls, thresh, cap, center, split, kx):
+        """Shapes form of stages 2 and 3 (always split, with centre-pixel output layers): `cap` entries per kernel shape.  Patch slot k * cap + i belongs to
         entry i of shape k; the four tower launches are gated window sets with one window per shape (PlanarConv.window_segments), shape k's
         output launches read segment k and are gated by its blocks."""
-        head, (B, sizes, _, ntot, dev) = self.head, g
-        _, _, _, _, cls_l, small_l = self._build_sparse()
-        t1c, t1r, t2c, t2r = self._sparse_layers[:4]
+        head, (B, sizes, _, _, dev) = self.head, g
+        small_l, trk_l = self._sparse_layers[5], [f.trk for f in self.finals]
         t1b, t1m, t2b, t2m = self._split_layers
-        trk_l = [f.trk for f in self.finals]
-        K, lv = len(self.finals), g.lv
-        cw, P = self.tower2.O // 4, self.GROUP_PAD
+        K, cw = len(self.finals), self.tower2.O // 4
         S0, S1, S2 = self.SPARSE_SIDES
         NP, pdt = ops.plane_layout(self.fmt)
-        kx = ntot >= self.finals[0].small.kxr_rule_pixels()
-        x = t1c(up, lv, out="planes", splitk=False)
-        x = t2c(x, lv, out="planes", splitk=False)
-        cls = [c(x, lv, out="f32", splitk=False, kxr=kx) for c in cls_l]
-        toc("head_towers")
         shp = [(c.kh, c.kw) for c in small_l]
         if any(c.kh > S2 or c.kw > S2 or not (c.kh & c.kw & 1) or (t.kh, t.kw) != (c.kh, c.kw) for c, t in zip(small_l, trk_l)):
             raise StmError("sparse head: an output layer's kernel does not fit the patch maps")
@@ -704,25 +712,18 @@ class PlanarGraph:
         t2b.window_segments(x1, tot, S1, S1, w2, xq, S2, (ctl, seg + ops.HEAD_CTL_GATE_B))
         t2m.window_segments(x1, tot, S1, S1, w2, xq, S2, (ctl, seg + own + ops.HEAD_CTL_GATE_B), x_ch_off=cw, out_slab_off=cw // 32)
         ops.head_patch_mask(xq, S2, cap, B, sizes, lst, ctl, segs=K)
-        c2 = S2 // 2
+        small = [self._centre_rows(c, xq, cap, k * cap * S2 * S2, (ctl, seg * (k + 1) + ops.HEAD_CTL_GATE_POS), kxr=kx) for k, c in enumerate(small_l)]
+        trk = [self._centre_rows(c, xq, cap, k * cap * S2 * S2, (ctl, seg * (k + 1) + own + ops.HEAD_CTL_GATE_POS), x_ch_off=2 * cw, kxr=False)
+               for k, c in enumerate(trk_l)]
+        return lst, ctl, small, trk, (1, 0)
 
-        def centre(c, k, blk, **kw):
-            return c(xq, ("img", cap, S2, S2), x_off=k * cap * S2 * S2, out="f32", out_f32=torch.empty(cap, c.O, device=dev),
-                     window=(0, 0, 1, 1, c.ph - c2, c.pw - c2, 1, 1), gate=(ctl, seg * (k + 1) + blk + ops.HEAD_CTL_GATE_POS), **kw)
+    @property
+    def sparse(self):
+        return self._sparse
 
-        small = [centre(c, k, 0, kxr=kx) for k, c in enumerate(small_l)]
-        trk = [centre(c, k, own, x_ch_off=2 * cw, kxr=False) for k, c in enumerate(trk_l)]
-        gd = (ctl, ops.HEAD_CTL_DENSE)
-        x = t1r(up, lv, out="planes", gate=gd)
-        x = t2r(x, lv, out="planes", gate=gd)
-        small_d = [c(x, lv, out="f32", gate=gd, kxr=kx) for c in small_l]
-        trk_d = [c(x, lv, out="f32", x_ch_off=2 * cw, gate=gd) for c in trk_l]
-        toc("head_finals")
-        out = ops.head_assemble_sparse(cls, small, trk, small_d, trk_d, B, sizes, head.num_classes, head.mask_dim, head.embed_dim, P,
-                                       1, 0, lst, ctl, cap, split=True, shapes=True)
-        # (tests, diagnosis: the two blocks of sums read as the split form's -- counts of entries -- and sparse_list the entries' pixels)
-        self.sparse_ctl, self.sparse_list, self.sparse_segments = ctl[:ops.HEAD_CTL_SEG], None, (ctl, lst, cap)
-        return out
+    @sparse.setter
+    def sparse(self, setting):
+        self._sparse = None if setting is None else SparseHead(*setting)
 
     @property
     def sparse_list(self):
@@ -754,9 +755,7 @@ class PlanarGraph:
         for d in self.fpn_down:
             h, w = sizes[-1]
             sizes.append(ops.conv_out_hw(h, w, d.kh, d.kw, d.sh, d.sw, d.ph, d.pw, 1, 1))
-        starts = [0]
-        for h, w in sizes:
-            starts.append(starts[-1] + B * h * w)
+        starts = ops.level_starts(B, sizes)
         g = _Levels(B, tuple(sizes), tuple(starts), starts[-1], (latp[0] if latp[0] is not None else lat[0]).device)
         # Second-stream branches (TRUNK_BRANCHES), only while a HIP graph is captured: the graph then holds parallel paths, and on small batches --
         # where a launch fills a fraction of the 256 CUs -- the GPU runs them side by side.  Same kernels on the same data: bit-equal to the plain order.
@@ -1227,8 +1226,8 @@ class PlanarChain:
 
     def __call__(self, mid1, x, B, H, W):
         if self._packed is None:
-            g = _lib.ConvGeom()
-            g.C, g.Cout, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, g.groups, g.fmt = 64, 64, 3, 3, 1, 1, 1, 1, 1, 1
+            g = ops.layer_geom(64, 64, 3, 3, 1, 1, 1, 1, 0, 1)
+            g.fmt = 1
             ops.planar_range_flag()
             w2p, s2 = ops.conv_pack_weights_kxr(self.w2, g)
             tail, s3, s1 = ops.chain_pack_tail(self.w3, self.w1, self.wds)

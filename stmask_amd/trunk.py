@@ -139,9 +139,9 @@ class TrunkRunner:
             return None
         if not getattr(self.net.Detect_TF, "use_cross_class_nms", True):
             return None
-        return (float(self.cfg.eval_conf_thresh), self.sparse_capacity, self.head_center, self.head_split,
-                # (a capacity given by the caller counts POSITIONS and keeps the list of positions; the segments of entries are sized by the default rule)
-                self.head_shapes and self.sparse_capacity is None)
+        return planar.SparseHead(thresh=float(self.cfg.eval_conf_thresh), capacity=self.sparse_capacity, center=self.head_center, split=self.head_split,
+                                 # (a capacity given by the caller counts POSITIONS and keeps the list of positions; the segments of entries are sized by the default rule)
+                                 shapes=self.head_shapes and self.sparse_capacity is None)
 
     def _trunk(self, frames):
         pg = getattr(self.net, "_planar", None)

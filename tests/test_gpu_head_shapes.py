@@ -1,4 +1,4 @@
-"""The sparse head's shapes form (planar.PlanarGraph._sparse_head_shapes, a fifth setting element; csrc/head_sparse.hip with K << 28 added to the
+"""The sparse head's shapes form (planar.PlanarGraph._sparse_patches_shapes, SparseHead.shapes; csrc/head_sparse.hip with K << 28 added to the
 capacity; the gated window set of csrc/conv_bf16x.hip): the list holds (pixel, kernel shape) entries, one segment per shape, and the patch towers
 run over the rectangle that shape's output layers read at the centre -- kh x kw of tower 2, (kh + 2) x (kw + 2) of tower 1.
 
