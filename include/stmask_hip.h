@@ -341,7 +341,9 @@ int stm_mask_resize_rle_f32(const float* masks, int n, int mh, int mw, int crop_
  * Bottleneck.forward (backbone.py:38-58), FPN.forward (FPN.py:68-108), the proto-net (make_net.py:5-59) and the
  * PredictionModule_FC tower (prediction_head_FC.py:146-195).  Activations are NHWC fp32 (a torch channels_last tensor
  * is exactly this); every fp32 operand is split into `planes` bf16 terms (3: six products, error ~2^-24, the default;
- * 2: three products, error ~2^-16) and accumulated in fp32.  Input channels must be a multiple of 32. */
+ * 2: three products p0 q0 + p0 q1 + p1 q0 of planes 0 and 1, error ~2^-16: at most 3 * 2^-18 (1 + 2^-9) of sum |x w| from the
+ * split -- two 8-bit roundings per operand and the dropped p1 q1 -- beside the fp32 accumulation; tests/test_gpu_conv_rows.py
+ * derives and holds it) and accumulated in fp32.  Input channels must be a multiple of 32. */
 typedef struct stm_conv_geom {
     int B, H, W, C;       /* input  [B, H, W, C] (NHWC) */
     int Ho, Wo, Cout;     /* output [B, Ho, Wo, Cout] */

@@ -1920,12 +1920,13 @@ def conv2d_planar(xp, packed, weight_shape, hw, bias=None, residual=None, stride
     """The same convolution on the planar activation format: xp [P, C/32, B*H*W, 32] (split_planes / a previous layer's
     output), hw = (B, H, W).  `residual` may be fp32 [B*Ho*Wo, O] or planes [P, O/32, B*Ho*Wo, 32].
     out: "planes" | "f32" | "both"; fp32 result [B*Ho*Wo, O].  fmt 1: fp16 planes, `packed` / `out_scale` from
-    conv_pack_weights(..., fmt=1)."""
+    conv_pack_weights(..., fmt=1).  fmt 0 with planes = 2 (weights packed with planes = 2): the three-product mode, which reads planes 0
+    and 1 of xp -- all three planes or only those two may be given; outputs and a planar residual always have three."""
     _dev(xp, packed, bias, residual)
     P, dt = plane_layout(fmt)
     if fmt >= 1:
         planes = P
-    if xp.dtype != dt or xp.dim() != 4 or xp.shape[0] != P or xp.shape[3] != 32 or not xp.is_contiguous():
+    if xp.dtype != dt or xp.dim() != 4 or xp.shape[0] not in (P, planes) or xp.shape[3] != 32 or not xp.is_contiguous():
         raise StmError(f"conv2d_planar: expected contiguous {dt} planes [{P},C/32,N,32], got {xp.dtype} {tuple(xp.shape)}")
     O, C, kh, kw = weight_shape
     B, H, W = hw

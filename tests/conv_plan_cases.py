@@ -17,6 +17,14 @@ BIG = 1 << 40                                                                   
 TUNABLES = ("STM_CONV_RING", "STM_CONV_RING64", "STM_CONV_SPLITK", "STM_CONV_MG", "STM_CONV_KX3")
 PLANES = {0: 3, 1: 2, 2: 1}
 
+# conv_planar_kernel<NPL, MG, NJ, DT, ST, ABL, DUAL, CLS> of the default build: the 26 rows of PLANAR_ROWS (csrc/conv_bf16x.hip) and the window-set pair
+ROWS = ([(3, 1, 1, 0, 2, 0), (2, 1, 1, 0, 2, 0)] + [(npl, 1, 1, 1, st, dual) for npl in (2, 1) for st in (2, 3) for dual in (0, 1)] +
+        [(npl, mg, 2, 0, 2, 0) for npl in (3, 2) for mg in (1, 2)] + [(npl, mg, 2, 1, st, 0) for npl in (2, 1) for mg in (1, 2) for st in (2, 3)] +
+        [(npl, mg, 2, 1, 3, 1) for npl in (2, 1) for mg in (1, 2)])
+KERNELS = (["conv_planar_kernel<%d,%d,%d,%d,%d,0,%d,0>" % r for r in ROWS] +
+           ["conv_planar_kernel<2,2,2,1,3,0,0,1>", "conv_planar_kernel<2,2,2,1,3,0,0,2>", "conv_planar_kx3_kernel<0,0>", "conv_planar_kx3_kernel<0,1>",
+            "planar_splitk_finish_kernel"])
+
 CASES = {}
 
 

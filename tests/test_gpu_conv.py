@@ -15,26 +15,11 @@ from stmask_amd import ops
 from ctypes import c_int
 
 from stmask_amd._lib import StmError
+from conv_oracle import DEV, level_group_oracle, rnd, worst_ratio
+from conv_oracle import planar_conv_vs_oracle as _planar_conv_vs_oracle
+from conv_rows_cases import CONV_CASES, DUAL_CASES, KX3_CASES, KX3_ENV, LOOP_CASES, LOOP_VARIANTS, WINDOW_TEST   # (the shapes: data of the coverage claim too)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-CONV_CASES = [
-    # B, H,  W,  C, Cout, kh, kw, stride, pad(h,w), bias, residual, relu
-    (2, 12, 20, 32, 64, 3, 3, 1, (1, 1), True, False, True),      # head-tower-like 3x3
-    (1, 24, 40, 64, 256, 1, 1, 1, (0, 0), True, True, True),      # bottleneck conv3 + residual
-    (2, 13, 17, 32, 27, 3, 3, 2, (1, 1), True, False, False),     # conv_offset_mask-like: stride 2, Cout 27, odd sizes
-    (1, 6, 10, 64, 41, 3, 5, 1, (1, 2), True, False, False),      # FCB trailing conv 3x5 -> 41 classes
-    (1, 3, 5, 32, 130, 5, 3, 1, (2, 1), False, False, True),      # P7: 15 pixels, 5x3, Cout just over one tile
-    (3, 9, 11, 96, 4, 3, 3, 1, (1, 1), True, False, False),       # bbox layer: Cout 4
-    (1, 48, 80, 256, 256, 3, 3, 1, (1, 1), True, False, True),    # the P3 tower layer at full size
-]
 
 
 def conv_nhwc(x, w, b=None, r=None, stride=1, padding=0, relu=False, fmt=0, tile_n=128):
@@ -343,15 +328,14 @@ def test_conv_planar_fp16_loop_variants_agree_bitwise(tile_n, fmt, tunables):
     the same order: same bits.  Split-K (partial sums + finishing kernel) differs by the summation order only."""
     from stmask_amd.planar import PlanarConv
     tol = 2e-6 if fmt == 1 else 1e-3
-    for (B, H, W, C, O, k) in [(2, 24, 40, 64, 128, 3), (8, 48, 80, 128, 256, 3), (1, 12, 20, 512, 64, 1), (2, 6, 10, 1024, 128, 3)]:
+    for (B, H, W, C, O, k) in LOOP_CASES:
         x = rnd(B, H, W, C, seed=C + k)
         w = rnd(O, C, k, k, seed=O, scale=(C * k * k) ** -0.5)
         b = rnd(O, seed=7)
         conv = PlanarConv(w.to(DEV), b.to(DEV), 1, k // 2, relu=True, tile_n=tile_n, fmt=fmt)
         xp = ops.split_planes(x.to(DEV), fmt=fmt)
         outs = {}
-        for name, env in [("ring", {}), ("two-buffer", {"STM_CONV_RING": "2", "STM_CONV_RING64": "2"}), ("ring64", {"STM_CONV_RING64": "4"}),
-                          ("splitk", {"STM_CONV_SPLITK": "3"})]:
+        for name, env in LOOP_VARIANTS:
             tunables.set(**env)
             y32, ypl = conv(xp, ("img", B, H, W), out="both")
             outs[name] = (y32.cpu(), ypl.cpu())
@@ -568,29 +552,6 @@ def test_f16_entry_points_are_plane_format_2():
 
 
 # ---------------------------------------------------------------------------------------------- narrow layers: the kx-reuse kernel
-def _planar_conv_vs_oracle(conv, xs, sizes, B, wts, bias, pad, relu, C, groups, cg, real, fmt, tol):
-    """Run `conv` over the concatenated levels and compare every (level, group) with the fp64 oracle."""
-    starts = [0]
-    for h, w in sizes:
-        starts.append(starts[-1] + B * h * w)
-    flat = torch.cat([x.reshape(-1, x.shape[-1]) for x in xs], 0)
-    xp = ops.split_planes(flat.to(DEV), fmt)
-    shape = ("levels", B, sizes) if len(sizes) > 1 else ("img", B, *sizes[0])
-    y32, ypl = conv(xp, shape, out="both")
-    y32, ypl = y32.cpu(), ypl.cpu()
-    worst = 0.0
-    for l, (h, w) in enumerate(sizes):
-        for g in range(groups):
-            xg = xs[l][..., g * C:(g + 1) * C].contiguous()
-            wg, bg = wts[g * cg:g * cg + real[g]], (bias[g * cg:g * cg + real[g]] if bias is not None else None)
-            ref = oracle.conv2d_nhwc(xg, wg, bg, None, padding=pad, relu=relu)
-            mag = oracle.conv2d_nhwc(xg.abs(), wg.abs(), bg.abs() if bg is not None else None, None, padding=pad)
-            out = y32[starts[l]:starts[l + 1], g * cg:g * cg + real[g]].view(B, h, w, real[g])
-            worst = max(worst, ((out - ref).abs() / mag.clamp_min(1e-6)).max().item())
-    assert worst < tol, worst
-    return y32, ypl, worst
-
-
 KXR_CASES = [
     # kh, kw, groups, channels per group (row stride), real channels per group, sizes, B, relu
     (3, 3, 3, 64, (41, 5, 32), [(12, 20), (6, 10), (3, 5), (2, 3), (1, 2)], 3, False),     # head output layers, five levels
@@ -716,8 +677,7 @@ def test_stem_fused_equals_three_kernel_stem():
 
 # ---------------------------------------------------------------------------------------------- conv3 + projection shortcut as one product
 @pytest.mark.parametrize("fmt", [1, 2])
-@pytest.mark.parametrize("case", [(2, 24, 40, 64, 64, 256, 1, 64), (2, 25, 39, 128, 256, 512, 2, 64), (1, 12, 20, 256, 512, 1024, 2, 128),
-                                  (3, 6, 10, 512, 1024, 2048, 2, 128)])
+@pytest.mark.parametrize("case", DUAL_CASES)
 def test_conv_dual_source_vs_oracle(case, fmt):
     """stm_conv2d_planar_dual_f32: relu(W3 mid + b3 + Wds x[::s, ::s] + bds) as one two-source 1x1 product (the first bottleneck of a ResNet
     stage, backbone.py:38-58) against the fp64 oracle of the two convolutions -- the stated bound of the planar kernel, 2e-6 of sum |x w|
@@ -876,14 +836,14 @@ def test_bottleneck_chain_projection_form(case):
 
 
 # ---------------------------------------------------------------------------------------------- window launches (TemporalNet's border classes)
-@pytest.mark.parametrize("hw", [(7, 7), (5, 9), (3, 3)])
+@pytest.mark.parametrize("hw", WINDOW_TEST["hw"])
 def test_conv_window_launches_equal_the_padded_convolution(hw):
     """stm_conv_geom.win_*: a 3x3 / pad-1 convolution computed as nine window launches -- row classes {0}, {1..H-2}, {H-1} x column
     classes, each with the sub-kernel of its real taps and negative padding -- writes the same tensor as the single launch: the skipped
     taps only ever added exact zeros, so the fp32 sums are the same sums (bit-equal where no launch is split along K; both against fp64)."""
     from stmask_amd.planar import PlanarConv
     H, W = hw
-    n, C, O = 37, 64, 128
+    n, C, O = WINDOW_TEST["n"], WINDOW_TEST["C"], WINDOW_TEST["O"]
     x = rnd(n, H, W, C, seed=70)
     w = rnd(O, C, 3, 3, seed=71, scale=(C * 9) ** -0.5)
     b = rnd(O, seed=72)
@@ -997,26 +957,18 @@ def test_temporalnet_pooled_epilogue_equals_pool_of_the_written_tensor(monkeypat
         ops.conv2d_planar_windows_pool(xp, [], [], None, n, 7, 7, 96, 256, 7, 7, 1.0, torch.zeros(n, 256, device=DEV))   # not int64
 
 
-KX3_CASES = [
-    # B, sizes (levels) or one (H, W), C per group, O, groups, kh, residual
-    ("img 48x80", 8, [(48, 80)], 128, 256, 1, 3, False),
-    ("img 37x53 odd, residual, partial last tile", 19, [(37, 53)], 64, 128, 1, 3, True),
-    ("levels, grouped towers", 6, [(24, 40), (12, 20), (6, 10), (3, 5), (2, 3)], 64, 512, 4, 3, False),
-    ("levels 5x3 kernel", 5, [(24, 40), (12, 20), (6, 10), (3, 5), (2, 3)], 64, 128, 1, 5, False),
-    ("1x3 kernel", 4, [(40, 64)], 96, 128, 1, 1, False),
-]
-
-
 @pytest.mark.parametrize("case", KX3_CASES, ids=[c[0] for c in KX3_CASES])
 def test_conv_planar_kx3_staging_is_bit_equal_to_the_ring_kernel(case, tunables):
     """conv_planar_kx3_kernel (STM_CONV_KX3=1: one staged run of BM + 2 pixels per (channel slab, ky) serves the three taps of a kernel row, the
     image-row borders read an always-zero staged row) multiplies the same fragments in the same order as the ring kernel that stages every tap:
     bit-equal fp32 and plane outputs -- single image size with odd widths and a partial last tile, the concatenated-levels pixel axis of the shared
-    head (tiles that span two levels), grouped layers, kh = 1 / 3 / 5, residual + ReLU; and against the fp64 oracle on the plain case."""
+    head (tiles that span two levels), grouped layers, kh = 1 / 3 / 5, residual + ReLU; and every case against the fp64 oracle per (level, group), at the
+    bound of the two-plane fp16 format (the residual the oracle adds is the value its planes hold)."""
     from stmask_amd import _lib
     from stmask_amd.planar import PlanarConv
     name, B, sizes, C, O, groups, kh, with_res = case
-    x = torch.cat([rnd(B, h, w, C * groups, seed=7 + i).reshape(-1, C * groups) for i, (h, w) in enumerate(sizes)], 0)      # [M, C] concatenated levels
+    xs = [rnd(B, h, w, C * groups, seed=7 + i) for i, (h, w) in enumerate(sizes)]
+    x = torch.cat([t.reshape(-1, C * groups) for t in xs], 0)                                                                # [M, C] concatenated levels
     M = x.shape[0]
     w = rnd(O, C, kh, 3, seed=3, scale=(C * kh * 3) ** -0.5)
     b = rnd(O, seed=4)
@@ -1026,7 +978,7 @@ def test_conv_planar_kx3_staging_is_bit_equal_to_the_ring_kernel(case, tunables)
     shape = ("levels", B, sizes) if len(sizes) > 1 else ("img", B, sizes[0][0], sizes[0][1])
     outs = []
     for kx3 in ("0", "1"):
-        tunables.set(STM_CONV_KX3=kx3, STM_CONV_MG="2", STM_CONV_SPLITK="1")     # (256-pixel tiles and no split along K whatever the pixel count)
+        tunables.set(STM_CONV_KX3=kx3, **KX3_ENV)                                 # (256-pixel tiles and no split along K whatever the pixel count)
         n0 = _lib.lib().stm_debug_launch_count(c_int(0))
         y32, ypl = conv(xp, shape, out="both", residual=res)
         torch.cuda.synchronize()
@@ -1034,11 +986,9 @@ def test_conv_planar_kx3_staging_is_bit_equal_to_the_ring_kernel(case, tunables)
         outs.append((y32.clone(), ypl.clone()))
         tunables.clear("STM_CONV_KX3", "STM_CONV_MG", "STM_CONV_SPLITK")
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
-    if name == "img 48x80":
-        xi = x.view(B, sizes[0][0], sizes[0][1], C)
-        ref = oracle.conv2d_nhwc(xi, w, b, None, padding=(1, 1), relu=True)
-        mag = oracle.conv2d_nhwc(xi.abs(), w.abs(), b.abs(), None, padding=(1, 1))
-        assert ((outs[1][0].cpu().view(ref.shape) - ref).abs() / mag.clamp_min(1e-6)).max().item() < 2e-6
+    refs = level_group_oracle(xs, sizes, B, w, b, (kh // 2, 1), True, C, groups, O // groups, (O // groups,) * groups,
+                              res=ops.planes_to_f32(res.cpu()) if with_res else None)
+    assert worst_ratio(outs[1][0].cpu(), refs) < 2e-6
 
 
 @pytest.mark.parametrize("kh,ph", [(3, 0), (5, 1), (3, 2)])
