@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from stmask_amd import layers, synthetic  # noqa: E402
 from stmask_amd.config import get_cfg  # noqa: E402
 from stmask_amd.model import STMask  # noqa: E402
-from stmask_amd.train import NetLoss, train_step  # noqa: E402
+from stmask_amd.train import NetLoss, train_step, use_deterministic  # noqa: E402
 
 
 def main():
@@ -26,7 +26,11 @@ def main():
     ap.add_argument("--hw", type=int, nargs=2, default=(128, 192))
     ap.add_argument("--composed", action="store_true", help="T2S_concat_feat from torch ops instead of csrc/t2s_feat.hip")
     ap.add_argument("--same-batch", action="store_true", help="every step on the batch of seed 0")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="torch.use_deterministic_algorithms(True) and MIOpen's deterministic solvers: a bit-reproducible backward")
     args = ap.parse_args()
+    if args.deterministic:
+        use_deterministic()
     dev = "cuda:0"
     cfg = get_cfg(args.config)
     net = STMask(cfg)

@@ -55,7 +55,7 @@ from stmask_amd.model import STMask  # noqa: E402
 from stmask_amd.optim import DataParallelSGD, GuardedSGD  # noqa: E402
 from stmask_amd.parallel import DataParallelTrainer  # noqa: E402
 from stmask_amd.preprocess import MEANS  # noqa: E402
-from stmask_amd.train import LossLog, NetLoss, autoscale, lr_at, train_step  # noqa: E402
+from stmask_amd.train import LossLog, NetLoss, autoscale, lr_at, train_step, use_deterministic  # noqa: E402
 
 READ_EVERY = 10
 
@@ -97,6 +97,8 @@ def parse_args(argv=None):
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="the gradient exchange of --gpus N > 1")
     ap.add_argument("--batch_alloc", default=None, help="comma list, one entry per rank: the clips of each global batch a rank takes (default: equal)")
     ap.add_argument("--share-gpu", action="store_true", help="every rank on device 0 (gloo only: the test form)")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="torch.use_deterministic_algorithms(True) and MIOpen's deterministic solvers, in every rank: a bit-reproducible backward")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error(f"--gpus {args.gpus}")
@@ -133,6 +135,8 @@ def main(argv=None):
         from benchlib.launch import start_ranks
         raise SystemExit(start_ranks(world, sys.argv[1:] if argv is None else argv, __file__).wait())
     dev = "cuda:0"
+    if args.deterministic:                      # past the parent's branch: this is the single process or one of the ranks
+        use_deterministic()
     if world > 1:
         import torch.distributed as dist
         rank = int(os.environ["RANK"])

@@ -242,6 +242,17 @@ DP_SIGNATURES = {
 }
 DP_MAX_TENSORS = 64   # csrc/dp_step.h STM_DP_MAX_TENSORS
 DP_CHUNK = 4096       # csrc/dp_step.h STM_DP_CHUNK
+# ... and those of csrc/det_backward.h: the deterministic mode of the training backward (autograd.set_deterministic).  A fifth private table, kept
+# beside the four above; det_tables() lists it, private_call() resolves it and build() walks it too.
+DET_SIGNATURES = {
+    "stm_det_exponent": ("i", "iillppp"),
+    "stm_det_workspace_bytes": ("z", "l"),
+    "stm_deform_col2im_det_f32": ("i", "pplplipppzp"),
+    "stm_roi_align_backward_det_f32": ("i", "pppiiiiiiifiipzp"),
+    "stm_upsample_bilinear_backward_f32": ("i", "ppliiiiddp"),
+}
+DET_MIN_BITS = 36                                     # csrc/det_accum.h STM_DET_MIN_BITS
+DET_FINITE, DET_ZERO, DET_NONFINITE = 0, 1, 2         # csrc/det_accum.h STM_DET_FINITE / _ZERO / _NONFINITE
 
 
 def private_tables():
@@ -252,6 +263,11 @@ def private_tables():
 def dp_tables():
     """{header under csrc/: its table} of the data-parallel step's package-private header."""
     return {"dp_step.h": DP_SIGNATURES}
+
+
+def det_tables():
+    """{header under csrc/: its table} of the deterministic backward's package-private header."""
+    return {"det_backward.h": DET_SIGNATURES}
 
 
 _private_calls = {}   # name -> (function, argument count) for private_call()
@@ -400,11 +416,12 @@ def call(name, *args):
 
 
 def private_call(name, *args):
-    """call() for an entry of PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES or DP_SIGNATURES: restype / argtypes are set from the table when
-    the entry is first used."""
+    """call() for an entry of PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES, DP_SIGNATURES or DET_SIGNATURES: restype / argtypes are set from
+    the table when the entry is first used."""
     got = _private_calls.get(name)
     if got is None:
-        ret, params = next(table[name] for table in (PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES, DP_SIGNATURES) if name in table)
+        ret, params = next(table[name] for table in (PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES, DP_SIGNATURES, DET_SIGNATURES)
+                           if name in table)
         fn = getattr(lib(), name, None)
         if fn is None:
             raise StmError(f"{LIB_PATH} lacks {name}: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")

@@ -12,12 +12,36 @@ csrc/temporal_backward.hip, csrc/mask_backward.hip, csrc/lincomb_backward.hip, c
 csrc/mbox_loss.hip on the current stream; a gradient nobody asked for (ctx.needs_input_grad) launches nothing.  The backward kernels have no derivative of their own, so
 every backward is @first_order_only: a double backward (create_graph=True, then differentiating the result) raises instead of
 silently dropping the second-order term.
+
+Deterministic mode.  Two of these backwards scatter with fp32 atomic adds -- grad_x of the deformable convolutions and
+grad_feat of RoIAlign -- and torch's own bilinear-upsampling backward does too (under torch.use_deterministic_algorithms(True) torch raises, or, from
+the release on that swaps in a decomposition, runs another forward whose values differ in the last bits).  With the
+mode on, ops.deform_col2im and ops.roi_align_backward take the order-independent 64-bit fixed-point form of csrc/det_backward.hip, and FPN /
+InterpolateModule differentiate their bilinear upsampling through UpsampleBilinearFunction, a gather.  The mode is read where the backward launch
+is chosen, not when the forward ran.  Off (the default without torch's flag), every call makes exactly the launches it made before.
 """
 import functools
 
 import torch
 
 from . import ops
+
+_deterministic = None   # set_deterministic(): True / False, or None = follow torch's flag
+
+
+def set_deterministic(mode):
+    """True / False: the deterministic backward on / off.  None (the default): follow torch.are_deterministic_algorithms_enabled(), which is also
+    true under torch.use_deterministic_algorithms(True, warn_only=True).  False while torch's flag is on: the atomic scatters are taken and raise
+    (warn, with warn_only) as torch's own nondeterministic operators do under the flag (ops._alert_not_deterministic)."""
+    global _deterministic
+    if mode is not None and not isinstance(mode, bool):
+        raise ValueError(f"set_deterministic: mode must be True, False or None, got {mode!r}")
+    _deterministic = mode
+
+
+def is_deterministic():
+    """Whether a backward launched now takes the deterministic kernels."""
+    return torch.are_deterministic_algorithms_enabled() if _deterministic is None else _deterministic
 
 
 def wants_grad(*tensors):
@@ -410,6 +434,44 @@ class MboxReduceFunction(torch.autograd.Function):
             return (None,) * 5
         scale_rows, n_dev, status = ctx.saved_tensors
         return (ops.mbox_reduce_backward(grad_loss.contiguous(), scale_rows, n_dev, status, ctx.alpha),) + (None,) * 4
+
+
+class UpsampleBilinearFunction(torch.autograd.Function):
+    """F.interpolate(x, size= or scale_factor=, mode="bilinear", align_corners=False) on [B,C,H,W]: the forward is the ATen kernel that call
+    launches, so values are torch's bit for bit; the backward is the gather of csrc/det_backward.hip (fixed order, no atomics) instead of torch's
+    atomic scatter.  Only shapes are saved.
+    The kernel is called by its own name because F.interpolate itself, on a GPU tensor under torch.use_deterministic_algorithms(True), swaps it for
+    a slow decomposition (torch._decomp) whose VALUES differ in the last bits from those of the kernel: with this Function the forward under the
+    flag is the forward without it."""
+
+    @staticmethod
+    def forward(ctx, x, size, scale_factor):
+        if (size is None) == (scale_factor is None):
+            raise ValueError("upsample_bilinear: exactly one of size and scale_factor")
+        if size is not None:
+            out_size, factors = ([size, size] if isinstance(size, int) else list(size)), None
+        else:
+            out_size, factors = None, ([float(scale_factor)] * 2 if isinstance(scale_factor, (int, float)) else [float(v) for v in scale_factor])
+        ctx.in_shape, ctx.scale_factor = tuple(x.shape), scale_factor
+        return torch._C._nn.upsample_bilinear2d(x, out_size, False, factors)     # what F.interpolate calls (recompute_scale_factor=None)
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return ops.upsample_bilinear_backward(grad_out.contiguous(), ctx.in_shape, ctx.scale_factor), None, None
+
+
+def takes_upsample_kernel(x, mode, align_corners):
+    """Whether FPN / InterpolateModule differentiate this interpolation through UpsampleBilinearFunction: the deterministic mode is on, the tensor is
+    on the GPU, a gradient is wanted, and it is the bilinear, align_corners=False form the kernel is the adjoint of."""
+    return (mode == "bilinear" and align_corners is False and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and wants_grad(x)
+            and is_deterministic())
+
+
+def upsample_bilinear(x, size=None, scale_factor=None):
+    return UpsampleBilinearFunction.apply(x, size, scale_factor)
 
 
 def modulated_deform_conv(x, offset, mask, weight, bias, stride, padding, dilation, deform_groups):

@@ -2,7 +2,8 @@
 //
 // The gradients dcn_v2's and mmcv's backward passes produce, for the training path of the drop-in shims (stmask_amd/autograd.py):
 //   stm_deform_col2im_f32       grad_x      scattered from grad_cols to the 4 bilinear corners of every tap, times the mask.  Offsets are
-//                                           arbitrary, so this is a scatter: fp32 atomic adds (last-bit run-to-run variation).
+//                                           arbitrary, so this is a scatter: fp32 atomic adds (last-bit run-to-run variation; the deterministic
+//                                           mode takes stm_deform_col2im_det_f32 of det_backward.hip instead, which has none).
 //   stm_deform_col2im_coord_f32 grad_offset / grad_mask: one reduction over the C / dg channels of a deformable group per output, in a fixed
 //                                           channel order, no atomics (run-to-run identical).
 // The sample position, the validity rule (-1 < h < H, -1 < w < W), the corner weights and the in-kernel sigmoid of a logit mask are the

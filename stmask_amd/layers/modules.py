@@ -20,6 +20,11 @@ class InterpolateModule(nn.Module):
         self.args, self.kwargs = args, kwargs
 
     def forward(self, x):
+        kw = self.kwargs
+        # deterministic mode (autograd.set_deterministic): the same forward, its backward a gather instead of torch's atomic scatter
+        if (not self.args and set(kw) <= {"size", "scale_factor", "mode", "align_corners"}
+                and autograd.takes_upsample_kernel(x, kw.get("mode"), kw.get("align_corners"))):
+            return autograd.upsample_bilinear(x, kw.get("size"), kw.get("scale_factor"))
         return F.interpolate(x, *self.args, **self.kwargs)
 
 
@@ -69,7 +74,10 @@ class FPN(nn.Module):
                 x = lateral  # reference adds to torch.zeros(1): identical values
             else:
                 h, w = convouts[j].shape[2:]
-                x = F.interpolate(x, size=(h, w), mode=self.interpolation_mode, align_corners=False) + lateral
+                if autograd.takes_upsample_kernel(x, self.interpolation_mode, False):     # deterministic mode: same values, a gather backward
+                    x = autograd.upsample_bilinear(x, size=(h, w)) + lateral
+                else:
+                    x = F.interpolate(x, size=(h, w), mode=self.interpolation_mode, align_corners=False) + lateral
             out[j] = x
         for i, pred in enumerate(self.pred_layers):
             j = n - 1 - i

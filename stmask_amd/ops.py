@@ -6,6 +6,7 @@ no CPU fallback (oracle/ is test infrastructure and is never imported from here)
 """
 import ctypes
 import os
+import warnings
 
 import torch
 
@@ -322,11 +323,66 @@ def roi_align(feat, rois, output_size, spatial_scale=1.0, sampling_ratio=0, alig
     return out
 
 
+def _deterministic():
+    from . import autograd     # autograd imports this module
+    return autograd.is_deterministic()
+
+
+def _alert_not_deterministic(name):
+    """What every torch operator without a deterministic implementation does under torch.use_deterministic_algorithms(True), for the two fp32
+    atomic scatters: they are reached under the flag only when autograd.set_deterministic(False) switched the fixed-point kernels off, and then
+    they say so the way torch's own operators do -- a RuntimeError, or a warning with warn_only=True -- instead of running unnoticed.  (torch's flag
+    knows nothing of this library's kernels, and from torch 2.10 on it no longer stops such a step itself: bilinear F.interpolate runs as a
+    decomposition there.)  Without torch's flag nothing is checked and nothing changes."""
+    if not torch.are_deterministic_algorithms_enabled():
+        return
+    msg = (f"{name} does not have a deterministic implementation, but you set 'torch.use_deterministic_algorithms(True)' and switched its "
+           "deterministic replacement off with stmask_amd.autograd.set_deterministic(False).  Leave the mode at None (or True) to take the "
+           "fixed-point kernel, or pass warn_only=True to torch.use_deterministic_algorithms to run the atomic one with a warning.")
+    if torch.is_deterministic_algorithms_warn_only_enabled():
+        warnings.warn(msg)
+    else:
+        raise RuntimeError(msg)
+
+
+def _det_workspace(out):
+    """The int64 accumulator of a deterministic scatter into `out` and its two words of state (csrc/det_backward.h), as a tensor: the caching
+    allocator hands it back to the next layer's backward.  The library clears it."""
+    return torch.empty(out.numel() + 1, device=out.device, dtype=torch.int64)
+
+
+def upsample_bilinear_backward(grad_out, in_shape, scale_factor=None):
+    """grad of F.interpolate(x [B,C,h,w], size= or scale_factor=, mode="bilinear", align_corners=False) w.r.t. x from grad_out [B,C,H,W]: a gather
+    in a fixed order (csrc/det_backward.hip).  scale_factor: what the forward was given (a number, a pair or None for the size= form)."""
+    _dev(grad_out)
+    go = _f32c(grad_out)
+    B, C, h, w = in_shape
+    if go.dim() != 4 or tuple(go.shape[:2]) != (B, C):
+        raise StmError(f"upsample_bilinear_backward: grad_out {tuple(go.shape)} does not belong to an input {tuple(in_shape)}")
+    if scale_factor is None:
+        sf_h = sf_w = 0.0       # the library takes in / out
+    elif isinstance(scale_factor, (int, float)):
+        sf_h = sf_w = float(scale_factor)
+    else:
+        sf_h, sf_w = (float(v) for v in scale_factor)
+    gin = torch.empty(B, C, h, w, device=go.device, dtype=torch.float32)
+    _lib.private_call("stm_upsample_bilinear_backward_f32", _p(go), _p(gin), B * C, h, w, go.shape[2], go.shape[3], sf_h, sf_w, _stream())
+    return gin
+
+
 def deform_col2im(grad_cols, offset, mask, g, fused_om=None):
-    """grad_x [B,C,H,W] of deform_im2col from the column gradient grad_cols [B, C*kh*kw, Ho*Wo] (fp32 atomic scatter)."""
+    """grad_x [B,C,H,W] of deform_im2col from the column gradient grad_cols [B, C*kh*kw, Ho*Wo]: an fp32 atomic scatter, or under
+    autograd.is_deterministic() the same terms summed in 64-bit fixed point (csrc/det_backward.hip; the workspace is 8 bytes per element of grad_x)."""
     _dev(grad_cols, offset, mask, fused_om)
     grad_cols = _f32c(grad_cols)
     off, obs, _, mk_ptr, mbs = _offset_mask_views(offset, mask, g, fused_om)
+    if _deterministic():
+        gx = torch.empty(g.B, g.C, g.H, g.W, device=grad_cols.device, dtype=torch.float32)
+        ws = _det_workspace(gx)
+        _lib.private_call("stm_deform_col2im_det_f32", _p(grad_cols), _p(off), obs, c_p(mk_ptr), mbs, 1 if fused_om is not None else 0, _p(gx),
+                          ctypes.byref(g), _p(ws), 8 * ws.numel(), _stream())
+        return gx
+    _alert_not_deterministic("stm_deform_col2im_f32")
     gx = torch.zeros(g.B, g.C, g.H, g.W, device=grad_cols.device, dtype=torch.float32)
     call("stm_deform_col2im_f32", _p(grad_cols), _p(off), obs, c_p(mk_ptr), mbs, 1 if fused_om is not None else 0, _p(gx), ctypes.byref(g), _stream())
     return gx
@@ -392,7 +448,8 @@ def deform_conv_backward(grad_out, x, offset, mask, weight, stride=1, padding=0,
 
 
 def roi_align_backward(grad_out, rois, feat_shape, output_size, spatial_scale=1.0, sampling_ratio=0, aligned=True):
-    """grad_feat of roi_align (fp32 atomic scatter); no gradient w.r.t. rois."""
+    """grad_feat of roi_align: an fp32 atomic scatter, or under autograd.is_deterministic() the same terms summed in 64-bit fixed point
+    (csrc/det_backward.hip); no gradient w.r.t. rois."""
     _dev(grad_out, rois)
     go, rois = _f32c(grad_out), _f32c(rois)
     ph, pw = _pair(output_size)
@@ -400,6 +457,13 @@ def roi_align_backward(grad_out, rois, feat_shape, output_size, spatial_scale=1.
     n = rois.shape[0]
     if tuple(go.shape) != (n, C, ph, pw):
         raise StmError(f"roi_align_backward: grad_out {tuple(go.shape)} != {(n, C, ph, pw)}")
+    if _deterministic():
+        gfeat = torch.empty(B, C, H, W, device=go.device, dtype=torch.float32)
+        ws = _det_workspace(gfeat)
+        _lib.private_call("stm_roi_align_backward_det_f32", _p(go), _p(rois), _p(gfeat), B, C, H, W, n, ph, pw, spatial_scale, sampling_ratio,
+                          1 if aligned else 0, _p(ws), 8 * ws.numel(), _stream())
+        return gfeat
+    _alert_not_deterministic("stm_roi_align_backward_f32")
     gfeat = torch.zeros(B, C, H, W, device=go.device, dtype=torch.float32)
     call("stm_roi_align_backward_f32", _p(go), _p(rois), _p(gfeat), B, C, H, W, n, ph, pw, spatial_scale, sampling_ratio, 1 if aligned else 0,
          _stream())

@@ -26,6 +26,14 @@ class NetLoss(nn.Module):
         return self.criterion(self.net, preds, gt_bboxes, gt_labels, gt_masks, gt_ids)
 
 
+def use_deterministic():
+    """What --deterministic of the training scripts sets, in every rank: torch's flag, which autograd.is_deterministic() follows (the backward's
+    scatters then sum in fixed point, bilinear upsampling differentiates through a gather), and MIOpen's deterministic solvers without a search."""
+    torch.use_deterministic_algorithms(True)
+    torch.backends.cudnn.deterministic = True
+    torch.backends.cudnn.benchmark = False
+
+
 def train_step(net_loss, optimizer, batch):
     """One step on batch = (images, gt_bboxes, gt_labels, gt_masks, gt_ids[, img_meta]): zero the gradients, forward, backward through the sum of
     the loss terms, optimizer step.  A GuardedSGD is handed that sum: it skips the update on the device when the loss (or, with guard="grads", a
