@@ -27,6 +27,10 @@ Input conditions of a golden case (asserted by the generator, which tries seeds 
 (mask_loss_restate.input_condition: nearer 1, fp32 rounding decides between log(1 - p) and the clamp at -100), and every crop edge stays at
 least EDGE = 1e-4 prototype pixels away from where the crop rule (sanitize_coordinates, padding 1, cast=False) changes an integer, so that a
 few ULP of exp cannot move a pixel in or out.
+
+CONSTRUCTED holds a module-level case that no run of the reference backs: the loss kernels end in single-workgroup scans over 256-row tiles whose
+threads own more than one tile only past 256 tiles (conf_loss_restate, pos_loss_restate), a size no golden case has; its seed meets the same input
+conditions (INPUT_CONDITIONS, EDGE, t2s_loss_restate.KINK), which tests/test_mbox_loss_cpu.py asserts.
 """
 import types
 
@@ -157,6 +161,20 @@ GOLDEN = {
 }
 GOLDEN_SEED0 = {name: 51000 + 1000 * i for i, name in enumerate(GOLDEN)}
 NET_SEED = T2S.NET_SEED
+# Constructed, not captured from the reference: a batch above both lines of the loss kernels' single-workgroup scans (conf_loss_restate,
+# pos_loss_restate).  P = 48 * 80 * 3 = 11 520 and 6 images (3 clips): 69 120 OHEM rows in 270 tiles, and 45 list tiles per image -- an odd
+# number, so images begin inside a scan thread's chunk of 2 -- 270 in all.  "seed": the first from 54000 on that meets the input conditions the
+# golden cases meet (INPUT_CONDITIONS; tests/test_mbox_loss_cpu.py asserts them).
+CONSTRUCTED = {
+    "rows_270": dict(grid=(48, 80), scales=[0.1, 0.16, 0.24], proto=(12, 20), M=8, HW=(48, 80), G=(2, 3, 1, 2, 2, 1), big=None, seed=54153),
+}
+# what the generator of the golden cases requires of a seed: the margins of the target assignment and of the OHEM cut, the smallest clamp
+# argument of the track loss (the crop edges' EDGE and smooth-L1's t2s_loss_restate.KINK are defined with their restatements)
+INPUT_CONDITIONS = dict(match_margin=1e-3, ohem_margin=1e-3, track_min_v=2e-3)
+
+
+def spec_of(name):
+    return GOLDEN[name] if name in GOLDEN else CONSTRUCTED[name]
 
 
 def make_priors(grid, scales):

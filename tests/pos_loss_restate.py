@@ -30,6 +30,13 @@ Bounds.  Every bound is MARGIN times a first-order forward error analysis with e
 MARGIN is the constant that keeps the reference's own fp32 CPU result inside on every golden case (tests/golden/gen_pos_loss_golden.py asserts it and
 stores the observed fraction per case): the derived bounds need no widening, MARGIN = 1, and the reference's largest fraction of them is 0.43
 (grad_centerness; 0.18 for the track loss).
+
+The list cases (LIST_CASES, list_targets).  The ordered list of the positives that the track loss, the temporal-fusion loss and the mask term
+share is built over tiles of TILE = 256 priors of one image (tpi = ceil(P / 256) tiles per image) and ends in one workgroup of 256 threads: thread
+t owns the tiles [t * chunk, (t + 1) * chunk), chunk = ceil(B * tpi / 256), carries the count across them, and takes the images t, t + 256, ...
+The reference's generators stay below 256 tiles and 4 images, where neither the carry nor the second trip over the images runs.  The list cases
+reach chunk = 2 with images that begin in the middle of a thread's chunk (tpi odd), chunk = 4 with B > 256, and B > 256 with one tile per image,
+with positives in an image's first and last row and on both sides of both kinds of tile border (inside a chunk, between two chunks).
 """
 import numpy as np
 import torch
@@ -297,6 +304,37 @@ def scalar(a):
     return float(np.asarray(a).reshape(-1)[0])
 
 
+TILE = 256                              # priors per tile of the positive list, threads of its scanning workgroup
+
+# name -> (B, P, period, {image index modulo the period: its positive priors}); the images not named have none
+LIST_CASES = {
+    # tpi = 37, 259 tiles, chunk = 2: the images 1, 3 and 5 begin at an odd tile, inside a thread's chunk; the last thread owns one tile
+    "tiles_259": (7, 9400, 7, {0: [0, 255, 256, 511, 512, 9399], 1: [0, 1279, 1280, 9399], 3: [0, 2660, 9399], 5: [9399],
+                               6: [0, 255, 256, 9215, 9216, 9399]}),
+    # tpi = 3 (256 + 256 + 88 priors), 900 tiles, chunk = 4, 300 images
+    "tiles_900": (300, 600, 10, {1: [0, 599], 3: [255, 256], 5: [300, 511, 512], 8: [0, 255, 256, 511, 512, 599]}),
+    # tpi = 1, 300 tiles, chunk = 2, 300 images: every tile border is an image border
+    "images_300": (300, 37, 7, {1: [0, 36], 2: [0], 4: [36], 5: [0, 1, 17, 20, 35, 36]}),
+}
+
+
+def list_positives(name):
+    """(B, P, [the positive priors of image b, ascending] for every b) of a list case."""
+    B, P, period, table = LIST_CASES[name]
+    return B, P, [table.get(b % period, []) for b in range(B)]
+
+
+def list_targets(name):
+    """conf_t int64 [B,P] of a list case: labels 1 .. 40 at its positives, neutrals (-1) at every 11th prior besides, background elsewhere."""
+    B, P, per_image = list_positives(name)
+    t = torch.zeros(B, P, dtype=torch.int64)
+    t[:, 7::11] = -1
+    for b, priors in enumerate(per_image):
+        for p in priors:
+            t[b, p] = 1 + (b * P + p) % 40
+    return t
+
+
 # name -> (B, P, positives per image, neutrals per image, priors per image?)
 BOX_GOLDEN = [
     ("p37", 1, 37, [5], 2, False),
@@ -370,4 +408,9 @@ def constructed_track_cases():
     x, ids = draw_track(3, 300, 8, 5302, 3)
     ids = torch.tensor([0, -7, 0, 1 << 40])[ids]                        # (draw_track's ids are 1..3)
     cases["cross_image"] = (x, draw_conf_t(3, 300, [9, 0, 5], gen, 2), ids)
+    # the list cases (module docstring), D = 8: W = (s1^2 - s2) / 2 passes through the scan's loop over more than 256 images
+    for i, name in enumerate(LIST_CASES):
+        B, P, _ = list_positives(name)
+        x, ids = draw_track(B, P, 8, 5310 + i, 6)
+        cases[name] = (x, list_targets(name), ids)
     return cases

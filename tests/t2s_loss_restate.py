@@ -36,6 +36,7 @@ import torch.nn.functional as F
 
 import autograd_restate
 import layer_grad_restate
+import pos_loss_restate
 
 EPS = 2.0 ** -24
 MARGIN = 1.0
@@ -289,9 +290,29 @@ def find_seed(name, decode_f32, tries=200):
     raise SystemExit(f"{name}: no seed keeps smooth-L1 off its kink")
 
 
+def _list_spec(name, seed):
+    """A list case of pos_loss_restate read as clips: clip b's shift-positives are image b's positives.  Even clips have 3 reference and 2 next
+    boxes, odd clips 2 and 3; a few more priors carry an id that one frame lacks, or a negative one.  `seed`: what draws the case."""
+    B, P, per_image = pos_loss_restate.list_positives(name)
+    clips = []
+    for b, priors in enumerate(per_image):
+        if b % 2 == 0:
+            c = dict(ref=[1, 2, 3], nxt=[3, 1], assign={2: 2, -5: 2})
+        else:
+            c = dict(ref=[1, 2], nxt=[2, 1, 4], assign={4: 2, -5: 1})
+        shared = [i for i in c["ref"] if i in c["nxt"]]
+        c["rows"] = {p: shared[j % len(shared)] for j, p in enumerate(priors)}
+        clips.append(c)
+    return dict(P=P, M=8, HW=(24, 40), clips=clips, seed=seed)
+
+
 def constructed_cases():
-    """name -> spec of cases the reference cannot digest (the documented deviations) or that expose a particular confusion."""
+    """name -> spec of cases the reference cannot digest (the documented deviations) or that expose a particular confusion, and two list cases
+    of pos_loss_restate (more than 256 tiles with clips that begin inside a scan thread's chunk; more than 256 clips) for the target kernel,
+    which writes the tiles' counts itself.  A spec that carries a "seed" is drawn with it."""
     return {
+        "tiles_259": _list_spec("tiles_259", 42001),
+        "images_300": _list_spec("images_300", 42002),
         # duplicate ids: 4 twice in the reference frame (the LAST index wins), 6 twice in the next frame (the FIRST index wins)
         "duplicates": dict(P=37, M=8, HW=(24, 40), clips=[dict(ref=[4, 6, 4], nxt=[6, 4, 6], assign={4: 3, 6: 3})]),
         # a positive id (9) that is in the next frame but not in the reference frame: not shift-positive

@@ -84,6 +84,79 @@ def test_ties_at_the_cut_go_to_the_lower_index():
     assert r["neg"][[255, 256, 299, 300]].tolist() == [True, True, False, False] and r["num_neg"] == 12
 
 
+# name -> what the case exists for: (scan chunk over its tiles, scan chunk over its images, rows the score kernel stages at a time)
+SCAN_PATHS = {"rows_chunk2": (2, 1, 256), "rows_chunk4": (4, 1, 256), "images_300": (1, 2, 256), "c81": (1, 1, 128), "c60": (1, 1, 192),
+              "ties_across_chunks": (2, 1, 256), "ties_cut_at_tile_end": (2, 1, 256)}
+
+
+@pytest.mark.parametrize("name", list(SCAN_PATHS))
+def test_scan_cases_reach_what_they_exist_for(name):
+    """More than 256 tiles or images, or a staging count of 128 / 192; a margin at the cut for the drawn cases; positives at both ends."""
+    conf, conf_t = CASES[name]
+    r = R.restate(conf, conf_t, RATIO, ALPHA)
+    tiles = -(-r["N"] // R.TILE)
+    assert (R.scan_chunk(tiles), R.scan_chunk(r["B"]), R.stage_rows(r["C"])) == SCAN_PATHS[name]
+    assert (tiles > 256) == (SCAN_PATHS[name][0] > 1) and (r["B"] > 256) == (SCAN_PATHS[name][1] > 1)
+    assert 0 < r["k"] < r["N"] and r["num_neg"] == r["k"]
+    if name in R.SCAN_DRAWS:
+        assert r["margin"] > R.MARGIN
+    pos_tile = torch.unique(r["pos"].nonzero()[:, 0] // R.TILE)
+    npos_img = r["pos"].view(r["B"], r["P"]).sum(1)
+    if name in ("rows_chunk2", "rows_chunk4"):                          # the kept rows' ranks matter to the last tile
+        assert int(pos_tile[0]) == 0 and int(pos_tile[-1]) == tiles - 1
+        last_of_image = (torch.arange(1, r["B"] + 1) * r["P"] - 1) // R.TILE
+        assert all(int(v) in pos_tile.tolist() for v in last_of_image[-2:])
+        assert int((npos_img == 0).sum()) >= 1 and len(set(npos_img.tolist())) > 4             # the two weight modes differ
+        ra = R.restate(conf, conf_t, RATIO, ALPHA, "aligned")
+        assert not torch.equal(ra["w"], r["w"])
+        kept = r["keep"].nonzero()[:, 0]                                # ... and the rank decides the weight past the 256th tile
+        assert int(kept[r["num_pos"] - 1]) // R.TILE > 256 and int((kept[:r["num_pos"]] // R.TILE > 256).sum()) > 20
+    if name == "images_300":
+        assert int((npos_img == 0).sum()) * 3 >= r["B"] and int(npos_img[256:].sum()) > 0 and int(npos_img[:256].sum()) > 0
+    if name == "c60":                                                   # a whole tile: stages of 192 and 64; the last tile partial
+        assert r["N"] > R.TILE and r["N"] % R.TILE not in (0, 192) and R.TILE - R.stage_rows(60) == 64
+
+
+@pytest.mark.parametrize("name", list(R.TIE_TAKEN))
+def test_tie_cases_cut_where_they_say(name):
+    """770 identical true negatives in five tiles, strictly between two neighbouring drawn scores; both tiles of scan thread 50's chunk (100,
+    101) hold some, as do tiles of other threads before and behind; k cuts TIE_TAKEN ties deep and the lower indices are taken."""
+    conf, conf_t = CASES[name]
+    r = R.restate(conf, conf_t, RATIO, ALPHA)
+    s, t = r["score"], conf_t.view(-1)
+    tied = torch.tensor(R.tie_rows())
+    v = s[tied[0]]
+    eq = s == v
+    assert r["margin"] == 0.0 and R.scan_chunk(-(-r["N"] // R.TILE)) == 2
+    assert torch.equal(eq.nonzero()[:, 0], tied) and tied.numel() >= 600 and bool((t[tied] == 0).all())
+    higher, lower = s[s > v].min(), s[s < v].max()
+    assert float(higher) > float(v) > float(lower)
+    assert int(((s < higher) & (s > lower)).sum()) == tied.numel()       # nothing else between the two neighbours
+    per_tile = torch.bincount(tied // R.TILE, minlength=300)
+    assert {int(i): int(per_tile[i]) for i in per_tile.nonzero()[:, 0]} == R.TIE_TILES
+    assert {100, 101} <= set(R.TIE_TILES) and any(i // 2 != 50 and i < 100 for i in R.TIE_TILES) and any(i // 2 > 50 for i in R.TIE_TILES)
+    krem = r["k"] - int((s > v).sum())
+    assert krem == R.TIE_TAKEN[name] and 0 < krem < tied.numel()
+    before = torch.cumsum(per_tile, 0) - per_tile                        # ties in the tiles before each tile
+    cut = [int(i) for i in per_tile.nonzero()[:, 0] if int(before[i]) < krem < int(before[i] + per_tile[i])]
+    if name == "ties_across_chunks":                                    # cut inside the second tile of a chunk, ties before it and behind it
+        assert cut == [101] and cut[0] % 2 == 1 and int(before[101]) > 0 and int(per_tile[102:].sum()) > 0
+    else:                                                               # exactly behind tile 100: no tile is cut, tile 101 takes nothing
+        assert cut == [] and int(before[101]) == krem and int(per_tile[101]) > 0
+    taken = r["neg"][tied]
+    assert int(taken.sum()) == krem and bool(taken[:krem].all()) and not bool(taken[krem:].any())
+    assert r["num_neg"] == r["k"]
+    # the count of kept rows carried from tile 160 to tile 161 (one thread's chunk) decides weights: none of tile 160's ties is taken; tile 161's
+    # kept rows rank below num_pos and carry a positive's weight, and would rank above it, with the negatives' weight, were those ties counted
+    kept = r["keep"].nonzero()[:, 0]
+    rank = torch.arange(kept.numel())
+    in161 = kept // R.TILE == 161
+    assert int(in161.sum()) >= 3 and int(per_tile[160]) > 0 and not bool(r["neg"][tied[tied // R.TILE == 160]].any())
+    assert int(rank[in161].max()) < r["num_pos"] <= int(rank[in161].min()) + int(per_tile[160])
+    w_neg = RATIO * r["B"] / r["num_neg"]
+    assert bool((r["w"][kept[in161]] != w_neg).all()) and bool((r["w"][kept[rank >= r["num_pos"]]] == w_neg).all())
+
+
 def test_no_positive_selects_nothing():
     conf, conf_t = CASES["no_pos"]
     for mode in ("reference", "aligned"):

@@ -6,7 +6,7 @@ End-to-end tolerance: it cannot be derived (MIOpen and the CPU add the convoluti
 the fixture stores the relative deviation of the reference's own fp32 CPU run from the fp64 composition (e2e_loss, e2e_grad), and the GPU is
 allowed 8 x the largest over the golden cases -- three bits for the different summation order.  Every test prints its observed fraction.
 
-Observed on the MI355X (largest fraction of each bound over the cases): reg_t columns 2-3 0.50, B_shift 0.04, M_shift 0.08, grad_bbox_reg 0.27,
+Observed on the MI355X (largest fraction of each bound over the cases): reg_t columns 2-3 0.76, B_shift 0.04, M_shift 0.08, grad_bbox_reg 0.27,
 grad_bce 0.16, grad_coeff 0.05 of its tolerance; end to end 0.07 (losses), 0.06 (parameter gradients), 0.07 (grad concat_feat) of the tolerance."""
 import functools
 import os
@@ -39,8 +39,14 @@ E2E_GRAD = 8 * max(_s(GOLD[f"{n}__e2e_grad"]) for n in WITH_ROWS)
 @functools.lru_cache(maxsize=None)
 def cpu_case(name):
     """(case on the CPU, its restated targets): drawn once, shared, never modified."""
-    seed = int(_s(GOLD[f"{name}__seed"])) if name in R.GOLDEN else 41000 + sorted(R.constructed_cases()).index(name)
-    case = R.draw_case(ALL_SPECS[name], seed)
+    spec = ALL_SPECS[name]
+    if name in R.GOLDEN:
+        seed = int(_s(GOLD[f"{name}__seed"]))
+    elif "seed" in spec:
+        seed = spec["seed"]
+    else:                                                                                 # the constructed cases that carry no seed of their own
+        seed = 41000 + sorted(n for n, s in R.constructed_cases().items() if "seed" not in s).index(name)
+    case = R.draw_case(spec, seed)
     return case, R.restate_targets(case["ids_t"], case["gt_bboxes"], case["gt_ids"])
 
 

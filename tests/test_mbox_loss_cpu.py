@@ -166,6 +166,32 @@ def test_the_other_gradients_and_the_shift_losses_of_the_golden_forward(name):
     assert e_grad <= 8 * max(R.scalar(t2s_gold[f"{n}__e2e_grad"]) for n in with_rows)
 
 
+@pytest.mark.parametrize("name", list(R.CONSTRUCTED))
+def test_constructed_case_lies_above_both_scan_lines_and_meets_the_input_conditions(name):
+    """The module-level case that no run of the reference backs: more than 256 OHEM tiles of 256 flattened rows, more than 256 list tiles with an
+    odd number per image (images begin inside a scan thread's chunk of 2), and the input conditions the generator of the golden cases demands
+    of a seed -- the bounds the GPU tests apply are derived under them."""
+    spec = R.CONSTRUCTED[name]
+    case = R.draw_case(spec, spec["seed"])
+    B, P = case["conf_t"].shape
+    assert (B, P, spec["M"], spec["proto"], spec["HW"], spec["G"]) == (6, 11520, 8, (12, 20), (48, 80), (2, 3, 1, 2, 2, 1)) and len(spec["scales"]) == 3
+    ohem_tiles, tpi = -(-B * P // CR.TILE), -(-P // PR.TILE)
+    assert (ohem_tiles, tpi, B * tpi) == (270, 45, 270) and CR.scan_chunk(ohem_tiles) == 2 and -(-B * tpi // PR.TILE) == 2 and tpi % 2 == 1
+    n_b = (case["conf_t"] > 0).sum(1)
+    assert int(n_b.min()) >= 1 and case["match_margin"] > R.INPUT_CONDITIONS["match_margin"]
+    tile = torch.unique(torch.nonzero(case["conf_t"].reshape(-1) > 0).reshape(-1) // CR.TILE)
+    assert int(tile[-1]) >= (B - 1) * P // CR.TILE and int((tile % 2 == 1).sum()) > 0 and int((tile % 2 == 0).sum()) > 0    # ... into the last image
+    assert CR.margin(case["conf"], case["conf_t"], R.RATIO) > R.INPUT_CONDITIONS["ohem_margin"]
+    comp = R.compose(case["loc"], case["mask_coeff"], case["proto"], case["priors"], case["conf_t"], case["idx_t"], sum(case["gt_masks"], []),
+                     oracle.decode, R.MASK_ALPHA, 1.0 / B)
+    assert comp["n"] == int(n_b.sum()) and comp["pred_ok"] and comp["min_edge"] >= R.EDGE
+    tr = PR.restate_track(case["track"], case["conf_t"], case["ids_t"], R.ALPHAS["track_alpha"], 1.0)
+    assert tr["min_v"] > R.INPUT_CONDITIONS["track_min_v"]
+    t2s = T2S.compose(R.t2s_case(case), R.stand_in_net(spec["M"], double=True).TemporalNet, oracle.decode, R.ALPHAS["boxshift_alpha"],
+                      R.ALPHAS["maskshift_alpha"], want_grads=False)
+    assert t2s["n"] > 0 and t2s["min_kink"] > T2S.KINK
+
+
 def test_module_has_the_reference_s_constructor_and_forward():
     assert layers.modules.MultiBoxLoss is layers.MultiBoxLoss and issubclass(layers.MultiBoxLoss, torch.nn.Module)
     init = list(inspect.signature(layers.MultiBoxLoss.__init__).parameters)

@@ -202,6 +202,52 @@ def test_ids_are_compared_for_equality_only():
     assert bool(cross.any()) and sorted(img.unique().tolist()) == [0, 2]
 
 
+# name -> (tiles per image, tiles, the scan's chunk, more than 256 images?)
+LIST_PATHS = {"tiles_259": (37, 259, 2, False), "tiles_900": (3, 900, 4, True), "images_300": (1, 300, 2, True)}
+
+
+@pytest.mark.parametrize("name", list(R.LIST_CASES))
+def test_list_cases_reach_what_they_exist_for(name):
+    """More than 256 tiles (the scan's carry inside a thread's chunk), images that begin inside a chunk, more than 256 images; few positives per
+    image and many images without; positives in an image's first and last row and on both sides of a tile border inside a chunk and of one
+    between two chunks."""
+    B, P, per_image = R.list_positives(name)
+    conf_t = R.list_targets(name)
+    tpi = -(-P // R.TILE)
+    nT = B * tpi
+    chunk = -(-nT // R.TILE)
+    assert (tpi, nT, chunk, B > 256) == LIST_PATHS[name] and nT > 256
+    pos = conf_t > 0
+    assert [row.nonzero()[:, 0].tolist() for row in pos] == per_image and bool((conf_t < 0).any())
+    counts = pos.sum(1)
+    assert int(counts.max()) <= 6 and int((counts == 0).sum()) * 4 >= B and int(counts.sum()) <= 500
+    if B > 256:
+        assert int(counts[256:].sum()) > 0 and int((counts[256:] == 0).sum()) > 0
+    if name == "tiles_259":                                             # prefix[b] is read from the middle of another thread's chunk
+        assert tpi % 2 == 1 and any((b * tpi) % chunk and int(counts[b]) for b in range(B))
+    assert bool(pos[:, 0].any()) and bool(pos[:, P - 1].any())
+    tile = (torch.arange(B)[:, None] * tpi + torch.arange(P)[None, :] // R.TILE)[pos]     # the tile of every positive, in list order
+    rows = pos.reshape(-1).nonzero()[:, 0]
+    prior = rows % P
+    last_of_tile = (prior % R.TILE == R.TILE - 1) | (prior == P - 1)
+    first_of_tile = prior % R.TILE == 0
+    inside, between = 0, 0                                              # borders i | i + 1 with a positive in the last row of i and the first of i + 1
+    for i in tile[last_of_tile].tolist():
+        if bool((first_of_tile & (tile == i + 1)).any()):
+            if (i + 1) % chunk:
+                inside += 1
+            else:
+                between += 1
+    assert inside > 0 and between > 0, (inside, between)
+    x, t, ids = R.constructed_track_cases()[name]
+    assert torch.equal(t, conf_t) and x.shape == (B, P, 8)
+    r = R.restate_track(x, t, ids, AT, G_T)
+    assert r["n"] == int(counts.sum()) >= 20 and r["min_v"] > 2e-3       # no pair near a clamp, as on the golden cases
+    w = 1.0 / counts.clamp(min=1).double()
+    s1, s2 = (counts * w).sum(), (counts * w * w).sum()
+    assert abs(float((s1 * s1 - s2) / 2) - float(r["W"])) < 1e-9 * float(r["W"])             # W as the kernel forms it, over all B images
+
+
 def test_layers_fail_loudly_on_cpu_tensors():
     """No CPU fallback: the new layer functions exist and refuse CPU tensors."""
     loc, pri, gt, conf_t, cent = R.golden_box_case(Z, "p37")

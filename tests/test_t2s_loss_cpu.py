@@ -97,6 +97,26 @@ def _encode64(nxt, ref):
                         torch.log((n[3] - n[1]) / h) / R.V1])
 
 
+@pytest.mark.parametrize("name", ["tiles_259", "images_300"])
+def test_list_cases_put_the_shift_positives_where_pos_loss_restate_lists_them(name):
+    """The two constructed specs for the target kernel's own tile counts: more than 256 tiles of 256 priors, 2 to 3 boxes per frame; the
+    shift-positives are exactly the list case's positives (what each reaches is pinned in tests/test_pos_loss_cpu.py); priors with an id that
+    one frame lacks, and with a negative id, stand beside them."""
+    import pos_loss_restate as PR
+    spec = R.constructed_cases()[name]
+    B, P, per_image = PR.list_positives(name)
+    assert len(spec["clips"]) == B and spec["P"] == P and B * -(-P // 256) > 256
+    assert all(2 <= len(c["ref"]) <= 3 and 2 <= len(c["nxt"]) <= 3 for c in spec["clips"])
+    case = R.draw_case(spec, spec["seed"])
+    t = R.restate_targets(case["ids_t"], case["gt_bboxes"], case["gt_ids"])
+    assert [row.nonzero()[:, 0].tolist() for row in t["pos"]] == per_image
+    assert torch.equal(t["pos"], PR.list_targets(name) > 0)
+    other = (case["ids_t"] != 0) & ~t["pos"]
+    assert bool((case["ids_t"][other] > 0).any()) and bool((case["ids_t"][other] < 0).any())
+    kg = t["k_global"][t["pos"]]
+    assert len(set(kg.tolist())) > B // 2 and bool(torch.isfinite(t["reg"]).all())
+
+
 def test_duplicate_ids_resolve_to_the_last_reference_and_the_first_next_index():
     case = R.draw_case(R.constructed_cases()["duplicates"], 41001)          # ref ids [4, 6, 4], next ids [6, 4, 6]
     t = R.restate_targets(case["ids_t"], case["gt_bboxes"], case["gt_ids"])
