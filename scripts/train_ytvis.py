@@ -87,6 +87,8 @@ def parse_args(argv=None):
     ap.add_argument("--start_iter", type=int, default=-1, help="iteration to resume at; -1 takes it from the checkpoint")
     ap.add_argument("--guard", choices=["loss", "grads", "off"], default="loss", help="what makes the optimizer skip a step, on the device")
     ap.add_argument("--extra_aug", default="", help="comma list of photo, expand, crop: ExtraAugmentation with the reference's settings for each")
+    ap.add_argument("--decode", choices=["host", "device"], default="host",
+                    help="where the frames' JPEG files are decoded, for training batches and validation: PIL on the host, or the MI355X (stmask_amd.jpeg)")
     ap.add_argument("--log", default=None, help="a file of one JSON line per iteration (appended to when resuming)")
     ap.add_argument("--valid_ann", default=None, help="annotation file of the validation split (with or without annotations)")
     ap.add_argument("--valid_img_prefix", default=None, help="folder of the validation split's frames")
@@ -173,7 +175,7 @@ def main(argv=None):
     opt = make_optimizer(args, net.parameters(), lr, rank)
     trainer = DataParallelTrainer(net_loss, opt) if world > 1 else None      # weights from rank 0, verified equal
     extra_aug = config_from_names(args.extra_aug, MEANS)
-    loader = make_loader(args, datasets.YTVISTrainSet(args.ann, args.img_prefix, extra_aug=extra_aug), dev, rank)
+    loader = make_loader(args, datasets.YTVISTrainSet(args.ann, args.img_prefix, extra_aug=extra_aug, decode=args.decode), dev, rank)
     if len(loader) == 0:
         raise SystemExit(f"{len(loader.dataset)} frame pairs do not fill one batch of {args.batch_size}")
     say(f"{len(loader.dataset)} frame pairs, {len(loader)} iterations per epoch, {math.ceil(max_iter / len(loader))} epochs" +
@@ -236,7 +238,7 @@ def main(argv=None):
     twin = valid_set = None
     validating = bool(args.valid_ann and args.validation_interval > 0)
     if validating and chief:
-        valid_set = datasets.YTVISValSet(args.valid_ann, args.valid_img_prefix, read_ahead=8)
+        valid_set = datasets.YTVISValSet(args.valid_ann, args.valid_img_prefix, read_ahead=8, decode=args.decode)
         twin = validate.InferenceTwin(net, planes=args.eval_planes)
 
     def validate_at(path):
@@ -258,7 +260,7 @@ def main(argv=None):
         scored = valid_set.has_annotations
         print(f"validating -> {out_json}", flush=True)
         metrics = validate.validation(twin, valid_set, out_json, ann_file=args.valid_ann if scored else None,
-                                      metrics_file=metrics_file if scored else None, n_slots=args.eval_slots)
+                                      metrics_file=metrics_file if scored else None, n_slots=args.eval_slots, decode=args.decode)
         if log_file:
             listed = None if metrics is None else [float(v) for v in metrics]      # calc_metrics: the 12 summary numbers
             log_file.write(json.dumps({"kind": "valid", "iteration": iteration, "metrics": listed}) + "\n")

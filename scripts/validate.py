@@ -20,6 +20,8 @@ def parse_args(argv=None):
     ap.add_argument("--config", default="STMask_plus_resnet50_config")
     ap.add_argument("--slots", type=int, default=8, help="videos in flight")
     ap.add_argument("--planes", choices=["fp16x2", "bf16x3", "fp16x1"], default="fp16x2", help="plane format of the inference graph")
+    ap.add_argument("--decode", choices=["host", "device"], default="host",
+                    help="where the frames' JPEG files are decoded: PIL on the host, or the MI355X (stmask_amd.jpeg)")
     ap.add_argument("--out", default=None, help="the results JSON (default: CKPT with .pth replaced by .json); the mAP file lies beside it")
     return ap.parse_args(argv)
 
@@ -35,11 +37,11 @@ def main():
     out_json, metrics_file = validate.result_paths(args.ckpt)
     if args.out:
         out_json, metrics_file = args.out, os.path.splitext(args.out)[0] + ".txt"
-    dataset = datasets.YTVISValSet(args.ann, args.img_prefix, read_ahead=8)
+    dataset = datasets.YTVISValSet(args.ann, args.img_prefix, read_ahead=8, decode=args.decode)
     scored = dataset.has_annotations
     twin = validate.InferenceTwin(net, planes=args.planes)
     metrics = validate.validation(twin, dataset, out_json, ann_file=args.ann if scored else None, metrics_file=metrics_file if scored else None,
-                                  n_slots=args.slots)
+                                  n_slots=args.slots, decode=args.decode)
     dataset.close()
     print(f"results: {out_json}" + (f"   metrics: {metrics_file}" if scored else "   (no annotations: nothing scored)"))
     return metrics

@@ -254,6 +254,19 @@ DET_SIGNATURES = {
 DET_MIN_BITS = 36                                     # csrc/det_accum.h STM_DET_MIN_BITS
 DET_FINITE, DET_ZERO, DET_NONFINITE = 0, 1, 2         # csrc/det_accum.h STM_DET_FINITE / _ZERO / _NONFINITE
 
+# ... and those of csrc/jpeg.h: baseline JPEG frames decoded on the device (jpeg.py decode_batch).  A sixth private table, kept beside the five
+# above; jpeg_tables() lists it, private_call() resolves it and build() walks it too.
+JPEG_SIGNATURES = {
+    "stm_jpeg_struct_bytes": ("z", "i"),
+    "stm_jpeg_workspace_bytes": ("z", "pi"),
+    "stm_jpeg_decode_u8": ("i", "pipipzzzpzppziip"),
+}
+JPEG_MAX_DIM = 8192                                                         # csrc/jpeg.h STM_JPEG_MAX_DIM
+JPEG_LOOK_BITS = 9                                                          # csrc/jpeg.h STM_JPEG_LOOK_BITS
+JPEG_DECODE, JPEG_RAW = 0, 1                                                # csrc/jpeg.h STM_JPEG_DECODE / _RAW
+JPEG_ENOCODE, JPEG_EINDEX, JPEG_ESIZE, JPEG_ETRUNCATED = 1, 2, 3, 4         # csrc/jpeg.h STM_JPEG_E*
+JPEG_STAGE_ENTROPY, JPEG_STAGE_IDCT, JPEG_STAGE_COLOUR = 1, 2, 4            # csrc/jpeg.h STM_JPEG_STAGE_*
+
 
 def private_tables():
     """{header under csrc/: its table} of every package-private header."""
@@ -268,6 +281,11 @@ def dp_tables():
 def det_tables():
     """{header under csrc/: its table} of the deterministic backward's package-private header."""
     return {"det_backward.h": DET_SIGNATURES}
+
+
+def jpeg_tables():
+    """{header under csrc/: its table} of the JPEG decoder's package-private header."""
+    return {"jpeg.h": JPEG_SIGNATURES}
 
 
 _private_calls = {}   # name -> (function, argument count) for private_call()
@@ -347,6 +365,29 @@ class AugDesc(ctypes.Structure):
                 [(n, c_i) for n in ("x0", "y0", "x1", "y1", "cast_clip")])
 
 
+class JpegImage(ctypes.Structure):
+    """stm_jpeg_image of csrc/jpeg.h (package-private: its size is checked against stm_jpeg_struct_bytes(0) where it is first used and in
+    tests/test_jpeg_cpu.py, not through STRUCTS)."""
+    _fields_ = ([("out_off", c_l), ("src_off", c_l)] + [(n, ctypes.c_int32) for n in ("kind", "width", "height", "ncomp", "hs", "vs", "mcu_w", "mcu_h")] +
+                [("tq", ctypes.c_int32 * 3), ("td", ctypes.c_int32 * 3), ("ta", ctypes.c_int32 * 3)] +
+                [(n, ctypes.c_int32) for n in ("blk_first", "quad_first", "reserved")])
+
+
+class JpegSegment(ctypes.Structure):
+    """stm_jpeg_segment of csrc/jpeg.h (stm_jpeg_struct_bytes(1))."""
+    _fields_ = [("byte_off", c_l)] + [(n, ctypes.c_int32) for n in ("nbytes", "image", "mcu_first", "mcu_count")]
+
+
+class JpegHuff(ctypes.Structure):
+    """stm_jpeg_huff of csrc/jpeg.h."""
+    _fields_ = [("look", ctypes.c_uint16 * 512), ("maxcode", ctypes.c_int32 * 18), ("valoff", ctypes.c_int32 * 18), ("huffval", ctypes.c_uint8 * 256)]
+
+
+class JpegTables(ctypes.Structure):
+    """stm_jpeg_tables of csrc/jpeg.h (stm_jpeg_struct_bytes(2))."""
+    _fields_ = [("quant", ctypes.c_uint16 * 64 * 4), ("huff", JpegHuff * 4)]
+
+
 class FoldRow(ctypes.Structure):
     """stm_fold_row of csrc/fold.h (package-private: its size is checked against stm_fold_struct_bytes(0) where it is first used and in
     tests/test_validate_cpu.py, not through STRUCTS)."""
@@ -416,12 +457,12 @@ def call(name, *args):
 
 
 def private_call(name, *args):
-    """call() for an entry of PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES, DP_SIGNATURES or DET_SIGNATURES: restype / argtypes are set from
-    the table when the entry is first used."""
+    """call() for an entry of PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES, DP_SIGNATURES, DET_SIGNATURES or JPEG_SIGNATURES: restype /
+    argtypes are set from the table when the entry is first used."""
     got = _private_calls.get(name)
     if got is None:
-        ret, params = next(table[name] for table in (PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES, DP_SIGNATURES, DET_SIGNATURES)
-                           if name in table)
+        ret, params = next(table[name] for table in (PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES, DP_SIGNATURES, DET_SIGNATURES,
+                                                              JPEG_SIGNATURES) if name in table)
         fn = getattr(lib(), name, None)
         if fn is None:
             raise StmError(f"{LIB_PATH} lacks {name}: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")

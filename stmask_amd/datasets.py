@@ -15,6 +15,10 @@ proposals, keep_ratio=True, more than one img_scale.  One rank's share of a batc
 
 YTVISValSet / LazyVideo at the end of the file are the test-mode half: the videos of a validation split in the form
 serve.VideoBatcher.run takes, every frame read when the batcher asks for it.
+
+decode="device" (YTVISTrainSet, YTVISValSet; the default is "host") leaves the frames in their files' bytes (jpeg.CompressedFrame) and has the
+MI355X decode them: collate_device through jpeg.decode_batch in the place of upload_frames, the batcher through jpeg.compressed_prep
+(INTEGRATION.md section 26).  Records, random draws and every other launch are those of "host".
 """
 import ctypes
 import os
@@ -25,6 +29,7 @@ import torch
 
 from . import _lib, vis_eval
 from . import extra_aug as _extra_aug
+from . import jpeg as _jpeg
 from ._lib import StmError, c_p, call, private_call
 from .extra_aug import AugParams, ExtraAugmentation  # noqa: F401  (part of this module's interface)
 from .preprocess import MEANS, STD
@@ -255,6 +260,17 @@ class BatchStatus:
         vis_eval.raise_for_status(self.host.numpy(), self.pos, self.who)
 
 
+class JoinedStatus:
+    """The statuses of one batch (the frames' decode, the masks) behind one raise_if_bad(), looked at in the order given."""
+
+    def __init__(self, *parts):
+        self.parts = parts
+
+    def raise_if_bad(self):
+        for p in self.parts:
+            p.raise_if_bad()
+
+
 class GroundTruth:
     """render_ground_truth's result.  masks uint8 [n, Hp, Wp], boxes fp32 [n, 4] (None without boxes), extra int64 [k, n] (the rows handed in),
     area int64 [n] and n_runs int32 [n] in the lists' order (list of mask i: pos[i]), status: a BatchStatus; uploaded: the buffers the launches
@@ -384,10 +400,18 @@ class YTVISTrainSet:
     extra_aug: None, or the reference's dict(photo_metric_distortion=..., expand=..., random_crop=...) (or an ExtraAugmentation).  With None every
     record and every random draw is what it is without the argument.  With a dict the frames are read first, frame 0's augmentation is drawn,
     then frame 1's, THEN the clip's one flip (datasets/ytvos.py:243-248); the record gains aug = [AugParams, AugParams] and its bboxes / labels /
-    obj_ids / segms are what the augmentation left.  The pixels are augmented on the device by collate_device."""
+    obj_ids / segms are what the augmentation left.  The pixels are augmented on the device by collate_device.
+    decode: "host" (frame_reader returns pixels; read_frame by default) or "device": frame_reader returns jpeg.CompressedFrames
+    (jpeg.read_compressed by default), `frames` holds them, the sizes come from their headers and collate_device has the device decode them; every
+    other field of the record and every random draw is that of "host"."""
 
     def __init__(self, ann, img_prefix=None, frame_reader=None, img_scale=(640, 360), size_divisor=32, flip_ratio=0.5, clip_frames=1, to_rgb=True,
-                 mean=MEANS, std=STD, extra_aug=None, crop_boxes="reference", cast="reference"):
+                 mean=MEANS, std=STD, extra_aug=None, crop_boxes="reference", cast="reference", decode="host"):
+        if decode not in ("host", "device"):
+            raise ValueError(f"YTVISTrainSet: decode={decode!r}")
+        self.decode = decode
+        if frame_reader is None and decode == "device":
+            frame_reader = _jpeg.read_compressed
         data = vis_eval._load(ann)
         self.extra_aug = _extra_aug.from_config(extra_aug, crop_boxes, cast)
         if isinstance(img_scale, list):
@@ -448,6 +472,8 @@ class YTVISTrainSet:
         for f in clip:
             name = info["file_names"][f]
             frames.append(self.frame_reader(name if self.img_prefix is None else os.path.join(self.img_prefix, name)))
+            if (self.decode == "device") != isinstance(frames[-1], _jpeg.CompressedFrame):
+                raise ValueError(f"YTVISTrainSet: decode={self.decode!r}, the frame_reader returned a {type(frames[-1]).__name__} for {name}")
         H0, W0 = int(frames[0].shape[0]), int(frames[0].shape[1])
         anns = [self.get_ann_info(vid, f) for f in clip]
         aug = None
@@ -478,7 +504,9 @@ def collate_device(records, device=None, max_gt=None, check="raise"):
     view into one buffer per kind.  max_gt keeps the first max_gt objects of a frame.  One upload each for the frames (pinned staging), the run
     lists, the descriptors (labels and ids ride along) and the boxes; at most 64 frames take 4 launches, plus one when a mask arrives as a
     compressed string.  Records that carry aug (YTVISTrainSet(extra_aug=...)) are augmented inside those same launches: one more upload (the
-    descriptors), no more launches; records with and without aug may not be mixed.  A flagged mask raises ValueError naming the video id, annotation id and frame: check="raise" waits for the status words
+    descriptors), no more launches; records with and without aug may not be mixed.  Records of YTVISTrainSet(decode="device") carry
+    jpeg.CompressedFrames: jpeg.decode_batch (one upload, at most three launches) takes the place of the frames' upload, its status joins the
+    batch's, and nothing else changes; compressed and decoded frames may not be mixed.  A flagged mask raises ValueError naming the video id, annotation id and frame: check="raise" waits for the status words
     here; check="deferred" appends a BatchStatus to the tuple whose .raise_if_bad() the caller invokes a step later, so the call itself never
     waits for the device."""
     if check not in ("raise", "deferred"):
@@ -516,8 +544,17 @@ def collate_device(records, device=None, max_gt=None, check="raise"):
             labels.append(r["labels"][t][:g])
             ids.append(np.asarray(r["obj_ids"][t][:g], dtype=np.int64))
     who = lambda i: "video %s, annotation %s, frame %s" % names[i]      # noqa: E731
+    compressed = isinstance(frames[0], _jpeg.CompressedFrame)
+    if any(isinstance(f, _jpeg.CompressedFrame) != compressed for f in frames):
+        raise StmError("collate_device: compressed and decoded frames in one batch")
+    decode_status = None
     with torch.cuda.device(device):
-        dev_frames = upload_frames(frames, device)
+        if compressed:
+            f_names = ["video %s, frame %s%s" % (r["video_id"], r["frame_ids"][t], f" ({f.name})" if f.name else "")
+                       for r in records for t, f in enumerate(r["frames"])]
+            dev_frames, decode_status = _jpeg.decode_batch(frames, device, order="bgr", names=f_names, check="deferred")
+        else:
+            dev_frames = upload_frames(frames, device)
         block = upload_aug(dev_frames, f_flips, params, frame_of, device) if augmented else None
         images = train_frames(dev_frames, f_flips, r0["img_scale"], r0["size_divisor"], r0["mean"], r0["std"], r0["to_rgb"], aug=block)
         gt = render_ground_truth(rles, sizes, flips, np.concatenate(boxes).reshape(-1, 4), (np.concatenate(labels), np.concatenate(ids)),
@@ -526,9 +563,10 @@ def collate_device(records, device=None, max_gt=None, check="raise"):
     per = lambda t: [[t[edges[2 * c + k]:edges[2 * c + k + 1]] for k in range(2)] for c in range(len(records))]   # noqa: E731
     out = (images.view(len(records), 2, *images.shape[1:]), per(gt.boxes), per(gt.extra[0]), per(gt.masks), per(gt.extra[1]),
            [r["img_meta"] for r in records])
+    status = gt.status if decode_status is None else JoinedStatus(decode_status, gt.status)
     if check == "deferred":
-        return out + (gt.status,)
-    gt.status.raise_if_bad()
+        return out + (status,)
+    status.raise_if_bad()
     return out
 
 
@@ -623,7 +661,9 @@ class LazyVideo:
     """One video of a YTVISValSet in the form serve.VideoBatcher.run indexes: .shape is (T, H, W, 3) from the annotation, video[t] is frame t as a
     uint8 [H, W, 3] tensor (pinned when there is a GPU), read when first asked for and dropped once `keep` later frames of the video have been
     asked for (a frame asked for again after that is read again).  With a pool, asking for frame t also starts the reads of the next
-    `read_ahead` frames, in the video's own order."""
+    `read_ahead` frames, in the video's own order.  A frame_reader that returns a jpeg.CompressedFrame (YTVISValSet(decode="device")) has
+    video[t] return it as it is: its size is checked from the header, no pixel work is done here, and the batcher's prep decodes it
+    (jpeg.compressed_prep)."""
 
     def __init__(self, names, height, width, frame_reader, keep=2, pool=None, read_ahead=0):
         self.names, self.shape = list(names), (len(names), int(height), int(width), 3)
@@ -636,6 +676,10 @@ class LazyVideo:
 
     def _read(self, t):
         a = self.frame_reader(self.names[t])
+        if isinstance(a, _jpeg.CompressedFrame):
+            if tuple(a.shape) != self.shape[1:]:
+                raise ValueError(f"{self.names[t]}: its header says {tuple(a.shape)}, the annotation says {self.shape[1:]}")
+            return a
         if tuple(a.shape) != self.shape[1:]:
             raise ValueError(f"{self.names[t]}: decoded to {tuple(a.shape)}, the annotation says {self.shape[1:]}")
         f = torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))
@@ -652,7 +696,7 @@ class LazyVideo:
         got = self._held.get(t)
         if got is None:
             got = self._read(t)
-        elif not isinstance(got, torch.Tensor):
+        elif not isinstance(got, (torch.Tensor, _jpeg.CompressedFrame)):
             got = got.result()
         self._held[t] = got
         if t not in self._asked:
@@ -667,11 +711,17 @@ class YTVISValSet:
     file order, each with id, filenames, height, width, length, with or without `annotations` (the official valid split has none).  videos() is
     the list of (video_id, LazyVideo) serve.VideoBatcher.run takes: no frame is read before the batcher asks for it, and a video holds at most
     keep + read_ahead frames.  read_ahead=k > 0: a thread pool of min(8, k) threads reads up to k frames ahead in each video's own order.
+    decode="device": the frames stay jpeg.CompressedFrames (frame_reader: jpeg.read_compressed by default) and the batcher takes
+    prep=jpeg.compressed_prep(...); read_ahead then reads file bytes ahead, not pixels.
     Not restated: several img_scales, test-time flip (commented out in the reference), proposals, clip_eval_mode."""
 
-    def __init__(self, ann, img_prefix=None, frame_reader=None, read_ahead=0):
+    def __init__(self, ann, img_prefix=None, frame_reader=None, read_ahead=0, decode="host"):
+        if decode not in ("host", "device"):
+            raise ValueError(f"YTVISValSet: decode={decode!r}")
+        self.decode = decode
         data = vis_eval._load(ann)
-        self.img_prefix, self.frame_reader, self.read_ahead = img_prefix, frame_reader or read_frame, int(read_ahead)
+        self.img_prefix, self.read_ahead = img_prefix, int(read_ahead)
+        self.frame_reader = frame_reader or (_jpeg.read_compressed if decode == "device" else read_frame)
         if self.read_ahead < 0:
             raise ValueError(f"YTVISValSet: read_ahead={read_ahead}")
         self.has_annotations = bool(data.get("annotations"))

@@ -103,7 +103,9 @@ class VideoBatcher:
     @torch.no_grad()
     def run(self, videos, out_file=None, on_frame=None):
         """-> the YouTube-VIS records (or results2json_videoseg's output when out_file is given).  on_frame(video_id, frame_id, frame_u8):
-        called per busy slot and step with its frame annotated on the device (uint8 [H, W, 3] in the frame's own channel order)."""
+        called per busy slot and step with its frame annotated on the device (uint8 [H, W, 3] in the frame's own channel order).  Not built:
+        on_frame over videos whose frames are jpeg.CompressedFrames (prep=jpeg.compressed_prep): the drawing reads the source frame's pixels,
+        which such a video does not hold; serve those without on_frame."""
         videos = list(videos)
         plan = schedule([int(v[1].shape[0]) for v in videos], self.B)
         depth = self.pipe.prefetch_depth if self.lookahead is None else int(self.lookahead)
