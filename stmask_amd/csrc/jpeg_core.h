@@ -8,6 +8,8 @@
  *   - h2v1: edge samples copied, elsewhere (3 c + prev + 1) >> 2 and (3 c + next + 2) >> 2;
  *   - h2v2: column sums t = 3 cur + neighbour row (the row above for the upper output row, the row below for the lower, both replicated at the
  *     first and last real chroma row), then (3 t + last + 8) >> 4 and (3 t + next + 7) >> 4, the edges (4 t + 8) >> 4 and (4 t + 7) >> 4;
+ *   - a chroma plane of one or two real columns (dw <= 2) is not interpolated at all: libjpeg (jdsample.c) chooses fancy upsampling only when
+ *     downsampled_width > 2 and replicates the sample otherwise, row[xo >> 1] for h2v1 and p[yo >> 1][xo >> 1] for h2v2 (vertically too);
  *   - YCbCr: R = Y + ((91881 Cr' + 32768) >> 16), B = Y + ((116130 Cb' + 32768) >> 16), G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16).
  * The transform's sums are formed in uint32_t, whose wrap-around is defined: coefficients no encoder writes (a damaged file) cannot overflow a
  * signed integer, and the values of a sound file are the same in either arithmetic.  Right shifts of negative values are arithmetic. */
@@ -236,6 +238,7 @@ JPEG_HD int jpeg_sample(int32_t v)
 JPEG_HD int jpeg_h2v1(const uint8_t* row, int dw, int xo)
 {
     const int cx = xo >> 1, c = row[cx];
+    if (dw <= 2) return c;
     if (xo & 1) return cx == dw - 1 ? c : (3 * c + row[cx + 1] + 2) >> 2;
     return cx == 0 ? c : (3 * c + row[cx - 1] + 1) >> 2;
 }
@@ -244,6 +247,7 @@ JPEG_HD int jpeg_h2v1(const uint8_t* row, int dw, int xo)
 JPEG_HD int jpeg_h2v2(const uint8_t* p, int pw, int dw, int dh, int xo, int yo)
 {
     const int cy = yo >> 1, cx = xo >> 1;
+    if (dw <= 2) return p[(int64_t)cy * pw + cx];
     const int ny = (yo & 1) ? (cy + 1 < dh ? cy + 1 : dh - 1) : (cy > 0 ? cy - 1 : 0);
     const uint8_t* cur = p + (int64_t)cy * pw;
     const uint8_t* nb = p + (int64_t)ny * pw;

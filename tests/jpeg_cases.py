@@ -40,6 +40,26 @@ def by_name(name):
     return next(c for c in load()[0] if c.name == name)
 
 
+EDGE_GROUPS = ("narrow", "layout", "tables", "magnitudes", "staging", "extent")
+
+
+@functools.lru_cache(maxsize=None)
+def load_edge():
+    """The edge fixtures (tests/golden/jpeg_edge_cases.npz, written by tests/golden/gen_jpeg_edge_cases.py): files PIL's encoder does not
+    write, or the grid does not reach, each with PIL's RGB -> [Case]; a name starts with its group, one of EDGE_GROUPS.  Shared: do not write."""
+    z = np.load(os.path.join(HERE, "golden", "jpeg_edge_cases.npz"))
+    cases = []
+    for i, n in enumerate(str(n) for n in z["names"]):
+        rgb = z[f"rgb_{i}"]
+        rgb.setflags(write=False)
+        cases.append(Case(n, z[f"data_{i}"].tobytes(), rgb))
+    return cases
+
+
+def edge_by_name(name):
+    return next(c for c in load_edge() if c.name == name)
+
+
 def damaged():
     """The damaged files: three fixtures cut at 25 %, 50 % and 99 % of their entropy-coded bytes and with one byte inverted at five seeded
     positions -> [Case]; .rgb is PIL's decode of the damaged bytes, or None where PIL refuses them."""

@@ -1,5 +1,5 @@
 """The JPEG decoder on the MI355X (stmask_amd/jpeg.py, csrc/jpeg_decode.hip) against PIL's pixels: every fixture of tests/golden/jpeg_cases.npz
-bit for bit, singly and in one mixed batch, both channel orders; the host fallback; damaged files beside sound ones; no host wait in deferred
+and of tests/golden/jpeg_edge_cases.npz bit for bit, singly and in one mixed batch, both channel orders; the host fallback; damaged files beside sound ones; no host wait in deferred
 mode; the launch and upload counts; and the places it plugs into (collate_device, serve.device_prep) against the host-decoded path."""
 import io
 import random
@@ -14,6 +14,7 @@ from stmask_amd import datasets, jpeg, serve
 
 pytestmark = pytest.mark.gpu
 GRID, UNSUPPORTED, DAMAGED = JC.load()
+EDGE = JC.load_edge()
 
 
 def _want(c, order):
@@ -43,6 +44,47 @@ def test_all_fixtures_in_one_mixed_batch(order):
     assert 0 < jpeg.COUNTERS["h2d_bytes"] < 4 * sum(len(c.data) for c in GRID)
     base = frames[0].untyped_storage().data_ptr()
     assert all(f.untyped_storage().data_ptr() == base for f in frames)                 # views of ONE buffer
+
+
+def test_every_edge_fixture_singly():
+    """Narrow chroma planes, header layouts, table selections, the largest magnitudes, the staging window's offsets, 8192-pixel sides: each file
+    alone, so that a failure names it."""
+    jpeg.reset_counters()
+    for c in EDGE:
+        _assert_frames(jpeg.decode_batch([c.data], order="rgb", names=[c.name]), [c], "rgb")
+    assert jpeg.COUNTERS["host_fallback"] == 0 and jpeg.COUNTERS["uploads"] == len(EDGE) and jpeg.COUNTERS["launches"] == 3 * len(EDGE)
+
+
+@pytest.mark.parametrize("order", ["rgb", "bgr"])
+@pytest.mark.parametrize("first", ["grid", "edge"])
+def test_edge_fixtures_and_the_grid_in_one_batch(order, first):
+    cases = GRID + EDGE if first == "grid" else EDGE + GRID
+    jpeg.reset_counters()
+    _assert_frames(jpeg.decode_batch([c.data for c in cases], order=order), cases, order)
+    assert jpeg.COUNTERS == {"launches": 3, "uploads": 1, "h2d_bytes": jpeg.COUNTERS["h2d_bytes"], "host_fallback": 0}
+
+
+def test_a_1024_segment_file_between_two_one_pixel_frames():
+    """One wave a restart interval: 1024 workgroups of one image between images of one block, and the restart counter wraps 128 times."""
+    long = next(c for c in EDGE if c.name.endswith("_grey_rst1"))
+    assert len(jpeg.parse(long.data).segments) == 1024
+    cases = [JC.by_name("1x1_420_q90"), long, JC.by_name("1x1_grey_q30opt")]
+    for order in ("rgb", "bgr"):
+        jpeg.reset_counters()
+        _assert_frames(jpeg.decode_batch([c.data for c in cases], order=order), cases, order)
+        assert jpeg.COUNTERS["launches"] == 3 and jpeg.COUNTERS["uploads"] == 1 and jpeg.COUNTERS["host_fallback"] == 0
+
+
+def test_host_decoded_frames_first_last_and_side_by_side():
+    """Images without blocks or segments share their first block index with the image behind them: the lookups must pass over them wherever
+    they stand."""
+    pytest.importorskip("PIL.Image")
+    u, v = UNSUPPORTED
+    a, b, c = JC.edge_by_name("narrow_3x9_420"), JC.by_name("33x31_422_q75rst3"), JC.edge_by_name("tables_three_selections")
+    for cases in ([u, a, b, c], [a, b, c, u], [a, u, v, b, c], [u, v, a, b, v, u, c, u, v], [v, u, u, a]):
+        jpeg.reset_counters()
+        _assert_frames(jpeg.decode_batch([x.data for x in cases], order="rgb"), cases, "rgb")
+        assert jpeg.COUNTERS["host_fallback"] == sum(x in UNSUPPORTED for x in cases) and jpeg.COUNTERS["uploads"] == 1 and jpeg.COUNTERS["launches"] == 3
 
 
 def test_sixty_five_tiny_frames_in_one_batch():
