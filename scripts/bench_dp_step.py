@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The finish of a data-parallel step (optim.DataParallelSGD.step, csrc/dp_step.hip: average, step and clear the gradient arena in one pass)
+"""The finish of a data-parallel step (optim.DataParallelSGD.step, csrc/optim.hip: average, step and clear the gradient arena in one pass)
 against what the single-process loop does for the same work -- optim.GuardedSGD.step plus a memset of the gradients -- and, where the machine
 has two GPUs or more, the scaling of a synthetic-batch training loop:   python scripts/bench_dp_step.py [--out profiles/bench_dp_step.txt]
 

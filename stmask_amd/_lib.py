@@ -209,42 +209,33 @@ HEADERS = {
     "stmask_hip_data.h": DATA_SIGNATURES,
 }
 
-# Package-private entry points of the same library: declared in csrc/optim.h, not under include/, so HEADERS, all_signatures() and ABI_VERSION do
-# not count them (an optimizer step is nothing a C client of the drop-in boundary calls).  private_call() binds them on first use.
-PRIVATE_SIGNATURES = {
+# Package-private entry points of the same library: declared in headers under csrc/, not under include/, so HEADERS, all_signatures() and
+# ABI_VERSION do not count them (an optimizer step is nothing a C client of the drop-in boundary calls).  One table per header, listed in
+# PRIVATE_HEADERS below; private_call() binds an entry on first use, so a library without, say, the optimizer still serves inference.
+PRIVATE_SIGNATURES = {   # csrc/optim.h: the guarded SGD step of the training loop (optim.py)
     "stm_sgd_step_multi_f32": ("i", "ppppipppifffp"),
     "stm_grads_nonfinite_multi_f32": ("i", "ppipip"),
 }
-# ... and those of csrc/extra_aug.h: ExtraAugmentation inside the training-batch kernels (datasets.py).  A second private table, so that
-# PRIVATE_SIGNATURES stays the restatement of csrc/optim.h alone; private_call() resolves both.
-AUG_SIGNATURES = {
+AUG_SIGNATURES = {       # csrc/extra_aug.h: ExtraAugmentation inside the training-batch kernels (datasets.py)
     "stm_aug_struct_bytes": ("z", "i"),
     "stm_aug_frames_u8_f32": ("i", "ppipiiiippip"),
     "stm_aug_masks_u8": ("i", "pppipppiilpiiiip"),
     "stm_aug_source_u8": ("i", "pppp"),
 }
-PRIVATE_TABLES = {"optim.h": PRIVATE_SIGNATURES, "extra_aug.h": AUG_SIGNATURES}   # header under csrc/ -> its table
 AUG_FRAMES_PER_LAUNCH = 64   # csrc/extra_aug.h STM_AUG_FRAMES_PER_LAUNCH
-# ... and those of csrc/fold.h: the parameter write of the inference twin (validate.py).  A third private table, kept beside PRIVATE_TABLES (which
-# stays the pair of the training loop's headers); private_tables() is all three, which is what private_call() and build() walk.
-FOLD_SIGNATURES = {
+FOLD_SIGNATURES = {      # csrc/fold.h: the parameter write of the inference twin (validate.py)
     "stm_fold_struct_bytes": ("z", "i"),
     "stm_fold_rows_f32": ("i", "pip"),
 }
 FOLD_MAX_ROWS = 64   # csrc/fold.h STM_FOLD_MAX_ROWS
 FOLD_CHUNK = 4096    # csrc/fold.h STM_FOLD_CHUNK
 FOLD_COPY, FOLD_WEIGHT, FOLD_BIAS = 0, 1, 2   # csrc/fold.h STM_FOLD_COPY / _WEIGHT / _BIAS
-# ... and that of csrc/dp_step.h: the finish of a data-parallel training step (optim.py DataParallelSGD).  A fourth private table, kept beside
-# the three above (private_tables() stays what the training loop and the twin bind); dp_tables() lists it, private_call() resolves it and
-# build() walks it too.
-DP_SIGNATURES = {
+DP_SIGNATURES = {        # csrc/dp_step.h: the finish of a data-parallel training step (optim.py DataParallelSGD)
     "stm_dp_sgd_finish_multi_f32": ("i", "ppppipppiffffp"),
 }
-DP_MAX_TENSORS = 64   # csrc/dp_step.h STM_DP_MAX_TENSORS
-DP_CHUNK = 4096       # csrc/dp_step.h STM_DP_CHUNK
-# ... and those of csrc/det_backward.h: the deterministic mode of the training backward (autograd.set_deterministic).  A fifth private table, kept
-# beside the four above; det_tables() lists it, private_call() resolves it and build() walks it too.
-DET_SIGNATURES = {
+DP_MAX_TENSORS = 64   # csrc/dp_step.h STM_DP_MAX_TENSORS and csrc/optim.h STM_OPTIM_MAX_TENSORS (optim.MAX_TENSORS is this name)
+DP_CHUNK = 4096       # csrc/dp_step.h STM_DP_CHUNK and csrc/optim.h STM_OPTIM_CHUNK (optim.CHUNK is this name)
+DET_SIGNATURES = {       # csrc/det_backward.h: the deterministic mode of the training backward (autograd.set_deterministic)
     "stm_det_exponent": ("i", "iillppp"),
     "stm_det_workspace_bytes": ("z", "l"),
     "stm_deform_col2im_det_f32": ("i", "pplplipppzp"),
@@ -253,10 +244,7 @@ DET_SIGNATURES = {
 }
 DET_MIN_BITS = 36                                     # csrc/det_accum.h STM_DET_MIN_BITS
 DET_FINITE, DET_ZERO, DET_NONFINITE = 0, 1, 2         # csrc/det_accum.h STM_DET_FINITE / _ZERO / _NONFINITE
-
-# ... and those of csrc/jpeg.h: baseline JPEG frames decoded on the device (jpeg.py decode_batch).  A sixth private table, kept beside the five
-# above; jpeg_tables() lists it, private_call() resolves it and build() walks it too.
-JPEG_SIGNATURES = {
+JPEG_SIGNATURES = {      # csrc/jpeg.h: baseline JPEG frames decoded on the device (jpeg.py decode_batch)
     "stm_jpeg_struct_bytes": ("z", "i"),
     "stm_jpeg_workspace_bytes": ("z", "pi"),
     "stm_jpeg_decode_u8": ("i", "pipipzzzpzppziip"),
@@ -266,29 +254,19 @@ JPEG_LOOK_BITS = 9                                                          # cs
 JPEG_DECODE, JPEG_RAW = 0, 1                                                # csrc/jpeg.h STM_JPEG_DECODE / _RAW
 JPEG_ENOCODE, JPEG_EINDEX, JPEG_ESIZE, JPEG_ETRUNCATED = 1, 2, 3, 4         # csrc/jpeg.h STM_JPEG_E*
 JPEG_STAGE_ENTROPY, JPEG_STAGE_IDCT, JPEG_STAGE_COLOUR = 1, 2, 4            # csrc/jpeg.h STM_JPEG_STAGE_*
+# The private counterpart of HEADERS: every package-private header of csrc/ and the table that restates it, in the order they were added.
+# private_fn() / private_call(), __graft_entry__.build() and tests/test_abi_private.py walk this mapping.  A new header takes its table, an entry
+# here and a row in EXPECTED of tests/test_abi_private.py; structs that cross the boundary also take their mirrors in PRIVATE_STRUCTS below.
+PRIVATE_HEADERS = {
+    "optim.h": PRIVATE_SIGNATURES,
+    "extra_aug.h": AUG_SIGNATURES,
+    "fold.h": FOLD_SIGNATURES,
+    "dp_step.h": DP_SIGNATURES,
+    "det_backward.h": DET_SIGNATURES,
+    "jpeg.h": JPEG_SIGNATURES,
+}
 
-
-def private_tables():
-    """{header under csrc/: its table} of every package-private header."""
-    return {**PRIVATE_TABLES, "fold.h": FOLD_SIGNATURES}
-
-
-def dp_tables():
-    """{header under csrc/: its table} of the data-parallel step's package-private header."""
-    return {"dp_step.h": DP_SIGNATURES}
-
-
-def det_tables():
-    """{header under csrc/: its table} of the deterministic backward's package-private header."""
-    return {"det_backward.h": DET_SIGNATURES}
-
-
-def jpeg_tables():
-    """{header under csrc/: its table} of the JPEG decoder's package-private header."""
-    return {"jpeg.h": JPEG_SIGNATURES}
-
-
-_private_calls = {}   # name -> (function, argument count) for private_call()
+_private_calls = {}   # name -> (function, argument count) for private_call(); private_fn() fills it
 
 
 def all_signatures():
@@ -357,8 +335,7 @@ class HeadLayout(ctypes.Structure):
 
 
 class AugDesc(ctypes.Structure):
-    """stm_aug_desc of csrc/extra_aug.h (package-private: its size is checked against stm_aug_struct_bytes(0) where it is first used and in
-    tests/test_extra_aug_cpu.py, not through STRUCTS)."""
+    """stm_aug_desc of csrc/extra_aug.h (package-private: PRIVATE_STRUCTS, not STRUCTS)."""
     _fields_ = ([("ptr", c_p), ("row_stride_bytes", c_l), ("H0", c_i), ("W0", c_i), ("flip", c_i), ("photo", c_i)] +
                 [(n, c_f) for n in ("delta", "alpha_pre", "saturation", "hue", "alpha_post")] + [("perm", c_i * 3)] +
                 [(n, c_i) for n in ("Hc", "Wc", "top", "left")] + [("fill", c_f * 3)] +
@@ -366,8 +343,7 @@ class AugDesc(ctypes.Structure):
 
 
 class JpegImage(ctypes.Structure):
-    """stm_jpeg_image of csrc/jpeg.h (package-private: its size is checked against stm_jpeg_struct_bytes(0) where it is first used and in
-    tests/test_jpeg_cpu.py, not through STRUCTS)."""
+    """stm_jpeg_image of csrc/jpeg.h (package-private: PRIVATE_STRUCTS, not STRUCTS)."""
     _fields_ = ([("out_off", c_l), ("src_off", c_l)] + [(n, ctypes.c_int32) for n in ("kind", "width", "height", "ncomp", "hs", "vs", "mcu_w", "mcu_h")] +
                 [("tq", ctypes.c_int32 * 3), ("td", ctypes.c_int32 * 3), ("ta", ctypes.c_int32 * 3)] +
                 [(n, ctypes.c_int32) for n in ("blk_first", "quad_first", "reserved")])
@@ -389,8 +365,7 @@ class JpegTables(ctypes.Structure):
 
 
 class FoldRow(ctypes.Structure):
-    """stm_fold_row of csrc/fold.h (package-private: its size is checked against stm_fold_struct_bytes(0) where it is first used and in
-    tests/test_validate_cpu.py, not through STRUCTS)."""
+    """stm_fold_row of csrc/fold.h (package-private: PRIVATE_STRUCTS, not STRUCTS)."""
     _fields_ = [(n, c_p) for n in ("dst", "src", "gamma", "beta", "mean", "var")] + [("numel", c_l), ("inner", c_l), ("kind", c_i), ("eps", c_f)]
 
 
@@ -399,6 +374,12 @@ STRUCTS = {
     "stm_struct_bytes": [DeformGeom, ConvGeom, ConvWindow, HeadLayout, FrameDesc, RenderFrame],
     "stm_output_struct_bytes": [OutputFrame, OutputRow, OutputHeader],
     "stm_data_struct_bytes": [DataFrameDesc, DataMaskDesc],
+}
+# ... and of the package-private headers: private_fn() checks a header's mirrors the first time it binds any of the header's entries
+PRIVATE_STRUCTS = {
+    "stm_aug_struct_bytes": [AugDesc],
+    "stm_fold_struct_bytes": [FoldRow],
+    "stm_jpeg_struct_bytes": [JpegImage, JpegSegment, JpegTables],
 }
 
 
@@ -456,19 +437,31 @@ def call(name, *args):
         check(rc, name)
 
 
-def private_call(name, *args):
-    """call() for an entry of PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES, DP_SIGNATURES, DET_SIGNATURES or JPEG_SIGNATURES: restype /
-    argtypes are set from the table when the entry is first used."""
+def private_fn(name):
+    """The entry `name` of a table of PRIVATE_HEADERS, bound on first use: restype / argtypes are set from the table then, after the mirrors of
+    the header's structs (PRIVATE_STRUCTS) have been held against the library's sizes."""
     got = _private_calls.get(name)
     if got is None:
-        ret, params = next(table[name] for table in (PRIVATE_SIGNATURES, AUG_SIGNATURES, FOLD_SIGNATURES, DP_SIGNATURES, DET_SIGNATURES,
-                                                              JPEG_SIGNATURES) if name in table)
+        table = next(t for t in PRIVATE_HEADERS.values() if name in t)
+        for size_fn in PRIVATE_STRUCTS.keys() & table.keys() - {name}:
+            private_fn(size_fn)
         fn = getattr(lib(), name, None)
         if fn is None:
             raise StmError(f"{LIB_PATH} lacks {name}: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")
+        ret, params = table[name]
         fn.restype, fn.argtypes = _KINDS[ret], [_KINDS[k] for k in params]
+        for i, mirror in enumerate(PRIVATE_STRUCTS.get(name, ())):
+            if fn(i) != ctypes.sizeof(mirror):
+                raise StmError(f"{LIB_PATH}: struct {i} of {name} has {fn(i)} bytes, this binding's mirror {mirror.__name__} "
+                               f"{ctypes.sizeof(mirror)}: rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")
         got = _private_calls[name] = (fn, len(params))
-    fn, n = got
+    return got[0]
+
+
+def private_call(name, *args):
+    """call() for an entry of a table of PRIVATE_HEADERS."""
+    fn = private_fn(name)
+    n = _private_calls[name][1]
     if len(args) != n:
         raise StmError(f"{name} takes {n} arguments, got {len(args)}")
     rc = fn(*args)

@@ -17,14 +17,6 @@ namespace {
 constexpr int AUG_MASK_ROWS = 16;      // as TD_MASK_ROWS / TD_LANE_PX of train_data.hip
 constexpr int AUG_LANE_PX = 4;
 
-// cv2 resizeNN: the source index of destination index d on an axis resized from `src` to `dst` (include/stmask_hip_data.h states the rule)
-__device__ __forceinline__ int aug_nearest(int d, int src, int dst)
-{
-    const double inv = (double)dst / (double)src;
-    const double ifx = 1.0 / inv;
-    return min((int)floor((double)d * ifx), src - 1);
-}
-
 __device__ __forceinline__ float sel4(int i, float t0, float t1, float t2, float t3)
 {
     return i == 0 ? t0 : i == 1 ? t1 : i == 2 ? t2 : t3;
@@ -102,7 +94,7 @@ __device__ __forceinline__ unsigned char aug_cast(float x, int clip)
 __device__ __forceinline__ uchar3 aug_byte(const stm_aug_desc& d, int sy, int sx)
 {
     if (sx < d.x0 || sx >= d.x1 || sy < d.y0 || sy >= d.y1) return make_uchar3(0, 0, 0);
-    const int cy = aug_nearest(sy, d.Hc, d.H0) - d.top, cx = aug_nearest(sx, d.Wc, d.W0) - d.left;
+    const int cy = resize_nearest(sy, d.Hc, d.H0) - d.top, cx = resize_nearest(sx, d.Wc, d.W0) - d.left;
     float b = d.fill[0], g = d.fill[1], r = d.fill[2];
     if (cy >= 0 && cy < d.H0 && cx >= 0 && cx < d.W0) {
         const uint8_t* px = d.ptr + (int64_t)cy * d.row_stride_bytes + 3 * cx;
@@ -156,13 +148,6 @@ __global__ __launch_bounds__(256) void aug_frames_kernel(const stm_aug_desc* __r
     out[at + 2 * plane] = o2;
 }
 
-// a mask's slot [c0, c1) of a buffer of `total` elements, never outside it whatever the offsets hold (td_slot of train_data.hip)
-__device__ __forceinline__ void aug_slot(const int64_t* off, int64_t i, int64_t total, int64_t& c0, int64_t& c1)
-{
-    c0 = min(max(off[i], (int64_t)0), total);
-    c1 = min(max(off[i + 1], c0), total);
-}
-
 // grid (n, ceil(Hp / 16), ceil(Wp / 256)), block 64: data_masks_kernel's walk (lanes along x, four output pixels each, 16 rows; the first live
 // row of a column finds its run by binary search, the rows below move a cursor) with the augmentation's maps between the target pixel and the
 // lookup.  Both maps are non-decreasing in y, so for a fixed column the source index k still rises over the rows that land on the source.
@@ -183,7 +168,7 @@ __global__ __launch_bounds__(STM_WAVE) void aug_masks_kernel(const unsigned int*
     const bool listed = d.list >= 0 && d.list < n_lists;
     const int m = listed ? d.list : 0;
     int64_t c0, c1;
-    aug_slot(off, m, total, c0, c1);
+    stm_slot(off, m, total, c0, c1);
     const int nr = listed ? (int)min((int64_t)max(n_runs[m], 0), min(c1 - c0, (int64_t)INT_MAX)) : 0;
     const bool live = framed && nr > 0 && d.H0 > 0 && d.W0 > 0 && a.Hc > 0 && a.Wc > 0;
     const unsigned int* __restrict__ st = starts + c0;
@@ -197,8 +182,8 @@ __global__ __launch_bounds__(STM_WAVE) void aug_masks_kernel(const unsigned int*
         bool ok = live && x < w;
         int cx = 0;
         if (ok) {
-            const int ax = aug_nearest(d.flip ? w - 1 - x : x, d.W0, w);             // the augmented image's column
-            cx = aug_nearest(ax, a.Wc, d.W0) - a.left;                               // the source's
+            const int ax = resize_nearest(d.flip ? w - 1 - x : x, d.W0, w);             // the augmented image's column
+            cx = resize_nearest(ax, a.Wc, d.W0) - a.left;                               // the source's
             ok = ax >= a.x0 && ax < a.x1 && cx >= 0 && cx < d.W0;
         }
         inside[c] = ok;
@@ -209,8 +194,8 @@ __global__ __launch_bounds__(STM_WAVE) void aug_masks_kernel(const unsigned int*
     for (int y = y_begin; y < y_end; ++y) {
         unsigned int word = 0;
         if (live && y < h) {
-            const int ay = aug_nearest(y, d.H0, h);
-            const int cy = aug_nearest(ay, a.Hc, d.H0) - a.top;
+            const int ay = resize_nearest(y, d.H0, h);
+            const int cy = resize_nearest(ay, a.Hc, d.H0) - a.top;
             if (ay >= a.y0 && ay < a.y1 && cy >= 0 && cy < d.H0) {
 #pragma unroll
                 for (int c = 0; c < AUG_LANE_PX; ++c) {

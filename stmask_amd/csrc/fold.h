@@ -26,9 +26,10 @@
 #include <stdint.h>
 
 #include "../../include/stmask_hip.h"
+#include "chunk_table.h"
 
-#define STM_FOLD_MAX_ROWS 64
-#define STM_FOLD_CHUNK 4096
+#define STM_FOLD_MAX_ROWS STM_CHUNK_MAX_ROWS
+#define STM_FOLD_CHUNK STM_CHUNK_ELEMS
 
 #define STM_FOLD_COPY 0
 #define STM_FOLD_WEIGHT 1

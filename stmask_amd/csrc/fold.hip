@@ -5,20 +5,19 @@
 //                       BatchNorm vectors (cached: a channel's four values serve `inner` elements); no LDS, no second pass.
 //
 // The table is a kernel argument (FoldTable, ~3.8 KB): six pointers a row, element counts, channel lengths and the index of each row's first chunk.
-// A workgroup owns one chunk of STM_FOLD_CHUNK elements and finds its row by a binary search over the first-chunk prefix, as csrc/optim.hip does
-// (wave-uniform: scalar loads from the kernel arguments).  The kind of a row is told by the pointers it carries (no var: copy; var and no mean:
-// weight; mean: bias), so the table needs no word for it.  The scale s = gamma / sqrt(var + eps) is recomputed whenever a thread's run of
+// A workgroup owns one chunk of STM_FOLD_CHUNK elements and finds its row as csrc/optim.hip does (chunk_table.h).  The kind of a row is told by
+// the pointers it carries (no var: copy; var and no mean: weight; mean: bias), so the table needs no word for it.  The scale s = gamma / sqrt(var + eps) is recomputed whenever a thread's run of
 // elements enters another channel: two cached loads, one sqrt and one division against a scratch buffer of scales and a pass to fill it.
 // Compiled with -ffp-contract=off and without fast-math; the division is the `/` operator and the square root sqrtf(), which hipcc expands to their
 // correctly rounded forms (HIP's __fsqrt_rn is the hardware's 1-ulp v_sqrt_f32 here: measured, one channel in ten differed): every operation is
 // rounded once, as torch's CPU kernels do.
 #include "stm_common.h"
+#include "chunk_table.h"
 #include "fold.h"
 
 namespace {
 
 constexpr int FOLD_T = STM_FOLD_MAX_ROWS;
-constexpr int FOLD_CHUNK = STM_FOLD_CHUNK;
 constexpr int FOLD_THREADS = 256;
 
 struct FoldTable {
@@ -34,18 +33,6 @@ struct FoldTable {
     int count;
 };
 static_assert(sizeof(FoldTable) + 64 < 4096, "the table travels in the kernel arguments");
-
-// the row of chunk b: the last i with first[i] <= b (rows without elements share their first chunk with the next one and are passed over)
-__device__ __forceinline__ int fold_find(const FoldTable& t, int b)
-{
-    int lo = 0, hi = t.count - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (t.first[mid] <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ float fold_scale(const float* __restrict__ gamma, const float* __restrict__ var, int c, float eps)
 {
@@ -108,10 +95,8 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_rows_kernel(const FoldTable
 {
     const int b = blockIdx.x;
     if (b >= total_chunks) return;
-    const int ti = fold_find(t, b);
-    const int e0 = (b - t.first[ti]) * FOLD_CHUNK;           // < n < 2^31
-    const int left = t.n[ti] - e0;
-    const int cnt = left < FOLD_CHUNK ? left : FOLD_CHUNK;
+    int e0, cnt;                                             // e0 < n < 2^31
+    const int ti = stm_chunk_of(t, b, e0, cnt);
     float* dst = t.dst[ti] + e0;
     const float* src = t.src[ti] ? t.src[ti] + e0 : nullptr;
     const float* var = t.var[ti];
@@ -184,9 +169,8 @@ extern "C" int stm_fold_rows_f32(const stm_fold_row* rows, int count, stm_stream
             t.mean[k] = bias ? r.mean : nullptr;
             t.n[k] = (int)r.numel;
             t.inner[k] = fold && r.numel > 0 ? (int)r.inner : 1;
-            t.first[k] = (int)chunks;
-            chunks += (r.numel + FOLD_CHUNK - 1) / FOLD_CHUNK;
-            STM_REQUIRE(chunks < ((int64_t)1 << 31), STM_EUNSUPPORTED, "%s: 2^31 chunks of %d elements or more in one call", who, FOLD_CHUNK);
+            const int rc = stm_chunk_append(who, t.first, k, r.numel, chunks);
+            if (rc) return rc;
         }
         t.count = end - begin;
         begin = end;

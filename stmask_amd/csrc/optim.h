@@ -13,9 +13,10 @@
 #include <stdint.h>
 
 #include "../../include/stmask_hip.h"
+#include "chunk_table.h"
 
-#define STM_OPTIM_MAX_TENSORS 64
-#define STM_OPTIM_CHUNK 4096
+#define STM_OPTIM_MAX_TENSORS STM_CHUNK_MAX_ROWS
+#define STM_OPTIM_CHUNK STM_CHUNK_ELEMS
 
 #ifdef __cplusplus
 extern "C" {

@@ -21,6 +21,14 @@ __device__ __forceinline__ void resize_coeffs(int src, int dst, int d, bool clam
     c1 = min(max(a1, -32768), 32767);
 }
 
+// cv2 resizeNN: the source index of destination index d on an axis resized from `src` to `dst` (include/stmask_hip_data.h states the rule)
+__device__ __forceinline__ int resize_nearest(int d, int src, int dst)
+{
+    const double inv = (double)dst / (double)src;
+    const double ifx = 1.0 / inv;
+    return min((int)floor((double)d * ifx), src - 1);
+}
+
 // One output pixel (x, y) < (w, h) of an image whose source rows start at `img` with `row_stride` bytes between rows (3 bytes per pixel):
 // the fixed-point bilinear taps, then the mode's normalisation in double.  mean / stdv are indexed by the SOURCE channel c, as o is.
 __device__ __forceinline__ void preprocess_pixel(const uint8_t* __restrict__ img, int64_t row_stride, int H0, int W0, int h, int w, int x, int y,

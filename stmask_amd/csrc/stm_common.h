@@ -305,6 +305,29 @@ __device__ __forceinline__ int stm_wave_sum_rows(unsigned row_sums)
     return (int)row_sums;
 #endif
 }
+// the sum of a 64-bit integer over the wave, in every lane
+__device__ __forceinline__ long long stm_wave_sum_i64(long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, STM_WAVE);
+    return v;
+}
+// inclusive prefix sum over the lanes of a wave (wrapping unsigned arithmetic: the sums of a run list that fails its checks are garbage, not undefined)
+__device__ __forceinline__ unsigned long long stm_wave_scan_u64(unsigned long long v, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < STM_WAVE; o <<= 1) {
+        const unsigned long long u = __shfl_up(v, o, STM_WAVE);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+// item i's slot [c0, c1) of a buffer of `total` elements, never outside it whatever the offsets hold
+__device__ __forceinline__ void stm_slot(const int64_t* off, int64_t i, int64_t total, int64_t& c0, int64_t& c1)
+{
+    c0 = min(max(off[i], (int64_t)0), total);
+    c1 = min(max(off[i + 1], c0), total);
+}
 
 // exclusive prefix of v over the 256 threads of a workgroup in thread order, and the total; sw: 4 words of LDS.  Has barriers: call it uniformly.
 __device__ __forceinline__ unsigned stm_block_excl_scan(unsigned v, unsigned* sw, unsigned& total)

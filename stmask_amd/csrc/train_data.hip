@@ -47,31 +47,6 @@ __global__ __launch_bounds__(256) void data_frames_kernel(const FrameArgs a, flo
     for (int c = 0; c < 3; ++c) out[(((size_t)i * 3 + c) * Hp + y) * Wp + x] = o[c];
 }
 
-__device__ __forceinline__ long long td_wave_sum(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, STM_WAVE);
-    return v;
-}
-
-// inclusive prefix sum over the lanes of a wavefront (wrapping unsigned arithmetic: the runs of a list that fails its sum check are garbage)
-__device__ __forceinline__ unsigned long long td_wave_scan(unsigned long long v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < STM_WAVE; o <<= 1) {
-        const unsigned long long u = __shfl_up(v, o, STM_WAVE);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
-// a mask's slot [c0, c1) of a buffer of `total` elements, never outside it whatever the offsets hold
-__device__ __forceinline__ void td_slot(const int64_t* off, int64_t i, int64_t total, int64_t& c0, int64_t& c1)
-{
-    c0 = min(max(off[i], (int64_t)0), total);
-    c1 = min(max(off[i + 1], c0), total);
-}
-
 // grid ceil(n / 4), block 256: a wavefront per mask, 64 runs per pass, the total so far carried from pass to pass
 __global__ __launch_bounds__(TD_THREADS) void data_rle_starts_kernel(const unsigned int* __restrict__ runs, const int64_t* __restrict__ off,
                                                                      const int* n_runs_in, const int* status_in, const int64_t* __restrict__ hw,
@@ -82,7 +57,7 @@ __global__ __launch_bounds__(TD_THREADS) void data_rle_starts_kernel(const unsig
     const int64_t i = (int64_t)blockIdx.x * TD_WAVES + (threadIdx.x >> 6);
     if (i >= n) return;                                          // wavefront-uniform
     int64_t c0, c1;
-    td_slot(off, i, total, c0, c1);
+    stm_slot(off, i, total, c0, c1);
     int st = status_in ? status_in[i] : 0;
     int64_t cnt = c1 - c0;
     if (n_runs_in) cnt = min(cnt, (int64_t)max(n_runs_in[i], 0));
@@ -96,28 +71,20 @@ __global__ __launch_bounds__(TD_THREADS) void data_rle_starts_kernel(const unsig
         const int64_t p = b + lane;
         const bool in = p < cnt;
         const unsigned long long v = in ? (unsigned long long)runs[c0 + p] : 0ull;
-        const unsigned long long incl = td_wave_scan(v, lane);
+        const unsigned long long incl = stm_wave_scan_u64(v, lane);
         if (in) {
             starts[c0 + p] = (unsigned int)(carry + incl - v);
             if (p & 1) sum_odd += (long long)v;
         }
         carry += __shfl(incl, 63, STM_WAVE);
     }
-    sum_odd = td_wave_sum(sum_odd);
+    sum_odd = stm_wave_sum_i64(sum_odd);
     if (!st && carry != (unsigned long long)hw[i]) st |= STM_VIS_RLE_SUM;
     if (lane == 0) {
         n_runs[i] = st ? 0 : (int)cnt;
         area[i] = st ? 0 : sum_odd;
         status[i] = st;
     }
-}
-
-// cv2 resizeNN: the source index of destination index d on an axis resized from `src` to `dst`
-__device__ __forceinline__ int td_nearest(int d, int src, int dst)
-{
-    const double inv = (double)dst / (double)src;
-    const double ifx = 1.0 / inv;
-    return min((int)floor((double)d * ifx), src - 1);
 }
 
 // grid (n, ceil(Hp / 16), ceil(Wp / 256)), block 64: lanes lie along x, four output pixels each, and walk 16 rows.  For a fixed output column
@@ -136,7 +103,7 @@ __global__ __launch_bounds__(STM_WAVE) void data_masks_kernel(const unsigned int
     const bool listed = d.list >= 0 && d.list < n_lists;
     const int m = listed ? d.list : 0;                           // the run list this mask is drawn from
     int64_t c0, c1;
-    td_slot(off, m, total, c0, c1);
+    stm_slot(off, m, total, c0, c1);
     const int nr = listed ? (int)min((int64_t)max(n_runs[m], 0), min(c1 - c0, (int64_t)INT_MAX)) : 0;
     const bool live = nr > 0 && d.H0 > 0 && d.W0 > 0;
     const unsigned int* __restrict__ st = starts + c0;
@@ -148,14 +115,14 @@ __global__ __launch_bounds__(STM_WAVE) void data_masks_kernel(const unsigned int
     for (int c = 0; c < TD_LANE_PX; ++c) {
         const int x = x4 + c;
         inside[c] = live && x < w;
-        kbase[c] = inside[c] ? (unsigned int)td_nearest(d.flip ? w - 1 - x : x, d.W0, w) * (unsigned int)d.H0 : 0u;
+        kbase[c] = inside[c] ? (unsigned int)resize_nearest(d.flip ? w - 1 - x : x, d.W0, w) * (unsigned int)d.H0 : 0u;
         cur[c] = -1;
     }
     const int y_end = min(y_begin + TD_MASK_ROWS, Hp);
     for (int y = y_begin; y < y_end; ++y) {
         unsigned int word = 0;
         if (live && y < h) {
-            const unsigned int sy = (unsigned int)td_nearest(y, d.H0, h);
+            const unsigned int sy = (unsigned int)resize_nearest(y, d.H0, h);
 #pragma unroll
             for (int c = 0; c < TD_LANE_PX; ++c) {
                 if (!inside[c]) continue;

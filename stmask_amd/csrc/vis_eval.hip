@@ -12,31 +12,6 @@ constexpr int VE_WAVES = VE_THREADS / STM_WAVE;
 constexpr int VE_MAX_VALUE_CHARS = 7;           // 35 bits: every |x| < 2^32 fits (rle_common.h stm_rle_chars)
 constexpr int VE_LDS_IOU = 2048;                // doubles of a group's IoU block staged in LDS (16 KiB); larger blocks are read from global memory
 
-__device__ __forceinline__ long long ve_wave_sum(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, STM_WAVE);
-    return v;
-}
-
-// inclusive prefix sum over the lanes of a wavefront (wrapping unsigned arithmetic: garbage in a flagged string must not be undefined)
-__device__ __forceinline__ unsigned long long ve_wave_scan(unsigned long long v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < STM_WAVE; o <<= 1) {
-        const unsigned long long u = __shfl_up(v, o, STM_WAVE);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
-// a mask's slice [c0, c1) of a buffer of `total` elements, never outside it whatever the offsets hold
-__device__ __forceinline__ void ve_slice(const int64_t* off, int64_t i, int64_t total, int64_t& c0, int64_t& c1)
-{
-    c0 = min(max(off[i], (int64_t)0), total);
-    c1 = min(max(off[i + 1], c0), total);
-}
-
 // grid ceil(n / 4), block 256: a wavefront per string, 64 characters per pass.  A lane whose character ends a value (bit 5 clear) rebuilds the
 // value from its (at most 7) characters; the ballot of those lanes numbers the runs, and two prefix sums (odd runs; even runs from run 2) undo
 // the delta coding.
@@ -49,7 +24,7 @@ __global__ __launch_bounds__(VE_THREADS) void vis_rle_decode_kernel(const unsign
     const int64_t i = (int64_t)blockIdx.x * VE_WAVES + (threadIdx.x >> 6);
     if (i >= n) return;                                          // wavefront-uniform
     int64_t c0, c1;
-    ve_slice(off, i, total, c0, c1);
+    stm_slot(off, i, total, c0, c1);
     const int64_t L = c1 - c0;
     const unsigned char* __restrict__ s = chars + c0;
     unsigned int* __restrict__ out = runs + c0;
@@ -84,8 +59,8 @@ __global__ __launch_bounds__(VE_THREADS) void vis_rle_decode_kernel(const unsign
             }
         }
         const bool odd = (j & 1) != 0;
-        const unsigned long long se = ve_wave_scan(end && !odd && j >= 2 ? (unsigned long long)x : 0ull, lane);
-        const unsigned long long so = ve_wave_scan(end && odd ? (unsigned long long)x : 0ull, lane);
+        const unsigned long long se = stm_wave_scan_u64(end && !odd && j >= 2 ? (unsigned long long)x : 0ull, lane);
+        const unsigned long long so = stm_wave_scan_u64(end && odd ? (unsigned long long)x : 0ull, lane);
         const unsigned long long cnt = j == 0 ? (unsigned long long)x : (odd ? carry_o + so : carry_e + se);
         carry_e += __shfl(se, 63, STM_WAVE);
         carry_o += __shfl(so, 63, STM_WAVE);
@@ -103,8 +78,8 @@ __global__ __launch_bounds__(VE_THREADS) void vis_rle_decode_kernel(const unsign
         if (ends) value_start = b + (63 - __clzll((long long)ends)) + 1;
     }
     if (value_start != L) st |= STM_VIS_RLE_UNTERMINATED;
-    sum_all = ve_wave_sum(sum_all);
-    sum_odd = ve_wave_sum(sum_odd);
+    sum_all = stm_wave_sum_i64(sum_all);
+    sum_odd = stm_wave_sum_i64(sum_odd);
     if (sum_all != hw[i]) st |= STM_VIS_RLE_SUM;
     if (lane == 0) {
         n_runs[i] = st ? 0 : (int)nr;
@@ -122,15 +97,15 @@ __global__ __launch_bounds__(VE_THREADS) void vis_rle_check_kernel(const unsigne
     const int64_t i = (int64_t)blockIdx.x * VE_WAVES + (threadIdx.x >> 6);
     if (i >= n) return;
     int64_t c0, c1;
-    ve_slice(off, i, total, c0, c1);
+    stm_slot(off, i, total, c0, c1);
     long long sum_all = 0, sum_odd = 0;
     for (int64_t p = c0 + lane; p < c1; p += 64) {
         const long long c = (long long)runs[p];
         sum_all += c;
         if ((p - c0) & 1) sum_odd += c;
     }
-    sum_all = ve_wave_sum(sum_all);
-    sum_odd = ve_wave_sum(sum_odd);
+    sum_all = stm_wave_sum_i64(sum_all);
+    sum_odd = stm_wave_sum_i64(sum_odd);
     int st = sum_all != hw[i] ? STM_VIS_RLE_SUM : 0;
     if (c1 - c0 > INT_MAX) st |= STM_VIS_RLE_RANGE;
     if (lane == 0) {
@@ -204,8 +179,8 @@ __global__ __launch_bounds__(VE_THREADS) void vis_tube_iou_kernel(const TubeArgs
             u += a.area[mg];
         }
     }
-    i = ve_wave_sum(i);
-    u = ve_wave_sum(u);
+    i = stm_wave_sum_i64(i);
+    u = stm_wave_sum_i64(u);
     if (lane == 0) {
         a.inter[pair] = i;
         a.uni[pair] = u;

@@ -127,9 +127,6 @@ class AugBlock:
         return c_p(self.buf.data_ptr() + self.n * ctypes.sizeof(_lib.AugDesc)) if self.n_masks else c_p(0)
 
 
-_aug_struct_checked = False
-
-
 def _rows_ok(f):
     return f.stride(2) == 1 and f.stride(1) == 3 and f.stride(0) >= 3 * f.shape[1]
 
@@ -138,14 +135,6 @@ def upload_aug(frames, flips, params, frame_of=(), device=None):
     """One upload for a batch's augmentation: params = one extra_aug.AugParams per frame, frames = the uint8 [H0, W0, 3] device tensors they
     augment (None entries: descriptors for masks only, no pointer), flips = one flag per frame, frame_of = for every mask the index of its
     frame.  -> AugBlock."""
-    global _aug_struct_checked
-    if not _aug_struct_checked:
-        got = _lib.lib().stm_aug_struct_bytes
-        got.restype, got.argtypes = ctypes.c_size_t, [ctypes.c_int]
-        if got(0) != ctypes.sizeof(_lib.AugDesc):
-            raise StmError(f"{_lib.LIB_PATH}: stm_aug_desc has {got(0)} bytes, this binding's mirror {ctypes.sizeof(_lib.AugDesc)}: rebuild with "
-                           "`python -c 'import __graft_entry__ as g; g.build()'`")
-        _aug_struct_checked = True
     n = len(params)
     if len(frames) != n or len(flips) != n:
         raise StmError(f"upload_aug: {len(frames)} frames, {len(flips)} flip flags, {n} parameter records")

@@ -423,21 +423,6 @@ class DecodeStatus:
             raise ValueError(f"{self.names[i]}: the JPEG data is damaged ({STATUS_TEXT.get(bad[i], bad[i])})")
 
 
-_struct_checked = False
-
-
-def _check_structs():
-    global _struct_checked
-    if not _struct_checked:
-        got = _lib.lib().stm_jpeg_struct_bytes
-        got.restype, got.argtypes = ctypes.c_size_t, [ctypes.c_int]
-        for which, mirror in enumerate((_lib.JpegImage, _lib.JpegSegment, _lib.JpegTables)):
-            if got(which) != ctypes.sizeof(mirror):
-                raise StmError(f"{_lib.LIB_PATH}: struct {which} of csrc/jpeg.h has {got(which)} bytes, this binding's mirror {ctypes.sizeof(mirror)}: "
-                               "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")
-        _struct_checked = True
-
-
 def _device(device):
     if device is None:
         if not torch.cuda.is_available():
@@ -469,7 +454,6 @@ def decode_batch(datas, device=None, order="bgr", names=None, check="raise"):
     if check not in ("raise", "deferred"):
         raise ValueError(f"decode_batch: check={check!r}")
     device = _device(device)
-    _check_structs()
     batch = pack_batch(datas, order, names)
     names = batch.names
     COUNTERS["host_fallback"] += batch.fallbacks

@@ -11,8 +11,8 @@ import torch
 from . import _lib
 from ._lib import StmError, c_p
 
-MAX_TENSORS = 64    # csrc/optim.h STM_OPTIM_MAX_TENSORS: tensors per launch (the table travels in the kernel arguments)
-CHUNK = 4096        # csrc/optim.h STM_OPTIM_CHUNK: elements per workgroup
+MAX_TENSORS = _lib.DP_MAX_TENSORS    # csrc/optim.h STM_OPTIM_MAX_TENSORS: tensors per launch (the table travels in the kernel arguments)
+CHUNK = _lib.DP_CHUNK                # csrc/optim.h STM_OPTIM_CHUNK: elements per workgroup
 GUARDS = ("loss", "grads", None)
 
 
@@ -184,7 +184,7 @@ class DataParallelSGD(GuardedSGD):
     parallel.GradArena of one layout over the trainable parameters: `grads` (every p.grad is a view of its segment, so autograd accumulates in
     place; the tail carries the loss) and `momentum` (its views are the momentum_buffer entries of the state, in torch.optim.SGD's layout, so a
     checkpoint keeps its format and loads either way).  Between backward and step(), parallel.exchange(opt.grads) sums the arena over the ranks.
-    step() is then csrc/dp_step.hip: per element  g = s * inv_world;  g' = g + wd * p;  m = mu * m + g';  p = p - lr * m  with s the summed
+    step() is then dp_sgd_finish_multi_kernel of csrc/optim.hip: per element  g = s * inv_world;  g' = g + wd * p;  m = mu * m + g';  p = p - lr * m  with s the summed
     gradient and inv_world the fp32 value of 1 / world, and 0.0f written back over every gradient element -- also when the guard skips the step,
     so zero_grad() has nothing left to do and a NaN never survives into the next iteration.  The guard reads the reduced tail slot 0 (the sum of
     the ranks' losses; not finite as soon as one rank's is) and, with guard="grads", a flag that one pass of stm_grads_nonfinite_multi_f32 over

@@ -6,7 +6,7 @@ GradArena is one flat fp32 buffer: a segment per trainable parameter, in paramet
 and stay zero), then a tail of n_tail floats.  Every p.grad is a view of its segment (the parameter's shape and dense layout), so autograd
 accumulates in place and nothing is packed or unpacked.  The tail rides in the same buffer and so in the same collective: slot 0 the rank's total
 loss (the guard of optim.DataParallelSGD reads its sum), slots 1.. the loss terms in the criterion's key order (the log reads their mean).
-exchange() is that collective: one sum all-reduce over the whole buffer.  The finish kernel of csrc/dp_step.hip then averages, steps and writes
+exchange() is that collective: one sum all-reduce over the whole buffer.  The finish kernel of csrc/optim.hip then averages, steps and writes
 zeros back over the gradients (optim.DataParallelSGD.step).
 
 Not built: overlap of the all-reduce with the backward pass (buckets, post-accumulate hooks), multi-GPU validation, more than one node."""

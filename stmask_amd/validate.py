@@ -17,7 +17,6 @@ eval; its parameters, buffers, flags, the optimizer state and the random generat
 
 Not built: multi-GPU validation, iouType='bbox', compute_validation_loss, in-place update of the packed planar weights."""
 import copy
-import ctypes
 
 import torch
 import torch.nn as nn
@@ -29,8 +28,6 @@ FOLDS = ("device", "torch")
 COPY, WEIGHT, BIAS, BIAS3 = "copy", "weight", "bias", "bias3"
 # launches of the last refresh()'s parameter write: kernel launches of csrc/fold.hip, or torch operations of the torch form
 COUNTERS = {"fold_launches": 0, "torch_ops": 0}
-
-_struct_checked = False
 
 
 def _fold_pairs(net):
@@ -176,14 +173,6 @@ class InferenceTwin:
                     COUNTERS["torch_ops"] += 3
 
     def _write_device(self):
-        global _struct_checked
-        if not _struct_checked:
-            size = _lib.lib().stm_fold_struct_bytes
-            size.restype, size.argtypes = ctypes.c_size_t, [ctypes.c_int]
-            if size(0) != ctypes.sizeof(FoldRow):
-                raise StmError(f"{_lib.LIB_PATH}: stm_fold_row has {size(0)} bytes, this binding's mirror {ctypes.sizeof(FoldRow)}: rebuild with "
-                               "`python -c 'import __graft_entry__ as g; g.build()'`")
-            _struct_checked = True
         rows = []
         for row in self.sources:
             if row.kind == BIAS3:

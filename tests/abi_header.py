@@ -1,4 +1,4 @@
-"""What tests/test_abi*.py read out of a header of include/: its prototypes as ctypes types, its struct fields, and the comparison of a header
+"""What tests/test_abi*.py read out of a header of include/ or a package-private one of stmask_amd/csrc/: its prototypes as ctypes types, its struct fields, and the comparison of a header
 with the table of stmask_amd/_lib.py that restates it."""
 import ctypes
 import itertools
@@ -12,8 +12,14 @@ C_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "long long": ctypes.c
            "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p}
 
 
+def header_path(header):
+    """include/<header>, or stmask_amd/csrc/<header> for a package-private or internal one."""
+    public = os.path.join(ROOT, "include", header)
+    return public if os.path.exists(public) else os.path.join(ROOT, "stmask_amd", "csrc", header)
+
+
 def header_raw(header):
-    return open(os.path.join(ROOT, "include", header)).read()
+    return open(header_path(header)).read()
 
 
 def header_text(header):
@@ -47,16 +53,28 @@ def struct_field_names(header, struct):
             for n in re.sub(r"^(const\s+)?\w+\*?\s+", "", decl.strip()).split(",")]
 
 
+def header_define(header, name):
+    """The integer a `#define name ...` of the header stands for; a value that is another macro is looked up in the header and the csrc/ headers
+    it includes."""
+    text = header_raw(header)
+    value = re.search(r"^#define %s (\w+)\s*(?:/[/*].*)?$" % name, text, flags=re.M).group(1)
+    if re.fullmatch(r"\d+", value):
+        return int(value)
+    found = [h for h in [header] + re.findall(r'^#include "(\w+\.h)"', text, flags=re.M) if re.search(r"^#define %s " % value, header_raw(h), flags=re.M)]
+    assert len(found) == 1, (header, name, value, found)
+    return header_define(found[0], value)
+
+
 def assert_table_matches_header(header, table):
-    """Every argument of every entry point: the header, the table and the loaded library (whose restype / argtypes lib() took from the table) say
-    the same thing."""
+    """Every argument of every entry point: the header, the table and the loaded library (whose restype / argtypes lib() or, for a
+    package-private header, private_fn() took from the table) say the same thing."""
     protos = header_prototypes(header)
     assert sorted(protos) == sorted(table)
     assert header_symbols(header) == sorted(protos)                 # a prototype the expression misses fails here instead of skipping a function
     lib = _lib.lib()
     for name, (ret_kind, kinds) in table.items():
         ret, args = protos[name]
-        fn = getattr(lib, name)                                     # exported by the built library
+        fn = getattr(lib, name) if header in _lib.HEADERS else _lib.private_fn(name)      # exported by the built library
         assert fn.restype == ret == _lib._KINDS[ret_kind], (name, fn.restype, ret)
         # "-": one of the three ends before the others, so that an argument too few or too many is named by its index too
         for i, (got, want, kind) in enumerate(itertools.zip_longest(fn.argtypes, args, kinds, fillvalue="-")):

@@ -1,4 +1,4 @@
-"""The finish of a data-parallel step (csrc/dp_step.hip) restated in numpy float32, one rounding per operation, in the kernel's order:
+"""The finish of a data-parallel step (dp_sgd_finish_multi_kernel of csrc/optim.hip) restated in numpy float32, one rounding per operation, in the kernel's order:
 
     g = s * inv_world;   g' = g + wd * p;   m' = mu * m + g';   p' = p - lr * m'
 

@@ -10,6 +10,7 @@ import torch
 
 from abi_header import assert_table_matches_header, header_raw, header_symbols, header_text, struct_field_names
 from conftest import ROOT
+from kernel_resources import kernel_resources
 from stmask_amd import _lib, ops
 
 # What every header declares, in the order of _lib.HEADERS: how many entries, and (but for the first header's 129) which.  The one place these live.
@@ -47,6 +48,20 @@ def test_headers_tables_and_expectations_are_the_same_list():
 def test_header_and_signature_table_agree(header):
     """Every argument of every entry point: the table lib() takes restype / argtypes from says what the header says."""
     assert_table_matches_header(header, _lib.HEADERS[header])
+
+
+@pytest.mark.parametrize("header,name,wrong", [("stmask_hip_tracker.h", "stm_track_drop_plan", ("i", "ppiippi")),
+                                               ("stmask_hip_tracker.h", "stm_track_drop_plan", ("i", "ppiipp")),
+                                               ("dp_step.h", "stm_dp_sgd_finish_multi_f32", ("i", "ppppipppifffip")),
+                                               ("dp_step.h", "stm_dp_sgd_finish_multi_f32", ("z", "ppppipppiffffp"))])
+def test_a_wrong_table_entry_is_caught(header, name, wrong, monkeypatch):
+    """The comparison can fail: one kind, the argument count or the return kind of one entry off, in a public and in a private table."""
+    table = _lib.HEADERS.get(header) or _lib.PRIVATE_HEADERS[header]
+    assert table[name] != wrong
+    assert_table_matches_header(header, table)            # also binds the private entry from the table as it is
+    monkeypatch.setitem(table, name, wrong)
+    with pytest.raises(AssertionError, match=name):
+        assert_table_matches_header(header, table)
 
 
 @pytest.mark.parametrize("header", list(EXPECTED))
@@ -183,20 +198,10 @@ def test_product_path_never_imports_oracle():
 def test_planar_conv_kernels_do_not_spill():
     """hipcc's resource report for csrc/conv_bf16x.hip: no instantiation of the planar convolution kernels may use scratch
     (a register spill in the MFMA loop costs 2x: seen once when the 128-wide body was duplicated)."""
-    import re
-    import subprocess
-    src = os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc", "conv_bf16x.hip")
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-slp-vectorize",
-           "--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600).stderr
-    blocks = re.split(r"remark: [^\n]*Function Name: ", out)[1:]
     seen = 0
-    for b in blocks:
-        name = b.split()[0]
+    for name, r in kernel_resources("conv_bf16x.hip").items():
         if "conv_planar_kernel" not in name and "conv_planar_kx3_kernel" not in name:
             continue
         seen += 1
-        scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-        vgprs = int(re.search(r" VGPRs: (\d+)", b).group(1))
-        assert scratch == 0 and vgprs <= 256, (name, scratch, vgprs)
+        assert r.scratch == 0 and r.vgpr <= 256, (name, r.scratch, r.vgpr)
     assert seen >= 8

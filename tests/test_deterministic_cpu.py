@@ -3,7 +3,6 @@ of tests/det_restate.py against their own float64 oracles (and torch's CPU backw
 stmask_amd.autograd, which calls the mode routes through which table, and the package-private binding of csrc/det_backward.h."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 import warnings
@@ -13,17 +12,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import abi_header
 import det_restate as D
+from kernel_resources import kernel_resources
 from conftest import ROOT
 from stmask_amd import _lib, autograd, ops
 from stmask_amd._lib import StmError
 from stmask_amd.config import get_cfg
 from stmask_amd.layers.modules import FPN, InterpolateModule
 
-DET_H = os.path.join("..", "stmask_amd", "csrc", "det_backward.h")     # relative to include/, where abi_header looks
-NAMES = ["stm_deform_col2im_det_f32", "stm_det_exponent", "stm_det_workspace_bytes", "stm_roi_align_backward_det_f32",
-         "stm_upsample_bilinear_backward_f32"]
 UPSAMPLE_CASES = [((4, 6), (8, 12), None), ((5, 7), (12, 17), None), ((3, 5), (3, 5), None), ((6, 10), None, 2.0), ((1, 1), (4, 4), None),
                   ((2, 3), (5, 4), None)]
 
@@ -301,34 +297,6 @@ def test_upsample_route_conditions():
 
 
 # ---- the private binding ----------------------------------------------------------------------------------------------------------------------
-def test_det_signatures_match_det_backward_h():
-    protos = abi_header.header_prototypes(DET_H)
-    assert sorted(protos) == sorted(_lib.DET_SIGNATURES) == NAMES == abi_header.header_symbols(DET_H)
-    for name, (ret_kind, kinds) in _lib.DET_SIGNATURES.items():
-        ret, args = protos[name]
-        assert ret == _lib._KINDS[ret_kind], name
-        assert len(args) == len(kinds), (name, len(args), len(kinds))
-        for i, (want, kind) in enumerate(zip(args, kinds)):
-            assert want == _lib._KINDS[kind], (name, i, want, kind)
-    assert _lib.det_tables() == {"det_backward.h": _lib.DET_SIGNATURES}
-    text = open(os.path.join(ROOT, "stmask_amd", "csrc", "det_accum.h")).read()
-    assert int(re.search(r"#define STM_DET_MIN_BITS (\d+)", text).group(1)) == _lib.DET_MIN_BITS == D.MIN_BITS == 36
-    for name, value in (("FINITE", _lib.DET_FINITE), ("ZERO", _lib.DET_ZERO), ("NONFINITE", _lib.DET_NONFINITE)):
-        assert int(re.search(r"#define STM_DET_%s (\d+)" % name, text).group(1)) == value == getattr(D, name)
-
-
-def test_det_table_is_its_own_and_the_public_boundary_is_unchanged():
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        assert hasattr(lib, name) and name not in _lib.all_signatures()
-        assert all(name not in table for table in _lib.private_tables().values())
-        assert all(name not in table for table in _lib.dp_tables().values())
-        for header in os.listdir(os.path.join(ROOT, "include")):
-            assert name not in open(os.path.join(ROOT, "include", header)).read(), (name, header)
-    assert _lib.ABI_VERSION == 6 and len(_lib.HEADERS) == 7 and sorted(_lib.private_tables()) == ["extra_aug.h", "fold.h", "optim.h"]
-    assert sorted(_lib.dp_tables()) == ["dp_step.h"] and sorted(_lib.det_tables()) == ["det_backward.h"]
-
-
 def test_private_call_resolves_the_entries_and_refusals_launch_nothing():
     with pytest.raises(StmError, match="takes 10 arguments, got 2"):
         _lib.private_call("stm_upsample_bilinear_backward_f32", None, None)
@@ -351,15 +319,11 @@ def test_private_call_resolves_the_entries_and_refusals_launch_nothing():
 
 
 def test_det_kernels_use_no_scratch_and_no_lds():
-    src = os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc", "det_backward.hip")
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
-           "--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600).stderr
-    blocks = re.split(r"remark: [^\n]*Function Name: ", out)[1:]
-    assert len(blocks) == 5
-    for b in blocks:
-        assert int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1)) == 0, b.split()[0]
-        assert int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1)) == 0, b.split()[0]
+    rows = kernel_resources("det_backward.hip")
+    assert len(rows) == 5
+    for name, r in rows.items():
+        assert r.scratch == 0, name
+        assert r.lds == 0, name
 
 
 def test_training_scripts_take_the_flag():

@@ -6,22 +6,19 @@ import ctypes
 import json
 import os
 import random
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import abi_header
 import extra_aug_restate as R
+from kernel_resources import kernel_resources
 import train_data_cases as C
 from conftest import GOLDEN
 from stmask_amd import _lib, datasets
 from stmask_amd import extra_aug as EA
 from stmask_amd._lib import StmError
 
-AUG_H = os.path.join("..", "stmask_amd", "csrc", "extra_aug.h")     # relative to include/, where abi_header looks
-NAMES = ["stm_aug_frames_u8_f32", "stm_aug_masks_u8", "stm_aug_source_u8", "stm_aug_struct_bytes"]
 ALL_ON = dict(photo_metric_distortion=dict(), expand=dict(mean=C.MEAN, to_rgb=True, ratio_range=(1, 3)), random_crop=dict())
 
 
@@ -237,29 +234,8 @@ def test_the_dataset_does_not_change_its_annotations():
 
 
 # ---- the private binding ----------------------------------------------------------------------------------------------------------------------
-def test_aug_signatures_match_extra_aug_h():
-    protos = abi_header.header_prototypes(AUG_H)
-    assert sorted(protos) == sorted(_lib.AUG_SIGNATURES) == NAMES == abi_header.header_symbols(AUG_H)
-    for name, (ret_kind, kinds) in _lib.AUG_SIGNATURES.items():
-        ret, args = protos[name]
-        assert ret == _lib._KINDS[ret_kind], name
-        assert len(args) == len(kinds), (name, len(args), len(kinds))
-        for i, (want, kind) in enumerate(zip(args, kinds)):
-            assert want == _lib._KINDS[kind], (name, i, want, kind)
-    assert _lib.PRIVATE_TABLES == {"optim.h": _lib.PRIVATE_SIGNATURES, "extra_aug.h": _lib.AUG_SIGNATURES}
-    text = abi_header.header_raw(AUG_H)
-    assert int(re.search(r"#define STM_AUG_FRAMES_PER_LAUNCH (\d+)", text).group(1)) == _lib.AUG_FRAMES_PER_LAUNCH
-
-
-def test_the_boundary_does_not_list_the_new_names_and_the_library_exports_them():
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        assert hasattr(lib, name) and name not in _lib.all_signatures() and name not in _lib.PRIVATE_SIGNATURES
-    assert _lib.ABI_VERSION == 6 and "AugDesc" not in [s.__name__ for mirrors in _lib.STRUCTS.values() for s in mirrors]
-
-
 def test_descriptor_mirror_has_the_headers_fields_and_size():
-    fields = abi_header.struct_field_names(AUG_H, "stm_aug_desc")
+    fields = abi_header.struct_field_names("extra_aug.h", "stm_aug_desc")
     assert fields == [f[0] for f in _lib.AugDesc._fields_]
     size = ctypes.CDLL(_lib.LIB_PATH).stm_aug_struct_bytes
     size.restype, size.argtypes = ctypes.c_size_t, [ctypes.c_int]
@@ -337,17 +313,9 @@ def test_source_and_masks_refusals():
 
 # ---- the kernels' resources --------------------------------------------------------------------------------------------------------------------
 def test_aug_kernels_use_no_scratch_and_no_lds():
-    src = os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc", "extra_aug.hip")
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
-           "--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600).stderr
-    blocks = re.split(r"remark: [^\n]*Function Name: ", out)[1:]
     seen = []
-    for b in blocks:
-        name = b.split()[0]
+    for name, r in kernel_resources("extra_aug.hip").items():
         if any(k in name for k in ("aug_frames_kernel", "aug_masks_kernel", "aug_source_kernel")):
             seen.append(name)
-            scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-            lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
-            assert scratch == 0 and lds == 0, (name, scratch, lds)
+            assert r.scratch == 0 and r.lds == 0, (name, r.scratch, r.lds)
     assert len(seen) == 3, seen

@@ -1,4 +1,4 @@
-"""optim.DataParallelSGD.step (csrc/dp_step.hip) on the MI355X: bit-equality with the numpy restatement of tests/dp_restate.py over every path of
+"""optim.DataParallelSGD.step (csrc/optim.hip) on the MI355X: bit-equality with the numpy restatement of tests/dp_restate.py over every path of
 the kernel, the gradients and pads left at exactly zero, world == 1 against stm_sgd_step_multi_f32, the guard (which still clears the
 gradients), the refusals, and steps without host synchronisation."""
 import numpy as np

@@ -10,8 +10,8 @@ import pytest
 
 import jpeg_cases as JC
 import jpeg_restate
+from kernel_resources import kernel_resources
 import train_data_cases as C
-from abi_header import header_prototypes
 from stmask_amd import _lib, datasets, jpeg
 
 GRID, UNSUPPORTED, DAMAGED = JC.load()
@@ -232,40 +232,13 @@ def test_read_compressed(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the binding
-def test_jpeg_table_and_the_other_tables():
-    assert _lib.jpeg_tables() == {"jpeg.h": _lib.JPEG_SIGNATURES}
-    assert sorted(_lib.JPEG_SIGNATURES) == ["stm_jpeg_decode_u8", "stm_jpeg_struct_bytes", "stm_jpeg_workspace_bytes"]
-    assert sorted(_lib.private_tables()) == ["extra_aug.h", "fold.h", "optim.h"] and sorted(_lib.dp_tables()) == ["dp_step.h"]
-    assert sorted(_lib.det_tables()) == ["det_backward.h"] and _lib.ABI_VERSION == 6 and len(_lib.HEADERS) == 7
-    every_other = [n for t in (*_lib.private_tables().values(), *_lib.dp_tables().values(), *_lib.det_tables().values(), *_lib.HEADERS.values()) for n in t]
-    assert not set(every_other) & set(_lib.JPEG_SIGNATURES)
-    protos = header_prototypes("../stmask_amd/csrc/jpeg.h")
-    assert sorted(protos) == sorted(_lib.JPEG_SIGNATURES)
-    for name, (ret, kinds) in _lib.JPEG_SIGNATURES.items():
-        assert protos[name] == (_lib._KINDS[ret], [_lib._KINDS[k] for k in kinds]), name
-        assert hasattr(_lib.lib(), name)
-
-
-def test_struct_mirrors_have_the_library_sizes():
-    fn = _lib.lib().stm_jpeg_struct_bytes
-    fn.restype, fn.argtypes = ctypes.c_size_t, [ctypes.c_int]
-    assert [fn(i) for i in range(4)] == [ctypes.sizeof(_lib.JpegImage), ctypes.sizeof(_lib.JpegSegment), ctypes.sizeof(_lib.JpegTables), 0]
-    header = open(JC.ROOT + "/stmask_amd/csrc/jpeg.h").read()
-    for name, value in (("STM_JPEG_MAX_DIM", _lib.JPEG_MAX_DIM), ("STM_JPEG_LOOK_BITS", _lib.JPEG_LOOK_BITS), ("STM_JPEG_RAW", _lib.JPEG_RAW),
-                        ("STM_JPEG_ENOCODE", _lib.JPEG_ENOCODE), ("STM_JPEG_EINDEX", _lib.JPEG_EINDEX), ("STM_JPEG_ESIZE", _lib.JPEG_ESIZE),
-                        ("STM_JPEG_ETRUNCATED", _lib.JPEG_ETRUNCATED), ("STM_JPEG_STAGE_COLOUR", _lib.JPEG_STAGE_COLOUR)):
-        assert f"#define {name} {value}" in header, name
-
-
 def _call(batch, **over):
     """stm_jpeg_decode_u8 over a packed batch with fake (never dereferenced) device pointers -> the return code"""
     a = dict(images=batch.images, n_images=batch.n_images, segments=batch.segments, n_segments=batch.n_segments, blob=0x1000, blob_bytes=batch.blob_bytes,
              images_off=batch.images_off, segments_off=batch.segments_off, out=0x2000, out_bytes=batch.out_bytes, status=0x3000, workspace=0x4000,
              workspace_bytes=batch.workspace_bytes, bgr=1, stages=7, stream=None)
     a.update(over)
-    fn = _lib.lib().stm_jpeg_decode_u8
-    fn.restype, fn.argtypes = _lib._KINDS["i"], [_lib._KINDS[k] for k in _lib.JPEG_SIGNATURES["stm_jpeg_decode_u8"][1]]
-    return fn(*a.values())
+    return _lib.private_fn("stm_jpeg_decode_u8")(*a.values())
 
 
 def _copy(batch):
@@ -316,8 +289,7 @@ def test_entry_point_refuses_bad_arguments_before_any_launch():
         many[i].mcu_w = many[i].mcu_h = 1024
         many[i].blk_first, many[i].quad_first, many[i].out_off = (i * 1024 * 1024) & 0x7FFFFFFF, (i * 2048 * 8192) & 0x7FFFFFFF, i * 8192 * 8192 * 3
     assert _call(g, images=many, n_images=2200, n_segments=0, segments=None, status=None, out_bytes=1 << 60) in (EUNSUPPORTED, EINVAL)
-    fn = _lib.lib().stm_jpeg_workspace_bytes
-    fn.restype, fn.argtypes = ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int]
+    fn = _lib.private_fn("stm_jpeg_workspace_bytes")
     assert fn(b.images, 2) == b.workspace_bytes == 192 * (36 + 90) and fn(None, 2) == 0 and fn(b.images, 0) == 0 and fn(images, 1) == 0
     assert "stm_jpeg_decode_u8" in _lib.lib().stm_last_error_string().decode()
 
@@ -467,21 +439,13 @@ def test_host_program_ends_damaged_files_flagged_or_bit_equal_under_sanitizers(h
 def test_jpeg_kernels_use_no_scratch():
     """The entropy loop keeps the byte window, four first-level lookups and the block's coefficient in registers and cannot afford a spill; 8 lanes
     a block in the IDCT, and launches 2 and 3 left apart, were chosen from this report."""
-    import os
-    import re
-    import subprocess
-    src = os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc", "jpeg_decode.hip")
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
-           "--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600).stderr
     seen = {}
-    for b in re.split(r"remark: [^\n]*Function Name: ", out)[1:]:
-        kernel = next((k for k in ("jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_colour_kernel") if k in b.split()[0]), None)
+    for name, r in kernel_resources("jpeg_decode.hip").items():
+        kernel = next((k for k in ("jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_colour_kernel") if k in name), None)
         if kernel is None:
             continue
-        field = lambda name: int(re.search(re.escape(name) + r": (\d+)", b).group(1))          # noqa: E731
-        assert field("ScratchSize [bytes/lane]") == 0 and field("VGPRs Spill") == 0 and field("SGPRs Spill") == 0, (kernel, b[:800])
-        seen[kernel] = (field("VGPRs"), field("LDS Size [bytes/block]"))
-    assert sorted(seen) == ["jpeg_colour_kernel", "jpeg_entropy_kernel", "jpeg_idct_kernel"], out[-2000:]
+        assert r.scratch == 0 and r.spills == (0, 0), (kernel, r, r.spills)
+        seen[kernel] = (r.vgpr, r.lds)
+    assert sorted(seen) == ["jpeg_colour_kernel", "jpeg_entropy_kernel", "jpeg_idct_kernel"], sorted(seen)
     assert seen["jpeg_entropy_kernel"][0] <= 64 and seen["jpeg_entropy_kernel"][1] <= 4096        # 1 KiB window + the tables' canonical part
     assert seen["jpeg_idct_kernel"][1] == 9216 and seen["jpeg_colour_kernel"][1] == 0

@@ -2,23 +2,17 @@
 package-private binding of csrc/optim.h, the refusals of the two entry points (NULL pointers: nothing is launched), GuardedSGD on CPU parameters,
 and the compiler's resource report for csrc/optim.hip."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-import abi_header
 import optim_restate as R
-from conftest import ROOT
+from kernel_resources import kernel_resources
 from stmask_amd import _lib, optim
 from stmask_amd._lib import StmError
 from stmask_amd.optim import GuardedSGD
 
-OPTIM_H = os.path.join("..", "stmask_amd", "csrc", "optim.h")     # relative to include/, where abi_header looks
-NAMES = ["stm_grads_nonfinite_multi_f32", "stm_sgd_step_multi_f32"]
 SCALES = [(1.0, 1.0, 1.0), (1e-3, 1.0, 1e3), (1e3, 1e-3, 1.0), (1e-6, 1e-6, 1e-6), (1e4, 1e4, 1e4)]     # of p, g, m
 HYPER = [(1e-3, 0.9, 1e-4), (0.0137, 0.9, 0.0), (1e-3, 0.0, 1e-4), (0.3, 0.0, 0.0)]
 
@@ -81,32 +75,6 @@ def test_fp64_hyper_parameters_alone_take_a_share_of_the_bound():
 
 
 # ---- the private binding ------------------------------------------------------------------------------------------------------------------
-def test_private_signatures_match_optim_h():
-    protos = abi_header.header_prototypes(OPTIM_H)
-    assert sorted(protos) == sorted(_lib.PRIVATE_SIGNATURES) == NAMES == abi_header.header_symbols(OPTIM_H)
-    for name, (ret_kind, kinds) in _lib.PRIVATE_SIGNATURES.items():
-        ret, args = protos[name]
-        assert ret == _lib._KINDS[ret_kind], name
-        assert len(args) == len(kinds), (name, len(args), len(kinds))
-        for i, (want, kind) in enumerate(zip(args, kinds)):
-            assert want == _lib._KINDS[kind], (name, i, want, kind)
-
-
-def test_header_constants_match_the_python_module():
-    text = abi_header.header_raw(OPTIM_H)
-    assert int(re.search(r"#define STM_OPTIM_MAX_TENSORS (\d+)", text).group(1)) == optim.MAX_TENSORS
-    assert int(re.search(r"#define STM_OPTIM_CHUNK (\d+)", text).group(1)) == optim.CHUNK
-
-
-def test_library_exports_both_names_and_the_boundary_does_not_list_them():
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        assert hasattr(lib, name)
-        assert name not in _lib.all_signatures()
-        for header in os.listdir(os.path.join(ROOT, "include")):
-            assert name not in open(os.path.join(ROOT, "include", header)).read(), (name, header)
-
-
 def test_private_call_checks_the_argument_count_and_types():
     with pytest.raises(StmError, match="takes 13 arguments, got 2"):
         _lib.private_call("stm_sgd_step_multi_f32", None, None)
@@ -273,17 +241,9 @@ def test_load_state_dict_none_buffers_unknown_keys_and_refusals():
 
 # ---- the kernels' resources --------------------------------------------------------------------------------------------------------------------
 def test_optim_kernels_use_no_scratch_and_no_lds():
-    src = os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc", "optim.hip")
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-slp-vectorize",
-           "--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600).stderr
-    blocks = re.split(r"remark: [^\n]*Function Name: ", out)[1:]
     seen = []
-    for b in blocks:
-        name = b.split()[0]
+    for name, r in kernel_resources("optim.hip").items():
         if "sgd_step_multi_kernel" in name or "grads_nonfinite_multi_kernel" in name:
             seen.append(name)
-            scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-            lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
-            assert scratch == 0 and lds == 0, (name, scratch, lds)
+            assert r.scratch == 0 and r.lds == 0, (name, r.scratch, r.lds)
     assert len(seen) == 2, seen

@@ -2,9 +2,7 @@
 csrc/dp_step.h and its refusals (nothing is launched), TrainLoader(shard=...), parallel.exchange between two gloo processes on CPU tensors, the
 numpy restatement of the finish pinned to the single-rank step, and the new arguments of scripts/train_ytvis.py."""
 import copy
-import ctypes
 import os
-import re
 import socket
 import subprocess
 import sys
@@ -13,16 +11,14 @@ import numpy as np
 import pytest
 import torch
 
-import abi_header
 import dp_restate as D
+from kernel_resources import kernel_resources
 import optim_restate as R
 from conftest import ROOT
 from stmask_amd import _lib, datasets, optim, parallel
 from stmask_amd._lib import StmError
 from stmask_amd.optim import DataParallelSGD, GuardedSGD
 
-DP_H = os.path.join("..", "stmask_amd", "csrc", "dp_step.h")     # relative to include/, where abi_header looks
-NAMES = ["stm_dp_sgd_finish_multi_f32"]
 SHAPES = [(3, 5), (0,), (7,), (2, 1, 3), (4,), (2, 3, 4, 5)]
 
 
@@ -155,32 +151,6 @@ def test_dp_sgd_arguments_and_no_cpu_fallback():
 
 
 # ---- the private binding ------------------------------------------------------------------------------------------------------------------
-def test_dp_signatures_match_dp_step_h():
-    protos = abi_header.header_prototypes(DP_H)
-    assert sorted(protos) == sorted(_lib.DP_SIGNATURES) == NAMES == abi_header.header_symbols(DP_H)
-    for name, (ret_kind, kinds) in _lib.DP_SIGNATURES.items():
-        ret, args = protos[name]
-        assert ret == _lib._KINDS[ret_kind], name
-        assert len(args) == len(kinds), (name, len(args), len(kinds))
-        for i, (want, kind) in enumerate(zip(args, kinds)):
-            assert want == _lib._KINDS[kind], (name, i, want, kind)
-    assert _lib.dp_tables() == {"dp_step.h": _lib.DP_SIGNATURES}
-    text = abi_header.header_raw(DP_H)
-    assert int(re.search(r"#define STM_DP_MAX_TENSORS (\d+)", text).group(1)) == _lib.DP_MAX_TENSORS == optim.MAX_TENSORS
-    assert int(re.search(r"#define STM_DP_CHUNK (\d+)", text).group(1)) == _lib.DP_CHUNK == optim.CHUNK
-
-
-def test_the_library_exports_the_entry_and_no_other_table_lists_it():
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        assert hasattr(lib, name) and name not in _lib.all_signatures()
-        assert all(name not in table for table in _lib.PRIVATE_TABLES.values())
-        assert all(name not in table for table in _lib.private_tables().values())
-        for header in os.listdir(os.path.join(ROOT, "include")):
-            assert name not in open(os.path.join(ROOT, "include", header)).read(), (name, header)
-    assert _lib.ABI_VERSION == 6 and len(_lib.HEADERS) == 7 and sorted(_lib.private_tables()) == ["extra_aug.h", "fold.h", "optim.h"]
-
-
 def test_private_call_resolves_the_entry_and_checks_the_argument_count():
     with pytest.raises(StmError, match="takes 14 arguments, got 2"):
         _lib.private_call("stm_dp_sgd_finish_multi_f32", None, None)
@@ -194,14 +164,10 @@ def test_finish_refusals(change, code, text):
 
 
 def test_finish_kernel_uses_no_scratch_and_no_lds():
-    src = os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc", "dp_step.hip")
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
-           "--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600).stderr
-    blocks = [b for b in re.split(r"remark: [^\n]*Function Name: ", out)[1:] if "dp_sgd_finish_multi_kernel" in b.split()[0]]
-    assert len(blocks) == 1
-    assert int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", blocks[0]).group(1)) == 0
-    assert int(re.search(r"LDS Size \[bytes/block\]: (\d+)", blocks[0]).group(1)) == 0
+    rows = [r for name, r in kernel_resources("optim.hip").items() if "dp_sgd_finish_multi_kernel" in name]
+    assert len(rows) == 1
+    assert rows[0].scratch == 0
+    assert rows[0].lds == 0
 
 
 # ---- the restatement -------------------------------------------------------------------------------------------------------------------------

@@ -5,8 +5,6 @@ import copy
 import ctypes
 import json
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,14 +13,13 @@ import torch.nn as nn
 
 import abi_header
 import fold_restate as R
+from kernel_resources import kernel_resources
 from validate_helpers import LENGTHS, SIZES, Reader, differing, fresh_copy, full_state, perturb, rng_states, same_rng, same_snapshot, snapshot, val_ann
 from stmask_amd import _lib, datasets, eval_utils, fuse, synthetic, validate
 from stmask_amd._lib import StmError
 from stmask_amd.config import get_cfg
 from stmask_amd.model import STMask
 
-FOLD_H = os.path.join("..", "stmask_amd", "csrc", "fold.h")     # relative to include/, where abi_header looks
-NAMES = ["stm_fold_rows_f32", "stm_fold_struct_bytes"]
 
 
 # ---- the restatement against fuse._fold on CPU convolutions ------------------------------------------------------------------------------
@@ -250,33 +247,8 @@ def test_train_script_parses_the_validation_arguments():
 
 
 # ---- the private binding -------------------------------------------------------------------------------------------------------------------
-def test_fold_signatures_match_fold_h():
-    protos = abi_header.header_prototypes(FOLD_H)
-    assert sorted(protos) == sorted(_lib.FOLD_SIGNATURES) == NAMES == abi_header.header_symbols(FOLD_H)
-    for name, (ret_kind, kinds) in _lib.FOLD_SIGNATURES.items():
-        ret, args = protos[name]
-        assert ret == _lib._KINDS[ret_kind], name
-        assert len(args) == len(kinds), (name, len(args), len(kinds))
-        for i, (want, kind) in enumerate(zip(args, kinds)):
-            assert want == _lib._KINDS[kind], (name, i, want, kind)
-    assert _lib.private_tables() == {**_lib.PRIVATE_TABLES, "fold.h": _lib.FOLD_SIGNATURES}
-    text = abi_header.header_raw(FOLD_H)
-    for macro, value in (("MAX_ROWS", _lib.FOLD_MAX_ROWS), ("CHUNK", _lib.FOLD_CHUNK), ("COPY", _lib.FOLD_COPY), ("WEIGHT", _lib.FOLD_WEIGHT),
-                         ("BIAS", _lib.FOLD_BIAS)):
-        assert int(re.search(r"#define STM_FOLD_%s (\d+)" % macro, text).group(1)) == value
-
-
-def test_the_library_exports_the_fold_entries_and_the_boundary_does_not_list_them():
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        assert hasattr(lib, name) and name not in _lib.all_signatures()
-        assert all(name not in table for table in _lib.PRIVATE_TABLES.values())
-    assert _lib.ABI_VERSION == 6 and len(_lib.SIGNATURES) == 129 and len(_lib.HEADERS) == 7
-    assert "FoldRow" not in [s.__name__ for mirrors in _lib.STRUCTS.values() for s in mirrors]
-
-
 def test_row_mirror_has_the_headers_fields_and_size():
-    assert abi_header.struct_field_names(FOLD_H, "stm_fold_row") == [f[0] for f in _lib.FoldRow._fields_]
+    assert abi_header.struct_field_names("fold.h", "stm_fold_row") == [f[0] for f in _lib.FoldRow._fields_]
     size = ctypes.CDLL(_lib.LIB_PATH).stm_fold_struct_bytes
     size.restype, size.argtypes = ctypes.c_size_t, [ctypes.c_int]
     assert size(0) == ctypes.sizeof(_lib.FoldRow) == 72 and size(1) == 0
@@ -310,11 +282,7 @@ def test_fold_entry_refuses_bad_rows_before_any_launch():
 
 
 def test_fold_kernel_uses_no_scratch_and_no_lds():
-    src = os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc", "fold.hip")
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
-           "--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600).stderr
-    blocks = [b for b in re.split(r"remark: [^\n]*Function Name: ", out)[1:] if "fold_rows_kernel" in b.split()[0]]
-    assert len(blocks) == 1
-    assert int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", blocks[0]).group(1)) == 0
-    assert int(re.search(r"LDS Size \[bytes/block\]: (\d+)", blocks[0]).group(1)) == 0
+    rows = [r for name, r in kernel_resources("fold.hip").items() if "fold_rows_kernel" in name]
+    assert len(rows) == 1
+    assert rows[0].scratch == 0
+    assert rows[0].lds == 0
