@@ -89,6 +89,9 @@ def parse_args(argv=None):
     ap.add_argument("--extra_aug", default="", help="comma list of photo, expand, crop: ExtraAugmentation with the reference's settings for each")
     ap.add_argument("--decode", choices=["host", "device"], default="host",
                     help="where the frames' JPEG files are decoded, for training batches and validation: PIL on the host, or the MI355X (stmask_amd.jpeg)")
+    ap.add_argument("--decode-split", dest="decode_split", choices=["auto", "all"], default=None,
+                    help="with --decode device: decode a file without restart markers at many places at once (stmask_amd.jpeg split=): every such "
+                         "file, or those of jpeg.SPLIT_MIN_BYTES or more; default: one wavefront a file")
     ap.add_argument("--log", default=None, help="a file of one JSON line per iteration (appended to when resuming)")
     ap.add_argument("--valid_ann", default=None, help="annotation file of the validation split (with or without annotations)")
     ap.add_argument("--valid_img_prefix", default=None, help="folder of the validation split's frames")
@@ -175,7 +178,8 @@ def main(argv=None):
     opt = make_optimizer(args, net.parameters(), lr, rank)
     trainer = DataParallelTrainer(net_loss, opt) if world > 1 else None      # weights from rank 0, verified equal
     extra_aug = config_from_names(args.extra_aug, MEANS)
-    loader = make_loader(args, datasets.YTVISTrainSet(args.ann, args.img_prefix, extra_aug=extra_aug, decode=args.decode), dev, rank)
+    loader = make_loader(args, datasets.YTVISTrainSet(args.ann, args.img_prefix, extra_aug=extra_aug, decode=args.decode,
+                                                      decode_split=args.decode_split), dev, rank)
     if len(loader) == 0:
         raise SystemExit(f"{len(loader.dataset)} frame pairs do not fill one batch of {args.batch_size}")
     say(f"{len(loader.dataset)} frame pairs, {len(loader)} iterations per epoch, {math.ceil(max_iter / len(loader))} epochs" +
@@ -238,7 +242,7 @@ def main(argv=None):
     twin = valid_set = None
     validating = bool(args.valid_ann and args.validation_interval > 0)
     if validating and chief:
-        valid_set = datasets.YTVISValSet(args.valid_ann, args.valid_img_prefix, read_ahead=8, decode=args.decode)
+        valid_set = datasets.YTVISValSet(args.valid_ann, args.valid_img_prefix, read_ahead=8, decode=args.decode, decode_split=args.decode_split)
         twin = validate.InferenceTwin(net, planes=args.eval_planes)
 
     def validate_at(path):

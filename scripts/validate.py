@@ -22,6 +22,9 @@ def parse_args(argv=None):
     ap.add_argument("--planes", choices=["fp16x2", "bf16x3", "fp16x1"], default="fp16x2", help="plane format of the inference graph")
     ap.add_argument("--decode", choices=["host", "device"], default="host",
                     help="where the frames' JPEG files are decoded: PIL on the host, or the MI355X (stmask_amd.jpeg)")
+    ap.add_argument("--decode-split", dest="decode_split", choices=["auto", "all"], default=None,
+                    help="with --decode device: decode a file without restart markers at many places at once (stmask_amd.jpeg split=): every such "
+                         "file, or those of jpeg.SPLIT_MIN_BYTES or more; default: one wavefront a file")
     ap.add_argument("--out", default=None, help="the results JSON (default: CKPT with .pth replaced by .json); the mAP file lies beside it")
     return ap.parse_args(argv)
 
@@ -37,7 +40,7 @@ def main():
     out_json, metrics_file = validate.result_paths(args.ckpt)
     if args.out:
         out_json, metrics_file = args.out, os.path.splitext(args.out)[0] + ".txt"
-    dataset = datasets.YTVISValSet(args.ann, args.img_prefix, read_ahead=8, decode=args.decode)
+    dataset = datasets.YTVISValSet(args.ann, args.img_prefix, read_ahead=8, decode=args.decode, decode_split=args.decode_split)
     scored = dataset.has_annotations
     twin = validate.InferenceTwin(net, planes=args.planes)
     metrics = validate.validation(twin, dataset, out_json, ann_file=args.ann if scored else None, metrics_file=metrics_file if scored else None,

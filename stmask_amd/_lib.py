@@ -254,6 +254,11 @@ JPEG_LOOK_BITS = 9                                                          # cs
 JPEG_DECODE, JPEG_RAW = 0, 1                                                # csrc/jpeg.h STM_JPEG_DECODE / _RAW
 JPEG_ENOCODE, JPEG_EINDEX, JPEG_ESIZE, JPEG_ETRUNCATED = 1, 2, 3, 4         # csrc/jpeg.h STM_JPEG_E*
 JPEG_STAGE_ENTROPY, JPEG_STAGE_IDCT, JPEG_STAGE_COLOUR = 1, 2, 4            # csrc/jpeg.h STM_JPEG_STAGE_*
+JPEG_REDONE = 1 << 8                                                        # csrc/jpeg.h STM_JPEG_REDONE
+JPEG_SUB_BYTES, JPEG_SUB_GROUP = 128, 64                                    # csrc/jpeg.h STM_JPEG_SUB_BYTES / _SUB_GROUP
+JPEG_SPLIT_ROUNDS = 2                                                       # csrc/jpeg.h STM_JPEG_SPLIT_ROUNDS
+JPEG_SPLIT_LAUNCHES = JPEG_SPLIT_ROUNDS + 4                                 # csrc/jpeg.h STM_JPEG_SPLIT_LAUNCHES
+JPEG_SPLIT_MAX_BYTES = 1 << 30                                              # csrc/jpeg.h STM_JPEG_SPLIT_MAX_BYTES
 # The private counterpart of HEADERS: every package-private header of csrc/ and the table that restates it, in the order they were added.
 # private_fn() / private_call(), __graft_entry__.build() and tests/test_abi_private.py walk this mapping.  A new header takes its table, an entry
 # here and a row in EXPECTED of tests/test_abi_private.py; structs that cross the boundary also take their mirrors in PRIVATE_STRUCTS below.
@@ -346,7 +351,7 @@ class JpegImage(ctypes.Structure):
     """stm_jpeg_image of csrc/jpeg.h (package-private: PRIVATE_STRUCTS, not STRUCTS)."""
     _fields_ = ([("out_off", c_l), ("src_off", c_l)] + [(n, ctypes.c_int32) for n in ("kind", "width", "height", "ncomp", "hs", "vs", "mcu_w", "mcu_h")] +
                 [("tq", ctypes.c_int32 * 3), ("td", ctypes.c_int32 * 3), ("ta", ctypes.c_int32 * 3)] +
-                [(n, ctypes.c_int32) for n in ("blk_first", "quad_first", "reserved")])
+                [(n, ctypes.c_int32) for n in ("blk_first", "quad_first", "split")])
 
 
 class JpegSegment(ctypes.Structure):

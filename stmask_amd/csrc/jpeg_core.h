@@ -176,6 +176,16 @@ JPEG_HD int jpeg_image_blocks(const stm_jpeg_image& im)
 }
 JPEG_HD int jpeg_image_quads(const stm_jpeg_image& im) { return (im.width * im.height + 3) >> 2; }
 
+/* A split image (csrc/jpeg.h, stm_jpeg_image.split): the sub-sequences and groups of a segment of nbytes, and whether the sub-sequences' records
+ * (32 bytes each) fit in the plane region of an image of `blocks` blocks (64 bytes each). */
+JPEG_HD int jpeg_blocks_per_mcu(const stm_jpeg_image& im) { return im.hs * im.vs + (im.ncomp - 1); }
+JPEG_HD int jpeg_split_subs(int nbytes) { return nbytes / STM_JPEG_SUB_BYTES + (nbytes % STM_JPEG_SUB_BYTES != 0); }
+JPEG_HD int jpeg_split_groups(int nbytes) { return (jpeg_split_subs(nbytes) + STM_JPEG_SUB_GROUP - 1) / STM_JPEG_SUB_GROUP; }
+JPEG_HD bool jpeg_split_fits(int nbytes, int blocks)
+{
+    return nbytes > STM_JPEG_SUB_BYTES && nbytes <= STM_JPEG_SPLIT_MAX_BYTES && (int64_t)jpeg_split_subs(nbytes) * 32 <= (int64_t)blocks * 64;
+}
+
 /* ---- launch 2: dequantised coefficients -> samples ---------------------------------------------------------------------------------------- */
 
 /* One 8-point pass of jidctint.c (jpeg_idct_islow) over dequantised values; shift = 11 for the column pass, 18 for the row pass. */
@@ -311,11 +321,12 @@ inline const char* jpeg_image_reason(const stm_jpeg_image& im)
 
 /* The whole batch: every image, the numbering of blocks and 4-pixel groups, where frames and sources lie, and the segments, which must tile each
  * image's MCUs in order.  -> STM_OK, STM_EINVAL or STM_EUNSUPPORTED; *why (a string constant) and *which (the image or segment) say what.
- * total_blocks: the batch's 8x8 blocks (the workspace holds 192 bytes for each), total_quads: its 4-pixel groups. */
+ * total_blocks: the batch's 8x8 blocks (the workspace holds 192 bytes for each), total_quads: its 4-pixel groups.  (The batch's sub-sequence
+ * groups: jpeg_total_groups(), once this has passed.) */
 inline int jpeg_check_batch(const stm_jpeg_image* images, int n_images, const stm_jpeg_segment* segments, int n_segments, size_t blob_bytes,
                             size_t out_bytes, int64_t* total_blocks, int64_t* total_quads, const char** why, int* which)
 {
-    int64_t blocks = 0, quads = 0;
+    int64_t blocks = 0, quads = 0, groups = 0;
     int seg = 0;
     *why = "";
     *which = 0;
@@ -333,6 +344,7 @@ inline int jpeg_check_batch(const stm_jpeg_image* images, int n_images, const st
         quads += q;
         if (blocks >= ((int64_t)1 << 31) || quads >= ((int64_t)1 << 31)) { *why = "2^31 blocks or 4-pixel groups in one batch"; return STM_EUNSUPPORTED; }
         /* the image's segments: next in the list, MCUs in order, none empty */
+        const int seg_begin = seg;
         int64_t mcu = 0;
         const int64_t mcus = im.kind == STM_JPEG_DECODE ? (int64_t)im.mcu_w * im.mcu_h : 0;
         while (mcu < mcus) {
@@ -346,9 +358,26 @@ inline int jpeg_check_batch(const stm_jpeg_image* images, int n_images, const st
             mcu += s.mcu_count;
             ++seg;
         }
+        /* the split field: the groups before this image, and whether it has any itself */
+        if (im.split < 0 || (im.split >> 1) != groups) { *why = "a split field that does not continue the groups of the images before"; return STM_EINVAL; }
+        if (im.split & 1) {
+            if (im.kind != STM_JPEG_DECODE || seg - seg_begin != 1) { *why = "a split field and other than one segment"; return STM_EINVAL; }
+            if (!jpeg_split_fits(segments[seg_begin].nbytes, jpeg_image_blocks(im))) { *why = "a split field and a segment whose records do not fit"; return STM_EINVAL; }
+            groups += jpeg_split_groups(segments[seg_begin].nbytes);
+            if (groups >= ((int64_t)1 << 30)) { *why = "2^30 sub-sequence groups in one batch"; return STM_EUNSUPPORTED; }
+        }
     }
     if (seg != n_segments) { *which = seg; *why = "segments beyond the images'"; return STM_EINVAL; }
     *total_blocks = blocks;
     *total_quads = quads;
     return STM_OK;
+}
+
+/* the sub-sequence groups of a batch that jpeg_check_batch has passed: the last image's first group and, if it is split, those of its one
+ * segment, which is the last of the list */
+inline int64_t jpeg_total_groups(const stm_jpeg_image* images, int n_images, const stm_jpeg_segment* segments, int n_segments)
+{
+    if (n_images <= 0) return 0;
+    const stm_jpeg_image& im = images[n_images - 1];
+    return (im.split >> 1) + ((im.split & 1) && n_segments > 0 ? jpeg_split_groups(segments[n_segments - 1].nbytes) : 0);
 }

@@ -10,7 +10,9 @@
 //                         order) of the current block in a register -- it takes the value when the symbol of its zig-zag position is decoded --
 //                         so a finished block leaves as one 128-byte store, 2 bytes a lane, and never passes through LDS or scratch.
 //                         A malformed segment sets its status word and writes zero blocks from there on.  Parallel decoding INSIDE one segment
-//                         (self-synchronising sub-sequences) is not built.
+//                         (self-synchronising sub-sequences) is csrc/jpeg_split.hip, for the images marked split; its launches come first,
+//                         and for the segment of such an image this kernel returns at once unless they marked it REDO (record 0 of the
+//                         image's plane region), in which case it decodes the segment as any other and says so in the status word.
 //   jpeg_idct_kernel      8 lanes per 8x8 block.  Lane j loads row j of the coefficients (16 bytes) and of the quantisation table, multiplies and
 //                         parks the row in LDS; then it runs the column pass over column j in place, the row pass over row j, and stores the 8
 //                         samples of row j as 8 bytes.  int32 throughout.
@@ -21,7 +23,11 @@
 // No atomics; every result is written with vector stores.  The image of a block or pixel group is found by binary search over the descriptors'
 // blk_first / quad_first in device memory.
 #include "stm_common.h"
-#include "jpeg_core.h"
+#include "jpeg_split_core.h"
+
+// csrc/jpeg_split.hip: the launches in front of jpeg_entropy_kernel for a batch with split images
+int jpeg_split_launch(const uint8_t* blob, const stm_jpeg_image* d_images, int n_images, const stm_jpeg_segment* d_segments, int n_segments,
+                      int total_groups, uint8_t* planes, int16_t* coef, hipStream_t stream);
 
 namespace {
 
@@ -104,7 +110,8 @@ struct LaneSink {
 
 __global__ __launch_bounds__(STM_WAVE) void jpeg_entropy_kernel(const uint8_t* __restrict__ blob, const stm_jpeg_image* __restrict__ images,
                                                                 const stm_jpeg_segment* __restrict__ segments, int n_segments,
-                                                                int16_t* __restrict__ coef, int* __restrict__ status)
+                                                                int16_t* __restrict__ coef, int* __restrict__ status,
+                                                                const uint8_t* __restrict__ split_planes)     // null: no image of the batch is split
 {
     __shared__ __attribute__((aligned(16))) HuffRest s_rest[4];
     __shared__ __attribute__((aligned(16))) uint8_t s_win[JPEG_STAGE];
@@ -113,6 +120,14 @@ __global__ __launch_bounds__(STM_WAVE) void jpeg_entropy_kernel(const uint8_t* _
     const int lane = threadIdx.x;
     const stm_jpeg_segment sg = segments[s];
     const stm_jpeg_image im = images[sg.image];
+    int redone = 0;
+    if (split_planes && (im.split & 1)) {
+        if (!reinterpret_cast<const JpegSplitRec*>(split_planes + 64 * (int64_t)im.blk_first)->redo) {
+            if (lane == 0) status[s] = 0;
+            return;
+        }
+        redone = STM_JPEG_REDONE;
+    }
     const stm_jpeg_huff* global = reinterpret_cast<const stm_jpeg_huff*>(blob + im.src_off + offsetof(stm_jpeg_tables, huff));
     {
         constexpr int PER = (int)sizeof(HuffRest) / 16;                        // 16-byte pieces of one table's canonical part
@@ -160,7 +175,7 @@ __global__ __launch_bounds__(STM_WAVE) void jpeg_entropy_kernel(const uint8_t* _
             ++my;
         }
     }
-    if (lane == 0) status[s] = err;
+    if (lane == 0) status[s] = err | redone;
 }
 
 // the image of batch-wide index g: the last one whose first index (a field of the descriptor) is <= g.  Images without blocks share their first
@@ -329,8 +344,13 @@ extern "C" int stm_jpeg_decode_u8(const stm_jpeg_image* images, int n_images, co
     int16_t* coef = static_cast<int16_t*>(workspace);
     uint8_t* planes = static_cast<uint8_t*>(workspace) + 128 * total_blocks;
     if ((stages & STM_JPEG_STAGE_ENTROPY) && n_segments) {
+        const int total_groups = (int)jpeg_total_groups(images, n_images, segments, n_segments);
+        if (total_groups) {
+            const int rs = jpeg_split_launch(b8, d_images, n_images, d_segments, n_segments, total_groups, planes, coef, stm_hs(stream));
+            if (rs != STM_OK) return rs;
+        }
         hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)n_segments), dim3(STM_WAVE), 0, stm_hs(stream), b8, d_images, d_segments, n_segments, coef,
-                           status);
+                           status, total_groups ? planes : nullptr);
         STM_CHECK_LAUNCH("jpeg_entropy_kernel");
     }
     if ((stages & STM_JPEG_STAGE_IDCT) && total_blocks) {

@@ -391,14 +391,17 @@ class YTVISTrainSet:
     then frame 1's, THEN the clip's one flip (datasets/ytvos.py:243-248); the record gains aug = [AugParams, AugParams] and its bboxes / labels /
     obj_ids / segms are what the augmentation left.  The pixels are augmented on the device by collate_device.
     decode: "host" (frame_reader returns pixels; read_frame by default) or "device": frame_reader returns jpeg.CompressedFrames
-    (jpeg.read_compressed by default), `frames` holds them, the sizes come from their headers and collate_device has the device decode them; every
+    (jpeg.read_compressed by default), `frames` holds them, the sizes come from their headers and collate_device has the device decode them
+    (decode_split: jpeg.decode_batch's split, None | "auto" | "all", which the records carry to collate_device); every
     other field of the record and every random draw is that of "host"."""
 
     def __init__(self, ann, img_prefix=None, frame_reader=None, img_scale=(640, 360), size_divisor=32, flip_ratio=0.5, clip_frames=1, to_rgb=True,
-                 mean=MEANS, std=STD, extra_aug=None, crop_boxes="reference", cast="reference", decode="host"):
+                 mean=MEANS, std=STD, extra_aug=None, crop_boxes="reference", cast="reference", decode="host", decode_split=None):
         if decode not in ("host", "device"):
             raise ValueError(f"YTVISTrainSet: decode={decode!r}")
-        self.decode = decode
+        if decode_split not in (None, "auto", "all") or (decode_split is not None and decode != "device"):
+            raise ValueError(f"YTVISTrainSet: decode_split={decode_split!r} with decode={decode!r}")
+        self.decode, self.decode_split = decode, decode_split
         if frame_reader is None and decode == "device":
             frame_reader = _jpeg.read_compressed
         data = vis_eval._load(ann)
@@ -483,10 +486,12 @@ class YTVISTrainSet:
                    mean=self.mean, std=self.std)
         if aug is not None:
             rec["aug"] = aug
+        if self.decode_split is not None:
+            rec["decode_split"] = self.decode_split
         return rec
 
 
-def collate_device(records, device=None, max_gt=None, check="raise"):
+def collate_device(records, device=None, max_gt=None, check="raise", decode_split=None):
     """Records of YTVISTrainSet -> (images [bs, 2, 3, Hp, Wp] fp32, gt_bboxes, gt_labels, gt_masks, gt_ids, img_meta) on the device, ready for
     train.train_step, in the nesting synthetic.synthetic_train_batch documents: the four ground-truth entries are lists over the clips of
     [frame 0, frame 1] tensors (boxes [G, 4] fp32 relative to the padded image, labels int64 [G], masks uint8 [G, Hp, Wp], ids int64 [G]), each a
@@ -495,7 +500,8 @@ def collate_device(records, device=None, max_gt=None, check="raise"):
     compressed string.  Records that carry aug (YTVISTrainSet(extra_aug=...)) are augmented inside those same launches: one more upload (the
     descriptors), no more launches; records with and without aug may not be mixed.  Records of YTVISTrainSet(decode="device") carry
     jpeg.CompressedFrames: jpeg.decode_batch (one upload, at most three launches) takes the place of the frames' upload, its status joins the
-    batch's, and nothing else changes; compressed and decoded frames may not be mixed.  A flagged mask raises ValueError naming the video id, annotation id and frame: check="raise" waits for the status words
+    batch's, and nothing else changes (decode_split, or else what the first record carries from YTVISTrainSet(decode_split=...), is its
+    `split`); compressed and decoded frames may not be mixed.  A flagged mask raises ValueError naming the video id, annotation id and frame: check="raise" waits for the status words
     here; check="deferred" appends a BatchStatus to the tuple whose .raise_if_bad() the caller invokes a step later, so the call itself never
     waits for the device."""
     if check not in ("raise", "deferred"):
@@ -541,7 +547,8 @@ def collate_device(records, device=None, max_gt=None, check="raise"):
         if compressed:
             f_names = ["video %s, frame %s%s" % (r["video_id"], r["frame_ids"][t], f" ({f.name})" if f.name else "")
                        for r in records for t, f in enumerate(r["frames"])]
-            dev_frames, decode_status = _jpeg.decode_batch(frames, device, order="bgr", names=f_names, check="deferred")
+            dev_frames, decode_status = _jpeg.decode_batch(frames, device, order="bgr", names=f_names, check="deferred",
+                                                           split=decode_split if decode_split is not None else r0.get("decode_split"))
         else:
             dev_frames = upload_frames(frames, device)
         block = upload_aug(dev_frames, f_flips, params, frame_of, device) if augmented else None
@@ -701,13 +708,16 @@ class YTVISValSet:
     the list of (video_id, LazyVideo) serve.VideoBatcher.run takes: no frame is read before the batcher asks for it, and a video holds at most
     keep + read_ahead frames.  read_ahead=k > 0: a thread pool of min(8, k) threads reads up to k frames ahead in each video's own order.
     decode="device": the frames stay jpeg.CompressedFrames (frame_reader: jpeg.read_compressed by default) and the batcher takes
-    prep=jpeg.compressed_prep(...); read_ahead then reads file bytes ahead, not pixels.
+    prep=jpeg.compressed_prep(...); read_ahead then reads file bytes ahead, not pixels.  decode_split (None | "auto" | "all") is kept for whoever
+    makes that prep (validate.validation does): jpeg.compressed_prep(split=dataset.decode_split).
     Not restated: several img_scales, test-time flip (commented out in the reference), proposals, clip_eval_mode."""
 
-    def __init__(self, ann, img_prefix=None, frame_reader=None, read_ahead=0, decode="host"):
+    def __init__(self, ann, img_prefix=None, frame_reader=None, read_ahead=0, decode="host", decode_split=None):
         if decode not in ("host", "device"):
             raise ValueError(f"YTVISValSet: decode={decode!r}")
-        self.decode = decode
+        if decode_split not in (None, "auto", "all") or (decode_split is not None and decode != "device"):
+            raise ValueError(f"YTVISValSet: decode_split={decode_split!r} with decode={decode!r}")
+        self.decode, self.decode_split = decode, decode_split
         data = vis_eval._load(ann)
         self.img_prefix, self.read_ahead = img_prefix, int(read_ahead)
         self.frame_reader = frame_reader or (_jpeg.read_compressed if decode == "device" else read_frame)

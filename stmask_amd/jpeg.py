@@ -8,8 +8,13 @@ On the device: 8-bit baseline sequential DCT (SOF0), Huffman coding, one interle
 tables, optional restart intervals, 1 component or 3 (YCbCr) with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1, width and height 1..8192.
 Everything else -- progressive, arithmetic, 12-bit, multi-scan, 4 components, other sampling factors, an Adobe marker with a non-YCbCr
 transform, DNL, a file that is no JPEG -- is `Unsupported`: decode_batch decodes such a file on the host with PIL, its pixels ride in the same
-copy, and COUNTERS["host_fallback"] counts it.  A file whose markers contradict themselves is `Malformed` (a ValueError).  Not built: decoding
-several places of one segment at once, PNG, EXIF orientation (PIL ignores it too), encoding.
+copy, and COUNTERS["host_fallback"] counts it.  A file whose markers contradict themselves is `Malformed` (a ValueError).  Not built: PNG, EXIF
+orientation (PIL ignores it too), encoding.
+
+A file without restart markers is one segment and, by default, one wavefront's serial work.  split="all" | "auto" (pack_batch, decode_batch,
+launch_batch's batch, compressed_prep) decodes such a segment at many places at once instead (csrc/jpeg_split.hip: self-synchronising
+sub-sequences of JPEG_SUB_BYTES bytes, SPLIT_LAUNCHES launches in place of the first one); a segment that does not converge, or is damaged, is
+decoded by the serial kernel after all, with the serial path's pixels and status word plus the bit _lib.JPEG_REDONE (DecodeStatus.redone()).
 
 The library's default stays the host decoder (datasets.read_frame); this path is chosen with decode="device".
 """
@@ -24,6 +29,12 @@ from ._lib import StmError, c_p, private_call
 
 # launches of stm_jpeg_decode_u8's kernels, host -> device copies and their bytes, and files decoded on the host since the last reset_counters()
 COUNTERS = {"launches": 0, "uploads": 0, "h2d_bytes": 0, "host_fallback": 0}
+# images that were split since the last reset_counters(), and the segments of such images a caller of DecodeStatus.redone() has seen redone
+SPLIT_COUNTERS = {"images": 0, "redone": 0}
+SPLIT_LAUNCHES = _lib.JPEG_SPLIT_LAUNCHES      # what the entropy launch becomes for a batch with a split image: sync rounds 0..R, scan, write, serial
+# split="auto" splits a segment of at least this many bytes: one group's.  Measured (profiles/bench_jpeg_split.txt, part 6: one noise file alone,
+# the slowest content to synchronise): the split launches lose to the serial kernel at 3.7 KB and win from 8.3 KB on.
+SPLIT_MIN_BYTES = _lib.JPEG_SUB_BYTES * _lib.JPEG_SUB_GROUP
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56,
                    57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
@@ -35,6 +46,8 @@ _GUARD = 16        # zero bytes behind every segment in the blob
 def reset_counters():
     for k in COUNTERS:
         COUNTERS[k] = 0
+    for k in SPLIT_COUNTERS:
+        SPLIT_COUNTERS[k] = 0
 
 
 class Unsupported(ValueError):
@@ -292,8 +305,9 @@ class Batch:
     blob_bytes bytes: the image descriptors, the segment descriptors, the table sets (one per distinct set), the segments, the raw pixels."""
 
     def __init__(self, images, segments, n_images, n_segments, images_off, segments_off, blob_bytes, out_bytes, pieces, shapes, seg_image, fallbacks,
-                 names):
+                 names, split_images=(), total_groups=0):
         self.names = names                 # one per file: what a message about it says
+        self.split_images, self.total_groups = list(split_images), total_groups     # the files decoded at many places at once; their groups
         self.images, self.segments, self.n_images, self.n_segments = images, segments, n_images, n_segments
         self.images_off, self.segments_off, self.blob_bytes, self.out_bytes = images_off, segments_off, blob_bytes, out_bytes
         self.pieces, self.shapes, self.seg_image, self.fallbacks = pieces, shapes, seg_image, fallbacks
@@ -318,11 +332,22 @@ def _blocks(im):
     return im.mcu_w * im.mcu_h * (im.hs * im.vs + im.ncomp - 1) if im.kind == _lib.JPEG_DECODE else 0
 
 
-def pack_batch(datas, order="bgr", names=None):
+def split_fits(nbytes, blocks):
+    """csrc/jpeg_core.h jpeg_split_fits: a segment of nbytes has two sub-sequences or more, and their records (32 bytes each) fit in the plane
+    region of an image of `blocks` blocks (64 bytes each)."""
+    subs = -(-nbytes // _lib.JPEG_SUB_BYTES)
+    return _lib.JPEG_SUB_BYTES < nbytes <= _lib.JPEG_SPLIT_MAX_BYTES and 32 * subs <= 64 * blocks
+
+
+def pack_batch(datas, order="bgr", names=None, split=None):
     """Parse every file and lay the batch out (no device work): -> Batch.  A file parse() refuses as Unsupported is decoded here with PIL and
-    rides as pixels; Malformed raises ValueError naming the file.  datas: bytes objects or CompressedFrames."""
+    rides as pixels; Malformed raises ValueError naming the file.  datas: bytes objects or CompressedFrames.  split: None -- every segment is one
+    wavefront's work; "all" -- every image of one segment whose sub-sequence records fit (split_fits) is split; "auto" -- those of them whose
+    segment has SPLIT_MIN_BYTES or more."""
     if order not in ("bgr", "rgb"):
         raise ValueError(f"jpeg: order={order!r}")
+    if split not in (None, "auto", "all"):
+        raise ValueError(f"jpeg: split={split!r}")
     n = len(datas)
     names = list(names) if names is not None else [getattr(x, "name", None) or f"frame {i}" for i, x in enumerate(datas)]
     if len(names) != n:
@@ -348,6 +373,7 @@ def pack_batch(datas, order="bgr", names=None):
     cur = _pad16(segments_off + n_seg * ctypes.sizeof(_lib.JpegSegment))
     pieces, table_at, shapes, seg_image = [], {}, [], []
     out, blk, quad, k, fallbacks = 0, 0, 0, 0, 0
+    grp, split_images = 0, []
     for h, _ in headers:                       # the table sets first, so that they share cache lines
         if h is not None and h.tables not in table_at:
             table_at[h.tables] = cur
@@ -381,15 +407,23 @@ def pack_batch(datas, order="bgr", names=None):
                 k += 1
             shape = h.shape
         im.out_off, im.blk_first, im.quad_first = out, blk, quad
+        if split is not None:
+            nb = int(h.segments[0][1] - h.segments[0][0]) if h is not None and len(h.segments) == 1 else 0
+            if split_fits(nb, _blocks(im)) and (split == "all" or nb >= SPLIT_MIN_BYTES):
+                im.split = 2 * grp + 1
+                split_images.append(i)
+                grp += -(-(-(-nb // _lib.JPEG_SUB_BYTES)) // _lib.JPEG_SUB_GROUP)
+            else:
+                im.split = 2 * grp                # (0 while nothing is split: the descriptors of such a batch are what they were)
         q = (shape[0] * shape[1] + 3) // 4
         out += _pad16(12 * q)
         blk += _blocks(im)
         quad += q
         shapes.append(tuple(int(v) for v in shape))
-    if blk >= 2 ** 31 or quad >= 2 ** 31:
-        raise StmError("jpeg: 2^31 blocks or 4-pixel groups in one batch")
+    if blk >= 2 ** 31 or quad >= 2 ** 31 or grp >= 2 ** 30:
+        raise StmError("jpeg: 2^31 blocks or 4-pixel groups, or 2^30 sub-sequence groups, in one batch")
     return Batch(images, segments, n, n_seg, images_off, segments_off, _pad16(cur), out, pieces, shapes, np.asarray(seg_image, dtype=np.int64), fallbacks,
-                 names)
+                 names, split_images, grp)
 
 
 class DecodeStatus:
@@ -410,17 +444,24 @@ class DecodeStatus:
         if self.host is None:
             return {}
         self.event.synchronize()
-        st = self.host.numpy()
+        st = self.host.numpy() & ~_lib.JPEG_REDONE
         out = {}
         for s in np.flatnonzero(st):
             out.setdefault(int(self.seg_image[s]), int(st[s]))
         return out
 
+    def redone(self):
+        """The indices of the split files whose segment the serial kernel decoded after all (damaged, or not converged); waits for the event."""
+        if self.host is None:
+            return set()
+        self.event.synchronize()
+        return {int(self.seg_image[s]) for s in np.flatnonzero(self.host.numpy() & _lib.JPEG_REDONE)}
+
     def raise_if_bad(self):
         bad = self.flagged()
         if bad:
             i = min(bad)
-            raise ValueError(f"{self.names[i]}: the JPEG data is damaged ({STATUS_TEXT.get(bad[i], bad[i])})")
+            raise ValueError(f"{self.names[i]}: the JPEG data is damaged ({STATUS_TEXT.get(bad[i] & ~_lib.JPEG_REDONE, bad[i])})")
 
 
 def _device(device):
@@ -435,10 +476,12 @@ def _device(device):
 
 
 def launch_batch(batch, blob, out, status, workspace, order="bgr", stages=7):
-    """The device part of decode_batch over an uploaded blob: at most three launches, nothing copied, nothing read.  (A function of its own so
-    that scripts/bench_jpeg_decode.py can time the launches alone and one at a time.)"""
+    """The device part of decode_batch over an uploaded blob: at most three launches (SPLIT_LAUNCHES - 1 more when pack_batch split an image),
+    nothing copied, nothing read.  (A function of its own so that scripts/bench_jpeg_decode.py can time the launches alone and one at a time.)"""
     launches = ((1 if stages & 1 and batch.n_segments else 0) + (1 if stages & 2 and batch.total_blocks else 0) +
-                (1 if stages & 4 and batch.n_images else 0))
+                (1 if stages & 4 and batch.n_images else 0) + (SPLIT_LAUNCHES - 1 if stages & 1 and batch.split_images else 0))
+    if stages & 1:
+        SPLIT_COUNTERS["images"] += len(batch.split_images)
     COUNTERS["launches"] += launches
     p = lambda t: c_p(t.data_ptr()) if t is not None and t.numel() else c_p(0)     # noqa: E731
     with torch.cuda.device(blob.device):
@@ -447,14 +490,15 @@ def launch_batch(batch, blob, out, status, workspace, order="bgr", stages=7):
                      c_p(torch.cuda.current_stream().cuda_stream))
 
 
-def decode_batch(datas, device=None, order="bgr", names=None, check="raise"):
+def decode_batch(datas, device=None, order="bgr", names=None, check="raise", split=None):
     """JPEG files (bytes or CompressedFrames) -> their frames as uint8 [H_i, W_i, 3] device views of ONE buffer, channels in `order`.  One pinned
     staging blob, one host -> device copy, at most three launches, whatever the batch's size and mix of sizes.  A damaged file raises ValueError
-    naming it: check="raise" waits for the status words here; check="deferred" returns (frames, DecodeStatus) and never waits for the device."""
+    naming it: check="raise" waits for the status words here; check="deferred" returns (frames, DecodeStatus) and never waits for the device.
+    split: pack_batch's; a batch with a split image takes SPLIT_LAUNCHES + 2 launches, whatever its size."""
     if check not in ("raise", "deferred"):
         raise ValueError(f"decode_batch: check={check!r}")
     device = _device(device)
-    batch = pack_batch(datas, order, names)
+    batch = pack_batch(datas, order, names, split)
     names = batch.names
     COUNTERS["host_fallback"] += batch.fallbacks
     if batch.n_images == 0:
@@ -481,10 +525,10 @@ def decode_batch(datas, device=None, order="bgr", names=None, check="raise"):
     return frames
 
 
-def compressed_prep(size=(640, 360), channels_last=True):
+def compressed_prep(size=(640, 360), channels_last=True, split=None):
     """A `prep` for serve.VideoBatcher over videos whose frames are CompressedFrames (datasets.YTVISValSet(decode="device")): the busy slots'
-    frames of a step are decoded in ONE decode_batch and handed to serve.device_prep as device frames.  A damaged file raises at the step that
-    decodes it (check="raise")."""
+    frames of a step are decoded in ONE decode_batch (split: its argument) and handed to serve.device_prep as device frames.  A damaged
+    file raises at the step that decodes it (check="raise")."""
     from . import serve
 
     def prep(frames, frame_ids):
@@ -492,7 +536,7 @@ def compressed_prep(size=(640, 360), channels_last=True):
         if busy:
             if not all(isinstance(frames[i], CompressedFrame) for i in busy):
                 raise StmError("jpeg.compressed_prep: the videos' frames must be CompressedFrames (YTVISValSet(decode=\"device\"))")
-            decoded = decode_batch([frames[i] for i in busy], order="bgr")
+            decoded = decode_batch([frames[i] for i in busy], order="bgr", split=split)
             frames = list(frames)
             for i, f in zip(busy, decoded):
                 frames[i] = f

@@ -253,13 +253,14 @@ def fold_rows(rows, stream=None):
     return calls
 
 
-def validation(twin, dataset, out_json, ann_file=None, metrics_file=None, n_slots=8, scorer=None, batcher=None, decode="host"):
+def validation(twin, dataset, out_json, ann_file=None, metrics_file=None, n_slots=8, scorer=None, batcher=None, decode="host", decode_split=None):
     """The round trip: twin.refresh(); the split through a VideoBatcher on the twin into out_json (results2json_videoseg's file, rows under
     cfg.eval_conf_thresh dropped as in the reference's validation); with ann_file, (scorer or eval_utils.calc_metrics)(ann_file, out_json,
     output_file=metrics_file) -- the two branches of eval.py:566-573.  -> the metrics, or None when nothing was scored.  batcher (anything with
     run(videos, out_file=...)) and scorer are injectable.  Nothing of the live net, the optimizer or the random generators changes.
     decode="device": the dataset is a YTVISValSet(decode="device"), whose frames are still JPEG bytes, and the batcher made here decodes them on
-    the device (prep=jpeg.compressed_prep()); a batcher handed in must bring such a prep itself."""
+    the device (prep=jpeg.compressed_prep(split=decode_split), decode_split defaulting to the dataset's); a batcher handed in must bring such a
+    prep itself."""
     if decode not in ("host", "device"):
         raise ValueError(f"validation: decode={decode!r}")
     if getattr(dataset, "decode", decode) != decode:
@@ -269,7 +270,7 @@ def validation(twin, dataset, out_json, ann_file=None, metrics_file=None, n_slot
         vb = batcher
     elif decode == "device":
         from . import jpeg
-        vb = twin.batcher(n_slots, prep=jpeg.compressed_prep())
+        vb = twin.batcher(n_slots, prep=jpeg.compressed_prep(split=decode_split if decode_split is not None else getattr(dataset, "decode_split", None)))
     else:
         vb = twin.batcher(n_slots)
     twin.run(vb, dataset.videos(), out_file=out_json)
